@@ -4,6 +4,7 @@ bench.py — headline benchmark of BASELINE.json: ANM modes/s (Hessian build + f
 N = 2000 C-alpha, HinsenForceField without cutoff (config C3), float64, all 6000 modes.
 
     python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--structures-per-gpu B] [--n-atoms N]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--cpu-runs R]]
 
 With ``--gpus N`` (N > 1) and no RANK in the environment the script starts the N ranks itself (a child
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py ...``, started
@@ -22,7 +23,18 @@ rank every rank pins its host threads to the cores of its GPU's NUMA node before
     32 structures, the root gathers the eigenvalues.  One step = one such call (the exchange steps are inside the
     timed region); eigenvalues of every structure are checked against the oracle-independent residual on the ranks.
 
-Rank 0 prints ONE JSON line with the driver's contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the driver's contract fields
+(metric, value, unit, higher_is_better, dtype, ms_per_step = wall time of one timed step, ...) and nothing else.
+
+--dump-outputs DIR
+    After the timed steps rank 0 writes what the last timed step returned, float64, at most 64 MiB in all:
+    DIR/eigenvalues.npy (structures x modes; a seeded sample of whole structures if they would not fit into 16 MiB, their
+    indices in DIR/eigenvalues_index.npy), DIR/eigenvectors.npy (rows = modes, as returned; every vector if they fit into
+    44 MiB, else a seeded sample of whole vectors) and DIR/eigenvectors_index.npy ([structure, mode] of each row).  The
+    inputs depend only on the arguments, so two builds can be compared output for output.  (c4: the gathered
+    eigenvalues of all structures and the eigenvectors of rank 0's shard.)
+
+--full adds to the line what takes work beyond the timed steps (--no-cpu-baseline leaves out the last two):
   roofline      the kernel (group) with the longest duration in one extra profiled step right after the timed region
                 (C3: k_bt2_apply, f64-MFMA bound: algorithmic flops of the launch / its duration vs the 78.6 TFLOP/s
                 f64 matrix peak; one-stage path: k_symv_tiles, HBM bound).  Durations from HIP events on the solver's
@@ -118,6 +130,39 @@ def synthetic_coords(n_atoms, seeds):
     for k, s in enumerate(seeds):
         out[k] = np.random.RandomState(s).rand(n_atoms, 3) * box
     return out
+
+
+DUMP_W_BYTES = 16 << 20     # --dump-outputs: eigenvalues ...
+DUMP_V_BYTES = 44 << 20     # ... and eigenvectors, index files included: 60 MiB at most
+DUMP_SEED = 20240601
+
+
+def dump_outputs(path, w, v):
+    """
+    --dump-outputs: the last timed step's eigenvalues w (B, modes) and eigenvectors v (B, modes, n; rows = modes) as
+    float64 .npy files.  Whole structures / whole vectors are kept so that a comparison can fix each vector's sign; when
+    they do not fit, a sample drawn from a fixed seed (the same for the same arguments) and its indices are written.
+    """
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    w = w if torch.is_tensor(w) else torch.from_numpy(np.asarray(w))
+    B, nw = w.shape
+    if B * nw * 8 > DUMP_W_BYTES:                       # budgets count the index entries too
+        rows = np.sort(rng.choice(B, size=max(1, DUMP_W_BYTES // (nw * 8 + 8)), replace=False))
+        np.save(os.path.join(path, "eigenvalues_index.npy"), rows.astype(np.float64))
+        w = w[torch.from_numpy(rows).to(w.device)]
+    np.save(os.path.join(path, "eigenvalues.npy"), w.to(torch.float64).cpu().numpy())
+    if v is None:
+        return
+    Bv, nv, n = v.shape
+    flat = np.arange(Bv * nv)
+    if Bv * nv * (n * 8 + 16) > DUMP_V_BYTES:
+        flat = np.sort(rng.choice(Bv * nv, size=max(1, DUMP_V_BYTES // (n * 8 + 16)), replace=False))
+    rows = v.reshape(Bv * nv, n)[torch.from_numpy(flat).to(v.device)]
+    np.save(os.path.join(path, "eigenvectors.npy"), rows.to(torch.float64).cpu().numpy())
+    np.save(os.path.join(path, "eigenvectors_index.npy"), np.stack([flat // nv, flat % nv], axis=1).astype(np.float64))
 
 
 def host_threads():
@@ -559,7 +604,7 @@ def run_batch(args, rank, world, torch, dist):
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        solver.solve(coord)
+        w, v = solver.solve(coord)
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -569,6 +614,25 @@ def run_batch(args, rank, world, torch, dist):
 
     out = None
     if rank == 0:
+        if args.dump_outputs:
+            solver.finish()
+            dump_outputs(args.dump_outputs, w, v)
+        total_structures = B * world * args.steps
+        out = {
+            "metric": metric,
+            "value": round(nmodes * total_structures / elapsed, 1), "unit": "modes/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {
+                "workload": workload.format(n_atoms=n_atoms, n=n),
+                "structures_per_gpu_per_step": B,
+                "solves_per_s": round(total_structures / elapsed, 3),
+                "parallelism": "independent structures sharded over GPUs, no data-path collective",
+                "host_binding": args.host_binding,
+            },
+        }
+    if rank == 0 and args.full:
         # ---- one extra profiled step: durations of the kernel groups (HIP events, solver's stream)
         solver.set_profiling(True)
         c_before = {k: solver.ctx.counter(k) for k in CHASE_COUNTERS}
@@ -598,8 +662,6 @@ def run_batch(args, rank, world, torch, dist):
         }
         counters = {k: solver.ctx.counter(k) for k in CHASE_COUNTERS}
 
-        total_structures = B * world * args.steps
-        value = nmodes * total_structures / elapsed
         cpu = gates = None
         if not args.no_cpu_baseline:
             with host_cores():
@@ -609,21 +671,8 @@ def run_batch(args, rank, world, torch, dist):
                 else:
                     gates = parity_gates_partial(solver, coord, w.clone(), v.clone(), torch)
                     cpu = cpu_baseline_partial(n_atoms, nmodes)
-        out = {
-            "metric": metric,
-            "value": round(value, 1), "unit": "modes/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {
-                "workload": workload.format(n_atoms=n_atoms, n=n),
-                "structures_per_gpu_per_step": B,
-                "solves_per_s": round(total_structures / elapsed, 3),
-                "parallelism": "independent structures sharded over GPUs, no data-path collective",
-                "host_binding": args.host_binding,
-            },
-            "roofline": roofline, "rooflines": rooflines, "phases_ms_profiled_step": dict(t), "counters": counters,
-            "parity_gates": gates, "cpu_baseline": cpu,
-        }
+        out.update({"roofline": roofline, "rooflines": rooflines, "phases_ms_profiled_step": dict(t), "counters": counters,
+                    "parity_gates": gates, "cpu_baseline": cpu})
     return out
 
 
@@ -645,19 +694,40 @@ def run_c4(args, rank, world, torch, dist):
         dist.barrier()
         torch.cuda.synchronize()
 
-    w = None
+    w = v = None
     for _ in range(args.warmup):
         w, _ = solve_sharded(coords, ff, dim=3, want_vectors=True, solver=solver)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        w, _ = solve_sharded(coords, ff, dim=3, want_vectors=True, solver=solver)
+        w, v = solve_sharded(coords, ff, dim=3, want_vectors=True, solver=solver)
     barrier()
     elapsed = time.perf_counter() - t0
     cdev = "cuda" if dist.get_backend() == "nccl" else "cpu"
     t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    out = None
+    if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, w, v)
+        out = {
+            "metric": "ANM modes/sec, batch of independent N=1000 C-alpha solves sharded over GPUs (config C4)",
+            "value": round(3 * n_atoms * total * args.steps / elapsed, 1), "unit": "modes/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {
+                "workload": f"C4: {total} independent N={n_atoms} C-alpha ANM (InvariantForceField 13 A), all modes + vectors, "
+                            f"{per_gpu} per GPU, solve_sharded: RCCL scatter of coordinates + gather of eigenvalues inside the step",
+                "structures_per_gpu_per_step": per_gpu,
+                "solves_per_s": round(total * args.steps / elapsed, 3),
+                "parallelism": "independent structures sharded over GPUs; collectives only for scatter / gather",
+                "backend": dist.get_backend(),
+                "host_binding": args.host_binding,
+            },
+        }
+    if not args.full:
+        return out
     # every rank checks its own shard: residual + orthogonality of its first and last structure (device arithmetic);
     # the shard's coordinates are regenerated from the seeds (the scatter's own correctness is what w is checked for below)
     local = torch.from_numpy(synthetic_coords(n_atoms, list(range(lo, hi)))).cuda()
@@ -672,7 +742,6 @@ def run_c4(args, rank, world, torch, dist):
         worst[1] = max(worst[1], (vb @ vb.T - eye).abs().max())
     worst = worst.to(cdev)
     dist.all_reduce(worst, op=dist.ReduceOp.MAX)
-    out = None
     if rank == 0:
         # one extra profiled local solve of rank 0's shard: kernel-group durations -> rooflines
         solver.set_profiling(True)
@@ -706,23 +775,8 @@ def run_c4(args, rank, world, torch, dist):
                                  and gates["last_structure_eigenvalues_max_rel_diff"] <= 1e-5
                                  and gates["residual_max_over_norm_all_ranks"] <= 1e-5
                                  and gates["orthogonality_max_all_ranks"] <= 1e-8)
-        out = {
-            "metric": "ANM modes/sec, batch of independent N=1000 C-alpha solves sharded over GPUs (config C4)",
-            "value": round(3 * n_atoms * total * args.steps / elapsed, 1), "unit": "modes/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {
-                "workload": f"C4: {total} independent N={n_atoms} C-alpha ANM (InvariantForceField 13 A), all modes + vectors, "
-                            f"{per_gpu} per GPU, solve_sharded: RCCL scatter of coordinates + gather of eigenvalues inside the step",
-                "structures_per_gpu_per_step": per_gpu,
-                "solves_per_s": round(total * args.steps / elapsed, 3),
-                "parallelism": "independent structures sharded over GPUs; collectives only for scatter / gather",
-                "backend": dist.get_backend(),
-                "host_binding": args.host_binding,
-            },
-            "roofline": roofline, "rooflines": rooflines, "phases_ms_profiled_step": dict(tt), "counters": counters,
-            "parity_gates": gates, "cpu_baseline": cpu,
-        }
+        out.update({"roofline": roofline, "rooflines": rooflines, "phases_ms_profiled_step": dict(tt), "counters": counters,
+                    "parity_gates": gates, "cpu_baseline": cpu})
     return out
 
 
@@ -734,8 +788,12 @@ def main():
     ap.add_argument("--config", choices=["c2", "c3", "c4", "c5"], default="c3")
     ap.add_argument("--structures-per-gpu", type=int, default=None)
     ap.add_argument("--n-atoms", type=int, default=0, help="override the configuration's atom count (c2 / c3 / c5)")
-    ap.add_argument("--cpu-runs", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned under DIR as .npy (float64, at most 64 MiB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the profiled step (roofline, rooflines, phases, counters), parity gates and CPU baseline")
+    ap.add_argument("--cpu-runs", type=int, default=3, help="--full: minimum runs of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without parity gates and CPU baseline")
     args = ap.parse_args()
     args.structures_per_gpu_set = args.structures_per_gpu is not None
     if args.structures_per_gpu is None:

@@ -72,3 +72,56 @@ def test_cpu_legs_get_the_start_up_cores_back():
     assert out["before"] == [1, 1]                                 # one BLAS thread on one core: the broken leg
     assert out["inside"] == [out["start"], out["start"], out["start"]]
     assert out["after"] == [1, 1]                                  # the GPU-driving phase gets its binding back
+
+
+def test_dump_outputs_is_seeded_whole_and_bounded(tmp_path):
+    """--dump-outputs: float64 files, whole vectors with their [structure, mode] index, the same sample every run and
+    at most 64 MiB even where the step's eigenvectors are far larger (C3: 64 x 6000 x 6000)."""
+    import numpy as np
+    import torch
+
+    bench = _bench()
+    small_w = torch.arange(4 * 6, dtype=torch.float64).reshape(4, 6)
+    small_v = torch.randn(4, 6, 6, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "small"), small_w, small_v)
+    idx = np.load(tmp_path / "small" / "eigenvectors_index.npy").astype(int)
+    assert np.array_equal(np.load(tmp_path / "small" / "eigenvalues.npy"), small_w.numpy())
+    assert np.array_equal(np.load(tmp_path / "small" / "eigenvectors.npy"), small_v.numpy()[idx[:, 0], idx[:, 1]])
+    assert len(idx) == 24
+
+    B, m = 64, 6000
+    w = torch.linspace(0.0, 1.0, B * m, dtype=torch.float64).reshape(B, m)
+    row = torch.arange(m, dtype=torch.float64)
+    v = row.expand(B, m, m)                          # a zero-stride view: no 18 GB allocation
+    assert v.stride() == (0, 0, 1)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), w, v)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["eigenvalues.npy", "eigenvectors.npy", "eigenvectors_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    vec = np.load(tmp_path / "a" / "eigenvectors.npy")
+    assert vec.shape[1] == m and 100 < vec.shape[0] < B * m and (vec == row.numpy()[None, :]).all()
+
+
+def test_dump_outputs_samples_whole_structures_of_large_eigenvalue_sets(tmp_path):
+    """Eigenvalues above their 16 MiB share: a seeded sample of whole structures, with their indices, the same every run."""
+    import numpy as np
+    import torch
+
+    bench = _bench()
+    B, m = 4000, 600                                 # 19.2 MB of eigenvalues
+    w = torch.arange(B * m, dtype=torch.float64).reshape(B, m)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), w, None)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["eigenvalues.npy", "eigenvalues_index.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 16 << 20
+    for f in files:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    rows = np.load(tmp_path / "a" / "eigenvalues_index.npy").astype(np.int64)
+    assert 1000 < len(rows) < B and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "eigenvalues.npy"), w.numpy()[rows])

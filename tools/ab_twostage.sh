@@ -4,13 +4,14 @@
 #   tools/ab_twostage.sh a.hip b.hip
 set -u
 cd ${GRAFT_REPO_ROOT:-.}
+mkdir -p results
 . tools/ab_lib.sh
 ab_keep springcraft_amd/csrc/twostage.hip
 for rep in 1 2; do
   for v in "$@"; do
     cp "$v" springcraft_amd/csrc/twostage.hip
     ab_build "" || continue
-    timeout -k 10 120 python bench.py --no-cpu-baseline --steps 2 --warmup 1 > gpurun_out/ab.json 2>/dev/null
-    echo "[$v] $(python tools/show_bench.py gpurun_out/ab.json | sed 's/.*tri /tri /')"
+    timeout -k 10 120 python bench.py --full --no-cpu-baseline --steps 2 --warmup 1 > results/ab.json 2>/dev/null
+    echo "[$v] $(python tools/show_bench.py results/ab.json | sed 's/.*tri /tri /')"
   done
 done

@@ -10,7 +10,7 @@ cd /tmp && export TMPDIR=/tmp
 run() {
   local name=$1; shift
   rocprofv3 --pmc "$@" --kernel-trace --kernel-include-regex "$KERNEL" -d $OUT/run_$name -o r --output-format csv -- \
-    python3 $ROOT/bench.py --no-cpu-baseline --steps 1 --warmup 0 $BENCH_ARGS > $OUT/run_$name.log 2>&1
+    python3 $ROOT/bench.py --full --no-cpu-baseline --steps 1 --warmup 0 $BENCH_ARGS > $OUT/run_$name.log 2>&1
   echo "pass $name: $(tail -c 300 $OUT/run_$name.log | tr '\n' ' ' | cut -c1-200)"
 }
 BENCH_ARGS="$*"

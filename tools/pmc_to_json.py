@@ -37,7 +37,7 @@ alg = batch * (2 * z_bytes + frag_bytes)
 out = {
     "command": "bash tools/r06_final.sh b  ->  bash tools/pmc_kernel.sh %s <tag>  (rocprofv3 --pmc, counters only, separate passes: "
                "SQ counters | FETCH_SIZE | WRITE_SIZE TCC_HIT_sum TCC_MISS_sum; --kernel-trace --kernel-include-regex; "
-               "python3 bench.py --no-cpu-baseline --steps 1 --warmup 0), summed by tools/pmc_to_json.py" % kernel,
+               "python3 bench.py --full --no-cpu-baseline --steps 1 --warmup 0), summed by tools/pmc_to_json.py" % kernel,
     "kernel": kernel, "n": n, "batch": batch,
     "launches_sampled": max([len(v) for v in disp.values()] + [0]),
     "counters_per_launch_mean": {c: mean[c] for c in sorted(mean)},

@@ -16,17 +16,17 @@ part=${1:-a}
 if [ $part = a ]; then
   timeout -k 10 600 python -m pytest tests -m gpu -q --durations=15 > $OUT/gputest_durations.txt 2>&1 || { tail -30 $OUT/gputest_durations.txt; exit 1; }
   tail -3 $OUT/gputest_durations.txt
-  timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+  timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
   python tools/show_bench.py $OUT/bench.json
   for c in c2 c4 c5; do
-    timeout -k 10 300 python bench.py --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -5 $OUT/bench_$c.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -5 $OUT/bench_$c.err; exit 1; }
     python tools/show_bench.py $OUT/bench_$c.json
   done
   timeout -k 10 200 python tools/latency_phases.py > $OUT/latency.txt 2>&1 || exit 1
   grep -v amdgpu.ids $OUT/latency.txt
 elif [ $part = b ]; then
   (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench --output-format csv -- \
-     python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err) || { tail -5 $OUT/bench_under_rocprof.err; exit 1; }
+     python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err) || { tail -5 $OUT/bench_under_rocprof.err; exit 1; }
   rm -f $OUT/prof/*kernel_trace.csv $OUT/prof/*/*kernel_trace.csv
   cp $(ls $OUT/prof/*kernel_stats.csv $OUT/prof/*/*kernel_stats.csv 2>/dev/null | head -1) $OUT/rocprofv3_kernel_stats_bench.csv
   head -8 $OUT/rocprofv3_kernel_stats_bench.csv
@@ -37,8 +37,8 @@ elif [ $part = b ]; then
   grep -v amdgpu.ids $OUT/pair_stamps.txt
 elif [ $part = c ]; then
   # the same (small) workload on one rank and on two ranks sharing the GPU: the CPU baseline must come out the same
-  timeout -k 10 300 python bench.py --structures-per-gpu 8 --steps 2 --warmup 1 > $OUT/rehearsal_1rank.json 2> $OUT/rehearsal_1rank.err || { tail -5 $OUT/rehearsal_1rank.err; exit 1; }
-  SPRINGCRAFT_BENCH_SHARE_GPUS=1 timeout -k 10 400 python bench.py --gpus 2 --structures-per-gpu 8 --steps 2 --warmup 1 > $OUT/rehearsal_2ranks.json 2> $OUT/rehearsal_2ranks.err || { tail -5 $OUT/rehearsal_2ranks.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --structures-per-gpu 8 --steps 2 --warmup 1 > $OUT/rehearsal_1rank.json 2> $OUT/rehearsal_1rank.err || { tail -5 $OUT/rehearsal_1rank.err; exit 1; }
+  SPRINGCRAFT_BENCH_SHARE_GPUS=1 timeout -k 10 400 python bench.py --full --gpus 2 --structures-per-gpu 8 --steps 2 --warmup 1 > $OUT/rehearsal_2ranks.json 2> $OUT/rehearsal_2ranks.err || { tail -5 $OUT/rehearsal_2ranks.err; exit 1; }
   python - $OUT/rehearsal_1rank.json $OUT/rehearsal_2ranks.json <<'PY'
 import json, sys
 for p in sys.argv[1:]:
@@ -46,7 +46,7 @@ for p in sys.argv[1:]:
     c = d["cpu_baseline"]
     print(p.split("/")[-1], "n_gpus", d["n_gpus"], "value", d["value"], "host_binding", d["config"]["host_binding"], "| cpu_baseline", c["value"], "cores", c["cores"], c["sample"][:90])
 PY
-  SPRINGCRAFT_BENCH_SHARE_GPUS=1 timeout -k 10 300 python bench.py --config c4 --gpus 2 --structures-per-gpu 8 --steps 2 --warmup 1 > $OUT/rehearsal_c4_2ranks.json 2> $OUT/rehearsal_c4_2ranks.err || { tail -5 $OUT/rehearsal_c4_2ranks.err; exit 1; }
+  SPRINGCRAFT_BENCH_SHARE_GPUS=1 timeout -k 10 300 python bench.py --full --config c4 --gpus 2 --structures-per-gpu 8 --steps 2 --warmup 1 > $OUT/rehearsal_c4_2ranks.json 2> $OUT/rehearsal_c4_2ranks.err || { tail -5 $OUT/rehearsal_c4_2ranks.err; exit 1; }
   python tools/show_bench.py $OUT/rehearsal_c4_2ranks.json
   timeout -k 10 500 python tools/crossover.py > $OUT/two_stage_crossover.txt 2>&1
   cat $OUT/two_stage_crossover.txt

@@ -7,7 +7,7 @@ S=${3:-3}
 i=0
 for lib in "$1" "$2" "$1" "$2"; do
   i=$((i+1))
-  SPRINGCRAFT_HIP_LIB=$PWD/$lib timeout -k 10 600 python bench.py --steps $S --warmup 1 --no-cpu-baseline > $O/lib_$i.json 2> $O/lib_$i.err; echo "[$lib] rc $?"
+  SPRINGCRAFT_HIP_LIB=$PWD/$lib timeout -k 10 600 python bench.py --full --steps $S --warmup 1 --no-cpu-baseline > $O/lib_$i.json 2> $O/lib_$i.err; echo "[$lib] rc $?"
   python - <<PY
 import json
 d=json.loads([l for l in open("$O/lib_$i.json") if l.startswith('{')][-1])

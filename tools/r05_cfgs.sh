@@ -5,7 +5,7 @@ mkdir -p gpurun_out/r05_cfg
 O=gpurun_out/r05_cfg
 for c in ${CFGS:-c5 c4 c2}; do
   for e in ${ENVS:-SPRINGCRAFT_GEMM3=1}; do
-  env $e timeout -k 10 400 python bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline > $O/$c.json 2> $O/$c.err; echo "[$c $e] rc $?"
+  env $e timeout -k 10 400 python bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline > $O/$c.json 2> $O/$c.err; echo "[$c $e] rc $?"
   python - <<PY
 import json
 d=json.loads([l for l in open("$O/$c.json") if l.startswith('{')][-1])

@@ -7,7 +7,7 @@ timeout -k 10 400 python -m pytest tests/test_two_stage_gpu.py -x -q -k "coopera
 grep -q "rc 0" $O/test.txt || exit 1
 if grep -q "Memory access fault" $O/test.txt; then exit 1; fi
 for e in ${ENVS:-SPRINGCRAFT_QR_COOP=0 SPRINGCRAFT_QR_COOP=1}; do
-  env $e timeout -k 10 300 python bench.py --config c5 --steps 3 --warmup 1 --no-cpu-baseline > $O/c5_$e.json 2> $O/c5_$e.err; echo "[c5 $e] rc $?"
+  env $e timeout -k 10 300 python bench.py --full --config c5 --steps 3 --warmup 1 --no-cpu-baseline > $O/c5_$e.json 2> $O/c5_$e.err; echo "[c5 $e] rc $?"
   python - <<PY
 import json
 d=json.loads([l for l in open("$O/c5_$e.json") if l.startswith('{')][-1])

@@ -21,17 +21,17 @@ part=${1:-a}
 if [ $part = a ]; then
   timeout -k 10 900 python -m pytest tests -m gpu -q --durations=15 > $OUT/gputest_durations.txt 2>&1 || { tail -30 $OUT/gputest_durations.txt; exit 1; }
   tail -3 $OUT/gputest_durations.txt
-  timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+  timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
   python tools/show_bench.py $OUT/bench.json
   for c in c2 c4 c5; do
-    timeout -k 10 300 python bench.py --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -5 $OUT/bench_$c.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -5 $OUT/bench_$c.err; exit 1; }
     python tools/show_bench.py $OUT/bench_$c.json
   done
   timeout -k 10 200 python tools/latency_phases.py > $OUT/latency.txt 2>&1 || exit 1
   grep -v amdgpu.ids $OUT/latency.txt
 elif [ $part = b ]; then
   (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench --output-format csv -- \
-     python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err) || { tail -5 $OUT/bench_under_rocprof.err; exit 1; }
+     python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err) || { tail -5 $OUT/bench_under_rocprof.err; exit 1; }
   rm -f $OUT/prof/*kernel_trace.csv $OUT/prof/*/*kernel_trace.csv
   cp $(ls $OUT/prof/*kernel_stats.csv $OUT/prof/*/*kernel_stats.csv 2>/dev/null | head -1) $OUT/rocprofv3_kernel_stats_bench.csv
   head -8 $OUT/rocprofv3_kernel_stats_bench.csv
@@ -45,7 +45,7 @@ elif [ $part = b ]; then
 elif [ $part = b2 ]; then
   # per-kernel totals of the C5 line (one n = 24 000 matrix, 106 modes): k_panel_coop among them
   (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d $OUT/prof_c5 -o bench --output-format csv -- \
-     python3 $ROOT/bench.py --config c5 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_c5_under_rocprof.json 2> $OUT/bench_c5_under_rocprof.err) || { tail -5 $OUT/bench_c5_under_rocprof.err; exit 1; }
+     python3 $ROOT/bench.py --full --config c5 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_c5_under_rocprof.json 2> $OUT/bench_c5_under_rocprof.err) || { tail -5 $OUT/bench_c5_under_rocprof.err; exit 1; }
   rm -f $OUT/prof_c5/*kernel_trace.csv $OUT/prof_c5/*/*kernel_trace.csv
   cp $(ls $OUT/prof_c5/*kernel_stats.csv $OUT/prof_c5/*/*kernel_stats.csv 2>/dev/null | head -1) $OUT/rocprofv3_kernel_stats_bench_c5.csv
   head -12 $OUT/rocprofv3_kernel_stats_bench_c5.csv | cut -c1-220

@@ -7,7 +7,7 @@ O=gpurun_out/r06_cfg
 IFS=';' read -ra EL <<< "${ENVS:-X=0}"
 for c in ${CFGS:-c5 c4 c2}; do
   for e in "${EL[@]}"; do
-  env $e timeout -k 10 400 python bench.py --config $c --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline > $O/$c.json 2> $O/$c.err; echo "[$c $e] rc $?"
+  env $e timeout -k 10 400 python bench.py --full --config $c --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline > $O/$c.json 2> $O/$c.err; echo "[$c $e] rc $?"
   python - <<PY
 import json
 d=json.loads([l for l in open("$O/$c.json") if l.startswith('{')][-1])

@@ -4,7 +4,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/r06_dc
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace -d $OUT/trace -o r --output-format csv -- python3 $ROOT/bench.py --no-cpu-baseline --steps 1 --warmup 0 > $OUT/run.log 2>&1
+rocprofv3 --kernel-trace -d $OUT/trace -o r --output-format csv -- python3 $ROOT/bench.py --full --no-cpu-baseline --steps 1 --warmup 0 > $OUT/run.log 2>&1
 python3 - <<PY
 import csv, glob
 f = glob.glob("$OUT/trace/**/*kernel_trace.csv", recursive=True)[0]

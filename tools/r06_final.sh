@@ -28,26 +28,26 @@ part=${1:-a}
 if [ $part = a ]; then
   timeout -k 10 900 python -m pytest tests -m gpu -q --durations=15 > $OUT/gputest_durations.txt 2>&1 || { tail -30 $OUT/gputest_durations.txt; exit 1; }
   tail -3 $OUT/gputest_durations.txt
-  timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+  timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
   python tools/show_bench.py $OUT/bench.json
   for c in c2 c4 c5; do
-    timeout -k 10 300 python bench.py --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -5 $OUT/bench_$c.err; exit 1; }
+    timeout -k 10 300 python bench.py --full --config $c > $OUT/bench_$c.json 2> $OUT/bench_$c.err || { tail -5 $OUT/bench_$c.err; exit 1; }
     python tools/show_bench.py $OUT/bench_$c.json
   done
   timeout -k 10 300 python tools/latency_phases.py > $OUT/latency.txt 2>&1 || exit 1
   grep -v amdgpu.ids $OUT/latency.txt
 elif [ $part = ab ]; then
   # the default bench line and the rocprofv3 kernel statistics of the same command on ONE box (boxes differ by 3 - 5 %)
-  timeout -k 10 400 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
+  timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
   python tools/show_bench.py $OUT/bench.json
   (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench --output-format csv -- \
-     python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err) || { tail -5 $OUT/bench_under_rocprof.err; exit 1; }
+     python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err) || { tail -5 $OUT/bench_under_rocprof.err; exit 1; }
   rm -f $OUT/prof/*kernel_trace.csv $OUT/prof/*/*kernel_trace.csv
   cp $(ls -t $OUT/prof/*kernel_stats.csv $OUT/prof/*/*kernel_stats.csv 2>/dev/null | head -1) $OUT/rocprofv3_kernel_stats_bench.csv
   head -4 $OUT/rocprofv3_kernel_stats_bench.csv | cut -c1-200
 elif [ $part = b ]; then
   (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d $OUT/prof -o bench --output-format csv -- \
-     python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err) || { tail -5 $OUT/bench_under_rocprof.err; exit 1; }
+     python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err) || { tail -5 $OUT/bench_under_rocprof.err; exit 1; }
   rm -f $OUT/prof/*kernel_trace.csv $OUT/prof/*/*kernel_trace.csv
   cp $(ls $OUT/prof/*kernel_stats.csv $OUT/prof/*/*kernel_stats.csv 2>/dev/null | head -1) $OUT/rocprofv3_kernel_stats_bench.csv
   head -8 $OUT/rocprofv3_kernel_stats_bench.csv | cut -c1-200
@@ -99,7 +99,7 @@ elif [ $part = e ]; then
     echo "== a few matrices, one XCD per matrix (SPRINGCRAFT_BULGE_SPREAD=0) against all XCDs for every matrix (=1): tools/spread_sweep.py"
     for sp in 0 1; do SPRINGCRAFT_BULGE_SPREAD=$sp timeout -k 10 400 python tools/spread_sweep.py 2>/dev/null; done
     echo "== n = 12000 (bench.py --config c5 --n-atoms 4000), SPRINGCRAFT_BULGE_SPREAD = 0 / default"
-    for e in SPRINGCRAFT_BULGE_SPREAD=0 X=default; do env $e timeout -k 10 300 python bench.py --config c5 --n-atoms 4000 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('  $e', round(d['ms_per_step'],1), 'ms per solve, bulge chasing', round(d['phases_ms_profiled_step'].get('bulge_chasing_ms',0),1))"; done; } > $OUT/spread_chase.txt 2>&1
+    for e in SPRINGCRAFT_BULGE_SPREAD=0 X=default; do env $e timeout -k 10 300 python bench.py --full --config c5 --n-atoms 4000 --steps 3 --warmup 1 --no-cpu-baseline 2>/dev/null | python -c "import sys,json; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('  $e', round(d['ms_per_step'],1), 'ms per solve, bulge chasing', round(d['phases_ms_profiled_step'].get('bulge_chasing_ms',0),1))"; done; } > $OUT/spread_chase.txt 2>&1
   cat $OUT/spread_chase.txt
   bash tools/r06_dc_levels.sh > $OUT/dc_levels.txt 2>&1
   cat $OUT/dc_levels.txt
@@ -135,9 +135,9 @@ elif [ $part = c5 ]; then
     row SPRINGCRAFT_TWO_STAGE=0; } > $OUT/test_matrix_5.txt 2>&1
   cat $OUT/test_matrix_5.txt
 else
-  SPRINGCRAFT_BENCH_SHARE_GPUS=1 timeout -k 10 500 python bench.py --gpus 2 --steps 2 --warmup 1 > $OUT/rehearsal_2ranks.json 2> $OUT/rehearsal_2ranks.err; echo "rehearsal rc $?"
+  SPRINGCRAFT_BENCH_SHARE_GPUS=1 timeout -k 10 500 python bench.py --full --gpus 2 --steps 2 --warmup 1 > $OUT/rehearsal_2ranks.json 2> $OUT/rehearsal_2ranks.err; echo "rehearsal rc $?"
   python tools/show_bench.py $OUT/rehearsal_2ranks.json
-  SPRINGCRAFT_BENCH_SHARE_GPUS=1 timeout -k 10 400 python bench.py --gpus 2 --config c4 --steps 2 --warmup 1 > $OUT/rehearsal_c4_2ranks.json 2> $OUT/rehearsal_c4_2ranks.err; echo "rehearsal c4 rc $?"
+  SPRINGCRAFT_BENCH_SHARE_GPUS=1 timeout -k 10 400 python bench.py --full --gpus 2 --config c4 --steps 2 --warmup 1 > $OUT/rehearsal_c4_2ranks.json 2> $OUT/rehearsal_c4_2ranks.err; echo "rehearsal c4 rc $?"
   python tools/show_bench.py $OUT/rehearsal_c4_2ranks.json
 fi
 echo "part $part done"

@@ -5,13 +5,14 @@
 # does not compile is reported and skipped, never timed as the previous build.)
 set -u
 cd ${GRAFT_REPO_ROOT:-.}
+mkdir -p results
 . tools/ab_lib.sh
 ab_keep springcraft_amd/csrc/twostage.hip
 i=0
 for flags in "$@"; do
   touch springcraft_amd/csrc/twostage.hip
   ab_build "$flags" || continue
-  timeout -k 10 120 python bench.py --no-cpu-baseline --steps 1 --warmup 1 > gpurun_out/var_$i.json 2>/dev/null
-  echo "[$flags] $(python tools/show_bench.py gpurun_out/var_$i.json | sed 's/.*bt2 /bt2 /')"
+  timeout -k 10 120 python bench.py --full --no-cpu-baseline --steps 1 --warmup 1 > results/var_$i.json 2>/dev/null
+  echo "[$flags] $(python tools/show_bench.py results/var_$i.json | sed 's/.*bt2 /bt2 /')"
   i=$((i+1))
 done

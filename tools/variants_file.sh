@@ -4,6 +4,7 @@
 # (the library is rebuilt without extra flags at the end, also when the run is interrupted)
 set -u
 cd ${GRAFT_REPO_ROOT:-.}
+mkdir -p results
 . tools/ab_lib.sh
 F=$1; shift
 ab_keep $F
@@ -12,8 +13,8 @@ for rep in 1 2; do
   for flags in "$@"; do
     touch $F
     ab_build "$flags" || continue
-    timeout -k 10 120 python bench.py --no-cpu-baseline --steps 2 --warmup 1 > gpurun_out/varf_$i.json 2>/dev/null
-    echo "[$flags] $(python tools/show_bench.py gpurun_out/varf_$i.json | sed 's/.*modes\/s //')"
+    timeout -k 10 120 python bench.py --full --no-cpu-baseline --steps 2 --warmup 1 > results/varf_$i.json 2>/dev/null
+    echo "[$flags] $(python tools/show_bench.py results/varf_$i.json | sed 's/.*modes\/s //')"
     i=$((i+1))
   done
 done
