@@ -299,7 +299,9 @@ int sc_last_eigh_phase_ms(sc_ctx* ctx, const char* name, double* ms);
  *                      flag but with sweeps left), and the context stops using the persistent form
  *   "chase_sweeps"     sweeps the persistent chases finished themselves
  *   "stepwise_chases"  bulge chases that ran as per-wavefront launches from the start
- *   "chase_xcd_min" / "chase_xcd_max"   workgroups per XCD in the most recent persistent chase
+ *   "chase_xcd_min" / "chase_xcd_max"   workgroups per XCD in the most recent persistent chase (the spread form, one
+ *                      matrix on all XCDs, counts as one XCD)
+ *   "chase_xcd_total"  workgroups of the most recent persistent chase (its grid)
  *   "chase_wait_matrix" / "_sweep" / "_task"   where the last timed-out wait stood (-1: never)
  *   "chase_pair_fallbacks"   pair launches the device refused (dynamic LDS) and that were re-issued in the one-sweep form
  *   "xcd_count"        XCDs of the device as a probe launch saw them (0: not probed yet)

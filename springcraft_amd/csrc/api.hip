@@ -108,7 +108,7 @@ int sc_collect_events(sc_ctx* ctx) {
   if (h[3] || h[6]) ctx->chase_ok = 0;
   if (h[5]) ctx->coop_ok = 0;
   if (ctx->last_chase_ctl) {   // the most recent chase's control block: tickets per XCD, where a wait timed out
-    int c[32] = {0};
+    int c[kChaseCtlInts] = {0};
     SC_HIP(ctx, hipMemcpy(c, ctx->last_chase_ctl, sizeof(c), hipMemcpyDeviceToHost));
     for (int x = 0; x < 8; ++x) ctx->chase_tickets[x] = c[2 + x];
     if (c[0] && c[1] == 0) { ctx->chase_wait[0] = c[10]; ctx->chase_wait[1] = c[11]; ctx->chase_wait[2] = c[12]; }
@@ -208,9 +208,12 @@ int ctx_create_impl(int device, void* stream, bool own, sc_ctx** out) {
   if (hipMalloc((void**)&ctx->d_status, kSpStatusWords * sizeof(unsigned long long)) != hipSuccess ||
       hipMemset(ctx->d_status, 0, kSpStatusWords * sizeof(unsigned long long)) != hipSuccess ||
       hipMalloc((void**)&ctx->d_zeros, 16384) != hipSuccess || hipMemset(ctx->d_zeros, 0, 16384) != hipSuccess ||
+      hipMalloc((void**)&ctx->d_chase_ctl, kChaseCtlInts * sizeof(int)) != hipSuccess ||
+      hipMemset(ctx->d_chase_ctl, 0, kChaseCtlInts * sizeof(int)) != hipSuccess ||
       hipDeviceSynchronize() != hipSuccess) {
     if (ctx->d_status) (void)hipFree(ctx->d_status);
     if (ctx->d_zeros) (void)hipFree(ctx->d_zeros);
+    if (ctx->d_chase_ctl) (void)hipFree(ctx->d_chase_ctl);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return SC_ERR_NOMEM;
@@ -369,6 +372,7 @@ void sc_ctx_destroy(sc_ctx* ctx) {
   if (ctx->pinv_ws) (void)hipFree(ctx->pinv_ws);
   if (ctx->d_status) (void)hipFree(ctx->d_status);
   if (ctx->d_zeros) (void)hipFree(ctx->d_zeros);
+  if (ctx->d_chase_ctl) (void)hipFree(ctx->d_chase_ctl);
   for (int c = 0; c < 2; ++c) {
     if (ctx->h_stage[c]) (void)hipHostFree(ctx->h_stage[c]);
     if (ctx->h_stage_done[c]) (void)hipEventDestroy(ctx->h_stage_done[c]);
@@ -452,10 +456,14 @@ int sc_ctx_get_counter(sc_ctx* ctx, const char* name, int64_t* value) {
   SC_HIP(ctx, hipSetDevice(ctx->device));
   SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   SC_TRY(sc_collect_events(ctx));
+  // (over the ticket slots the last chase drew from: one for the spread form, whose workgroups all count as XCD 0, or
+  // the device's XCDs; the sum is the chase's grid)
   int tmin = ctx->chase_tickets[0], tmax = ctx->chase_tickets[0];
-  for (int x = 1; x < 8; ++x) {
+  long long tsum = 0;
+  for (int x = 0; x < std::max(1, std::min(8, ctx->chase_ctl_xcds)); ++x) {
     tmin = std::min(tmin, ctx->chase_tickets[x]);
     tmax = std::max(tmax, ctx->chase_tickets[x]);
+    tsum += ctx->chase_tickets[x];
   }
   if (k == "chase_launches") *value = ctx->cnt_chase_launches;
   else if (k == "chase_pair_launches") *value = ctx->cnt_pair_launches;
@@ -477,6 +485,7 @@ int sc_ctx_get_counter(sc_ctx* ctx, const char* name, int64_t* value) {
   else if (k == "stepwise_chases") *value = ctx->cnt_stepwise_chases;
   else if (k == "chase_xcd_min") *value = tmin;
   else if (k == "chase_xcd_max") *value = tmax;
+  else if (k == "chase_xcd_total") *value = tsum;
   else if (k == "chase_wait_matrix") *value = ctx->chase_wait[0];
   else if (k == "chase_wait_sweep") *value = ctx->chase_wait[1];
   else if (k == "chase_wait_task") *value = ctx->chase_wait[2];

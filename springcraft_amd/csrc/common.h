@@ -93,12 +93,18 @@ struct sc_ctx {
   long long cnt_resident_launches = 0, cnt_resident_takeovers = 0, cnt_resident_rollcalls = 0, cnt_resident_lost = 0;
   long long resident_lost_at = -1;   // (step << 32 | workgroup) of the most recent lost wait / arrivals at the last failed roll call
   int resident_strikes = 0;          // failed roll calls since the kernel was (re-)armed: the context gives it up at the third
-  int* last_chase_ctl = nullptr;   // control block of the most recent persistent chase (in dc_aux), read by sc_collect_events
+  // control block of the persistent chase (kChaseCtlInts ints, allocated with the context and zeroed before every chase
+  // launch): an allocation of its own, since dc_aux is reused by the D&C of the same solve before the block is read --
+  // for n > 7000 its global scratch covers the bytes the block sat at in dc_aux.  last_chase_ctl points to it after a
+  // chase launch until sc_collect_events has read it; chase_ctl_xcds: ticket slots that launch used (1 for the spread form)
+  int* d_chase_ctl = nullptr;
+  int* last_chase_ctl = nullptr;
+  int chase_ctl_xcds = 8;
   long long cnt_coop_launches = 0, cnt_coop_timeouts = 0;
   // event counters since the context was created (sc_ctx_get_counter)
   long long cnt_chase_launches = 0, cnt_chase_timeouts = 0, cnt_chase_incomplete = 0, cnt_chase_resumed = 0,
             cnt_chase_sweeps = 0, cnt_stepwise_chases = 0, cnt_pair_launches = 0;
-  int chase_tickets[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // workgroups per XCD of the most recent chase launch
+  int chase_tickets[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // workgroups per XCD of the most recent chase launch (chase_ctl_xcds of them)
   int chase_wait[3] = {-1, -1, -1};                  // (matrix, sweep, task) of the wait that timed out last
   bool profiling = false;
   double last_timings[6] = {0, 0, 0, 0, 0, 0};
@@ -186,6 +192,8 @@ int sc_stage_end(sc_ctx* ctx);
 // after a synchronisation of ctx->stream: SC_ERR_NOCONV (and the flags cleared) if a solve since the last call met
 // non-finite input or a QL failure, else SC_OK
 constexpr int kSpStatusWords = 16;
+// ints of the persistent chase's control block (sc_ctx::d_chase_ctl; layout at k_bulge_chase in twostage.hip)
+constexpr int kChaseCtlInts = 32;
 int sc_deferred_status(sc_ctx* ctx);
 // adds the device-side event words to the context's counters (the context's stream must be idle)
 int sc_collect_events(sc_ctx* ctx);

@@ -1589,8 +1589,8 @@ __global__ __launch_bounds__(256) void k_chase_finish(double* __restrict__ sb_al
 // per-wavefront launches from the published counters and does not use the persistent form on that context again.
 //
 // ctl (ints): [0] time-out flag, [1] workgroup-local tasks after which the test hook raised it, [2..9] tickets drawn
-// per XCD, [10..12] (matrix, sweep, task) of the wait that timed out, [16..23] sweeps finished per XCD.
-constexpr int kChaseCtlInts = 32;
+// per XCD, [10..12] (matrix, sweep, task) of the wait that timed out, [16..23] sweeps finished per XCD (kChaseCtlInts
+// ints: sc_ctx::d_chase_ctl).
 
 // Early hand-off (round 4).  Task (s, k) reads three things from sweep s - 1: the blocks task (s - 1, k) has left --
 // all its rows but the last --, and from task (s - 1, k + 1) its last row: the entry beta (what remains of the column that
@@ -4556,21 +4556,22 @@ int sytrd_2stage_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, in
       const int useful = pair ? std::max(4, chase_len(n, 0) / 3 + 2) : std::max(8, chase_len(n, 0) / 2 + 1);
       const int W = slots_per_xcd > 0 ? std::max(1, std::min(useful, slots_per_xcd / mpx)) : 0;
       if (W >= 1) {
-        // progress counters (batch x n) | claim counters (batch) | ctl
+        // progress counters (batch x n) | claim counters (batch) in dc_aux; the control block is the context's own
+        // (dc_aux is reused by the D&C of this solve before sc_collect_events reads the block)
         const size_t prog_bytes = align_up((size_t)batch * n * sizeof(int), 256);
         const size_t next_bytes = align_up((size_t)batch * sizeof(int), 256);
-        const size_t ctl_bytes = align_up(kChaseCtlInts * sizeof(int), 256);
         // early hand-off records of k_bulge_chase (16 B x kEarlyRing per sweep; zeroed with the counters: a stale tag of
         // the previous solve would pass for this one's)
         static const bool no_early = getenv("SPRINGCRAFT_BULGE_NO_EARLY") != nullptr;
         const size_t early_bytes = (pair || no_early) ? 0 : align_up((size_t)batch * n * kEarlyRing * sizeof(v4i), 256);
-        SC_TRY(sc_reserve_dc_aux(ctx, prog_bytes + next_bytes + ctl_bytes + early_bytes));
+        SC_TRY(sc_reserve_dc_aux(ctx, prog_bytes + next_bytes + early_bytes));
         int* d_prog = reinterpret_cast<int*>(ctx->dc_aux);
         int* d_next = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->dc_aux) + prog_bytes);
-        int* d_ctl = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->dc_aux) + prog_bytes + next_bytes);
-        v4i* d_early = early_bytes ? reinterpret_cast<v4i*>(reinterpret_cast<char*>(ctx->dc_aux) + prog_bytes + next_bytes + ctl_bytes)
+        int* d_ctl = ctx->d_chase_ctl;
+        v4i* d_early = early_bytes ? reinterpret_cast<v4i*>(reinterpret_cast<char*>(ctx->dc_aux) + prog_bytes + next_bytes)
                                    : nullptr;
-        SC_HIP(ctx, hipMemsetAsync(ctx->dc_aux, 0, prog_bytes + next_bytes + ctl_bytes + early_bytes, st));
+        SC_HIP(ctx, hipMemsetAsync(ctx->dc_aux, 0, prog_bytes + next_bytes + early_bytes, st));
+        SC_HIP(ctx, hipMemsetAsync(d_ctl, 0, kChaseCtlInts * sizeof(int), st));
         // the dispatcher deals workgroups round-robin over the XCDs, so 8 x (workgroups one XCD needs) gives every XCD
         // its share; the kernel does not rely on it (a short-changed XCD is just slower, see the kernel's header)
         const int grid = nxcd * std::min(slots_per_xcd, mpx * W);
@@ -4608,6 +4609,7 @@ int sytrd_2stage_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, in
           ++ctx->cnt_chase_launches;
           if (pair) ++ctx->cnt_pair_launches;
           ctx->last_chase_ctl = d_ctl;
+          ctx->chase_ctl_xcds = nxcd;
           chased = true;
         }
       }

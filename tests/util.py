@@ -95,6 +95,16 @@ def check_eigenvalues(w, w_ref, n_trivial, rtol=1e-5):
     assert np.all(np.diff(w) >= -1e-12 * lam_max), "eigenvalues not ascending"
 
 
+def device_checks(torch, h, w, v):
+    """Residual (max column norm / lambda_max) and orthogonality of ALL eigenpairs of one matrix, on the device."""
+    r = h @ v.T - v.T * w[None, :]
+    res = float(torch.linalg.vector_norm(r, dim=0).max() / w.abs().max())
+    del r
+    eye = torch.eye(len(w), dtype=torch.float64, device=w.device)
+    orth = float((v @ v.T - eye).abs().max())
+    return res, orth
+
+
 def check_eigenvectors(a, w, v, tol_res=1e-5, tol_orth=1e-8):
     """Residual ||A v - lambda v|| <= tol * ||A|| and ||V V^T - I||_max <= tol_orth (rows = modes)."""
     a = np.asarray(a)
