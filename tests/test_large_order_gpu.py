@@ -20,11 +20,16 @@ import os
 import numpy as np
 import pytest
 
+from tests.util import LATTICE_CUTOFF as CUTOFF
+from tests.util import LATTICE_SPACING as SPACING
+from tests.util import anm_exact as _anm_exact
 from tests.util import device_checks, forced_two_stage, generated, synthetic_coord
+from tests.util import gnm_exact as _gnm_exact
+from tests.util import lattice as _lattice
+from tests.util import path_eigs as _path_eigs
 
 pytestmark = pytest.mark.gpu
 
-SPACING, CUTOFF = 3.8, 4.5
 TOL = 1e-11
 
 
@@ -42,37 +47,9 @@ def _path_overridden():
     return any(k.startswith("SPRINGCRAFT_BULGE_") or k.startswith("SPRINGCRAFT_RESIDENT") for k in os.environ)
 
 
-def _rotation(seed):
-    q, r = np.linalg.qr(np.random.RandomState(seed).randn(3, 3))
-    q = q * np.sign(np.diag(r))
-    if np.linalg.det(q) < 0:
-        q[:, 0] = -q[:, 0]
-    return q
-
-
-def _lattice(a, b, c, seed):
-    """a x b x c grid points (index order i, j, k), spacing 3.8 A, rotated and shifted."""
-    g = np.stack(np.meshgrid(np.arange(a), np.arange(b), np.arange(c), indexing="ij"), -1).reshape(-1, 3)
-    return g * SPACING @ _rotation(seed).T + np.array([12.5, -7.25, 3.0])
-
-
 def _chain(m, offset):
     """m points on a straight line (spacing 3.8 A), far from everything else."""
     return np.arange(m)[:, None] * np.array([SPACING, 0.0, 0.0]) + np.asarray(offset, dtype=np.float64)
-
-
-def _path_eigs(m):
-    return 4.0 * np.sin(np.pi * np.arange(m) / (2.0 * m)) ** 2
-
-
-def _gnm_exact(a, b, c):
-    pa, pb, pc = (_path_eigs(m).astype(np.longdouble) for m in (a, b, c))
-    return (pa[:, None, None] + pb[None, :, None] + pc[None, None, :]).ravel()
-
-
-def _anm_exact(a, b, c):
-    return np.concatenate([np.repeat(_path_eigs(a), b * c), np.repeat(_path_eigs(b), a * c),
-                           np.repeat(_path_eigs(c), a * b)])
 
 
 def _grid_laplacian(a, b, c):

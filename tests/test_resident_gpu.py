@@ -72,6 +72,10 @@ def test_whole_matrix_in_one_launch(res, n):
     assert np.abs(w_only - w).max() <= 1e-11 * np.abs(w).max()
     ws, vs = sc.nma.eigh(a, subset_by_index=(3, 40))
     assert np.abs(ws - w[3:41]).max() <= 1e-11 * np.abs(w).max()
+    # the vectors of the partial spectrum: residual (relative to max |w| of the whole spectrum) and orthogonality
+    r = a @ vs.T - vs.T * ws[None, :]
+    assert np.linalg.norm(r, axis=0).max() <= 1e-11 * np.abs(w).max()
+    assert np.abs(vs @ vs.T - np.eye(38)).max() <= 1e-11
     assert counter("resident_launches") == before + 3 and counter("resident_takeovers") == t0
     # same eigenvalues as the launches per column give
     set_(0)

@@ -95,10 +95,13 @@ def check_eigenvalues(w, w_ref, n_trivial, rtol=1e-5):
     assert np.all(np.diff(w) >= -1e-12 * lam_max), "eigenvalues not ascending"
 
 
-def device_checks(torch, h, w, v):
-    """Residual (max column norm / lambda_max) and orthogonality of ALL eigenpairs of one matrix, on the device."""
+def device_checks(torch, h, w, v, scale=None):
+    """
+    Residual (max column norm / lambda_max) and orthogonality of the eigenpairs (w, v) of one matrix, on the device.
+    ``scale``: lambda_max of the whole spectrum when (w, v) is only part of it (default: max |w|).
+    """
     r = h @ v.T - v.T * w[None, :]
-    res = float(torch.linalg.vector_norm(r, dim=0).max() / w.abs().max())
+    res = float(torch.linalg.vector_norm(r, dim=0).max() / (w.abs().max() if scale is None else scale))
     del r
     eye = torch.eye(len(w), dtype=torch.float64, device=w.device)
     orth = float((v @ v.T - eye).abs().max())
@@ -116,3 +119,118 @@ def check_eigenvectors(a, w, v, tol_res=1e-5, tol_orth=1e-8):
     orth = np.abs(g - np.eye(len(w))).max()
     assert orth <= tol_orth, orth
     return res, orth
+
+
+def subspace_error(a, w_ref, v_ref, lo, hi, v, res_fro, cluster_gap=1e-3):
+    """
+    Subspace check of the eigenvectors v (rows) of the eigenvalues lo..hi of the symmetric matrix `a`, against the
+    reference eigenpairs (w_ref ascending, v_ref columns): the sine of the largest angle between v and the reference's
+    invariant subspace of the clusters (split at gaps >= cluster_gap lambda_max) that [lo, hi] touches, with its
+    Davis-Kahan bound 2 (||R||_F + ||R_ref||_F) / gap (res_fro = ||R||_F of v).  When the range holds whole clusters this
+    is ||P - P_ref||_2; when lo / hi cut a cluster, ||(I - P_cluster) v||.  Returns (error, bound, (first, last) index
+    of the clusters).
+    """
+    n = len(w_ref)
+    scale = np.abs(w_ref).max()
+    delta = cluster_gap * scale
+    a0, b0 = lo, hi
+    while a0 > 0 and w_ref[a0] - w_ref[a0 - 1] < delta:
+        a0 -= 1
+    while b0 < n - 1 and w_ref[b0 + 1] - w_ref[b0] < delta:
+        b0 += 1
+    gap = np.inf
+    if a0 > 0:
+        gap = min(gap, w_ref[a0] - w_ref[a0 - 1])
+    if b0 < n - 1:
+        gap = min(gap, w_ref[b0 + 1] - w_ref[b0])
+    u = v_ref[:, a0:b0 + 1]
+    r_ref = np.linalg.norm(a @ u - u * w_ref[a0:b0 + 1][None, :])
+    d = v.T - u @ (u.T @ v.T)
+    err = np.linalg.norm(d, 2) if d.size else 0.0
+    bound = 2.0 * (res_fro + r_ref) / gap if np.isfinite(gap) else 0.0
+    return err, max(bound, 1e-13), (a0, b0)
+
+
+# ---- matrices with known spectra ------------------------------------------------------------------------------
+# Elastic networks on a cubic lattice (spacing 3.8 A, cutoff 4.5 A: only axis neighbours are in contact) have the
+# spectra of sums of path graphs (tests/test_large_order_gpu.py explains the closed forms).
+LATTICE_SPACING, LATTICE_CUTOFF = 3.8, 4.5
+
+
+def rotation(seed):
+    q, r = np.linalg.qr(np.random.RandomState(seed).randn(3, 3))
+    q = q * np.sign(np.diag(r))
+    if np.linalg.det(q) < 0:
+        q[:, 0] = -q[:, 0]
+    return q
+
+
+def lattice(a, b, c, seed):
+    """a x b x c grid points (index order i, j, k), spacing 3.8 A, rotated and shifted."""
+    g = np.stack(np.meshgrid(np.arange(a), np.arange(b), np.arange(c), indexing="ij"), -1).reshape(-1, 3)
+    return g * LATTICE_SPACING @ rotation(seed).T + np.array([12.5, -7.25, 3.0])
+
+
+def path_eigs(m):
+    return 4.0 * np.sin(np.pi * np.arange(m) / (2.0 * m)) ** 2
+
+
+def gnm_exact(a, b, c):
+    pa, pb, pc = (path_eigs(m).astype(np.longdouble) for m in (a, b, c))
+    return (pa[:, None, None] + pb[None, :, None] + pc[None, None, :]).ravel()
+
+
+def anm_exact(a, b, c):
+    return np.concatenate([np.repeat(path_eigs(a), b * c), np.repeat(path_eigs(b), a * c),
+                           np.repeat(path_eigs(c), a * b)])
+
+
+def glued_wilkinson(blocks, glue, order=21):
+    """
+    (d, e) of `blocks` Wilkinson matrices W_order^+ (d_i = |i - (order - 1) / 2|, e_i = 1) glued by off-diagonal
+    entries `glue`: every eigenvalue of W^+ becomes a cluster of `blocks` eigenvalues spread by ~glue, and the top pairs
+    of W^+ (already equal to ~1e-14) clusters of 2 * blocks.
+    """
+    d0 = np.abs(np.arange(order) - (order - 1) / 2.0)
+    d = np.tile(d0, blocks)
+    e = np.ones(blocks * order - 1)
+    e[order - 1::order] = glue
+    return d, e
+
+
+def tridiagonal(d, e):
+    return np.diag(d) + np.diag(e, 1) + np.diag(e, -1)
+
+
+def signed_permutation(seed, n):
+    """An exact orthogonal similarity: P A P^T with P a random permutation with random signs."""
+    rs = np.random.RandomState(seed)
+    return rs.permutation(n), rs.choice([-1.0, 1.0], n)
+
+
+def permute(a, perm, signs):
+    return (a * signs[:, None] * signs[None, :])[np.ix_(perm, perm)]
+
+
+def clustered_spectrum(rel_spacing, sizes=(1, 5, 12, 1, 8, 3, 20, 1, 7, 2), seed=0, n=None):
+    """
+    Eigenvalues in clusters: cluster c of `sizes[c]` members at centre mu_c (mu_c spread over [-3, 5], well apart) with
+    members mu_c (1 + k rel_spacing), k = 0 .. size - 1 (rel_spacing 0: exact multiplicities), then simple eigenvalues up
+    to order `n` filling the gaps between the centres.
+    """
+    rs = np.random.RandomState(seed)
+    centres = np.linspace(-3.0, 5.0, len(sizes)) + 0.01
+    w = [mu * (1.0 + rel_spacing * np.arange(s)) for mu, s in zip(centres, sizes)]
+    k = sum(sizes)
+    if n is not None and n > k:
+        fill = rs.uniform(-3.5, 5.5, n - k)
+        # keep the simple eigenvalues 0.05 away from every cluster centre
+        for mu in centres:
+            fill = np.where(np.abs(fill - mu) < 0.05, fill + 0.1, fill)
+        w.append(fill)
+    return np.sort(np.concatenate(w))
+
+
+def random_orthogonal(seed, n):
+    q, r = np.linalg.qr(np.random.RandomState(seed).randn(n, n))
+    return q * np.sign(np.diag(r))
