@@ -178,6 +178,16 @@ int sc_eigh_f64(sc_ctx* ctx, const double* a, int64_t n, double* w, double* v);
  * matrix, back-transformation of the selected vectors only. */
 int sc_eigh_range_f64(sc_ctx* ctx, const double* a, int64_t n, int64_t il, int64_t iu, double* w, double* v);
 
+/* Eigenvalue window: the eigenpairs whose eigenvalues lie in the half-open interval (vl, vu], as
+ * scipy.linalg.eigh(a, subset_by_value=(vl, vu)) selects them; vl = -INFINITY / vu = INFINITY are allowed, vl >= vu or a
+ * NaN bound is SC_ERR_INVALID_ARG.  The count m is taken on the device by Sturm counts on the tridiagonal matrix that is
+ * then solved (one tridiagonalisation), after which exactly m pairs are computed as sc_eigh_range_f64 computes them.  An
+ * eigenvalue within about n eps |A| of a bound may fall on either side of it (as in LAPACK's dsyevr).
+ * Results: *m, and *w (m,) ascending, *v (m, n) rows = modes (want_vectors != 0; v may be NULL otherwise) in page-locked
+ * blocks from sc_host_alloc that the caller releases with sc_host_free; m = 0 leaves *w = *v = NULL. */
+int sc_eigh_window_f64(sc_ctx* ctx, const double* a, int64_t n, double vl, double vu, int want_vectors, int64_t* m,
+                       double** w, double** v);
+
 /* Hermitian pseudo-inverse, replaces np.linalg.pinv(M, hermitian=True, rcond=1e-6) in the covariance / matrix
  * properties (anm.py:114-117,132-136; gnm.py:107-110,125-131): eigendecomposition on the device, then
  * (U * s) U^T with s_i = 1/w_i where |w_i| > rcond * max|w| and 0 elsewhere (one f64-MFMA GEMM).
@@ -194,6 +204,10 @@ int sc_gnm_eigen_f64(sc_ctx* ctx, const double* coord, int64_t n_atoms, const sc
 int sc_anm_eigen_range_f64(sc_ctx* ctx, const double* coord, int64_t n_atoms, const sc_ff_desc* ff,
                            const sc_patch_desc* patch, const double* inv_sqrt_mass, int64_t il, int64_t iu,
                            double* w, double* v);
+/* Same, eigenvalue window (vl, vu] of the 3n x 3n Hessian (scipy's subset_by_value; results as sc_eigh_window_f64). */
+int sc_anm_eigen_window_f64(sc_ctx* ctx, const double* coord, int64_t n_atoms, const sc_ff_desc* ff,
+                            const sc_patch_desc* patch, const double* inv_sqrt_mass, double vl, double vu,
+                            int want_vectors, int64_t* m, double** w, double** v);
 
 /* ---- device-resident / batched entry points (bench + multi-structure sharding) ------------
  * All pointers are device pointers on the context's device.  Work is enqueued on the context's
@@ -262,6 +276,13 @@ int sc_dev_eigh_f64(sc_ctx* ctx, double* d_a, int64_t n, int64_t batch, double* 
 /* Partial spectrum of `batch` matrices: d_w (batch, m), d_v NULL or (batch, m, n). d_a is destroyed. */
 int sc_dev_eigh_range_f64(sc_ctx* ctx, double* d_a, int64_t n, int64_t batch, int64_t il, int64_t iu,
                           double* d_w, double* d_v);
+/* Eigenvalue window (vl, vu] of `batch` matrices (scipy's subset_by_value semantics, as sc_eigh_window_f64), enqueue only.
+ * Every matrix gets a slot of K = capacity (1 <= K <= n) eigenpairs: d_w (batch, K), d_v NULL or (batch, K, n), and
+ * d_count (batch,) int64 receives the TRUE count of every window.  A slot holds the first min(count, K) eigenpairs of its
+ * window in ascending order, then NaN in d_w and zero rows in d_v.  A matrix with a NaN / Inf entry gets count 0 (and is
+ * reported as sc_dev_eigh_f64 reports it).  d_a is destroyed. */
+int sc_dev_eigh_window_f64(sc_ctx* ctx, double* d_a, int64_t n, int64_t batch, double vl, double vu, int64_t capacity,
+                           double* d_w, double* d_v, int64_t* d_count);
 
 /* Tridiagonalisation path of the eigensolver: -1 automatic (default: two-stage when n >= 512 and
  * batch * n^2 >= max(2e7, 1e4 n), else one-stage), 0 always one-stage, 1 two-stage whenever n >= 256.  Both give the

@@ -45,6 +45,7 @@ EXPORTED_SYMBOLS = [
     "sc_modes_msf", "sc_modes_dcc", "sc_modes_prs", "sc_ctx_set_two_stage", "sc_last_eigh_phase_ms",
     "sc_ctx_get_counter", "sc_batch_plan_create", "sc_batch_plan_assemble_f64", "sc_batch_plan_order",
     "sc_batch_plan_destroy", "sc_batch_plan_contacts", "sc_batch_plan_pairs", "sc_batch_plan_fill_from_pairs_f64",
+    "sc_eigh_window_f64", "sc_anm_eigen_window_f64", "sc_dev_eigh_window_f64",
 ]
 
 
@@ -172,6 +173,10 @@ def lib():
         "sc_pinvh_f64": (i32, [vp, vp, i64, dbl, vp]),
         "sc_anm_eigen_range_f64": (i32, [vp, vp, i64, P(FFDesc), P(PatchDesc), vp, i64, i64, vp, vp]),
         "sc_dev_eigh_range_f64": (i32, [vp, vp, i64, i64, i64, i64, vp, vp]),
+        "sc_eigh_window_f64": (i32, [vp, vp, i64, dbl, dbl, i32, P(i64), P(vp), P(vp)]),
+        "sc_anm_eigen_window_f64": (i32, [vp, vp, i64, P(FFDesc), P(PatchDesc), vp, dbl, dbl, i32, P(i64), P(vp),
+                                          P(vp)]),
+        "sc_dev_eigh_window_f64": (i32, [vp, vp, i64, i64, dbl, dbl, i64, vp, vp, vp]),
         "sc_ctx_set_profiling": (i32, [vp, i32]),
         "sc_ctx_set_two_stage": (i32, [vp, i32]),
         "sc_last_eigh_timings": (i32, [vp, P(dbl)]),
@@ -449,6 +454,39 @@ def host_array(shape):
     block = (C.c_double * count).from_address(address)
     weakref.finalize(block, _pin_release, address, nbytes)   # runs when the last array / view on the block is gone
     return np.frombuffer(block, dtype=np.float64).reshape(shape)
+
+
+def _adopt_host_block(address, shape):
+    """
+    A C-contiguous float64 array on a page-locked block that the library allocated with sc_host_alloc (a result whose size
+    only the call knew).  The array owns the block: when it and its views are gone, the block joins the pool above.
+    """
+    global _pin_live
+    import weakref
+
+    count = int(np.prod(shape))
+    nbytes = 8 * count
+    with _pin_lock:
+        _pin_live += nbytes
+    block = (C.c_double * count).from_address(address)
+    weakref.finalize(block, _pin_release, address, nbytes)
+    return np.frombuffer(block, dtype=np.float64).reshape(shape)
+
+
+def solve_window(ctx, fn, args, n, want_vectors):
+    """
+    Call one of the host window entries (``sc_eigh_window_f64`` / ``sc_anm_eigen_window_f64``): ``args`` are its arguments
+    up to the bounds.  Returns (w (m,), v (m, n) or None) on the blocks the call allocated.
+    """
+    m = C.c_int64(0)
+    pw, pv = C.c_void_p(), C.c_void_p()
+    ctx.check(fn(*args, 1 if want_vectors else 0, C.byref(m), C.byref(pw), C.byref(pv)))
+    m = int(m.value)
+    if m == 0:
+        return np.empty(0), (np.empty((0, n)) if want_vectors else None)
+    w = _adopt_host_block(pw.value, (m,))
+    v = _adopt_host_block(pv.value, (m, n)) if want_vectors else None
+    return w, v
 
 
 def make_ff_desc(kind, cutoff_distance):

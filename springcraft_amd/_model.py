@@ -207,7 +207,7 @@ class ElasticNetworkModel:
         matrix = self._get_matrix()
         return _hip.Modes.from_matrix(_hip.context(), matrix, self._dim)
 
-    def _eigen_device(self, subset_by_index=None):
+    def _eigen_device(self, subset_by_index=None, subset_by_value=None):
         """
         (eig_values, eig_vectors[rows]) on the device.  When the matrix has not been materialised
         on the host and the force field is evaluated on device, assembly and eigensolve are fused
@@ -215,6 +215,24 @@ class ElasticNetworkModel:
         matrix (possibly user-assigned, anm.py:120-130) is solved as it is.
         """
         from . import nma
+
+        window = nma._value_window(subset_by_value, subset_by_index)
+        if window is not None:
+            if self._matrix is None and self._covariance is None and self._dim == 3:
+                ff_desc, patch, fused = device_plan(self._ff)
+                if fused:
+                    coord = _validated_coord(self._coord, self._ff)
+                    n = len(coord)
+                    keep = []
+                    patch_desc = _normalised_patch(patch, n, keep)
+                    pd = C.byref(patch_desc) if patch_desc is not None else None
+                    ism = None
+                    if self._inv_sqrt_mass is not None:
+                        ism = np.ascontiguousarray(self._inv_sqrt_mass, dtype=np.float64)
+                    ctx = _hip.context()
+                    args = (ctx.handle, _hip.ptr(coord), n, C.byref(ff_desc), pd, _hip.ptr(ism)) + window
+                    return _hip.solve_window(ctx, _hip.lib().sc_anm_eigen_window_f64, args, 3 * n, True)
+            return nma.eigh(self._get_matrix(), subset_by_value=window)
 
         if subset_by_index is not None:
             lo, hi = (int(x) for x in subset_by_index)

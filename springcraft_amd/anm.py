@@ -53,12 +53,13 @@ class ANM(ElasticNetworkModel):
     def covariance(self, value):
         self._set_covariance(value)
 
-    def eigen(self, subset_by_index=None):
+    def eigen(self, subset_by_index=None, subset_by_value=None):
         """
         Eigenvalues (ascending, shape (3n,)) and eigenvectors (rows, shape (3n,3n)) of the
         Hessian; the first six belong to rigid-body motions (anm.py:150-167).
+        ``subset_by_index`` / ``subset_by_value``: a part of the spectrum only, see :func:`nma.eigen`.
         """
-        return nma.eigen(self, subset_by_index)
+        return nma.eigen(self, subset_by_index, subset_by_value)
 
     def normal_mode(self, index, amplitude, frames, movement="sine"):
         """Displacements (frames, n, 3) animating mode ``index`` (anm.py:169-207)."""

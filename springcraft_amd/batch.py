@@ -41,11 +41,28 @@ class DeviceBatchSolver:
     ``ANM.hessian`` / ``GNM.kirchhoff`` do (anm.py:89-94,112-113; gnm.py:85-87,104-105).
     ``subset_by_index=(lo, hi)``: only the eigenpairs with ascending index lo..hi (inclusive) through the
     partial-spectrum path (no reference counterpart; BASELINE config 5): ``w`` is (batch, m), ``v`` (batch, m, n).
+    ``subset_by_value=(vl, vu)`` with ``max_modes=K``: the eigenpairs whose eigenvalues lie in (vl, vu] (scipy's
+    semantics, see :func:`nma.eigh`), counted per structure on the device, so :meth:`solve` still only enqueues.  ``w`` is
+    (batch, K), ``v`` (batch, K, n) and ``counts`` an int64 tensor (batch,) of the true counts: structure b's first
+    ``min(counts[b], K)`` rows are its window in ascending order, the rest NaN (``w``) / zero (``v``).  :meth:`finish`
+    raises ValueError for structures whose window held more than K eigenpairs (their slots keep the K lowest).
     Structures of different sizes, patched or tabulated force fields: :class:`RaggedBatchSolver`.
     """
 
     def __init__(self, n_atoms, batch, force_field, dim=3, device=None, want_vectors=True, masses=None,
-                 subset_by_index=None):
+                 subset_by_index=None, subset_by_value=None, max_modes=None):
+        from .nma import _value_window
+
+        m = int(n_atoms) * int(dim)
+        self.window = _value_window(subset_by_value, subset_by_index)
+        if self.window is None and max_modes is not None:
+            raise ValueError("max_modes applies to subset_by_value only")
+        if self.window is not None:
+            if max_modes is None:
+                raise ValueError("subset_by_value needs max_modes, the number of eigenpairs kept per structure")
+            if not 1 <= int(max_modes) <= m:
+                raise ValueError(f"max_modes {max_modes} outside 1..{m}")
+            max_modes = int(max_modes)
         import torch
 
         self.torch = torch
@@ -70,6 +87,11 @@ class DeviceBatchSolver:
                 raise ValueError(f"subset_by_index {subset_by_index} outside 0..{m - 1}")
             self.subset = (lo, hi)
             nvec = hi - lo + 1
+        self.max_modes = max_modes
+        self.counts = None
+        if self.window is not None:
+            nvec = max_modes
+            self.counts = torch.zeros((self.batch,), dtype=torch.int64, device=self.device)
         self.matrix = torch.empty((self.batch, m, m), dtype=f64, device=self.device)
         self.w = torch.empty((self.batch, nvec), dtype=f64, device=self.device)
         self.v = torch.empty((self.batch, nvec, m), dtype=f64, device=self.device) if want_vectors else None
@@ -104,7 +126,12 @@ class DeviceBatchSolver:
     def eigh(self):
         """Eigendecompose self.matrix (destroyed) -> (w, v) tensors; v rows are modes (nma.py:63)."""
         vp = C.c_void_p(self.v.data_ptr()) if self.v is not None else None
-        if self.subset is None:
+        if self.window is not None:
+            self.ctx.check(self._L.sc_dev_eigh_window_f64(self.ctx.handle, C.c_void_p(self.matrix.data_ptr()), self.m,
+                                                          self.batch, self.window[0], self.window[1], self.max_modes,
+                                                          C.c_void_p(self.w.data_ptr()), vp,
+                                                          C.c_void_p(self.counts.data_ptr())))
+        elif self.subset is None:
             self.ctx.check(self._L.sc_dev_eigh_f64(self.ctx.handle, C.c_void_p(self.matrix.data_ptr()), self.m,
                                                    self.batch, C.c_void_p(self.w.data_ptr()), vp))
         else:
@@ -126,9 +153,17 @@ class DeviceBatchSolver:
         Wait for the solves enqueued so far and raise what they could only find out on the device:
         ``np.linalg.LinAlgError`` -- what ``np.linalg.eigh`` raises at nma.py:61 -- if a matrix held a NaN / Inf entry
         (its eigenvalues come back NaN, the other structures of the batch are unaffected) or a tridiagonal QL iteration
-        did not converge.  The condition is reported once.  Returns (w, v).
+        did not converge.  The condition is reported once.  With ``subset_by_value``, then ValueError naming every structure
+        whose window held more than ``max_modes`` eigenpairs.  Returns (w, v).
         """
         self.ctx.synchronize()
+        if self.window is not None:
+            counts = self.counts.cpu().numpy()
+            over = np.nonzero(counts > self.max_modes)[0]
+            if len(over):
+                which = ", ".join(f"{b} ({counts[b]})" for b in over)
+                raise ValueError(f"the eigenvalue window {self.window} holds more than max_modes = {self.max_modes} "
+                                 f"eigenpairs for structure(s) {which}; their slots hold the {self.max_modes} lowest")
         return self.w, self.v
 
 

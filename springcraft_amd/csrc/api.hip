@@ -143,6 +143,19 @@ int sc_reserve_pinv(sc_ctx* ctx, size_t bytes) {
   return SC_OK;
 }
 
+int sc_reserve_win(sc_ctx* ctx, size_t bytes) {
+  if (bytes <= ctx->win_ws_bytes) return SC_OK;
+  if (ctx->win_ws) {
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SC_HIP(ctx, hipFree(ctx->win_ws));
+    ctx->win_ws = nullptr;
+    ctx->win_ws_bytes = 0;
+  }
+  SC_HIP(ctx, hipMalloc(&ctx->win_ws, bytes));
+  ctx->win_ws_bytes = bytes;
+  return SC_OK;
+}
+
 int sc_reserve_dc_aux(sc_ctx* ctx, size_t bytes) {
   if (bytes <= ctx->dc_aux_bytes) return SC_OK;
   if (ctx->dc_aux) {
@@ -370,6 +383,7 @@ void sc_ctx_destroy(sc_ctx* ctx) {
   if (ctx->scratch) (void)hipFree(ctx->scratch);
   if (ctx->dc_aux) (void)hipFree(ctx->dc_aux);
   if (ctx->pinv_ws) (void)hipFree(ctx->pinv_ws);
+  if (ctx->win_ws) (void)hipFree(ctx->win_ws);
   if (ctx->d_status) (void)hipFree(ctx->d_status);
   if (ctx->d_zeros) (void)hipFree(ctx->d_zeros);
   if (ctx->d_chase_ctl) (void)hipFree(ctx->d_chase_ctl);
@@ -768,6 +782,88 @@ int sc_dev_eigh_range_f64(sc_ctx* ctx, double* d_a, int64_t n, int64_t batch, in
   if (n <= 0 || batch <= 0 || !d_a || !d_w) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
   SC_HIP(ctx, hipSetDevice(ctx->device));
   return eigh_range_batched_async(ctx, d_a, n, batch, il, iu, d_w, d_v);
+}
+
+// Results of a one-matrix window solve (device, in ctx->win_ws) -> page-locked host blocks of exactly (m,) and (m, n)
+// that the caller owns (sc_host_free); m = 0: none, *w = *v = NULL.
+static int window_results_to_host(sc_ctx* ctx, int64_t m, int64_t n, const double* d_w, const double* d_v, double** w,
+                                  double** v) {
+  if (m == 0) return SC_OK;
+  void* hw = nullptr;
+  void* hv = nullptr;
+  int rc = sc_host_alloc((size_t)m * 8, &hw);
+  if (rc == SC_OK && d_v) rc = sc_host_alloc((size_t)m * n * 8, &hv);
+  if (rc == SC_OK && hipMemcpyAsync(hw, d_w, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = SC_ERR_HIP;
+  if (rc == SC_OK && d_v && hipMemcpyAsync(hv, d_v, (size_t)m * n * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    rc = SC_ERR_HIP;
+  if (rc == SC_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = SC_ERR_HIP;
+  if (rc != SC_OK) {
+    (void)hipGetLastError();
+    (void)sc_host_free(hw);
+    (void)sc_host_free(hv);
+    return sc_set_error(ctx, rc, "cannot return the %lld eigenpairs of the window", (long long)m);
+  }
+  *w = (double*)hw;
+  if (v) *v = (double*)hv;
+  return SC_OK;
+}
+
+static int check_window_outputs(sc_ctx* ctx, int want_vectors, int64_t* m, double** w, double** v) {
+  if (!m || !w || (want_vectors && !v)) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  *m = 0;
+  *w = nullptr;
+  if (v) *v = nullptr;
+  return SC_OK;
+}
+
+int sc_eigh_window_f64(sc_ctx* ctx, const double* a, int64_t n, double vl, double vu, int want_vectors, int64_t* m,
+                       double** w, double** v) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  SC_TRY(check_window_outputs(ctx, want_vectors, m, w, v));
+  if (n <= 0 || !a) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t elems = (size_t)n * n;
+  SC_TRY(sc_reserve_scratch(ctx, elems * 8 + 4096));
+  Bump bump{(char*)ctx->scratch};
+  double* d_a = bump.take<double>(elems);
+  SC_HIP(ctx, hipMemcpyAsync(d_a, a, elems * 8, hipMemcpyHostToDevice, ctx->stream));
+  int64_t mm = 0;
+  double *d_w = nullptr, *d_v = nullptr;
+  SC_TRY(eigh_window(ctx, d_a, n, vl, vu, want_vectors != 0, &mm, &d_w, &d_v));
+  SC_TRY(window_results_to_host(ctx, mm, n, d_w, d_v, w, want_vectors ? v : nullptr));
+  *m = mm;
+  return SC_OK;
+}
+
+int sc_anm_eigen_window_f64(sc_ctx* ctx, const double* coord, int64_t n, const sc_ff_desc* ff,
+                            const sc_patch_desc* patch, const double* inv_sqrt_mass, double vl, double vu,
+                            int want_vectors, int64_t* m, double** w, double** v) {
+  SC_TRY(check_coord_args(ctx, coord, n));
+  SC_TRY(check_ff(ctx, ff));
+  SC_TRY(check_window_outputs(ctx, want_vectors, m, w, v));
+  if (n <= 0) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const int64_t dim3n = 3 * n;
+  const size_t elems = (size_t)dim3n * dim3n;
+  Staged st;
+  Bump bump{};
+  SC_TRY(stage_inputs(ctx, coord, n, ff, patch, inv_sqrt_mass, elems * 8 + 4096, st, bump));
+  double* d_m = bump.take<double>(elems);
+  SC_TRY(launch_hessian(ctx, st.d_coord, n, 1, st.ff_dev, st.has_patch ? &st.patch : nullptr, st.d_w, d_m));
+  int64_t mm = 0;
+  double *d_w = nullptr, *d_v = nullptr;
+  SC_TRY(eigh_window(ctx, d_m, dim3n, vl, vu, want_vectors != 0, &mm, &d_w, &d_v));
+  SC_TRY(window_results_to_host(ctx, mm, dim3n, d_w, d_v, w, want_vectors ? v : nullptr));
+  *m = mm;
+  return SC_OK;
+}
+
+int sc_dev_eigh_window_f64(sc_ctx* ctx, double* d_a, int64_t n, int64_t batch, double vl, double vu, int64_t capacity,
+                           double* d_w, double* d_v, int64_t* d_count) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  if (n <= 0 || batch <= 0 || !d_a || !d_w || !d_count) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return eigh_window_batched_async(ctx, d_a, n, batch, vl, vu, capacity, d_w, d_v, d_count);
 }
 
 static int enm_eigen_host(sc_ctx* ctx, const double* coord, int64_t n, const sc_ff_desc* ff,

@@ -41,6 +41,10 @@ struct sc_ctx {
   // eigenvector / scaled-eigenvector buffers of pinvh_device (covariance properties), alive across its eigensolve
   void* pinv_ws = nullptr;
   size_t pinv_ws_bytes = 0;
+  // what a one-matrix value-window solve sizes only after its count (eigh_window): the inverse-iteration workspace and the
+  // m eigenpairs.  Growing `ws` at that point would move the tridiagonalisation's slabs, which are still needed
+  void* win_ws = nullptr;
+  size_t win_ws_bytes = 0;
 
   // host -> device uploads of descriptor tables without a stream synchronisation: the tables are copied into this
   // pinned arena first (sc_stage_upload) and the arena is recycled once the event recorded at the end of the solve
@@ -185,6 +189,7 @@ int sc_side_streams(sc_ctx* ctx, int count);   // makes sure side_streams / side
 int sc_reserve_scratch(sc_ctx* ctx, size_t bytes);
 int sc_reserve_dc_aux(sc_ctx* ctx, size_t bytes);
 int sc_reserve_pinv(sc_ctx* ctx, size_t bytes);
+int sc_reserve_win(sc_ctx* ctx, size_t bytes);
 // d_dst <- bytes at h_src, enqueued on ctx->stream; h_src may be released as soon as the call returns
 int sc_stage_upload(sc_ctx* ctx, void* d_dst, const void* h_src, size_t bytes);
 // end of a solve that used sc_stage_upload: the arena may be reused when everything enqueued so far has run
@@ -264,6 +269,14 @@ int eigh_range_batched(sc_ctx* ctx, double* d_a, int64_t n, int64_t batch, int64
                        double* d_w, double* d_v);
 int eigh_range_batched_async(sc_ctx* ctx, double* d_a, int64_t n, int64_t batch, int64_t il, int64_t iu,
                              double* d_w, double* d_v);
+// Eigenvalue window (vl, vu] (scipy's subset_by_value): K slots per matrix, d_w (batch, K), d_v nullptr or (batch, K, n),
+// d_count (batch) int64 true counts (may be nullptr); a slot holds the window's first min(count, K) eigenpairs, then NaN /
+// zero rows.  Only enqueues.
+int eigh_window_batched_async(sc_ctx* ctx, double* d_a, int64_t n, int64_t batch, double vl, double vu, int64_t K,
+                              double* d_w, double* d_v, int64_t* d_count);
+// One matrix, synchronising: *m eigenpairs of the window into ctx->win_ws (*d_w (m), *d_v (m, n) or nullptr).
+int eigh_window(sc_ctx* ctx, double* d_a, int64_t n, double vl, double vu, bool vectors, int64_t* m, double** d_w,
+                double** d_v);
 // Hermitian pseudo-inverse of the (n,n) matrix d_a (destroyed) into d_out, numpy.linalg.pinv(hermitian=True) rule.
 int pinvh_device(sc_ctx* ctx, double* d_a, int64_t n, double rcond, double* d_out);
 

@@ -348,105 +348,71 @@ int eigh_batched(sc_ctx* ctx, double* d_a, int64_t n, int64_t batch, double* d_w
 
 
 // ---- partial spectrum --------------------------------------------------------------------------------------
-int eigh_range_batched_async(sc_ctx* ctx, double* d_a, int64_t n64, int64_t batch64, int64_t il64, int64_t iu64,
-                             double* d_w, double* d_v) {
-  if (n64 > 46000) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "matrix order %lld too large", (long long)n64);
-  const int n = (int)n64, batch = (int)batch64, il = (int)il64, iu = (int)iu64;
-  if (il < 0 || iu < il || iu >= n)
-    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad eigenvalue index range [%d, %d] for order %d", il, iu, n);
-  const int m = iu - il + 1;
-  hipStream_t st = ctx->stream;
-  const long long stride_a = (long long)n * n;
+namespace {
 
-  // workspace: tri slab | [sb slab | diamond offsets] | stein | bt slab | VT (n x n) | descriptors
+// Workspace of a partial-spectrum solve: tri slab | [sb slab | diamond offsets] | [stein] | [bt slab | VT (n x n)] |
+// descriptors | [window counts | copy of w].  m_stein: columns of the inverse-iteration workspace held here (0: none, for
+// values only, or when the caller allocates it itself); window_k: slots of a value window (0: an index range).
+struct PartialPlan {
   TriLayout TL;
   BtLayout BL;
   SbLayout SL;
-  const bool two = two_stage_for(ctx, n, batch);
+  bool two = false, vectors = false;
+  int npanels = 0, n_tri_desc = 0;
+  size_t off_tri = 0, off_sb = 0, off_dia = 0, off_stein = 0, off_bt = 0, off_vt = 0, off_desc = 0, off_win = 0,
+         off_wcopy = 0, total = 0;
+};
+
+PartialPlan make_partial_plan(const sc_ctx* ctx, int n, int batch, bool vectors, int m_stein, int window_k) {
+  PartialPlan P;
+  P.vectors = vectors;
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
-  const size_t off_tri = take(tri_slab_doubles(n, &TL) * 8 * batch);
-  const int npanels = (n + kNb - 1) / kNb;
-  size_t off_stein = 0, off_bt = 0, off_vt = 0, off_sb = 0, off_dia = 0;
+  P.off_tri = take(tri_slab_doubles(n, &P.TL) * 8 * batch);
+  P.npanels = (n + kNb - 1) / kNb;
+  P.n_tri_desc = P.npanels * batch;
+  P.two = two_stage_for(ctx, n, batch);
   int n_bt = 0;
-  int n_tri_desc = npanels * batch;
-  if (two) {
-    off_sb = take(sb_slab_doubles(n, batch, &SL) * 8 * batch);
-    off_dia = take(sizeof(int) * ((size_t)n / 64 + 8));
-    n_tri_desc = std::max(n_tri_desc, sb_desc_count(n, batch));
+  if (P.two) {
+    P.off_sb = take(sb_slab_doubles(n, batch, &P.SL) * 8 * batch);
+    P.off_dia = take(sizeof(int) * ((size_t)n / 64 + 8));
+    P.n_tri_desc = std::max(P.n_tri_desc, sb_desc_count(n, batch));
   }
-  if (d_v) {
-    off_stein = take(stein_workspace_doubles(n, m) * 8 * batch);
-    off_bt = take(bt_slab_doubles(n, &BL) * 8 * batch);
-    off_vt = take((size_t)n * n * 8 * batch);
+  if (vectors) {
+    if (m_stein > 0) P.off_stein = take(stein_workspace_doubles(n, m_stein) * 8 * batch);
+    P.off_bt = take(bt_slab_doubles(n, &P.BL) * 8 * batch);
+    P.off_vt = take((size_t)n * n * 8 * batch);
     n_bt = bt_desc_count(n, batch);
   }
-  const size_t n_desc = (size_t)n_tri_desc + n_bt + 2 * (size_t)batch + 8;
-  const size_t off_desc = take(sizeof(GemmDesc) * n_desc);
-  SC_TRY(sc_reserve_ws(ctx, off));
-  char* base = (char*)ctx->ws;
-  double* tri_ws = (double*)(base + off_tri);
-  double* sb_ws = (double*)(base + off_sb);
-  GemmDesc* descs = (GemmDesc*)(base + off_desc);
+  const size_t n_desc = (size_t)P.n_tri_desc + n_bt + 2 * (size_t)batch + 8;
+  P.off_desc = take(sizeof(GemmDesc) * n_desc);
+  if (window_k > 0) {
+    P.off_win = take(sizeof(WinCount) * batch);
+    P.off_wcopy = take(sizeof(double) * batch * (size_t)window_k);
+  }
+  P.total = off;
+  return P;
+}
 
-  std::vector<GemmDesc> h((size_t)npanels * batch);
-  // profiled solve: [0] tridiagonalisation, [1] bisection + inverse iteration, [2] back-transformation, and as in
-  // eigh_batched [3] / [4] = band reduction / bulge chasing (two-stage) or SYMV / SYR2K sums, [5] = k_bt2_apply
+// Profiled solve: [0] tridiagonalisation, [1] bisection + inverse iteration, [2] back-transformation, and as in
+// eigh_batched [3] / [4] = band reduction / bulge chasing (two-stage) or SYMV / SYR2K sums, [5] = k_bt2_apply
+struct PartialProfile {
+  sc_ctx* ctx;
   ScopedEvents<4> ev;
-  const bool prof = ctx->profiling;
   float ms_a = 0.f, ms_b = 0.f, ms_bt2 = 0.f;
-  if (prof) {
-    ctx->phases.clear();
-    for (auto& e : ev) SC_HIP(ctx, hipEventCreate(&e));
-    SC_HIP(ctx, hipEventRecord(ev[0], st));
-  }
-  SC_TRY(prepare_matrix_batched(ctx, d_a, stride_a, n, batch, tri_ws, TL));
-  if (two) {
-    SC_TRY(sytrd_2stage_batched(ctx, d_a, stride_a, n, batch, tri_ws, TL, sb_ws, SL, (int*)(base + off_dia), descs,
-                                &ms_a, &ms_b));
-  } else {
-    for (int p = 0; p < npanels; ++p) {
-      const int pend = std::min((p + 1) * kNb, n);
-      for (int b = 0; b < batch; ++b) {
-        double* ws = tri_ws + (size_t)b * TL.slab;
-        GemmDesc D{};
-        D.a = ws + TL.vw + pend; D.sa_i = 1; D.sa_k = n;
-        D.b = ws + TL.wv + pend; D.sb_k = n; D.sb_j = 1;
-        D.c = d_a + (size_t)b * stride_a + (size_t)pend * n + pend; D.ldc = n;
-        D.m = n - pend; D.n = n - pend; D.k = 2 * kNb;
-        D.alpha = -1.0; D.beta = 1.0;
-        D.lower_only = 1;
-        h[(size_t)p * batch + b] = D;
-      }
+  explicit PartialProfile(sc_ctx* c) : ctx(c) {}
+  int mark(int i) {
+    if (!ctx->profiling) return SC_OK;
+    if (i == 0) {
+      ctx->phases.clear();
+      for (auto& e : ev) SC_HIP(ctx, hipEventCreate(&e));
     }
-    SC_TRY(sc_stage_upload(ctx, descs, h.data(), h.size() * sizeof(GemmDesc)));
-    SC_TRY(tridiag_batched(ctx, d_a, stride_a, n, batch, tri_ws, TL, descs, &ms_a, &ms_b));
+    SC_HIP(ctx, hipEventRecord(ev[i], ctx->stream));
+    return SC_OK;
   }
-  if (prof) SC_HIP(ctx, hipEventRecord(ev[1], st));
-  GemmDesc* d2 = descs + (size_t)n_tri_desc;
-  if (!d_v) {
-    SC_TRY(stein_batched(ctx, n, batch, tri_ws, TL, il, iu, d_w, m, nullptr, 0, nullptr, d2));
-    SC_TRY(unscale_values_batched(ctx, d_w, m, m, batch, tri_ws, TL));
-    if (prof) SC_HIP(ctx, hipEventRecord(ev[2], st));
-  } else {
-    const long long stride_x = (long long)n * m;
-    SC_TRY(stein_batched(ctx, n, batch, tri_ws, TL, il, iu, d_w, m, d_v, stride_x, (double*)(base + off_stein), d2));
-    SC_TRY(unscale_values_batched(ctx, d_w, m, m, batch, tri_ws, TL));
-    if (prof) SC_HIP(ctx, hipEventRecord(ev[2], st));
-    if (two) {
-      PhaseTimer t_tf(ctx, "dia_tfactor", st);
-      t_tf.start();
-      SC_TRY(bt2_prepare(ctx, n, batch, sb_ws, SL, st));
-      t_tf.stop();
-      SC_TRY(bt2_batched(ctx, n, batch, sb_ws, SL, (const int*)(base + off_dia), d_v, stride_x, m, &ms_bt2));
-      t_tf.finish();
-    }
-    // the back-transformation indexes its scratch with the matrix stride: VT lives in an n x n buffer per matrix
-    SC_TRY(backtransform_batched(ctx, d_a, stride_a, n, batch, tri_ws, TL, (double*)(base + off_bt), BL, d_v,
-                                 stride_x, m, (double*)(base + off_vt), d2 + 2 * batch, two ? sb_band_width() : 1));
-  }
-  if (prof) {
-    SC_HIP(ctx, hipEventRecord(ev[3], st));
+  int finish(bool two, bool vectors) {
+    if (!ctx->profiling) return SC_OK;
+    SC_TRY(mark(3));
     SC_HIP(ctx, hipEventSynchronize(ev[3]));
     float t01 = 0, t12 = 0, t23 = 0;
     SC_HIP(ctx, hipEventElapsedTime(&t01, ev[0], ev[1]));
@@ -457,9 +423,119 @@ int eigh_range_batched_async(sc_ctx* ctx, double* d_a, int64_t n64, int64_t batc
     ctx->last_timings[2] = t23;
     ctx->last_timings[3] = ms_a;
     ctx->last_timings[4] = ms_b;
-    ctx->last_timings[5] = two ? (d_v ? ms_bt2 : 1e-9) : 0.0;
+    ctx->last_timings[5] = two ? (vectors ? ms_bt2 : 1e-9) : 0.0;
+    return SC_OK;
   }
+};
+
+// mirror, scaling and tridiagonalisation of the batch into the plan's tri slab
+int partial_tridiagonalise(sc_ctx* ctx, double* d_a, int n, int batch, const PartialPlan& P, char* base,
+                           PartialProfile& prof) {
+  const long long stride_a = (long long)n * n;
+  double* tri_ws = (double*)(base + P.off_tri);
+  GemmDesc* descs = (GemmDesc*)(base + P.off_desc);
+  SC_TRY(prof.mark(0));
+  SC_TRY(prepare_matrix_batched(ctx, d_a, stride_a, n, batch, tri_ws, P.TL));
+  if (P.two) {
+    SC_TRY(sytrd_2stage_batched(ctx, d_a, stride_a, n, batch, tri_ws, P.TL, (double*)(base + P.off_sb), P.SL,
+                                (int*)(base + P.off_dia), descs, &prof.ms_a, &prof.ms_b));
+  } else {
+    std::vector<GemmDesc> h((size_t)P.npanels * batch);
+    for (int p = 0; p < P.npanels; ++p) {
+      const int pend = std::min((p + 1) * kNb, n);
+      for (int b = 0; b < batch; ++b) {
+        double* ws = tri_ws + (size_t)b * P.TL.slab;
+        GemmDesc D{};
+        D.a = ws + P.TL.vw + pend; D.sa_i = 1; D.sa_k = n;
+        D.b = ws + P.TL.wv + pend; D.sb_k = n; D.sb_j = 1;
+        D.c = d_a + (size_t)b * stride_a + (size_t)pend * n + pend; D.ldc = n;
+        D.m = n - pend; D.n = n - pend; D.k = 2 * kNb;
+        D.alpha = -1.0; D.beta = 1.0;
+        D.lower_only = 1;
+        h[(size_t)p * batch + b] = D;
+      }
+    }
+    SC_TRY(sc_stage_upload(ctx, descs, h.data(), h.size() * sizeof(GemmDesc)));
+    SC_TRY(tridiag_batched(ctx, d_a, stride_a, n, batch, tri_ws, P.TL, descs, &prof.ms_a, &prof.ms_b));
+  }
+  return prof.mark(1);
+}
+
+// bisection, inverse iteration and back-transformation of m eigenpairs per matrix (il.., or from d_win[b].start);
+// d_stein: stein_workspace_doubles(n, m) * batch doubles when vectors are wanted
+int partial_eigenpairs(sc_ctx* ctx, double* d_a, int n, int batch, const PartialPlan& P, char* base, int il, int m,
+                       const WinCount* d_win, double* d_w, double* d_v, double* d_stein, PartialProfile& prof) {
+  const long long stride_a = (long long)n * n;
+  double* tri_ws = (double*)(base + P.off_tri);
+  GemmDesc* d2 = (GemmDesc*)(base + P.off_desc) + (size_t)P.n_tri_desc;
+  hipStream_t st = ctx->stream;
+  const int iu = il + m - 1;
+  if (!d_v) {
+    SC_TRY(stein_batched(ctx, n, batch, tri_ws, P.TL, il, iu, d_w, m, nullptr, 0, nullptr, d2, d_win));
+    SC_TRY(unscale_values_batched(ctx, d_w, m, m, batch, tri_ws, P.TL));
+    return prof.mark(2);
+  }
+  const long long stride_x = (long long)n * m;
+  SC_TRY(stein_batched(ctx, n, batch, tri_ws, P.TL, il, iu, d_w, m, d_v, stride_x, d_stein, d2, d_win));
+  SC_TRY(unscale_values_batched(ctx, d_w, m, m, batch, tri_ws, P.TL));
+  SC_TRY(prof.mark(2));
+  if (P.two) {
+    double* sb_ws = (double*)(base + P.off_sb);
+    PhaseTimer t_tf(ctx, "dia_tfactor", st);
+    t_tf.start();
+    SC_TRY(bt2_prepare(ctx, n, batch, sb_ws, P.SL, st));
+    t_tf.stop();
+    SC_TRY(bt2_batched(ctx, n, batch, sb_ws, P.SL, (const int*)(base + P.off_dia), d_v, stride_x, m, &prof.ms_bt2));
+    t_tf.finish();
+  }
+  // the back-transformation indexes its scratch with the matrix stride: VT lives in an n x n buffer per matrix
+  return backtransform_batched(ctx, d_a, stride_a, n, batch, tri_ws, P.TL, (double*)(base + P.off_bt), P.BL, d_v,
+                               stride_x, m, (double*)(base + P.off_vt), d2 + 2 * batch, P.two ? sb_band_width() : 1);
+}
+
+// one solve of the batch: eigenpairs il .. il + m - 1 of every matrix, or (window) the K = m slots of a value window
+struct ValueWindow {
+  double vl, vu;
+  long long* d_count;
+};
+
+int partial_batched_async(sc_ctx* ctx, double* d_a, int n, int batch, int il, int m, const ValueWindow* window,
+                          double* d_w, double* d_v) {
+  const PartialPlan P = make_partial_plan(ctx, n, batch, d_v != nullptr, m, window ? m : 0);
+  SC_TRY(sc_reserve_ws(ctx, P.total));
+  char* base = (char*)ctx->ws;
+  PartialProfile prof(ctx);
+  SC_TRY(partial_tridiagonalise(ctx, d_a, n, batch, P, base, prof));
+  WinCount* d_win = nullptr;
+  if (window) {
+    d_win = (WinCount*)(base + P.off_win);
+    SC_TRY(window_count_batched(ctx, batch, (const double*)(base + P.off_tri), P.TL, window->vl, window->vu, m, d_win,
+                                window->d_count));
+  }
+  SC_TRY(partial_eigenpairs(ctx, d_a, n, batch, P, base, il, m, d_win, d_w, d_v, (double*)(base + P.off_stein), prof));
+  if (window)   // (the VT buffer of the back-transformation is free again: the copy of v goes there)
+    SC_TRY(window_compact_batched(ctx, n, batch, m, d_win, d_w, d_v, (double*)(base + P.off_wcopy),
+                                  (double*)(base + P.off_vt)));
+  SC_TRY(prof.finish(P.two, d_v != nullptr));
   return sc_stage_end(ctx);
+}
+
+int check_window(sc_ctx* ctx, double vl, double vu) {
+  if (!(vl < vu))   // (also a NaN bound)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "eigenvalue window (%g, %g] is empty or not a number: need vl < vu", vl,
+                        vu);
+  return SC_OK;
+}
+
+}  // namespace
+
+int eigh_range_batched_async(sc_ctx* ctx, double* d_a, int64_t n64, int64_t batch64, int64_t il64, int64_t iu64,
+                             double* d_w, double* d_v) {
+  if (n64 > 46000) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "matrix order %lld too large", (long long)n64);
+  const int n = (int)n64, batch = (int)batch64, il = (int)il64, iu = (int)iu64;
+  if (il < 0 || iu < il || iu >= n)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad eigenvalue index range [%d, %d] for order %d", il, iu, n);
+  return partial_batched_async(ctx, d_a, n, batch, il, iu - il + 1, nullptr, d_w, d_v);
 }
 
 int eigh_range_batched(sc_ctx* ctx, double* d_a, int64_t n, int64_t batch, int64_t il, int64_t iu, double* d_w,
@@ -467,6 +543,60 @@ int eigh_range_batched(sc_ctx* ctx, double* d_a, int64_t n, int64_t batch, int64
   SC_TRY(eigh_range_batched_async(ctx, d_a, n, batch, il, iu, d_w, d_v));
   SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return sc_deferred_status(ctx);
+}
+
+int eigh_window_batched_async(sc_ctx* ctx, double* d_a, int64_t n64, int64_t batch64, double vl, double vu, int64_t K64,
+                              double* d_w, double* d_v, int64_t* d_count) {
+  if (n64 > 46000) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "matrix order %lld too large", (long long)n64);
+  SC_TRY(check_window(ctx, vl, vu));
+  if (K64 < 1 || K64 > n64)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "window capacity %lld outside 1..%lld", (long long)K64, (long long)n64);
+  const ValueWindow window{vl, vu, (long long*)d_count};
+  return partial_batched_async(ctx, d_a, (int)n64, (int)batch64, 0, (int)K64, &window, d_w, d_v);
+}
+
+// One matrix: tridiagonalise, count the window on the device, read m on the host (the one synchronisation), then the m
+// eigenpairs exactly as the index range il .. il + m - 1 computes them.  The inverse-iteration workspace and the results
+// depend on m, which sc_reserve_ws could not know: they live in a buffer of their own (ctx->win_ws), so that the tri / sb
+// slabs the eigenpairs still need never move.  On success *d_w / *d_v point into that buffer (valid until the next
+// window solve on the context).
+int eigh_window(sc_ctx* ctx, double* d_a, int64_t n64, double vl, double vu, bool vectors, int64_t* m_out, double** d_w,
+                double** d_v) {
+  if (n64 > 46000) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "matrix order %lld too large", (long long)n64);
+  SC_TRY(check_window(ctx, vl, vu));
+  const int n = (int)n64;
+  *m_out = 0;
+  *d_w = *d_v = nullptr;
+  const PartialPlan P = make_partial_plan(ctx, n, 1, vectors, 0, 1);
+  SC_TRY(sc_reserve_ws(ctx, P.total));
+  char* base = (char*)ctx->ws;
+  PartialProfile prof(ctx);
+  SC_TRY(partial_tridiagonalise(ctx, d_a, n, 1, P, base, prof));
+  WinCount* d_win = (WinCount*)(base + P.off_win);
+  SC_TRY(window_count_batched(ctx, 1, (const double*)(base + P.off_tri), P.TL, vl, vu, 1, d_win, nullptr));
+  WinCount h{};
+  SC_HIP(ctx, hipMemcpyAsync(&h, d_win, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  SC_TRY(sc_deferred_status(ctx));   // (a matrix with a NaN / Inf entry: LinAlgError, as the other solves)
+  const int m = h.count;
+  if (m <= 0) return sc_stage_end(ctx);
+  if (h.il < 0 || h.il + m > n)
+    return sc_set_error(ctx, SC_ERR_HIP, "window count [%d, %d) outside order %d", h.il, h.il + m, n);
+  const size_t stein_bytes = vectors ? align_up(stein_workspace_doubles(n, m) * 8, 256) : 0;
+  const size_t w_bytes = align_up((size_t)m * 8, 256);
+  SC_TRY(sc_reserve_win(ctx, stein_bytes + w_bytes + (vectors ? (size_t)m * n * 8 : 0)));
+  char* wb = (char*)ctx->win_ws;
+  double* w = (double*)(wb + stein_bytes);
+  double* v = vectors ? (double*)(wb + stein_bytes + w_bytes) : nullptr;
+  SC_TRY(partial_eigenpairs(ctx, d_a, n, 1, P, base, h.il, m, nullptr, w, v, (double*)wb, prof));
+  SC_TRY(prof.finish(P.two, vectors));
+  SC_TRY(sc_stage_end(ctx));
+  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  SC_TRY(sc_deferred_status(ctx));
+  *m_out = m;
+  *d_w = w;
+  *d_v = v;
+  return SC_OK;
 }
 
 

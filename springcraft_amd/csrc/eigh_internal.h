@@ -146,7 +146,21 @@ int bt2_batched(sc_ctx* ctx, int n, int batch, double* d_sb_ws, const SbLayout& 
                 long long stride_z, int ncols, float* ms_fused = nullptr);
 
 // ---- partial spectrum (stein.hip) -----------------------------------------------------------------------
+// Eigenvalue window (vl, vu] of one matrix, counted on the device: il = #(lambda <= vl), count = #(lambda <= vu) - il;
+// its slot of K eigenpairs holds eigenpairs start .. start + K - 1, start = min(il, n - K)
+struct WinCount {
+  int il, count, start, pad;
+};
 size_t stein_workspace_doubles(int n, int m);
+// d_win: null (eigenpairs il..iu of every matrix), or the counts of window_count_batched (matrix b: eigenpairs
+// d_win[b].start .. d_win[b].start + iu - il)
 int stein_batched(sc_ctx* ctx, int n, int batch, const double* d_tri_ws, const TriLayout& TL, int il, int iu,
                   double* d_w, long long stride_w, double* d_x, long long stride_x, double* d_ws,
-                  GemmDesc* d_descs /* 2 * batch */);
+                  GemmDesc* d_descs /* 2 * batch */, const WinCount* d_win = nullptr);
+// d_win[b] (and d_count[b] = count unless null) for every matrix of the tridiagonalised batch; 1 <= K <= n
+int window_count_batched(sc_ctx* ctx, int batch, const double* d_tri_ws, const TriLayout& TL, double vl, double vu, int K,
+                         WinCount* d_win, long long* d_count);
+// The window's rows of every slot of d_w (batch, K) / d_v (null or (batch, K, n)) to the front, NaN / zero rows behind;
+// d_w_copy (batch K) and d_v_copy (batch K n) are scratch
+int window_compact_batched(sc_ctx* ctx, int n, int batch, int K, const WinCount* d_win, double* d_w, double* d_v,
+                           double* d_w_copy, double* d_v_copy);

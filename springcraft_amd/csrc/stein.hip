@@ -11,6 +11,9 @@
 //   CholQR2         G = X^T X (split-K MFMA GEMM), k_chol_inv (one workgroup: Cholesky + inverse of R),
 //                   X <- X R^-1 (MFMA GEMM); twice.  Inside a numerically degenerate cluster (the six
 //                   rigid-body modes of an ANM) this picks an orthonormal basis of the invariant subspace.
+//   k_window_count  eigenvalue window (vl, vu]: Sturm counts at the bounds, one wave per matrix; the start of every
+//                   matrix' slot of K eigenpairs goes to k_sturm_range
+//   k_window_compact  the window's rows to the front of every slot, NaN / zero rows behind them
 #include <algorithm>
 #include <vector>
 
@@ -25,19 +28,12 @@ __host__ __device__ inline size_t stein_nm4(int n, int m) { return ((size_t)n * 
 
 constexpr double kEpsS = 2.220446049250313e-16;
 
-// One WAVE per requested eigenvalue: multisection.  Every round the 64 lanes count the eigenvalues below 64 equally
-// spaced shifts inside the current bracket (the Sturm recurrence is sequential in n but independent between shifts, so
-// a round costs what one bisection step costs) and the bracket shrinks 65-fold: ~9 rounds instead of ~53 bisection
-// steps; a few plain bisection steps then close the bracket to neighbouring floating-point numbers as before.
-__global__ __launch_bounds__(64) void k_sturm_range(const double* __restrict__ tri_all, TriLayout TL, int il,
-                                                    int m, double* __restrict__ w_all, long long stride_w) {
-  const double* tri = tri_all + (size_t)blockIdx.y * TL.slab;
-  const double* d = tri + TL.d;
-  const double* e = tri + TL.e;
-  const int n = TL.n;
-  const int lane = threadIdx.x;
-  // Gershgorin bounds, lanes strided over the rows
-  double lo = 1e300, hi = -1e300, emax = 0.0;
+typedef double d2s __attribute__((ext_vector_type(2)));
+
+// Gershgorin bounds of T (lanes strided over the rows, reduced over the wave) and the largest |e_i|
+__device__ __forceinline__ void sturm_gershgorin(const double* __restrict__ d, const double* __restrict__ e, int n, int lane,
+                                                 double& lo, double& hi, double& emax) {
+  lo = 1e300, hi = -1e300, emax = 0.0;
   for (int i = lane; i < n; i += 64) {
     const double el = i > 0 ? fabs(e[i - 1]) : 0.0, er = i < n - 1 ? fabs(e[i]) : 0.0;
     lo = fmin(lo, d[i] - el - er);
@@ -50,35 +46,31 @@ __global__ __launch_bounds__(64) void k_sturm_range(const double* __restrict__ t
     hi = fmax(hi, __shfl_xor(hi, off));
     emax = fmax(emax, __shfl_xor(emax, off));
   }
-  const double span = fmax(fabs(lo), fabs(hi));
-  const double pivmin = fmax(2.2250738585072014e-308 * fmax(1.0, emax * emax), 1e-290);
-  lo -= 2.0 * kEpsS * span * n + 2.0 * pivmin;
-  hi += 2.0 * kEpsS * span * n + 2.0 * pivmin;
-  const int j = blockIdx.x;
-  if (j >= m) return;
-  const int k = il + j;
-  // Sturm count WITHOUT a division in the chain (round 5).  The ratio form q_i = (d_i - x) - e_{i-1}^2 / q_{i-1} that
-  // dstebz uses is a chain of n IEEE divisions -- ~150 cycles each on this chip: 4 ms per count at n = 24 000, 68 ms for
-  // the 16 counts an eigenvalue needs.  The product form p_i = a_i p_{i-1} - b_i p_{i-2} (a_i = (d_i - x) s,
-  // b_i = (e_{i-1} s)^2, q_i = p_i / p_{i-1}) has ONE fused multiply-add in the chain (b_i p_{i-2} is known a step
-  // earlier); the eigenvalues below x are the sign changes of the sequence, as Wilkinson's bisection counted them.  The
-  // rows are scaled by s = 1 / (Gershgorin radius) so that |a_i| <= 2, b_i <= 1: a sequence grows by at most 3^4 between
-  // two re-normalisations (every 4 rows, by the exponent of the larger of the last two members).  An exact zero takes
-  // the sign opposite to its predecessor -- dstebz's q = -pivmin.  What the product form gives up against the ratio form:
-  // rows whose entries AND distance to the shift are below ~1e-60 of the matrix' norm shrink the sequence into underflow
-  // and then count as decoupled zeros -- shifts that small are 44 orders below the eps |T| to which a tridiagonal matrix
-  // that came out of an orthogonal reduction is known at all (tools/models/sturm_product_model.py, tests/test_sturm_model.py).
-  // The rows reach the chain through LDS: lane l of the wave loads row 64 c + l of a 64-row chunk c (two coalesced loads
-  // per chunk and lane instead of 2 x 64 loads of one address each), a group of four chunks ahead of the one in work; a
-  // chunk in work is written to LDS once (16 bytes per lane) and every step reads its row as ONE broadcast ds_read_b128.
-  // (History of the 68 ms this kernel took at n = 24 000: every lane loading every row in chunks of 16, the count waited for
-  // memory 1 500 times -- the division-free chain alone: 64 ms; rows from the lanes by v_readlane, four per step, with the
-  // wait states they need and a scalar branch per step for the tail: 42 ms.)
-  const double sc = 1.0 / fmax(span + 2.0 * emax, 1e-300);
+}
+
+// Number of eigenvalues of T below x: every lane of the wave counts for its own x, all 64 lanes must call.  sc scales the
+// rows (1 / Gershgorin radius), rows: 2 x 64 entries of LDS owned by the caller.
+// Sturm count WITHOUT a division in the chain (round 5).  The ratio form q_i = (d_i - x) - e_{i-1}^2 / q_{i-1} that
+// dstebz uses is a chain of n IEEE divisions -- ~150 cycles each on this chip: 4 ms per count at n = 24 000, 68 ms for
+// the 16 counts an eigenvalue needs.  The product form p_i = a_i p_{i-1} - b_i p_{i-2} (a_i = (d_i - x) s,
+// b_i = (e_{i-1} s)^2, q_i = p_i / p_{i-1}) has ONE fused multiply-add in the chain (b_i p_{i-2} is known a step
+// earlier); the eigenvalues below x are the sign changes of the sequence, as Wilkinson's bisection counted them.  The
+// rows are scaled by s = 1 / (Gershgorin radius) so that |a_i| <= 2, b_i <= 1: a sequence grows by at most 3^4 between
+// two re-normalisations (every 4 rows, by the exponent of the larger of the last two members).  An exact zero takes
+// the sign opposite to its predecessor -- dstebz's q = -pivmin.  What the product form gives up against the ratio form:
+// rows whose entries AND distance to the shift are below ~1e-60 of the matrix' norm shrink the sequence into underflow
+// and then count as decoupled zeros -- shifts that small are 44 orders below the eps |T| to which a tridiagonal matrix
+// that came out of an orthogonal reduction is known at all (tools/models/sturm_product_model.py, tests/test_sturm_model.py).
+// The rows reach the chain through LDS: lane l of the wave loads row 64 c + l of a 64-row chunk c (two coalesced loads
+// per chunk and lane instead of 2 x 64 loads of one address each), a group of four chunks ahead of the one in work; a
+// chunk in work is written to LDS once (16 bytes per lane) and every step reads its row as ONE broadcast ds_read_b128.
+// (History of the 68 ms this kernel took at n = 24 000: every lane loading every row in chunks of 16, the count waited for
+// memory 1 500 times -- the division-free chain alone: 64 ms; rows from the lanes by v_readlane, four per step, with the
+// wait states they need and a scalar branch per step for the tail: 42 ms.)
+__device__ __forceinline__ int sturm_count_below(const double* __restrict__ d, const double* __restrict__ e, int n,
+                                                 int lane, double sc, double x, d2s (*rows)[64]) {
   const double tiny_p = 0x1p-900;
   const int nchunk = (n + 63) / 64;
-  typedef double d2s __attribute__((ext_vector_type(2)));
-  __shared__ d2s rows[2][64];
   auto load_rows = [&](int c, double& as, double& bs) {
     const int i = min(c * 64 + lane, n - 1);
     const double es = i > 0 ? e[i - 1] * sc : 0.0;
@@ -86,81 +78,106 @@ __global__ __launch_bounds__(64) void k_sturm_range(const double* __restrict__ t
     bs = es * es;
   };
   auto hi32 = [](double v) { return (unsigned)((unsigned long long)__double_as_longlong(v) >> 32); };
-  auto count_below = [&](double x) {
-    const double xs = x * sc;
-    unsigned cnt = 0;
-    double p2 = 1.0, p1 = 1.0;           // p_{-1} (any: b_0 = 0), p_0 = 1
-    // one step: row (a, b) -> the next member of the sequence.  An exact zero (rare: a branch for the whole wave) takes a
-    // tiny value of the sign opposite to its predecessor, so that a decoupled block behind it (b = 0) starts afresh
+  const double xs = x * sc;
+  unsigned cnt = 0;
+  double p2 = 1.0, p1 = 1.0;           // p_{-1} (any: b_0 = 0), p_0 = 1
+  // one step: row (a, b) -> the next member of the sequence.  An exact zero (rare: a branch for the whole wave) takes a
+  // tiny value of the sign opposite to its predecessor, so that a decoupled block behind it (b = 0) starts afresh
 #define STURM_STEP(r)                                                                  \
-    {                                                                                  \
-      double p0 = fma((r)[0] - xs, p1, -((r)[1] * p2));                                \
-      if (__builtin_expect(__any(p0 == 0.0), 0))                                       \
-        if (p0 == 0.0) p0 = -copysign(tiny_p, p1);                                     \
-      cnt += (hi32(p0) ^ hi32(p1)) >> 31;                                              \
-      p2 = p1;                                                                         \
-      p1 = p0;                                                                         \
-    }
+  {                                                                                    \
+    double p0 = fma((r)[0] - xs, p1, -((r)[1] * p2));                                  \
+    if (__builtin_expect(__any(p0 == 0.0), 0))                                         \
+      if (p0 == 0.0) p0 = -copysign(tiny_p, p1);                                       \
+    cnt += (hi32(p0) ^ hi32(p1)) >> 31;                                                \
+    p2 = p1;                                                                           \
+    p1 = p0;                                                                           \
+  }
 #define STURM_RENORM()                                                                 \
-    {                                                                                  \
-      int ex;                                                                          \
-      (void)frexp(fmax(fabs(p1), fabs(p2)), &ex);                                      \
-      p1 = ldexp(p1, -ex);                                                             \
-      p2 = ldexp(p2, -ex);                                                             \
-    }
-    // groups of four chunks: the rows of group g + 1 are requested at the top of group g and used a group (256 rows) later
-    // -- inside ONE loop body, so that the compiler's wait in front of their first use is the only one
-    const int ngroup = (nchunk + 3) / 4;
-    double ca[4], cb[4], na[4], nb[4];
+  {                                                                                    \
+    int ex;                                                                            \
+    (void)frexp(fmax(fabs(p1), fabs(p2)), &ex);                                        \
+    p1 = ldexp(p1, -ex);                                                               \
+    p2 = ldexp(p2, -ex);                                                               \
+  }
+  // groups of four chunks: the rows of group g + 1 are requested at the top of group g and used a group (256 rows) later
+  // -- inside ONE loop body, so that the compiler's wait in front of their first use is the only one
+  const int ngroup = (nchunk + 3) / 4;
+  double ca[4], cb[4], na[4], nb[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) load_rows(min(t, nchunk - 1), ca[t], cb[t]);
-    for (int g = 0; g < ngroup; ++g) {
+  for (int t = 0; t < 4; ++t) load_rows(min(t, nchunk - 1), ca[t], cb[t]);
+  for (int g = 0; g < ngroup; ++g) {
 #pragma unroll
-      for (int t = 0; t < 4; ++t) load_rows(min(4 * (g + 1) + t, nchunk - 1), na[t], nb[t]);
+    for (int t = 0; t < 4; ++t) load_rows(min(4 * (g + 1) + t, nchunk - 1), na[t], nb[t]);
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int c = 4 * g + t;
-        const int lim = min(64, n - c * 64);      // (<= 0 behind the last chunk)
-        if (lim <= 0) break;
-        rows[t & 1][lane] = d2s{ca[t], cb[t]};
-        __builtin_amdgcn_wave_barrier();
-        if (lim == 64) {
-          // (the rows of the next eight steps are read while these eight run: one exposed LDS latency per step otherwise)
-          d2s r8[8], n8[8];
+    for (int t = 0; t < 4; ++t) {
+      const int c = 4 * g + t;
+      const int lim = min(64, n - c * 64);      // (<= 0 behind the last chunk)
+      if (lim <= 0) break;
+      rows[t & 1][lane] = d2s{ca[t], cb[t]};
+      __builtin_amdgcn_wave_barrier();
+      if (lim == 64) {
+        // (the rows of the next eight steps are read while these eight run: one exposed LDS latency per step otherwise)
+        d2s r8[8], n8[8];
 #pragma unroll
-          for (int q = 0; q < 8; ++q) r8[q] = rows[t & 1][q];
+        for (int q = 0; q < 8; ++q) r8[q] = rows[t & 1][q];
 #pragma unroll
-          for (int blk = 0; blk < 8; ++blk) {
-            if (blk < 7) {
+        for (int blk = 0; blk < 8; ++blk) {
+          if (blk < 7) {
 #pragma unroll
-              for (int q = 0; q < 8; ++q) n8[q] = rows[t & 1][8 * (blk + 1) + q];
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-              STURM_STEP(r8[q])
-              if ((q & 3) == 3) STURM_RENORM()
-            }
-#pragma unroll
-            for (int q = 0; q < 8; ++q) r8[q] = n8[q];
+            for (int q = 0; q < 8; ++q) n8[q] = rows[t & 1][8 * (blk + 1) + q];
           }
-        } else {
-          for (int u = 0; u < lim; ++u) {
-            const d2s r = rows[t & 1][u];
-            STURM_STEP(r)
-            if ((u & 3) == 3) STURM_RENORM()
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            STURM_STEP(r8[q])
+            if ((q & 3) == 3) STURM_RENORM()
           }
-          STURM_RENORM()
+#pragma unroll
+          for (int q = 0; q < 8; ++q) r8[q] = n8[q];
         }
-        __builtin_amdgcn_wave_barrier();
+      } else {
+        for (int u = 0; u < lim; ++u) {
+          const d2s r = rows[t & 1][u];
+          STURM_STEP(r)
+          if ((u & 3) == 3) STURM_RENORM()
+        }
+        STURM_RENORM()
       }
-#pragma unroll
-      for (int t = 0; t < 4; ++t) { ca[t] = na[t]; cb[t] = nb[t]; }
+      __builtin_amdgcn_wave_barrier();
     }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) { ca[t] = na[t]; cb[t] = nb[t]; }
+  }
 #undef STURM_STEP
 #undef STURM_RENORM
-    return (int)cnt;
-  };
+  return (int)cnt;
+}
+
+// One WAVE per requested eigenvalue: multisection.  Every round the 64 lanes count the eigenvalues below 64 equally
+// spaced shifts inside the current bracket (the Sturm recurrence is sequential in n but independent between shifts, so
+// a round costs what one bisection step costs) and the bracket shrinks 65-fold: ~9 rounds instead of ~53 bisection
+// steps; a few plain bisection steps then close the bracket to neighbouring floating-point numbers as before.
+// win: null, or one WinCount per matrix (k_window_count): matrix b's first eigenvalue is then win[b].start, not il.
+__global__ __launch_bounds__(64) void k_sturm_range(const double* __restrict__ tri_all, TriLayout TL, int il,
+                                                    int m, double* __restrict__ w_all, long long stride_w,
+                                                    const WinCount* __restrict__ win) {
+  const double* tri = tri_all + (size_t)blockIdx.y * TL.slab;
+  const double* d = tri + TL.d;
+  const double* e = tri + TL.e;
+  const int n = TL.n;
+  const int lane = threadIdx.x;
+  double lo, hi, emax;
+  sturm_gershgorin(d, e, n, lane, lo, hi, emax);
+  const double span = fmax(fabs(lo), fabs(hi));
+  const double pivmin = fmax(2.2250738585072014e-308 * fmax(1.0, emax * emax), 1e-290);
+  lo -= 2.0 * kEpsS * span * n + 2.0 * pivmin;
+  hi += 2.0 * kEpsS * span * n + 2.0 * pivmin;
+  const int j = blockIdx.x;
+  if (j >= m) return;
+  const int k = (win ? win[blockIdx.y].start : il) + j;
+  const double sc = 1.0 / fmax(span + 2.0 * emax, 1e-300);
+  __shared__ d2s rows[2][64];
+  auto count_below = [&](double x) { return sturm_count_below(d, e, n, lane, sc, x, rows); };
   double a = lo, b = hi;   // invariant: count_below(a) <= k < count_below(b)
   // Stop at a bracket of eps |T| (dstebz's abstol): narrower brackets cost counts and, next to an exactly
   // zero eigenvalue of a decoupled block, drive the shift into the range where the product-form count flushes rows to
@@ -191,6 +208,70 @@ __global__ __launch_bounds__(64) void k_sturm_range(const double* __restrict__ t
     if (count_below(mid) > k) b = mid; else a = mid;
   }
   if (lane == 0) w_all[(size_t)blockIdx.y * stride_w + j] = 0.5 * (a + b);
+}
+
+// Window (vl, vu] of every matrix, on the scaled T = f A of the tridiagonalisation: il = #(lambda <= vl),
+// count = #(lambda <= vu) - il, start = min(il, n - K) (the first of the K eigenpairs its slot receives).  One wave per
+// matrix; lane 0 counts at vl, lane 1 at vu.  #(lambda <= x) is the count below the next double above x; shifts outside the
+// padded Gershgorin interval (the infinities, and finite bounds that the factor f pushed beyond the doubles) are resolved
+// to 0 / n without the recurrence.  A matrix with a NaN / Inf entry (solved as the zero matrix) gets il = count = 0.
+__global__ __launch_bounds__(64) void k_window_count(const double* __restrict__ tri_all, TriLayout TL, double vl,
+                                                     double vu, int K, WinCount* __restrict__ win,
+                                                     long long* __restrict__ count_out) {
+  const double* tri = tri_all + (size_t)blockIdx.x * TL.slab;
+  const double* d = tri + TL.d;
+  const double* e = tri + TL.e;
+  const int n = TL.n;
+  const int lane = threadIdx.x;
+  double lo, hi, emax;
+  sturm_gershgorin(d, e, n, lane, lo, hi, emax);
+  const double span = fmax(fabs(lo), fabs(hi));
+  const double pivmin = fmax(2.2250738585072014e-308 * fmax(1.0, emax * emax), 1e-290);
+  lo -= 2.0 * kEpsS * span * n + 2.0 * pivmin;
+  hi += 2.0 * kEpsS * span * n + 2.0 * pivmin;
+  const double sc = 1.0 / fmax(span + 2.0 * emax, 1e-300);
+  const double f = tri[TL.hscale + 2];   // an exact power of two (matrix_scale_factor)
+  const bool bad = *reinterpret_cast<const unsigned long long*>(tri + TL.hscale + 3) != 0ull;
+  const double bound = lane == 1 ? vu : vl;
+  double x = bound * f;
+  if (isinf(x) && !isinf(bound)) x = copysign(1.7976931348623157e308, bound);   // (clamped: f moved it past the doubles)
+  x = nextafter(x, __builtin_inf());                                            // #(lambda <= x) = #(lambda < next(x))
+  const bool inside = x > lo && x < hi;
+  __shared__ d2s rows[2][64];
+  int cnt = x <= lo ? 0 : n;
+  if (__any(inside)) {
+    const int c = sturm_count_below(d, e, n, lane, sc, inside ? x : 0.5 * (lo + hi), rows);
+    if (inside) cnt = c;
+  }
+  const int cnt_vu = __shfl(cnt, 1);
+  if (lane == 0) {
+    const int il = bad ? 0 : cnt;
+    const int count = bad ? 0 : max(cnt_vu - cnt, 0);
+    win[blockIdx.x] = WinCount{il, count, min(il, n - K), 0};
+    if (count_out) count_out[blockIdx.x] = count;
+  }
+}
+
+// Moves rows il - start .. il - start + min(count, K) - 1 of every slot of w (batch, K) and v (batch, K, n) to the front of
+// the slot, NaN / zero rows behind them.  Source and destination overlap, so the rows are read from copies of w and v
+// (w_src, v_src: same layout) made before the launch.  Grid (K, batch), one row per workgroup; v may be null.
+__global__ __launch_bounds__(256) void k_window_compact(const WinCount* __restrict__ win, int K, int n,
+                                                        const double* __restrict__ w_src, double* __restrict__ w,
+                                                        const double* __restrict__ v_src, double* __restrict__ v) {
+  const int r = blockIdx.x, b = blockIdx.y;
+  const WinCount c = win[b];
+  const int off = min(max(c.il - c.start, 0), K);
+  const int keep = min(c.count, K - off);
+  const size_t slot = (size_t)b * K;
+  if (threadIdx.x == 0) w[slot + r] = r < keep ? w_src[slot + off + r] : __builtin_nan("");
+  if (!v) return;
+  double* dst = v + (slot + r) * n;
+  if (r < keep) {
+    const double* src = v_src + (slot + off + r) * n;
+    for (int i = threadIdx.x; i < n; i += 256) dst[i] = src[i];
+  } else {
+    for (int i = threadIdx.x; i < n; i += 256) dst[i] = 0.0;
+  }
 }
 
 __device__ __forceinline__ double hash_unit(unsigned a, unsigned b) {
@@ -410,16 +491,17 @@ size_t stein_workspace_doubles(int n, int m) {
   return (7 * stein_nm4(n, m) + (size_t)33 * m * m + 64 + 3) / 4 * 4;
 }
 
-// Eigenvalues il..iu (0-based, inclusive) into d_w (batch, m) and eigenvectors of T into d_x (batch, n, m
+// Eigenvalues il..iu (0-based, inclusive; with d_win: win[b].start .. win[b].start + iu - il) into d_w (batch, m) and eigenvectors of T into d_x (batch, n, m
 // column-major = (m, n) rows-are-modes).  d_ws: stein_workspace_doubles(n, m) * batch doubles.
 int stein_batched(sc_ctx* ctx, int n, int batch, const double* d_tri_ws, const TriLayout& TL, int il, int iu,
                   double* d_w, long long stride_w, double* d_x, long long stride_x, double* d_ws,
-                  GemmDesc* d_descs /* 2 * batch */) {
+                  GemmDesc* d_descs /* 2 * batch */, const WinCount* d_win) {
   hipStream_t st = ctx->stream;
   const int m = iu - il + 1;
   PhaseTimer t_sturm(ctx, "sturm", st), t_stein(ctx, "stein", st), t_qr(ctx, "cholqr", st);
   t_sturm.start();
-  hipLaunchKernelGGL(k_sturm_range, dim3((unsigned)m, (unsigned)batch), dim3(64), 0, st, d_tri_ws, TL, il, m, d_w, stride_w);
+  hipLaunchKernelGGL(k_sturm_range, dim3((unsigned)m, (unsigned)batch), dim3(64), 0, st, d_tri_ws, TL, il, m, d_w, stride_w,
+                     d_win);
   t_sturm.stop();
   if (!d_x) {
     t_sturm.finish();
@@ -470,6 +552,27 @@ int stein_batched(sc_ctx* ctx, int n, int batch, const double* d_tri_ws, const T
   }
   t_qr.stop();
   t_sturm.finish(); t_stein.finish(); t_qr.finish();
+  SC_HIP(ctx, hipGetLastError());
+  return SC_OK;
+}
+
+
+int window_count_batched(sc_ctx* ctx, int batch, const double* d_tri_ws, const TriLayout& TL, double vl, double vu, int K,
+                         WinCount* d_win, long long* d_count) {
+  hipLaunchKernelGGL(k_window_count, dim3((unsigned)batch), dim3(64), 0, ctx->stream, d_tri_ws, TL, vl, vu, K, d_win,
+                     d_count);
+  SC_HIP(ctx, hipGetLastError());
+  return SC_OK;
+}
+
+int window_compact_batched(sc_ctx* ctx, int n, int batch, int K, const WinCount* d_win, double* d_w, double* d_v,
+                           double* d_w_copy, double* d_v_copy) {
+  hipStream_t st = ctx->stream;
+  const size_t rows = (size_t)batch * K;
+  SC_HIP(ctx, hipMemcpyAsync(d_w_copy, d_w, rows * sizeof(double), hipMemcpyDeviceToDevice, st));
+  if (d_v) SC_HIP(ctx, hipMemcpyAsync(d_v_copy, d_v, rows * n * sizeof(double), hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(k_window_compact, dim3((unsigned)K, (unsigned)batch), dim3(256), 0, st, d_win, K, n, d_w_copy, d_w,
+                     d_v ? d_v_copy : nullptr, d_v);
   SC_HIP(ctx, hipGetLastError());
   return SC_OK;
 }

@@ -49,9 +49,12 @@ class GNM(ElasticNetworkModel):
     def covariance(self, value):
         self._set_covariance(value)
 
-    def eigen(self, subset_by_index=None):
-        """Eigenvalues (ascending, (n,)) and eigenvectors (rows, (n,n)) of the Kirchhoff matrix (gnm.py:145-158)."""
-        return nma.eigen(self, subset_by_index)
+    def eigen(self, subset_by_index=None, subset_by_value=None):
+        """
+        Eigenvalues (ascending, (n,)) and eigenvectors (rows, (n,n)) of the Kirchhoff matrix (gnm.py:145-158).
+        ``subset_by_index`` / ``subset_by_value``: a part of the spectrum only, see :func:`nma.eigen`.
+        """
+        return nma.eigen(self, subset_by_index, subset_by_value)
 
     def frequencies(self):
         """Mode frequencies in arbitrary units (gnm.py:160-176)."""

@@ -24,7 +24,23 @@ K_B = 1.380649e-23
 N_A = 6.02214076e23
 
 
-def eigh(matrix, eigenvectors=True, subset_by_index=None):
+def _value_window(subset_by_value, subset_by_index=None):
+    """
+    ``subset_by_value`` checked as ``scipy.linalg.eigh`` checks it (same errors, before any device call): None, or the
+    bounds (vl, vu) as floats, vl < vu, +-inf allowed.
+    """
+    if subset_by_value is None:
+        return None
+    if subset_by_index is not None:
+        raise ValueError("Either index or value subset can be requested.")
+    vl, vu = (float(x) for x in subset_by_value)
+    if not (vl < vu):   # (also a NaN bound)
+        raise ValueError("Requested eigenvalue bounds are not valid. Valid range is (-inf, inf) and low < high, but "
+                         f"low={vl}, high={vu} is given")
+    return vl, vu
+
+
+def eigh(matrix, eigenvectors=True, subset_by_index=None, subset_by_value=None):
     """
     Device replacement for ``np.linalg.eigh(matrix)`` as used at nma.py:61: ascending
     eigenvalues of a symmetric float64 matrix (lower triangle read) and, as ROWS, the
@@ -33,12 +49,25 @@ def eigh(matrix, eigenvectors=True, subset_by_index=None):
     ``subset_by_index=(lo, hi)`` (inclusive, like ``scipy.linalg.eigh``) selects the partial-spectrum
     path: only eigenpairs lo..hi are computed (bisection + inverse iteration), which is what large
     models that only need their slowest modes should use.
+
+    ``subset_by_value=(vl, vu)`` (like ``scipy.linalg.eigh``) selects the eigenvalues in the half-open interval
+    (vl, vu], +-inf allowed: the m of them are counted on the device on the tridiagonal matrix that is then solved (one
+    tridiagonalisation), and exactly m pairs are returned, ``w`` (m,) and ``v`` (m, n); m may be 0.  Whether an eigenvalue
+    within about n eps ||A|| of a bound is inside is decided by that count, as LAPACK's dsyevr decides it.  For an ENM,
+    eigenvalue and frequency are related by lambda = (2 pi f)^2 (:func:`frequencies`); the six trivial eigenvalues of an
+    ANM sit at rounding level around zero (|lambda| ~ 1e-14 .. 1e-13 of lambda_max, either sign), so a window meant to
+    skip them needs a small positive ``vl``.  Giving both subsets, ``vl >= vu`` or a NaN bound raises ValueError.
     """
+    window = _value_window(subset_by_value, subset_by_index)
     a = np.ascontiguousarray(matrix, dtype=np.float64)
     if a.ndim != 2 or a.shape[0] != a.shape[1]:
         raise ValueError(f"Expected a square matrix, got shape {a.shape}")
     n = a.shape[0]
     ctx = _hip.context()
+    if window is not None:
+        w, v = _hip.solve_window(ctx, _hip.lib().sc_eigh_window_f64, (ctx.handle, _hip.ptr(a), n) + window, n,
+                                 eigenvectors)
+        return (w, v) if eigenvectors else w
     if subset_by_index is not None:
         lo, hi = (int(x) for x in subset_by_index)
         if not (0 <= lo <= hi < n):
@@ -80,14 +109,19 @@ def _model_kind(enm):
     raise ValueError("Instance of GNM/ANM class expected.")
 
 
-def eigen(enm, subset_by_index=None):
+def eigen(enm, subset_by_index=None, subset_by_value=None):
     """
     Eigenvalues (ascending) and eigenvectors (rows) of the Kirchhoff / Hessian matrix of a
     GNM / ANM (reference: nma.py:29-63).  ``subset_by_index=(lo, hi)`` (extension, inclusive) restricts
-    the computation to modes lo..hi.
+    the computation to modes lo..hi; ``subset_by_value=(vl, vu)`` (extension, scipy's semantics, see :func:`eigh`) to the
+    modes whose eigenvalue lies in (vl, vu].  lambda = (2 pi f)^2: every mode below the frequency f is
+    ``subset_by_value=(vl, (2 * np.pi * f) ** 2)``.  An ANM's six trivial eigenvalues are ~0 at rounding level, of either
+    sign (|lambda| ~ 1e-14 .. 1e-13 of lambda_max): ``vl = -inf`` includes them, a small positive ``vl`` (e.g. 1e-6
+    lambda_max) leaves them out.
     """
     _model_kind(enm)
-    return enm._eigen_device(subset_by_index)
+    _value_window(subset_by_value, subset_by_index)
+    return enm._eigen_device(subset_by_index, subset_by_value)
 
 
 def frequencies(enm):
