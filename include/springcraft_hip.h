@@ -367,6 +367,57 @@ int sc_modes_dcc(sc_modes* modes, const int64_t* mode_idx, int64_t k, int norm, 
  * rule); norm != 0 divides row a by out[a, a]. */
 int sc_modes_prs(sc_modes* modes, double rcond, int norm, double* out);
 
+/* ---- the same consumers for a batch: device pointers in, device pointers out, enqueue only ------------------------
+ * What nma.py:108-184 (mean_square_fluctuation) and nma.py:233-359 (dcc) derive from nma.eigen for ONE model, for every
+ * structure of a batch at once and on the very tensors the batched solvers above leave in device memory: d_w (batch,
+ * nvec), d_v (batch, nvec, m) rows = modes, and, behind a window solve, d_counts (batch,) int64.  Like the solvers they
+ * only enqueue on the context's stream; nothing is copied to the host, the eigenvalues included.
+ *
+ *   msf[b, a]    = sum_r  s[b, r] * sum_d V[b, r, dim a + d]^2
+ *   dcc[b, a, c] = sum_r  s[b, r] * sum_d V[b, r, dim a + d] V[b, r, dim c + d]
+ *
+ * with s[b, r] = 1 / w[b, r] for a selected row r and exactly 0 for every other one: a row without weight contributes
+ * nothing, whatever it holds (the NaN / zero padding of a window solve).  The selection names ROWS of d_w / d_v, not
+ * global mode indices -- the caller knows which modes it solved:
+ *   SC_SEL_FROM_ROW  every row r >= row0                                 (nma.py:161-163: all non-trivial modes)
+ *   SC_SEL_ROWS      the n_rows rows listed in d_rows, int32 in DEVICE memory and shared by all structures; a row listed
+ *                    twice counts twice, as NumPy's fancy indexing makes it at nma.py:167-168 / :339-340; an entry
+ *                    outside 0..nvec-1 is not read and turns the structure's result into NaN
+ *   SC_SEL_PINV      every row with |w| > rcond * max|w|, the maximum taken per structure on the device: the rule of
+ *                    numpy.linalg.pinv(hermitian=True) behind the covariance the reference takes for "all modes"
+ *                    (nma.py:324-336, anm.py:114-117); only meaningful when all m modes were solved
+ * d_counts != NULL clips every selection to the rows r < min(d_counts[b], nvec) of structure b.
+ * A structure whose eigenvalues are NaN (a matrix with a NaN / Inf entry) gets NaN results, its neighbours are unaffected. */
+#define SC_SEL_FROM_ROW 0
+#define SC_SEL_ROWS 1
+#define SC_SEL_PINV 2
+typedef struct sc_mode_selection {
+  int32_t kind;
+  int32_t reserved;
+  int64_t row0;          /* SC_SEL_FROM_ROW */
+  const int32_t* d_rows; /* SC_SEL_ROWS: (n_rows,) device memory */
+  int64_t n_rows;
+  double rcond;          /* SC_SEL_PINV */
+} sc_mode_selection;
+
+/* d_out (batch, m / dim).  One pass over the selected rows of d_v; a structure's result does not depend on the batch
+ * size or on its position in the batch, bit for bit. */
+int sc_dev_modes_msf_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                         int dim, const sc_mode_selection* sel, const int64_t* d_counts, double* d_out);
+/* d_out (batch, m / dim, m / dim); norm != 0 divides by sqrt(c_aa c_cc) (nma.py:352-354; 0 / 0 = NaN for an empty
+ * selection, as in NumPy).  One grouped float64 MFMA GEMM per slab of structures: the packed operands take at most
+ * budget_bytes (0: SPRINGCRAFT_MODES_BUDGET_BYTES, else 1 GiB) at a time -- structures in slabs, and when one
+ * structure's operands do not fit, its rows in chunks that accumulate.  The chunks depend on (m, rows, dim, budget)
+ * only and every slab of a call uses the same block tile, so a structure's result does not depend on its position. */
+int sc_dev_modes_dcc_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                         int dim, const sc_mode_selection* sel, const int64_t* d_counts, int norm, int64_t budget_bytes,
+                         double* d_out);
+/* Bytes of device workspace the two entries above hold for such a call (allocated lazily, cached, grown on demand --
+ * the one step of a first call that waits for the stream).  n_sel: rows that carry a weight (nvec - row0, n_rows, or
+ * nvec for SC_SEL_PINV); what: 0 = msf, 1 = dcc; budget_bytes as above. */
+int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
+                                     int64_t budget_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,7 +46,12 @@ EXPORTED_SYMBOLS = [
     "sc_ctx_get_counter", "sc_batch_plan_create", "sc_batch_plan_assemble_f64", "sc_batch_plan_order",
     "sc_batch_plan_destroy", "sc_batch_plan_contacts", "sc_batch_plan_pairs", "sc_batch_plan_fill_from_pairs_f64",
     "sc_eigh_window_f64", "sc_anm_eigen_window_f64", "sc_dev_eigh_window_f64",
+    "sc_dev_modes_msf_f64", "sc_dev_modes_dcc_f64", "sc_dev_modes_workspace_bytes",
 ]
+
+SC_SEL_FROM_ROW = 0
+SC_SEL_ROWS = 1
+SC_SEL_PINV = 2
 
 
 class HipUnavailableError(RuntimeError):
@@ -64,6 +69,18 @@ class TabDesc(C.Structure):
         ("atom_type", C.c_void_p),
         ("chain", C.c_void_p),
         ("bonded_next", C.c_void_p),
+    ]
+
+
+class ModeSelection(C.Structure):
+    """sc_mode_selection: which rows of a batch solver's (w, v) a consumer takes."""
+    _fields_ = [
+        ("kind", C.c_int32),
+        ("reserved", C.c_int32),
+        ("row0", C.c_int64),
+        ("d_rows", C.c_void_p),
+        ("n_rows", C.c_int64),
+        ("rcond", C.c_double),
     ]
 
 
@@ -197,6 +214,9 @@ def lib():
         "sc_modes_msf": (i32, [vp, vp, i64, vp]),
         "sc_modes_dcc": (i32, [vp, vp, i64, i32, vp]),
         "sc_modes_prs": (i32, [vp, dbl, i32, vp]),
+        "sc_dev_modes_msf_f64": (i32, [vp, vp, vp, i64, i64, i64, i32, P(ModeSelection), vp, vp]),
+        "sc_dev_modes_dcc_f64": (i32, [vp, vp, vp, i64, i64, i64, i32, P(ModeSelection), vp, i32, i64, vp]),
+        "sc_dev_modes_workspace_bytes": (i64, [i64, i64, i64, i32, i64, i32, i64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -21,7 +21,9 @@ from . import _hip
 from .forcefield import device_plan
 
 __all__ = ["DeviceBatchSolver", "RaggedBatchSolver", "shard_bounds", "solve_sharded", "partition_lpt", "size_buckets",
-           "solve_ragged"]
+           "solve_ragged", "batch_mode_rows"]
+
+K_B = 1.380649e-23
 
 
 def shard_bounds(n_items, world_size, rank):
@@ -29,6 +31,42 @@ def shard_bounds(n_items, world_size, rank):
     base, rem = divmod(n_items, world_size)
     lo = rank * base + min(rank, rem)
     return lo, lo + base + (1 if rank < rem else 0)
+
+
+def batch_mode_rows(mode_subset, ntriv, subset, m, window=None):
+    """
+    Rows of a batch solver's ``w`` / ``v`` for the GLOBAL ascending mode indices ``mode_subset`` (the reference's
+    ``mode_subset``, nma.py:161-168): pure host arithmetic, checked before any device call.
+
+    ntriv    trivial modes, 6 for an ANM, 1 for a GNM
+    subset   None for a full-spectrum solver (row r is mode r) or its ``subset_by_index=(lo, hi)`` (row r is mode lo + r)
+    m        matrix order
+    window   the solver's ``subset_by_value`` or None; with a window the modes' indices are not known on the host, so
+             ``mode_subset`` must be None and None is returned: the selection is the window itself
+
+    ``mode_subset=None`` gives every solved mode with index >= ``ntriv``.  A trivial index raises the reference's
+    ValueError (nma.py:164-166), an index that was not solved a ValueError naming the solved range.  Repeated and
+    unsorted indices are kept as they are: each occurrence counts (NumPy fancy indexing, nma.py:167-168).
+    Returns an int32 array of row numbers.
+    """
+    if window is not None:
+        if mode_subset is not None:
+            raise ValueError("mode_subset cannot be combined with subset_by_value: the solved modes are the eigenvalue "
+                             "window, whose mode indices are only known on the device")
+        return None
+    lo, hi = (0, m - 1) if subset is None else (int(subset[0]), int(subset[1]))
+    if mode_subset is None:
+        return np.arange(max(ntriv, lo) - lo, hi - lo + 1, dtype=np.int32)
+    idx = np.asarray(mode_subset)
+    if idx.size and idx.dtype.kind not in "iu":
+        raise IndexError("mode_subset must hold integer mode indices")
+    idx = idx.astype(np.int64).reshape(-1)
+    if np.any(idx < ntriv):
+        raise ValueError("Trivial modes are included in the current selection. Please check your input.")
+    if np.any(idx < lo) or np.any(idx > hi):
+        bad = idx[(idx < lo) | (idx > hi)][0]
+        raise ValueError(f"mode {bad} was not solved: this solver holds modes {lo}..{hi}")
+    return (idx - lo).astype(np.int32)
 
 
 class DeviceBatchSolver:
@@ -165,6 +203,105 @@ class DeviceBatchSolver:
                 raise ValueError(f"the eigenvalue window {self.window} holds more than max_modes = {self.max_modes} "
                                  f"eigenpairs for structure(s) {which}; their slots hold the {self.max_modes} lowest")
         return self.w, self.v
+
+    # ---- consumers of the solved modes (reference: nma.py:66-359, there for one model) --------------------------------
+    # Like solve() they ONLY ENQUEUE on the solver's stream and return CUDA tensors that are valid in stream order: no
+    # synchronisation, no host copy of w.  The one exception is the first call of a kind, which allocates its workspace.
+
+    #: bytes the packed GEMM operands of :meth:`dcc` may take at a time (None: SPRINGCRAFT_MODES_BUDGET_BYTES, else 1 GiB)
+    consumer_budget_bytes = None
+
+    @property
+    def _ntriv(self):
+        return 6 if self.dim == 3 else 1
+
+    def _selection(self, mode_subset, pinv_default):
+        """(ModeSelection, counts pointer, objects to keep alive) for a consumer call; every check is on the host."""
+        if self.v is None:
+            raise ValueError("the mode consumers need the eigenvectors: build the solver with want_vectors=True")
+        rows = batch_mode_rows(mode_subset, self._ntriv, self.subset, self.m, self.window)
+        sel = _hip.ModeSelection()
+        keep = None
+        nvec = self.w.shape[1]
+        if self.window is not None:
+            sel.kind, sel.row0 = _hip.SC_SEL_FROM_ROW, 0
+        elif mode_subset is None and pinv_default and self.subset is None:
+            sel.kind, sel.rcond = _hip.SC_SEL_PINV, 1e-6
+        elif mode_subset is None:
+            sel.kind, sel.row0 = _hip.SC_SEL_FROM_ROW, (int(rows[0]) if len(rows) else nvec)
+        else:
+            # through page-locked memory: a copy from pageable memory would make the host wait for the stream
+            host = self.torch.from_numpy(rows).pin_memory()
+            keep = host.to(self.device, non_blocking=True)
+            sel.kind, sel.d_rows, sel.n_rows = _hip.SC_SEL_ROWS, keep.data_ptr(), len(rows)
+        counts = C.c_void_p(self.counts.data_ptr()) if self.window is not None else None
+        self._rows_keep = keep
+        return sel, counts, keep
+
+    def frequencies(self):
+        """
+        (batch, nvec) frequencies ``sqrt(lambda) / (2 pi)`` of the solved modes; rows whose global mode index is trivial
+        enter as ``abs(lambda)`` (nma.py:66-105).  With ``subset_by_value`` the mode indices are not known, so no row is
+        treated as trivial (a negative rounding-level eigenvalue gives NaN, as do the padding rows).
+        """
+        w = self.w.clone()
+        if self.window is None:
+            k = max(0, min(self._ntriv - (self.subset[0] if self.subset else 0), w.shape[1]))
+            w[:, :k] = w[:, :k].abs()
+        return self.torch.sqrt(w) / (2 * np.pi)
+
+    def mean_square_fluctuation(self, mode_subset=None, tem=None, tem_factors=K_B):
+        """
+        (batch, n_atoms) mean square fluctuations ``sum_k v_k^2 / lambda_k`` over the selected modes (nma.py:108-184), one
+        pass over the selected rows of ``v`` on the device.
+
+        ``mode_subset`` holds GLOBAL ascending mode indices as in the reference, never row numbers of ``v``
+        (:func:`batch_mode_rows`); None takes every solved mode that is not trivial.  With ``subset_by_value`` it must be
+        None and the selection is the window: the first ``min(counts[b], max_modes)`` rows of structure b, read from
+        ``counts`` on the device; a structure with an empty window gives zeros.  Whether the window contains trivial modes
+        is the caller's choice of ``vl``: an ANM's six trivial eigenvalues are ~0 at rounding level, of either sign, so
+        ``vl = -inf`` includes them and a small positive ``vl`` (e.g. 1e-6 lambda_max) leaves them out.
+        A structure whose solve failed (NaN eigenvalues) gives NaN, its neighbours are unaffected; behind a window solve such
+        a structure has count 0 and gives the empty window's result.
+        """
+        sel, counts, keep = self._selection(mode_subset, pinv_default=False)
+        out = self.torch.empty((self.batch, self.n_atoms), dtype=self.torch.float64, device=self.device)
+        self.ctx.check(self._L.sc_dev_modes_msf_f64(
+            self.ctx.handle, C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr()), self.m, self.w.shape[1],
+            self.batch, self.dim, C.byref(sel), counts, C.c_void_p(out.data_ptr())))
+        if tem is not None:
+            out *= tem * tem_factors
+        return out
+
+    def bfactor(self, mode_subset=None, tem=None, tem_factors=K_B):
+        """(batch, n_atoms) isotropic B-factors, ``8 pi^2 / 3`` times :meth:`mean_square_fluctuation` (nma.py:187-230)."""
+        out = self.mean_square_fluctuation(mode_subset, tem, tem_factors)
+        out *= (8 * np.pi**2) / 3
+        return out
+
+    def dcc(self, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
+        """
+        (batch, n_atoms, n_atoms) dynamic cross-correlations over the selected modes (nma.py:233-359); ``norm`` divides by
+        ``sqrt(c_aa c_bb)``, ``tem`` is applied after the normalisation as the reference does (nma.py:355-357).
+
+        ``mode_subset`` as in :meth:`mean_square_fluctuation`.  None on a full-spectrum solver takes, per structure, every
+        mode with ``|lambda| > 1e-6 max|lambda|`` of THAT structure -- the reference's covariance rule, see :func:`nma.dcc`
+        -- with the maximum found on the device.  None on a ``subset_by_index`` solver takes every solved mode that is not
+        trivial: the covariance rule needs ``lambda_max``, which such a solve does not compute.  With ``subset_by_value``
+        the selection is the window (see :meth:`mean_square_fluctuation`, also for trivial modes inside it); an empty
+        window gives zeros, and NaN under ``norm=True`` as 0 / 0 does in NumPy.
+        """
+        sel, counts, keep = self._selection(mode_subset, pinv_default=True)
+        n = self.n_atoms
+        out = self.torch.empty((self.batch, n, n), dtype=self.torch.float64, device=self.device)
+        self.ctx.check(self._L.sc_dev_modes_dcc_f64(
+            self.ctx.handle, C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr()), self.m, self.w.shape[1],
+            self.batch, self.dim, C.byref(sel), counts, int(bool(norm)), int(self.consumer_budget_bytes or 0),
+            C.c_void_p(out.data_ptr())))
+        if tem is not None:
+            out *= tem
+            out *= tem_factors
+        return out
 
 
 class RaggedBatchSolver:

@@ -156,6 +156,19 @@ int sc_reserve_win(sc_ctx* ctx, size_t bytes) {
   return SC_OK;
 }
 
+int sc_reserve_modes(sc_ctx* ctx, size_t bytes) {
+  if (bytes <= ctx->modes_ws_bytes) return SC_OK;
+  if (ctx->modes_ws) {
+    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SC_HIP(ctx, hipFree(ctx->modes_ws));
+    ctx->modes_ws = nullptr;
+    ctx->modes_ws_bytes = 0;
+  }
+  SC_HIP(ctx, hipMalloc(&ctx->modes_ws, bytes));
+  ctx->modes_ws_bytes = bytes;
+  return SC_OK;
+}
+
 int sc_reserve_dc_aux(sc_ctx* ctx, size_t bytes) {
   if (bytes <= ctx->dc_aux_bytes) return SC_OK;
   if (ctx->dc_aux) {
@@ -384,6 +397,7 @@ void sc_ctx_destroy(sc_ctx* ctx) {
   if (ctx->dc_aux) (void)hipFree(ctx->dc_aux);
   if (ctx->pinv_ws) (void)hipFree(ctx->pinv_ws);
   if (ctx->win_ws) (void)hipFree(ctx->win_ws);
+  if (ctx->modes_ws) (void)hipFree(ctx->modes_ws);
   if (ctx->d_status) (void)hipFree(ctx->d_status);
   if (ctx->d_zeros) (void)hipFree(ctx->d_zeros);
   if (ctx->d_chase_ctl) (void)hipFree(ctx->d_chase_ctl);
@@ -948,6 +962,57 @@ int sc_ctx_set_two_stage(sc_ctx* ctx, int mode) {
 int64_t sc_eigh_workspace_bytes(int64_t n, int64_t batch, int want_vectors) {
   if (n <= 0 || batch <= 0) return 0;
   return (int64_t)eigh_workspace_bytes(n, batch, want_vectors != 0);
+}
+
+// ---- batch consumers (batch_consumers.hip) -------------------------------------------------------------------------
+static int check_modes_args(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                            int dim, const sc_mode_selection* sel, const double* d_out) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  if (m <= 0 || nvec <= 0 || batch <= 0 || !d_w || !d_v || !sel || !d_out)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  if ((dim != 1 && dim != 3) || m % dim != 0)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "dim must be 1 or 3 and divide m = %lld", (long long)m);
+  if (m > INT32_MAX || nvec > m || batch > INT32_MAX || (size_t)batch * nvec > (size_t)INT32_MAX)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "(batch, nvec, m) = (%lld, %lld, %lld) is not a solver's result shape",
+                        (long long)batch, (long long)nvec, (long long)m);
+  switch (sel->kind) {
+    case SC_SEL_FROM_ROW:
+      if (sel->row0 < 0 || sel->row0 > nvec)
+        return sc_set_error(ctx, SC_ERR_INDEX, "row0 %lld outside 0..%lld", (long long)sel->row0, (long long)nvec);
+      break;
+    case SC_SEL_ROWS:
+      if (sel->n_rows < 0 || sel->n_rows > INT32_MAX / 4 || (sel->n_rows > 0 && !sel->d_rows))
+        return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad row list");
+      break;
+    case SC_SEL_PINV:
+      if (!(sel->rcond >= 0.0)) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "rcond must be >= 0");
+      break;
+    default:
+      return sc_set_error(ctx, SC_ERR_INVALID_ARG, "unknown selection kind %d", (int)sel->kind);
+  }
+  return SC_OK;
+}
+
+int sc_dev_modes_msf_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                         int dim, const sc_mode_selection* sel, const int64_t* d_counts, double* d_out) {
+  SC_TRY(check_modes_args(ctx, d_w, d_v, m, nvec, batch, dim, sel, d_out));
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return batch_msf_device(ctx, d_w, d_v, m, nvec, batch, dim, *sel, d_counts, 0, d_out);
+}
+
+int sc_dev_modes_dcc_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                         int dim, const sc_mode_selection* sel, const int64_t* d_counts, int norm, int64_t budget_bytes,
+                         double* d_out) {
+  SC_TRY(check_modes_args(ctx, d_w, d_v, m, nvec, batch, dim, sel, d_out));
+  if (budget_bytes < 0) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "budget_bytes must be >= 0");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return batch_dcc_device(ctx, d_w, d_v, m, nvec, batch, dim, *sel, d_counts, norm, (size_t)budget_bytes, d_out);
+}
+
+int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
+                                     int64_t budget_bytes) {
+  if (m <= 0 || nvec <= 0 || batch <= 0 || n_sel < 0 || (dim != 1 && dim != 3) || budget_bytes < 0) return 0;
+  return (int64_t)batch_modes_workspace_bytes(m, nvec, batch, dim, n_sel, what, (size_t)budget_bytes);
 }
 
 // ---- ragged / decorated batches ---------------------------------------------------------------------------------

@@ -45,6 +45,10 @@ struct sc_ctx {
   // m eigenpairs.  Growing `ws` at that point would move the tridiagonalisation's slabs, which are still needed
   void* win_ws = nullptr;
   size_t win_ws_bytes = 0;
+  // weights, partial sums and GEMM operands of the batch consumers (batch_consumers.hip): a buffer of their own, so that
+  // a consumer enqueued behind a solve never grows -- and thereby moves -- a buffer that solve still uses
+  void* modes_ws = nullptr;
+  size_t modes_ws_bytes = 0;
 
   // host -> device uploads of descriptor tables without a stream synchronisation: the tables are copied into this
   // pinned arena first (sc_stage_upload) and the arena is recycled once the event recorded at the end of the solve
@@ -190,6 +194,7 @@ int sc_reserve_scratch(sc_ctx* ctx, size_t bytes);
 int sc_reserve_dc_aux(sc_ctx* ctx, size_t bytes);
 int sc_reserve_pinv(sc_ctx* ctx, size_t bytes);
 int sc_reserve_win(sc_ctx* ctx, size_t bytes);
+int sc_reserve_modes(sc_ctx* ctx, size_t bytes);
 // d_dst <- bytes at h_src, enqueued on ctx->stream; h_src may be released as soon as the call returns
 int sc_stage_upload(sc_ctx* ctx, void* d_dst, const void* h_src, size_t bytes);
 // end of a solve that used sc_stage_upload: the arena may be reused when everything enqueued so far has run
@@ -289,6 +294,18 @@ int modes_dcc_device(sc_ctx* ctx, const double* d_v, const double* d_w, int64_t 
                      int64_t nsel, int norm, char* scratch, double* d_out);
 int modes_prs_device(sc_ctx* ctx, const double* d_v, const double* d_w, int64_t n, double rcond, int norm,
                      char* scratch, double* d_out);
+
+// ---- the same quantities for a batch, on the solver's own (w, v, counts) tensors (batch_consumers.hip) ----------
+// what: 0 = msf, 1 = dcc.  n_sel: weighted rows per structure (batch_modes_nsel).  budget: bytes the partial sums (msf) /
+// the packed GEMM operands (dcc) may take, 0 = modes_budget_default().
+size_t modes_budget_default();
+int64_t batch_modes_nsel(const sc_mode_selection& sel, int64_t nvec);
+size_t batch_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
+                                   size_t budget);
+int batch_msf_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
+                     const sc_mode_selection& sel, const int64_t* d_counts, size_t budget, double* d_out);
+int batch_dcc_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
+                     const sc_mode_selection& sel, const int64_t* d_counts, int norm, size_t budget, double* d_out);
 
 // Raises a kernel's dynamic LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) once per (device, kernel).  The
 // attribute belongs to the device that is current when it is set: a function-local static done-flag (rounds 2-5) served

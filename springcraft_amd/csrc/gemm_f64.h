@@ -48,8 +48,13 @@ constexpr int kGemmTile = 3;
 // lower_grid: every record of the launch is square, lower_only with row_off = col_off = 0 (the SYR2K of the band
 // reduction): only the tiles on and below the diagonal are launched (layout kGemmAmBn, no split-K).
 constexpr int kGemmAmBk = 0, kGemmAkBk = 1, kGemmAmBn = 2;
+// pin_tile: 0 = the block tile follows the launch size; 1 / 2 / 3 = 128 x 128 / 128 x 64 / 64 x 64 whatever the size, for
+// callers that cut one piece of work into several launches and want every piece to round alike (gemm_f64_tile returns
+// the code the size rule picks for a launch).
 int launch_gemm_f64(sc_ctx* ctx, const GemmDesc* d_desc, int count, int max_m, int max_n, int tile,
-                    int split_k = 1, bool gather = false, bool tri = false, int layout = -1, bool lower_grid = false);
+                    int split_k = 1, bool gather = false, bool tri = false, int layout = -1, bool lower_grid = false,
+                    int pin_tile = 0);
+int gemm_f64_tile(const sc_ctx* ctx, int count, int max_m, int max_n, int layout);
 
 // The role-split persistent kernel k_gemm3 (gemm3.hip) for launches whose records share (m, n, k): returns SC_OK when it
 // took the launch, 1 when the launch is not one it takes (the caller then uses launch_gemm_f64).  alpha must be 1 and beta

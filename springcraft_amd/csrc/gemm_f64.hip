@@ -426,9 +426,10 @@ namespace {
 int g_gemm2_force_tile = 0;   // debugging (sc_dbg_gemm_bench): 1 = 128 x 128, 2 = 128 x 64, 3 = 64 x 64
 // block tile of k_gemm2: 128-wide in a dimension when the problem is at least that wide there and the launch still has
 // >= 2 workgroups per CU (lower-only launches: about half of the square grid does work)
-void gemm2_tile(const sc_ctx* ctx, int count, int max_m, int max_n, int split_k, int layout, int* bm, int* bn) {
+void gemm2_tile(const sc_ctx* ctx, int count, int max_m, int max_n, int split_k, int layout, int* bm, int* bn,
+                int pin_tile = 0) {
   static const int env_force = [] { const char* e = getenv("SPRINGCRAFT_GEMM2_TILE"); return e ? atoi(e) : 0; }();
-  const int force = g_gemm2_force_tile ? g_gemm2_force_tile : env_force;
+  const int force = g_gemm2_force_tile ? g_gemm2_force_tile : env_force ? env_force : pin_tile;
   if (force == 1 && layout != kGemmAkBk) { *bm = 128; *bn = 128; return; }
   if (force == 1) { *bm = 128; *bn = 64; return; }
   if (force == 2) { *bm = 128; *bn = 64; return; }
@@ -443,8 +444,14 @@ void gemm2_tile(const sc_ctx* ctx, int count, int max_m, int max_n, int split_k,
 }
 }  // namespace
 
+int gemm_f64_tile(const sc_ctx* ctx, int count, int max_m, int max_n, int layout) {
+  int bm, bn;
+  gemm2_tile(ctx, count, max_m, max_n, 1, layout, &bm, &bn);
+  return bm == 128 ? (bn == 128 ? 1 : 2) : 3;
+}
+
 int launch_gemm_f64(sc_ctx* ctx, const GemmDesc* d_desc, int count, int max_m, int max_n, int tile,
-                    int split_k, bool gather, bool tri, int layout, bool lower_grid) {
+                    int split_k, bool gather, bool tri, int layout, bool lower_grid, int pin_tile) {
   static const bool no_lower = getenv("SPRINGCRAFT_GEMM_NO_LOWER_GRID") != nullptr;
   const bool lower = lower_grid && !no_lower && layout == kGemmAmBn && !tri && !gather && split_k <= 1 && max_m == max_n;
   if (count <= 0 || max_m <= 0 || max_n <= 0) return SC_OK;
@@ -456,7 +463,7 @@ int launch_gemm_f64(sc_ctx* ctx, const GemmDesc* d_desc, int count, int max_m, i
     const int max_rec = 65535 / split_k;
     for (int r0 = 0; r0 < count; r0 += max_rec)
       SC_TRY(launch_gemm_f64(ctx, d_desc + r0, std::min(max_rec, count - r0), max_m, max_n, tile, split_k, gather, tri,
-                             layout, lower_grid));
+                             layout, lower_grid, pin_tile));
     return SC_OK;
   }
   hipStream_t st = ctx->stream;
@@ -475,7 +482,7 @@ int launch_gemm_f64(sc_ctx* ctx, const GemmDesc* d_desc, int count, int max_m, i
   }
   if (!gather && layout >= 0 && layout <= 2 && !(tri && layout == kGemmAmBn)) {
     int bm, bn;
-    gemm2_tile(ctx, count, max_m, max_n, split_k, layout, &bm, &bn);
+    gemm2_tile(ctx, count, max_m, max_n, split_k, layout, &bm, &bn, pin_tile);
     const long long gz = (long long)count * split_k;
     if (gz > 65535) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "GEMM launch with %lld records x slices (max 65535)", gz);
     dim3 grid((unsigned)((max_m + bm - 1) / bm), (unsigned)((max_n + bn - 1) / bn), (unsigned)gz);
