@@ -71,7 +71,7 @@ int sc_dbg_two_stage(sc_ctx* ctx, const double* a, int n, double* band_out, doub
  * out[64 workgroups][8 waves][16 sums + diamond count].  tools/bt2_stamps.py */
 int sc_dbg_bt2_stamps(unsigned long long* out);
 
-/* Shader clock while the most recent k_bt2_apply / k_bt2_role launch ran (library built with -DBT2_CLOCK; returns 1
+/* Shader clock while the most recent k_bt2_apply launch ran (library built with -DBT2_CLOCK; returns 1
  * otherwise): out2 = {shader cycles (s_memtime), 100 MHz ticks (s_memrealtime)} over the life of wave 0 of workgroup 0.
  * tools/bt2_clock.py */
 int sc_dbg_bt2_clock(unsigned long long* out2);
@@ -88,8 +88,7 @@ int sc_dbg_bulge_stamps(unsigned long long* out6);
  * 48 entries.  [0..15] thread 0 (team A): [0..6] = cycles between the barriers of a common step (wait + [0], block reads +
  * [1], E right update + reflector, column sums + D image, E left update + D products, w, D update), [8] = steps, [9] =
  * common steps, [12] = block reads alone; [16..31] thread 256 (team B), same layout, [23] its look at the predecessor pair, [30] steps in which it polled, [26] slot reads, [27] store drain,
- * [29] D update + stores; [32..47] lane 0 of the first loader wave (k_bulge_pair<1>): [32] wait for E, [33] barrier [0],
- * [34] [1] [2], [35] wait for D, [36] [3] [4], [37] E requests, [38] [5] [6] [7], [39] D requests, [40] steps counted. */
+ * [29] D update + stores; [32..47] unused (zero). */
 int sc_dbg_pair_stamps(unsigned long long* out48);
 /* The same for the persistent chase with one sweep per workgroup (k_bulge_chase; library built with -DCHASE_STAMPS, else
  * returns 1): out16[1..11] = cycles of all waves between eleven points of a task, summed over all tasks since the last call

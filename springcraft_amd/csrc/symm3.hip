@@ -47,6 +47,7 @@
 #include <vector>
 
 #include "gemm_f64.h"
+#include "twostage_policy.h"
 
 namespace {
 
@@ -500,7 +501,7 @@ bool g_symm3_any_size = false;   // debugging (sc_dbg_symm3_host): take every la
 
 // Whether launch_symm3 takes X = A V for `count` symmetric matrices of order m with `split` K slices (see the header).
 static bool symm3_takes(sc_ctx* ctx, int count, int m, int split, bool aligned16, bool any_size) {
-  static const int env = [] { const char* e = getenv("SPRINGCRAFT_SYMM3"); return e ? atoi(e) : 1; }();
+  const int env = sc_host::two_stage_env().symm3;   // SPRINGCRAFT_SYMM3, read with the rest of the two-stage environment
   if (env == 0 || count <= 0 || !aligned16) return false;
   if (m < 256 || (m & 1)) return false;
   if (split < 1 || split > 16 || ((m + 15) / 16 + 8) / split < 4) return false;   // (every item has a few K steps)

@@ -22,10 +22,11 @@
 #include <vector>
 
 #include "eigh_internal.h"
+#include "twostage_policy.h"
 
 namespace {
 
-constexpr int kB = 64;            // band half-width = panel width = reflector length of stage 2
+constexpr int kB = sc_host::kBand;  // band half-width = panel width = reflector length of stage 2
 constexpr int kG = 64;            // sweeps per diamond
 constexpr int kLdab = 2 * kB;     // rows of the band storage: AB(i, j) = ab[(i - j) + j * kLdab]
 constexpr int kDiaLd = 128;       // leading dimension of a diamond (kB + kG - 1 = 127 rows used)
@@ -781,9 +782,8 @@ __global__ __launch_bounds__(NT) void k_panel_wg(double* __restrict__ a_all, lon
 // matrices x G well below the number of CUs; a wait that runs into its bound (never expected: seconds) raises a flag that
 // every workgroup sees in its polls, the kernel ends, the host returns an error and the context does not use the kernel
 // again.  Sequence numbers are unique within a solve ((panel + 1) * 128 + step) and the records are zeroed per solve.
-constexpr int kCoopRows = 256;
+constexpr int kCoopRows = sc_host::kCoopRows;
 constexpr int kCoopLd = kCoopRows + 1;
-constexpr int kCoopMaxG = 128;
 constexpr int kCoopVals = 8 * kB;                 // values of one block exchange (M and the Gram matrix)
 constexpr size_t kCoopLdsBytes = sizeof(double) * ((size_t)kB * kCoopLd + kCoopRows * 8 + 8 * kB + 64 + 16 + kB + 128 + 2);
 // workspace of one matrix (16-byte records): column records [2][G][16] | block partials [G][512] | block totals [512]
@@ -1315,7 +1315,7 @@ __global__ __launch_bounds__(256) void k_sb_clean(double* __restrict__ a_all, lo
 }
 
 // Number of chase positions of sweep s: blocks of kB rows from row s+1 to n-1
-__host__ __device__ inline int chase_len(int n, int s) { return (n - 1 - s + kB - 1) / kB; }
+using sc_host::chase_len;
 
 // Diagnostic build (-DBULGE_STAMPS): shader cycles of wave 0 between five points of every task, summed over all tasks
 // since the last read (sc_dbg_bulge_stamps, tools/bulge_stamps.py); no stamp executes in the normal build.
@@ -1605,7 +1605,7 @@ __global__ __launch_bounds__(256) void k_chase_finish(double* __restrict__ sb_al
 // Records: a ring of kEarlyRing per sweep, slot k mod kEarlyRing holds {beta of task k, k + 1}; written and read as ONE
 // 16-byte access.  A reader that finds a later tag knows that its task (s - 1, k + 1) is long complete and takes the
 // entry from the band instead.
-constexpr int kEarlyRing = 8;
+constexpr int kEarlyRing = sc_host::kEarlyRing;
 __device__ __forceinline__ void st16(void* p, v4i v) { asm volatile("global_store_dwordx4 %0, %1, off" ::"v"(p), "v"(v) : "memory"); }
 __device__ __forceinline__ void st16_sc1(void* p, v4i v) { asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory"); }
 // a band entry as the chase's workgroups hand it on.  SPREAD = 0: all workgroups of a matrix sit behind ONE L2, a plain
@@ -1984,21 +1984,18 @@ __global__ __launch_bounds__(256, 2) void k_bulge_chase(double* __restrict__ sb_
 // workgroup writes its live slots back to the band and publishes both sweeps' counts, so the per-wavefront launches can
 // finish the chase from the counters exactly as after k_bulge_chase.
 constexpr int kSlotE = kB * (kB + 1);          // E block, row stride 65 (conflict-free column access)
-// D block, lower triangle packed by rows: (i, j) at i (i + 1) / 2 + j (2080 doubles).  The region is a little larger: the
-// loader waves (below) land the triangle packed by COLUMNS in 16-byte pieces, column j as ceil((64 - j) / 2) pieces from
-// piece pair_cc(j) on: 1056 pieces, fetched by 17 LDS-DMA instructions of 64 pieces = 2176 doubles.
+// D block, lower triangle packed by rows: (i, j) at i (i + 1) / 2 + j (2080 doubles).  The region is a little larger
+// (2176 doubles: sized in round 6 for a form of the kernel that has been removed; kept, so that the
+// LDS layout and the launch stay what they were).
 constexpr int kSlotD = 17 * 128;
 constexpr int kSlot = kSlotE + kSlotD;
-// first 16-byte piece of column jj of the landed triangle: sum over j' < jj of ceil((64 - j') / 2)
-__host__ __device__ constexpr int pair_cc(int jj) { return 32 * jj - (jj >> 1) * ((jj - 1) >> 1); }
-static_assert(pair_cc(0) == 0 && pair_cc(1) == 32 && pair_cc(2) == 64 && pair_cc(3) == 95 && pair_cc(64) == 1056, "pieces");
 constexpr int kTeamLds = 2 * kB + kB + 4 * kB + 8;   // vbuf[2][64], u[64], red[256], tau, beta (+ pad)
 constexpr size_t kPairLdsBytes = sizeof(double) * (3 * kSlot + 2 * kTeamLds);
 
 // Diagnostic build (-DPAIR_STAMPS): shader cycles of thread 0 between the barriers of every step, summed over all steps
 // of all workgroups since the last read (sc_dbg_pair_stamps, tools/pair_stamps.py); nothing of it in the normal build.
-// (round 6: the sums are kept in LDS -- one writer per entry: thread 0 [0..15], thread 256 [16..31], lane 0 of the first
-// loader wave [32..47] -- and added to the global table when the thread leaves the kernel: a global atomic per stamp
+// (round 6: the sums are kept in LDS -- one writer per entry: thread 0 [0..15], thread 256 [16..31]; [32..47] are
+// unused -- and added to the global table when the thread leaves the kernel: a global atomic per stamp
 // more than doubled the stage's time)
 #ifdef PAIR_STAMPS
 __device__ unsigned long long g_pair_stamps[48];
@@ -2006,7 +2003,6 @@ __shared__ unsigned long long s_pair_stamps[48];
 #define PAIR_STAMP(var) unsigned long long var; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(var)::"memory");
 #define PAIR_ACC(slot, a, b) if (tid == 0) s_pair_stamps[slot] += (b) - (a);
 #define PAIR_ACC_B(slot, a, b) if (tid == 256) s_pair_stamps[16 + (slot)] += (b) - (a);
-#define PAIR_ACC_L(slot, a, b) if (lw == 0 && lane == 0) s_pair_stamps[32 + (slot)] += (b) - (a);
 #define PAIR_FLUSH(first)                                                                         \
   for (int i_ = 0; i_ < 16; ++i_)                                                                 \
     if (s_pair_stamps[(first) + i_]) atomicAdd(&g_pair_stamps[(first) + i_], s_pair_stamps[(first) + i_]);
@@ -2014,7 +2010,6 @@ __shared__ unsigned long long s_pair_stamps[48];
 #define PAIR_STAMP(var)
 #define PAIR_ACC(slot, a, b)
 #define PAIR_ACC_B(slot, a, b)
-#define PAIR_ACC_L(slot, a, b)
 #define PAIR_FLUSH(first)
 #endif
 
@@ -2034,16 +2029,12 @@ struct PairStepArgs {
   size_t dia;
   int cc;
   int tid;
-  const int* prev;   // the predecessor sweep's counter (null: none, or no early read) and the stop flag: read behind [1]
-  const int* ctl;
 };
 
-// LOADER = 1: team A's blocks have been landed in its slot by the loader waves (k_bulge_pair's header): E column by column
-// ((i, j) at j * 64 + i), the triangle of D by columns in 16-byte pieces (pair_cc) -- A issues no global load.
-template <int TEAM, int LOADER>
-__device__ __forceinline__ void pair_step_full(const PairStepArgs& P, double& tau_p, int& pend_k, int& h_have, int& h_stop) {
+template <int TEAM>
+__device__ __forceinline__ void pair_step_full(const PairStepArgs& P, double& tau_p, int& pend_k) {
   const int tid = P.tid, tt = tid & 255, i = tid & 63;
-  const int q = LOADER ? __builtin_amdgcn_readfirstlane((tid >> 6) & 3) : (tid >> 6) & 3;
+  const int q = (tid >> 6) & 3;
   const int k = P.k, s = P.s;
   const int r0 = s + 1 + k * kB;
   ldptr vp = P.vbuf + ((k + 1) & 1) * kB;
@@ -2059,14 +2050,8 @@ __device__ __forceinline__ void pair_step_full(const PairStepArgs& P, double& ta
   double d16[16], t16[16], vr[16];
   PAIR_STAMP(f0)
   if (TEAM == 0) {
-    if (LOADER) {
-      const ldptr ecol = Eimg + q * 16 * kB + i;
 #pragma unroll
-      for (int c = 0; c < 16; ++c) t16[c] = ecol[c * kB];
-    } else {
-#pragma unroll
-      for (int c = 0; c < 16; ++c) t16[c] = ld_l2(ebase_k + (o_e + (unsigned)(c * (kLdab - 1))));
-    }
+    for (int c = 0; c < 16; ++c) t16[c] = ld_l2(ebase_k + (o_e + (unsigned)(c * (kLdab - 1))));
   } else {
     const ldptr En = P.slots + ((k + 1) % 3) * kSlot;
     const int i1 = min(i + 1, kB - 1);
@@ -2095,13 +2080,7 @@ __device__ __forceinline__ void pair_step_full(const PairStepArgs& P, double& ta
   if (TEAM == 1) {
     if (tt == 0 && pend_k >= 0) __hip_atomic_store(P.prog + s, pend_k + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     pend_k = k;
-    // the NEXT step's look at the predecessor pair, requested a step ahead (k_bulge_pair: "early look"): this wave has no
-    // load in flight and its stores of this step come later, so the values are there when the step ends
-    if (tt == 0 && P.prev) {
-      h_have = __hip_atomic_load(P.prev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      h_stop = __hip_atomic_load(P.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  } else if (!LOADER) {
+  } else {
     // D is not touched before step (5): its loads are issued here, behind the barrier, so that the other team does not
     // wait for their issue (under load the memory pipeline takes a block's 16 load instructions per wave slowly: issuing
     // them costs as much as waiting for the data) and land behind steps (2)-(4).  Entries above the diagonal: whatever
@@ -2142,13 +2121,6 @@ __device__ __forceinline__ void pair_step_full(const PairStepArgs& P, double& ta
 #pragma unroll
     for (int c = 0; c < 16; ++c) a += ecol[c * (kB + 1)] * vr[c];
     red[q * kB + i] = a;
-  }
-  if (TEAM == 0 && LOADER) {
-    // the landed triangle (complete since barrier [3]) into the registers, row i: entry (i, jj) is entry i - jj of
-    // column jj; above the diagonal whatever lies in front of the column (masked below).  All of it is read before
-    // barrier [4], behind which the row-packed image takes the region over.
-#pragma unroll
-    for (int c = 0; c < 16; ++c) d16[c] = Dimg[2 * pair_cc(q * 16 + c) - (q * 16 + c) + i];
   }
   lds_barrier();                                                                  // [4]
   if (tt < kB) u[tt] = P.sc[0] * ((red[tt] + red[kB + tt]) + (red[2 * kB + tt] + red[3 * kB + tt]));
@@ -2236,17 +2208,12 @@ struct PairGenArgs {
   int n, s, k, my_len, team, to_lds;
   size_t dia0;
   int cc, tid;
-  const int* prev;   // (as in PairStepArgs)
-  const int* ctl;
 };
 struct PairCarry {
   double tau_p;
   int pend_k;
-  int h_have, h_stop;
 };
 
-// (one copy per kernel instantiation: a shared copy would be compiled for the smaller register budget of the two)
-template <int LOADER>
 __device__ __noinline__ PairCarry pair_step_general(const PairGenArgs P, double tau_p, int pend_k) {
   double* const ab = P.ab;
   const ldptr slots = P.slots, vbuf = P.vbuf, u = P.u, red = P.red, sc = P.sc;
@@ -2326,12 +2293,7 @@ __device__ __noinline__ PairCarry pair_step_general(const PairGenArgs P, double 
     if (pend_k + 1 == my_len) atomicAdd(P.sweeps_done, 1);
   }
   pend_k = -1;
-  int h_have = 0, h_stop = 0;
-  if (team == 1 && tt == 0 && P.prev) {   // the next step's early look (see pair_step_full)
-    h_have = __hip_atomic_load(P.prev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    h_stop = __hip_atomic_load(P.ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  
+
   // ---- (2) u = tau_p E vp: partial sums over this wave's 16 columns
   if (eph) {
     double a = 0.0;
@@ -2442,7 +2404,7 @@ __device__ __noinline__ PairCarry pair_step_general(const PairGenArgs P, double 
     tau_p = tau_now;
     if (!to_lds) pend_k = k;   // published once the stores have drained: behind the next step's loads
   }
-  return PairCarry{tau_p, pend_k, h_have, h_stop};
+  return PairCarry{tau_p, pend_k};
 }
 
 // (the few fields of the band workspace's layout the kernel needs, instead of all of SbLayout in scalar registers)
@@ -2451,188 +2413,14 @@ struct PairLayout {
   long long slab, ab, vd, tau2;
 };
 
-// ---- Loader waves (round 6, LOADER = 1: 768 threads).  In the form above only team A's 256 threads issue global loads,
-// in one of the step's eight phases, and wait for them in the next: the memory system has this CU's requests in flight
-// for a fraction of the step.  Here waves 8-11 issue nothing but LDS-DMA (global_load_lds_dwordx4: 64 x 16 bytes from
-// per-lane addresses to one contiguous KB of LDS, no VGPR for the data, no VALU instruction in steady state) and fetch
-// team A's blocks of position m + 1 while the compute waves are in step m:
-//   * where to: the slot of position m + 1 is the slot of position m - 2, which team B emptied at the start of step m and
-//     uses as its scratch image -- the E image until barrier [4], the D image until barrier [6].  So E(m + 1) is requested
-//     behind [4] (32 instructions: two columns each, 8 per loader wave behind ONE write of M0) and the triangle of
-//     D(m + 1) behind [7] (17 instructions of 64 pieces, see kSlotD; the second M0 write of a wave waits for its E pieces
-//     in flight -- behind [7] nobody waits for the loader before the next [0], which needs E landed anyway);
-//   * handshake: a loader wave arrives at the next step's barrier [0] with its E pieces landed (s_waitcnt vmcnt(#D)) and
-//     at barrier [3] with everything landed.  Team A reads E from the slot in front of [1] (column-major as landed: row
-//     accesses are conflict-free), re-writes it row-major behind [2] as before; it reads its rows of D between [3] and
-//     [4] and writes the row-packed image behind [4] as before;
-//   * only the common step is served (both teams on full blocks): the loaders evaluate the same predicate for m + 1 as
-//     the compute waves, the general step loads for itself as before;
-//   * the predecessor pair must have left position m + 1 by the time it is fetched: thread 0's wait in front of step m
-//     covers m + 3 instead of m + 2 of its tasks when a fetch follows;
-//   * only the triangle of D crosses the fabric (17 KB instead of the 32 KB square whose upper half was masked).
-// The loader waves execute every workgroup barrier of the compute waves, in the same number.
+// whether step m of a pair is the common one (both teams on full blocks, neither at a sweep start)
 __device__ __forceinline__ bool pair_common_step(bool hasB, int m, int lenA, int sA, int n) {
   return hasB && m >= 3 && m < lenA && sA + 1 + (m + 1) * kB <= n;
 }
 
-// The loader waves of k_bulge_pair<1> (its header): the same claims, steps and workgroup barriers as the compute waves.
-__device__ __forceinline__ void pair_loader_run(double* __restrict__ sb_all, const PairLayout& SL, int nxcd, int xcd, int slot,
-                                                int mpx, const volatile __attribute__((address_space(3))) int* s_claim,
-                                                const volatile __attribute__((address_space(3))) int* s_go,
-                                                unsigned lds_base, int lw, int lane) {
-  const int n = SL.n;
-  // per-lane byte offsets of this wave's pieces, once per kernel (nothing of it changes from step to step).
-  // E: wave lw fetches column pairs 8 lw .. 8 lw + 7; instruction x lands at M0 + (1024 x - 3584) + 16 lane; lanes 0-31
-  // take rows (2 l, 2 l + 1) of the even column, lanes 32-63 those of the odd one (its pieces start 127 doubles later).
-  // D: wave lw fetches instructions d0 .. d0 + nd - 1 of the 17 (5, 4, 4, 4), instruction x lands at M0 + (1024 x - 2048)
-  // + 16 lane; piece g = 64 (d0 + x) + lane is piece g - pair_cc(j) of column j; pieces beyond the 1056 re-read the last.
-  const int ld_d0 = lw == 0 ? 0 : 1 + 4 * lw;
-  unsigned voff_e[8], voff_d[5];
-  {
-    const unsigned lane_off = lane < 32 ? 16u * lane : (unsigned)(8 * (kLdab - 1)) + 16u * (lane - 32);
-#pragma unroll
-    for (int x = 0; x < 8; ++x) voff_e[x] = lane_off + (unsigned)(16 * (kLdab - 1) * (8 * lw + x)) - (unsigned)(1024 * x) + 3584u;
-#pragma unroll
-    for (int x = 0; x < 5; ++x) {
-      const int g = min(64 * (ld_d0 + x) + lane, pair_cc(kB) - 1);
-      int j = 0;
-      while (pair_cc(j + 1) <= g) ++j;
-      voff_d[x] = (unsigned)(8 * (j * kLdab + 2 * (g - pair_cc(j)))) - (unsigned)(1024 * x) + 2048u;
-    }
-  }
-  int cur = slot % mpx, exhausted = 0;
-  while (exhausted < mpx) {
-    const int b = xcd + nxcd * cur;
-    __builtin_amdgcn_s_barrier();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const int sA = 2 * __builtin_amdgcn_readfirstlane(*s_claim);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    if (sA > n - 3) {
-      ++exhausted;
-      cur = cur + 1 < mpx ? cur + 1 : 0;
-      continue;
-    }
-    exhausted = 0;
-    const unsigned long long ab_u = (unsigned long long)(size_t)wave_uniform(sb_all + (size_t)b * SL.slab + SL.ab);
-    const bool hasB = sA + 1 <= n - 3;
-    const int lenA = chase_len(n, sA);
-    const int nsteps = hasB ? lenA + 2 : lenA;
-    for (int m = 0; m < nsteps; ++m) {
-      PAIR_STAMP(l0)
-      if (pair_common_step(hasB, m, lenA, sA, n)) {
-        // this step's E pieces have landed (the D pieces requested after them may still be on their way)
-        if (lw == 0) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      }
-      PAIR_STAMP(l1)
-      __builtin_amdgcn_s_barrier();                                                     // [0]
-      PAIR_STAMP(l2)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      const int go = __builtin_amdgcn_readfirstlane(*s_go);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (!go) {
-        // give-up: the pieces in flight land in the slot nobody flushes; then the compute waves' barriers
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (hasB) __builtin_amdgcn_s_barrier();
-        if (lw == 0 && lane == 0) { PAIR_FLUSH(32) }
-        return;
-      }
-      // ---- a step of a loader wave: the compute waves' seven barriers, position m + 1 requested behind [4] and [7]
-      const bool fetch = pair_common_step(hasB, m + 1, lenA, sA, n);
-      __builtin_amdgcn_s_barrier();                                                     // [1]
-      __builtin_amdgcn_s_barrier();                                                     // [2]
-      PAIR_STAMP(l3)
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this step's D pieces have landed
-      PAIR_STAMP(l4)
-      __builtin_amdgcn_s_barrier();                                                     // [3]
-      __builtin_amdgcn_s_barrier();                                                     // [4]
-      PAIR_STAMP(l5)
-      const int r0n = sA + 1 + (m + 1) * kB;
-      const unsigned slot_b = lds_base + (unsigned)(((m + 1) % 3) * kSlot * 8);
-#ifdef PAIR_VAR_NODMA
-      if (false) {
-#else
-      if (fetch) {
-#endif
-        const unsigned long long eb = ab_u + ((unsigned long long)(r0n - kB) * kLdab + kB) * 8ull;   // E(0, 0) of position m + 1
-        const unsigned m0v = (unsigned)__builtin_amdgcn_readfirstlane((int)(slot_b + (unsigned)(1024 * 8 * lw + 3584)));
-        asm volatile(
-            "s_mov_b32 m0, %0\n\ts_nop 4\n\t"
-            "global_load_lds_dwordx4 %1, %9 offset:-3584\n\t"
-            "global_load_lds_dwordx4 %2, %9 offset:-2560\n\t"
-            "global_load_lds_dwordx4 %3, %9 offset:-1536\n\t"
-            "global_load_lds_dwordx4 %4, %9 offset:-512\n\t"
-            "global_load_lds_dwordx4 %5, %9 offset:512\n\t"
-            "global_load_lds_dwordx4 %6, %9 offset:1536\n\t"
-            "global_load_lds_dwordx4 %7, %9 offset:2560\n\t"
-            "global_load_lds_dwordx4 %8, %9 offset:3584"
-            :
-            : "s"(m0v), "v"(voff_e[0]), "v"(voff_e[1]), "v"(voff_e[2]), "v"(voff_e[3]), "v"(voff_e[4]), "v"(voff_e[5]),
-              "v"(voff_e[6]), "v"(voff_e[7]), "s"(eb)
-            : "memory");
-      }
-      PAIR_STAMP(l6)
-      __builtin_amdgcn_s_barrier();                                                     // [5]
-      __builtin_amdgcn_s_barrier();                                                     // [6]
-      __builtin_amdgcn_s_barrier();                                                     // [7]
-      PAIR_STAMP(l7)
-#ifdef PAIR_VAR_NODMA
-      if (false) {
-#else
-      if (fetch) {
-#endif
-        const unsigned long long db = ab_u + (unsigned long long)r0n * kLdab * 8ull;                  // D(0, 0) of position m + 1
-        const unsigned m0v = (unsigned)__builtin_amdgcn_readfirstlane((int)(slot_b + (unsigned)(kSlotE * 8 + 1024 * ld_d0 + 2048)));
-        if (lw == 0)
-          asm volatile(
-              "s_mov_b32 m0, %0\n\ts_nop 4\n\t"
-              "global_load_lds_dwordx4 %1, %6 offset:-2048\n\t"
-              "global_load_lds_dwordx4 %2, %6 offset:-1024\n\t"
-              "global_load_lds_dwordx4 %3, %6\n\t"
-              "global_load_lds_dwordx4 %4, %6 offset:1024\n\t"
-              "global_load_lds_dwordx4 %5, %6 offset:2048"
-              :
-              : "s"(m0v), "v"(voff_d[0]), "v"(voff_d[1]), "v"(voff_d[2]), "v"(voff_d[3]), "v"(voff_d[4]), "s"(db)
-              : "memory");
-        else
-          asm volatile(
-              "s_mov_b32 m0, %0\n\ts_nop 4\n\t"
-              "global_load_lds_dwordx4 %1, %5 offset:-2048\n\t"
-              "global_load_lds_dwordx4 %2, %5 offset:-1024\n\t"
-              "global_load_lds_dwordx4 %3, %5\n\t"
-              "global_load_lds_dwordx4 %4, %5 offset:1024"
-              :
-              : "s"(m0v), "v"(voff_d[0]), "v"(voff_d[1]), "v"(voff_d[2]), "v"(voff_d[3]), "s"(db)
-              : "memory");
-      }
-#ifdef PAIR_STAMPS
-      if (fetch && pair_common_step(hasB, m, lenA, sA, n)) {
-        PAIR_STAMP(l8)
-        PAIR_ACC_L(0, l0, l1) PAIR_ACC_L(1, l1, l2) PAIR_ACC_L(2, l2, l3) PAIR_ACC_L(3, l3, l4) PAIR_ACC_L(4, l4, l5)
-        PAIR_ACC_L(5, l5, l6) PAIR_ACC_L(6, l6, l7) PAIR_ACC_L(7, l7, l8) PAIR_ACC_L(8, 0ull, 1ull)
-      }
-#endif
-    }
-    // ---- end of the pair (nothing is in flight: the last steps fetch nothing)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-  }
-  if (lw == 0 && lane == 0) { PAIR_FLUSH(32) }
-}
-
-// (diagnostic variants, tools/r06_pair_variants.sh: PAIR_VAR_CAP168 compiles the 512-thread form for the register budget
-// of the 768-thread one; PAIR_VAR_NODMA keeps the loader waves and their barriers but requests nothing -- wrong results)
-#ifdef PAIR_VAR_CAP168
-#define PAIR_BOUNDS(LOADER) 768
-#else
-#define PAIR_BOUNDS(LOADER) (LOADER ? 768 : 512)
-#endif
-template <int LOADER>
-__global__ __launch_bounds__(PAIR_BOUNDS(LOADER), 1) void k_bulge_pair(double* __restrict__ sb_all, PairLayout SL, int batch, int W, int nxcd,
-                                                      int* __restrict__ progress, int* __restrict__ next_pair,
-                                                      int* __restrict__ ctl, int give_up_after, int early_look) {
+__global__ __launch_bounds__(512, 1) void k_bulge_pair(double* __restrict__ sb_all, PairLayout SL, int batch, int W, int nxcd,
+                                                       int* __restrict__ progress, int* __restrict__ next_pair,
+                                                       int* __restrict__ ctl, int give_up_after) {
   extern __shared__ __attribute__((aligned(16))) double pair_lds[];
   __shared__ int s_go, s_claim, s_xcd, s_slot;
 
@@ -2641,10 +2429,9 @@ __global__ __launch_bounds__(PAIR_BOUNDS(LOADER), 1) void k_bulge_pair(double* _
   // (the team is uniform over a wave: told to the compiler, so that the position, the step's case and the branches on
   // them are scalar)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int team = wave >= 8 ? 0 : wave >> 2;
+  const int team = wave >> 2;
   const int tt = tid & 255;
   double* const slots = pair_lds;
-  const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) double*)pair_lds;
   double* const tl = pair_lds + 3 * kSlot + team * kTeamLds;
   double* const vbuf = tl;
   double* const u = tl + 2 * kB;
@@ -2664,11 +2451,6 @@ __global__ __launch_bounds__(PAIR_BOUNDS(LOADER), 1) void k_bulge_pair(double* _
   const int xcd = s_xcd, slot = s_slot;
   const int mpx = xcd < batch ? (batch - xcd + nxcd - 1) / nxcd : 0;   // matrices of this XCD: xcd, xcd + nxcd, ...
   if (mpx == 0 || slot >= mpx * W) return;
-  if (LOADER && wave >= 8) {
-    pair_loader_run(sb_all, SL, nxcd, xcd, slot, mpx, (const volatile __attribute__((address_space(3))) int*)&s_claim,
-                    (const volatile __attribute__((address_space(3))) int*)&s_go, lds_base, wave - 8, tid & 63);
-    return;
-  }
   const int K0 = chase_len(n, 0);
   int steps_left = give_up_after;
 
@@ -2700,33 +2482,22 @@ __global__ __launch_bounds__(PAIR_BOUNDS(LOADER), 1) void k_bulge_pair(double* _
 
     const int nsteps = hasB ? lenA + 2 : lenA;
     // ---- the look at the predecessor pair (A's dependence; B's are inside the workgroup), by thread 256: the first wave of
-    // team B opens a step with LDS reads only.  Round 6, "early look": followers run at the dependence's limit -- pair p + 1
-    // starts when its workgroup has finished pair p - 3, a few steps behind pair p, and both advance at the same rate -- so a
-    // look taken when the step begins was needed in 0.6 of all steps and cost 2 300 cycles of a 16 900-cycle step, all
-    // other waves waiting at [0] (profiles/r06_pair_stamps.txt).  Now the counter and the stop flag are requested behind
-    // barrier [1] of the PREVIOUS step and are in a register when this step begins; a value that does not cover the step
-    // falls back to polling, for one task more than needed, which buys the step of distance that keeps the early values
-    // sufficient from there on.
+    // team B opens a step with LDS reads only.  Followers run at the dependence's limit -- pair p + 1 starts when its
+    // workgroup has finished pair p - 3, a few steps behind pair p, and both advance at the same rate -- so the look is
+    // needed in 0.6 of all steps and costs 2 300 cycles of a 16 900-cycle step, all other waves waiting at [0]
+    // (profiles/r06_pair_stamps.txt; requesting the values a step ahead did not pay: profiles/r06_pair_ab.txt).
     int have_c = 0;      // thread 256: last value seen of the predecessor's counter (it only grows)
-    int h_have = 0, h_stop = 0;
-    const int* prev = (early_look && sA > 0) ? prog + sA - 1 : nullptr;
     int pend_k = -1;     // task of this team whose stores are on their way: published behind the next step's loads
     for (int m = 0; m < nsteps; ++m) {
       PAIR_STAMP(ts0)
       if (tid == 256) {
-        // (a step whose successor is fetched ahead by the loader waves needs the predecessor one task further)
-        const int ahead = LOADER && pair_common_step(hasB, m + 1, lenA, sA, n) ? 3 : 2;
-        const int need = (sA > 0 && m < lenA) ? min(m + ahead, len_prev) : 0;
+        const int need = (sA > 0 && m < lenA) ? min(m + 2, len_prev) : 0;
         int go = 1;
-        if (prev) {
-          have_c = max(have_c, h_have);
-          if (h_stop) go = 0;
-        }
-        if (go && (have_c < need || (!prev && (m & 7) == 0))) {
+        if (have_c < need || (m & 7) == 0) {
 #ifdef PAIR_STAMPS
           s_pair_stamps[16 + 14] += 1ull;
 #endif
-          const int want = prev ? min(need + 1, len_prev) : need;
+          const int want = need;
           const int stop0 = __hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           int have = sA > 0 ? __hip_atomic_load(prog + sA - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
           if (stop0) go = 0;
@@ -2794,21 +2565,19 @@ __global__ __launch_bounds__(PAIR_BOUNDS(LOADER), 1) void k_bulge_pair(double* _
       // ---- the common step: both teams at work on full 64-row blocks, neither at a sweep start (pair_step_full)
       if (pair_common_step(hasB, m, lenA, sA, n)) {
         PairStepArgs pa{ab, sb + SL.vd, sb + SL.tau2, (ldptr)slots, (ldptr)vbuf, (ldptr)u, (ldptr)red, (ldptr)sc, prog, s, k,
-                        dia0 + k, cc, tid, prev, ctl};
-        if (team == 0) pair_step_full<0, LOADER>(pa, tau_p, pend_k, h_have, h_stop);
-        else pair_step_full<1, LOADER>(pa, tau_p, pend_k, h_have, h_stop);
+                        dia0 + k, cc, tid};
+        if (team == 0) pair_step_full<0>(pa, tau_p, pend_k);
+        else pair_step_full<1>(pa, tau_p, pend_k);
 #ifdef PAIR_STAMPS
         if (tid == 0) { s_pair_stamps[9] += 1ull; s_pair_stamps[0] += ts1 - ts0; }
         if (tid == 256) { s_pair_stamps[16] += ts1 - ts0; s_pair_stamps[16 + 7] += tsp - ts0; }
 #endif
       } else {
         PairGenArgs ga{ab, sb + SL.vd, sb + SL.tau2, (ldptr)slots, (ldptr)vbuf, (ldptr)u, (ldptr)red, (ldptr)sc, prog,
-                       ctl + 16 + xcd, n, s, k, my_len, team, to_lds ? 1 : 0, dia0, cc, tid, prev, ctl};
-        const PairCarry pc = pair_step_general<LOADER>(ga, tau_p, pend_k);
+                       ctl + 16 + xcd, n, s, k, my_len, team, to_lds ? 1 : 0, dia0, cc, tid};
+        const PairCarry pc = pair_step_general(ga, tau_p, pend_k);
         tau_p = pc.tau_p;
         pend_k = pc.pend_k;
-        h_have = pc.h_have;
-        h_stop = pc.h_stop;
       }
       // (no barrier here: the next step's [0] orders this step's slot writes before their readers, and nothing else of
       // the next step touches LDS before it)
@@ -2888,7 +2657,7 @@ __device__ unsigned long long g_bt2_stamps[64 * 8 * 17];
 #define BT2_STAMP(i)
 #define BT2_STAMP_WRITE
 #endif
-// Diagnostic build (-DBT2_CLOCK): the shader clock while k_bt2_apply / k_bt2_role run -- wave 0 of workgroup 0 reads
+// Diagnostic build (-DBT2_CLOCK): the shader clock while k_bt2_apply runs -- wave 0 of workgroup 0 reads
 // s_memtime (shader cycles) and s_memrealtime (100 MHz) at its start and end (sc_dbg_bt2_clock, tools/bt2_clock.py).
 #ifdef BT2_CLOCK
 __device__ unsigned long long g_bt2_clk[2];
@@ -3521,436 +3290,6 @@ __global__ __launch_bounds__(64 * NW, 2) void k_bt2_apply(const double* __restri
   BT2_CLOCK_END
 }
 
-// ================================================================================================================
-// k_bt2_role (round 5): the same product Z <- Q2 Z with the ROLES of a workgroup's waves split, as in k_gemm3
-// (gemm3.hip).  k_bt2_apply's eight waves each do everything -- MFMAs, the LDS-DMA of the fragments, the loads /
-// transposition / masks / stores of the window rows -- and every one of their memory and vector instructions costs the
-// SIMD's matrix pipe time (the pipes are busy 0.79 of that launch).  Here
-//   * waves 0-3 are one MFMA wave per SIMD, 16 columns each (a workgroup = 64 columns of one matrix): the 128-row window
-//     in eight accumulator tiles that alternate between two code phases (see below), 160 MFMAs per diamond from
-//     ready-made fragments in LDS -- and nothing else but LDS reads / writes: the 64 rows that enter the window at a slide
-//     are read from an LDS image in accumulator layout, the 64 finished rows are written to one;
-//   * waves 4-7 stream the fragments a quarter-diamond (one mini: 20 KB, five 1-KB pieces per wave behind ONE write of
-//     M0) at a time into a ring of three quarter buffers, two quarters ahead;
-//   * waves 8-11 (one per MFMA wave) move the window rows: LDS-DMA of the entering rows, column by column (512 bytes per
-//     instruction: lanes 0-31), into one of two images, a whole diamond before the MFMA wave reads them, and
-//     16-byte-per-lane stores of the finished rows out of a third image; they also zero what lies below the matrix, so
-//     the MFMA waves need no masks.
-// One barrier per quarter-diamond; per sweep group two more in front (the window's two halves come in through the two
-// images) and four behind (they go out).  LDS: 3 x 20 KB + 3 x 4 x 8 448 B = 162 816 B.
-// (Version 1 -- ring of two half-diamond buffers, one image in, everything fetched one half ahead -- was correct and took
-// 999 ms per C3 step against k_bt2_apply's 605: a loader's two M0 groups per half land one after the other, and the
-// entering rows come from HBM: both sat on the critical path of every diamond.  Version 3, one barrier at the head of
-// every quarter: 645 ms; its stamps (profiles/r05_bt2_role_stamps.txt) showed the MFMA waves waiting 1 250 + 710 cycles
-// per diamond for the Z waves -- whose vector-ALU instructions only issue in the gaps the MFMA wave leaves -- and 1 480
-// cycles in the slide, when all four MFMA waves push 64 KB of window rows through the LDS at once.  This version: 614 ms
-// against 594, the same 12.2 k cycles per diamond and SIMD as k_bt2_apply -- 0.84 of the MFMA issue slots -- at the
-// 2.17 - 2.20 GHz both kernels run at, profiles/r05_bt2_clock.txt.  Not the default: SPRINGCRAFT_BT2_ROLE = 1.)
-// Image layout: column c of a wave's 16 at c * 528 B (64 rows + 16 B: an accumulator register's 16 columns x 2 rows fall
-// into 32 distinct 8-byte bank pairs).  Needs n even (the window starts at an odd row and moves in pairs of rows) --
-// bt2_batched checks.
-constexpr int kRoleCol = 528;                       // bytes between the columns of a window image
-constexpr int kRoleImg = 16 * kRoleCol;             // one wave's image: 16 columns x 64 rows
-constexpr int kQuarterBytes = kMiniFrags * 64 * 8;  // 20 480
-constexpr int kRoleRing = 3 * kQuarterBytes;
-constexpr int kRoleLds = kRoleRing + 3 * 4 * kRoleImg;
-
-__device__ __forceinline__ unsigned long long role_uni64(unsigned long long v) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-  return ((unsigned long long)hi << 32) | lo;
-}
-
-// (diagnostic build -DBT2_STAMPS -DBT2_ROLE_STAMPS: cycles of an MFMA wave per diamond -- slots 4 q: the MFMAs of quarter
-// q up to the barrier inside it (+ the tail of the quarter before), 4 q + 1: the wait in that barrier, 14: the tail of
-// quarter 3, 15: the slide; tools/bt2_role_stamps.py)
-#if defined(BT2_STAMPS) && defined(BT2_ROLE_STAMPS)
-#define ROLE_STAMP(i) BT2_STAMP(i)
-#define ROLE_STAMP_DECL BT2_STAMP_DECL
-#define ROLE_STAMP_WRITE BT2_STAMP_WRITE
-#else
-#define ROLE_STAMP(i)
-#define ROLE_STAMP_DECL
-#define ROLE_STAMP_WRITE
-#endif
-__global__ __launch_bounds__(768, 1) void k_bt2_role(const double* __restrict__ sb_all, SbLayout SL,
-                                                     const int* __restrict__ dia_off, double* __restrict__ z_all,
-                                                     long long stride_z, int ncols, int batch) {
-  extern __shared__ __attribute__((aligned(16))) char rl[];   // ring of 3 quarter buffers | 2 x 4 images in | 4 images out
-  const int n = SL.n;
-  const int nchunk = (ncols + 63) / 64;
-  const int xcd = blockIdx.x & 7, slot_wg = blockIdx.x >> 3;
-  const int mat = xcd + 8 * (slot_wg / nchunk), chunk = slot_wg % nchunk;   // all column chunks of a matrix on one XCD
-  if (mat >= batch) return;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)rl;
-  const int ngroups = SL.ngroups;
-  auto barrier = [&]() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
-  // diamonds of sweep group S (read from global memory: made uniform for the compiler)
-  auto group_d0 = [&](int S) { return __builtin_amdgcn_readfirstlane(dia_off[S]); };
-
-  if (w >= 4 && w < 8) {
-    // ------------------------------------------------------------------------------------------ fragment loaders
-    // wave lw fetches pieces 5 lw .. 5 lw + 4 of a quarter (20 pieces of 1 KB) behind ONE write of M0.  A write to M0
-    // waits for the wave's LDS-DMA in flight: issuing quarter q + 2 therefore also means that quarter q + 1 has landed.
-    const int lw = w - 4;
-    const unsigned voff = (unsigned)lane * 16u;
-    const double* sb = sb_all + (size_t)mat * SL.slab;
-    auto fetch_quarter = [&](const double* src, int buf) {
-      // (scalar by construction: kernel arguments, blockIdx, readfirstlane'd counters -- no VALU instruction in this wave's
-      // loop: a helper wave's VALU instructions wait for issue slots of a SIMD that the MFMA wave keeps busy)
-      const unsigned long long g = (unsigned long long)(size_t)src + (unsigned long long)(5 * lw + 2) * 1024ull;
-      const unsigned m0v = lds_base + (unsigned)(buf * kQuarterBytes + (5 * lw + 2) * 1024);
-      asm volatile(
-          "s_mov_b32 m0, %0\n\ts_nop 4\n\t"
-          "global_load_lds_dwordx4 %1, %2 offset:-2048\n\t"
-          "global_load_lds_dwordx4 %1, %2 offset:-1024\n\t"
-          "global_load_lds_dwordx4 %1, %2\n\t"
-          "global_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-          "global_load_lds_dwordx4 %1, %2 offset:2048"
-          :
-          : "s"(m0v), "v"(voff), "s"(g)
-          : "memory");
-    };
-    for (int S = ngroups - 1; S >= 0; --S) {
-      const int d0 = group_d0(S), nk = group_d0(S + 1) - d0;
-      const int nq = 4 * nk;
-      const char* fgrp = (const char*)(sb + SL.frag + (size_t)d0 * kFragDoubles);
-      fetch_quarter((const double*)fgrp, 0);
-      fetch_quarter((const double*)(fgrp + kQuarterBytes), 1);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      barrier();   // b0
-      barrier();   // b1
-      int buf = 2;
-      for (int q = 0; q < nq; ++q) {
-        barrier();   // quarter q starts; the buffer of quarter q - 1 is free
-        if (q + 2 < nq) {
-          fetch_quarter((const double*)(fgrp + (size_t)(q + 2) * kQuarterBytes), buf);
-          // quarter q + 1 (the five instructions before these five) must have LANDED at the next barrier: an explicit
-          // count -- the wait that a write to M0 implies is not one to build on (version 2 without it: wrong results in
-          // some members of a batch)
-          asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-        } else {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        buf = buf == 2 ? 0 : buf + 1;
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      barrier(); barrier(); barrier(); barrier();   // e0 .. e3
-    }
-    return;
-  }
-
-  if (w >= 8) {
-    // ------------------------------------------------------------------------------------------------- Z waves
-    // NO vector-ALU instruction in this wave's steady state: a helper wave's VALU instruction only issues when the MFMA
-    // wave of its SIMD leaves a gap, i.e. at that wave's next barrier -- the stamps of the first version showed the MFMA
-    // waves waiting 1 250 cycles per diamond for this wave, which was still computing lane addresses and predicates.  So:
-    // lane offsets are computed once per kernel, everything that changes goes into the scalar base, lanes are switched off
-    // by scalar writes of EXEC inside the asm statements, and only windows that reach below the matrix (the last one or two
-    // of a sweep group) take the general path.
-    const int zw = w - 8;
-    const int c0 = chunk * 64 + 16 * zw;                       // first of this wave's 16 columns
-    double* z_mat = z_all + (size_t)mat * stride_z;
-    const unsigned img_in0 = lds_base + (unsigned)(kRoleRing + zw * kRoleImg);
-    char* p_in0 = rl + kRoleRing + zw * kRoleImg;
-    char* p_out = rl + kRoleRing + 8 * kRoleImg + zw * kRoleImg;
-    const unsigned long long col8 = (unsigned long long)n * 8ull;
-    const int pos = lane & 31, jj = lane >> 5;
-    unsigned lane16 = (unsigned)pos * 16u;                                        // a pair of rows per lane
-    unsigned lane_st = (unsigned)((unsigned long long)jj * col8) + (unsigned)pos * 16u;   // stores: two columns per instruction
-    unsigned img_st = (unsigned)(size_t)(const __attribute__((address_space(3))) char*)p_out + (unsigned)(jj * kRoleCol + pos * 16);
-    asm volatile("" : "+v"(lane16), "+v"(lane_st), "+v"(img_st));
-    // rows row0 .. row0 + 63 of the 16 columns -> image `which` (lanes 0-31: rows row0 + 2 l, + 1 of one column per
-    // instruction; M0 = the middle of the image)
-    // (one instruction per column; the scalar base moves on by a column less the 528 bytes that the immediate grows by.
-    // The base is an in-out operand of the asm statement: hipcc then cannot compute the sixteen bases ahead -- it did, kept
-    // them across the diamond loop, ran out of scalar registers and reloaded them with v_readlane, a VALU instruction)
-#define ROLE_DMA(J, IMM)                                                                                      \
-  asm volatile("s_mov_b32 exec_hi, 0\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %1, %0 offset:" #IMM                \
-               "\n\ts_mov_b32 exec_hi, -1" : "+s"(b_) : "v"(vo) : "memory");                                   \
-  b_ += (c0 + (J) + 1 < nc) ? step : (unsigned long long)(-528ll);
-#define ROLE_DMA16                                                                                     \
-  ROLE_DMA(0, -3960) ROLE_DMA(1, -3432) ROLE_DMA(2, -2904) ROLE_DMA(3, -2376)                        \
-  ROLE_DMA(4, -1848) ROLE_DMA(5, -1320) ROLE_DMA(6, -792) ROLE_DMA(7, -264)                          \
-  ROLE_DMA(8, 264) ROLE_DMA(9, 792) ROLE_DMA(10, 1320) ROLE_DMA(11, 1848)                            \
-  ROLE_DMA(12, 2376) ROLE_DMA(13, 2904) ROLE_DMA(14, 3432) ROLE_DMA(15, 3960)
-    auto fetch_rows = [&](int row0, int which) {
-      asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" : : "s"(img_in0 + (unsigned)(which * 4 * kRoleImg) + 3960u) : "memory");
-      int nc = ncols;
-      asm volatile("" : "+s"(nc));
-      const unsigned long long step = col8 - 528ull;
-      if (row0 + 64 <= n) {
-        // all 64 rows exist: the row goes into the scalar base; lanes 32-63 are off inside each asm statement (EXEC is
-        // whole again at its end: the compiler knows nothing of the change and may place its own instructions in between)
-        unsigned long long b_ = (unsigned long long)(size_t)z_mat + (unsigned long long)row0 * 8ull +
-                                (unsigned long long)min(c0, nc - 1) * col8 + 3960ull;
-        const unsigned vo = lane16;
-        ROLE_DMA16
-      } else {
-        // (rows beyond the matrix re-read its last pair and are put right by fix_rows)
-        unsigned long long b_ = (unsigned long long)(size_t)z_mat + (unsigned long long)min(c0, nc - 1) * col8 + 3960ull;
-        const unsigned vo = (unsigned)min(row0 + 2 * pos, n - 2) * 8u;
-        ROLE_DMA16
-      }
-    };
-#undef ROLE_DMA16
-#undef ROLE_DMA
-    // (after the rows have landed) what lies below the matrix reads as zero; a pair that straddles the last row was read
-    // one row early: its second value is the last row
-    auto fix_rows = [&](int row0, int which) {
-      if (row0 + 64 <= n) return;
-      typedef double d2z __attribute__((ext_vector_type(2)));
-      if (lane < 32) {
-        const int r = row0 + 2 * lane;
-        for (int j = 0; j < 16; ++j) {
-          d2z* u = (d2z*)(p_in0 + which * 4 * kRoleImg + j * kRoleCol + lane * 16);
-          if (r >= n) *u = d2z{0.0, 0.0};
-          else if (r == n - 1) { const d2z v = *u; *u = d2z{v[1], 0.0}; }
-        }
-      }
-    };
-    // image out -> rows row0 .. row0 + 63 of the 16 columns, two columns per instruction: all eight reads first, then
-    // the stores with the scalar base of the column pair (+ the row).  Windows inside the matrix and waves whose 16 columns
-    // all exist -- all but the last one or two windows of a sweep group and the last column chunk -- store without any
-    // predicate; the others take plain predicated stores.  (Switching lanes off by writing EXEC inside the asm statement,
-    // as the row fetch does, gave wrong results for the stores: tools/r05_role_dbg.sh, dbg 0 against dbg 1.)
-    auto store_rows = [&](int row0) {
-      typedef double d2z __attribute__((ext_vector_type(2)));
-      const __attribute__((address_space(3))) char* img = (const __attribute__((address_space(3))) char*)(size_t)img_st;
-      d2z vv[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) vv[i] = *(const __attribute__((address_space(3))) d2z*)(img + 2 * i * kRoleCol);
-      __builtin_amdgcn_sched_barrier(0);
-      int nc = ncols;
-      asm volatile("" : "+s"(nc));
-      if (row0 + 64 <= n && c0 + 16 <= nc) {
-        unsigned long long b = (unsigned long long)(size_t)z_mat + (unsigned long long)c0 * col8 + (unsigned long long)row0 * 8ull;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          asm volatile("s_nop 4\n\tglobal_store_dwordx4 %1, %2, %0\n\ts_nop 1" : "+s"(b) : "v"(lane_st), "v"(vv[i]) : "memory");
-          b += 2ull * col8;
-        }
-      } else {
-        const int r = row0 + 2 * pos;
-        for (int i = 0; i < 8; ++i) {
-          double* dst = z_mat + (size_t)(c0 + 2 * i + jj) * n + r;
-          if (c0 + 2 * i + jj < nc) {
-            if (r + 1 < n) { dst[0] = vv[i][0]; dst[1] = vv[i][1]; }
-            else if (r + 1 == n) dst[0] = vv[i][0];
-          }
-        }
-      }
-    };
-    for (int S = ngroups - 1; S >= 0; --S) {
-      const int d0 = group_d0(S), nk = group_d0(S + 1) - d0;
-      const int win0 = S * kG + 1;
-      fetch_rows(win0, 0);
-      fetch_rows(win0 + 64, 1);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      fix_rows(win0, 0);
-      fix_rows(win0 + 64, 1);
-      barrier();   // b0: both halves of the window are in the images
-      barrier();   // b1: the MFMA wave has read them
-      // E_k = the rows that enter after diamond k (rows win_k + 128 ..), read by the MFMA wave during the last quarter of
-      // diamond k out of image k & 1; fetched more than a diamond earlier
-      if (1 < nk) fetch_rows(win0 + 128, 0);
-      for (int k = 0; k < nk; ++k) {
-        const int win = win0 + 64 * k;
-        barrier();   // quarter 0 (the rows finished at the last slide went into the image out at the end of the last diamond)
-        barrier();   // quarter 1
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // E_k (fetched a diamond ago) has landed; the last diamond's stores are out
-        if (k + 1 < nk) fix_rows(win + 128, k & 1);
-        if (k > 0) store_rows(win - 64);
-        barrier();   // quarter 2
-        // E_{k+1} into the image that the MFMA wave read a diamond ago.  Here, not behind the barrier of quarter 3: the
-        // slide that follows that one is the busiest moment of the LDS
-        if (k + 2 < nk) fetch_rows(win + 192, (k + 1) & 1);
-        barrier();   // quarter 3: the MFMA wave reads E_k
-      }
-      const int winl = win0 + 64 * (nk - 1);
-      barrier();   // e0
-      barrier();   // e1: rows winl .. + 63 are in the image out
-      store_rows(winl);
-      barrier();   // e2 (they have been read)
-      barrier();   // e3: rows winl + 64 .. + 127
-      store_rows(winl + 64);
-    }
-    return;
-  }
-
-  // ---------------------------------------------------------------------------------------------- MFMA waves
-  const int fr = lane & 15, fk = lane >> 4;
-  // this lane's place in a window image: column fr, row fk (+ 16 per tile, + 4 per register)
-  char* q_in0 = rl + kRoleRing + w * kRoleImg + fr * kRoleCol + fk * 8;
-  char* q_out = q_in0 + 8 * kRoleImg;
-  // The window: eight accumulator tiles (128 rows x 16 columns) in ONE array.  Diamonds alternate between two code PHASES:
-  // logical tile t of the window is zz[(t + 4 * phase) & 7], so the slide -- the upper half leaves, the lower half becomes
-  // the upper, 64 new rows enter below -- moves no register: the four tiles that leave are written to the image out and the
-  // entering rows are read into the same registers, which are the lower half of the next phase.  (k_bt2_apply rotates
-  // three arrays of four tiles through three phases; with the 168 registers of a 12-wave workgroup hipcc moved accumulator
-  // tuples through scratch where those phases join: 1 130 ms.  Version 3 kept one phase and moved 16 registers per
-  // diamond: 645 ms.)
-  d4 zz[8];
-  ROLE_STAMP_DECL
-  BT2_CLOCK_BEGIN
-  // fragment registers: two rings of eight that alternate from quarter to quarter.  The barrier that opens quarter q + 1
-  // sits INSIDE quarter q, behind its 36th MFMA: by then every fragment of quarter q is in registers (its buffer may be
-  // overwritten), the first eight fragments of quarter q + 1 are requested right behind the barrier, and the last four
-  // MFMAs of quarter q cover their way from LDS -- no MFMA waits at a quarter's start.
-  double fa[8], fb[8];
-  typedef double d2l __attribute__((ext_vector_type(2)));
-  typedef const __attribute__((address_space(3))) char* lcp;
-  auto frag_ptr = [&](const char* ring) {
-    // (opaque: the constants below go into the LDS instructions' offset fields instead of registers of their own)
-    unsigned ring_a = (unsigned)(size_t)(lcp)ring + (unsigned)lane * 16u;
-    asm volatile("" : "+v"(ring_a));
-    return (const __attribute__((address_space(3))) d2l*)(size_t)ring_a;
-  };
-  auto first_frags = [&](const char* ring, double (&f)[8]) {
-    const __attribute__((address_space(3))) d2l* lp = frag_ptr(ring);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const d2l t = lp[j * 64];
-      f[2 * j] = t[0];
-      f[2 * j + 1] = t[1];
-    }
-  };
-  // One quarter-diamond = one mini (st = 3 - QI): 20 MFMAs of W = V^T Z, 20 of Z -= (V T) W, fragments at `ring`; `more`:
-  // another quarter follows in this sweep group (its fragments at `next_ring`).
-  // the 64 rows that enter at the next slide: read tile by tile during quarter 3 (four reads behind its MFMAs 1, 9, 17, 25)
-  d4 ze[4];
-  auto quarter = [&](auto QI, auto PH, const char* ring, const char* next_ring, double (&cur)[8], double (&nxt)[8],
-                     const char* enter) {
-    // (no "another quarter follows" flag: the last quarter of a sweep group does the same -- its barrier is the first of the
-    // group's epilogue, e0, and the fragments and rows it reads ahead are simply not used.  With a branch around the barrier
-    // and the reads, hipcc joined the two paths' pending-read counts conservatively and made MFMA 36 wait for the fragments
-    // of the NEXT quarter; with a second copy of the diamond for "no successor" it moved accumulator tuples through
-    // scratch: 301 spills)
-    constexpr bool more = true;
-    constexpr int st = 3 - decltype(QI)::value;
-    constexpr int ph4 = 4 * decltype(PH)::value;
-    const __attribute__((address_space(3))) d2l* ldsP = frag_ptr(ring);
-    d4 wa = d4{0, 0, 0, 0};
-    constexpr int kAhead = 8;
-#pragma unroll
-    for (int p = 0; p < kMiniFrags; ++p) {
-      const double a = cur[p % kAhead];
-      if (p < 20) {
-        const int rt = (st + p / 4 + ph4) & 7, r = p % 4;
-        wa = __builtin_amdgcn_mfma_f64_16x16x4f64(a, zz[rt][r], p == 0 ? d4{0, 0, 0, 0} : wa, 0, 0, 0);
-      } else {
-        const int jj = p - 20, r = jj / 5, rt = (st + jj % 5 + ph4) & 7;
-        zz[rt] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, wa[r], zz[rt], 0, 0, 0);
-      }
-      if ((p & 1) && p + kAhead - 1 < kMiniFrags) {
-        const d2l t = ldsP[((p + kAhead - 1) / 2) * 64];
-        cur[(p - 1) % kAhead] = t[0];
-        cur[p % kAhead] = t[1];
-      }
-      if (decltype(QI)::value == 3 && more && (p & 7) == 1 && p < 32) {
-        unsigned img_a = (unsigned)(size_t)(lcp)enter;
-        asm volatile("" : "+v"(img_a));
-        lcp img = (lcp)(size_t)img_a;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) ze[p >> 3][r] = *(const __attribute__((address_space(3))) double*)(img + (16 * (p >> 3) + 4 * r) * 8);
-      }
-      if (p == 35 && more) {
-        ROLE_STAMP(4 * decltype(QI)::value)
-        barrier();                    // quarter q + 1 starts (the last fragment reads of this one were issued at p = 31)
-        ROLE_STAMP(4 * decltype(QI)::value + 1)
-        first_frags(next_ring, nxt);
-      }
-      __builtin_amdgcn_sched_barrier(0);   // (the order as written: fragment reads a few MFMAs ahead, not all at once)
-    }
-  };
-  // four tiles <-> an image (64 rows x 16 columns), a tile at a time
-  auto tiles_in = [&](int base, const char* img_) {
-    unsigned img_a = (unsigned)(size_t)(lcp)img_;
-    asm volatile("" : "+v"(img_a));
-    lcp img = (lcp)(size_t)img_a;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) zz[base + i][r] = *(const __attribute__((address_space(3))) double*)(img + (16 * i + 4 * r) * 8);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  auto tiles_out = [&](int base) {
-    unsigned out_a = (unsigned)(size_t)(__attribute__((address_space(3))) char*)q_out;
-    asm volatile("" : "+v"(out_a));
-    __attribute__((address_space(3))) char* qo = (__attribute__((address_space(3))) char*)(size_t)out_a;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) *(__attribute__((address_space(3))) double*)(qo + (16 * i + 4 * r) * 8) = zz[base + i][r];
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  // the slide behind a diamond of phase PH: tile by tile, the finished rows to the image out, the entering rows E_k (read
-  // into `ze` during quarter 3: all four MFMA waves slide at the same moment, and 64 KB of window rows + the fragments
-  // of the next quarter + the rows the Z waves fetch through the LDS in one burst took 1 480 cycles) into the same registers
-  auto slide = [&](int base) {
-    unsigned out_a = (unsigned)(size_t)(__attribute__((address_space(3))) char*)q_out;
-    asm volatile("" : "+v"(out_a));
-    __attribute__((address_space(3))) char* qo = (__attribute__((address_space(3))) char*)(size_t)out_a;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) *(__attribute__((address_space(3))) double*)(qo + (16 * i + 4 * r) * 8) = zz[base + i][r];
-      zz[base + i] = ze[i];
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>;
-  using I3 = std::integral_constant<int, 3>;
-  for (int S = ngroups - 1; S >= 0; --S) {
-    const int nk = group_d0(S + 1) - group_d0(S);
-    barrier();                 // b0: the window's two halves are in the two images
-    tiles_in(0, q_in0);
-    tiles_in(4, q_in0 + 4 * kRoleImg);
-    barrier();                 // b1
-    barrier();                 // the group's first quarter starts (all later quarters: inside their predecessor)
-    first_frags(rl, fa);
-    int buf = 0;               // 4 k % 3: the ring buffer of the diamond's first quarter
-    auto diamond = [&](auto PH, int k) {
-      constexpr int base = 4 * decltype(PH)::value;     // registers of the logical tiles 0 .. 3
-      const char* r0 = rl + buf * kQuarterBytes;
-      const char* r1 = rl + (buf + 1 > 2 ? buf - 2 : buf + 1) * kQuarterBytes;
-      const char* r2 = rl + (buf + 2 > 2 ? buf - 1 : buf + 2) * kQuarterBytes;
-      quarter(I0{}, PH, r0, r1, fa, fb, nullptr);
-      quarter(I1{}, PH, r1, r2, fb, fa, nullptr);
-      quarter(I2{}, PH, r2, r0, fa, fb, nullptr);  // (4 k + 3) % 3 = 4 k % 3
-      quarter(I3{}, PH, r0, r1, fb, fa, q_in0 + (k & 1) * 4 * kRoleImg);   // 4 (k + 1) % 3 = (4 k + 1) % 3
-      ROLE_STAMP(14)
-      if (k + 1 < nk) slide(base);
-      ROLE_STAMP(15)
-      buf = buf == 2 ? 0 : buf + 1;
-    };
-#pragma clang loop unroll(disable)
-    for (int k = 0; k < nk; k += 2) {
-      diamond(I0{}, k);
-      if (k + 1 < nk) diamond(I1{}, k + 1);
-    }
-    // the window of the last diamond goes back to memory (its phase: (nk - 1) & 1); e0 -- the image out is free -- was the
-    // barrier inside the last quarter
-    if ((nk - 1) & 1) tiles_out(4); else tiles_out(0);
-    barrier();                                   // e1
-    barrier();                                   // e2
-    if ((nk - 1) & 1) tiles_out(0); else tiles_out(4);
-    barrier();                                   // e3
-  }
-  ROLE_STAMP_WRITE
-  BT2_CLOCK_END
-}
-
 // ---- few columns (partial spectrum): one launch per WAVEFRONT of diamonds ------------------------------------------
 // k_bt2_apply gives a workgroup 16 NW columns and lets it walk all diamonds in order: with the ~100 columns of a
 // partial-spectrum solve that is two workgroups on the whole chip, each applying ~n^2 / 8192 diamonds one after the other
@@ -4050,43 +3389,6 @@ __global__ __launch_bounds__(256) void k_bt2_wave(const double* __restrict__ sb_
 
 // ================================================================================================================
 // Layout
-// K slices of the SYMM X = A22 V: with few matrices its launch has only n / 64 tiles per matrix, each walking a K range of
-// up to n (longest first, but the longest IS the critical path): slices of the K range give the launch 2 - 8 times the
-// workgroups and a fraction of the critical path.  Config C5 (one 24000 x 24000 matrix): 596 -> 307 ms.
-// Whether the band reduction of order-n matrices runs its SYMM on k_symm3 (symm3.hip; the launcher may still decline a
-// panel -- too few tiles late in the reduction -- which then takes the two triangular-operand launches below)
-bool symm3_for(int n) {
-  static const int env = [] { const char* e = getenv("SPRINGCRAFT_SYMM3"); return e ? atoi(e) : 1; }();
-  return env != 0 && n >= 512 && (n & 1) == 0;
-}
-
-int symm_split_for(int n, int batch) {
-  static const int env = [] { const char* e = getenv("SPRINGCRAFT_SYMM_SPLIT"); return e ? atoi(e) : 0; }();
-  if (env >= 1) return std::min(env, 16);
-  if (symm3_for(n)) {
-    // k_symm3: a work item is (128-row tile, K slice), all of equal length; 256 persistent workgroups want a few rounds
-    // of them (a launch holds half the batch from 32 matrices on: the two half batches run on two streams)
-    const long long items = (long long)((n + 127) / 128) * (batch >= 32 ? batch / 2 : batch);
-    // (C5, one n = 24000 matrix = 188 tile rows, tools/r06_cfgs.sh: 3 / 4 / 5 / 6 / 8 slices 1143 / 1114 / 1105 / 1092 / 1083 ms)
-    if (items >= 768) return 1;
-    return (int)std::min<long long>(16, (1536 + items - 1) / items);
-  }
-  const long long tiles = (long long)batch * ((n + 63) / 64);
-  if (tiles >= 1024 || n < 2048) return 1;
-  // (one 24000 x 24000 matrix: 3 slices 338 ms, 6 slices 307 ms, 8 slices 378 ms of SYMM time)
-  // Round 5, same matrix, `tools/r05_symm_sweep.sh`: 4 slices 407 ms, 5: 312, 6: 325, 7: 299, 8: 395, 9: 285, 10: 295,
-  // 12: 303 -- slice counts that share a factor with the 8 XCDs put the same slice of every tile on the same XCD (the
-  // workgroups are dealt round-robin) and with it the long K ranges of the triangle: ODD counts spread them.  Nine where six
-  // were taken (at most 409 tiles: one large matrix or a few); the smaller counts of larger launches are unchanged
-  // (n = 6000, one to four matrices: 6, 7 and 9 slices within 1 %).
-  // The middle regime follows the same rule (`tools/r05_symm_mid.sh`, 6 x n = 6000 = 564 tiles: 4 slices 38.9 ms of SYMM
-  // per step, 5 slices 31.0): an even count takes the next odd one.
-  // (ceil(2048 / tiles) is 3 for 683 .. 1023 tiles, 4 for 512 .. 682, 5 for 410 .. 511, 6 and more below: the only even
-  // count the rule replaces is the measured 4 -> 5)
-  const long long s0 = std::min<long long>(6, (2048 + tiles - 1) / tiles);
-  return s0 >= 6 ? 9 : (s0 == 4 ? 5 : (int)s0);
-}
-
 size_t sb_slab_doubles(int n, int batch, SbLayout* out) {
   SbLayout L{};
   L.n = n;
@@ -4096,7 +3398,7 @@ size_t sb_slab_doubles(int n, int batch, SbLayout* out) {
   L.vw = take((long long)n * 4 * kB);
   L.wv = take((long long)n * 4 * kB);
   L.xv = take((long long)n * 3 * kB);
-  L.symm_split = symm_split_for(n, batch);
+  L.symm_split = sc_host::symm_split_for(sc_host::two_stage_env(), n, batch);
   L.xsplit = L.symm_split > 1 ? take((long long)2 * L.symm_split * n * kB) : 0;
   L.qrpart = take((long long)2 * nchunk * kB);
   L.qrpiv = take(2 * (kB + 8));
@@ -4139,6 +3441,358 @@ static std::vector<int> dia_offsets(int n) {
 }
 
 // ================================================================================================================
+// Host side of stages 1 and 2.  Which kernel form a panel / a chase gets: twostage_policy.h.
+
+// kernel-group timers of a profiled solve (the driver owns them: they are resolved when both stages have been enqueued)
+struct SbTimers {
+  PhaseTimer qr, symm, syr2k, bulge;
+  SbTimers(sc_ctx* ctx, hipStream_t st) : qr(ctx, "panel_qr", st), symm(ctx, "symm", st), syr2k(ctx, "syr2k", st), bulge(ctx, "bulge", st) {}
+  void finish() { qr.finish(); symm.finish(); syr2k.finish(); bulge.finish(); }
+};
+
+// What a panel needs of its solve.
+struct PanelRun {
+  sc_ctx* ctx;
+  hipStream_t st;   // the solve's own stream
+  double* d_a; long long stride_a; int n, batch;
+  double* d_tri_ws; const TriLayout& TL;
+  double* d_sb_ws; const SbLayout& SL;
+  const GemmDesc* d_descs;
+  const std::vector<int>& role;
+  sc_host::CoopPlan coop;
+  v4i* coop_recs;   // null: no k_panel_coop in this solve
+  int* coop_ctl;
+  bool use_symm3;
+  int symm3_nb_min;
+  SbTimers& t;
+};
+
+// One panel of the matrices [lo, hi) on `ps`: QR of the panel, X = A22 V, the small products, W, the trailing update
+// its role asks for (single: SYR2K; first of a pair: the next panel's columns only; second: the joint update).
+static int run_panel(const PanelRun& R, int p, int lo, int hi, hipStream_t ps, bool timed) {
+  using sc_host::PanelQr;
+  const sc_host::TwoStageEnv& E = sc_host::two_stage_env();
+  sc_ctx* ctx = R.ctx;
+  const TriLayout& TL = R.TL;
+  const SbLayout& SL = R.SL;
+  const int n = R.n, batch = R.batch;
+  const long long stride_a = R.stride_a;
+  struct StreamScope {   // launch_gemm_f64 launches on the context's stream
+    sc_ctx* c; hipStream_t old;
+    StreamScope(sc_ctx* c_, hipStream_t s) : c(c_), old(c_->stream) { c->stream = s; }
+    ~StreamScope() { c->stream = old; }
+  } scope(ctx, ps);
+  const int nb = hi - lo;
+  const int rl = R.role[(size_t)p];
+  double* a_h = R.d_a + (size_t)lo * stride_a;
+  double* tri_h = R.d_tri_ws + (size_t)lo * TL.slab;
+  double* sb_h = R.d_sb_ws + (size_t)lo * SL.slab;
+  const int j0 = p * kB, r0 = j0 + kB, m = n - r0;
+  const int nr = std::min(kB, m - 1);
+  const int nchunks = (m + kQrRows - 1) / kQrRows;
+  const dim3 qgrid((unsigned)nchunks, (unsigned)nb);
+  SbLayout SQ = SL;     // where the panel QR leaves V: the second panel of a pair uses the second half of [V|W..], [W|V..]
+  if (rl == 2) { SQ.vw += (long long)2 * kB * n; SQ.wv += (long long)2 * kB * n; }
+  if (timed) R.t.qr.start();
+  const sc_host::PanelQrForm F = sc_host::panel_qr_form(E, R.coop, R.coop_recs != nullptr, m, nb, ps == R.st);
+  switch (F.kind) {
+    case PanelQr::Coop: {
+      const int coop_g = F.coop_g;
+      // (test hook, sc_dbg_set_panel_coop_fail: from this panel on the matrices' abort flags are up, as after a time-out)
+      if (p == ctx->coop_fail_panel) SC_HIP(ctx, hipMemsetAsync(R.coop_ctl + 8 * lo, 1, sizeof(int) * 8 * nb, ps));
+      hipLaunchKernelGGL(k_panel_coop, dim3((unsigned)coop_g, (unsigned)nb), dim3(kCoopRows), kCoopLdsBytes, ps, a_h, stride_a,
+                         tri_h, TL, sb_h, SQ, j0, coop_g, R.coop_recs + (size_t)lo * coop_recs_per_matrix(coop_g),
+                         R.coop_ctl + 8 * lo, (p + 1) * 128);
+      // the take-over: returns at once unless a wait of the launch above (or of an earlier panel) timed out
+      hipLaunchKernelGGL(k_panel_serial, dim3((unsigned)nb), dim3(1024), 0, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0,
+                         (const int*)(R.coop_ctl + 8 * lo), ctx->d_status);
+      ++ctx->cnt_coop_launches;
+      break;
+    }
+    case PanelQr::Wg1024: {
+      const size_t lds_wg = sizeof(double) * (size_t)(2 * kWgWaves * 8 + 16 + 8 + 8 * kB + kWgWaves * kB * 8);
+      const dim3 g1((unsigned)nb), b1((unsigned)kWgThreads);
+      if (F.ru == 1) hipLaunchKernelGGL((k_panel_wg<1, 8>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
+      else if (F.ru == 2) hipLaunchKernelGGL((k_panel_wg<2, 8>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
+      else if (F.ru == 3) hipLaunchKernelGGL((k_panel_wg<3, 4>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
+      else hipLaunchKernelGGL((k_panel_wg<4, 2>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
+      break;
+    }
+    case PanelQr::Wg512: {
+      constexpr int kW = 512 / 64;
+      const size_t lds_wg = sizeof(double) * (size_t)(2 * kW * 8 + 16 + 8 + 8 * kB + kW * kB * 8);
+      const dim3 g1((unsigned)nb), b1(512u);
+      if (F.ru == 10) hipLaunchKernelGGL((k_panel_wg<10, 1, 512>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
+      else hipLaunchKernelGGL((k_panel_wg<12, 1, 512>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
+      break;
+    }
+    case PanelQr::Blocked: {
+      // blocked panel: inner blocks of 8 columns, their reflectors applied to the rest of the panel at once
+      const size_t lds_qr_blk = sizeof(double) * ((size_t)(kIb + 1) * (kQrRows + 1) + kB + kQrRows + 4 * kB);
+      const size_t lds_blk_a = sizeof(double) * ((size_t)kB * (kQrRows + 1) + kQrRows + 8 * kB);
+      const size_t lds_blk_b = sizeof(double) * ((size_t)kB * (kQrRows + 1) + kIb * kB + 4 * kB);
+      hipLaunchKernelGGL(k_panel_qr, qgrid, dim3(256), lds_qr_blk, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, 0, nr, kIb);
+      for (int c0 = 0; c0 < kB; c0 += kIb) {
+        for (int j = c0 + 1; j < c0 + kIb; ++j)
+          hipLaunchKernelGGL(k_panel_qr, qgrid, dim3(256), lds_qr_blk, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, j, nr,
+                             c0 + kIb);
+        // (their LDS image holds columns c0 .. kB-1 only)
+        const size_t cut = sizeof(double) * (size_t)c0 * (kQrRows + 1);
+        hipLaunchKernelGGL(k_pqr_blk_a, qgrid, dim3(256), lds_blk_a - cut, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, c0);
+        if (c0 + kIb < kB)
+          hipLaunchKernelGGL(k_pqr_blk_b, qgrid, dim3(256), lds_blk_b - cut, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, c0);
+      }
+      break;
+    }
+    case PanelQr::Unblocked: {
+      const size_t lds_qr = sizeof(double) * ((size_t)kB * (kQrRows + 1) + kB + kQrRows + 4 * kB);
+      for (int j = 0; j <= nr; ++j)
+        hipLaunchKernelGGL(k_panel_qr, qgrid, dim3(256), lds_qr, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, j, nr, kB);
+      break;
+    }
+  }
+  if (timed) R.t.qr.stop();
+  const GemmDesc* g = R.d_descs + (size_t)p * kDescKinds * batch;   // [kind][batch]
+  if (timed) R.t.symm.start();
+  // X = A22 V: one launch of k_symm3 (X into X1; X2 was zeroed for the whole solve) while the panel has enough tiles
+  // for it, else X1 = L V and X2 = strict(L)^T V by two triangular-operand launches of k_gemm2
+  if (R.use_symm3 && symm3_would_take(ctx, R.symm3_nb_min, m, SL.symm_split, /*aligned16=*/true) &&
+      launch_symm3(ctx, g + lo, nb, m, SL.symm_split, /*aligned16=*/true, /*any_size=*/true) == SC_OK) {
+    if (SL.symm_split > 1)
+      hipLaunchKernelGGL(k_sum_xslices, dim3((unsigned)((m + 255) / 256), kB, (unsigned)nb), dim3(256), 0, ps, sb_h, SL, r0);
+  } else {
+    SC_TRY(launch_gemm_f64(ctx, g + lo, nb, m, kB, kGemmTile, SL.symm_split, false, true, kGemmAmBk));           // X1 = L V
+    SC_TRY(launch_gemm_f64(ctx, g + batch + lo, nb, m, kB, kGemmTile, SL.symm_split, false, true, kGemmAkBk));   // X2 = strict(L)^T V
+    if (SL.symm_split > 1)
+      hipLaunchKernelGGL(k_sum_xslices, dim3((unsigned)((m + 255) / 256), 2 * kB, (unsigned)nb), dim3(256), 0, ps, sb_h, SL, r0);
+  }
+  if (rl == 2) {   // the trailing matrix has not seen the first panel's update yet: X1 -= [V1|W1] ([W1|V1]^T V2)
+    SC_TRY(launch_gemm_f64(ctx, g + 7 * batch + lo, nb, 2 * kB, kB, kGemmTile, kSmallSplit, false, false, kGemmAkBk));
+    hipLaunchKernelGGL(k_sum_p2, dim3((unsigned)(2 * kB * kB / 256), (unsigned)nb), dim3(256), 0, ps, sb_h, SL);
+    SC_TRY(launch_gemm_f64(ctx, g + 8 * batch + lo, nb, m, kB, kGemmTile, 1, false, false, kGemmAmBk));
+  }
+  if (timed) R.t.symm.stop();
+  SC_TRY(launch_gemm_f64(ctx, g + 2 * batch + lo, nb, kB, 3 * kB, kGemmTile, kSmallSplit, false, false, kGemmAkBk));
+  const size_t lds_small = sizeof(double) * 4 * kB * (kB + 1);
+  hipLaunchKernelGGL(k_sb_small, dim3((unsigned)nb), dim3(1024), lds_small, ps, tri_h, TL, sb_h, SL, j0);
+  if (nb == batch) {
+    SC_TRY(launch_gemm_f64(ctx, g + 3 * batch, 2 * batch, m, kB, kGemmTile, 1, false, false, kGemmAmBk));
+  } else {
+    SC_TRY(launch_gemm_f64(ctx, g + 3 * batch + lo, nb, m, kB, kGemmTile, 1, false, false, kGemmAmBk));
+    SC_TRY(launch_gemm_f64(ctx, g + 4 * batch + lo, nb, m, kB, kGemmTile, 1, false, false, kGemmAmBk));
+  }
+  if (timed) R.t.syr2k.start();
+  if (rl == 1)
+    SC_TRY(launch_gemm_f64(ctx, g + 6 * batch + lo, nb, m, kB, kGemmTile, 1, false, false, kGemmAmBn));
+  else
+    // (records of one launch share (m, m, K); operands start at even rows of buffers with even leading dimension n)
+    if (launch_gemm3_uniform(ctx, g + 5 * batch + lo, nb, m, m, rl == 2 ? 4 * kB : 2 * kB, kGemmAmBn, /*lower=*/R.use_symm3 ? 2 : 1, 1.0, 1.0,
+                             /*aligned16=*/(n & 1) == 0 && (r0 & 1) == 0) != SC_OK)
+      SC_TRY(launch_gemm_f64(ctx, g + 5 * batch + lo, nb, m, m, kGemmTile, 1, false, false, kGemmAmBn, /*lower_grid=*/true));
+  if (timed) R.t.syr2k.stop();
+  return SC_OK;
+}
+
+// Stage 1 on ctx->stream, the GEMM records of the solve uploaded: dense -> band.
+static int sb_stage1(sc_ctx* ctx, double* d_a, long long stride_a, int n, int batch, double* d_tri_ws, const TriLayout& TL,
+                     double* d_sb_ws, const SbLayout& SL, const GemmDesc* d_descs, const std::vector<int>& role, bool prof,
+                     SbTimers& timers) {
+  const sc_host::TwoStageEnv& E = sc_host::two_stage_env();
+  hipStream_t st = ctx->stream;
+  const int npanels = (int)role.size();
+
+  // tau of columns without a reflector must read 0
+  for (int b = 0; b < batch; ++b)
+    SC_HIP(ctx, hipMemsetAsync(d_tri_ws + (size_t)b * TL.slab + TL.tau, 0, sizeof(double) * n, st));
+
+  const int s1_parts = sc_host::stage1_parts(E, batch, prof);
+  const sc_host::CoopPlan coop = sc_host::coop_plan(E, n, batch, ctx->num_cus, prof, ctx->coop_min_rows, ctx->coop_ok);
+  v4i* coop_recs = nullptr;
+  int* coop_ctl = nullptr;
+  if (coop.ask) {
+    if (ctx->coop_attr < 0)
+      ctx->coop_attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_panel_coop),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCoopLdsBytes) == hipSuccess;
+    if (ctx->coop_attr == 1 && coop.nb_max >= 1) {
+      const size_t rec_bytes = (size_t)batch * coop_recs_per_matrix(coop.gmax) * sizeof(v4i);
+      const size_t ctl_bytes = align_up((size_t)batch * 8 * sizeof(int), 256);   // one control record per matrix
+      SC_TRY(sc_reserve_dc_aux(ctx, ctl_bytes + rec_bytes));
+      coop_ctl = reinterpret_cast<int*>(ctx->dc_aux);
+      coop_recs = reinterpret_cast<v4i*>(reinterpret_cast<char*>(ctx->dc_aux) + ctl_bytes);
+      // (sequence numbers are unique within a solve only)
+      SC_HIP(ctx, hipMemsetAsync(ctx->dc_aux, 0, ctl_bytes + rec_bytes, st));
+    }
+  }
+  // k_symm3 writes X into the X1 block of [X1 | X2 | V]; the X2 block reads zero for the whole solve (the panels at the
+  // end of the reduction that fall back to the two triangular-operand launches rewrite their rows of it themselves)
+  const bool use_symm3 = sc_host::symm3_for(E, n);
+  if (use_symm3)
+    for (int b = 0; b < batch; ++b)
+      SC_HIP(ctx, hipMemsetAsync(d_sb_ws + (size_t)b * SL.slab + SL.xv + (size_t)kB * n, 0, sizeof(double) * (size_t)kB * n, st));
+  // (whether a panel takes k_symm3 is decided for the SMALLEST part of a batch that is split over streams, and then holds
+  // for every part: sc_host::stage1_parts)
+  const PanelRun R{ctx, st, d_a, stride_a, n, batch, d_tri_ws, TL, d_sb_ws, SL, d_descs, role, coop, coop_recs, coop_ctl,
+                   use_symm3, std::max(1, batch / s1_parts), timers};
+  if (s1_parts > 1) {
+    struct SideBySide {   // (k_gemm3 leaves CUs to the other parts' kernels while this is set: gemm3_would_take)
+      sc_ctx* c;
+      explicit SideBySide(sc_ctx* c_) : c(c_) { c->gemm3_side_by_side = true; }
+      ~SideBySide() { c->gemm3_side_by_side = false; }
+    } side_by_side(ctx);
+    SC_TRY(sc_aux_stream(ctx));
+    SC_TRY(sc_side_streams(ctx, s1_parts - 1));
+    SC_HIP(ctx, hipEventRecord(ctx->aux_fork, st));
+    for (int q = 1; q < s1_parts; ++q) SC_HIP(ctx, hipStreamWaitEvent(ctx->side_streams[q - 1], ctx->aux_fork, 0));
+    int rc_parts = SC_OK;
+    for (int p = 0; p < npanels && rc_parts == SC_OK; ++p)
+      for (int q = 0; q < s1_parts && rc_parts == SC_OK; ++q) {
+        const int lo = (int)((long long)batch * q / s1_parts), hi = (int)((long long)batch * (q + 1) / s1_parts);
+        rc_parts = run_panel(R, p, lo, hi, q == 0 ? st : ctx->side_streams[q - 1], q == 0);
+      }
+    // (also after an error: the side streams are joined before anything returns, so that what they still have queued
+    // is ordered before whatever the caller enqueues next on the main stream)
+    for (int q = 1; q < s1_parts; ++q) {
+      SC_HIP(ctx, hipEventRecord(ctx->side_joins[q - 1], ctx->side_streams[q - 1]));
+      SC_HIP(ctx, hipStreamWaitEvent(st, ctx->side_joins[q - 1], 0));
+    }
+    SC_TRY(rc_parts);
+  } else {
+    for (int p = 0; p < npanels; ++p) SC_TRY(run_panel(R, p, 0, batch, st, true));
+  }
+  SC_HIP(ctx, hipGetLastError());
+  return SC_OK;
+}
+
+// The persistent chase of the whole batch as ONE launch (+ k_chase_finish, the take-over) in the form sc_host::chase_form_for
+// chose.  Returns whether it went out; if not, the caller chases by the per-wavefront launches.
+static int launch_chase(sc_ctx* ctx, sc_host::ChaseForm form, int n, int batch, double* d_sb_ws, const SbLayout& SL,
+                        SbTimers& timers, bool* chased) {
+  using sc_host::ChaseForm;
+  hipStream_t st = ctx->stream;
+  const bool pair = form == ChaseForm::Pair;
+  int per_cu = 0;
+  const hipError_t oe =
+      pair ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bulge_pair, 512, kPairLdsBytes)
+           : (form == ChaseForm::Spread ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bulge_chase<1>, 256, 0)
+                                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bulge_chase<0>, 256, 0));
+  if (oe != hipSuccess) per_cu = 0;
+  const sc_host::ChaseLaunch L =
+      sc_host::chase_launch(sc_host::two_stage_env(), form, n, batch, ctx->nxcd, ctx->num_cus, per_cu);
+  if (L.W < 1) return SC_OK;
+  // progress counters (batch x n) | claim counters (batch) | early hand-off records in dc_aux; the control block is the
+  // context's own (dc_aux is reused by the D&C of this solve before sc_collect_events reads the block)
+  SC_TRY(sc_reserve_dc_aux(ctx, L.prog_bytes + L.next_bytes + L.early_bytes));
+  int* d_prog = reinterpret_cast<int*>(ctx->dc_aux);
+  int* d_next = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->dc_aux) + L.prog_bytes);
+  int* d_ctl = ctx->d_chase_ctl;
+  v4i* d_early = L.early_bytes ? reinterpret_cast<v4i*>(reinterpret_cast<char*>(ctx->dc_aux) + L.prog_bytes + L.next_bytes)
+                               : nullptr;
+  SC_HIP(ctx, hipMemsetAsync(ctx->dc_aux, 0, L.prog_bytes + L.next_bytes + L.early_bytes, st));
+  SC_HIP(ctx, hipMemsetAsync(d_ctl, 0, kChaseCtlInts * sizeof(int), st));
+  timers.bulge.start();
+  if (pair)
+    hipLaunchKernelGGL(k_bulge_pair, dim3((unsigned)L.grid), dim3(512), kPairLdsBytes, st, d_sb_ws,
+                       PairLayout{SL.n, SL.slab, SL.ab, SL.vd, SL.tau2}, batch, L.W, L.nxcd, d_prog, d_next, d_ctl,
+                       ctx->chase_give_up);
+  else if (form == ChaseForm::Spread)
+    hipLaunchKernelGGL(k_bulge_chase<1>, dim3((unsigned)L.grid), dim3(256), 0, st, d_sb_ws, SL, batch, L.W, L.nxcd, d_prog,
+                       d_next, d_ctl, ctx->chase_give_up, d_early);
+  else
+    hipLaunchKernelGGL(k_bulge_chase<0>, dim3((unsigned)L.grid), dim3(256), 0, st, d_sb_ws, SL, batch, L.W, L.nxcd, d_prog,
+                       d_next, d_ctl, ctx->chase_give_up, d_early);
+  const hipError_t le = hipGetLastError();
+  timers.bulge.stop();
+  if (le != hipSuccess) {
+    // a refused pair launch (e.g. the 157 KB of dynamic LDS on a device that does not grant them): this solve is
+    // finished by the per-wavefront launches, later solves of the context leave the pair form alone
+    if (pair) {
+      ctx->pair_attr = 0;
+      ++ctx->cnt_pair_fallbacks;
+    }
+    return SC_OK;
+  }
+  // (round 6: no look at the outcome from the host -- the take-over is a launch of its own that returns at once
+  // when the chase completed, and the control block's counts reach the context's counters at the next
+  // synchronising call: sc_collect_events)
+  hipLaunchKernelGGL(k_chase_finish, dim3((unsigned)batch), dim3(256), 0, st, d_sb_ws, SL, batch, L.nxcd, d_prog,
+                     (const int*)d_ctl, ctx->d_status);
+  SC_HIP(ctx, hipGetLastError());
+  ++ctx->cnt_chase_launches;
+  if (pair) ++ctx->cnt_pair_launches;
+  ctx->last_chase_ctl = d_ctl;
+  ctx->chase_ctl_xcds = L.nxcd;
+  *chased = true;
+  return SC_OK;
+}
+
+// The chase as one launch per wavefront of tasks (k_bulge_step), parts of the batch on separate streams.
+static int chase_stepwise(sc_ctx* ctx, int n, int batch, double* d_sb_ws, const SbLayout& SL) {
+  const sc_host::TwoStageEnv& E = sc_host::two_stage_env();
+  hipStream_t st = ctx->stream;
+  const int t_max = 2 * (n - 3) + chase_len(n, n - 3) - 1;
+  const int gx = chase_len(n, 0) / 2 + 1;
+  const int nparts = sc_host::bulge_stream_parts(E, batch);
+  if (nparts > 1) {
+    SC_TRY(sc_aux_stream(ctx));            // (its fork event)
+    SC_TRY(sc_side_streams(ctx, nparts - 1));
+    SC_HIP(ctx, hipEventRecord(ctx->aux_fork, st));
+    for (int p = 1; p < nparts; ++p) SC_HIP(ctx, hipStreamWaitEvent(ctx->side_streams[p - 1], ctx->aux_fork, 0));
+    const int burst = sc_host::bulge_burst(E);
+    for (int t0 = 0; t0 <= t_max; t0 += burst)
+      for (int p = 0; p < nparts; ++p) {
+        const int lo = (int)((long long)batch * p / nparts), hi = (int)((long long)batch * (p + 1) / nparts);
+        for (int t = t0; t <= std::min(t_max, t0 + burst - 1); ++t)
+          hipLaunchKernelGGL(k_bulge_step, dim3((unsigned)gx, (unsigned)(hi - lo)), dim3(256), 0,
+                             p == 0 ? st : ctx->side_streams[p - 1], d_sb_ws + (size_t)lo * SL.slab, SL, t);
+      }
+    for (int p = 1; p < nparts; ++p) {
+      SC_HIP(ctx, hipEventRecord(ctx->side_joins[p - 1], ctx->side_streams[p - 1]));
+      SC_HIP(ctx, hipStreamWaitEvent(st, ctx->side_joins[p - 1], 0));
+    }
+  } else {
+    for (int t = 0; t <= t_max; ++t)
+      hipLaunchKernelGGL(k_bulge_step, dim3((unsigned)gx, (unsigned)batch), dim3(256), 0, st, d_sb_ws, SL, t);
+  }
+  return SC_OK;
+}
+
+// Stage 2 on ctx->stream: band -> tridiagonal; d, e into the tri slab.
+static int sb_stage2(sc_ctx* ctx, double* d_a, long long stride_a, int n, int batch, double* d_tri_ws, const TriLayout& TL,
+                     double* d_sb_ws, const SbLayout& SL, double* d_band_copy, SbTimers& timers) {
+  hipStream_t st = ctx->stream;
+  hipLaunchKernelGGL(k_band_extract, dim3(256, (unsigned)batch), dim3(256), 0, st, d_a, stride_a, d_sb_ws, SL);
+  if (d_band_copy)   // debugging aid: the band as stage 1 left it (first matrix)
+    SC_HIP(ctx, hipMemcpyAsync(d_band_copy, d_sb_ws + SL.ab, sizeof(double) * kLdab * n, hipMemcpyDeviceToDevice, st));
+  hipLaunchKernelGGL(k_sb_clean, dim3((unsigned)n, (unsigned)batch), dim3(256), 0, st, d_a, stride_a, n);
+  for (int b = 0; b < batch; ++b) {
+    double* sb = d_sb_ws + (size_t)b * SL.slab;
+    SC_HIP(ctx, hipMemsetAsync(sb + SL.vd, 0, sizeof(double) * (size_t)SL.ndia * kDiaSize, st));
+    SC_HIP(ctx, hipMemsetAsync(sb + SL.tau2, 0, sizeof(double) * (size_t)SL.ndia * kG, st));
+  }
+  if (n >= 3) {
+    if (ctx->pair_attr < 0)   // per device, hence per context (ADVICE round 4): the caller made ctx->device current
+      ctx->pair_attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bulge_pair),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPairLdsBytes) == hipSuccess;
+    if (ctx->nxcd <= 0) SC_TRY(probe_xcd_count(ctx, st));
+    const sc_host::ChaseForm form =
+        sc_host::chase_form_for(sc_host::two_stage_env(), n, batch, ctx->nxcd, ctx->num_cus, ctx->pair_attr == 1,
+                                ctx->chase_mode, ctx->chase_form, ctx->chase_ok);
+    bool chased = false;
+    if (form != sc_host::ChaseForm::Stepwise) SC_TRY(launch_chase(ctx, form, n, batch, d_sb_ws, SL, timers, &chased));
+    if (!chased) {
+      ++ctx->cnt_stepwise_chases;
+      timers.bulge.start();
+      SC_TRY(chase_stepwise(ctx, n, batch, d_sb_ws, SL));
+      timers.bulge.stop();
+    }
+  }
+  hipLaunchKernelGGL(k_band_to_tri, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, st, d_sb_ws, SL,
+                     d_tri_ws, TL);
+  SC_HIP(ctx, hipGetLastError());
+  return SC_OK;
+}
+
+// ================================================================================================================
 // Stage 1 + 2 driver.  d_a: lower triangle valid (after mirror_lower_batched).  On exit: tri slab holds d, e and the
 // stage-1 tau; A holds the stage-1 reflectors (cleaned for the back-transformation); the sb slab holds the diamonds.
 int sytrd_2stage_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, int batch, double* d_tri_ws,
@@ -4152,22 +3806,10 @@ int sytrd_2stage_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, in
     SC_HIP(ctx, hipEventRecord(ev[0], st));
   }
 
-  // ---- descriptors of stage 1: per panel kDescKinds kinds x batch
-  // Panels are taken in PAIRS where the trailing matrix is large enough: the second panel of a pair is factored from
-  // columns that received the first panel's update alone (record D), its X = A22 V2 is computed from the NOT yet updated
-  // trailing matrix and corrected by - [V1|W1] ([W1|V1]^T V2) (records Q, Corr), and one trailing update
-  // A22 -= [V1|W1|V2|W2] [W1|V1|W2|V2]^T (K = 256) serves both panels: the lower triangle is read and written once per
-  // 128 columns of band instead of once per 64 (at K = 128 the C traffic of a tile takes as long as its MFMAs).
-  int npanels = 0;
-  while (n - (npanels + 1) * kB >= 2) ++npanels;
-  static const bool pair_env = [] { const char* e = getenv("SPRINGCRAFT_PANEL_PAIRS"); return !e || atoi(e) != 0; }();
-  std::vector<int> role((size_t)npanels, 0);   // 0 single, 1 first of a pair, 2 second of a pair
-  if (pair_env)
-    for (int p = 0; p + 1 < npanels;) {
-      const int m2 = n - (p + 2) * kB;
-      if (m2 >= 4 * kB) { role[(size_t)p] = 1; role[(size_t)p + 1] = 2; p += 2; }
-      else ++p;
-    }
+  // ---- descriptors of stage 1: per panel kDescKinds kinds x batch (the panels' roles: sc_host::panel_roles)
+  const sc_host::TwoStageEnv& E = sc_host::two_stage_env();
+  const std::vector<int> role = sc_host::panel_roles(E, n);   // 0 single, 1 first of a pair, 2 second of a pair
+  const int npanels = (int)role.size();
   std::vector<GemmDesc> h((size_t)npanels * kDescKinds * batch);
   for (int p = 0; p < npanels; ++p) {
     const int j0 = p * kB, r0 = j0 + kB, m = n - r0;
@@ -4223,7 +3865,7 @@ int sytrd_2stage_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, in
       R.c = a22; R.ldc = n;
       R.m = m; R.n = m; R.k = rl == 2 ? 4 * kB : 2 * kB; R.alpha = 1.0; R.beta = 1.0;   // b = -[W|V]
       // (with k_symm3 in use the trailing updates also keep the first super-diagonal entry of every even row: symm3.hip)
-      R.lower_only = symm3_for(n) ? 2 : 1;
+      R.lower_only = sc_host::symm3_for(E, n) ? 2 : 1;
       g[5] = R;
       // first of a pair: only the next panel's 64 columns (and the band block above them) get this panel's update now
       GemmDesc D = R;
@@ -4257,408 +3899,17 @@ int sytrd_2stage_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, in
   const std::vector<int> doff = dia_offsets(n);
   SC_TRY(sc_stage_upload(ctx, d_dia_off, doff.data(), doff.size() * sizeof(int)));
 
-  // tau of columns without a reflector must read 0
-  for (int b = 0; b < batch; ++b)
-    SC_HIP(ctx, hipMemsetAsync(d_tri_ws + (size_t)b * TL.slab + TL.tau, 0, sizeof(double) * n, st));
-
-  const size_t lds_qr = sizeof(double) * ((size_t)kB * (kQrRows + 1) + kB + kQrRows + 4 * kB);
-  const size_t lds_qr_blk = sizeof(double) * ((size_t)(kIb + 1) * (kQrRows + 1) + kB + kQrRows + 4 * kB);
-  const size_t lds_small = sizeof(double) * 4 * kB * (kB + 1);
-  const size_t lds_blk_a = sizeof(double) * ((size_t)kB * (kQrRows + 1) + kQrRows + 8 * kB);
-  const size_t lds_blk_b = sizeof(double) * ((size_t)kB * (kQrRows + 1) + kIb * kB + 4 * kB);
-  static const bool blocked_qr = getenv("SPRINGCRAFT_QR_UNBLOCKED") == nullptr;
-  PhaseTimer t_qr(ctx, "panel_qr", st), t_symm(ctx, "symm", st), t_syr2k(ctx, "syr2k", st), t_bulge(ctx, "bulge", st);
-  // ---- the cooperative panel kernel (k_panel_coop) for tall panels of a few matrices: SPRINGCRAFT_QR_COOP = 0 keeps the
-  // chunked launches, SPRINGCRAFT_QR_COOP_MIN = rows from which a panel takes it (default: above k_panel_wg's 4096)
-  static const int env_coop = [] { const char* e = getenv("SPRINGCRAFT_QR_COOP"); return e ? atoi(e) : 1; }();
-  // (one matrix, per panel: 0.77 ms by the chunked launches whatever the height, 0.3 - 0.5 ms by k_panel_wg's single
-  // workgroup, 0.25 - 0.3 ms here -- C5: panel QR 289 -> 109 ms, a single n = 6000 matrix: 52 -> 23 ms.  With four and more
-  // matrices the single-workgroup kernels run them side by side and keep their range; the taller panels come here)
-  static const int coop_min_env = [] { const char* e = getenv("SPRINGCRAFT_QR_COOP_MIN"); return e ? std::max(2 * kB, atoi(e)) : 0; }();
-  const int coop_min_few = ctx->coop_min_rows > 0 ? ctx->coop_min_rows : (coop_min_env > 0 ? coop_min_env : 300);
-  const int coop_min_many = ctx->coop_min_rows > 0 ? ctx->coop_min_rows : (coop_min_env > 0 ? coop_min_env : 12 * 512 + 1);
-  const int coop_min = std::min(coop_min_few, coop_min_many);
-  // every workgroup of a launch waits for all others: matrices x workgroups stays well below the CUs of the device
-  const int coop_budget = ctx->num_cus * 3 / 4;
-  const int coop_gmax = (std::max(n - kB, 1) + kCoopRows - 1) / kCoopRows;
-  v4i* coop_recs = nullptr;
-  int* coop_ctl = nullptr;
-  // (only when the whole batch runs on one stream: the parts of a split batch must not be factored by different kernels --
-  // other reduction trees, other last bits -- or the same structure at two batch positions gives different eigenvalues)
-  static const int env_s1_early = [] { const char* e = getenv("SPRINGCRAFT_STAGE1_STREAMS"); return e ? atoi(e) : 0; }();
-  const bool one_stream = std::max(1, std::min(env_s1_early > 0 ? env_s1_early : ((batch >= 32 && !prof) ? 2 : 1), std::min(batch, 4))) == 1;
-  if ((ctx->coop_min_rows > 0 || (ctx->coop_min_rows < 0 && env_coop != 0)) && ctx->coop_ok != 0 && n - kB >= coop_min &&
-      coop_gmax <= kCoopMaxG && one_stream) {
-    if (ctx->coop_attr < 0)
-      ctx->coop_attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_panel_coop),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCoopLdsBytes) == hipSuccess;
-    const int nb_max = std::min(batch, coop_budget / coop_gmax);
-    if (ctx->coop_attr == 1 && nb_max >= 1) {
-      const size_t rec_bytes = (size_t)batch * coop_recs_per_matrix(coop_gmax) * sizeof(v4i);
-      const size_t ctl_bytes = align_up((size_t)batch * 8 * sizeof(int), 256);   // one control record per matrix
-      SC_TRY(sc_reserve_dc_aux(ctx, ctl_bytes + rec_bytes));
-      coop_ctl = reinterpret_cast<int*>(ctx->dc_aux);
-      coop_recs = reinterpret_cast<v4i*>(reinterpret_cast<char*>(ctx->dc_aux) + ctl_bytes);
-      // (sequence numbers are unique within a solve only)
-      SC_HIP(ctx, hipMemsetAsync(ctx->dc_aux, 0, ctl_bytes + rec_bytes, st));
-    }
-  }
-  // k_symm3 writes X into the X1 block of [X1 | X2 | V]; the X2 block reads zero for the whole solve (the panels at the
-  // end of the reduction that fall back to the two triangular-operand launches rewrite their rows of it themselves)
-  const bool use_symm3 = symm3_for(n) && (n & 1) == 0;
-  // (whether a panel takes it is decided for the SMALLEST part of a batch that is split over streams, and then holds for
-  // every part: the same structure at two batch positions must not meet two kernels -- other summation orders, other last
-  // bits; found by tools/test_matrix.sh with three parts of unequal size, profiles/r06_test_matrix.txt)
-  const int symm3_parts = std::max(1, std::min(env_s1_early > 0 ? env_s1_early : ((batch >= 32 && !prof) ? 2 : 1), std::min(batch, 4)));
-  const int symm3_nb_min = std::max(1, batch / symm3_parts);
-  if (use_symm3)
-    for (int b = 0; b < batch; ++b)
-      SC_HIP(ctx, hipMemsetAsync(d_sb_ws + (size_t)b * SL.slab + SL.xv + (size_t)kB * n, 0, sizeof(double) * (size_t)kB * n, st));
-  // One panel of the matrices [lo, hi) on `ps`: QR of the panel, X = A22 V, the small products, W, the trailing update
-  // its role asks for (single: SYR2K; first of a pair: the next panel's columns only; second: the joint update).
-  auto run_panel = [&](int p, int lo, int hi, hipStream_t ps, bool timed) -> int {
-    struct StreamScope {   // launch_gemm_f64 launches on the context's stream
-      sc_ctx* c; hipStream_t old;
-      StreamScope(sc_ctx* c_, hipStream_t s) : c(c_), old(c_->stream) { c->stream = s; }
-      ~StreamScope() { c->stream = old; }
-    } scope(ctx, ps);
-    const int nb = hi - lo;
-    const int rl = role[(size_t)p];
-    double* a_h = d_a + (size_t)lo * stride_a;
-    double* tri_h = d_tri_ws + (size_t)lo * TL.slab;
-    double* sb_h = d_sb_ws + (size_t)lo * SL.slab;
-    const int j0 = p * kB, r0 = j0 + kB, m = n - r0;
-    const int nr = std::min(kB, m - 1);
-    const int nchunks = (m + kQrRows - 1) / kQrRows;
-    const dim3 qgrid((unsigned)nchunks, (unsigned)nb);
-    SbLayout SQ = SL;     // where the panel QR leaves V: the second panel of a pair uses the second half of [V|W..], [W|V..]
-    if (rl == 2) { SQ.vw += (long long)2 * kB * n; SQ.wv += (long long)2 * kB * n; }
-    if (timed) t_qr.start();
-    // (one workgroup per matrix while the panel is short enough for its rows to sit in the registers of 1024 threads --
-    // also for a single matrix: N = 512 two-stage 45 -> 37 ms; SPRINGCRAFT_QR_WG = 0 keeps the chunked launches)
-    static const int env_wg = [] { const char* e = getenv("SPRINGCRAFT_QR_WG"); return e ? atoi(e) : -1; }();
-    // (round 4: panels of 4097 .. 6144 rows -- the first 29 of n = 6000 -- by 512 threads with up to 12 rows each: twice
-    // the registers per thread; SPRINGCRAFT_QR_WG = 1 keeps them on the chunked launches)
-    const bool use_wg = nr == kB && m <= 4 * kWgThreads && env_wg != 0;
-    // (not for a few matrices: one workgroup streams its panel at the rate of ONE CU -- a single N = 2000 structure's
-    // panel QRs take 70 instead of 52 ms that way)
-    const bool use_wg512 = nr == kB && !use_wg && m <= 12 * 512 && env_wg != 0 && env_wg != 1 && nb >= 4;
-    const int coop_g = (m + kCoopRows - 1) / kCoopRows;
-    const bool use_coop = coop_recs != nullptr && nr == kB && m >= (nb < 4 ? coop_min_few : coop_min_many) &&
-                          nb * coop_g <= coop_budget && ps == st;
-    if (use_coop) {
-      // (test hook, sc_dbg_set_panel_coop_fail: from this panel on the matrices' abort flags are up, as after a time-out)
-      if (p == ctx->coop_fail_panel) SC_HIP(ctx, hipMemsetAsync(coop_ctl + 8 * lo, 1, sizeof(int) * 8 * nb, ps));
-      hipLaunchKernelGGL(k_panel_coop, dim3((unsigned)coop_g, (unsigned)nb), dim3(kCoopRows), kCoopLdsBytes, ps, a_h, stride_a,
-                         tri_h, TL, sb_h, SQ, j0, coop_g, coop_recs + (size_t)lo * coop_recs_per_matrix(coop_g),
-                         coop_ctl + 8 * lo, (p + 1) * 128);
-      // the take-over: returns at once unless a wait of the launch above (or of an earlier panel) timed out
-      hipLaunchKernelGGL(k_panel_serial, dim3((unsigned)nb), dim3(1024), 0, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0,
-                         (const int*)(coop_ctl + 8 * lo), ctx->d_status);
-      ++ctx->cnt_coop_launches;
-    } else if (use_wg) {
-      const size_t lds_wg = sizeof(double) * (size_t)(2 * kWgWaves * 8 + 16 + 8 + 8 * kB + kWgWaves * kB * 8);
-      const int ru = (m + kWgThreads - 1) / kWgThreads;
-      const dim3 g1((unsigned)nb), b1((unsigned)kWgThreads);
-      if (ru <= 1) hipLaunchKernelGGL((k_panel_wg<1, 8>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
-      else if (ru == 2) hipLaunchKernelGGL((k_panel_wg<2, 8>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
-      else if (ru == 3) hipLaunchKernelGGL((k_panel_wg<3, 4>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
-      else hipLaunchKernelGGL((k_panel_wg<4, 2>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
-    } else if (use_wg512) {
-      constexpr int kW = 512 / 64;
-      const size_t lds_wg = sizeof(double) * (size_t)(2 * kW * 8 + 16 + 8 + 8 * kB + kW * kB * 8);
-      const int ru = (m + 511) / 512;
-      const dim3 g1((unsigned)nb), b1(512u);
-      if (ru <= 10) hipLaunchKernelGGL((k_panel_wg<10, 1, 512>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
-      else hipLaunchKernelGGL((k_panel_wg<12, 1, 512>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
-    } else if (nr == kB && blocked_qr) {
-      // blocked panel: inner blocks of 8 columns, their reflectors applied to the rest of the panel at once
-      hipLaunchKernelGGL(k_panel_qr, qgrid, dim3(256), lds_qr_blk, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, 0, nr, kIb);
-      for (int c0 = 0; c0 < kB; c0 += kIb) {
-        for (int j = c0 + 1; j < c0 + kIb; ++j)
-          hipLaunchKernelGGL(k_panel_qr, qgrid, dim3(256), lds_qr_blk, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, j, nr,
-                             c0 + kIb);
-        // (their LDS image holds columns c0 .. kB-1 only)
-        const size_t cut = sizeof(double) * (size_t)c0 * (kQrRows + 1);
-        hipLaunchKernelGGL(k_pqr_blk_a, qgrid, dim3(256), lds_blk_a - cut, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, c0);
-        if (c0 + kIb < kB)
-          hipLaunchKernelGGL(k_pqr_blk_b, qgrid, dim3(256), lds_blk_b - cut, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, c0);
-      }
-    } else {
-      for (int j = 0; j <= nr; ++j)
-        hipLaunchKernelGGL(k_panel_qr, qgrid, dim3(256), lds_qr, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, j, nr, kB);
-    }
-    if (timed) t_qr.stop();
-    const GemmDesc* g = d_descs + (size_t)p * kDescKinds * batch;   // [kind][batch]
-    if (timed) t_symm.start();
-    // X = A22 V: one launch of k_symm3 (X into X1; X2 was zeroed for the whole solve) while the panel has enough tiles
-    // for it, else X1 = L V and X2 = strict(L)^T V by two triangular-operand launches of k_gemm2
-    if (use_symm3 && symm3_would_take(ctx, symm3_nb_min, m, SL.symm_split, /*aligned16=*/true) &&
-        launch_symm3(ctx, g + lo, nb, m, SL.symm_split, /*aligned16=*/true, /*any_size=*/true) == SC_OK) {
-      if (SL.symm_split > 1)
-        hipLaunchKernelGGL(k_sum_xslices, dim3((unsigned)((m + 255) / 256), kB, (unsigned)nb), dim3(256), 0, ps, sb_h, SL, r0);
-    } else {
-      SC_TRY(launch_gemm_f64(ctx, g + lo, nb, m, kB, kGemmTile, SL.symm_split, false, true, kGemmAmBk));           // X1 = L V
-      SC_TRY(launch_gemm_f64(ctx, g + batch + lo, nb, m, kB, kGemmTile, SL.symm_split, false, true, kGemmAkBk));   // X2 = strict(L)^T V
-      if (SL.symm_split > 1)
-        hipLaunchKernelGGL(k_sum_xslices, dim3((unsigned)((m + 255) / 256), 2 * kB, (unsigned)nb), dim3(256), 0, ps, sb_h, SL, r0);
-    }
-    if (rl == 2) {   // the trailing matrix has not seen the first panel's update yet: X1 -= [V1|W1] ([W1|V1]^T V2)
-      SC_TRY(launch_gemm_f64(ctx, g + 7 * batch + lo, nb, 2 * kB, kB, kGemmTile, kSmallSplit, false, false, kGemmAkBk));
-      hipLaunchKernelGGL(k_sum_p2, dim3((unsigned)(2 * kB * kB / 256), (unsigned)nb), dim3(256), 0, ps, sb_h, SL);
-      SC_TRY(launch_gemm_f64(ctx, g + 8 * batch + lo, nb, m, kB, kGemmTile, 1, false, false, kGemmAmBk));
-    }
-    if (timed) t_symm.stop();
-    SC_TRY(launch_gemm_f64(ctx, g + 2 * batch + lo, nb, kB, 3 * kB, kGemmTile, kSmallSplit, false, false, kGemmAkBk));
-    hipLaunchKernelGGL(k_sb_small, dim3((unsigned)nb), dim3(1024), lds_small, ps, tri_h, TL, sb_h, SL, j0);
-    if (nb == batch) {
-      SC_TRY(launch_gemm_f64(ctx, g + 3 * batch, 2 * batch, m, kB, kGemmTile, 1, false, false, kGemmAmBk));
-    } else {
-      SC_TRY(launch_gemm_f64(ctx, g + 3 * batch + lo, nb, m, kB, kGemmTile, 1, false, false, kGemmAmBk));
-      SC_TRY(launch_gemm_f64(ctx, g + 4 * batch + lo, nb, m, kB, kGemmTile, 1, false, false, kGemmAmBk));
-    }
-    if (timed) t_syr2k.start();
-    if (rl == 1)
-      SC_TRY(launch_gemm_f64(ctx, g + 6 * batch + lo, nb, m, kB, kGemmTile, 1, false, false, kGemmAmBn));
-    else
-      // (records of one launch share (m, m, K); operands start at even rows of buffers with even leading dimension n)
-      if (launch_gemm3_uniform(ctx, g + 5 * batch + lo, nb, m, m, rl == 2 ? 4 * kB : 2 * kB, kGemmAmBn, /*lower=*/use_symm3 ? 2 : 1, 1.0, 1.0,
-                               /*aligned16=*/(n & 1) == 0 && (r0 & 1) == 0) != SC_OK)
-        SC_TRY(launch_gemm_f64(ctx, g + 5 * batch + lo, nb, m, m, kGemmTile, 1, false, false, kGemmAmBn, /*lower_grid=*/true));
-    if (timed) t_syr2k.stop();
-    return SC_OK;
-  };
-  // Two parts of a large batch on separate streams: the latency-bound panel QR of one part runs beside the GEMMs of the
-  // other (618 -> 591 ms per step at 64 matrices).  A profiled solve keeps everything on one stream, because the
-  // kernel-group times (panel_qr / symm / syr2k) are event brackets on that stream: its band reduction is therefore
-  // about 30 ms longer than in an unprofiled solve.
-  static const int env_s1 = [] { const char* e = getenv("SPRINGCRAFT_STAGE1_STREAMS"); return e ? atoi(e) : 0; }();
-  const int s1_want = env_s1 > 0 ? env_s1 : ((batch >= 32 && !prof) ? 2 : 1);
-  const int s1_parts = std::max(1, std::min(s1_want, std::min(batch, 4)));
-  if (s1_parts > 1) {
-    struct SideBySide {   // (k_gemm3 leaves CUs to the other parts' kernels while this is set: gemm3_would_take)
-      sc_ctx* c;
-      explicit SideBySide(sc_ctx* c_) : c(c_) { c->gemm3_side_by_side = true; }
-      ~SideBySide() { c->gemm3_side_by_side = false; }
-    } side_by_side(ctx);
-    SC_TRY(sc_aux_stream(ctx));
-    SC_TRY(sc_side_streams(ctx, s1_parts - 1));
-    SC_HIP(ctx, hipEventRecord(ctx->aux_fork, st));
-    for (int q = 1; q < s1_parts; ++q) SC_HIP(ctx, hipStreamWaitEvent(ctx->side_streams[q - 1], ctx->aux_fork, 0));
-    int rc_parts = SC_OK;
-    for (int p = 0; p < npanels && rc_parts == SC_OK; ++p)
-      for (int q = 0; q < s1_parts && rc_parts == SC_OK; ++q) {
-        const int lo = (int)((long long)batch * q / s1_parts), hi = (int)((long long)batch * (q + 1) / s1_parts);
-        rc_parts = run_panel(p, lo, hi, q == 0 ? st : ctx->side_streams[q - 1], q == 0);
-      }
-    // (also after an error: the side streams are joined before anything returns, so that what they still have queued
-    // is ordered before whatever the caller enqueues next on the main stream)
-    for (int q = 1; q < s1_parts; ++q) {
-      SC_HIP(ctx, hipEventRecord(ctx->side_joins[q - 1], ctx->side_streams[q - 1]));
-      SC_HIP(ctx, hipStreamWaitEvent(st, ctx->side_joins[q - 1], 0));
-    }
-    SC_TRY(rc_parts);
-  } else {
-    for (int p = 0; p < npanels; ++p) SC_TRY(run_panel(p, 0, batch, st, true));
-  }
-  SC_HIP(ctx, hipGetLastError());
+  SbTimers timers(ctx, st);
+  SC_TRY(sb_stage1(ctx, d_a, stride_a, n, batch, d_tri_ws, TL, d_sb_ws, SL, d_descs, role, prof, timers));
   if (prof) SC_HIP(ctx, hipEventRecord(ev[1], st));
-
-  // ---- stage 2
-  hipLaunchKernelGGL(k_band_extract, dim3(256, (unsigned)batch), dim3(256), 0, st, d_a, stride_a, d_sb_ws, SL);
-  if (d_band_copy)   // debugging aid: the band as stage 1 left it (first matrix)
-    SC_HIP(ctx, hipMemcpyAsync(d_band_copy, d_sb_ws + SL.ab, sizeof(double) * kLdab * n, hipMemcpyDeviceToDevice, st));
-  hipLaunchKernelGGL(k_sb_clean, dim3((unsigned)n, (unsigned)batch), dim3(256), 0, st, d_a, stride_a, n);
-  for (int b = 0; b < batch; ++b) {
-    double* sb = d_sb_ws + (size_t)b * SL.slab;
-    SC_HIP(ctx, hipMemsetAsync(sb + SL.vd, 0, sizeof(double) * (size_t)SL.ndia * kDiaSize, st));
-    SC_HIP(ctx, hipMemsetAsync(sb + SL.tau2, 0, sizeof(double) * (size_t)SL.ndia * kG, st));
-  }
-  if (n >= 3) {
-    const int t_max = 2 * (n - 3) + chase_len(n, n - 3) - 1;
-    const int gx = chase_len(n, 0) / 2 + 1;
-    // The launches of one chase are strictly ordered and every one of them ends with a partly filled last round of
-    // workgroups.  Parts of the batch on separate streams run the same launches independently of each other, so the
-    // tail of one part's launch is filled by the next launch of another part.
-    // ---- persistent chase (k_bulge_chase: one launch, sweeps claimed dynamically) while the stage is latency-bound;
-    // else, or with SPRINGCRAFT_BULGE_PERSISTENT=0, one launch per wavefront below
-    static const int env_persist = [] { const char* e = getenv("SPRINGCRAFT_BULGE_PERSISTENT"); return e ? atoi(e) : 1; }();
-    const int persist = ctx->chase_mode >= 0 ? ctx->chase_mode : env_persist;
-    bool chased = false;
-    // Which form (profiles/r04_bulge_sweep.txt, batch x n: pair / one sweep per workgroup / per-wavefront launches, ms):
-    // 16 x 6000: 126 / 115 / 169, 32 x 3000: 63 / 56 / 82, 64 x 3000: 92 / 99 / 124, 32 x 6000: 182 / 223 / 256,
-    // 64 x 6000: 335 / 435 / 436.  While the stage is latency-bound (batch * n / 128 <= 1100) one sweep per workgroup has
-    // the shorter dependent chain; above that the stage is bound by bytes and the pair form moves half of them.  With
-    // fewer matrices than XCDs (a matrix is confined to one XCD) only while the order is moderate: a single n = 24000
-    // matrix chases 1.6 x faster with its ~188 tasks per wavefront spread over the whole chip (411 vs 676 ms)
-    static const bool use_pair = [] { const char* e = getenv("SPRINGCRAFT_BULGE_PAIR"); return !e || atoi(e) != 0; }();
-    static const int force_pair = [] { const char* e = getenv("SPRINGCRAFT_BULGE_PAIR"); return e ? atoi(e) : -1; }();
-    // SPRINGCRAFT_PAIR_LOADER = 1: the pair form with its loader waves (k_bulge_pair<1>, 768 threads: measured, slower --
-    // profiles/r06_pair_stamps.txt; default: the 512-thread form)
-    static const bool pair_loader = [] { const char* e = getenv("SPRINGCRAFT_PAIR_LOADER"); return e && atoi(e) != 0; }();
-    // SPRINGCRAFT_PAIR_EARLY = 1: the pair form looks at its predecessor a step ahead (measured: 317-319 against 312-313 ms
-    // at 64 x n = 6000, profiles/r06_pair_ab.txt; default: when a step begins, as in round 4)
-    static const int pair_early = [] { const char* e = getenv("SPRINGCRAFT_PAIR_EARLY"); return (e && atoi(e) != 0) ? 1 : 0; }();
-    if (ctx->pair_attr < 0)   // per device, hence per context (ADVICE round 4): the caller made ctx->device current
-      ctx->pair_attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bulge_pair<0>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPairLdsBytes) == hipSuccess &&
-                       hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bulge_pair<1>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPairLdsBytes) == hipSuccess;
-    const bool pair_attr = ctx->pair_attr == 1;
-    const long long work = (long long)batch * n / 128;
-    // SPRINGCRAFT_BULGE_PAIR = 0: never the pair form, 2: the pair form for every persistent chase (tests), else by size
-    static const long long kPairWorkMax = [] { const char* e = getenv("SPRINGCRAFT_BULGE_PAIR_MAX"); return e ? atoll(e) : 6000LL; }();
-    // (by size only inside the measured range -- profiles/r04_bulge_sweep.txt up to 64 x 6000, profiles/r05_bulge_sweep_ext.txt
-    // up to 96 x 6000 and 256 x 3000, B n / 128 = 6000: the pair form wins everywhere there (622 vs 742 / 775 ms, 354 vs
-    // 467 / 558) -- and only while every matrix of an XCD has a pair workgroup of its own (one per CU): 512 x 1026 puts 64
-    // matrices on the 32 CUs of an XCD, a workgroup then walks the matrices one after the other, 687 ms against 110 by
-    // the per-wavefront launches.  ADVICE round 4.)
-    if (ctx->nxcd <= 0) SC_TRY(probe_xcd_count(ctx, st));
-    const bool pair_measured = work <= kPairWorkMax && (batch + ctx->nxcd - 1) / ctx->nxcd <= std::max(1, ctx->num_cus / ctx->nxcd);
-    const bool pair = ctx->chase_form >= 0 ? (ctx->chase_form == 1 && pair_attr)
-                                           : use_pair && pair_attr &&
-                                                 (force_pair == 2 || (work > 1100 && batch >= 8 && pair_measured));
-    // Round 6, "spread": a few LARGE matrices (fewer than XCDs, n > 4500 -- config C5's single n = 24000 matrix has ~188
-    // tasks per wavefront, three times the workgroups one XCD holds) are chased by k_bulge_chase<1> from ALL XCDs, their
-    // band handed on by write-through stores; until round 5 the largest took one launch per wavefront.  One matrix on one XCD
-    // against all XCDs, bulge chasing in ms (tools/spread_sweep.py, profiles/r06_spread_chase.txt): n = 2100 24.3 / 26.4, 3000
-    // 35.2 / 38.2, 4200 54.0 / 53.4, 6000 84.2 / 76.9 (2 and 4 matrices: 86 / 78), 9000 144.6 / 116.3, 12000 195.6 / 156.3, 24000
-    // (per-wavefront launches) 418 / 318.  SPRINGCRAFT_BULGE_SPREAD = 0 / 1: never / for every chase with fewer matrices than
-    // XCDs (tests).
-    static const int env_spread = [] { const char* e = getenv("SPRINGCRAFT_BULGE_SPREAD"); return e ? atoi(e) : -1; }();
-    // (debug entry sc_dbg_set_chase: mode 5 forces it, modes 3 / 4 keep it off)
-    const bool spread = !pair && batch < ctx->nxcd &&
-                        (ctx->chase_form == 2 || (ctx->chase_form < 0 && env_spread != 0 && (env_spread == 1 || n > 4500)));
-    const bool want_chase =
-        persist == 2 || (persist == 1 && (pair || spread || (work <= 2800 && (batch >= 8 || n <= 6144))));
-    // a context whose chase ran into its time-out is not asked again (ctx->chase_ok = 0, counted in chase_timeouts):
-    // every further attempt could cost another bound's worth of spinning before the fallback
-    // XCDs of this device: the kernels bind matrix b to XCD b mod nxcd (an MI355X in SPX mode has 8 XCDs of 32 CUs; a
-    // partition of it has fewer, and a matrix bound to an XCD that is not there would never be claimed)
-    // (counted on the device, not derived from the CU count: ADVICE round 4)
-    if (ctx->nxcd <= 0) SC_TRY(probe_xcd_count(ctx, st));
-    const int nxcd = spread ? 1 : ctx->nxcd;   // (spread: every workgroup counts as "XCD 0" and serves every matrix)
-    if (want_chase && ctx->num_cus > 0 && (ctx->chase_ok != 0 || persist == 2)) {
-      int per_cu = 0;
-      if (pair) {
-        const hipError_t oe = pair_loader ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bulge_pair<1>, 768, kPairLdsBytes)
-                                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bulge_pair<0>, 512, kPairLdsBytes);
-        if (oe != hipSuccess) per_cu = 0;
-      } else {
-        const hipError_t oe = spread ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bulge_chase<1>, 256, 0)
-                                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bulge_chase<0>, 256, 0);
-        if (oe != hipSuccess) per_cu = 0;
-      }
-      const int slots_per_xcd = per_cu * ctx->num_cus / nxcd;
-      const int mpx = (batch + nxcd - 1) / nxcd;   // matrices per XCD (XCD 0 has the most)
-      // workgroups per matrix: all the XCD's slots divided by its matrices, but no more than sweeps can be in flight
-      // (every sweep trails its predecessor by two tasks; a pair its predecessor pair by three steps)
-      const int useful = pair ? std::max(4, chase_len(n, 0) / 3 + 2) : std::max(8, chase_len(n, 0) / 2 + 1);
-      const int W = slots_per_xcd > 0 ? std::max(1, std::min(useful, slots_per_xcd / mpx)) : 0;
-      if (W >= 1) {
-        // progress counters (batch x n) | claim counters (batch) in dc_aux; the control block is the context's own
-        // (dc_aux is reused by the D&C of this solve before sc_collect_events reads the block)
-        const size_t prog_bytes = align_up((size_t)batch * n * sizeof(int), 256);
-        const size_t next_bytes = align_up((size_t)batch * sizeof(int), 256);
-        // early hand-off records of k_bulge_chase (16 B x kEarlyRing per sweep; zeroed with the counters: a stale tag of
-        // the previous solve would pass for this one's)
-        static const bool no_early = getenv("SPRINGCRAFT_BULGE_NO_EARLY") != nullptr;
-        const size_t early_bytes = (pair || no_early) ? 0 : align_up((size_t)batch * n * kEarlyRing * sizeof(v4i), 256);
-        SC_TRY(sc_reserve_dc_aux(ctx, prog_bytes + next_bytes + early_bytes));
-        int* d_prog = reinterpret_cast<int*>(ctx->dc_aux);
-        int* d_next = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->dc_aux) + prog_bytes);
-        int* d_ctl = ctx->d_chase_ctl;
-        v4i* d_early = early_bytes ? reinterpret_cast<v4i*>(reinterpret_cast<char*>(ctx->dc_aux) + prog_bytes + next_bytes)
-                                   : nullptr;
-        SC_HIP(ctx, hipMemsetAsync(ctx->dc_aux, 0, prog_bytes + next_bytes + early_bytes, st));
-        SC_HIP(ctx, hipMemsetAsync(d_ctl, 0, kChaseCtlInts * sizeof(int), st));
-        // the dispatcher deals workgroups round-robin over the XCDs, so 8 x (workgroups one XCD needs) gives every XCD
-        // its share; the kernel does not rely on it (a short-changed XCD is just slower, see the kernel's header)
-        const int grid = nxcd * std::min(slots_per_xcd, mpx * W);
-        t_bulge.start();
-        if (pair && pair_loader)
-          hipLaunchKernelGGL(k_bulge_pair<1>, dim3((unsigned)grid), dim3(768), kPairLdsBytes, st, d_sb_ws,
-                             PairLayout{SL.n, SL.slab, SL.ab, SL.vd, SL.tau2}, batch, W, nxcd, d_prog, d_next, d_ctl,
-                             ctx->chase_give_up, pair_early);
-        else if (pair)
-          hipLaunchKernelGGL(k_bulge_pair<0>, dim3((unsigned)grid), dim3(512), kPairLdsBytes, st, d_sb_ws,
-                             PairLayout{SL.n, SL.slab, SL.ab, SL.vd, SL.tau2}, batch, W, nxcd, d_prog, d_next, d_ctl,
-                             ctx->chase_give_up, pair_early);
-        else
-          if (spread)
-            hipLaunchKernelGGL(k_bulge_chase<1>, dim3((unsigned)grid), dim3(256), 0, st, d_sb_ws, SL, batch, W, nxcd, d_prog,
-                               d_next, d_ctl, ctx->chase_give_up, d_early);
-          else
-            hipLaunchKernelGGL(k_bulge_chase<0>, dim3((unsigned)grid), dim3(256), 0, st, d_sb_ws, SL, batch, W, nxcd, d_prog,
-                               d_next, d_ctl, ctx->chase_give_up, d_early);
-        const hipError_t le = hipGetLastError();
-        t_bulge.stop();
-        if (le != hipSuccess && pair) {
-          // a refused pair launch (e.g. the 157 KB of dynamic LDS on a device that does not grant them): this solve is
-          // finished by the per-wavefront launches below, later solves of the context leave the pair form alone
-          ctx->pair_attr = 0;
-          ++ctx->cnt_pair_fallbacks;
-        }
-        if (le == hipSuccess) {
-          // (round 6: no look at the outcome from the host -- the take-over is a launch of its own that returns at once
-          // when the chase completed, and the control block's counts reach the context's counters at the next
-          // synchronising call: sc_collect_events)
-          hipLaunchKernelGGL(k_chase_finish, dim3((unsigned)batch), dim3(256), 0, st, d_sb_ws, SL, batch, nxcd, d_prog,
-                             (const int*)d_ctl, ctx->d_status);
-          SC_HIP(ctx, hipGetLastError());
-          ++ctx->cnt_chase_launches;
-          if (pair) ++ctx->cnt_pair_launches;
-          ctx->last_chase_ctl = d_ctl;
-          ctx->chase_ctl_xcds = nxcd;
-          chased = true;
-        }
-      }
-    }
-    if (!chased) ++ctx->cnt_stepwise_chases;
-    static const int env_streams = [] { const char* e = getenv("SPRINGCRAFT_BULGE_STREAMS"); return e ? atoi(e) : 0; }();
-    // (three parts from 48 matrices on: 477 -> 431 ms at 64; four and more exceed the ~11 us per launch one host thread
-    // needs -- the stage then takes 48 k launches x 11.4 us --, and replaying the launches as a captured hipGraph is slower
-    // still: 569 ms with three parts)
-    const int nparts = std::max(1, std::min(env_streams > 0 ? env_streams : (batch >= 48 ? 3 : (batch >= 16 ? 2 : 1)),
-                                            std::min(batch, 8)));
-    if (!chased) t_bulge.start();
-    if (chased) {
-    } else if (nparts > 1) {
-      SC_TRY(sc_aux_stream(ctx));            // (its fork event)
-      SC_TRY(sc_side_streams(ctx, nparts - 1));
-      SC_HIP(ctx, hipEventRecord(ctx->aux_fork, st));
-      for (int p = 1; p < nparts; ++p) SC_HIP(ctx, hipStreamWaitEvent(ctx->side_streams[p - 1], ctx->aux_fork, 0));
-      // launches go out in bursts of 32 wavefronts per stream rather than alternating streams launch by launch: the host
-      // needs ~11-13 us per launch and three parts x 12 k launches are close to the stage's own time (451 -> 434 ms with
-      // bursts of 16; round 3, same-box A/B on two boxes: 8 / 16 / 32 / 64 -> 465 / 464 / 421 / 463 and 437-467 / 430-434)
-      static const int burst = [] { const char* e = getenv("SPRINGCRAFT_BULGE_BURST"); return e ? std::max(1, atoi(e)) : 32; }();
-      for (int t0 = 0; t0 <= t_max; t0 += burst)
-        for (int p = 0; p < nparts; ++p) {
-          const int lo = (int)((long long)batch * p / nparts), hi = (int)((long long)batch * (p + 1) / nparts);
-          for (int t = t0; t <= std::min(t_max, t0 + burst - 1); ++t)
-            hipLaunchKernelGGL(k_bulge_step, dim3((unsigned)gx, (unsigned)(hi - lo)), dim3(256), 0,
-                               p == 0 ? st : ctx->side_streams[p - 1], d_sb_ws + (size_t)lo * SL.slab, SL, t);
-        }
-      for (int p = 1; p < nparts; ++p) {
-        SC_HIP(ctx, hipEventRecord(ctx->side_joins[p - 1], ctx->side_streams[p - 1]));
-        SC_HIP(ctx, hipStreamWaitEvent(st, ctx->side_joins[p - 1], 0));
-      }
-    } else {
-      for (int t = 0; t <= t_max; ++t)
-        hipLaunchKernelGGL(k_bulge_step, dim3((unsigned)gx, (unsigned)batch), dim3(256), 0, st, d_sb_ws, SL, t);
-    }
-    if (!chased) t_bulge.stop();
-  }
-  hipLaunchKernelGGL(k_band_to_tri, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, st, d_sb_ws, SL,
-                     d_tri_ws, TL);
-  SC_HIP(ctx, hipGetLastError());
+  SC_TRY(sb_stage2(ctx, d_a, stride_a, n, batch, d_tri_ws, TL, d_sb_ws, SL, d_band_copy, timers));
   if (prof) {
     SC_HIP(ctx, hipEventRecord(ev[2], st));
     SC_HIP(ctx, hipEventSynchronize(ev[2]));
     SC_HIP(ctx, hipEventElapsedTime(ms_stage1, ev[0], ev[1]));
     SC_HIP(ctx, hipEventElapsedTime(ms_stage2, ev[1], ev[2]));
   }
-  t_qr.finish(); t_symm.finish(); t_syr2k.finish(); t_bulge.finish();
+  timers.finish();
   return SC_OK;
 }
 
@@ -4687,11 +3938,8 @@ int bt2_batched(sc_ctx* ctx, int n, int batch, double* d_sb_ws, const SbLayout& 
     for (auto& e : ev) SC_HIP(ctx, hipEventCreate(&e));
     SC_HIP(ctx, hipEventRecord(ev[0], st));
   }
-  // few columns (partial spectrum): one launch per wavefront of independent diamonds, see k_bt2_wave
-  static const int env_wave = [] { const char* e = getenv("SPRINGCRAFT_BT2_WAVE"); return e ? atoi(e) : -1; }();
-  const long long col_wgs = (long long)((ncols + 63) / 64) * batch;
-  const bool wave_path = env_wave >= 0 ? env_wave != 0 : col_wgs <= 16;
-  if (wave_path) {
+  const sc_host::Bt2Plan P = sc_host::bt2_plan(sc_host::two_stage_env(), n, batch, ncols, ctx->num_cus);
+  if (P.wave) {
     int nk0 = 0;
     {
       const std::vector<int> doff = dia_offsets(n);
@@ -4704,25 +3952,6 @@ int bt2_batched(sc_ctx* ctx, int n, int batch, double* d_sb_ws, const SbLayout& 
                          d_sb_ws, SL, d_dia_off, d_z, stride_z, ncols, t);
     }
   } else {
-    // the role-split form (k_bt2_role: 64 columns per workgroup, MFMA / fragment / window-row waves): SPRINGCRAFT_BT2_ROLE = 1
-    static const int env_role = [] { const char* e = getenv("SPRINGCRAFT_BT2_ROLE"); return e ? atoi(e) : 0; }();
-    if (env_role != 0 && (n & 1) == 0 && batch >= 8 && n >= 256) {
-      // (per device, with the answer checked: sc_raise_dyn_lds)
-      const bool role_attr = sc_raise_dyn_lds(reinterpret_cast<const void*>(&k_bt2_role), kRoleLds);
-      if (role_attr) {
-        const int nchunk64 = (ncols + 63) / 64;
-        hipLaunchKernelGGL(k_bt2_role, dim3((unsigned)(8 * ((batch + 7) / 8) * nchunk64)), dim3(768), kRoleLds, st, d_sb_ws, SL,
-                           d_dia_off, d_z, stride_z, ncols, batch);
-        SC_HIP(ctx, hipGetLastError());
-        if (prof) {
-          SC_HIP(ctx, hipEventRecord(ev[1], st));
-          SC_HIP(ctx, hipEventSynchronize(ev[1]));
-          SC_HIP(ctx, hipEventElapsedTime(ms_fused, ev[0], ev[1]));
-        }
-        return SC_OK;
-      }
-    }
-    // 128 columns per workgroup (8 waves) when that still gives every CU a workgroup, else 64 (4 waves)
     // ring of three half-diamond fragment buffers + one 16 x 18 transposition tile per wave
     constexpr size_t lds = sizeof(double) * (3 * kHalfDoubles + 8 * 16 * 18);
     // (per device, with the answer checked -- ADVICE round 5: a process-wide flag left a context on a second GPU with a
@@ -4730,19 +3959,13 @@ int bt2_batched(sc_ctx* ctx, int n, int batch, double* d_sb_ws, const SbLayout& 
     if (!sc_raise_dyn_lds(reinterpret_cast<const void*>(&k_bt2_apply<8>), (int)lds) ||
         !sc_raise_dyn_lds(reinterpret_cast<const void*>(&k_bt2_apply<4>), (int)lds))
       return sc_set_error(ctx, SC_ERR_HIP, "k_bt2_apply: the device refuses %zu bytes of dynamic LDS", lds);
-    static const int force_nw = [] { const char* e = getenv("SPRINGCRAFT_BT2_NW"); return e ? atoi(e) : 0; }();
-    const int cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-    int nw = ((long long)((ncols + 127) / 128) * batch >= cus) ? 8 : 4;
-    if (force_nw == 4 || force_nw == 8) nw = force_nw;
-    const int nchunk = (ncols + 16 * nw - 1) / (16 * nw);
-    const bool xcd = batch >= 8;
-    const dim3 grid = xcd ? dim3((unsigned)(8 * ((batch + 7) / 8) * nchunk)) : dim3((unsigned)nchunk, (unsigned)batch);
-    if (nw == 8)
+    const dim3 grid(P.grid_x, P.grid_y);
+    if (P.nw == 8)
       hipLaunchKernelGGL(k_bt2_apply<8>, grid, dim3(512), lds, st, d_sb_ws, SL, d_dia_off, d_z, stride_z, ncols, batch,
-                         xcd ? 1 : 0);
+                         P.xcd ? 1 : 0);
     else
       hipLaunchKernelGGL(k_bt2_apply<4>, grid, dim3(256), lds, st, d_sb_ws, SL, d_dia_off, d_z, stride_z, ncols, batch,
-                         xcd ? 1 : 0);
+                         P.xcd ? 1 : 0);
   }
   SC_HIP(ctx, hipGetLastError());
   if (prof) {

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "host_logic.h"
+#include "twostage_policy.h"
 
 #define CHECK(cond) do { if (!(cond)) { std::fprintf(stderr, "CHECK failed: %s (line %d)\n", #cond, __LINE__); std::exit(1); } } while (0)
 
@@ -148,6 +149,110 @@ int main() {
       const int rows = (S.m - 1) / S.P + 1;
       CHECK(S.off % 64 == 0 && S.off + S.m == n && S.m <= 3072 && (1 << S.logP) == S.P && S.P <= 256);
       CHECK(rows <= (S.reg ? 12 : 8) && 256 * S.Q >= S.m && S.lds_bytes <= 160 * 1024);
+    }
+  }
+  // ---- the two-stage policy (csrc/twostage_policy.h): the decisions its comments document as measured, on a device of
+  // 256 CUs / 8 XCDs with the default environment (a default-constructed TwoStageEnv: the process environment is not read)
+  {
+    using namespace sc_host;
+    const TwoStageEnv E;
+    auto form = [&](int batch, int n) { return chase_form_for(E, n, batch, 8, 256, true, -1, -1, 1); };
+    CHECK(form(16, 6000) == ChaseForm::Sweep && form(32, 3000) == ChaseForm::Sweep);
+    CHECK(form(64, 3000) == ChaseForm::Pair && form(32, 6000) == ChaseForm::Pair && form(64, 6000) == ChaseForm::Pair);
+    CHECK(form(512, 1026) == ChaseForm::Stepwise);                                  // 64 matrices per XCD > 32 CUs
+    CHECK(form(1, 24000) == ChaseForm::Spread && form(1, 6000) == ChaseForm::Spread);
+    CHECK(form(1, 3000) == ChaseForm::Sweep);
+    CHECK(form(96, 6000) == ChaseForm::Pair && form(256, 3000) == ChaseForm::Pair);   // work 4500, 6000
+    CHECK(form(257, 3000) != ChaseForm::Pair);
+    CHECK(chase_form_for(E, 6000, 64, 8, 256, /*pair_attr=*/false, -1, -1, 1) != ChaseForm::Pair);   // LDS refused
+    CHECK(chase_form_for(E, 3000, 32, 8, 256, true, -1, -1, /*chase_ok=*/0) == ChaseForm::Stepwise);   // after a time-out
+    {
+      // 64 x 6000, two pair workgroups per CU: 8 matrices per XCD share its 64 slots; 95 tasks per sweep keep 33 pairs busy
+      const ChaseLaunch L = chase_launch(E, ChaseForm::Pair, 6000, 64, 8, 256, 2);
+      CHECK(L.nxcd == 8 && L.W == 8 && L.grid == 8 * 64 && L.early_bytes == 0);
+      const ChaseLaunch S = chase_launch(E, ChaseForm::Spread, 24000, 1, 8, 256, 2);
+      CHECK(S.nxcd == 1 && S.W == chase_len(24000, 0) / 2 + 1 && S.grid == S.W && S.early_bytes == (size_t)24000 * 8 * 16);
+      CHECK(chase_launch(E, ChaseForm::Sweep, 3000, 32, 8, 256, 0).W == 0);           // occupancy query failed: no launch
+    }
+    // parts of the batch
+    CHECK(stage1_parts(E, 31, false) == 1 && stage1_parts(E, 32, false) == 2 && stage1_parts(E, 32, true) == 1);
+    {
+      TwoStageEnv E3;
+      E3.stage1_streams = 3;
+      CHECK(stage1_parts(E3, 2, false) == 2 && stage1_parts(E3, 64, true) == 3);
+    }
+    CHECK(bulge_stream_parts(E, 15) == 1 && bulge_stream_parts(E, 16) == 2 && bulge_stream_parts(E, 48) == 3);
+    // panel pairs: while the trailing matrix behind the second panel has >= 256 rows
+    {
+      const std::vector<int> r = panel_roles(E, 6000);
+      CHECK((int)r.size() == panel_count(6000) && r.size() == 93 && r[0] == 1 && r[1] == 2 && r[86] == 1 && r[87] == 2 && r[88] == 0 && r[92] == 0);   // 6000 - 90 * 64 = 240 < 256
+      TwoStageEnv E1;
+      E1.panel_pairs = false;
+      for (int x : panel_roles(E1, 6000)) CHECK(x == 0);
+      CHECK(panel_roles(E, 65).empty() && panel_roles(E, 3).empty());
+    }
+    // panel QR form by the rows m of a full-width panel, coop granted, whole batch on one stream: budget 192 workgroups
+    {
+      auto kind = [&](const CoopPlan& C, bool recs, int m, int nb) { return panel_qr_form(E, C, recs, m, nb, true); };
+      const CoopPlan C4 = coop_plan(E, 6145 + 64, 4, 256, false, -1, 1);
+      CHECK(C4.ask && C4.budget == 192 && C4.min_many == 6145 && C4.gmax == 25 && C4.nb_max == 4);
+      PanelQrForm F = kind(C4, true, 4096, 4);
+      CHECK(F.kind == PanelQr::Wg1024 && F.ru == 4 && F.cu == 2);
+      F = kind(C4, true, 3072, 4);
+      CHECK(F.kind == PanelQr::Wg1024 && F.ru == 3 && F.cu == 4);
+      F = kind(C4, true, 4097, 4);
+      CHECK(F.kind == PanelQr::Wg512 && F.ru == 10 && F.cu == 1);
+      F = kind(C4, true, 5121, 4);
+      CHECK(F.kind == PanelQr::Wg512 && F.ru == 12 && F.cu == 1);
+      F = kind(C4, true, 6145, 4);
+      CHECK(F.kind == PanelQr::Coop && F.coop_g == 25);
+      CHECK(panel_qr_form(E, C4, true, 6145, 4, /*main_stream=*/false).kind == PanelQr::Blocked);   // a side stream never
+      const CoopPlan C1 = coop_plan(E, 6145 + 64, 1, 256, false, -1, 1);
+      CHECK(C1.ask && C1.min_few == 300);
+      F = kind(C1, true, 299, 1);
+      CHECK(F.kind == PanelQr::Wg1024 && F.ru == 1 && F.cu == 8);
+      CHECK(kind(C1, true, 300, 1).kind == PanelQr::Coop && kind(C1, true, 4096, 1).kind == PanelQr::Coop);
+      CHECK(kind(C1, false, 4097, 1).kind == PanelQr::Blocked && kind(C1, false, 4096, 1).kind == PanelQr::Wg1024);
+      CHECK(kind(C1, false, 64, 1).kind == PanelQr::Unblocked);                       // 63 reflectors: not a full panel
+      TwoStageEnv Eu;
+      Eu.qr_blocked = false;
+      CHECK(panel_qr_form(Eu, C1, false, 4097, 1, true).kind == PanelQr::Unblocked);
+      // two stage-1 parts (32 matrices, unprofiled): never coop; profiled, the batch is on one stream again
+      CHECK(!coop_plan(E, 6145 + 64, 32, 256, false, -1, 1).ask && coop_plan(E, 6145 + 64, 32, 256, true, -1, 1).ask);
+      CHECK(!coop_plan(E, 6145 + 64, 1, 256, false, /*coop_min_rows=*/0, 1).ask);   // switched off per context
+      CHECK(!coop_plan(E, 6145 + 64, 1, 256, false, -1, /*coop_ok=*/0).ask);        // after a time-out
+      CHECK(!coop_plan(E, 363, 1, 256, false, -1, 1).ask && coop_plan(E, 364, 1, 256, false, -1, 1).ask);   // 300 rows
+    }
+    // stage-2 back-transformation
+    CHECK(bt2_plan(E, 6000, 1, 20, 256).wave && bt2_plan(E, 6000, 16, 64, 256).wave && !bt2_plan(E, 6000, 17, 64, 256).wave);
+    CHECK(bt2_plan(E, 6000, 64, 6000, 256).nw == 8 && bt2_plan(E, 3000, 8, 3000, 256).nw == 4);
+    CHECK(bt2_plan(E, 16384, 2, 16384, 256).nw == 8 && bt2_plan(E, 16384, 2, 16383, 256).nw == 8 && bt2_plan(E, 16384, 2, 16256, 256).nw == 4);
+    {
+      const Bt2Plan P = bt2_plan(E, 6000, 64, 6000, 256);
+      CHECK(P.xcd && P.nchunk == 47 && P.grid_x == 64u * 47u && P.grid_y == 1u);
+      const Bt2Plan Q = bt2_plan(E, 6000, 4, 6000, 256);
+      CHECK(!Q.xcd && Q.nw == 4 && Q.nchunk == 94 && Q.grid_x == 94u && Q.grid_y == 4u);
+    }
+    // K slices of the SYMM: k_symm3 path (even n >= 512) ...
+    CHECK(symm3_for(E, 24000) && !symm3_for(E, 24001) && !symm3_for(E, 510));
+    CHECK(symm_split_for(E, 24000, 1) == 9);                                      // ceil(1536 / 188)
+    CHECK(symm_split_for(E, 6000, 17) == 1 && symm_split_for(E, 6000, 16) == 3);  // 799 items; 752: ceil(1536 / 752)
+    CHECK(symm_split_for(E, 6000, 32) == 3 && symm_split_for(E, 6000, 34) == 1);  // half the batch per launch from 32 on
+    CHECK(symm_split_for(E, 512, 1) == 16);
+    // ... and the odd-order path: 4 -> 5, six and more -> 9
+    CHECK(symm_split_for(E, 6001, 6) == 5);     // 564 tiles
+    CHECK(symm_split_for(E, 24001, 1) == 9);    // 376 tiles
+    CHECK(symm_split_for(E, 4481, 10) == 3);    // 710 tiles
+    CHECK(symm_split_for(E, 6001, 11) == 1 && symm_split_for(E, 2047, 1) == 1);   // >= 1024 tiles; n < 2048
+    {
+      TwoStageEnv Es;
+      Es.symm_split = 40;
+      CHECK(symm_split_for(Es, 6000, 1) == 16);
+    }
+    // the environment is read in one place; unset, it is the default-constructed struct
+    if (!getenv("SPRINGCRAFT_STAGE1_STREAMS") && !getenv("SPRINGCRAFT_BULGE_PAIR")) {
+      const TwoStageEnv R = read_two_stage_env();
+      CHECK(R.stage1_streams == 0 && R.bulge_pair == -1 && R.bulge_pair_max == 6000 && R.bulge_burst >= 1);
     }
   }
   std::puts("host logic ok");

@@ -27,5 +27,4 @@ for it in range(K):
     buf = (C.c_ulonglong * 2)()
     rc = L.sc_dbg_bt2_clock(buf)
     cyc, ticks = buf[0], buf[1]
-    print(f"solve {it}: rc {rc}  {cyc} shader cycles in {ticks / 100.0:.0f} us  ->  {cyc / max(ticks, 1) * 100.0:.0f} MHz "
-          f"(ROLE={os.environ.get('SPRINGCRAFT_BT2_ROLE', '0')})", flush=True)
+    print(f"solve {it}: rc {rc}  {cyc} shader cycles in {ticks / 100.0:.0f} us  ->  {cyc / max(ticks, 1) * 100.0:.0f} MHz", flush=True)

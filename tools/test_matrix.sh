@@ -7,7 +7,14 @@ HALF=${1:-0}
 PARTS=${2:-2}
 K=0
 # (a failing row stays in the output with the names of the tests that failed: -rf prints them above the summary line)
-run() { K=$((K+1)); if [ $HALF -ne 0 ] && [ $((K % PARTS)) -ne $((HALF % PARTS)) ]; then return; fi; echo "== $*"; env "$@" timeout -k 10 600 python -m pytest $T -x -q -rf 2>&1 | grep -E "^(FAILED|ERROR)|passed|failed|error" | tail -4; }
+# (a row that timed out, aborted or faulted ends the script: nothing more is started on a card that has just hung or faulted)
+run() {
+  K=$((K+1)); if [ $HALF -ne 0 ] && [ $((K % PARTS)) -ne $((HALF % PARTS)) ]; then return; fi
+  echo "== $*"
+  env "$@" timeout -k 10 600 python -m pytest $T -x -q -rf 2>&1 | grep -E "^(FAILED|ERROR)|passed|failed|error" | tail -4
+  local rc=${PIPESTATUS[0]}
+  case $rc in 124|134|137|139) echo "== row ended with status $rc: stopping"; exit $rc;; esac
+}
 run SPRINGCRAFT_BULGE_PERSISTENT=0 SPRINGCRAFT_BULGE_STREAMS=1 SPRINGCRAFT_STAGE1_STREAMS=1
 run SPRINGCRAFT_BULGE_PERSISTENT=0 SPRINGCRAFT_BULGE_STREAMS=3 SPRINGCRAFT_STAGE1_STREAMS=3
 run SPRINGCRAFT_BULGE_PERSISTENT=2
@@ -33,13 +40,10 @@ run SPRINGCRAFT_BULGE_NO_EARLY=1 SPRINGCRAFT_BULGE_PAIR=0
 run SPRINGCRAFT_BULGE_PERSISTENT=2 SPRINGCRAFT_BULGE_PAIR=0 SPRINGCRAFT_BULGE_NO_EARLY=1
 run SPRINGCRAFT_QR_COOP=0
 run SPRINGCRAFT_QR_COOP_MIN=128
-run SPRINGCRAFT_BT2_ROLE=1
 run SPRINGCRAFT_SYMM3=0
 run SPRINGCRAFT_SYMM3=2 SPRINGCRAFT_SYMM_SPLIT=3
 run SPRINGCRAFT_SYMM3_WGS=224 SPRINGCRAFT_GEMM3=2 SPRINGCRAFT_GEMM3_LOWER=1 SPRINGCRAFT_GEMM3_LOWER_WGS=224
 run SPRINGCRAFT_GEMM3_LOWER=0
-run SPRINGCRAFT_BULGE_PERSISTENT=2 SPRINGCRAFT_BULGE_PAIR=2 SPRINGCRAFT_PAIR_LOADER=1
-run SPRINGCRAFT_BULGE_PERSISTENT=2 SPRINGCRAFT_BULGE_PAIR=2 SPRINGCRAFT_PAIR_EARLY=1
 run SPRINGCRAFT_BULGE_SPREAD=1
 run SPRINGCRAFT_BULGE_SPREAD=0
 run SPRINGCRAFT_RESIDENT=0
