@@ -6,6 +6,10 @@ Builds libspringcraft_hip.so in-tree for gfx950 with hipcc (cross-compiles witho
 One object per .hip source (compiled in parallel, rebuilt only when the source or a header
 changed), linked into springcraft_amd/libspringcraft_hip.so.  assembly.hip is compiled with
 -ffp-contract=off (bit-exact contact predicate, see the file header).
+
+A variant library (diagnostic stamps, an experiment's macro) is built the same way next to the product library:
+SC_LIB_SUFFIX=_stamps SC_EXTRA_HIPCC_FLAGS=-DPAIR_STAMPS gives obj_stamps/ and libspringcraft_hip_stamps.so
+(tools/build_stamps_lib.sh); select it with SPRINGCRAFT_HIP_LIB.
 """
 import os
 import subprocess
@@ -16,8 +20,9 @@ from os.path import abspath, dirname, exists, getmtime, join
 HERE = dirname(abspath(__file__))
 PKG = dirname(HERE)
 REPO = dirname(PKG)
-OBJ = join(HERE, "obj")
-LIB = join(PKG, "libspringcraft_hip.so")
+SUFFIX = os.environ.get("SC_LIB_SUFFIX", "")
+OBJ = join(HERE, "obj" + SUFFIX)
+LIB = join(PKG, "libspringcraft_hip" + SUFFIX + ".so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 COMMON = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Werror=return-type",
@@ -26,6 +31,9 @@ PER_FILE = {
     "assembly.hip": ["-ffp-contract=off"],
     # k_bt2_apply's diamond loop is 80 fully unrolled steps per half-diamond (every register index must be a constant):
     # above LLVM's default budget for `#pragma unroll`, below which the accumulators would live in scratch memory
+    "bt2.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
+    # (bt2.hip came out of this file, which was built with the flag: without it k_panel_wg<10, 1, 512> and <12, 1, 512> come
+    # out as other code, so it stays; the other kernels of the file are identical either way)
     "twostage.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
 }
 

@@ -1,7 +1,7 @@
 """
 The partial spectrum (``subset_by_index``; BASELINE config 5) across batches, clusters and the boundaries of its paths.
 
-After the tridiagonalisation the range solve runs kernels of its own (stein.hip, twostage.hip): k_sturm_range
+After the tridiagonalisation the range solve runs kernels of its own (stein.hip, bt2.hip): k_sturm_range
 (multisection on the Sturm count), k_stein (inverse iteration, 4 steps from a hashed start vector, members of a run of
 near-equal eigenvalues shifted apart by 10 run eps |T|), CholQR2 (k_chol_inv and two grouped GEMMs, twice) and the
 back-transformation of m columns only (k_bt2_wave when ceil(m / 64) batch <= 16, else k_bt2_apply; then

@@ -1,6 +1,6 @@
 """
 GPU parity tests of the two-stage tridiagonalisation path of the eigensolver (csrc/twostage.hip: band reduction,
-bulge chasing, diamond back-transformation), forced on with ``Context.set_two_stage(True)``; the same gates as
+bulge chasing; csrc/bt2.hip: diamond back-transformation), forced on with ``Context.set_two_stage(True)``; the same gates as
 tests/test_eigh_gpu.py and direct comparison with the one-stage path.
 """
 import numpy as np

@@ -1,13 +1,6 @@
 #!/bin/bash
-# Diagnostic build of the library with the pair chase's per-phase stamps (-DPAIR_STAMPS) next to the product library:
-#   bash tools/build_stamps_lib.sh   ->  springcraft_amd/libspringcraft_hip_stamps.so   (git-ignored; select it with
-#   SPRINGCRAFT_HIP_LIB=...; tools/pair_stamps.py and tools/r04_final.sh b use it)
-set -eu
-cd ${GRAFT_REPO_ROOT:-$(dirname $0)/..}
-python springcraft_amd/csrc/build.py > /dev/null
-HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
-$HIPCC -c springcraft_amd/csrc/twostage.hip -o /tmp/twostage_stamps.o --offload-arch=gfx950 -O3 -fPIC -std=c++17 -Wall \
-  -Wno-unused-function -I include -mllvm -pragma-unroll-threshold=1000000 -DPAIR_STAMPS
-$HIPCC -shared -fPIC --offload-arch=gfx950 -o springcraft_amd/libspringcraft_hip_stamps.so /tmp/twostage_stamps.o \
-  $(ls springcraft_amd/csrc/obj/*.o | grep -v twostage.o)
-echo springcraft_amd/libspringcraft_hip_stamps.so
+# Diagnostic build of the whole library next to the product library, by the product's own build (csrc/build.py):
+#   bash tools/build_stamps_lib.sh [flags]  ->  springcraft_amd/libspringcraft_hip_stamps.so   (git-ignored; select it with
+#   SPRINGCRAFT_HIP_LIB=...).  Flags: -DPAIR_STAMPS (the default; tools/pair_stamps.py), -DCHASE_STAMPS (chase_stamps.py),
+#   -DBULGE_STAMPS (bulge_stamps.py), -DBT2_STAMPS (bt2_stamps.py), -DBT2_CLOCK (bt2_clock.py), -DBT2_TRACE (bt2_trace.py)
+SC_LIB_SUFFIX=_stamps SC_EXTRA_HIPCC_FLAGS="${*:--DPAIR_STAMPS}" python "$(dirname "$0")/../springcraft_amd/csrc/build.py" --force

@@ -1,5 +1,5 @@
 """
-NumPy model of the stage-2 back-transformation kernels (csrc/twostage.hip: k_dia_tfactor2, k_bt2_apply): the
+NumPy model of the stage-2 back-transformation kernels (csrc/bt2.hip: k_dia_tfactor2, k_bt2_apply): the
 fragment layout, the k-step lists that skip structural zeros, and the T = U^-1 formulation, checked against applying
 the 64 Householder reflectors of a diamond one by one.  Pure index arithmetic: it is the specification the HIP
 kernels are written against (the MFMA lane maps are restated by `mfma` below).
@@ -39,7 +39,7 @@ def steps():
     """Issue order of one diamond = order of the fragments in memory: for st = 3, 2, 1, 0:
     20 x ("p1", st, rt, r) with rt = st + j // 4, r = j % 4          (W = V_st^T Z; B operand = Z tile rt register r)
     20 x ("p2", st, rt, r) with r = j // 5, rt = st + j % 5          (Z -= (V_st T_st) W; B operand = W register r).
-    (In device memory the 64 lane values of fragments 2 p and 2 p + 1 are interleaved -- frag_off() in twostage.hip --
+    (In device memory the 64 lane values of fragments 2 p and 2 p + 1 are interleaved -- frag_off() in bt2.hip --
     so that a lane fetches both with one 16-byte LDS read; the order of the fragments is the one modelled here.)"""
     out = []
     for st in (3, 2, 1, 0):
