@@ -92,7 +92,7 @@ int sc_dbg_bulge_stamps(unsigned long long* out6);
 int sc_dbg_pair_stamps(unsigned long long* out48);
 /* The same for the persistent chase with one sweep per workgroup (k_bulge_chase; library built with -DCHASE_STAMPS, else
  * returns 1): out16[1..11] = cycles of all waves between eleven points of a task, summed over all tasks since the last call
- * (the segments are listed at the macro in twostage.hip), [15] = waves x tasks.  tools/chase_stamps.py */
+ * (the segments are listed at the macro in sb2st.hip), [15] = waves x tasks.  tools/chase_stamps.py */
 int sc_dbg_chase_stamps(unsigned long long* out16);
 
 /* Persistent bulge chase of this context: mode -1 = SPRINGCRAFT_BULGE_PERSISTENT or the size rule (default), 0 never,

@@ -22,31 +22,29 @@ int sc_set_error(sc_ctx* ctx, int code, const char* fmt, ...) {
   return code;
 }
 
-int sc_reserve_ws(sc_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->ws_bytes) return SC_OK;
-  if (ctx->ws) {
+// Grow-only cached device buffers of the context: nothing happens while the buffer is large enough; else the context's
+// stream is drained, the buffer freed and a larger one allocated.
+static int reserve(sc_ctx* ctx, void*& buf, size_t& have, size_t bytes, bool collect_events = false) {
+  if (bytes <= have) return SC_OK;
+  if (buf) {
     SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SC_HIP(ctx, hipFree(ctx->ws));
-    ctx->ws = nullptr;
-    ctx->ws_bytes = 0;
+    if (collect_events) SC_TRY(sc_collect_events(ctx));
+    SC_HIP(ctx, hipFree(buf));
+    buf = nullptr;
+    have = 0;
   }
-  SC_HIP(ctx, hipMalloc(&ctx->ws, bytes));
-  ctx->ws_bytes = bytes;
+  SC_HIP(ctx, hipMalloc(&buf, bytes));
+  have = bytes;
   return SC_OK;
 }
 
-int sc_reserve_scratch(sc_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->scratch_bytes) return SC_OK;
-  if (ctx->scratch) {
-    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SC_HIP(ctx, hipFree(ctx->scratch));
-    ctx->scratch = nullptr;
-    ctx->scratch_bytes = 0;
-  }
-  SC_HIP(ctx, hipMalloc(&ctx->scratch, bytes));
-  ctx->scratch_bytes = bytes;
-  return SC_OK;
-}
+int sc_reserve_ws(sc_ctx* ctx, size_t bytes) { return reserve(ctx, ctx->ws, ctx->ws_bytes, bytes); }
+int sc_reserve_scratch(sc_ctx* ctx, size_t bytes) { return reserve(ctx, ctx->scratch, ctx->scratch_bytes, bytes); }
+int sc_reserve_pinv(sc_ctx* ctx, size_t bytes) { return reserve(ctx, ctx->pinv_ws, ctx->pinv_ws_bytes, bytes); }
+int sc_reserve_win(sc_ctx* ctx, size_t bytes) { return reserve(ctx, ctx->win_ws, ctx->win_ws_bytes, bytes); }
+int sc_reserve_modes(sc_ctx* ctx, size_t bytes) { return reserve(ctx, ctx->modes_ws, ctx->modes_ws_bytes, bytes); }
+// (events are collected before the free: the last chase's control block lives in the buffer that goes away)
+int sc_reserve_dc_aux(sc_ctx* ctx, size_t bytes) { return reserve(ctx, ctx->dc_aux, ctx->dc_aux_bytes, bytes, true); }
 
 int sc_stage_upload(sc_ctx* ctx, void* d_dst, const void* h_src, size_t bytes) {
   if (bytes == 0) return SC_OK;
@@ -128,59 +126,6 @@ int sc_deferred_status(sc_ctx* ctx) {
     return sc_set_error(ctx, SC_ERR_NOCONV, "Eigenvalues did not converge: matrix %llu of the batch contains NaN or Inf",
                         h[0] - 1ull);
   return sc_set_error(ctx, SC_ERR_NOCONV, "tridiagonal QL iteration did not converge");
-}
-
-int sc_reserve_pinv(sc_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->pinv_ws_bytes) return SC_OK;
-  if (ctx->pinv_ws) {
-    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SC_HIP(ctx, hipFree(ctx->pinv_ws));
-    ctx->pinv_ws = nullptr;
-    ctx->pinv_ws_bytes = 0;
-  }
-  SC_HIP(ctx, hipMalloc(&ctx->pinv_ws, bytes));
-  ctx->pinv_ws_bytes = bytes;
-  return SC_OK;
-}
-
-int sc_reserve_win(sc_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->win_ws_bytes) return SC_OK;
-  if (ctx->win_ws) {
-    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SC_HIP(ctx, hipFree(ctx->win_ws));
-    ctx->win_ws = nullptr;
-    ctx->win_ws_bytes = 0;
-  }
-  SC_HIP(ctx, hipMalloc(&ctx->win_ws, bytes));
-  ctx->win_ws_bytes = bytes;
-  return SC_OK;
-}
-
-int sc_reserve_modes(sc_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->modes_ws_bytes) return SC_OK;
-  if (ctx->modes_ws) {
-    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SC_HIP(ctx, hipFree(ctx->modes_ws));
-    ctx->modes_ws = nullptr;
-    ctx->modes_ws_bytes = 0;
-  }
-  SC_HIP(ctx, hipMalloc(&ctx->modes_ws, bytes));
-  ctx->modes_ws_bytes = bytes;
-  return SC_OK;
-}
-
-int sc_reserve_dc_aux(sc_ctx* ctx, size_t bytes) {
-  if (bytes <= ctx->dc_aux_bytes) return SC_OK;
-  if (ctx->dc_aux) {
-    SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SC_TRY(sc_collect_events(ctx));   // (the last chase's control block lives in the buffer that goes away)
-    SC_HIP(ctx, hipFree(ctx->dc_aux));
-    ctx->dc_aux = nullptr;
-    ctx->dc_aux_bytes = 0;
-  }
-  SC_HIP(ctx, hipMalloc(&ctx->dc_aux, bytes));
-  ctx->dc_aux_bytes = bytes;
-  return SC_OK;
 }
 
 int sc_aux_stream(sc_ctx* ctx) {

@@ -32,9 +32,9 @@ PER_FILE = {
     # k_bt2_apply's diamond loop is 80 fully unrolled steps per half-diamond (every register index must be a constant):
     # above LLVM's default budget for `#pragma unroll`, below which the accumulators would live in scratch memory
     "bt2.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
-    # (bt2.hip came out of this file, which was built with the flag: without it k_panel_wg<10, 1, 512> and <12, 1, 512> come
-    # out as other code, so it stays; the other kernels of the file are identical either way)
-    "twostage.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
+    # (stage 1 was built with the flag while it shared a file with bt2: without it k_panel_wg<10, 1, 512> and <12, 1, 512>
+    # come out as other code, so it stays; the other kernels of the file are identical either way)
+    "sy2sb.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],
 }
 
 

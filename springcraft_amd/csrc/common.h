@@ -70,7 +70,7 @@ struct sc_ctx {
   unsigned long long* d_status = nullptr;
 
   int two_stage = -1;   // eigensolver path: -1 automatic, 0 one-stage, 1 two-stage tridiagonalisation
-  // persistent bulge chase (twostage.hip): chase_ok = 0 once a chase of this context ran into its time-out (never
+  // persistent bulge chase (sb2st.hip): chase_ok = 0 once a chase of this context ran into its time-out (never
   // expected; the per-wavefront launches take over from then on); chase_mode / chase_give_up are set through the debug
   // entry sc_dbg_set_chase (-1: SPRINGCRAFT_BULGE_PERSISTENT or the size rule; 0 / 1 / 2 as that variable).
   int chase_ok = -1;
@@ -90,7 +90,7 @@ struct sc_ctx {
   long long cnt_symm3_launches = 0;
   bool gemm3_side_by_side = false;   // the caller runs parts of the batch on several streams (band reduction): see gemm3_would_take
   long long cnt_gemm3_launches = 0;
-  // k_panel_coop (twostage.hip): dynamic LDS attribute of this device (-1 not tried, 0 refused, 1 set); coop_ok = 0
+  // k_panel_coop (sy2sb.hip): dynamic LDS attribute of this device (-1 not tried, 0 refused, 1 set); coop_ok = 0
   // once a wait between its workgroups timed out (the context then keeps to the chunked panel launches)
   int coop_attr = -1, coop_ok = -1;
   int coop_min_rows = -1;   // debug entry sc_dbg_set_panel_coop: rows from which a panel takes it (0 never, -1 default rule)
@@ -188,13 +188,13 @@ int sc_set_error(sc_ctx* ctx, int code, const char* fmt, ...);
 
 // Grow-only cached allocations.
 int sc_reserve_ws(sc_ctx* ctx, size_t bytes);
-int sc_aux_stream(sc_ctx* ctx);   // creates aux_stream / aux_fork / aux_join if needed
-int sc_side_streams(sc_ctx* ctx, int count);   // makes sure side_streams / side_joins hold `count` entries
 int sc_reserve_scratch(sc_ctx* ctx, size_t bytes);
 int sc_reserve_dc_aux(sc_ctx* ctx, size_t bytes);
 int sc_reserve_pinv(sc_ctx* ctx, size_t bytes);
 int sc_reserve_win(sc_ctx* ctx, size_t bytes);
 int sc_reserve_modes(sc_ctx* ctx, size_t bytes);
+int sc_aux_stream(sc_ctx* ctx);   // creates aux_stream / aux_fork / aux_join if needed
+int sc_side_streams(sc_ctx* ctx, int count);   // makes sure side_streams / side_joins hold `count` entries
 // d_dst <- bytes at h_src, enqueued on ctx->stream; h_src may be released as soon as the call returns
 int sc_stage_upload(sc_ctx* ctx, void* d_dst, const void* h_src, size_t bytes);
 // end of a solve that used sc_stage_upload: the arena may be reused when everything enqueued so far has run
@@ -202,7 +202,7 @@ int sc_stage_end(sc_ctx* ctx);
 // after a synchronisation of ctx->stream: SC_ERR_NOCONV (and the flags cleared) if a solve since the last call met
 // non-finite input or a QL failure, else SC_OK
 constexpr int kSpStatusWords = 16;
-// ints of the persistent chase's control block (sc_ctx::d_chase_ctl; layout at k_bulge_chase in twostage.hip)
+// ints of the persistent chase's control block (sc_ctx::d_chase_ctl; layout at k_bulge_chase in sb2st.hip)
 constexpr int kChaseCtlInts = 32;
 int sc_deferred_status(sc_ctx* ctx);
 // adds the device-side event words to the context's counters (the context's stream must be idle)

@@ -51,7 +51,7 @@ size_t tri_slab_doubles(int n, TriLayout* out) {
   return (size_t)off;
 }
 
-// Two-stage tridiagonalisation (twostage.hip) instead of the one-stage panel algorithm.  The one-stage SYMV streams
+// Two-stage tridiagonalisation (twostage.hip and the files it names) instead of the one-stage panel algorithm.  The one-stage SYMV streams
 // 4/3 n^3 bytes per matrix and is bandwidth-bound as soon as a few matrices are in flight; the two-stage path does its
 // O(n^3) work in MFMA GEMMs but pays ~3 n short launches and twice the back-transformation flops.  Measured crossover
 // on MI355X: batch * n^2 above ~ max(1.7e7, 5e3 n) (round 4: max(2e7, 1e4 n), round 2: 5e7 + 6.7e3 n, round 1: 1.2e8;

@@ -109,7 +109,7 @@ int backtransform_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, i
                           const BtLayout& BL, double* d_z, long long stride_z, int ncols, double* d_vt,
                           GemmDesc* d_descs /* bt_desc_count(n, batch) records */, int off = 1, int phase = 0);
 
-// ---- two-stage tridiagonalisation (twostage.hip, bt2.hip) -------------------------------------------------------
+// ---- two-stage tridiagonalisation (twostage.hip, sy2sb.hip, sb2st.hip, bt2.hip) -------------------------------
 struct SbLayout {
   int n;
   long long slab;

@@ -1,5 +1,5 @@
 // k_symm3: X = A V for a symmetric A of which only the lower triangle is stored -- the SYMM of the band reduction
-// (twostage.hip, X = A22 V: 2/3 n^3 flops of the eigensolver) as ONE role-split persistent launch (round 6).
+// (sy2sb.hip, X = A22 V: 2/3 n^3 flops of the eigensolver) as ONE role-split persistent launch (round 6).
 //
 // Until round 5 the product ran as two triangular-operand launches of k_gemm2 (X1 = L V with the K range 0 .. row,
 // X2 = strict(L)^T V with the K range row .. m) whose tiles have K ranges between 0 and m: the lowest MFMA group of the

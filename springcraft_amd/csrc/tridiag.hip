@@ -590,7 +590,7 @@ __device__ __forceinline__ double res_dpp(double x) {
   const int hi = __builtin_amdgcn_update_dpp(0, (int)(unsigned)(b >> 32), CTRL, 0xf, 0xf, true);
   return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned long long)(unsigned)lo));
 }
-// eight sums over the 64 lanes at the cost of three (as twostage.hip's wave_reduce8): lane l < 8 returns the total of
+// eight sums over the 64 lanes at the cost of three (as sy2sb.hip's wave_reduce8): lane l < 8 returns the total of
 // v[res_reduce8_index(l)]
 __device__ __forceinline__ int res_reduce8_index(int lane) { return 4 * (lane & 1) + 2 * ((lane >> 1) & 1) + ((lane >> 2) & 1); }
 __device__ __forceinline__ double res_reduce8(const double (&v)[8]) {

@@ -1,5 +1,5 @@
-// What twostage.hip (stages 1 and 2, driver, slab layout) and bt2.hip (the Q2 back-transformation) share; everything
-// else is in its file.
+// What the files of the two-stage solver share -- twostage.hip (slab layout, driver), sy2sb.hip (stage 1), sb2st.hip
+// (stage 2), bt2.hip (the Q2 back-transformation): whatever more than one of them needs; everything else is in its file.
 #pragma once
 
 #include <algorithm>
@@ -8,7 +8,7 @@
 #include "eigh_internal.h"
 #include "twostage_policy.h"
 
-// (internal linkage: both files get their own copy of the constants and of the device helper, which is always inlined)
+// (internal linkage: every file gets its own copy of the constants and of the device helpers, which are always inlined)
 namespace {
 
 constexpr int kB = sc_host::kBand;  // band half-width = panel width = reflector length of stage 2
@@ -20,6 +20,50 @@ constexpr int kDiaSize = kDiaLd * kG;
 constexpr int kMiniFrags = 40;                     // fragments per mini: 20 of V^T, 20 of -(V T)
 constexpr int kDiaFrags = 4 * kMiniFrags;          // 160 per diamond
 constexpr int kFragDoubles = kDiaFrags * 64;       // 10240 doubles = 80 KB
+
+constexpr int kLdab = 2 * kB;     // rows of the band storage: AB(i, j) = ab[(i - j) + j * kLdab]
+constexpr int kQrRows = 128;      // rows of the panel one k_panel_qr workgroup owns
+constexpr int kSmallSplit = 8;    // split-K of the V^T [X1|X2|V] product
+constexpr int kDescKinds = 9;     // GEMM records per panel and matrix (stage 1)
+#ifndef SC_QR_IB
+#define SC_QR_IB 8
+#endif
+constexpr int kIb = SC_QR_IB;     // inner block of the blocked panel QR (columns whose reflectors are applied to the rest at once)
+
+typedef int v4i __attribute__((ext_vector_type(4)));   // a 16-byte record (early hand-off of the chase, the cooperative panel)
+
+struct HH {
+  double beta, tau, scale;
+};
+
+// LAPACK dlarfg scalars: x = (alpha, tail), xn2 = ||tail||^2;  H x = beta e1,  v = (1, scale * tail)
+__device__ __forceinline__ HH householder(double alpha, double xn2) {
+  HH h;
+  // No reflection either when the column (pivot included) is below 1e-140: its squares are in the underflow range, where
+  // a norm is not a norm any more (LAPACK's dlarfg rescales there) and the reflector would come out non-orthogonal.  The
+  // input is scaled to [1e-100, 1e100] (matrix_scale_factor), so such a column is < 1e-40 of the matrix: the caller
+  // stores zeros for its tail, a backward error far below rounding.  Seen with exactly rank-deficient input such as
+  // ones(n, n), whose trailing matrices shrink by a factor eps per column.
+  if (xn2 == 0.0 || alpha * alpha + xn2 < 1e-280) {
+    h.beta = alpha; h.tau = 0.0; h.scale = 0.0;
+    return h;
+  }
+  h.beta = -copysign(sqrt(alpha * alpha + xn2), alpha);
+  h.tau = (h.beta - alpha) / h.beta;
+  h.scale = 1.0 / (alpha - h.beta);
+  return h;
+}
+
+// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory counter, i.e. waits for
+// the acknowledgement of every global store in flight (about 2 us under load) -- wasted when no thread of the workgroup
+// reads global data that another one wrote in the same kernel.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
 
 typedef double __attribute__((address_space(1)))* gdptr;          // global memory: global_load / global_store, never flat
 // a pointer every lane of the wave holds the same value of, told so to the compiler (scalar registers, and memory
@@ -41,3 +85,21 @@ inline std::vector<int> dia_offsets(int n) {
   for (int S = 0; S < ng; ++S) off[(size_t)S + 1] = off[(size_t)S] + (n - 1 - S * kG + kB - 1) / kB;
   return off;
 }
+
+// kernel-group timers of a profiled solve (the driver owns them: they are resolved when both stages have been enqueued)
+struct SbTimers {
+  PhaseTimer qr, symm, syr2k, bulge;
+  SbTimers(sc_ctx* ctx, hipStream_t st) : qr(ctx, "panel_qr", st), symm(ctx, "symm", st), syr2k(ctx, "syr2k", st), bulge(ctx, "bulge", st) {}
+  void finish() { qr.finish(); symm.finish(); syr2k.finish(); bulge.finish(); }
+};
+
+// The GEMM records of stage 1 in [panel][kind][batch] order (sy2sb.hip); the driver uploads them.
+std::vector<GemmDesc> sb_stage1_records(int n, int batch, const std::vector<int>& role, double* d_a, long long stride_a,
+                                        double* d_sb_ws, const SbLayout& SL);
+// Stage 1 on ctx->stream, the GEMM records of the solve uploaded: dense -> band (sy2sb.hip).
+int sb_stage1(sc_ctx* ctx, double* d_a, long long stride_a, int n, int batch, double* d_tri_ws, const TriLayout& TL,
+              double* d_sb_ws, const SbLayout& SL, const GemmDesc* d_descs, const std::vector<int>& role, bool prof,
+              SbTimers& timers);
+// Stage 2 on ctx->stream: band -> tridiagonal; d, e into the tri slab (sb2st.hip).
+int sb_stage2(sc_ctx* ctx, double* d_a, long long stride_a, int n, int batch, double* d_tri_ws, const TriLayout& TL,
+              double* d_sb_ws, const SbLayout& SL, double* d_band_copy, SbTimers& timers);

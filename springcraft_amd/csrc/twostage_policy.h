@@ -1,8 +1,9 @@
 // The policy of the two-stage tridiagonalisation: which kernel form a given (n, batch, device) gets.  Every rule is a
 // closed-form function of integers -- the environment (read once, TwoStageEnv), the context's overrides and what the
 // runtime answered (occupancy, granted attributes) are INPUTS.  No HIP, header-only, same rules as host_logic.h:
-// tests/host_sanitize/ compiles exactly this code with g++ -fsanitize=address,undefined.  twostage.hip and bt2.hip call
-// each function once per solve (or per panel) and launch what it says; the measurements that justify a rule stand beside it.
+// tests/host_sanitize/ compiles exactly this code with g++ -fsanitize=address,undefined.  sy2sb.hip, sb2st.hip, twostage.hip
+// and bt2.hip call each function once per solve (or per panel) and launch what it says; the measurements that justify a
+// rule stand beside it.
 #pragma once
 #include <algorithm>
 #include <cstddef>

@@ -1,5 +1,5 @@
 """
-The data flow of k_bulge_pair (twostage.hip: two consecutive sweeps of the bulge chase per workgroup, the second team taking
+The data flow of k_bulge_pair (sb2st.hip: two consecutive sweeps of the bulge chase per workgroup, the second team taking
 its blocks from the first team's LDS slots, shifted by one row and one column) as a NumPy model, checked on the CPU
 against the plain task-by-task chase -- including the give-up at any step with the write-back of the live slots and the
 take-over from the published counts.  The kernel's index arithmetic was derived from this model

@@ -276,7 +276,7 @@ def test_chase_counters_survive_the_d_and_c_above_7000():
     sat in.  One full-spectrum solve at n = 7001 on a fresh context: no time-out, no take-over, the wait triple -1, and
     the ticket counts of a one-matrix chase: all workgroups on one ticket slot (the spread form counts as one XCD; so does
     a device with one), 1 <= min <= max = total <= max(8, ceil((n - 1) / 64) / 2 + 1), the workgroups one matrix's chase
-    can use (twostage.hip, `useful`).  The same order without eigenvectors (no D&C) is the control: same grid.
+    can use (twostage_policy.h, `useful`).  The same order without eigenvectors (no D&C) is the control: same grid.
     """
     import ctypes as C
 

@@ -1,5 +1,5 @@
 """
-GPU parity tests of the two-stage tridiagonalisation path of the eigensolver (csrc/twostage.hip: band reduction,
+GPU parity tests of the two-stage tridiagonalisation path of the eigensolver (csrc/sy2sb.hip: band reduction; csrc/sb2st.hip:
 bulge chasing; csrc/bt2.hip: diamond back-transformation), forced on with ``Context.set_two_stage(True)``; the same gates as
 tests/test_eigh_gpu.py and direct comparison with the one-stage path.
 """

@@ -1,5 +1,5 @@
 """
-NumPy model of k_bulge_pair's data flow (twostage.hip): team A chases sweep sA = 2p with its blocks kept in a ring of
+NumPy model of k_bulge_pair's data flow (sb2st.hip): team A chases sweep sA = 2p with its blocks kept in a ring of
 three LDS slots, team B chases sweep sA + 1 two positions behind from the shifted slots and writes the band.  Checked
 against the plain task-by-task chase on the band storage (what k_bulge_step does).  CPU only; run it after changing the
 kernel's index arithmetic:   python tools/models/bulge_pair_model.py

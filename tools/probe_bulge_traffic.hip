@@ -1,6 +1,6 @@
 // How long does the memory traffic of the bulge chase take by itself?  (gfx950)
 //   hipcc --offload-arch=gfx950 -O3 tools/probe_bulge_traffic.hip -o /tmp/probe_bulge && /tmp/probe_bulge [n] [batch]
-// Same launch structure, workgroup shape and addresses as k_bulge_step (twostage.hip): launch t runs the tasks (s, k)
+// Same launch structure, workgroup shape and addresses as k_bulge_step (sb2st.hip): launch t runs the tasks (s, k)
 // with 2 s + k = t, one 256-thread workgroup each; a task reads its 64 x 64 off-diagonal block E and the lower triangle
 // of its diagonal block D from the band storage (128 x n doubles per matrix, column-major), and writes both back.  Here
 // NOTHING is computed in between (the values go through registers unchanged, kept alive by an add of a kernel argument
