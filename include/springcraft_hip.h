@@ -393,7 +393,7 @@ int sc_modes_prs(sc_modes* modes, double rcond, int norm, double* out);
 #define SC_SEL_PINV 2
 typedef struct sc_mode_selection {
   int32_t kind;
-  int32_t reserved;
+  int32_t reserved;      /* 0 for the sc_dev_* entries; sc_batch_plan_modes_*: first_row, see there */
   int64_t row0;          /* SC_SEL_FROM_ROW */
   const int32_t* d_rows; /* SC_SEL_ROWS: (n_rows,) device memory */
   int64_t n_rows;
@@ -417,6 +417,40 @@ int sc_dev_modes_dcc_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int6
  * nvec for SC_SEL_PINV); what: 0 = msf, 1 = dcc; budget_bytes as above. */
 int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
                                      int64_t budget_bytes);
+
+/* ---- partial spectrum and mode consumers of a ragged batch (sc_batch_plan) ---------------------------------------------
+ * The reference models one arbitrary structure per object (anm.py:62-63); a plan solves many in padded slots
+ * diag(M, D) whose pad eigenvalues lie above M's spectrum (see sc_batch_plan_create), so a slot's lowest eigenpairs are
+ * the structure's own.  The plan keeps one small device record per structure (own order dim * n_atoms, atom offset,
+ * square offset) that the entries below read; nothing is uploaded per call, all of them only enqueue.
+ *
+ * Eigenpairs il..iu of every slot, as sc_dev_eigh_range_f64 on (count, order, order): d_w (count, m), d_v NULL or
+ * (count, m, order), m = iu - il + 1.  0 <= il <= iu < dim * min(n_atoms), so that every row is a structure's mode and
+ * never a pad (SC_ERR_INDEX otherwise).  d_a is destroyed. */
+int sc_batch_plan_eigh_range_f64(sc_batch_plan* plan, double* d_a, int64_t il, int64_t iu, double* d_w, double* d_v);
+/* Eigenvalue window (vl, vu] of every slot, as sc_dev_eigh_window_f64 with 1 <= capacity <= dim * min(n_atoms), except
+ * that only a structure's own dim * n_atoms eigenvalues count: d_count[b] = min(count, dim n_b - il_b) -- the pads are
+ * never counted, also for vu = +inf -- and the K = capacity solved rows of slot b start at min(il_b, dim n_b - K). */
+int sc_batch_plan_eigh_window_f64(sc_batch_plan* plan, double* d_a, double vl, double vu, int64_t capacity, double* d_w,
+                                  double* d_v, int64_t* d_count);
+/* The batch consumers above (nma.py:108-184 mean_square_fluctuation, nma.py:233-359 dcc) on a plan's slots: d_w (count,
+ * nvec), d_v (count, nvec, order), sel and d_counts as for sc_dev_modes_*.  sel->reserved holds first_row, the global
+ * mode index of row 0 (il of an index-range solve, otherwise 0): rows r >= dim n_b - first_row of structure b are pads and
+ * never carry a weight, whatever the selection names; SC_SEL_PINV takes its maximum over the structure's own eigenvalues
+ * only (the pads are the largest of the slot).  Pad columns are neither read into a sum nor packed.
+ * msf: d_out (sum n_atoms,) packed, structure b at its atom offset.  A structure's bits depend on the slot order and the
+ * selection, not on its neighbours or its position. */
+int sc_batch_plan_modes_msf_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
+                                const sc_mode_selection* sel, const int64_t* d_counts, double* d_out);
+/* dcc: d_out (sum n_atoms^2,) packed, structure b's (n_b, n_b) block at the sum of the squares before it.  One grouped
+ * GEMM record per structure with M = N = ldc = n_b; slabs, row chunks and the block tile as for sc_dev_modes_dcc_f64,
+ * functions of (order, rows, dim, budget) only. */
+int sc_batch_plan_modes_dcc_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
+                                const sc_mode_selection* sel, const int64_t* d_counts, int norm, int64_t budget_bytes,
+                                double* d_out);
+/* What sc_dev_modes_workspace_bytes answers for a uniform batch, for the plan's (count, order). */
+int64_t sc_batch_plan_modes_workspace_bytes(const sc_batch_plan* plan, int64_t nvec, int64_t n_sel, int what,
+                                            int64_t budget_bytes);
 
 #ifdef __cplusplus
 }

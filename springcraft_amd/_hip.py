@@ -47,6 +47,8 @@ EXPORTED_SYMBOLS = [
     "sc_batch_plan_destroy", "sc_batch_plan_contacts", "sc_batch_plan_pairs", "sc_batch_plan_fill_from_pairs_f64",
     "sc_eigh_window_f64", "sc_anm_eigen_window_f64", "sc_dev_eigh_window_f64",
     "sc_dev_modes_msf_f64", "sc_dev_modes_dcc_f64", "sc_dev_modes_workspace_bytes",
+    "sc_batch_plan_eigh_range_f64", "sc_batch_plan_eigh_window_f64", "sc_batch_plan_modes_msf_f64",
+    "sc_batch_plan_modes_dcc_f64", "sc_batch_plan_modes_workspace_bytes",
 ]
 
 SC_SEL_FROM_ROW = 0
@@ -217,6 +219,11 @@ def lib():
         "sc_dev_modes_msf_f64": (i32, [vp, vp, vp, i64, i64, i64, i32, P(ModeSelection), vp, vp]),
         "sc_dev_modes_dcc_f64": (i32, [vp, vp, vp, i64, i64, i64, i32, P(ModeSelection), vp, i32, i64, vp]),
         "sc_dev_modes_workspace_bytes": (i64, [i64, i64, i64, i32, i64, i32, i64]),
+        "sc_batch_plan_eigh_range_f64": (i32, [vp, vp, i64, i64, vp, vp]),
+        "sc_batch_plan_eigh_window_f64": (i32, [vp, vp, dbl, dbl, i64, vp, vp, vp]),
+        "sc_batch_plan_modes_msf_f64": (i32, [vp, vp, vp, i64, P(ModeSelection), vp, vp]),
+        "sc_batch_plan_modes_dcc_f64": (i32, [vp, vp, vp, i64, P(ModeSelection), vp, i32, i64, vp]),
+        "sc_batch_plan_modes_workspace_bytes": (i64, [vp, i64, i64, i32, i64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

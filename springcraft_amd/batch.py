@@ -21,7 +21,7 @@ from . import _hip
 from .forcefield import device_plan
 
 __all__ = ["DeviceBatchSolver", "RaggedBatchSolver", "shard_bounds", "solve_sharded", "partition_lpt", "size_buckets",
-           "solve_ragged", "batch_mode_rows"]
+           "solve_ragged", "batch_mode_rows", "ragged_subset_plan"]
 
 K_B = 1.380649e-23
 
@@ -67,6 +67,50 @@ def batch_mode_rows(mode_subset, ntriv, subset, m, window=None):
         bad = idx[(idx < lo) | (idx > hi)][0]
         raise ValueError(f"mode {bad} was not solved: this solver holds modes {lo}..{hi}")
     return (idx - lo).astype(np.int32)
+
+
+def ragged_subset_plan(sizes, dim, subset_by_index=None, subset_by_value=None, max_modes=None):
+    """
+    What a :class:`RaggedBatchSolver` solves per slot, checked on the host before any device call.  A slot is
+    ``diag(M, D)`` with the pad D above M's spectrum, so its lowest eigenpairs are the structure's own; a subset must stay
+    inside the ``dim * min(sizes)`` modes that EVERY structure has, or the smallest one would return pads as modes.
+
+    subset_by_index  None or (lo, hi), inclusive: needs ``0 <= lo <= hi < dim * min(sizes)``
+    subset_by_value  None or (vl, vu) with ``max_modes = K``, ``1 <= K <= dim * min(sizes)``; the same mutual-exclusion
+                     and ``max_modes`` rules as :class:`DeviceBatchSolver` (``nma._value_window``)
+
+    Returns a dict: ``subset`` ((lo, hi) or None), ``window`` ((vl, vu) or None), ``max_modes`` (int or None), ``nvec``
+    (rows of ``w`` / ``v`` per slot; None for the full spectrum, where it is the slot order), ``first_row`` (global mode
+    index of row 0: lo, else 0) and ``row_limits`` (per structure, how many rows can be its own modes: ``dim * n_b`` for the
+    full spectrum, else ``nvec``).
+    """
+    from .nma import _value_window
+
+    sizes = [int(n) for n in sizes]
+    dim = int(dim)
+    if not sizes:
+        raise ValueError("no structures")
+    window = _value_window(subset_by_value, subset_by_index)
+    if window is None and max_modes is not None:
+        raise ValueError("max_modes applies to subset_by_value only")
+    smallest = int(np.argmin(sizes))
+    own_min = dim * sizes[smallest]
+    whose = f"the smallest structure ({smallest}: {sizes[smallest]} atoms) has {own_min} modes"
+    plan = {"subset": None, "window": window, "max_modes": None, "nvec": None, "first_row": 0,
+            "row_limits": [dim * n for n in sizes]}
+    if window is not None:
+        if max_modes is None:
+            raise ValueError("subset_by_value needs max_modes, the number of eigenpairs kept per structure")
+        if not 1 <= int(max_modes) <= own_min:
+            raise ValueError(f"max_modes {max_modes} outside 1..{own_min}: {whose}")
+        k = int(max_modes)
+        plan.update(max_modes=k, nvec=k, row_limits=[k] * len(sizes))
+    elif subset_by_index is not None:
+        lo, hi = int(subset_by_index[0]), int(subset_by_index[1])
+        if not 0 <= lo <= hi < own_min:
+            raise ValueError(f"subset_by_index {tuple(subset_by_index)} outside 0..{own_min - 1}: {whose}")
+        plan.update(subset=(lo, hi), nvec=hi - lo + 1, first_row=lo, row_limits=[hi - lo + 1] * len(sizes))
+    return plan
 
 
 class DeviceBatchSolver:
@@ -326,16 +370,34 @@ class RaggedBatchSolver:
     ``solve(coord)`` takes the structures' coordinates back to back, (sum(sizes), 3) float64 on the device, and returns
     the padded result tensors (w (B, order), v (B, order, order)); ``results()`` slices them into per-structure views
     (w_i (dim n_i,), v_i (dim n_i, dim n_i), rows = modes as nma.py:63).
+
+    A slot is ``diag(M, D)`` with every pad entry above M's spectrum, so a slot's lowest eigenpairs are the structure's
+    own and the partial-spectrum path applies (:func:`ragged_subset_plan` checks the arguments on the host):
+
+    ``subset_by_index=(lo, hi)``: ``w`` (B, hi-lo+1), ``v`` (B, hi-lo+1, order); needs ``hi < dim * min(sizes)``.
+    ``subset_by_value=(vl, vu)`` with ``max_modes=K <= dim * min(sizes)``: as on :class:`DeviceBatchSolver` -- scipy's
+    (vl, vu], counted on the device, :meth:`solve` only enqueues, ``counts`` an int64 device tensor, :meth:`finish` raises
+    ValueError for members above K -- where ``counts[b]`` counts only the structure's own ``dim * n_b`` eigenvalues (pads
+    never count, also for ``vu = +inf``) and the K rows of slot b start at ``min(il_b, dim * n_b - K)``.
+    ``results()`` cuts ``v_i`` to the structure's own ``dim * n_i`` columns and, behind a window solve, both to the first
+    ``min(counts[i], K)`` rows.
+
+    :meth:`frequencies`, :meth:`mean_square_fluctuation`, :meth:`bfactor` and :meth:`dcc` have the meaning, defaults and
+    trivial-mode rules of :class:`DeviceBatchSolver`'s, per structure: they only enqueue and return a list of CUDA tensors,
+    (n_i,) / (n_i, n_i), views into one packed buffer.  Pad rows and columns are never read into a result, and the
+    ``|lambda| > 1e-6 max|lambda|`` rule of the dcc default takes its maximum over the structure's own eigenvalues.
     """
 
-    def __init__(self, sizes, force_fields, dim=3, masses=None, device=None, want_vectors=True, order=None):
+    def __init__(self, sizes, force_fields, dim=3, masses=None, device=None, want_vectors=True, order=None,
+                 subset_by_index=None, subset_by_value=None, max_modes=None):
+        self.sizes = [int(n) for n in sizes]
+        self.batch, self.dim = len(self.sizes), int(dim)
+        self._subset_plan = ragged_subset_plan(self.sizes, self.dim, subset_by_index, subset_by_value, max_modes)
+        self.subset, self.window = self._subset_plan["subset"], self._subset_plan["window"]
+        self.max_modes = self._subset_plan["max_modes"]
         import torch
 
         self.torch = torch
-        self.sizes = [int(n) for n in sizes]
-        self.batch, self.dim = len(self.sizes), int(dim)
-        if self.batch == 0:
-            raise ValueError("no structures")
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         if not isinstance(force_fields, (list, tuple)):
             force_fields = [force_fields] * self.batch
@@ -376,9 +438,11 @@ class RaggedBatchSolver:
         self.offsets = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
         f64 = torch.float64
         m = self.order
+        nvec = self._subset_plan["nvec"] or m
+        self.counts = torch.zeros((self.batch,), dtype=torch.int64, device=self.device) if self.window is not None else None
         self.matrix = torch.empty((self.batch, m, m), dtype=f64, device=self.device)
-        self.w = torch.empty((self.batch, m), dtype=f64, device=self.device)
-        self.v = torch.empty((self.batch, m, m), dtype=f64, device=self.device) if want_vectors else None
+        self.w = torch.empty((self.batch, nvec), dtype=f64, device=self.device)
+        self.v = torch.empty((self.batch, nvec, m), dtype=f64, device=self.device) if want_vectors else None
         self.inv_sqrt_mass = None
         if masses is not None:
             if len(masses) != self.batch:
@@ -444,8 +508,15 @@ class RaggedBatchSolver:
 
     def eigh(self):
         vp = C.c_void_p(self.v.data_ptr()) if self.v is not None else None
-        self.ctx.check(self._L.sc_dev_eigh_f64(self.ctx.handle, C.c_void_p(self.matrix.data_ptr()), self.order,
-                                               self.batch, C.c_void_p(self.w.data_ptr()), vp))
+        ap, wp = C.c_void_p(self.matrix.data_ptr()), C.c_void_p(self.w.data_ptr())
+        if self.window is not None:
+            self.ctx.check(self._L.sc_batch_plan_eigh_window_f64(self._plan, ap, self.window[0], self.window[1],
+                                                                 self.max_modes, wp, vp,
+                                                                 C.c_void_p(self.counts.data_ptr())))
+        elif self.subset is not None:
+            self.ctx.check(self._L.sc_batch_plan_eigh_range_f64(self._plan, ap, self.subset[0], self.subset[1], wp, vp))
+        else:
+            self.ctx.check(self._L.sc_dev_eigh_f64(self.ctx.handle, ap, self.order, self.batch, wp, vp))
         return self.w, self.v
 
     def solve(self, coord):
@@ -453,21 +524,124 @@ class RaggedBatchSolver:
         return self.eigh()
 
     def finish(self):
-        """As :meth:`DeviceBatchSolver.finish`: wait, and raise ``np.linalg.LinAlgError`` for NaN / Inf input or a QL failure."""
+        """
+        As :meth:`DeviceBatchSolver.finish`: wait, and raise ``np.linalg.LinAlgError`` for NaN / Inf input or a QL failure;
+        with ``subset_by_value``, then ValueError naming every structure whose window held more than ``max_modes`` eigenpairs.
+        """
         self.ctx.synchronize()
+        if self.window is not None:
+            counts = self.counts.cpu().numpy()
+            over = np.nonzero(counts > self.max_modes)[0]
+            if len(over):
+                which = ", ".join(f"{b} ({counts[b]})" for b in over)
+                raise ValueError(f"the eigenvalue window {self.window} holds more than max_modes = {self.max_modes} "
+                                 f"eigenpairs for structure(s) {which}; their slots hold the {self.max_modes} lowest")
         return self.w, self.v
 
     def results(self):
         """
-        Per-structure views of the last solve: [(w_i, v_i or None), ...].  Waits for the solve and raises
-        ``np.linalg.LinAlgError`` as ``np.linalg.eigh`` does at nma.py:61 (see :meth:`finish`).
+        Per-structure views of the last solve: [(w_i, v_i or None), ...], ``v_i`` cut to the structure's own ``dim n_i``
+        columns; behind a window solve both are cut to the first ``min(counts[i], max_modes)`` rows.  Waits for the solve
+        and raises ``np.linalg.LinAlgError`` as ``np.linalg.eigh`` does at nma.py:61 (see :meth:`finish`).
         """
         self.ctx.synchronize()
+        rows = list(self._subset_plan["row_limits"])
+        if self.window is not None:
+            rows = [min(int(c), self.max_modes) for c in self.counts.cpu().numpy()]
         out = []
         for b, n in enumerate(self.sizes):
             m = self.dim * n
-            out.append((self.w[b, :m], self.v[b, :m, :m] if self.v is not None else None))
+            out.append((self.w[b, :rows[b]], self.v[b, :rows[b], :m] if self.v is not None else None))
         return out
+
+    # ---- consumers of the solved modes: DeviceBatchSolver's, per structure ------------------------------------------------
+    # They ONLY ENQUEUE on the solver's stream (the first call of a kind allocates its workspace) and return lists of views
+    # into one packed buffer: structure b's atoms start at sum(sizes[:b]), its (n_b, n_b) block at sum(sizes[:b] ** 2).
+
+    #: bytes the packed GEMM operands of :meth:`dcc` may take at a time (None: SPRINGCRAFT_MODES_BUDGET_BYTES, else 1 GiB)
+    consumer_budget_bytes = None
+
+    @property
+    def _ntriv(self):
+        return 6 if self.dim == 3 else 1
+
+    def _selection(self, mode_subset, pinv_default):
+        """(ModeSelection, counts pointer) for a consumer call; every check is on the host."""
+        if self.v is None:
+            raise ValueError("the mode consumers need the eigenvectors: build the solver with want_vectors=True")
+        # an explicit list is checked against the modes EVERY structure has: one the smallest structure lacks raises the
+        # "was not solved" error instead of being dropped for that structure alone
+        rows = batch_mode_rows(mode_subset, self._ntriv, self.subset, self.dim * min(self.sizes), self.window)
+        sel = _hip.ModeSelection()
+        sel.reserved = self._subset_plan["first_row"]
+        nvec = self.w.shape[1]
+        keep = None
+        if self.window is not None:
+            sel.kind, sel.row0 = _hip.SC_SEL_FROM_ROW, 0
+        elif mode_subset is None and pinv_default and self.subset is None:
+            sel.kind, sel.rcond = _hip.SC_SEL_PINV, 1e-6
+        elif mode_subset is None:
+            # every solved non-trivial row; on a full-spectrum solver the records end the rows at dim * n_b
+            sel.kind, sel.row0 = _hip.SC_SEL_FROM_ROW, min(max(self._ntriv - sel.reserved, 0), nvec)
+        else:
+            host = self.torch.from_numpy(rows).pin_memory()     # (page-locked: the copy must not wait for the stream)
+            keep = host.to(self.device, non_blocking=True)
+            sel.kind, sel.d_rows, sel.n_rows = _hip.SC_SEL_ROWS, keep.data_ptr(), len(rows)
+        self._rows_keep = keep
+        return sel, (C.c_void_p(self.counts.data_ptr()) if self.window is not None else None)
+
+    def frequencies(self):
+        """
+        Per structure the frequencies ``sqrt(lambda) / (2 pi)`` of its solved modes, trivial ones entering as
+        ``abs(lambda)`` (nma.py:66-105): (dim n_i,) for a full-spectrum solver, else all ``nvec`` rows (with
+        ``subset_by_value`` no row is treated as trivial and the rows behind the count are NaN).
+        """
+        w = self.w.clone()
+        if self.window is None:
+            k = max(0, min(self._ntriv - self._subset_plan["first_row"], w.shape[1]))
+            w[:, :k] = w[:, :k].abs()
+        f = self.torch.sqrt(w) / (2 * np.pi)
+        return [f[b, :r] for b, r in enumerate(self._subset_plan["row_limits"])]
+
+    def mean_square_fluctuation(self, mode_subset=None, tem=None, tem_factors=K_B):
+        """
+        [(n_i,), ...] mean square fluctuations (nma.py:108-184), as :meth:`DeviceBatchSolver.mean_square_fluctuation`.
+        ``mode_subset=None``: every own non-trivial solved mode of each structure (behind a window solve: the window).  An
+        explicit ``mode_subset`` holds global mode indices below ``dim * min(sizes)``.
+        """
+        sel, counts = self._selection(mode_subset, pinv_default=False)
+        out = self.torch.empty((int(self.offsets[-1]),), dtype=self.torch.float64, device=self.device)
+        self.ctx.check(self._L.sc_batch_plan_modes_msf_f64(
+            self._plan, C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr()), self.w.shape[1], C.byref(sel),
+            counts, C.c_void_p(out.data_ptr())))
+        if tem is not None:
+            out *= tem * tem_factors
+        return [out[self.offsets[b]: self.offsets[b + 1]] for b in range(self.batch)]
+
+    def bfactor(self, mode_subset=None, tem=None, tem_factors=K_B):
+        """[(n_i,), ...] isotropic B-factors, ``8 pi^2 / 3`` times :meth:`mean_square_fluctuation` (nma.py:187-230)."""
+        out = self.mean_square_fluctuation(mode_subset, tem, tem_factors)
+        for o in out:
+            o *= (8 * np.pi**2) / 3
+        return out
+
+    def dcc(self, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
+        """
+        [(n_i, n_i), ...] dynamic cross-correlations (nma.py:233-359), as :meth:`DeviceBatchSolver.dcc`.
+        ``mode_subset=None`` on a full-spectrum solver: per structure every mode with ``|lambda| > 1e-6 max|lambda|``, the
+        maximum taken over the structure's OWN eigenvalues (the slot's pads are larger and never enter); on a
+        ``subset_by_index`` solver every solved non-trivial mode; behind a window solve the window.
+        """
+        sel, counts = self._selection(mode_subset, pinv_default=True)
+        sq = np.concatenate([[0], np.cumsum(np.asarray(self.sizes, dtype=np.int64) ** 2)])
+        out = self.torch.empty((int(sq[-1]),), dtype=self.torch.float64, device=self.device)
+        self.ctx.check(self._L.sc_batch_plan_modes_dcc_f64(
+            self._plan, C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr()), self.w.shape[1], C.byref(sel),
+            counts, int(bool(norm)), int(self.consumer_budget_bytes or 0), C.c_void_p(out.data_ptr())))
+        if tem is not None:
+            out *= tem
+            out *= tem_factors
+        return [out[sq[b]: sq[b + 1]].view(n, n) for b, n in enumerate(self.sizes)]
 
     def close(self):
         if getattr(self, "_plan", None) is not None and self._plan.value:
@@ -651,7 +825,8 @@ def partition_lpt(costs, n_bins):
     return [sorted(b) for b in bins]
 
 
-def solve_ragged(coords_list, force_field, dim=3, group=None, solver_factory=None, solvers=None, max_flop_ratio=1.25):
+def solve_ragged(coords_list, force_field, dim=3, group=None, solver_factory=None, solvers=None, max_flop_ratio=1.25,
+                 subset_by_index=None):
     """
     Independent structures of DIFFERENT sizes over all ranks of ``group``.
 
@@ -664,6 +839,12 @@ def solve_ragged(coords_list, force_field, dim=3, group=None, solver_factory=Non
     Two exchange steps, as in :func:`solve_sharded`; eigenvectors are not returned (they stay where they were computed,
     inside the solvers' buffers).  ``solvers``: optional dict {tuple of the bucket's sizes: RaggedBatchSolver} reused
     across calls.  Device-side failures raise ``np.linalg.LinAlgError`` after the gather, as in :func:`solve_sharded`.
+
+    ``subset_by_index=(lo, hi)``: only eigenvalues lo..hi of every structure, through the partial-spectrum path of the
+    local solvers; the result arrays are (hi-lo+1,).  Every rank checks the range against the broadcast sizes before the
+    scatter (:func:`ragged_subset_plan`), so all ranks raise the same ValueError and no collective is left unmatched.  A
+    ``solver_factory`` keeps its contract (full spectrum) and the columns lo..hi are sliced here.  ``solvers`` must then
+    hold solvers built with the same subset.
     """
     import torch
     import torch.distributed as dist
@@ -692,6 +873,10 @@ def solve_ragged(coords_list, force_field, dim=3, group=None, solver_factory=Non
     if distributed:
         dist.broadcast(sizes, src=0, group=group)
     sizes = [int(x) for x in sizes[:B].cpu()]
+    lo_col, ncol = 0, None        # columns of a structure's spectrum that travel: all, or lo .. lo + ncol - 1
+    if subset_by_index is not None and B:
+        lo_col, hi_col = ragged_subset_plan(sizes, dim, subset_by_index)["subset"]
+        ncol = hi_col - lo_col + 1
     parts = partition_lpt([float(n) ** 3 for n in sizes], world)
     mine = parts[rank]
     atoms_per_rank = [sum(sizes[i] for i in part) for part in parts]
@@ -736,8 +921,10 @@ def solve_ragged(coords_list, force_field, dim=3, group=None, solver_factory=Non
                 failure = e
                 w_np = np.full((len(items), n_atoms * dim), np.nan)
             w = torch.from_numpy(np.asarray(w_np))
+            if ncol is not None:
+                w = w[:, lo_col: lo_col + ncol]
             for k, i in enumerate(items):
-                w_local[offsets[i] * dim: (offsets[i] + n_atoms) * dim] = w[k].to(dev)
+                w_local[offsets[i] * dim: offsets[i] * dim + w.shape[1]] = w[k].to(dev)
                 results[i] = w[k].cpu().numpy().copy()
     else:
         for bucket in size_buckets([sizes[i] for i in mine], max_flop_ratio):
@@ -745,7 +932,8 @@ def solve_ragged(coords_list, force_field, dim=3, group=None, solver_factory=Non
             key = tuple(sizes[i] for i in items)
             solver = solvers.get(key) if solvers is not None else None
             if solver is None:
-                solver = RaggedBatchSolver(key, force_field, dim=dim, want_vectors=False)
+                solver = RaggedBatchSolver(key, force_field, dim=dim, want_vectors=False,
+                                           subset_by_index=None if ncol is None else (lo_col, lo_col + ncol - 1))
                 if solvers is not None:
                     solvers[key] = solver
             packed = torch.cat([local[offsets[i]: offsets[i] + sizes[i]] for i in items]).to(solver.device).contiguous()
@@ -756,7 +944,7 @@ def solve_ragged(coords_list, force_field, dim=3, group=None, solver_factory=Non
                 failure = e
                 per_structure = solver.results()
             for i, (wi, _) in zip(items, per_structure):
-                w_local[offsets[i] * dim: (offsets[i] + sizes[i]) * dim] = wi.to(dev)
+                w_local[offsets[i] * dim: offsets[i] * dim + len(wi)] = wi.to(dev)
                 results[i] = wi.cpu().numpy().copy()
     if failure is not None:
         w_local[-1] = 1.0
@@ -777,7 +965,7 @@ def solve_ragged(coords_list, force_field, dim=3, group=None, solver_factory=Non
             if buf[-1] != 0.0:
                 failed.append(r)
             for i in part:
-                out[i] = buf[off * dim: (off + sizes[i]) * dim].copy()
+                out[i] = buf[off * dim: off * dim + (sizes[i] * dim if ncol is None else ncol)].copy()
                 off += sizes[i]
         if failed:
             raise np.linalg.LinAlgError(f"Eigenvalues did not converge on rank(s) {failed} (NaN / Inf input or a failed "

@@ -911,11 +911,11 @@ int64_t sc_eigh_workspace_bytes(int64_t n, int64_t batch, int want_vectors) {
 
 // ---- batch consumers (batch_consumers.hip) -------------------------------------------------------------------------
 static int check_modes_args(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
-                            int dim, const sc_mode_selection* sel, const double* d_out) {
+                            int dim, const sc_mode_selection* sel, const double* d_out, bool padded = false) {
   if (!ctx) return SC_ERR_INVALID_ARG;
   if (m <= 0 || nvec <= 0 || batch <= 0 || !d_w || !d_v || !sel || !d_out)
     return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
-  if ((dim != 1 && dim != 3) || m % dim != 0)
+  if ((dim != 1 && dim != 3) || (!padded && m % dim != 0))   // (padded: m is a plan's slot order)
     return sc_set_error(ctx, SC_ERR_INVALID_ARG, "dim must be 1 or 3 and divide m = %lld", (long long)m);
   if (m > INT32_MAX || nvec > m || batch > INT32_MAX || (size_t)batch * nvec > (size_t)INT32_MAX)
     return sc_set_error(ctx, SC_ERR_INVALID_ARG, "(batch, nvec, m) = (%lld, %lld, %lld) is not a solver's result shape",
@@ -972,8 +972,10 @@ struct sc_batch_plan {
   int max_atoms = 0;
   bool any_patch = false, any_pad = false;
   char* d_blob = nullptr;
-  size_t off_items = 0, off_bound = 0;
+  size_t off_items = 0, off_bound = 0, off_ragged = 0;
   std::vector<int64_t> atom_off;   // count + 1: first atom of every structure in the packed buffers
+  int64_t total_sq = 0;            // sum of n_atoms^2: elements of a packed dcc
+  int min_atoms = 0;
 };
 
 namespace {
@@ -1023,6 +1025,20 @@ int sc_batch_plan_create(sc_ctx* ctx, int dim, const sc_structure_desc* structur
   const size_t off_items = blob.take(isz * (size_t)count);
   const size_t off_bound = blob.take(8 * (size_t)count);
   const size_t off_zero = blob.take(4 * ((size_t)max_atoms + 2));   // empty patch tables: shut = 0, row_ptr = 0
+  // own order and packed output offsets of every structure, for the window count and the consumers
+  const size_t off_ragged = blob.take(sizeof(RaggedRec) * (size_t)count);
+  int64_t total_sq = 0, min_atoms = max_atoms;
+  {
+    int64_t atoms = 0;
+    for (int64_t b = 0; b < count; ++b) {
+      const int64_t n = structures[b].n_atoms;
+      const RaggedRec r{(int)(dim * n), (int)n, (long long)atoms, (long long)total_sq};
+      memcpy(blob.bytes.data() + off_ragged + sizeof(RaggedRec) * (size_t)b, &r, sizeof(r));
+      atoms += n;
+      total_sq += n * n;
+      min_atoms = std::min(min_atoms, n);
+    }
+  }
   struct Rec {
     sc_ff_desc ff; sc_tab_desc tab; bool has_tab = false;
     size_t o_edges = 0, o_tables = 0, o_type = 0, o_chain = 0, o_bond = 0;
@@ -1119,7 +1135,8 @@ int sc_batch_plan_create(sc_ctx* ctx, int dim, const sc_structure_desc* structur
   if (!plan) { (void)hipFree(d_blob); return SC_ERR_NOMEM; }
   plan->ctx = ctx; plan->dim = dim; plan->count = count; plan->order = order; plan->max_atoms = (int)max_atoms;
   plan->any_patch = any_patch; plan->any_pad = any_pad;
-  plan->d_blob = d_blob; plan->off_items = off_items; plan->off_bound = off_bound;
+  plan->d_blob = d_blob; plan->off_items = off_items; plan->off_bound = off_bound; plan->off_ragged = off_ragged;
+  plan->total_sq = total_sq; plan->min_atoms = (int)min_atoms;
   plan->atom_off.assign((size_t)count + 1, 0);
   for (int64_t b = 0; b < count; ++b) plan->atom_off[(size_t)b + 1] = plan->atom_off[(size_t)b] + structures[b].n_atoms;
   *out = plan;
@@ -1237,6 +1254,80 @@ int sc_batch_plan_fill_from_pairs_f64(sc_batch_plan* plan, const double* d_coord
 }
 
 int64_t sc_batch_plan_order(const sc_batch_plan* plan) { return plan ? plan->order : 0; }
+
+// ---- partial spectrum and mode consumers of a plan's padded slots ------------------------------------------------------
+static const RaggedRec* plan_records(const sc_batch_plan* plan) {
+  return reinterpret_cast<const RaggedRec*>(plan->d_blob + plan->off_ragged);
+}
+
+static RaggedView plan_view(const sc_batch_plan* plan, int first_row) {
+  return RaggedView{plan_records(plan), first_row, plan->max_atoms, plan->atom_off.back(), plan->total_sq};
+}
+
+int sc_batch_plan_eigh_range_f64(sc_batch_plan* plan, double* d_a, int64_t il, int64_t iu, double* d_w, double* d_v) {
+  if (!plan) return SC_ERR_INVALID_ARG;
+  sc_ctx* ctx = plan->ctx;
+  if (!d_a || !d_w) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  const int64_t own_min = (int64_t)plan->dim * plan->min_atoms;
+  if (il < 0 || iu < il || iu >= own_min)
+    return sc_set_error(ctx, SC_ERR_INDEX, "eigenvalue index range [%lld, %lld] outside the %lld modes of the smallest "
+                        "structure", (long long)il, (long long)iu, (long long)own_min);
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return eigh_range_batched_async(ctx, d_a, plan->order, plan->count, il, iu, d_w, d_v);
+}
+
+int sc_batch_plan_eigh_window_f64(sc_batch_plan* plan, double* d_a, double vl, double vu, int64_t capacity, double* d_w,
+                                  double* d_v, int64_t* d_count) {
+  if (!plan) return SC_ERR_INVALID_ARG;
+  sc_ctx* ctx = plan->ctx;
+  if (!d_a || !d_w || !d_count) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  const int64_t own_min = (int64_t)plan->dim * plan->min_atoms;
+  if (capacity < 1 || capacity > own_min)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "window capacity %lld outside 1..%lld, the modes of the smallest structure",
+                        (long long)capacity, (long long)own_min);
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return eigh_window_batched_async(ctx, d_a, plan->order, plan->count, vl, vu, capacity, d_w, d_v, d_count,
+                                   plan_records(plan));
+}
+
+static int check_plan_modes_args(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
+                                 const sc_mode_selection* sel, const double* d_out) {
+  if (!plan) return SC_ERR_INVALID_ARG;
+  SC_TRY(check_modes_args(plan->ctx, d_w, d_v, plan->order, nvec, plan->count, plan->dim, sel, d_out, true));
+  if (sel->reserved < 0 || sel->reserved >= plan->order)
+    return sc_set_error(plan->ctx, SC_ERR_INDEX, "first row %d outside 0..%lld", (int)sel->reserved,
+                        (long long)plan->order - 1);
+  return SC_OK;
+}
+
+int sc_batch_plan_modes_msf_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
+                                const sc_mode_selection* sel, const int64_t* d_counts, double* d_out) {
+  SC_TRY(check_plan_modes_args(plan, d_w, d_v, nvec, sel, d_out));
+  sc_ctx* ctx = plan->ctx;
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const RaggedView rv = plan_view(plan, (int)sel->reserved);
+  return batch_msf_device(ctx, d_w, d_v, plan->order, nvec, plan->count, plan->dim, *sel, d_counts, 0, d_out, &rv);
+}
+
+int sc_batch_plan_modes_dcc_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
+                                const sc_mode_selection* sel, const int64_t* d_counts, int norm, int64_t budget_bytes,
+                                double* d_out) {
+  SC_TRY(check_plan_modes_args(plan, d_w, d_v, nvec, sel, d_out));
+  sc_ctx* ctx = plan->ctx;
+  if (budget_bytes < 0) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "budget_bytes must be >= 0");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const RaggedView rv = plan_view(plan, (int)sel->reserved);
+  return batch_dcc_device(ctx, d_w, d_v, plan->order, nvec, plan->count, plan->dim, *sel, d_counts, norm,
+                          (size_t)budget_bytes, d_out, &rv);
+}
+
+int64_t sc_batch_plan_modes_workspace_bytes(const sc_batch_plan* plan, int64_t nvec, int64_t n_sel, int what,
+                                            int64_t budget_bytes) {
+  if (!plan || nvec <= 0 || n_sel < 0 || budget_bytes < 0) return 0;
+  const RaggedView rv = plan_view(plan, 0);
+  return (int64_t)batch_modes_workspace_bytes(plan->order, nvec, plan->count, plan->dim, n_sel, what, (size_t)budget_bytes,
+                                              &rv);
+}
 
 void sc_batch_plan_destroy(sc_batch_plan* plan) {
   if (!plan) return;

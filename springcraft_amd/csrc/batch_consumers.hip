@@ -12,6 +12,11 @@
 //
 // A row without weight is never multiplied in (the kernels select, they do not multiply by zero), so the NaN / zero
 // padding behind a window's rows cannot reach a result.  No atomics: every sum is a fixed sequence.
+//
+// Ragged batches (sc_batch_plan): every kernel takes an optional table of RaggedRec, one per structure.  Without it the
+// batch is uniform and nothing differs from the above.  With it m is the common slot order, structure b owns the first
+// rag[b].own rows and columns of its slot -- pad rows never carry a weight, pad columns are never packed or summed -- and
+// the results go to packed buffers at rag[b].atom_off (msf, diagonals) and rag[b].sq_off (dcc).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -26,22 +31,29 @@ constexpr size_t kModesBudgetBytes = (size_t)1 << 30;
 // grid.z carries the structures of a slab
 constexpr int64_t kMaxSlab = 32768;
 
-// rows of structure b that may carry a weight: all nvec, or the window's min(counts[b], nvec)
-__device__ __forceinline__ int rows_limit(const long long* __restrict__ counts, int b, int nvec) {
-  if (!counts) return nvec;
-  const long long c = counts[b];
-  return c < 0 ? 0 : (c < nvec ? (int)c : nvec);
+// rows of structure b that may carry a weight: all nvec, or the window's min(counts[b], nvec); in a ragged batch no more
+// than the own - first_row rows that are the structure's modes (first_row: global index of row 0)
+__device__ __forceinline__ int rows_limit(const long long* __restrict__ counts, int b, int nvec,
+                                          const RaggedRec* __restrict__ rag, int first_row) {
+  int lim = nvec;
+  if (counts) {
+    const long long c = counts[b];
+    lim = c < 0 ? 0 : (c < nvec ? (int)c : nvec);
+  }
+  if (rag) lim = max(min(lim, rag[b].own - first_row), 0);
+  return lim;
 }
 
 // s[b, kk] for the kk-th listed row: rows[kk], or row0 + kk without a list.  One workgroup per structure.
 // pinv: the rule of numpy.linalg.pinv(hermitian=True): rows with |w| <= rcond * max|w| (of this structure) get 0.
 __global__ __launch_bounds__(256) void k_mode_weights(const double* __restrict__ w, int nvec, int pinv, int row0,
                                                       const int* __restrict__ rows, int nsel, double rcond,
-                                                      const long long* __restrict__ counts, double* __restrict__ s) {
+                                                      const long long* __restrict__ counts, double* __restrict__ s,
+                                                      const RaggedRec* __restrict__ rag, int first_row) {
   __shared__ double red[256];
   const int b = blockIdx.x;
   const double* wb = w + (size_t)b * nvec;
-  const int lim = rows_limit(counts, b, nvec);
+  const int lim = rows_limit(counts, b, nvec, rag, first_row);   // (bounds the weights AND the pinv maximum)
   double thr = -1.0;   // |w| <= thr never holds: nothing is dropped
   if (pinv) {
     double mx = 0.0;   // (fmax skips NaN: a failed structure keeps thr = 0 and 1 / NaN below)
@@ -114,17 +126,22 @@ template <bool VEC, bool LIST>
 __global__ __launch_bounds__(256) void k_bmsf_partial(const double* __restrict__ v, const double* __restrict__ s,
                                                       const int* __restrict__ rows, int row0, int nsel, int nvec, int m,
                                                       int chunk, const long long* __restrict__ counts, int b0,
-                                                      double* __restrict__ part) {
+                                                      double* __restrict__ part, const RaggedRec* __restrict__ rag,
+                                                      int first_row) {
   const int b = b0 + blockIdx.z;
   const int c = blockIdx.y;
+  // ragged: the structure's own columns; a tile wholly behind them returns here, before its first load, and the lanes
+  // of the tile that straddles them mask their tail (VEC: the 16-byte load may take one pad column, which is dropped)
+  const int mo = rag ? rag[b].own : m;
+  if ((int)blockIdx.x * 512 >= mo) return;
   const int k0 = c * chunk;
   int k1 = min(k0 + chunk, nsel);
-  // without a list the rows ascend: those behind the window's count are not even read
-  if (!LIST) k1 = min(k1, rows_limit(counts, b, nvec) - row0);
+  // without a list the rows ascend: those behind the window's count (and a slot's pad rows) are not even read
+  if (!LIST) k1 = min(k1, rows_limit(counts, b, nvec, rag, first_row) - row0);
   const int j0 = VEC ? (blockIdx.x * 256 + threadIdx.x) * 2 : blockIdx.x * 512 + threadIdx.x;
   const int j1 = VEC ? j0 + 1 : j0 + 256;
-  if (j0 >= m) return;
-  const bool has1 = j1 < m;
+  if (j0 >= mo) return;
+  const bool has1 = j1 < mo;
   const int j1c = has1 ? j1 : j0;
   const double* vb = v + (size_t)b * nvec * m;
   const double* sb = s + (size_t)b * nsel;
@@ -138,16 +155,18 @@ __global__ __launch_bounds__(256) void k_bmsf_partial(const double* __restrict__
 }
 
 // out[b, a] = sum over chunks, then over the dim components, in that fixed order
+// (ragged: over the structure's n_atoms, to its packed atom offset)
 __global__ __launch_bounds__(256) void k_bmsf_reduce(const double* __restrict__ part, int nchunk, int m, int dim, int b0,
-                                                     double* __restrict__ out) {
-  const int N = m / dim;
+                                                     double* __restrict__ out, const RaggedRec* __restrict__ rag) {
+  const int b = b0 + blockIdx.y;
+  const int N = rag ? rag[b].n_atoms : m / dim;
   const int a = blockIdx.x * 256 + threadIdx.x;
   if (a >= N) return;
   const double* pb = part + (size_t)blockIdx.y * nchunk * m;
   double acc = 0.0;
   for (int c = 0; c < nchunk; ++c)
     for (int d = 0; d < dim; ++d) acc += pb[(size_t)c * m + a * dim + d];
-  out[(size_t)(b0 + blockIdx.y) * N + a] = acc;
+  out[(rag ? (size_t)rag[b].atom_off : (size_t)b * N) + a] = acc;
 }
 
 // listed rows per chunk: from the number of listed rows alone.  20 rows -> 5 chunks of 4 (64 structures of m = 6000:
@@ -158,19 +177,22 @@ int msf_chunk(int64_t nsel) { return (int)std::min<int64_t>(128, std::max<int64_
 // Listed rows k0 .. k0 + kc - 1 of every structure of the slab, component-major, so that the contraction over (row,
 // component) is one GEMM per structure (k_dcc_pack of consumers.hip, batched and weighted):
 //   P[bz][(d * kc + k) * N + a] = V[b, row(k0 + k), dim a + d]        S = the same times s[b, k0 + k]
-// A row without weight is not read: zeros in both operands.
+// A row without weight is not read: zeros in both operands.  Ragged: N = n_atoms of the structure and only its first
+// dim * N columns are packed (the slot of `stride` elements is sized for the slot order).
 __global__ __launch_bounds__(256) void k_bdcc_pack(const double* __restrict__ v, const double* __restrict__ s,
                                                    const int* __restrict__ rows, int row0, int nsel, int nvec, int m,
                                                    int dim, int k0, int kc, int b0, size_t stride,
-                                                   double* __restrict__ p, double* __restrict__ sp) {
+                                                   double* __restrict__ p, double* __restrict__ sp,
+                                                   const RaggedRec* __restrict__ rag) {
   const int k = blockIdx.y, kk = k0 + k;
   const int b = b0 + blockIdx.z;
   const double sv = s[(size_t)b * nsel + kk];
   const double* vr = v + ((size_t)b * nvec + listed_row(rows, row0, kk, nvec)) * m;
-  const int N = m / dim;
+  const int N = rag ? rag[b].n_atoms : m / dim;
+  const int mo = N * dim;
   double* pb = p + (size_t)blockIdx.z * stride;
   double* sb = sp + (size_t)blockIdx.z * stride;
-  for (int j = blockIdx.x * 256 + threadIdx.x; j < m; j += gridDim.x * 256) {
+  for (int j = blockIdx.x * 256 + threadIdx.x; j < mo; j += gridDim.x * 256) {
     const int a = j / dim, d = j - a * dim;
     const size_t o = ((size_t)d * kc + k) * N + a;
     if (sv != 0.0) {   // (uniform over the workgroup)
@@ -184,34 +206,47 @@ __global__ __launch_bounds__(256) void k_bdcc_pack(const double* __restrict__ v,
   }
 }
 
-// one GEMM record per structure of the slab: out[b] (N, N) (+)= S^T-by-P over K = kc * dim (layout kGemmAmBn)
+// one GEMM record per structure of the slab: out[b] (N, N) (+)= S^T-by-P over K = kc * dim (layout kGemmAmBn).
+// out: the first structure of the slab (uniform) / the packed buffer (ragged: M = N = ldc = the structure's n_atoms, C at
+// its square offset)
 __global__ void k_bdcc_descs(GemmDesc* __restrict__ desc, int count, const double* __restrict__ sp,
                              const double* __restrict__ p, size_t stride, double* __restrict__ out, int N, int K,
-                             double beta) {
+                             double beta, const RaggedRec* __restrict__ rag, int b0) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= count) return;
   GemmDesc D{};
+  if (rag) N = rag[b0 + i].n_atoms;
   D.a = sp + (size_t)i * stride; D.sa_i = 1; D.sa_k = N;
   D.b = p + (size_t)i * stride; D.sb_k = N; D.sb_j = 1;
-  D.c = out + (size_t)i * N * N; D.ldc = N; D.m = N; D.n = N; D.k = K;
+  D.c = rag ? out + rag[b0 + i].sq_off : out + (size_t)i * N * N;
+  D.ldc = N; D.m = N; D.n = N; D.k = K;
   D.alpha = 1.0; D.beta = beta;
   desc[i] = D;
 }
 
-__global__ __launch_bounds__(256) void k_bcopy_diag(const double* __restrict__ c, int N, double* __restrict__ diag) {
+// (c, diag: the first structure of the launch; ragged: the packed buffers, b0 the first structure of the launch)
+__global__ __launch_bounds__(256) void k_bcopy_diag(const double* __restrict__ c, int N, double* __restrict__ diag,
+                                                    const RaggedRec* __restrict__ rag, int b0) {
   const int a = blockIdx.x * 256 + threadIdx.x;
   const size_t b = blockIdx.y;
+  if (rag) {
+    const RaggedRec r = rag[b0 + b];
+    if (a < r.n_atoms) diag[r.atom_off + a] = c[r.sq_off + (size_t)a * r.n_atoms + a];
+    return;
+  }
   if (a < N) diag[b * N + a] = c[(b * N + a) * N + a];
 }
 
 // in place; the reference divides by outer(sqrt(diag), sqrt(diag)) (nma.py:352-354)
-__global__ __launch_bounds__(256) void k_bdcc_norm(double* __restrict__ c, const double* __restrict__ diag, int N) {
+__global__ __launch_bounds__(256) void k_bdcc_norm(double* __restrict__ c, const double* __restrict__ diag, int N,
+                                                   const RaggedRec* __restrict__ rag, int b0) {
   const int a = blockIdx.x * 256 + threadIdx.x;
   const int r = blockIdx.y;
   const size_t b = blockIdx.z;
-  if (a >= N) return;
-  const double* db = diag + b * N;
-  double* cb = c + b * N * N;
+  if (rag) N = rag[b0 + b].n_atoms;
+  if (a >= N || r >= N) return;
+  const double* db = rag ? diag + rag[b0 + b].atom_off : diag + b * N;
+  double* cb = rag ? c + rag[b0 + b].sq_off : c + b * N * N;
   cb[(size_t)r * N + a] = cb[(size_t)r * N + a] / (sqrt(db[a]) * sqrt(db[r]));
 }
 
@@ -246,11 +281,12 @@ int64_t msf_slab(int64_t m, int64_t nsel, int64_t batch, size_t budget) {
 }
 
 int launch_weights(sc_ctx* ctx, const double* d_w, int64_t nvec, int64_t batch, const sc_mode_selection& sel,
-                   int64_t nsel, const int64_t* d_counts, double* d_s) {
+                   int64_t nsel, const int64_t* d_counts, double* d_s, const RaggedView* rv) {
   hipLaunchKernelGGL(k_mode_weights, dim3((unsigned)batch), dim3(256), 0, ctx->stream, d_w, (int)nvec,
                      sel.kind == SC_SEL_PINV ? 1 : 0, sel.kind == SC_SEL_FROM_ROW ? (int)sel.row0 : 0,
                      sel.kind == SC_SEL_ROWS ? sel.d_rows : nullptr, (int)nsel, sel.rcond,
-                     reinterpret_cast<const long long*>(d_counts), d_s);
+                     reinterpret_cast<const long long*>(d_counts), d_s, rv ? rv->d_rec : nullptr,
+                     rv ? rv->first_row : 0);
   SC_HIP(ctx, hipGetLastError());
   return SC_OK;
 }
@@ -275,8 +311,9 @@ int64_t batch_modes_nsel(const sc_mode_selection& sel, int64_t nvec) {
 }
 
 // weights (batch, n_sel) | msf: partial sums of one slab | dcc: P and S of one slab, diagonals (batch, N), records
+// (ragged: m is the slot order, the diagonals are packed over all atoms)
 size_t batch_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t nsel, int what,
-                                   size_t budget) {
+                                   size_t budget, const RaggedView* rv) {
   (void)nvec;
   if (budget == 0) budget = modes_budget_default();
   size_t bytes = align_up((size_t)batch * std::max<int64_t>(nsel, 1) * 8, 256);
@@ -285,27 +322,31 @@ size_t batch_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int d
     bytes += align_up((size_t)msf_slab(m, nsel, batch, budget) * ((nsel + chunk - 1) / chunk) * m * 8, 256);
   } else {
     const DccPlan pl = dcc_plan(m, nsel, batch, budget);
-    bytes += 2 * align_up((size_t)pl.slab * pl.stride * 8, 256) + align_up((size_t)batch * (m / dim) * 8, 256) +
+    const size_t diag = (size_t)(rv ? rv->total_atoms : batch * (m / dim));
+    bytes += 2 * align_up((size_t)pl.slab * pl.stride * 8, 256) + align_up(diag * 8, 256) +
              align_up((size_t)pl.slab * sizeof(GemmDesc), 256);
   }
   return bytes + 1024;
 }
 
 int batch_msf_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
-                     const sc_mode_selection& sel, const int64_t* d_counts, size_t budget, double* d_out) {
+                     const sc_mode_selection& sel, const int64_t* d_counts, size_t budget, double* d_out,
+                     const RaggedView* rv) {
   if (budget == 0) budget = modes_budget_default();
   hipStream_t st = ctx->stream;
   const int64_t nsel = batch_modes_nsel(sel, nvec);
-  const int64_t N = m / dim;
+  const int64_t N = rv ? rv->max_atoms : m / dim;   // (bounds the grid of the reduce)
+  const RaggedRec* rag = rv ? rv->d_rec : nullptr;
+  const int first_row = rv ? rv->first_row : 0;
   if (nsel == 0) {
-    SC_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)batch * N, st));
+    SC_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)(rv ? rv->total_atoms : batch * N), st));
     return SC_OK;
   }
-  SC_TRY(sc_reserve_modes(ctx, batch_modes_workspace_bytes(m, nvec, batch, dim, nsel, 0, budget)));
+  SC_TRY(sc_reserve_modes(ctx, batch_modes_workspace_bytes(m, nvec, batch, dim, nsel, 0, budget, rv)));
   char* base = (char*)ctx->modes_ws;
   double* d_s = reinterpret_cast<double*>(base);
   double* d_part = reinterpret_cast<double*>(base + align_up((size_t)batch * nsel * 8, 256));
-  SC_TRY(launch_weights(ctx, d_w, nvec, batch, sel, nsel, d_counts, d_s));
+  SC_TRY(launch_weights(ctx, d_w, nvec, batch, sel, nsel, d_counts, d_s, rv));
   const int chunk = msf_chunk(nsel);
   const int nchunk = (int)((nsel + chunk - 1) / chunk);
   const int64_t slab = msf_slab(m, nsel, batch, budget);
@@ -319,21 +360,23 @@ int batch_msf_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
     auto kern = vec ? (rows ? k_bmsf_partial<true, true> : k_bmsf_partial<true, false>)
                     : (rows ? k_bmsf_partial<false, true> : k_bmsf_partial<false, false>);
     hipLaunchKernelGGL(kern, grid, dim3(256), 0, st, d_v, d_s, rows, row0, (int)nsel, (int)nvec, (int)m, chunk, cnt,
-                       (int)b0, d_part);
+                       (int)b0, d_part, rag, first_row);
     hipLaunchKernelGGL(k_bmsf_reduce, dim3((unsigned)((N + 255) / 256), nb), dim3(256), 0, st, d_part, nchunk, (int)m,
-                       dim, (int)b0, d_out);
+                       dim, (int)b0, d_out, rag);
   }
   SC_HIP(ctx, hipGetLastError());
   return SC_OK;
 }
 
 int batch_dcc_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
-                     const sc_mode_selection& sel, const int64_t* d_counts, int norm, size_t budget, double* d_out) {
+                     const sc_mode_selection& sel, const int64_t* d_counts, int norm, size_t budget, double* d_out,
+                     const RaggedView* rv) {
   if (budget == 0) budget = modes_budget_default();
   hipStream_t st = ctx->stream;
   const int64_t nsel = batch_modes_nsel(sel, nvec);
-  const int N = (int)(m / dim);
-  SC_TRY(sc_reserve_modes(ctx, batch_modes_workspace_bytes(m, nvec, batch, dim, nsel, 1, budget)));
+  const int N = rv ? rv->max_atoms : (int)(m / dim);   // (ragged: bounds the grids; every kernel reads the structure's own)
+  const RaggedRec* rag = rv ? rv->d_rec : nullptr;
+  SC_TRY(sc_reserve_modes(ctx, batch_modes_workspace_bytes(m, nvec, batch, dim, nsel, 1, budget, rv)));
   const DccPlan pl = dcc_plan(m, nsel, batch, budget);
   char* base = (char*)ctx->modes_ws;
   size_t off = 0;
@@ -341,12 +384,12 @@ int batch_dcc_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
   double* d_s = reinterpret_cast<double*>(take((size_t)batch * std::max<int64_t>(nsel, 1) * 8));
   double* d_p = reinterpret_cast<double*>(take((size_t)pl.slab * pl.stride * 8));
   double* d_sp = reinterpret_cast<double*>(take((size_t)pl.slab * pl.stride * 8));
-  double* d_diag = reinterpret_cast<double*>(take((size_t)batch * N * 8));
+  double* d_diag = reinterpret_cast<double*>(take((size_t)(rv ? rv->total_atoms : batch * (int64_t)N) * 8));
   GemmDesc* d_desc = reinterpret_cast<GemmDesc*>(take((size_t)pl.slab * sizeof(GemmDesc)));
   if (nsel == 0) {
-    SC_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)batch * N * N, st));
+    SC_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(double) * (rv ? (size_t)rv->total_sq : (size_t)batch * N * N), st));
   } else {
-    SC_TRY(launch_weights(ctx, d_w, nvec, batch, sel, nsel, d_counts, d_s));
+    SC_TRY(launch_weights(ctx, d_w, nvec, batch, sel, nsel, d_counts, d_s, rv));
     const int* rows = sel.kind == SC_SEL_ROWS ? sel.d_rows : nullptr;
     const int row0 = sel.kind == SC_SEL_FROM_ROW ? (int)sel.row0 : 0;
     // one block tile for every launch of this call, the short last slab included: a structure rounds the same way in
@@ -358,9 +401,10 @@ int batch_dcc_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
         const int kc = (int)std::min(pl.kc, nsel - k0);
         hipLaunchKernelGGL(k_bdcc_pack, dim3((unsigned)std::min<int64_t>((m + 255) / 256, 64), (unsigned)kc, (unsigned)nb),
                            dim3(256), 0, st, d_v, d_s, rows, row0, (int)nsel, (int)nvec, (int)m, dim, (int)k0, kc,
-                           (int)b0, pl.stride, d_p, d_sp);
+                           (int)b0, pl.stride, d_p, d_sp, rag);
         hipLaunchKernelGGL(k_bdcc_descs, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, st, d_desc, nb, d_sp, d_p,
-                           pl.stride, d_out + (size_t)b0 * N * N, N, kc * dim, k0 == 0 ? 0.0 : 1.0);
+                           pl.stride, rag ? d_out : d_out + (size_t)b0 * N * N, N, kc * dim, k0 == 0 ? 0.0 : 1.0, rag,
+                           (int)b0);
         SC_HIP(ctx, hipGetLastError());
         SC_TRY(launch_gemm_f64(ctx, d_desc, nb, N, N, kGemmTile, 1, false, false, kGemmAmBn, false, pin));
       }
@@ -369,10 +413,11 @@ int batch_dcc_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
   if (norm) {
     for (int64_t b0 = 0; b0 < batch; b0 += kMaxSlab) {
       const unsigned nb = (unsigned)std::min(kMaxSlab, batch - b0);
-      double* c = d_out + (size_t)b0 * N * N;
-      hipLaunchKernelGGL(k_bcopy_diag, dim3((unsigned)((N + 255) / 256), nb), dim3(256), 0, st, c, N, d_diag + (size_t)b0 * N);
-      hipLaunchKernelGGL(k_bdcc_norm, dim3((unsigned)((N + 255) / 256), (unsigned)N, nb), dim3(256), 0, st, c,
-                         d_diag + (size_t)b0 * N, N);
+      double* c = rag ? d_out : d_out + (size_t)b0 * N * N;
+      double* dg = rag ? d_diag : d_diag + (size_t)b0 * N;
+      hipLaunchKernelGGL(k_bcopy_diag, dim3((unsigned)((N + 255) / 256), nb), dim3(256), 0, st, c, N, dg, rag, (int)b0);
+      hipLaunchKernelGGL(k_bdcc_norm, dim3((unsigned)((N + 255) / 256), (unsigned)N, nb), dim3(256), 0, st, c, dg, N, rag,
+                         (int)b0);
     }
     SC_HIP(ctx, hipGetLastError());
   }

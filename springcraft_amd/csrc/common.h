@@ -262,6 +262,8 @@ int launch_items_from_pairs(sc_ctx* ctx, int dim, const void* d_items, int64_t c
 // LOWER triangle in column-major order, i.e. the UPPER triangle of the row-major matrix the
 // assembly writes; the matrices are symmetric so both views agree.
 
+struct RaggedRec;   // (ragged batches, below)
+
 // ---- eigensolver (eigh.hip and friends) ----------------------------------------------------
 // d_a: (batch, n, n) symmetric (destroyed), d_w: (batch, n), d_v: nullptr or (batch, n, n) rows = modes.
 // eigh_batched synchronises the stream and returns this solve's errors (host-pointer entry points); the _async form only
@@ -277,8 +279,10 @@ int eigh_range_batched_async(sc_ctx* ctx, double* d_a, int64_t n, int64_t batch,
 // Eigenvalue window (vl, vu] (scipy's subset_by_value): K slots per matrix, d_w (batch, K), d_v nullptr or (batch, K, n),
 // d_count (batch) int64 true counts (may be nullptr); a slot holds the window's first min(count, K) eigenpairs, then NaN /
 // zero rows.  Only enqueues.
+// d_own: null, or one record per matrix: only the first own eigenvalues of matrix b count and its slot starts at
+// min(il, own - K) (padded slots of a ragged batch).
 int eigh_window_batched_async(sc_ctx* ctx, double* d_a, int64_t n, int64_t batch, double vl, double vu, int64_t K,
-                              double* d_w, double* d_v, int64_t* d_count);
+                              double* d_w, double* d_v, int64_t* d_count, const RaggedRec* d_own = nullptr);
 // One matrix, synchronising: *m eigenpairs of the window into ctx->win_ws (*d_w (m), *d_v (m, n) or nullptr).
 int eigh_window(sc_ctx* ctx, double* d_a, int64_t n, double vl, double vu, bool vectors, int64_t* m, double** d_w,
                 double** d_v);
@@ -297,15 +301,31 @@ int modes_prs_device(sc_ctx* ctx, const double* d_v, const double* d_w, int64_t 
 
 // ---- the same quantities for a batch, on the solver's own (w, v, counts) tensors (batch_consumers.hip) ----------
 // what: 0 = msf, 1 = dcc.  n_sel: weighted rows per structure (batch_modes_nsel).  budget: bytes the partial sums (msf) /
-// the packed GEMM operands (dcc) may take, 0 = modes_budget_default().
+// the packed GEMM operands (dcc) may take, 0 = modes_budget_default().  ragged: null for a uniform batch (d_out (batch,
+// m / dim[, m / dim])), or the plan's records: m is then the slot order and d_out is packed.
+// Ragged batches (sc_batch_plan): one record per structure in the plan's device blob, read by the window count and the
+// consumers.  own = dim * n_atoms rows / columns of the slot are the structure's, the rest is padding; atom_off / sq_off
+// are the structure's places in packed (sum n) and (sum n^2) outputs.
+struct RaggedRec {
+  int own, n_atoms;
+  long long atom_off, sq_off;
+};
+// d_rec: device records; first_row: global mode index of row 0 of (w, v) (lo of an index-range solve, else 0)
+struct RaggedView {
+  const RaggedRec* d_rec;
+  int first_row, max_atoms;
+  int64_t total_atoms, total_sq;
+};
 size_t modes_budget_default();
 int64_t batch_modes_nsel(const sc_mode_selection& sel, int64_t nvec);
 size_t batch_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
-                                   size_t budget);
+                                   size_t budget, const RaggedView* ragged = nullptr);
 int batch_msf_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
-                     const sc_mode_selection& sel, const int64_t* d_counts, size_t budget, double* d_out);
+                     const sc_mode_selection& sel, const int64_t* d_counts, size_t budget, double* d_out,
+                     const RaggedView* ragged = nullptr);
 int batch_dcc_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
-                     const sc_mode_selection& sel, const int64_t* d_counts, int norm, size_t budget, double* d_out);
+                     const sc_mode_selection& sel, const int64_t* d_counts, int norm, size_t budget, double* d_out,
+                     const RaggedView* ragged = nullptr);
 
 // Raises a kernel's dynamic LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) once per (device, kernel).  The
 // attribute belongs to the device that is current when it is set: a function-local static done-flag (rounds 2-5) served

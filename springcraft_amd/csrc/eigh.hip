@@ -497,6 +497,7 @@ int partial_eigenpairs(sc_ctx* ctx, double* d_a, int n, int batch, const Partial
 struct ValueWindow {
   double vl, vu;
   long long* d_count;
+  const RaggedRec* d_own;   // null, or the own orders of padded slots
 };
 
 int partial_batched_async(sc_ctx* ctx, double* d_a, int n, int batch, int il, int m, const ValueWindow* window,
@@ -510,7 +511,7 @@ int partial_batched_async(sc_ctx* ctx, double* d_a, int n, int batch, int il, in
   if (window) {
     d_win = (WinCount*)(base + P.off_win);
     SC_TRY(window_count_batched(ctx, batch, (const double*)(base + P.off_tri), P.TL, window->vl, window->vu, m, d_win,
-                                window->d_count));
+                                window->d_count, window->d_own));
   }
   SC_TRY(partial_eigenpairs(ctx, d_a, n, batch, P, base, il, m, d_win, d_w, d_v, (double*)(base + P.off_stein), prof));
   if (window)   // (the VT buffer of the back-transformation is free again: the copy of v goes there)
@@ -546,12 +547,12 @@ int eigh_range_batched(sc_ctx* ctx, double* d_a, int64_t n, int64_t batch, int64
 }
 
 int eigh_window_batched_async(sc_ctx* ctx, double* d_a, int64_t n64, int64_t batch64, double vl, double vu, int64_t K64,
-                              double* d_w, double* d_v, int64_t* d_count) {
+                              double* d_w, double* d_v, int64_t* d_count, const RaggedRec* d_own) {
   if (n64 > 46000) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "matrix order %lld too large", (long long)n64);
   SC_TRY(check_window(ctx, vl, vu));
   if (K64 < 1 || K64 > n64)
     return sc_set_error(ctx, SC_ERR_INVALID_ARG, "window capacity %lld outside 1..%lld", (long long)K64, (long long)n64);
-  const ValueWindow window{vl, vu, (long long*)d_count};
+  const ValueWindow window{vl, vu, (long long*)d_count, d_own};
   return partial_batched_async(ctx, d_a, (int)n64, (int)batch64, 0, (int)K64, &window, d_w, d_v);
 }
 

@@ -157,9 +157,10 @@ size_t stein_workspace_doubles(int n, int m);
 int stein_batched(sc_ctx* ctx, int n, int batch, const double* d_tri_ws, const TriLayout& TL, int il, int iu,
                   double* d_w, long long stride_w, double* d_x, long long stride_x, double* d_ws,
                   GemmDesc* d_descs /* 2 * batch */, const WinCount* d_win = nullptr);
-// d_win[b] (and d_count[b] = count unless null) for every matrix of the tridiagonalised batch; 1 <= K <= n
+// d_win[b] (and d_count[b] = count unless null) for every matrix of the tridiagonalised batch; 1 <= K <= n.
+// d_own: null, or per matrix the number of leading eigenvalues that are its own (1 <= K <= own <= n): the rest never count
 int window_count_batched(sc_ctx* ctx, int batch, const double* d_tri_ws, const TriLayout& TL, double vl, double vu, int K,
-                         WinCount* d_win, long long* d_count);
+                         WinCount* d_win, long long* d_count, const RaggedRec* d_own = nullptr);
 // The window's rows of every slot of d_w (batch, K) / d_v (null or (batch, K, n)) to the front, NaN / zero rows behind;
 // d_w_copy (batch K) and d_v_copy (batch K n) are scratch
 int window_compact_batched(sc_ctx* ctx, int n, int batch, int K, const WinCount* d_win, double* d_w, double* d_v,

@@ -215,9 +215,12 @@ __global__ __launch_bounds__(64) void k_sturm_range(const double* __restrict__ t
 // matrix; lane 0 counts at vl, lane 1 at vu.  #(lambda <= x) is the count below the next double above x; shifts outside the
 // padded Gershgorin interval (the infinities, and finite bounds that the factor f pushed beyond the doubles) are resolved
 // to 0 / n without the recurrence.  A matrix with a NaN / Inf entry (solved as the zero matrix) gets il = count = 0.
+// own: null, or per matrix the order of its own leading block -- a padded slot diag(M, D) whose pad eigenvalues lie above
+// M's: only the first own[b].own eigenvalues count, count = min(count, own - il), start = min(il, own - K).
 __global__ __launch_bounds__(64) void k_window_count(const double* __restrict__ tri_all, TriLayout TL, double vl,
                                                      double vu, int K, WinCount* __restrict__ win,
-                                                     long long* __restrict__ count_out) {
+                                                     long long* __restrict__ count_out,
+                                                     const RaggedRec* __restrict__ own) {
   const double* tri = tri_all + (size_t)blockIdx.x * TL.slab;
   const double* d = tri + TL.d;
   const double* e = tri + TL.e;
@@ -245,9 +248,10 @@ __global__ __launch_bounds__(64) void k_window_count(const double* __restrict__ 
   }
   const int cnt_vu = __shfl(cnt, 1);
   if (lane == 0) {
+    const int n_own = own ? own[blockIdx.x].own : n;
     const int il = bad ? 0 : cnt;
-    const int count = bad ? 0 : max(cnt_vu - cnt, 0);
-    win[blockIdx.x] = WinCount{il, count, min(il, n - K), 0};
+    const int count = bad ? 0 : max(min(cnt_vu - cnt, n_own - il), 0);
+    win[blockIdx.x] = WinCount{il, count, min(il, n_own - K), 0};
     if (count_out) count_out[blockIdx.x] = count;
   }
 }
@@ -558,9 +562,9 @@ int stein_batched(sc_ctx* ctx, int n, int batch, const double* d_tri_ws, const T
 
 
 int window_count_batched(sc_ctx* ctx, int batch, const double* d_tri_ws, const TriLayout& TL, double vl, double vu, int K,
-                         WinCount* d_win, long long* d_count) {
+                         WinCount* d_win, long long* d_count, const RaggedRec* d_own) {
   hipLaunchKernelGGL(k_window_count, dim3((unsigned)batch), dim3(64), 0, ctx->stream, d_tri_ws, TL, vl, vu, K, d_win,
-                     d_count);
+                     d_count, d_own);
   SC_HIP(ctx, hipGetLastError());
   return SC_OK;
 }
