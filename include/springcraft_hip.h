@@ -361,6 +361,11 @@ int64_t sc_modes_order(const sc_modes* modes);
 int sc_modes_get(sc_modes* modes, double* w, double* v);
 /* out (n / dim): sum over the k listed modes of v^2 / w, summed over the dim components of every atom. */
 int sc_modes_msf(sc_modes* modes, const int64_t* mode_idx, int64_t k, double* out);
+/* ANM only (a dim-1 object: SC_ERR_INVALID_ARG).  out (n / 3, 6): per atom the 3 x 3 tensor sum over the k listed modes
+ * of v_a v_a^T / w -- the diagonal blocks of the covariance over those modes, the anisotropic displacement parameters --
+ * as its six distinct entries in the order of a PDB ANISOU record: xx yy zz xy xz yz.  xx + yy + zz is sc_modes_msf's
+ * value.  Computed by the batch kernels below with a batch of one. */
+int sc_modes_aniso(sc_modes* modes, const int64_t* mode_idx, int64_t k, double* out);
 /* out (n / dim, n / dim): sum over the listed modes of <v_a, v_b> / w; norm != 0 divides by sqrt(c_aa c_bb). */
 int sc_modes_dcc(sc_modes* modes, const int64_t* mode_idx, int64_t k, int norm, double* out);
 /* ANM only. out (n / 3, n / 3) row-major: sums of the squared 3x3 blocks of pinv(H, rcond) (numpy hermitian
@@ -375,6 +380,7 @@ int sc_modes_prs(sc_modes* modes, double rcond, int norm, double* out);
  *
  *   msf[b, a]    = sum_r  s[b, r] * sum_d V[b, r, dim a + d]^2
  *   dcc[b, a, c] = sum_r  s[b, r] * sum_d V[b, r, dim a + d] V[b, r, dim c + d]
+ *   U[b, a, d, e] = sum_r  s[b, r] * V[b, r, 3 a + d] V[b, r, 3 a + e]      (dim 3 only: anisotropic fluctuation tensors)
  *
  * with s[b, r] = 1 / w[b, r] for a selected row r and exactly 0 for every other one: a row without weight contributes
  * nothing, whatever it holds (the NaN / zero padding of a window solve).  The selection names ROWS of d_w / d_v, not
@@ -412,9 +418,18 @@ int sc_dev_modes_msf_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int6
 int sc_dev_modes_dcc_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
                          int dim, const sc_mode_selection* sel, const int64_t* d_counts, int norm, int64_t budget_bytes,
                          double* d_out);
-/* Bytes of device workspace the two entries above hold for such a call (allocated lazily, cached, grown on demand --
+/* ANM only: m % 3 == 0 is required (SC_ERR_INVALID_ARG otherwise).  d_out (batch, m / 3, 6): per atom the six distinct
+ * entries of the symmetric 3 x 3 tensor U above in the order of a PDB ANISOU record, xx yy zz xy xz yz; its trace is the
+ * msf of the same selection.  No reference counterpart: these are the diagonal 3 x 3 blocks of the covariance
+ * (anm.py:114-117) restricted to the selected modes, without forming it.  One pass over the selected rows of d_v, the
+ * rows split in chunks by their number alone and the chunks added in a fixed order: a structure's result does not depend
+ * on the batch size or on its position in the batch, bit for bit.  Enqueue only. */
+int sc_dev_modes_aniso_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                           const sc_mode_selection* sel, const int64_t* d_counts, double* d_out);
+/* Bytes of device workspace the three entries above hold for such a call (allocated lazily, cached, grown on demand --
  * the one step of a first call that waits for the stream).  n_sel: rows that carry a weight (nvec - row0, n_rows, or
- * nvec for SC_SEL_PINV); what: 0 = msf, 1 = dcc; budget_bytes as above. */
+ * nvec for SC_SEL_PINV); what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3 and m % 3 == 0, else 0); budget_bytes as
+ * above. */
 int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
                                      int64_t budget_bytes);
 
@@ -448,6 +463,11 @@ int sc_batch_plan_modes_msf_f64(sc_batch_plan* plan, const double* d_w, const do
 int sc_batch_plan_modes_dcc_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
                                 const sc_mode_selection* sel, const int64_t* d_counts, int norm, int64_t budget_bytes,
                                 double* d_out);
+/* anisotropic tensors (a plan of dim 1: SC_ERR_INVALID_ARG): d_out (sum n_atoms, 6) packed, structure b's six values per
+ * atom (xx yy zz xy xz yz, as sc_dev_modes_aniso_f64) at 6 times its atom offset.  A structure's bits depend on the slot
+ * order and the selection, not on its neighbours or its position. */
+int sc_batch_plan_modes_aniso_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
+                                  const sc_mode_selection* sel, const int64_t* d_counts, double* d_out);
 /* What sc_dev_modes_workspace_bytes answers for a uniform batch, for the plan's (count, order). */
 int64_t sc_batch_plan_modes_workspace_bytes(const sc_batch_plan* plan, int64_t nvec, int64_t n_sel, int what,
                                             int64_t budget_bytes);

@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "sc_dev_modes_msf_f64", "sc_dev_modes_dcc_f64", "sc_dev_modes_workspace_bytes",
     "sc_batch_plan_eigh_range_f64", "sc_batch_plan_eigh_window_f64", "sc_batch_plan_modes_msf_f64",
     "sc_batch_plan_modes_dcc_f64", "sc_batch_plan_modes_workspace_bytes",
+    "sc_modes_aniso", "sc_dev_modes_aniso_f64", "sc_batch_plan_modes_aniso_f64",
 ]
 
 SC_SEL_FROM_ROW = 0
@@ -216,13 +217,16 @@ def lib():
         "sc_modes_msf": (i32, [vp, vp, i64, vp]),
         "sc_modes_dcc": (i32, [vp, vp, i64, i32, vp]),
         "sc_modes_prs": (i32, [vp, dbl, i32, vp]),
+        "sc_modes_aniso": (i32, [vp, vp, i64, vp]),
         "sc_dev_modes_msf_f64": (i32, [vp, vp, vp, i64, i64, i64, i32, P(ModeSelection), vp, vp]),
         "sc_dev_modes_dcc_f64": (i32, [vp, vp, vp, i64, i64, i64, i32, P(ModeSelection), vp, i32, i64, vp]),
+        "sc_dev_modes_aniso_f64": (i32, [vp, vp, vp, i64, i64, i64, P(ModeSelection), vp, vp]),
         "sc_dev_modes_workspace_bytes": (i64, [i64, i64, i64, i32, i64, i32, i64]),
         "sc_batch_plan_eigh_range_f64": (i32, [vp, vp, i64, i64, vp, vp]),
         "sc_batch_plan_eigh_window_f64": (i32, [vp, vp, dbl, dbl, i64, vp, vp, vp]),
         "sc_batch_plan_modes_msf_f64": (i32, [vp, vp, vp, i64, P(ModeSelection), vp, vp]),
         "sc_batch_plan_modes_dcc_f64": (i32, [vp, vp, vp, i64, P(ModeSelection), vp, i32, i64, vp]),
+        "sc_batch_plan_modes_aniso_f64": (i32, [vp, vp, vp, i64, P(ModeSelection), vp, vp]),
         "sc_batch_plan_modes_workspace_bytes": (i64, [vp, i64, i64, i32, i64]),
     }
     for name, (res, args) in sig.items():
@@ -321,7 +325,7 @@ class Context:
 class Modes:
     """
     Owns one ``sc_modes``: all eigenpairs of a model, resident in device memory, plus the consumers that
-    work on them there (msf, dcc, prs).  ``dim`` is 1 for a GNM and 3 for an ANM.
+    work on them there (msf, dcc, prs, anisotropic tensors).  ``dim`` is 1 for a GNM and 3 for an ANM.
     """
 
     def __init__(self, ctx, handle, dim):
@@ -374,6 +378,13 @@ class Modes:
         n = self.order // self.dim
         out = host_array((n, n))
         self._ctx.check(self._L.sc_modes_dcc(self._h, ptr(idx), len(idx), int(bool(norm)), ptr(out)))
+        return out
+
+    def aniso(self, mode_idx):
+        """(n_atoms, 6): the six distinct entries of every atom's fluctuation tensor, xx yy zz xy xz yz (ANM only)."""
+        idx = self._index_list(mode_idx)
+        out = np.empty((self.order // 3, 6))
+        self._ctx.check(self._L.sc_modes_aniso(self._h, ptr(idx), len(idx), ptr(out)))
         return out
 
     def prs(self, rcond, norm):

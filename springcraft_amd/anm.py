@@ -85,6 +85,10 @@ class ANM(ElasticNetworkModel):
         """Dynamic cross-correlation (n,n) between nodes (anm.py:323-382)."""
         return nma.dcc(self, mode_subset, norm, tem, tem_factors)
 
+    def anisotropic_fluctuation(self, mode_subset=None, tem=None, tem_factors=K_B):
+        """Per-atom 3x3 fluctuation tensors (n,3,3) whose trace is the MSF (:func:`nma.anisotropic_fluctuation`)."""
+        return nma.anisotropic_fluctuation(self, mode_subset, tem, tem_factors)
+
     def prs_effector_sensor(self, norm=True):
         """PRS matrix plus effector / sensor profiles (anm.py:384-445)."""
         prs_mat = nma.prs(self, norm)

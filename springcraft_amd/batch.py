@@ -113,6 +113,17 @@ def ragged_subset_plan(sizes, dim, subset_by_index=None, subset_by_value=None, m
     return plan
 
 
+def _aniso_expand(solver, packed):
+    """(..., 6) device tensor in ANISOU order -> (..., 3, 3): an index gather on the solver's device, enqueue only."""
+    if getattr(solver, "_aniso_index", None) is None:
+        from .nma import ANISOU_INDEX
+
+        # (once per solver, through page-locked memory: later calls find the nine indices on the device)
+        host = solver.torch.from_numpy(ANISOU_INDEX.reshape(-1).astype(np.int64)).pin_memory()
+        solver._aniso_index = host.to(solver.device, non_blocking=True)
+    return packed.index_select(-1, solver._aniso_index).view(*packed.shape[:-1], 3, 3)
+
+
 class DeviceBatchSolver:
     """
     ANM (dim=3) or GNM (dim=1) eigensolves for a batch of equally sized structures whose
@@ -323,6 +334,28 @@ class DeviceBatchSolver:
         out *= (8 * np.pi**2) / 3
         return out
 
+    def _aniso_packed(self, mode_subset=None, tem=None, tem_factors=K_B):
+        """(batch, n_atoms, 6): every tensor's six distinct entries xx yy zz xy xz yz, as the kernel leaves them."""
+        if self.dim != 3:
+            raise ValueError("anisotropic fluctuation tensors need an ANM solver (dim=3)")
+        sel, counts, keep = self._selection(mode_subset, pinv_default=False)
+        out = self.torch.empty((self.batch, self.n_atoms, 6), dtype=self.torch.float64, device=self.device)
+        self.ctx.check(self._L.sc_dev_modes_aniso_f64(
+            self.ctx.handle, C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr()), self.m, self.w.shape[1],
+            self.batch, C.byref(sel), counts, C.c_void_p(out.data_ptr())))
+        if tem is not None:
+            out *= tem * tem_factors
+        return out
+
+    def anisotropic_fluctuation(self, mode_subset=None, tem=None, tem_factors=K_B):
+        """
+        (batch, n_atoms, 3, 3) anisotropic fluctuation tensors ``sum_k v_k[a] v_k[a]^T / lambda_k`` over the selected
+        modes (:func:`nma.anisotropic_fluctuation`): symmetric, and their traces are :meth:`mean_square_fluctuation` of
+        the same selection, whose ``mode_subset``, window and failed-structure rules apply unchanged.  One pass over the
+        selected rows of ``v``; ANM solvers only (``dim != 3`` raises ValueError before anything is enqueued).
+        """
+        return _aniso_expand(self, self._aniso_packed(mode_subset, tem, tem_factors))
+
     def dcc(self, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
         """
         (batch, n_atoms, n_atoms) dynamic cross-correlations over the selected modes (nma.py:233-359); ``norm`` divides by
@@ -382,9 +415,9 @@ class RaggedBatchSolver:
     ``results()`` cuts ``v_i`` to the structure's own ``dim * n_i`` columns and, behind a window solve, both to the first
     ``min(counts[i], K)`` rows.
 
-    :meth:`frequencies`, :meth:`mean_square_fluctuation`, :meth:`bfactor` and :meth:`dcc` have the meaning, defaults and
-    trivial-mode rules of :class:`DeviceBatchSolver`'s, per structure: they only enqueue and return a list of CUDA tensors,
-    (n_i,) / (n_i, n_i), views into one packed buffer.  Pad rows and columns are never read into a result, and the
+    :meth:`frequencies`, :meth:`mean_square_fluctuation`, :meth:`bfactor`, :meth:`dcc` and :meth:`anisotropic_fluctuation`
+    have the meaning, defaults and trivial-mode rules of :class:`DeviceBatchSolver`'s, per structure: they only enqueue and
+    return a list of CUDA tensors, (n_i,) / (n_i, n_i) / (n_i, 3, 3), views into one packed buffer.  Pad rows and columns are never read into a result, and the
     ``|lambda| > 1e-6 max|lambda|`` rule of the dcc default takes its maximum over the structure's own eigenvalues.
     """
 
@@ -624,6 +657,27 @@ class RaggedBatchSolver:
         for o in out:
             o *= (8 * np.pi**2) / 3
         return out
+
+    def _aniso_packed(self, mode_subset=None, tem=None, tem_factors=K_B):
+        """(sum(sizes), 6): every tensor's six distinct entries xx yy zz xy xz yz, the structures back to back."""
+        if self.dim != 3:
+            raise ValueError("anisotropic fluctuation tensors need an ANM solver (dim=3)")
+        sel, counts = self._selection(mode_subset, pinv_default=False)
+        out = self.torch.empty((int(self.offsets[-1]), 6), dtype=self.torch.float64, device=self.device)
+        self.ctx.check(self._L.sc_batch_plan_modes_aniso_f64(
+            self._plan, C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr()), self.w.shape[1], C.byref(sel),
+            counts, C.c_void_p(out.data_ptr())))
+        if tem is not None:
+            out *= tem * tem_factors
+        return out
+
+    def anisotropic_fluctuation(self, mode_subset=None, tem=None, tem_factors=K_B):
+        """
+        [(n_i, 3, 3), ...] anisotropic fluctuation tensors, as :meth:`DeviceBatchSolver.anisotropic_fluctuation`, with the
+        selection of :meth:`mean_square_fluctuation`: views into one packed tensor.  ANM solvers only.
+        """
+        out = _aniso_expand(self, self._aniso_packed(mode_subset, tem, tem_factors))
+        return [out[self.offsets[b]: self.offsets[b + 1]] for b in range(self.batch)]
 
     def dcc(self, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
         """

@@ -9,6 +9,7 @@
 //
 //   msf[b, a]    = sum_r  s[b, r] * sum_d V[b, r, dim a + d]^2
 //   dcc[b, a, c] = sum_r  s[b, r] * sum_d V[b, r, dim a + d] V[b, r, dim c + d]
+//   U[b, a, d, e] = sum_r  s[b, r] * V[b, r, 3 a + d] V[b, r, 3 a + e]        (ANM: the anisotropic fluctuation tensors)
 //
 // A row without weight is never multiplied in (the kernels select, they do not multiply by zero), so the NaN / zero
 // padding behind a window's rows cannot reach a result.  No atomics: every sum is a fixed sequence.
@@ -16,7 +17,8 @@
 // Ragged batches (sc_batch_plan): every kernel takes an optional table of RaggedRec, one per structure.  Without it the
 // batch is uniform and nothing differs from the above.  With it m is the common slot order, structure b owns the first
 // rag[b].own rows and columns of its slot -- pad rows never carry a weight, pad columns are never packed or summed -- and
-// the results go to packed buffers at rag[b].atom_off (msf, diagonals) and rag[b].sq_off (dcc).
+// the results go to packed buffers at rag[b].atom_off (msf, diagonals; six values per atom for the tensors) and
+// rag[b].sq_off (dcc).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -173,6 +175,86 @@ __global__ __launch_bounds__(256) void k_bmsf_reduce(const double* __restrict__ 
 // 3840 workgroups), 6000 rows -> 48 chunks of 125 (36864 workgroups, partial sums 1.6 % of the bytes read).
 int msf_chunk(int64_t nsel) { return (int)std::min<int64_t>(128, std::max<int64_t>(4, (nsel + 47) / 48)); }
 
+// ---- anisotropic fluctuation tensors (ANM, dim 3) ----------------------------------------------------------------
+// The 3 x 3 diagonal blocks of the covariance over the selected modes, what crystallography records as ANISOU: six
+// values per atom in that record's order, e = xx yy zz xy xz yz; xx + yy + zz is the msf of the same selection.
+//   part[bz, c, e, a] = sum over the listed rows kk of chunk c, in order, of s[b, kk] V[b, row(kk), 3a + d] V[.., 3a + d']
+// grid (atom tiles of 256, chunks, structures of the slab); one lane per ATOM: it loads the atom's three consecutive
+// doubles of every listed row (rows are only 8-byte aligned for odd N, so three 8-byte pieces; a wavefront takes 1536
+// contiguous bytes of the row) and keeps the six sums.  The same rows are read exactly once, as k_bmsf_partial reads
+// them, and the chunks are msf_chunk's: a structure's bits are the same in any batch.  The partial sums are stored
+// component-major (`na` atoms per component: m / 3) so that lanes store, and k_baniso_reduce loads, side by side.
+// U listed rows from kk on: all row numbers and weights first, then all loads, then the sums in row order
+template <bool LIST, int U>
+__device__ __forceinline__ void aniso_rows(const double* __restrict__ vb, const double* __restrict__ sb,
+                                           const int* __restrict__ rows, int row0, int kk, int nvec, int m, int j0,
+                                           double (&acc)[6]) {
+  double sv[U], x[U], y[U], z[U];
+  const double* p[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    sv[u] = sb[kk + u];
+    p[u] = vb + (size_t)listed_row(LIST ? rows : nullptr, row0, kk + u, nvec) * m + j0;
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    x[u] = p[u][0]; y[u] = p[u][1]; z[u] = p[u][2];
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const double sx = sv[u] * x[u], sy = sv[u] * y[u], sz = sv[u] * z[u];
+    const double t[6] = {fma(sx, x[u], acc[0]), fma(sy, y[u], acc[1]), fma(sz, z[u], acc[2]),
+                         fma(sx, y[u], acc[3]), fma(sx, z[u], acc[4]), fma(sy, z[u], acc[5])};
+#pragma unroll
+    for (int e = 0; e < 6; ++e) acc[e] = sv[u] != 0.0 ? t[e] : acc[e];
+  }
+}
+
+template <bool LIST>
+__global__ __launch_bounds__(256) void k_baniso_partial(const double* __restrict__ v, const double* __restrict__ s,
+                                                        const int* __restrict__ rows, int row0, int nsel, int nvec, int m,
+                                                        int chunk, const long long* __restrict__ counts, int b0,
+                                                        double* __restrict__ part, const RaggedRec* __restrict__ rag,
+                                                        int first_row) {
+  const int b = b0 + blockIdx.z;
+  const int c = blockIdx.y;
+  const int na = m / 3;
+  // ragged: the structure's own atoms; a tile wholly behind them returns before its first load
+  const int N = rag ? rag[b].n_atoms : na;
+  const int a = blockIdx.x * 256 + threadIdx.x;
+  if (a >= N) return;
+  const int k0 = c * chunk;
+  int k1 = min(k0 + chunk, nsel);
+  // without a list the rows ascend: those behind the window's count (and a slot's pad rows) are not even read
+  if (!LIST) k1 = min(k1, rows_limit(counts, b, nvec, rag, first_row) - row0);
+  const double* vb = v + (size_t)b * nvec * m;
+  const double* sb = s + (size_t)b * nsel;
+  double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  int kk = k0;
+  for (; kk + 4 <= k1; kk += 4) aniso_rows<LIST, 4>(vb, sb, rows, row0, kk, nvec, m, 3 * a, acc);
+  for (; kk < k1; ++kk) aniso_rows<LIST, 1>(vb, sb, rows, row0, kk, nvec, m, 3 * a, acc);
+  double* pp = part + ((size_t)blockIdx.z * gridDim.y + c) * 6 * na + a;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) pp[(size_t)e * na] = acc[e];
+}
+
+// out[b, a, e] = sum over the chunks in their order (ragged: the structure's n_atoms, at 6 times its packed atom offset)
+__global__ __launch_bounds__(256) void k_baniso_reduce(const double* __restrict__ part, int nchunk, int na, int b0,
+                                                       double* __restrict__ out, const RaggedRec* __restrict__ rag) {
+  const int b = b0 + blockIdx.y;
+  const int N = rag ? rag[b].n_atoms : na;
+  const int a = blockIdx.x * 256 + threadIdx.x;
+  if (a >= N) return;
+  const double* pb = part + (size_t)blockIdx.y * nchunk * 6 * na + a;
+  double* o = out + ((rag ? (size_t)rag[b].atom_off : (size_t)b * N) + a) * 6;
+#pragma unroll
+  for (int e = 0; e < 6; ++e) {
+    double acc = 0.0;
+    for (int c = 0; c < nchunk; ++c) acc += pb[((size_t)c * 6 + e) * na];
+    o[e] = acc;
+  }
+}
+
 // ---- dcc ---------------------------------------------------------------------------------------------------------
 // Listed rows k0 .. k0 + kc - 1 of every structure of the slab, component-major, so that the contraction over (row,
 // component) is one GEMM per structure (k_dcc_pack of consumers.hip, batched and weighted):
@@ -280,6 +362,13 @@ int64_t msf_slab(int64_t m, int64_t nsel, int64_t batch, size_t budget) {
   return std::min(slab, std::max<int64_t>(batch, 1));
 }
 
+// six partial sums per atom and chunk where the msf keeps three
+int64_t aniso_slab(int64_t m, int64_t nsel, int64_t batch, size_t budget) {
+  const size_t per = (size_t)((nsel + msf_chunk(nsel) - 1) / msf_chunk(nsel)) * 6 * (m / 3) * 8;
+  const int64_t slab = std::min<int64_t>(kMaxSlab, (int64_t)std::max<size_t>(1, budget / std::max<size_t>(per, 1)));
+  return std::min(slab, std::max<int64_t>(batch, 1));
+}
+
 int launch_weights(sc_ctx* ctx, const double* d_w, int64_t nvec, int64_t batch, const sc_mode_selection& sel,
                    int64_t nsel, const int64_t* d_counts, double* d_s, const RaggedView* rv) {
   hipLaunchKernelGGL(k_mode_weights, dim3((unsigned)batch), dim3(256), 0, ctx->stream, d_w, (int)nvec,
@@ -310,7 +399,7 @@ int64_t batch_modes_nsel(const sc_mode_selection& sel, int64_t nvec) {
   }
 }
 
-// weights (batch, n_sel) | msf: partial sums of one slab | dcc: P and S of one slab, diagonals (batch, N), records
+// weights (batch, n_sel) | msf, tensors: partial sums of one slab | dcc: P and S of one slab, diagonals (batch, N), records
 // (ragged: m is the slot order, the diagonals are packed over all atoms)
 size_t batch_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t nsel, int what,
                                    size_t budget, const RaggedView* rv) {
@@ -320,6 +409,9 @@ size_t batch_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int d
   if (what == 0) {
     const int chunk = msf_chunk(nsel);
     bytes += align_up((size_t)msf_slab(m, nsel, batch, budget) * ((nsel + chunk - 1) / chunk) * m * 8, 256);
+  } else if (what == 2) {
+    const int chunk = msf_chunk(nsel);
+    bytes += align_up((size_t)aniso_slab(m, nsel, batch, budget) * ((nsel + chunk - 1) / chunk) * 6 * (m / 3) * 8, 256);
   } else {
     const DccPlan pl = dcc_plan(m, nsel, batch, budget);
     const size_t diag = (size_t)(rv ? rv->total_atoms : batch * (m / dim));
@@ -363,6 +455,44 @@ int batch_msf_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
                        (int)b0, d_part, rag, first_row);
     hipLaunchKernelGGL(k_bmsf_reduce, dim3((unsigned)((N + 255) / 256), nb), dim3(256), 0, st, d_part, nchunk, (int)m,
                        dim, (int)b0, d_out, rag);
+  }
+  SC_HIP(ctx, hipGetLastError());
+  return SC_OK;
+}
+
+// dim 3 only (the callers check): d_out (batch, m / 3, 6), ragged (sum n_atoms, 6) packed
+int batch_aniso_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                       const sc_mode_selection& sel, const int64_t* d_counts, size_t budget, double* d_out,
+                       const RaggedView* rv) {
+  if (budget == 0) budget = modes_budget_default();
+  hipStream_t st = ctx->stream;
+  const int64_t nsel = batch_modes_nsel(sel, nvec);
+  const int64_t na = m / 3;
+  const int64_t N = rv ? rv->max_atoms : na;   // (bounds the grids)
+  const RaggedRec* rag = rv ? rv->d_rec : nullptr;
+  const int first_row = rv ? rv->first_row : 0;
+  if (nsel == 0) {
+    SC_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(double) * 6 * (size_t)(rv ? rv->total_atoms : batch * N), st));
+    return SC_OK;
+  }
+  SC_TRY(sc_reserve_modes(ctx, batch_modes_workspace_bytes(m, nvec, batch, 3, nsel, 2, budget, rv)));
+  char* base = (char*)ctx->modes_ws;
+  double* d_s = reinterpret_cast<double*>(base);
+  double* d_part = reinterpret_cast<double*>(base + align_up((size_t)batch * nsel * 8, 256));
+  SC_TRY(launch_weights(ctx, d_w, nvec, batch, sel, nsel, d_counts, d_s, rv));
+  const int chunk = msf_chunk(nsel);
+  const int nchunk = (int)((nsel + chunk - 1) / chunk);
+  const int64_t slab = aniso_slab(m, nsel, batch, budget);
+  const int* rows = sel.kind == SC_SEL_ROWS ? sel.d_rows : nullptr;
+  const int row0 = sel.kind == SC_SEL_FROM_ROW ? (int)sel.row0 : 0;
+  const long long* cnt = reinterpret_cast<const long long*>(d_counts);
+  const unsigned tiles = (unsigned)((N + 255) / 256);
+  for (int64_t b0 = 0; b0 < batch; b0 += slab) {
+    const unsigned nb = (unsigned)std::min(slab, batch - b0);
+    hipLaunchKernelGGL(rows ? k_baniso_partial<true> : k_baniso_partial<false>, dim3(tiles, (unsigned)nchunk, nb),
+                       dim3(256), 0, st, d_v, d_s, rows, row0, (int)nsel, (int)nvec, (int)m, chunk, cnt, (int)b0, d_part,
+                       rag, first_row);
+    hipLaunchKernelGGL(k_baniso_reduce, dim3(tiles, nb), dim3(256), 0, st, d_part, nchunk, (int)na, (int)b0, d_out, rag);
   }
   SC_HIP(ctx, hipGetLastError());
   return SC_OK;

@@ -300,7 +300,7 @@ int modes_prs_device(sc_ctx* ctx, const double* d_v, const double* d_w, int64_t 
                      char* scratch, double* d_out);
 
 // ---- the same quantities for a batch, on the solver's own (w, v, counts) tensors (batch_consumers.hip) ----------
-// what: 0 = msf, 1 = dcc.  n_sel: weighted rows per structure (batch_modes_nsel).  budget: bytes the partial sums (msf) /
+// what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3).  n_sel: weighted rows per structure (batch_modes_nsel).  budget: bytes the partial sums (msf) /
 // the packed GEMM operands (dcc) may take, 0 = modes_budget_default().  ragged: null for a uniform batch (d_out (batch,
 // m / dim[, m / dim])), or the plan's records: m is then the slot order and d_out is packed.
 // Ragged batches (sc_batch_plan): one record per structure in the plan's device blob, read by the window count and the
@@ -326,6 +326,10 @@ int batch_msf_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
 int batch_dcc_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
                      const sc_mode_selection& sel, const int64_t* d_counts, int norm, size_t budget, double* d_out,
                      const RaggedView* ragged = nullptr);
+// dim 3 only: d_out (batch, m / 3, 6), six values per atom in ANISOU order; ragged: packed at 6 * atom_off
+int batch_aniso_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                       const sc_mode_selection& sel, const int64_t* d_counts, size_t budget, double* d_out,
+                       const RaggedView* ragged = nullptr);
 
 // Raises a kernel's dynamic LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) once per (device, kernel).  The
 // attribute belongs to the device that is current when it is set: a function-local static done-flag (rounds 2-5) served

@@ -6,6 +6,8 @@ eigendecomposition, here performed by the hand-written HIP solver (``csrc/eigh*.
 of LAPACK ``dsyevd``.  The mode-subset consumers (``frequencies``, ``mean_square_fluctuation``,
 ``bfactor``, ``dcc``, ``prs``; reference: nma.py:66-359, :476-524) run on the device-resident
 eigenpairs (``csrc/consumers.hip``): the (n, n) eigenvector matrix never crosses PCIe for them.
+``anisotropic_fluctuation`` (no reference counterpart: the per-atom 3x3 tensors whose trace is the MSF) does the same
+through ``csrc/batch_consumers.hip``; ``anisotropy`` reduces such tensors on the host.
 ``normal_mode``, ``linear_response`` and ``effector_sensor`` are O(n) / O(n^2) host arithmetic on
 results that are already on the host.
 """
@@ -17,7 +19,7 @@ from . import _hip
 
 __all__ = [
     "eigen", "eigh", "pinvh", "frequencies", "mean_square_fluctuation", "bfactor", "dcc",
-    "normal_mode", "linear_response", "prs", "effector_sensor",
+    "normal_mode", "linear_response", "prs", "effector_sensor", "anisotropic_fluctuation", "anisotropy",
 ]
 
 K_B = 1.380649e-23
@@ -174,6 +176,56 @@ def dcc(enm, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
     if tem is not None:  # applied after the normalisation, as the reference does (nma.py:355-357)
         cov = cov * tem * tem_factors
     return cov
+
+
+# position of tensor entry (d, e) among the six stored values xx yy zz xy xz yz, the order of a PDB ANISOU record
+ANISOU_INDEX = np.array([[0, 3, 4], [3, 1, 5], [4, 5, 2]])
+
+
+def _aniso_full(u6):
+    """(..., 6) values in ANISOU order -> (..., 3, 3) symmetric tensors (an index gather; works on NumPy arrays)."""
+    return u6[..., ANISOU_INDEX]
+
+
+def anisotropic_fluctuation(anm, mode_subset=None, tem=None, tem_factors=K_B):
+    """
+    Per-atom anisotropic fluctuation tensors ``U[a] = sum_k v_k[a] v_k[a]^T / lambda_k`` over the selected modes, shape
+    (n, 3, 3), symmetric: the anisotropic displacement parameters one compares with ANISOU records, i.e. the diagonal
+    3x3 blocks of the covariance restricted to the selection.  ``trace(U[a])`` is :func:`mean_square_fluctuation` of
+    the same selection, whose ``mode_subset`` (None: every non-trivial mode), ``tem`` and ``tem_factors`` this takes.
+    The reference has no counterpart; there one forms ``anm.covariance`` and reads its blocks.  Here it is one pass
+    over the selected device-resident eigenvectors.  ANM only.
+    """
+    from .anm import ANM
+
+    if not isinstance(anm, ANM):
+        raise ValueError("Instance of ANM class expected.")
+    if mode_subset is not None:
+        mode_subset = _mode_selection(anm, mode_subset, None)   # (the trivial-mode error needs no device)
+    modes = anm._modes_device()
+    if mode_subset is None:
+        mode_subset = _mode_selection(anm, None, modes.order)
+    tensors = _aniso_full(modes.aniso(mode_subset))
+    if tem is not None:
+        tensors = tensors * (tem * tem_factors)
+    return tensors
+
+
+def anisotropy(tensors):
+    """
+    Smallest over largest eigenvalue of each 3x3 tensor of ``tensors`` (..., n, 3, 3) -> (..., n): 1 for an isotropic
+    atom, towards 0 for motion confined to a plane or a line (the figure ANISOU validation reports).  NaN where the largest
+    eigenvalue is 0 (an empty selection) or the tensor is not finite.  Host NumPy on a result that is already there.
+    """
+    t = np.asarray(tensors, dtype=np.float64)
+    if t.shape[-2:] != (3, 3):
+        raise ValueError(f"Expected tensors of shape (..., 3, 3), got {t.shape}")
+    finite = np.isfinite(t).all(axis=(-2, -1))
+    lam = np.linalg.eigvalsh(np.where(finite[..., None, None], t, 0.0))
+    ok = finite & (lam[..., 2] != 0)
+    out = np.full(lam.shape[:-1], np.nan)
+    np.divide(lam[..., 0], lam[..., 2], out=out, where=ok)
+    return out
 
 
 def normal_mode(anm, index, amplitude, frames, movement="sine"):
