@@ -366,6 +366,15 @@ int sc_modes_msf(sc_modes* modes, const int64_t* mode_idx, int64_t k, double* ou
  * as its six distinct entries in the order of a PDB ANISOU record: xx yy zz xy xz yz.  xx + yy + zz is sc_modes_msf's
  * value.  Computed by the batch kernels below with a batch of one. */
 int sc_modes_aniso(sc_modes* modes, const int64_t* mode_idx, int64_t k, double* out);
+/* No reference counterpart (ProDy: calcOverlap / calcCollectivity; Bio3D: overlap); replaces pulling v to the host for
+ * them.  Host pointers.  disp (q, n): q displacement vectors in the coordinates of a mode (for a mass-weighted solve the
+ * caller passes sqrt(mass) * d).  overlap_out (q, k): <v_i, d_j> / (|v_i| |d_j|) for the k listed modes, signed; a zero
+ * d_j gives NaN.  collectivity_out (k): exp(-sum_a p_a ln p_a) / (n / dim) with p_a the share of atom a in |v_i|^2
+ * (a rigid translation: 1; a mode on one atom: dim / n).  overlap_out may be NULL with q = 0, collectivity_out may be
+ * NULL, not both.  GNM and ANM.  A mode index outside 0..n-1 (negative ones count from the end): SC_ERR_INDEX.
+ * Computed by sc_dev_modes_overlap_f64's kernel with a batch of one. */
+int sc_modes_overlap(sc_modes* modes, const int64_t* mode_idx, int64_t k, const double* disp, int64_t q,
+                     double* overlap_out, double* collectivity_out);
 /* out (n / dim, n / dim): sum over the listed modes of <v_a, v_b> / w; norm != 0 divides by sqrt(c_aa c_bb). */
 int sc_modes_dcc(sc_modes* modes, const int64_t* mode_idx, int64_t k, int norm, double* out);
 /* ANM only. out (n / 3, n / 3) row-major: sums of the squared 3x3 blocks of pinv(H, rcond) (numpy hermitian
@@ -426,10 +435,27 @@ int sc_dev_modes_dcc_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int6
  * on the batch size or on its position in the batch, bit for bit.  Enqueue only. */
 int sc_dev_modes_aniso_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
                            const sc_mode_selection* sel, const int64_t* d_counts, double* d_out);
+/* Overlaps of every row of d_v with displacement vectors, and the rows' collectivities: no reference counterpart (ProDy:
+ * calcOverlap / calcCollectivity; Bio3D: overlap); replaces copying d_v (18 GB at 64 x 6000 x 6000) to the host for a
+ * (batch, q, nvec) result.  d_disp (batch, q, m): q vectors per structure in the coordinates of a row (mass-weighted
+ * solve: the caller passes sqrt(mass) * d).  d_overlap (batch, q, nvec): O[b, j, r] = <v_r, d_j> / (|v_r| |d_j|), signed;
+ * a zero row or a zero d_j gives NaN.  d_collectivity (batch, nvec): exp(-sum_a p_a ln p_a) / N, p_a = s_a / sum s, s_a =
+ * the squared norm of atom a's dim components of the row, N = m / dim; a term with p_a = 0 is exactly 0.  d_overlap may
+ * be NULL with q = 0 (collectivity only), d_collectivity may be NULL; both NULL, q < 0 or m % dim != 0:
+ * SC_ERR_INVALID_ARG.  d_counts: NULL, or the counts of a window solve: rows r >= min(d_counts[b], nvec) are NaN in both
+ * outputs and are not read.  One pass over d_v, every row read once for the q vectors (in groups of four) and the
+ * collectivity together; no atomics, every sum a fixed sequence given by (m, dim): O[b, j, r] and the collectivity of a
+ * row do not depend, bit for bit, on the batch size, the structure's position, its neighbours, q or the vectors beside
+ * d_j.  A structure whose d_v is NaN gives NaN and leaves its neighbours alone; d_w is not read, so a structure whose
+ * batch solve failed (NaN eigenvalues beside a finite d_v without a meaning) is the caller's to mask, as
+ * DeviceBatchSolver.overlap does.  No workspace.  Enqueue only. */
+int sc_dev_modes_overlap_f64(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
+                             const double* d_disp, int64_t q, const int64_t* d_counts, double* d_overlap,
+                             double* d_collectivity);
 /* Bytes of device workspace the three entries above hold for such a call (allocated lazily, cached, grown on demand --
  * the one step of a first call that waits for the stream).  n_sel: rows that carry a weight (nvec - row0, n_rows, or
- * nvec for SC_SEL_PINV); what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3 and m % 3 == 0, else 0); budget_bytes as
- * above. */
+ * nvec for SC_SEL_PINV); what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3 and m % 3 == 0, else 0), 3 = overlaps /
+ * collectivities (always 0: sc_dev_modes_overlap_f64 holds no workspace); budget_bytes as above. */
 int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
                                      int64_t budget_bytes);
 
@@ -468,6 +494,15 @@ int sc_batch_plan_modes_dcc_f64(sc_batch_plan* plan, const double* d_w, const do
  * order and the selection, not on its neighbours or its position. */
 int sc_batch_plan_modes_aniso_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
                                   const sc_mode_selection* sel, const int64_t* d_counts, double* d_out);
+/* sc_dev_modes_overlap_f64 for the plan's padded slots: d_v (count, nvec, order); first_row: global mode index of row 0
+ * of d_v (lo of an index-range solve, else 0).  d_disp (q, dim * sum n_atoms) packed as the coordinates of
+ * sc_batch_plan_assemble_f64 are: structure b's vector j starts at j * dim * sum n + dim * atom_off_b.  d_overlap (count,
+ * q, nvec), d_collectivity (count, nvec).  Only a structure's own columns are read and N is its own atom count; a slot's
+ * pad rows (r >= own_b - first_row) and the rows behind d_counts[b] are NaN and are not read.  A structure's bits depend
+ * on the selection and its own size, not on its neighbours or its position. */
+int sc_batch_plan_modes_overlap_f64(sc_batch_plan* plan, const double* d_v, int64_t nvec, int64_t first_row,
+                                    const double* d_disp, int64_t q, const int64_t* d_counts, double* d_overlap,
+                                    double* d_collectivity);
 /* What sc_dev_modes_workspace_bytes answers for a uniform batch, for the plan's (count, order). */
 int64_t sc_batch_plan_modes_workspace_bytes(const sc_batch_plan* plan, int64_t nvec, int64_t n_sel, int what,
                                             int64_t budget_bytes);

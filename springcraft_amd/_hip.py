@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = [
     "sc_batch_plan_eigh_range_f64", "sc_batch_plan_eigh_window_f64", "sc_batch_plan_modes_msf_f64",
     "sc_batch_plan_modes_dcc_f64", "sc_batch_plan_modes_workspace_bytes",
     "sc_modes_aniso", "sc_dev_modes_aniso_f64", "sc_batch_plan_modes_aniso_f64",
+    "sc_modes_overlap", "sc_dev_modes_overlap_f64", "sc_batch_plan_modes_overlap_f64",
 ]
 
 SC_SEL_FROM_ROW = 0
@@ -228,6 +229,9 @@ def lib():
         "sc_batch_plan_modes_dcc_f64": (i32, [vp, vp, vp, i64, P(ModeSelection), vp, i32, i64, vp]),
         "sc_batch_plan_modes_aniso_f64": (i32, [vp, vp, vp, i64, P(ModeSelection), vp, vp]),
         "sc_batch_plan_modes_workspace_bytes": (i64, [vp, i64, i64, i32, i64]),
+        "sc_modes_overlap": (i32, [vp, vp, i64, vp, i64, vp, vp]),
+        "sc_dev_modes_overlap_f64": (i32, [vp, vp, i64, i64, i64, i32, vp, i64, vp, vp, vp]),
+        "sc_batch_plan_modes_overlap_f64": (i32, [vp, vp, i64, i64, vp, i64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -325,7 +329,7 @@ class Context:
 class Modes:
     """
     Owns one ``sc_modes``: all eigenpairs of a model, resident in device memory, plus the consumers that
-    work on them there (msf, dcc, prs, anisotropic tensors).  ``dim`` is 1 for a GNM and 3 for an ANM.
+    work on them there (msf, dcc, prs, anisotropic tensors, overlaps and collectivities).  ``dim`` is 1 for a GNM and 3 for an ANM.
     """
 
     def __init__(self, ctx, handle, dim):
@@ -386,6 +390,20 @@ class Modes:
         out = np.empty((self.order // 3, 6))
         self._ctx.check(self._L.sc_modes_aniso(self._h, ptr(idx), len(idx), ptr(out)))
         return out
+
+    def overlap(self, mode_idx, disp=None, collectivity=False):
+        """
+        (overlap, collectivity) of the listed modes: ``disp`` (q, order) C-contiguous float64 gives overlaps (q, k),
+        ``collectivity`` gives (k,); what is not asked for is None.
+        """
+        idx = self._index_list(mode_idx)
+        q = 0 if disp is None else disp.shape[0]
+        ov = np.empty((q, len(idx))) if q else None
+        co = np.empty(len(idx)) if collectivity else None
+        if q or collectivity:
+            self._ctx.check(self._L.sc_modes_overlap(self._h, ptr(idx), len(idx), ptr(disp) if q else None, q, ptr(ov),
+                                                     ptr(co)))
+        return ov, co
 
     def prs(self, rcond, norm):
         n = self.order // 3

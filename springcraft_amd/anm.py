@@ -89,6 +89,14 @@ class ANM(ElasticNetworkModel):
         """Per-atom 3x3 fluctuation tensors (n,3,3) whose trace is the MSF (:func:`nma.anisotropic_fluctuation`)."""
         return nma.anisotropic_fluctuation(self, mode_subset, tem, tem_factors)
 
+    def overlap(self, displacement, mode_subset=None):
+        """Overlap of the selected modes with one or q displacements, (k,) / (q, k) (:func:`nma.overlap`)."""
+        return nma.overlap(self, displacement, mode_subset)
+
+    def collectivity(self, mode_subset=None):
+        """Collectivity of the selected modes, (k,) (:func:`nma.collectivity`)."""
+        return nma.collectivity(self, mode_subset)
+
     def prs_effector_sensor(self, norm=True):
         """PRS matrix plus effector / sensor profiles (anm.py:384-445)."""
         prs_mat = nma.prs(self, norm)

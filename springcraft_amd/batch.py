@@ -124,6 +124,25 @@ def _aniso_expand(solver, packed):
     return packed.index_select(-1, solver._aniso_index).view(*packed.shape[:-1], 3, 3)
 
 
+def _device_displacement(solver, displacement, lead, tail, names):
+    """
+    Checks a displacement tensor for ``overlap`` on the host: CUDA float64 contiguous on the solver's device, shape
+    ``lead + tail`` (one vector per structure) or ``lead + (q,) + tail``.  Returns (tensor, q, whether it was one vector).
+    """
+    torch = solver.torch
+    d = displacement
+    if not isinstance(d, torch.Tensor) or not d.is_cuda or d.dtype != torch.float64 or not d.is_contiguous():
+        raise ValueError(f"displacement must be a contiguous CUDA float64 tensor of shape {names}")
+    if d.device != torch.device(solver.device):
+        raise ValueError(f"displacement is on {d.device}, the solver on {solver.device}")
+    shape = tuple(d.shape)
+    if shape == lead + tail:
+        return d, 1, True
+    if len(shape) == len(lead) + 1 + len(tail) and shape[:len(lead)] == lead and shape[len(lead) + 1:] == tail:
+        return d, shape[len(lead)], False
+    raise ValueError(f"Expected a displacement of shape {names}, got {shape}")
+
+
 class DeviceBatchSolver:
     """
     ANM (dim=3) or GNM (dim=1) eigensolves for a batch of equally sized structures whose
@@ -356,6 +375,59 @@ class DeviceBatchSolver:
         """
         return _aniso_expand(self, self._aniso_packed(mode_subset, tem, tem_factors))
 
+    def _overlap_call(self, d, q, want_collectivity):
+        nvec = self.w.shape[1]
+        f64 = self.torch.float64
+        ov = self.torch.empty((self.batch, q, nvec), dtype=f64, device=self.device) if q else None
+        co = self.torch.empty((self.batch, nvec), dtype=f64, device=self.device) if want_collectivity else None
+        if ov is not None or co is not None:
+            self.ctx.check(self._L.sc_dev_modes_overlap_f64(
+                self.ctx.handle, C.c_void_p(self.v.data_ptr()), self.m, nvec, self.batch, self.dim,
+                C.c_void_p(d.data_ptr()) if q else None, q,
+                C.c_void_p(self.counts.data_ptr()) if self.window is not None else None,
+                C.c_void_p(ov.data_ptr()) if q else None, C.c_void_p(co.data_ptr()) if want_collectivity else None))
+            # a structure whose solve failed is solved as the zero matrix: its eigenvalues are NaN, its rows of v some
+            # finite basis without a meaning.  The kernel does not read w, so a row is NaN here where its eigenvalue is
+            # (also the rows behind a window's count, which the kernel has set already); enqueued, like the kernel
+            bad = self.torch.isnan(self.w)
+            if ov is not None:
+                ov.masked_fill_(bad[:, None, :], float("nan"))
+            if co is not None:
+                co.masked_fill_(bad, float("nan"))
+        return ov, co
+
+    def overlap(self, displacement):
+        """
+        Overlaps ``<v_r, d> / (|v_r| |d|)`` of every row of ``v`` with the structure's displacement(s): which modes carry
+        an observed change (:func:`nma.overlap`; no reference counterpart).  ``displacement`` is a contiguous CUDA float64
+        tensor (batch, n_atoms, 3) or (batch, q, n_atoms, 3) -- for a GNM solver (batch, n_atoms) or (batch, q, n_atoms)
+        -- in the coordinates of the modes: with ``masses`` pass ``sqrt(mass) * d``, it is not done for you.  Returns
+        (batch, nvec) / (batch, q, nvec), signed, for ALL rows of ``w`` / ``v``, trivial ones included: slice as needed.
+        A row is NaN where its eigenvalue in ``w`` is: behind a window's count, and everywhere in a structure whose solve
+        failed (its ``v`` holds a finite basis without a meaning); a zero displacement gives NaN too.
+        One pass along the rows of ``v``; only enqueues on the solver's stream.
+        """
+        if self.v is None:
+            raise ValueError("the mode consumers need the eigenvectors: build the solver with want_vectors=True")
+        tail = (self.n_atoms, 3) if self.dim == 3 else (self.n_atoms,)
+        names = "(batch, N, 3) or (batch, q, N, 3)" if self.dim == 3 else "(batch, N) or (batch, q, N)"
+        d, q, single = _device_displacement(self, displacement, (self.batch,), tail,
+                                            f"{names} with batch = {self.batch}, N = {self.n_atoms}")
+        if q == 0:
+            return self.torch.empty((self.batch, 0, self.w.shape[1]), dtype=self.torch.float64, device=self.device)
+        ov, _ = self._overlap_call(d, q, False)
+        return ov[:, 0] if single else ov
+
+    def collectivity(self):
+        """
+        (batch, nvec) collectivities ``exp(-sum_a p_a ln p_a) / n_atoms`` of every row of ``v`` (:func:`nma.collectivity`;
+        no reference counterpart): 1 for a rigid translation, 1 / n_atoms for a mode on one atom.  All rows, NaN behind a
+        window's count.  Only enqueues.
+        """
+        if self.v is None:
+            raise ValueError("the mode consumers need the eigenvectors: build the solver with want_vectors=True")
+        return self._overlap_call(None, 0, True)[1]
+
     def dcc(self, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
         """
         (batch, n_atoms, n_atoms) dynamic cross-correlations over the selected modes (nma.py:233-359); ``norm`` divides by
@@ -416,6 +488,7 @@ class RaggedBatchSolver:
     ``min(counts[i], K)`` rows.
 
     :meth:`frequencies`, :meth:`mean_square_fluctuation`, :meth:`bfactor`, :meth:`dcc` and :meth:`anisotropic_fluctuation`
+    (and, per row instead of per atom, :meth:`overlap` and :meth:`collectivity`)
     have the meaning, defaults and trivial-mode rules of :class:`DeviceBatchSolver`'s, per structure: they only enqueue and
     return a list of CUDA tensors, (n_i,) / (n_i, n_i) / (n_i, 3, 3), views into one packed buffer.  Pad rows and columns are never read into a result, and the
     ``|lambda| > 1e-6 max|lambda|`` rule of the dcc default takes its maximum over the structure's own eigenvalues.
@@ -678,6 +751,56 @@ class RaggedBatchSolver:
         """
         out = _aniso_expand(self, self._aniso_packed(mode_subset, tem, tem_factors))
         return [out[self.offsets[b]: self.offsets[b + 1]] for b in range(self.batch)]
+
+    def _overlap_call(self, d, q, want_collectivity):
+        nvec = self.w.shape[1]
+        f64 = self.torch.float64
+        ov = self.torch.empty((self.batch, q, nvec), dtype=f64, device=self.device) if q else None
+        co = self.torch.empty((self.batch, nvec), dtype=f64, device=self.device) if want_collectivity else None
+        if ov is not None or co is not None:
+            self.ctx.check(self._L.sc_batch_plan_modes_overlap_f64(
+                self._plan, C.c_void_p(self.v.data_ptr()), nvec, self._subset_plan["first_row"],
+                C.c_void_p(d.data_ptr()) if q else None, q,
+                C.c_void_p(self.counts.data_ptr()) if self.window is not None else None,
+                C.c_void_p(ov.data_ptr()) if q else None, C.c_void_p(co.data_ptr()) if want_collectivity else None))
+            # a structure whose solve failed is solved as the zero matrix: its eigenvalues are NaN, its rows of v some
+            # finite basis without a meaning.  The kernel does not read w, so a row is NaN here where its eigenvalue is
+            # (also the rows behind a window's count, which the kernel has set already); enqueued, like the kernel
+            bad = self.torch.isnan(self.w)
+            if ov is not None:
+                ov.masked_fill_(bad[:, None, :], float("nan"))
+            if co is not None:
+                co.masked_fill_(bad, float("nan"))
+        return ov, co
+
+    def overlap(self, displacement):
+        """
+        [(rows_i,), ...] or [(q, rows_i), ...] overlaps of every structure's rows with its displacement(s), as
+        :meth:`DeviceBatchSolver.overlap`.  ``displacement`` is packed like the coordinates :meth:`solve` takes: a
+        contiguous CUDA float64 tensor (sum(sizes), 3) or (q, sum(sizes), 3) -- for a GNM solver (sum(sizes),) or
+        (q, sum(sizes)) -- structure i's atoms at ``offsets[i]``.  The views are cut as :meth:`frequencies` cuts them
+        ((dim n_i,) on a full-spectrum solver, else all ``nvec`` rows, NaN behind a window's count); only a structure's own
+        columns are read.
+        """
+        if self.v is None:
+            raise ValueError("the mode consumers need the eigenvectors: build the solver with want_vectors=True")
+        total = int(self.offsets[-1])
+        tail = (total, 3) if self.dim == 3 else (total,)
+        names = "(S, 3) or (q, S, 3)" if self.dim == 3 else "(S,) or (q, S)"
+        d, q, single = _device_displacement(self, displacement, (), tail, f"{names} with S = sum(sizes) = {total}")
+        limits = self._subset_plan["row_limits"]
+        if q == 0:
+            ov = self.torch.empty((self.batch, 0, self.w.shape[1]), dtype=self.torch.float64, device=self.device)
+        else:
+            ov, _ = self._overlap_call(d, q, False)
+        return [ov[b, 0, :r] if single else ov[b, :, :r] for b, r in enumerate(limits)]
+
+    def collectivity(self):
+        """[(rows_i,), ...] collectivities, as :meth:`DeviceBatchSolver.collectivity`; N is the structure's own size."""
+        if self.v is None:
+            raise ValueError("the mode consumers need the eigenvectors: build the solver with want_vectors=True")
+        co = self._overlap_call(None, 0, True)[1]
+        return [co[b, :r] for b, r in enumerate(self._subset_plan["row_limits"])]
 
     def dcc(self, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
         """

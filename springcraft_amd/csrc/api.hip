@@ -961,9 +961,38 @@ int sc_dev_modes_aniso_f64(sc_ctx* ctx, const double* d_w, const double* d_v, in
   return batch_aniso_device(ctx, d_w, d_v, m, nvec, batch, *sel, d_counts, 0, d_out);
 }
 
+// (shared with the plan entry: `padded` = m is a plan's slot order)
+static int check_overlap_args(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
+                              const double* d_disp, int64_t q, const double* d_overlap, const double* d_collectivity,
+                              bool padded = false) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  if (m <= 0 || nvec <= 0 || batch <= 0 || !d_v) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  if ((dim != 1 && dim != 3) || (!padded && m % dim != 0))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "dim must be 1 or 3 and divide m = %lld", (long long)m);
+  if (m > INT32_MAX || nvec > m || batch > INT32_MAX || (size_t)batch * nvec > (size_t)INT32_MAX)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "(batch, nvec, m) = (%lld, %lld, %lld) is not a solver's result shape",
+                        (long long)batch, (long long)nvec, (long long)m);
+  if (q < 0 || q > INT32_MAX / 4) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "q = %lld displacement vectors", (long long)q);
+  if (!d_overlap && !d_collectivity) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "both outputs are NULL");
+  if ((q > 0 && (!d_disp || !d_overlap)) || (q == 0 && !d_collectivity))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "q = %lld needs %s", (long long)q,
+                        q > 0 ? "d_disp and d_overlap" : "d_collectivity");
+  return SC_OK;
+}
+
+int sc_dev_modes_overlap_f64(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
+                             const double* d_disp, int64_t q, const int64_t* d_counts, double* d_overlap,
+                             double* d_collectivity) {
+  SC_TRY(check_overlap_args(ctx, d_v, m, nvec, batch, dim, d_disp, q, d_overlap, d_collectivity));
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return modes_overlap_device(ctx, d_v, m, nvec, batch, dim, nullptr, nvec, d_disp, q, d_counts, d_overlap,
+                              d_collectivity);
+}
+
 int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
                                      int64_t budget_bytes) {
   if (m <= 0 || nvec <= 0 || batch <= 0 || n_sel < 0 || (dim != 1 && dim != 3) || budget_bytes < 0) return 0;
+  if (what == 3) return 0;   // overlaps and collectivities hold no workspace
   if (what == 2 && (dim != 3 || m % 3 != 0)) return 0;
   return (int64_t)batch_modes_workspace_bytes(m, nvec, batch, dim, n_sel, what, (size_t)budget_bytes);
 }
@@ -1340,9 +1369,26 @@ int sc_batch_plan_modes_aniso_f64(sc_batch_plan* plan, const double* d_w, const 
   return batch_aniso_device(ctx, d_w, d_v, plan->order, nvec, plan->count, *sel, d_counts, 0, d_out, &rv);
 }
 
+int sc_batch_plan_modes_overlap_f64(sc_batch_plan* plan, const double* d_v, int64_t nvec, int64_t first_row,
+                                    const double* d_disp, int64_t q, const int64_t* d_counts, double* d_overlap,
+                                    double* d_collectivity) {
+  if (!plan) return SC_ERR_INVALID_ARG;
+  sc_ctx* ctx = plan->ctx;
+  SC_TRY(check_overlap_args(ctx, d_v, plan->order, nvec, plan->count, plan->dim, d_disp, q, d_overlap, d_collectivity,
+                            true));
+  if (first_row < 0 || first_row >= plan->order)
+    return sc_set_error(ctx, SC_ERR_INDEX, "first row %lld outside 0..%lld", (long long)first_row,
+                        (long long)plan->order - 1);
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const RaggedView rv = plan_view(plan, (int)first_row);
+  return modes_overlap_device(ctx, d_v, plan->order, nvec, plan->count, plan->dim, nullptr, nvec, d_disp, q, d_counts,
+                              d_overlap, d_collectivity, &rv);
+}
+
 int64_t sc_batch_plan_modes_workspace_bytes(const sc_batch_plan* plan, int64_t nvec, int64_t n_sel, int what,
                                             int64_t budget_bytes) {
   if (!plan || nvec <= 0 || n_sel < 0 || budget_bytes < 0) return 0;
+  if (what == 3) return 0;
   if (what == 2 && plan->dim != 3) return 0;
   const RaggedView rv = plan_view(plan, 0);
   return (int64_t)batch_modes_workspace_bytes(plan->order, nvec, plan->count, plan->dim, n_sel, what, (size_t)budget_bytes,
@@ -1523,6 +1569,34 @@ int sc_modes_aniso(sc_modes* m, const int64_t* mode_idx, int64_t k, double* out)
   sel.n_rows = k;
   SC_TRY(batch_aniso_device(ctx, m->d_w, m->d_v, m->n, m->n, 1, sel, nullptr, 0, d_out));
   SC_HIP(ctx, hipMemcpyAsync(out, d_out, N * 6 * 8, hipMemcpyDeviceToHost, ctx->stream));
+  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SC_OK;
+}
+
+int sc_modes_overlap(sc_modes* m, const int64_t* mode_idx, int64_t k, const double* disp, int64_t q, double* overlap_out,
+                     double* collectivity_out) {
+  if (!m) return SC_ERR_INVALID_ARG;
+  sc_ctx* ctx = m->ctx;
+  if (k < 0 || k > INT32_MAX / 4 || (k > 0 && !mode_idx) || q < 0 || q > INT32_MAX / 4 ||
+      (!overlap_out && !collectivity_out) || (q > 0 && (!disp || !overlap_out)) || (q == 0 && !collectivity_out))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t n = (size_t)m->n, K = (size_t)k, Q = (size_t)q;
+  SC_TRY(sc_reserve_scratch(ctx, align_up(K * 4, 256) + align_up(Q * n * 8, 256) + align_up(Q * K * 8, 256) +
+                                     align_up(K * 8, 256) + 1024));
+  Bump bump{(char*)ctx->scratch};
+  int* d_sel = bump.take<int>(std::max<size_t>(K, 1));
+  double* d_disp = bump.take<double>(std::max<size_t>(Q * n, 1));
+  double* d_ov = bump.take<double>(std::max<size_t>(Q * K, 1));
+  double* d_co = bump.take<double>(std::max<size_t>(K, 1));
+  SC_TRY(stage_mode_list(m, mode_idx, k, d_sel));   // (the index errors come first, whatever else is empty)
+  if (m->n == 0 || k == 0) return SC_OK;
+  if (q > 0) SC_HIP(ctx, hipMemcpyAsync(d_disp, disp, Q * n * 8, hipMemcpyHostToDevice, ctx->stream));
+  // the batch kernel with a batch of one: one arithmetic order for a model, a batch and a ragged batch
+  SC_TRY(modes_overlap_device(ctx, m->d_v, m->n, m->n, 1, m->dim, d_sel, k, d_disp, q, nullptr, q > 0 ? d_ov : nullptr,
+                              collectivity_out ? d_co : nullptr));
+  if (q > 0) SC_HIP(ctx, hipMemcpyAsync(overlap_out, d_ov, Q * K * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (collectivity_out) SC_HIP(ctx, hipMemcpyAsync(collectivity_out, d_co, K * 8, hipMemcpyDeviceToHost, ctx->stream));
   SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SC_OK;
 }

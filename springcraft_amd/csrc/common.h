@@ -331,6 +331,16 @@ int batch_aniso_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_
                        const sc_mode_selection& sel, const int64_t* d_counts, size_t budget, double* d_out,
                        const RaggedView* ragged = nullptr);
 
+// ---- overlaps with displacement vectors and collectivities of the modes (mode_overlap.hip) -----------------------
+// One pass over the rows of d_v (batch, nvec, m): d_overlap (batch, q, nout) and d_coll (batch, nout), either may be null
+// (d_overlap only with q = 0).  Output row kk is row kk of v (d_rows null, nout = nvec) or row d_rows[kk] (a validated
+// device list: one model's mode subset).  d_disp: (batch, q, m); ragged: (q, dim * sum n_atoms) packed, structure b's
+// vector j at j * dim * sum n + dim * atom_off_b.  Rows behind counts[b] / a slot's own rows are NaN and are not read.
+// No workspace; enqueue only.
+int modes_overlap_device(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
+                         const int* d_rows, int64_t nout, const double* d_disp, int64_t q, const int64_t* d_counts,
+                         double* d_overlap, double* d_coll, const RaggedView* ragged = nullptr);
+
 // Raises a kernel's dynamic LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) once per (device, kernel).  The
 // attribute belongs to the device that is current when it is set: a function-local static done-flag (rounds 2-5) served
 // the first device a process used and left contexts on a second GPU with refused launches.  Returns

@@ -71,3 +71,11 @@ class GNM(ElasticNetworkModel):
     def dcc(self, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
         """Dynamic cross-correlation (n,n) (gnm.py:246-303)."""
         return nma.dcc(self, mode_subset, norm, tem, tem_factors)
+
+    def overlap(self, displacement, mode_subset=None):
+        """Overlap of the selected modes with one or q displacements, (k,) / (q, k) (:func:`nma.overlap`)."""
+        return nma.overlap(self, displacement, mode_subset)
+
+    def collectivity(self, mode_subset=None):
+        """Collectivity of the selected modes, (k,) (:func:`nma.collectivity`)."""
+        return nma.collectivity(self, mode_subset)

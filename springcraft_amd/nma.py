@@ -8,6 +8,8 @@ of LAPACK ``dsyevd``.  The mode-subset consumers (``frequencies``, ``mean_square
 eigenpairs (``csrc/consumers.hip``): the (n, n) eigenvector matrix never crosses PCIe for them.
 ``anisotropic_fluctuation`` (no reference counterpart: the per-atom 3x3 tensors whose trace is the MSF) does the same
 through ``csrc/batch_consumers.hip``; ``anisotropy`` reduces such tensors on the host.
+``overlap`` and ``collectivity`` (no reference counterpart: which modes carry a displacement, and how many atoms a mode
+moves) are one pass along the selected rows (``csrc/mode_overlap.hip``); ``cumulative_overlap`` is array arithmetic.
 ``normal_mode``, ``linear_response`` and ``effector_sensor`` are O(n) / O(n^2) host arithmetic on
 results that are already on the host.
 """
@@ -20,6 +22,7 @@ from . import _hip
 __all__ = [
     "eigen", "eigh", "pinvh", "frequencies", "mean_square_fluctuation", "bfactor", "dcc",
     "normal_mode", "linear_response", "prs", "effector_sensor", "anisotropic_fluctuation", "anisotropy",
+    "overlap", "collectivity", "cumulative_overlap",
 ]
 
 K_B = 1.380649e-23
@@ -226,6 +229,71 @@ def anisotropy(tensors):
     out = np.full(lam.shape[:-1], np.nan)
     np.divide(lam[..., 0], lam[..., 2], out=out, where=ok)
     return out
+
+
+def _displacement(enm, displacement):
+    """``displacement`` as a C-contiguous float64 (q, dim * N) array, and whether the caller gave a single vector."""
+    kind, _ = _model_kind(enm)
+    n = len(enm._coord)
+    tail = (n, 3) if kind == "anm" else (n,)
+    d = np.asarray(displacement, dtype=np.float64)
+    if d.shape != tail and d.shape[1:] != tail:
+        names = "(N, 3) or (q, N, 3)" if kind == "anm" else "(N,) or (q, N)"
+        raise ValueError(f"Expected a displacement of shape {names} with N = {n} for this {kind.upper()}, got {d.shape}")
+    single = d.shape == tail
+    return np.ascontiguousarray(d.reshape(1 if single else d.shape[0], -1)), single
+
+
+def overlap(enm, displacement, mode_subset=None):
+    """
+    Overlap of the selected modes with a displacement, ``<v_k, d> / (|v_k| |d|)``: which modes carry an observed
+    conformational change (open -> closed, apo -> holo, snapshot t -> t + dt).  Signed; its square summed over a complete
+    set of modes is 1 (:func:`cumulative_overlap`).  ``displacement`` is (N, 3) or (q, N, 3) for an ANM and (N,) or
+    (q, N) for a GNM, in the coordinates of the modes: for a mass-weighted model pass ``sqrt(mass)[:, None] * d`` -- this
+    function does not do it for you, nor does it superpose the two conformers.  Returns (k,) or (q, k) for the k modes of
+    ``mode_subset`` (None: every non-trivial mode; trivial indices raise ValueError, as in :func:`mean_square_fluctuation`).
+    A zero displacement gives NaN.  No reference counterpart (ProDy: ``calcOverlap``, Bio3D: ``overlap``); one pass along
+    the selected device-resident eigenvectors, only (q, k) numbers cross PCIe.
+    """
+    d, single = _displacement(enm, displacement)
+    if mode_subset is not None:
+        mode_subset = _mode_selection(enm, mode_subset, None)   # (the trivial-mode error needs no device)
+    modes = enm._modes_device()
+    if mode_subset is None:
+        mode_subset = _mode_selection(enm, None, modes.order)
+    k = np.size(mode_subset)
+    out = modes.overlap(mode_subset, d)[0] if k and len(d) else np.empty((len(d), k))
+    return out[0] if single else out
+
+
+def collectivity(enm, mode_subset=None):
+    """
+    Collectivity of the selected modes (Bruschweiler 1995), ``exp(-sum_a p_a ln p_a) / N`` with ``p_a`` the share of atom
+    a in the squared norm of the mode: 1 when every atom moves alike (a rigid translation), 1 / N for a mode on a single
+    atom.  (k,) for the k modes of ``mode_subset``, chosen as in :func:`overlap`.  No reference counterpart (ProDy:
+    ``calcCollectivity``); same pass as :func:`overlap`.
+    """
+    _model_kind(enm)
+    if mode_subset is not None:
+        mode_subset = _mode_selection(enm, mode_subset, None)
+    modes = enm._modes_device()
+    if mode_subset is None:
+        mode_subset = _mode_selection(enm, None, modes.order)
+    if not np.size(mode_subset):
+        return np.empty(0)
+    return modes.overlap(mode_subset, None, collectivity=True)[1]
+
+
+def cumulative_overlap(overlap):
+    """
+    ``sqrt(cumsum(overlap**2))`` along the last (mode) axis: the share of a displacement the first k modes describe; over
+    a complete orthonormal set it ends at 1.  Pure array arithmetic on a NumPy array or a torch tensor (which stays on
+    its device).  No reference counterpart (ProDy: ``calcCumulOverlap``).
+    """
+    if hasattr(overlap, "cumsum") and not isinstance(overlap, np.ndarray):   # a torch tensor
+        return (overlap * overlap).cumsum(-1).sqrt()
+    o = np.asarray(overlap, dtype=np.float64)
+    return np.sqrt(np.cumsum(o * o, axis=-1))
 
 
 def normal_mode(anm, index, amplitude, frames, movement="sine"):
