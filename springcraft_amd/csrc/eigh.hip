@@ -154,6 +154,10 @@ __global__ __launch_bounds__(256) void k_sturm(const double* __restrict__ tri_al
 
   const int k = blockIdx.x * blockDim.x + threadIdx.x;  // eigenvalue index (ascending)
   if (k >= n) return;
+  if (span == 0.0) {   // d = e = 0: every eigenvalue is exactly 0 (the interval widened by pivmin would give 1e-290 in magnitude)
+    w_all[(size_t)blockIdx.y * stride_w + k] = 0.0;
+    return;
+  }
   double a = lo, b = hi;
   for (int it = 0; it < 120; ++it) {
     const double mid = 0.5 * (a + b);

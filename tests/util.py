@@ -234,3 +234,120 @@ def clustered_spectrum(rel_spacing, sizes=(1, 5, 12, 1, 8, 3, 20, 1, 7, 2), seed
 def random_orthogonal(seed, n):
     q, r = np.linalg.qr(np.random.RandomState(seed).randn(n, n))
     return q * np.sign(np.diag(r))
+
+
+def _largest_lattice(n):
+    """(a, a, c) with a = floor(cbrt(n)) and c = n // a**2: a near-cubic grid of at most n points."""
+    a = 1
+    while (a + 1) ** 3 <= n:
+        a += 1
+    return a, a, n // (a * a)
+
+
+def degenerate_members(n, seed, names=None):
+    """
+    The matrices at which eigensolvers go wrong, all of order `n`, for batched solves with mixed members
+    (tests/test_batched_degenerate_gpu.py; tests/test_batched_degenerate_host.py checks the constructions themselves).
+    Returns (members, exact): `members` a list of (name, a) in the fixed order below, every `a` exactly symmetric float64;
+    `exact` maps the names whose spectrum is known in closed form to it (ascending).  `names`: build only these (a member
+    is the same matrix whichever others are built with it: each draws from a random stream of its own).
+
+    random          randn + randn^T, the control
+    identity, zero  as named
+    diag            diagonal, random entries
+    tridiag         already tridiagonal
+    band40/64/65    random with half-width 40 (inside the stage-1 band of 64), exactly 64, and 65 (one diagonal outside)
+    blockdiag       two dense random blocks of orders n // 2 + 5 and the rest with exact zeros between them: the
+                    tridiagonal matrix splits at a position that is no multiple of 64
+    rank1           I + 5 q q^T
+    clustered       Q diag(clustered_spectrum(0)) Q^T: exact multiplicities (exact up to the rounding of the product)
+    nearclustered   the same with members 1e-13 (relative) apart: clustered but not deflated
+    graded          Q diag(logspace(-12, 3, n)) Q^T
+    gluedW          n // 21 Wilkinson blocks W21+ glued by 1e-10, embedded in 30 I, under a signed permutation
+    big, small      random * 1e150, random * 1e-150
+    kirchhoff       GNM Kirchhoff matrix of the largest near-cubic lattice with at most n atoms (integer entries, exact
+                    multiplicities, spectrum gnm_exact < 12), padded by the diagonal 13, 14, ...
+    """
+    order = ["random", "identity", "zero", "diag", "tridiag", "band40", "band64", "band65", "blockdiag", "rank1",
+             "clustered", "nearclustered", "graded", "gluedW", "big", "small", "kirchhoff"]
+    wanted = order if names is None else list(names)
+    assert set(wanted) <= set(order), sorted(set(wanted) - set(order))
+    exact, cache = {}, {}
+
+    def stream(name):
+        return np.random.RandomState([seed, order.index(name)])
+
+    def sym(a):
+        return np.tril(a) + np.tril(a, -1).T
+
+    def random():
+        if "random" not in cache:
+            g = stream("random").randn(n, n)
+            cache["random"] = sym(g + g.T)
+        return cache["random"]
+
+    def q():
+        if "q" not in cache:
+            cache["q"] = random_orthogonal(seed + 1, n)
+        return cache["q"]
+
+    def band(name):
+        i = np.arange(n)
+        return np.where(np.abs(i[:, None] - i[None, :]) <= int(name[4:]), stream(name).randn(n, n), 0.0)
+
+    def diag(name):
+        d = stream(name).randn(n)
+        exact[name] = np.sort(d)
+        return np.diag(d)
+
+    def tridiag(name):
+        rs = stream(name)
+        return tridiagonal(rs.randn(n), rs.randn(n - 1))
+
+    def blockdiag(name):
+        rs, n1 = stream(name), n // 2 + 5
+        a = np.zeros((n, n))
+        for lo, hi in ((0, n1), (n1, n)):
+            g = rs.randn(hi - lo, hi - lo)
+            a[lo:hi, lo:hi] = g + g.T
+        return a
+
+    def rank1(name):
+        q0 = q()[:, 0]
+        # (q0 is a unit vector to rounding: the one eigenvalue that is not 1 is 1 + 5 |q0|^2)
+        exact[name] = np.concatenate([np.ones(n - 1), [1.0 + 5.0 * float(q0 @ q0)]])
+        return np.eye(n) + 5.0 * np.outer(q0, q0)
+
+    def clustered(name):
+        lam = clustered_spectrum(0.0 if name == "clustered" else 1e-13, n=n)
+        if name == "clustered":
+            exact[name] = lam
+        return (q() * lam) @ q().T
+
+    def glued(name):
+        nw = n // 21
+        a = 30.0 * np.eye(n)
+        a[:21 * nw, :21 * nw] = tridiagonal(*glued_wilkinson(nw, 1e-10))
+        return permute(a, *signed_permutation(seed + 2, n))
+
+    def kirchhoff(name):
+        from oracle import enm_oracle as orc
+
+        a, b, c = _largest_lattice(n)
+        m = a * b * c
+        pad = 13.0 + np.arange(n - m)
+        k = np.diag(np.concatenate([np.zeros(m), pad]))
+        k[:m, :m] = orc.compute_kirchhoff(lattice(a, b, c, seed), orc.invariant_ff(LATTICE_CUTOFF))[0]
+        exact[name] = np.concatenate([np.sort(gnm_exact(a, b, c)).astype(np.float64), pad])
+        return k
+
+    def ones(name):
+        exact[name] = np.ones(n) if name == "identity" else np.zeros(n)
+        return np.eye(n) if name == "identity" else np.zeros((n, n))
+
+    build = {"random": lambda name: random(), "identity": ones, "zero": ones, "diag": diag, "tridiag": tridiag,
+             "band40": band, "band64": band, "band65": band, "blockdiag": blockdiag, "rank1": rank1, "clustered": clustered,
+             "nearclustered": clustered, "graded": lambda name: (q() * np.logspace(-12, 3, n)) @ q().T, "gluedW": glued,
+             "big": lambda name: random() * 1e150, "small": lambda name: random() * 1e-150, "kirchhoff": kirchhoff}
+    members = [(name, sym(build[name](name))) for name in order if name in wanted]
+    return members, exact
