@@ -143,7 +143,116 @@ def _device_displacement(solver, displacement, lead, tail, names):
     raise ValueError(f"Expected a displacement of shape {names}, got {shape}")
 
 
-class DeviceBatchSolver:
+def _trivial_rows(ntriv, first_row, nvec):
+    """
+    How many of a solver's ``nvec`` rows, row r being global mode ``first_row + r``, are trivial modes: the first row of
+    the "every solved non-trivial mode" selection (``nvec``: there is none) and the rows :meth:`frequencies` takes ``abs`` of.
+    """
+    return min(max(ntriv - first_row, 0), nvec)
+
+
+class _BatchSolver:
+    """
+    What :class:`DeviceBatchSolver` and :class:`RaggedBatchSolver` share.  A subclass sets ``_first_row`` (global mode index
+    of row 0 of ``w`` / ``v``) and ``_common_modes`` (modes every member has: an explicit ``mode_subset`` is checked against
+    them) and implements ``assemble``, ``eigh`` and ``_overlap_entry``.
+    """
+
+    #: bytes the packed GEMM operands of :meth:`dcc` may take at a time (None: SPRINGCRAFT_MODES_BUDGET_BYTES, else 1 GiB)
+    consumer_budget_bytes = None
+
+    def set_profiling(self, on):
+        self.ctx.check(self._L.sc_ctx_set_profiling(self.ctx.handle, 1 if on else 0))
+
+    def last_timings(self):
+        return _last_timings(self.ctx, self._L)
+
+    def solve(self, coord):
+        """
+        One pass of the hot path over the batch: assembly + eigensolve, all on device.  Only ENQUEUES (the result tensors
+        are valid in stream order); call :meth:`finish` before trusting them on the host.
+        """
+        self.assemble(coord)
+        return self.eigh()
+
+    def finish(self):
+        """
+        Wait for the solves enqueued so far and raise what they could only find out on the device:
+        ``np.linalg.LinAlgError`` -- what ``np.linalg.eigh`` raises at nma.py:61 -- if a matrix held a NaN / Inf entry
+        (its eigenvalues come back NaN, the other structures of the batch are unaffected) or a tridiagonal QL iteration
+        did not converge.  The condition is reported once.  With ``subset_by_value``, then ValueError naming every structure
+        whose window held more than ``max_modes`` eigenpairs.  Returns (w, v).
+        """
+        self.ctx.synchronize()
+        if self.window is not None:
+            counts = self.counts.cpu().numpy()
+            over = np.nonzero(counts > self.max_modes)[0]
+            if len(over):
+                which = ", ".join(f"{b} ({counts[b]})" for b in over)
+                raise ValueError(f"the eigenvalue window {self.window} holds more than max_modes = {self.max_modes} "
+                                 f"eigenpairs for structure(s) {which}; their slots hold the {self.max_modes} lowest")
+        return self.w, self.v
+
+    @property
+    def _ntriv(self):
+        return 6 if self.dim == 3 else 1
+
+    def _need_vectors(self):
+        if self.v is None:
+            raise ValueError("the mode consumers need the eigenvectors: build the solver with want_vectors=True")
+
+    def _selection(self, mode_subset, pinv_default):
+        """(ModeSelection, counts pointer) for a consumer call; every check is on the host."""
+        self._need_vectors()
+        rows = batch_mode_rows(mode_subset, self._ntriv, self.subset, self._common_modes, self.window)
+        sel = _hip.ModeSelection()
+        nvec = self.w.shape[1]
+        keep = None
+        if self.window is not None:
+            sel.kind, sel.row0 = _hip.SC_SEL_FROM_ROW, 0
+        elif mode_subset is None and pinv_default and self.subset is None:
+            sel.kind, sel.rcond = _hip.SC_SEL_PINV, 1e-6
+        elif mode_subset is None:
+            # every solved non-trivial row (a ragged full-spectrum solver: the records end the rows at dim * n_b)
+            sel.kind, sel.row0 = _hip.SC_SEL_FROM_ROW, _trivial_rows(self._ntriv, self._first_row, nvec)
+        else:
+            # through page-locked memory: a copy from pageable memory would make the host wait for the stream
+            host = self.torch.from_numpy(rows).pin_memory()
+            keep = host.to(self.device, non_blocking=True)
+            sel.kind, sel.d_rows, sel.n_rows = _hip.SC_SEL_ROWS, keep.data_ptr(), len(rows)
+        self._rows_keep = keep      # (the device list outlives the enqueued call)
+        return sel, (C.c_void_p(self.counts.data_ptr()) if self.window is not None else None)
+
+    def _frequencies(self):
+        """(batch, nvec) ``sqrt(lambda) / (2 pi)``; without a window the trivial rows enter as ``abs(lambda)``."""
+        w = self.w.clone()
+        if self.window is None:
+            k = _trivial_rows(self._ntriv, self._first_row, w.shape[1])
+            w[:, :k] = w[:, :k].abs()
+        return self.torch.sqrt(w) / (2 * np.pi)
+
+    def _overlap_call(self, d, q, want_collectivity):
+        nvec = self.w.shape[1]
+        f64 = self.torch.float64
+        ov = self.torch.empty((self.batch, q, nvec), dtype=f64, device=self.device) if q else None
+        co = self.torch.empty((self.batch, nvec), dtype=f64, device=self.device) if want_collectivity else None
+        if ov is not None or co is not None:
+            self.ctx.check(self._overlap_entry(
+                C.c_void_p(self.v.data_ptr()), nvec, C.c_void_p(d.data_ptr()) if q else None, q,
+                C.c_void_p(self.counts.data_ptr()) if self.window is not None else None,
+                C.c_void_p(ov.data_ptr()) if q else None, C.c_void_p(co.data_ptr()) if want_collectivity else None))
+            # a structure whose solve failed is solved as the zero matrix: its eigenvalues are NaN, its rows of v some
+            # finite basis without a meaning.  The kernel does not read w, so a row is NaN here where its eigenvalue is
+            # (also the rows behind a window's count, which the kernel has set already); enqueued, like the kernel
+            bad = self.torch.isnan(self.w)
+            if ov is not None:
+                ov.masked_fill_(bad[:, None, :], float("nan"))
+            if co is not None:
+                co.masked_fill_(bad, float("nan"))
+        return ov, co
+
+
+class DeviceBatchSolver(_BatchSolver):
     """
     ANM (dim=3) or GNM (dim=1) eigensolves for a batch of equally sized structures whose
     coordinates already live in HBM.  Buffers are torch CUDA tensors; all work is enqueued on
@@ -199,6 +308,7 @@ class DeviceBatchSolver:
                 raise ValueError(f"subset_by_index {subset_by_index} outside 0..{m - 1}")
             self.subset = (lo, hi)
             nvec = hi - lo + 1
+        self._first_row, self._common_modes = (self.subset[0] if self.subset else 0), m
         self.max_modes = max_modes
         self.counts = None
         if self.window is not None:
@@ -218,12 +328,6 @@ class DeviceBatchSolver:
             if bool((mm == 0).any()):
                 raise ValueError("masses must not be 0")          # anm.py:85-86
             self.inv_sqrt_mass = (1.0 / torch.sqrt(mm)).contiguous()
-
-    def set_profiling(self, on):
-        self.ctx.check(self._L.sc_ctx_set_profiling(self.ctx.handle, 1 if on else 0))
-
-    def last_timings(self):
-        return _last_timings(self.ctx, self._L)
 
     def assemble(self, coord):
         """coord: (batch, n_atoms, 3) float64 CUDA tensor -> self.matrix (Hessian / Kirchhoff)."""
@@ -252,65 +356,9 @@ class DeviceBatchSolver:
                                                          C.c_void_p(self.w.data_ptr()), vp))
         return self.w, self.v
 
-    def solve(self, coord):
-        """
-        One pass of the hot path over the batch: assembly + eigensolve, all on device.  Only ENQUEUES (the result tensors
-        are valid in stream order); call :meth:`finish` before trusting them on the host.
-        """
-        self.assemble(coord)
-        return self.eigh()
-
-    def finish(self):
-        """
-        Wait for the solves enqueued so far and raise what they could only find out on the device:
-        ``np.linalg.LinAlgError`` -- what ``np.linalg.eigh`` raises at nma.py:61 -- if a matrix held a NaN / Inf entry
-        (its eigenvalues come back NaN, the other structures of the batch are unaffected) or a tridiagonal QL iteration
-        did not converge.  The condition is reported once.  With ``subset_by_value``, then ValueError naming every structure
-        whose window held more than ``max_modes`` eigenpairs.  Returns (w, v).
-        """
-        self.ctx.synchronize()
-        if self.window is not None:
-            counts = self.counts.cpu().numpy()
-            over = np.nonzero(counts > self.max_modes)[0]
-            if len(over):
-                which = ", ".join(f"{b} ({counts[b]})" for b in over)
-                raise ValueError(f"the eigenvalue window {self.window} holds more than max_modes = {self.max_modes} "
-                                 f"eigenpairs for structure(s) {which}; their slots hold the {self.max_modes} lowest")
-        return self.w, self.v
-
     # ---- consumers of the solved modes (reference: nma.py:66-359, there for one model) --------------------------------
     # Like solve() they ONLY ENQUEUE on the solver's stream and return CUDA tensors that are valid in stream order: no
     # synchronisation, no host copy of w.  The one exception is the first call of a kind, which allocates its workspace.
-
-    #: bytes the packed GEMM operands of :meth:`dcc` may take at a time (None: SPRINGCRAFT_MODES_BUDGET_BYTES, else 1 GiB)
-    consumer_budget_bytes = None
-
-    @property
-    def _ntriv(self):
-        return 6 if self.dim == 3 else 1
-
-    def _selection(self, mode_subset, pinv_default):
-        """(ModeSelection, counts pointer, objects to keep alive) for a consumer call; every check is on the host."""
-        if self.v is None:
-            raise ValueError("the mode consumers need the eigenvectors: build the solver with want_vectors=True")
-        rows = batch_mode_rows(mode_subset, self._ntriv, self.subset, self.m, self.window)
-        sel = _hip.ModeSelection()
-        keep = None
-        nvec = self.w.shape[1]
-        if self.window is not None:
-            sel.kind, sel.row0 = _hip.SC_SEL_FROM_ROW, 0
-        elif mode_subset is None and pinv_default and self.subset is None:
-            sel.kind, sel.rcond = _hip.SC_SEL_PINV, 1e-6
-        elif mode_subset is None:
-            sel.kind, sel.row0 = _hip.SC_SEL_FROM_ROW, (int(rows[0]) if len(rows) else nvec)
-        else:
-            # through page-locked memory: a copy from pageable memory would make the host wait for the stream
-            host = self.torch.from_numpy(rows).pin_memory()
-            keep = host.to(self.device, non_blocking=True)
-            sel.kind, sel.d_rows, sel.n_rows = _hip.SC_SEL_ROWS, keep.data_ptr(), len(rows)
-        counts = C.c_void_p(self.counts.data_ptr()) if self.window is not None else None
-        self._rows_keep = keep
-        return sel, counts, keep
 
     def frequencies(self):
         """
@@ -318,11 +366,7 @@ class DeviceBatchSolver:
         enter as ``abs(lambda)`` (nma.py:66-105).  With ``subset_by_value`` the mode indices are not known, so no row is
         treated as trivial (a negative rounding-level eigenvalue gives NaN, as do the padding rows).
         """
-        w = self.w.clone()
-        if self.window is None:
-            k = max(0, min(self._ntriv - (self.subset[0] if self.subset else 0), w.shape[1]))
-            w[:, :k] = w[:, :k].abs()
-        return self.torch.sqrt(w) / (2 * np.pi)
+        return self._frequencies()
 
     def mean_square_fluctuation(self, mode_subset=None, tem=None, tem_factors=K_B):
         """
@@ -338,7 +382,7 @@ class DeviceBatchSolver:
         A structure whose solve failed (NaN eigenvalues) gives NaN, its neighbours are unaffected; behind a window solve such
         a structure has count 0 and gives the empty window's result.
         """
-        sel, counts, keep = self._selection(mode_subset, pinv_default=False)
+        sel, counts = self._selection(mode_subset, pinv_default=False)
         out = self.torch.empty((self.batch, self.n_atoms), dtype=self.torch.float64, device=self.device)
         self.ctx.check(self._L.sc_dev_modes_msf_f64(
             self.ctx.handle, C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr()), self.m, self.w.shape[1],
@@ -357,7 +401,7 @@ class DeviceBatchSolver:
         """(batch, n_atoms, 6): every tensor's six distinct entries xx yy zz xy xz yz, as the kernel leaves them."""
         if self.dim != 3:
             raise ValueError("anisotropic fluctuation tensors need an ANM solver (dim=3)")
-        sel, counts, keep = self._selection(mode_subset, pinv_default=False)
+        sel, counts = self._selection(mode_subset, pinv_default=False)
         out = self.torch.empty((self.batch, self.n_atoms, 6), dtype=self.torch.float64, device=self.device)
         self.ctx.check(self._L.sc_dev_modes_aniso_f64(
             self.ctx.handle, C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr()), self.m, self.w.shape[1],
@@ -375,26 +419,9 @@ class DeviceBatchSolver:
         """
         return _aniso_expand(self, self._aniso_packed(mode_subset, tem, tem_factors))
 
-    def _overlap_call(self, d, q, want_collectivity):
-        nvec = self.w.shape[1]
-        f64 = self.torch.float64
-        ov = self.torch.empty((self.batch, q, nvec), dtype=f64, device=self.device) if q else None
-        co = self.torch.empty((self.batch, nvec), dtype=f64, device=self.device) if want_collectivity else None
-        if ov is not None or co is not None:
-            self.ctx.check(self._L.sc_dev_modes_overlap_f64(
-                self.ctx.handle, C.c_void_p(self.v.data_ptr()), self.m, nvec, self.batch, self.dim,
-                C.c_void_p(d.data_ptr()) if q else None, q,
-                C.c_void_p(self.counts.data_ptr()) if self.window is not None else None,
-                C.c_void_p(ov.data_ptr()) if q else None, C.c_void_p(co.data_ptr()) if want_collectivity else None))
-            # a structure whose solve failed is solved as the zero matrix: its eigenvalues are NaN, its rows of v some
-            # finite basis without a meaning.  The kernel does not read w, so a row is NaN here where its eigenvalue is
-            # (also the rows behind a window's count, which the kernel has set already); enqueued, like the kernel
-            bad = self.torch.isnan(self.w)
-            if ov is not None:
-                ov.masked_fill_(bad[:, None, :], float("nan"))
-            if co is not None:
-                co.masked_fill_(bad, float("nan"))
-        return ov, co
+    def _overlap_entry(self, vp, nvec, dp, q, counts, ovp, cop):
+        return self._L.sc_dev_modes_overlap_f64(self.ctx.handle, vp, self.m, nvec, self.batch, self.dim, dp, q, counts, ovp,
+                                                cop)
 
     def overlap(self, displacement):
         """
@@ -407,8 +434,7 @@ class DeviceBatchSolver:
         failed (its ``v`` holds a finite basis without a meaning); a zero displacement gives NaN too.
         One pass along the rows of ``v``; only enqueues on the solver's stream.
         """
-        if self.v is None:
-            raise ValueError("the mode consumers need the eigenvectors: build the solver with want_vectors=True")
+        self._need_vectors()
         tail = (self.n_atoms, 3) if self.dim == 3 else (self.n_atoms,)
         names = "(batch, N, 3) or (batch, q, N, 3)" if self.dim == 3 else "(batch, N) or (batch, q, N)"
         d, q, single = _device_displacement(self, displacement, (self.batch,), tail,
@@ -424,8 +450,7 @@ class DeviceBatchSolver:
         no reference counterpart): 1 for a rigid translation, 1 / n_atoms for a mode on one atom.  All rows, NaN behind a
         window's count.  Only enqueues.
         """
-        if self.v is None:
-            raise ValueError("the mode consumers need the eigenvectors: build the solver with want_vectors=True")
+        self._need_vectors()
         return self._overlap_call(None, 0, True)[1]
 
     def dcc(self, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
@@ -440,7 +465,7 @@ class DeviceBatchSolver:
         the selection is the window (see :meth:`mean_square_fluctuation`, also for trivial modes inside it); an empty
         window gives zeros, and NaN under ``norm=True`` as 0 / 0 does in NumPy.
         """
-        sel, counts, keep = self._selection(mode_subset, pinv_default=True)
+        sel, counts = self._selection(mode_subset, pinv_default=True)
         n = self.n_atoms
         out = self.torch.empty((self.batch, n, n), dtype=self.torch.float64, device=self.device)
         self.ctx.check(self._L.sc_dev_modes_dcc_f64(
@@ -453,7 +478,7 @@ class DeviceBatchSolver:
         return out
 
 
-class RaggedBatchSolver:
+class RaggedBatchSolver(_BatchSolver):
     """
     ONE batched solve for structures that differ: in size, in force field -- any built-in one,
     :class:`TabulatedForceField` (forcefield.py:369-533) and :class:`PatchedForceField` (forcefield.py:117-261) around
@@ -501,6 +526,9 @@ class RaggedBatchSolver:
         self._subset_plan = ragged_subset_plan(self.sizes, self.dim, subset_by_index, subset_by_value, max_modes)
         self.subset, self.window = self._subset_plan["subset"], self._subset_plan["window"]
         self.max_modes = self._subset_plan["max_modes"]
+        # an explicit mode_subset is checked against the modes EVERY structure has: one the smallest structure lacks raises
+        # the "was not solved" error instead of being dropped for that structure alone
+        self._first_row, self._common_modes = self._subset_plan["first_row"], self.dim * min(self.sizes)
         import torch
 
         self.torch = torch
@@ -565,12 +593,6 @@ class RaggedBatchSolver:
                 packed[self.offsets[b]: self.offsets[b + 1]] = 1.0 / np.sqrt(mb)
             self.inv_sqrt_mass = torch.from_numpy(packed).to(self.device)
 
-    def set_profiling(self, on):
-        self.ctx.check(self._L.sc_ctx_set_profiling(self.ctx.handle, 1 if on else 0))
-
-    def last_timings(self):
-        return _last_timings(self.ctx, self._L)
-
     def assemble(self, coord):
         """coord: (sum(sizes), 3) float64 CUDA tensor -> self.matrix, one padded slot per structure."""
         assert coord.is_cuda and coord.dtype == self.torch.float64 and coord.is_contiguous()
@@ -625,25 +647,6 @@ class RaggedBatchSolver:
             self.ctx.check(self._L.sc_dev_eigh_f64(self.ctx.handle, ap, self.order, self.batch, wp, vp))
         return self.w, self.v
 
-    def solve(self, coord):
-        self.assemble(coord)
-        return self.eigh()
-
-    def finish(self):
-        """
-        As :meth:`DeviceBatchSolver.finish`: wait, and raise ``np.linalg.LinAlgError`` for NaN / Inf input or a QL failure;
-        with ``subset_by_value``, then ValueError naming every structure whose window held more than ``max_modes`` eigenpairs.
-        """
-        self.ctx.synchronize()
-        if self.window is not None:
-            counts = self.counts.cpu().numpy()
-            over = np.nonzero(counts > self.max_modes)[0]
-            if len(over):
-                which = ", ".join(f"{b} ({counts[b]})" for b in over)
-                raise ValueError(f"the eigenvalue window {self.window} holds more than max_modes = {self.max_modes} "
-                                 f"eigenpairs for structure(s) {which}; their slots hold the {self.max_modes} lowest")
-        return self.w, self.v
-
     def results(self):
         """
         Per-structure views of the last solve: [(w_i, v_i or None), ...], ``v_i`` cut to the structure's own ``dim n_i``
@@ -664,37 +667,10 @@ class RaggedBatchSolver:
     # They ONLY ENQUEUE on the solver's stream (the first call of a kind allocates its workspace) and return lists of views
     # into one packed buffer: structure b's atoms start at sum(sizes[:b]), its (n_b, n_b) block at sum(sizes[:b] ** 2).
 
-    #: bytes the packed GEMM operands of :meth:`dcc` may take at a time (None: SPRINGCRAFT_MODES_BUDGET_BYTES, else 1 GiB)
-    consumer_budget_bytes = None
-
-    @property
-    def _ntriv(self):
-        return 6 if self.dim == 3 else 1
-
     def _selection(self, mode_subset, pinv_default):
-        """(ModeSelection, counts pointer) for a consumer call; every check is on the host."""
-        if self.v is None:
-            raise ValueError("the mode consumers need the eigenvectors: build the solver with want_vectors=True")
-        # an explicit list is checked against the modes EVERY structure has: one the smallest structure lacks raises the
-        # "was not solved" error instead of being dropped for that structure alone
-        rows = batch_mode_rows(mode_subset, self._ntriv, self.subset, self.dim * min(self.sizes), self.window)
-        sel = _hip.ModeSelection()
-        sel.reserved = self._subset_plan["first_row"]
-        nvec = self.w.shape[1]
-        keep = None
-        if self.window is not None:
-            sel.kind, sel.row0 = _hip.SC_SEL_FROM_ROW, 0
-        elif mode_subset is None and pinv_default and self.subset is None:
-            sel.kind, sel.rcond = _hip.SC_SEL_PINV, 1e-6
-        elif mode_subset is None:
-            # every solved non-trivial row; on a full-spectrum solver the records end the rows at dim * n_b
-            sel.kind, sel.row0 = _hip.SC_SEL_FROM_ROW, min(max(self._ntriv - sel.reserved, 0), nvec)
-        else:
-            host = self.torch.from_numpy(rows).pin_memory()     # (page-locked: the copy must not wait for the stream)
-            keep = host.to(self.device, non_blocking=True)
-            sel.kind, sel.d_rows, sel.n_rows = _hip.SC_SEL_ROWS, keep.data_ptr(), len(rows)
-        self._rows_keep = keep
-        return sel, (C.c_void_p(self.counts.data_ptr()) if self.window is not None else None)
+        sel, counts = super()._selection(mode_subset, pinv_default)
+        sel.reserved = self._first_row      # (how the sc_batch_plan_modes_* entries learn the global index of row 0)
+        return sel, counts
 
     def frequencies(self):
         """
@@ -702,11 +678,7 @@ class RaggedBatchSolver:
         ``abs(lambda)`` (nma.py:66-105): (dim n_i,) for a full-spectrum solver, else all ``nvec`` rows (with
         ``subset_by_value`` no row is treated as trivial and the rows behind the count are NaN).
         """
-        w = self.w.clone()
-        if self.window is None:
-            k = max(0, min(self._ntriv - self._subset_plan["first_row"], w.shape[1]))
-            w[:, :k] = w[:, :k].abs()
-        f = self.torch.sqrt(w) / (2 * np.pi)
+        f = self._frequencies()
         return [f[b, :r] for b, r in enumerate(self._subset_plan["row_limits"])]
 
     def mean_square_fluctuation(self, mode_subset=None, tem=None, tem_factors=K_B):
@@ -752,26 +724,8 @@ class RaggedBatchSolver:
         out = _aniso_expand(self, self._aniso_packed(mode_subset, tem, tem_factors))
         return [out[self.offsets[b]: self.offsets[b + 1]] for b in range(self.batch)]
 
-    def _overlap_call(self, d, q, want_collectivity):
-        nvec = self.w.shape[1]
-        f64 = self.torch.float64
-        ov = self.torch.empty((self.batch, q, nvec), dtype=f64, device=self.device) if q else None
-        co = self.torch.empty((self.batch, nvec), dtype=f64, device=self.device) if want_collectivity else None
-        if ov is not None or co is not None:
-            self.ctx.check(self._L.sc_batch_plan_modes_overlap_f64(
-                self._plan, C.c_void_p(self.v.data_ptr()), nvec, self._subset_plan["first_row"],
-                C.c_void_p(d.data_ptr()) if q else None, q,
-                C.c_void_p(self.counts.data_ptr()) if self.window is not None else None,
-                C.c_void_p(ov.data_ptr()) if q else None, C.c_void_p(co.data_ptr()) if want_collectivity else None))
-            # a structure whose solve failed is solved as the zero matrix: its eigenvalues are NaN, its rows of v some
-            # finite basis without a meaning.  The kernel does not read w, so a row is NaN here where its eigenvalue is
-            # (also the rows behind a window's count, which the kernel has set already); enqueued, like the kernel
-            bad = self.torch.isnan(self.w)
-            if ov is not None:
-                ov.masked_fill_(bad[:, None, :], float("nan"))
-            if co is not None:
-                co.masked_fill_(bad, float("nan"))
-        return ov, co
+    def _overlap_entry(self, vp, nvec, dp, q, counts, ovp, cop):
+        return self._L.sc_batch_plan_modes_overlap_f64(self._plan, vp, nvec, self._first_row, dp, q, counts, ovp, cop)
 
     def overlap(self, displacement):
         """
@@ -782,8 +736,7 @@ class RaggedBatchSolver:
         ((dim n_i,) on a full-spectrum solver, else all ``nvec`` rows, NaN behind a window's count); only a structure's own
         columns are read.
         """
-        if self.v is None:
-            raise ValueError("the mode consumers need the eigenvectors: build the solver with want_vectors=True")
+        self._need_vectors()
         total = int(self.offsets[-1])
         tail = (total, 3) if self.dim == 3 else (total,)
         names = "(S, 3) or (q, S, 3)" if self.dim == 3 else "(S,) or (q, S)"
@@ -797,8 +750,7 @@ class RaggedBatchSolver:
 
     def collectivity(self):
         """[(rows_i,), ...] collectivities, as :meth:`DeviceBatchSolver.collectivity`; N is the structure's own size."""
-        if self.v is None:
-            raise ValueError("the mode consumers need the eigenvectors: build the solver with want_vectors=True")
+        self._need_vectors()
         co = self._overlap_call(None, 0, True)[1]
         return [co[b, :r] for b, r in enumerate(self._subset_plan["row_limits"])]
 

@@ -1448,6 +1448,31 @@ int stage_mode_list(sc_modes* m, const int64_t* idx, int64_t k, int* d_sel) {
   }
   return SC_OK;
 }
+
+// msf / tensors / dcc of one model over a mode list: the validated list and the (out_elems) result in ctx->scratch, `run`
+// on them, the result copied to `out`.  `run` is a batch consumer with a batch of one (nvec = m = n, no counts, default
+// budget; its workspace is ctx->modes_ws): one arithmetic order for a model, a batch and a ragged batch.
+template <typename Run>
+int modes_list_call(sc_modes* m, const int64_t* mode_idx, int64_t k, size_t out_elems, double* out, Run run) {
+  sc_ctx* ctx = m->ctx;
+  if (k < 0 || k > INT32_MAX / 4 || (k > 0 && !mode_idx) || (m->n > 0 && !out))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  if (m->n == 0) return SC_OK;
+  SC_TRY(sc_reserve_scratch(ctx, align_up((size_t)k * 4, 256) + align_up(out_elems * 8, 256) + 1024));
+  Bump bump{(char*)ctx->scratch};
+  int* d_sel = bump.take<int>((size_t)std::max<int64_t>(k, 1));
+  double* d_out = bump.take<double>(out_elems);
+  SC_TRY(stage_mode_list(m, mode_idx, k, d_sel));
+  sc_mode_selection sel{};
+  sel.kind = SC_SEL_ROWS;
+  sel.d_rows = d_sel;
+  sel.n_rows = k;
+  SC_TRY(run(sel, d_out));
+  SC_HIP(ctx, hipMemcpyAsync(out, d_out, out_elems * 8, hipMemcpyDeviceToHost, ctx->stream));
+  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1530,47 +1555,18 @@ int sc_modes_get(sc_modes* m, double* w, double* v) {
 
 int sc_modes_msf(sc_modes* m, const int64_t* mode_idx, int64_t k, double* out) {
   if (!m) return SC_ERR_INVALID_ARG;
-  sc_ctx* ctx = m->ctx;
-  if (k < 0 || (k > 0 && !mode_idx) || (m->n > 0 && !out)) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  if (m->n == 0) return SC_OK;
-  const size_t N = (size_t)(m->n / m->dim);
-  const size_t work = modes_scratch_bytes(m->n, m->dim, k, 0);
-  SC_TRY(sc_reserve_scratch(ctx, work + align_up((size_t)k * 4, 256) + align_up(N * 8, 256) + 1024));
-  Bump bump{(char*)ctx->scratch};
-  int* d_sel = bump.take<int>((size_t)std::max<int64_t>(k, 1));
-  double* d_out = bump.take<double>(N);
-  char* scratch = bump.take<char>(work);
-  SC_TRY(stage_mode_list(m, mode_idx, k, d_sel));
-  SC_TRY(modes_msf_device(ctx, m->d_v, m->d_w, m->n, m->dim, d_sel, k, scratch, d_out));
-  SC_HIP(ctx, hipMemcpyAsync(out, d_out, N * 8, hipMemcpyDeviceToHost, ctx->stream));
-  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SC_OK;
+  return modes_list_call(m, mode_idx, k, (size_t)(m->n / m->dim), out, [m](const sc_mode_selection& sel, double* d_out) {
+    return batch_msf_device(m->ctx, m->d_w, m->d_v, m->n, m->n, 1, m->dim, sel, nullptr, 0, d_out);
+  });
 }
 
 int sc_modes_aniso(sc_modes* m, const int64_t* mode_idx, int64_t k, double* out) {
   if (!m) return SC_ERR_INVALID_ARG;
-  sc_ctx* ctx = m->ctx;
-  if (m->dim != 3) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "anisotropic fluctuation tensors need an ANM (dim 3)");
-  if (k < 0 || k > INT32_MAX / 4 || (k > 0 && !mode_idx) || (m->n > 0 && !out))
-    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  if (m->n == 0) return SC_OK;
-  const size_t N = (size_t)(m->n / 3);
-  SC_TRY(sc_reserve_scratch(ctx, align_up((size_t)k * 4, 256) + align_up(N * 6 * 8, 256) + 1024));
-  Bump bump{(char*)ctx->scratch};
-  int* d_sel = bump.take<int>((size_t)std::max<int64_t>(k, 1));
-  double* d_out = bump.take<double>(N * 6);
-  SC_TRY(stage_mode_list(m, mode_idx, k, d_sel));
-  // the batch kernels with a batch of one: one arithmetic order for a model, a batch and a ragged batch
-  sc_mode_selection sel{};
-  sel.kind = SC_SEL_ROWS;
-  sel.d_rows = d_sel;
-  sel.n_rows = k;
-  SC_TRY(batch_aniso_device(ctx, m->d_w, m->d_v, m->n, m->n, 1, sel, nullptr, 0, d_out));
-  SC_HIP(ctx, hipMemcpyAsync(out, d_out, N * 6 * 8, hipMemcpyDeviceToHost, ctx->stream));
-  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SC_OK;
+  if (m->dim != 3)
+    return sc_set_error(m->ctx, SC_ERR_INVALID_ARG, "anisotropic fluctuation tensors need an ANM (dim 3)");
+  return modes_list_call(m, mode_idx, k, (size_t)(m->n / 3) * 6, out, [m](const sc_mode_selection& sel, double* d_out) {
+    return batch_aniso_device(m->ctx, m->d_w, m->d_v, m->n, m->n, 1, sel, nullptr, 0, d_out);
+  });
 }
 
 int sc_modes_overlap(sc_modes* m, const int64_t* mode_idx, int64_t k, const double* disp, int64_t q, double* overlap_out,
@@ -1603,22 +1599,10 @@ int sc_modes_overlap(sc_modes* m, const int64_t* mode_idx, int64_t k, const doub
 
 int sc_modes_dcc(sc_modes* m, const int64_t* mode_idx, int64_t k, int norm, double* out) {
   if (!m) return SC_ERR_INVALID_ARG;
-  sc_ctx* ctx = m->ctx;
-  if (k < 0 || (k > 0 && !mode_idx) || (m->n > 0 && !out)) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  if (m->n == 0) return SC_OK;
   const size_t N = (size_t)(m->n / m->dim);
-  const size_t work = modes_scratch_bytes(m->n, m->dim, k, 1);
-  SC_TRY(sc_reserve_scratch(ctx, work + align_up((size_t)k * 4, 256) + align_up(N * N * 8, 256) + 1024));
-  Bump bump{(char*)ctx->scratch};
-  int* d_sel = bump.take<int>((size_t)std::max<int64_t>(k, 1));
-  double* d_out = bump.take<double>(N * N);
-  char* scratch = bump.take<char>(work);
-  SC_TRY(stage_mode_list(m, mode_idx, k, d_sel));
-  SC_TRY(modes_dcc_device(ctx, m->d_v, m->d_w, m->n, m->dim, d_sel, k, norm, scratch, d_out));
-  SC_HIP(ctx, hipMemcpyAsync(out, d_out, N * N * 8, hipMemcpyDeviceToHost, ctx->stream));
-  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SC_OK;
+  return modes_list_call(m, mode_idx, k, N * N, out, [m, norm](const sc_mode_selection& sel, double* d_out) {
+    return batch_dcc_device(m->ctx, m->d_w, m->d_v, m->n, m->n, 1, m->dim, sel, nullptr, norm, 0, d_out);
+  });
 }
 
 int sc_modes_prs(sc_modes* m, double rcond, int norm, double* out) {
@@ -1629,7 +1613,7 @@ int sc_modes_prs(sc_modes* m, double rcond, int norm, double* out) {
   SC_HIP(ctx, hipSetDevice(ctx->device));
   if (m->n == 0) return SC_OK;
   const size_t N = (size_t)(m->n / 3);
-  const size_t work = modes_scratch_bytes(m->n, 3, m->n, 2);
+  const size_t work = prs_scratch_bytes(m->n);
   SC_TRY(sc_reserve_scratch(ctx, work + align_up(N * N * 8, 256) + 1024));
   Bump bump{(char*)ctx->scratch};
   double* d_out = bump.take<double>(N * N);

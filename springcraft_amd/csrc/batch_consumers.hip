@@ -1,8 +1,9 @@
 // Mode-subset consumers for a BATCH of structures, on the tensors the batched solvers leave in HBM.
 //
-// The reference derives these from nma.eigen for one model (nma.py:108-184 msf, :233-359 dcc); consumers.hip does so for
-// one model on the device.  Here the inputs are the batch solver's own w (batch, nvec), v (batch, nvec, m) rows = modes
-// and, behind a window solve, counts (batch): at the benchmarked shape v is 18 GB that nobody wants to move or copy.
+// The reference derives these from nma.eigen for one model (nma.py:108-184 msf, :233-359 dcc).  Here the inputs are the
+// batch solver's own w (batch, nvec), v (batch, nvec, m) rows = modes and, behind a window solve, counts (batch): at the
+// benchmarked shape v is 18 GB that nobody wants to move or copy.  One model's device-resident eigenpairs (sc_modes_*,
+// api.hip) come through here as a batch of one with a row list.
 //
 // One idea carries every selection: k_mode_weights turns (w, selection, counts) into a weight per (structure, listed
 // row), 1 / lambda for a selected row and exactly 0.0 for any other, and then
@@ -257,7 +258,7 @@ __global__ __launch_bounds__(256) void k_baniso_reduce(const double* __restrict_
 
 // ---- dcc ---------------------------------------------------------------------------------------------------------
 // Listed rows k0 .. k0 + kc - 1 of every structure of the slab, component-major, so that the contraction over (row,
-// component) is one GEMM per structure (k_dcc_pack of consumers.hip, batched and weighted):
+// component) is one GEMM per structure:
 //   P[bz][(d * kc + k) * N + a] = V[b, row(k0 + k), dim a + d]        S = the same times s[b, k0 + k]
 // A row without weight is not read: zeros in both operands.  Ragged: N = n_atoms of the structure and only its first
 // dim * N columns are packed (the slot of `stride` elements is sized for the slot order).

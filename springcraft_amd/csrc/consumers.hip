@@ -1,80 +1,22 @@
-// Mode-subset consumers on device-resident eigenpairs.
+// Perturbation response scanning on device-resident eigenpairs.
 //
-// The reference evaluates these with NumPy on the (eig_values, eig_vectors) pair that nma.eigen returns, solving the
-// eigenproblem again for every quantity (nma.py:108-184 msf, :233-359 dcc, :476-524 prs).  Here the eigenpairs stay in
-// HBM (struct sc_modes, api.hip) and each quantity is one or two kernels plus, for the matrix-valued ones, one MFMA
-// GEMM; only the (N) / (N, N) result crosses PCIe.
+// The reference evaluates it with NumPy on the (eig_values, eig_vectors) pair that nma.eigen returns, solving the
+// eigenproblem again (nma.py:476-524).  Here the eigenpairs stay in HBM (struct sc_modes, api.hip): two kernels and one
+// MFMA GEMM, and only the (N, N) result crosses PCIe.
 //
-//   msf[a]    = sum_{k in S} sum_d V[k, dim a + d]^2 / w[k]
-//   dcc[a, b] = sum_{k in S} sum_d V[k, dim a + d] V[k, dim b + d] / w[k]      (optionally / sqrt(dcc[a,a] dcc[b,b]))
 //   prs[a, b] = sum_{d, e} C[3a + d, 3b + e]^2,  C = pinv(H)                      (optionally / prs[a, a])
 //
-// V is stored as the solver leaves it: (n, n) row-major, row k = mode k.
-#include <algorithm>
-
+// V is stored as the solver leaves it: (n, n) row-major, row k = mode k.  The other consumers of one model (msf, dcc,
+// anisotropic tensors, overlaps) are the batch kernels with a batch of one: batch_consumers.hip, mode_overlap.hip.
 #include "common.h"
 #include "gemm_f64.h"
 
 namespace {
 
-// ---- msf: partial sums over chunks of 32 selected modes, then the chunk + dim reduction -----------------------
-constexpr int kMsfChunk = 32;
-
-__global__ __launch_bounds__(256) void k_msf_partial(const double* __restrict__ v, const double* __restrict__ w,
-                                                     const int* __restrict__ sel, int nsel, int n,
-                                                     double* __restrict__ part) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= n) return;
-  const int k0 = blockIdx.y * kMsfChunk, k1 = min(k0 + kMsfChunk, nsel);
-  double acc = 0.0;
-  for (int kk = k0; kk < k1; ++kk) {
-    const int k = sel[kk];
-    const double x = v[(size_t)k * n + j];
-    acc += x * x / w[k];
-  }
-  part[(size_t)blockIdx.y * n + j] = acc;
-}
-
-__global__ __launch_bounds__(256) void k_msf_reduce(const double* __restrict__ part, int nchunk, int n, int dim,
-                                                    double* __restrict__ out) {
-  const int a = blockIdx.x * 256 + threadIdx.x;
-  if (a >= n / dim) return;
-  double acc = 0.0;
-  for (int c = 0; c < nchunk; ++c)
-    for (int d = 0; d < dim; ++d) acc += part[(size_t)c * n + a * dim + d];
-  out[a] = acc;
-}
-
-// ---- dcc: pack the selected modes component-major, so the contraction over (mode, component) is one GEMM ------
-//   P[(d * nsel + kk) * N + a] = V[sel[kk], dim a + d]                S = same / w[sel[kk]]
-__global__ __launch_bounds__(256) void k_dcc_pack(const double* __restrict__ v, const double* __restrict__ w,
-                                                  const int* __restrict__ sel, int nsel, int n, int dim,
-                                                  double* __restrict__ p, double* __restrict__ s) {
-  const int kk = blockIdx.y;
-  const int k = sel[kk];
-  const double inv = 1.0 / w[k];
-  const int N = n / dim;
-  for (int j = blockIdx.x * 256 + threadIdx.x; j < n; j += gridDim.x * 256) {
-    const double x = v[(size_t)k * n + j];
-    const int a = j / dim, d = j - a * dim;
-    const size_t o = ((size_t)d * nsel + kk) * N + a;
-    p[o] = x;
-    s[o] = x * inv;
-  }
-}
-
-// in place: c[a, b] /= sqrt(c[a, a] c[b, b]) needs the original diagonal -> copy it first
+// in place: m[a, b] /= m[a, a] needs the original diagonal -> copy it first
 __global__ void k_copy_diag(const double* __restrict__ c, int N, double* __restrict__ diag) {
   const int a = blockIdx.x * 256 + threadIdx.x;
   if (a < N) diag[a] = c[(size_t)a * N + a];
-}
-
-__global__ __launch_bounds__(256) void k_dcc_norm(double* __restrict__ c, const double* __restrict__ diag, int N) {
-  const int a = blockIdx.x * 256 + threadIdx.x;   // fast axis of the column-major (= row-major, symmetric) result
-  const int b = blockIdx.y;
-  if (a >= N) return;
-  // the reference divides by outer(sqrt(diag), sqrt(diag)) (nma.py:352-354)
-  c[(size_t)b * N + a] = c[(size_t)b * N + a] / (sqrt(diag[a]) * sqrt(diag[b]));
 }
 
 // ---- prs ------------------------------------------------------------------------------------------------------
@@ -126,69 +68,19 @@ __global__ __launch_bounds__(256) void k_prs_norm(double* __restrict__ m, const 
 
 int run_gemm(sc_ctx* ctx, const GemmDesc& D, GemmDesc* d_desc) {
   SC_HIP(ctx, hipMemcpyAsync(d_desc, &D, sizeof(D), hipMemcpyHostToDevice, ctx->stream));
-  // both callers: A(i, k) with unit row stride, B(k, j) with unit column stride
+  // A(i, k) with unit row stride, B(k, j) with unit column stride
   return launch_gemm_f64(ctx, d_desc, 1, D.m, D.n, kGemmTile, 1, false, false, kGemmAmBn);
 }
 
 }  // namespace
 
-size_t modes_scratch_bytes(int64_t n, int dim, int64_t nsel, int what) {
-  const size_t N = (size_t)(n / dim);
-  switch (what) {
-    case 0: return align_up(((size_t)(nsel + kMsfChunk - 1) / kMsfChunk) * n * 8, 256) + align_up(N * 8, 256) + 1024;
-    case 1: return 2 * align_up((size_t)nsel * n * 8, 256) + align_up(N * N * 8, 256) + align_up(N * 8, 256) + 1024;
-    default: return 2 * align_up((size_t)n * n * 8, 256) + align_up(N * N * 8, 256) + align_up(N * 8, 256) + 1024;
-  }
+// bytes of modes_prs_device's scratch
+size_t prs_scratch_bytes(int64_t n) {
+  const size_t N = (size_t)(n / 3);
+  return 2 * align_up((size_t)n * n * 8, 256) + align_up(N * N * 8, 256) + align_up(N * 8, 256) + 1024;
 }
 
-// d_sel: (nsel) int32 mode indices on the device; d_out (N); d_part scratch of modes_scratch_bytes(.., 0)
-int modes_msf_device(sc_ctx* ctx, const double* d_v, const double* d_w, int64_t n64, int dim, const int* d_sel,
-                     int64_t nsel64, char* scratch, double* d_out) {
-  const int n = (int)n64, nsel = (int)nsel64, N = n / dim;
-  hipStream_t st = ctx->stream;
-  if (nsel == 0) {
-    SC_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(double) * N, st));
-    return SC_OK;
-  }
-  const int nchunk = (nsel + kMsfChunk - 1) / kMsfChunk;
-  double* d_part = reinterpret_cast<double*>(scratch);
-  hipLaunchKernelGGL(k_msf_partial, dim3((n + 255) / 256, nchunk), dim3(256), 0, st, d_v, d_w, d_sel, nsel, n, d_part);
-  hipLaunchKernelGGL(k_msf_reduce, dim3((N + 255) / 256), dim3(256), 0, st, d_part, nchunk, n, dim, d_out);
-  SC_HIP(ctx, hipGetLastError());
-  return SC_OK;
-}
-
-int modes_dcc_device(sc_ctx* ctx, const double* d_v, const double* d_w, int64_t n64, int dim, const int* d_sel,
-                     int64_t nsel64, int norm, char* scratch, double* d_out) {
-  const int n = (int)n64, nsel = (int)nsel64, N = n / dim;
-  hipStream_t st = ctx->stream;
-  if (nsel == 0) {
-    SC_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(double) * (size_t)N * N, st));
-  } else {
-    double* d_p = reinterpret_cast<double*>(scratch);
-    double* d_s = reinterpret_cast<double*>(scratch + align_up((size_t)nsel * n * 8, 256));
-    hipLaunchKernelGGL(k_dcc_pack, dim3(std::min((n + 255) / 256, 64), nsel), dim3(256), 0, st, d_v, d_w, d_sel, nsel,
-                       n, dim, d_p, d_s);
-    SC_HIP(ctx, hipGetLastError());
-    GemmDesc D{};
-    D.a = d_s; D.sa_i = 1; D.sa_k = N;
-    D.b = d_p; D.sb_k = N; D.sb_j = 1;
-    D.c = d_out; D.ldc = N; D.m = N; D.n = N; D.k = nsel * dim;
-    D.alpha = 1.0; D.beta = 0.0;
-    GemmDesc* d_desc = reinterpret_cast<GemmDesc*>(scratch + 2 * align_up((size_t)nsel * n * 8, 256) +
-                                                   align_up((size_t)N * 8, 256));
-    SC_TRY(run_gemm(ctx, D, d_desc));
-  }
-  if (norm) {
-    double* d_diag = reinterpret_cast<double*>(scratch + 2 * align_up((size_t)nsel * n * 8, 256));
-    hipLaunchKernelGGL(k_copy_diag, dim3((N + 255) / 256), dim3(256), 0, st, d_out, N, d_diag);
-    hipLaunchKernelGGL(k_dcc_norm, dim3((N + 255) / 256, N), dim3(256), 0, st, d_out, d_diag, N);
-    SC_HIP(ctx, hipGetLastError());
-  }
-  return SC_OK;
-}
-
-// ANM only (n = 3N).  scratch: VS (n^2) | COV (n^2) | diag (N) | desc
+// ANM only (n = 3N).  scratch (prs_scratch_bytes): VS (n^2) | COV (n^2) | diag (N) | desc
 int modes_prs_device(sc_ctx* ctx, const double* d_v, const double* d_w, int64_t n64, double rcond, int norm,
                      char* scratch, double* d_out) {
   const int n = (int)n64, N = n / 3;

@@ -5,9 +5,10 @@ Normal-mode analysis on top of the device eigensolver.
 eigendecomposition, here performed by the hand-written HIP solver (``csrc/eigh*.hip``) instead
 of LAPACK ``dsyevd``.  The mode-subset consumers (``frequencies``, ``mean_square_fluctuation``,
 ``bfactor``, ``dcc``, ``prs``; reference: nma.py:66-359, :476-524) run on the device-resident
-eigenpairs (``csrc/consumers.hip``): the (n, n) eigenvector matrix never crosses PCIe for them.
-``anisotropic_fluctuation`` (no reference counterpart: the per-atom 3x3 tensors whose trace is the MSF) does the same
-through ``csrc/batch_consumers.hip``; ``anisotropy`` reduces such tensors on the host.
+eigenpairs: the (n, n) eigenvector matrix never crosses PCIe for them.  ``mean_square_fluctuation``, ``bfactor``, ``dcc``
+and ``anisotropic_fluctuation`` (no reference counterpart: the per-atom 3x3 tensors whose trace is the MSF) are the batch
+kernels of ``csrc/batch_consumers.hip`` with a batch of one, ``prs`` is ``csrc/consumers.hip``; ``anisotropy`` reduces the
+tensors on the host.
 ``overlap`` and ``collectivity`` (no reference counterpart: which modes carry a displacement, and how many atoms a mode
 moves) are one pass along the selected rows (``csrc/mode_overlap.hip``); ``cumulative_overlap`` is array arithmetic.
 ``normal_mode``, ``linear_response`` and ``effector_sensor`` are O(n) / O(n^2) host arithmetic on

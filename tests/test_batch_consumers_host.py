@@ -67,6 +67,25 @@ def test_non_integer_indices_are_rejected(rows):
         rows([6.5, 7.0], 6, None, 300)
 
 
+@pytest.mark.parametrize("ntriv", [6, 1])
+@pytest.mark.parametrize("subset", [None, (0, 11), (6, 25), (9, 30), (0, 3)])
+def test_from_row_start_is_the_first_non_trivial_row(rows, ntriv, subset):
+    """
+    "Every solved non-trivial mode" is SC_SEL_FROM_ROW from the number of trivial rows at the head of ``w`` / ``v``, one
+    formula for both batch solvers: the first row ``batch_mode_rows(None, ...)`` lists, or ``nvec`` when it lists none.
+    """
+    from springcraft_amd.batch import _trivial_rows
+
+    m = 33
+    lo, hi = (0, m - 1) if subset is None else subset
+    nvec = hi - lo + 1
+    listed = rows(None, ntriv, subset, m)
+    start = _trivial_rows(ntriv, lo, nvec)
+    assert start == (int(listed[0]) if len(listed) else nvec)
+    assert np.array_equal(listed, np.arange(start, nvec))
+    assert start == sum(1 for r in range(nvec) if lo + r < ntriv)
+
+
 def test_new_symbols_are_declared_exported_and_typed():
     from springcraft_amd import _hip
 

@@ -1,7 +1,7 @@
 """
-GPU parity tests for the mode-subset consumers that run on device-resident eigenpairs
-(``csrc/consumers.hip`` through ``sc_modes_*``): frequencies, mean-square fluctuations, B-factors, dynamic
-cross-correlations and perturbation response scanning.
+GPU parity tests for the mode-subset consumers that run on device-resident eigenpairs through ``sc_modes_*``:
+frequencies, mean-square fluctuations, B-factors and dynamic cross-correlations (the batch kernels of
+``csrc/batch_consumers.hip`` with a batch of one) and perturbation response scanning (``csrc/consumers.hip``).
 
 The golden vectors are the reference's own fixtures (ProDy / Bio3D results, tests/data of the reference, compared
 the way tests/test_anm.py:145-334, :337-358 and tests/test_gnm.py:107-152 do) plus plain-NumPy evaluations of the
@@ -267,3 +267,37 @@ def test_dcc_all_modes_follows_the_pinv_rule_on_a_nearly_disconnected_network(sc
     n = len(coord)
     tr = covh.reshape(n, 3, n, 3).swapaxes(1, 2).trace(axis1=2, axis2=3)
     assert np.allclose(sc.ANM(coord, weak).dcc(norm=False), tr, rtol=1e-8, atol=1e-9)
+
+
+# ---- a model is a batch of one -----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n_atoms,dim", [(33, 3), (50, 3), (33, 1)])
+def test_model_msf_and_dcc_are_the_bits_of_a_batch_of_one(sc, n_atoms, dim):
+    """
+    ``sc_modes_msf`` / ``sc_modes_dcc`` run the batch kernels with a batch of one, so for the same eigenpairs and the same
+    list a model and a one-structure ``DeviceBatchSolver`` give the same bits.  m = 99 is odd (the 8-byte MSF loads),
+    m = 150 even (the 16-byte loads), the GNM has dim 1.  The model's own (w, v) are copied into the solver, so the
+    solvers' rounding plays no part.
+    """
+    import torch
+
+    from springcraft_amd.batch import DeviceBatchSolver
+
+    coord = synthetic_coord(n_atoms, 7)
+    model = sc.ANM(coord, sc.InvariantForceField(13.0)) if dim == 3 else sc.GNM(coord, sc.InvariantForceField(10.0))
+    modes = model._modes_device()
+    w, v = modes.eigen()
+    s = DeviceBatchSolver(n_atoms, 1, sc.InvariantForceField(13.0), dim=dim)
+    s.w[0].copy_(torch.from_numpy(w))
+    s.v[0].copy_(torch.from_numpy(np.ascontiguousarray(v)))
+    ntriv = 6 if dim == 3 else 1
+    for sel in (np.arange(ntriv, dim * n_atoms), np.arange(ntriv, ntriv + 20), np.array([9, 7, 9])):
+        msf = modes.msf(sel)
+        assert np.all(np.isfinite(msf)) and np.all(msf > 0)
+        assert np.array_equal(msf, s.mean_square_fluctuation(mode_subset=sel)[0].cpu().numpy())
+        for norm in (False, True):
+            assert np.array_equal(modes.dcc(sel, norm), s.dcc(mode_subset=sel, norm=norm)[0].cpu().numpy())
+        if dim == 3:
+            assert np.allclose(modes.aniso(sel)[:, :3].sum(axis=1), msf)     # other kernels: not bitwise
+    empty = np.array([], dtype=np.int64)
+    assert np.array_equal(modes.msf(empty), np.zeros(n_atoms))
+    assert np.array_equal(modes.dcc(empty, False), np.zeros((n_atoms, n_atoms)))

@@ -67,7 +67,7 @@ def case(torch, label, n_atoms, batch, subset, reps, runs):
     rel = float(((trace - msf).abs() / msf.abs()).max())
     del u, trace, msf
     # the kernels alone: the C entry on a preallocated output, with the selection the method builds
-    sel, counts, _keep = s._selection(None, pinv_default=False)
+    sel, counts = s._selection(None, pinv_default=False)
     out6 = torch.empty((batch, n_atoms, 6), dtype=torch.float64, device=s.device)
     L = _hip.lib()
 
