@@ -375,6 +375,12 @@ int sc_modes_aniso(sc_modes* modes, const int64_t* mode_idx, int64_t k, double* 
  * Computed by sc_dev_modes_overlap_f64's kernel with a batch of one. */
 int sc_modes_overlap(sc_modes* modes, const int64_t* mode_idx, int64_t k, const double* disp, int64_t q,
                      double* overlap_out, double* collectivity_out);
+/* No reference counterpart (ProDy: calcDistFlucts / calcMechStiff).  ANM only (a dim-1 object: SC_ERR_INVALID_ARG).
+ * coord: host (n / 3, 3), the coordinates the model was built from; out: host (n / 3, n / 3), for atoms a, c the
+ * fluctuation of their distance over the k listed modes, sum of (n_ac . (v[c] - v[a]))^2 / w with n_ac the unit vector
+ * from a to c; symmetric bit for bit, the diagonal exactly 0, NaN for two distinct atoms at one position.  Computed by
+ * sc_dev_modes_distfluct_f64's kernel with a batch of one (no atom scale: a mass-weighted model's modes enter as they are). */
+int sc_modes_distfluct(sc_modes* modes, const int64_t* mode_idx, int64_t k, const double* coord, double* out);
 /* out (n / dim, n / dim): sum over the listed modes of <v_a, v_b> / w; norm != 0 divides by sqrt(c_aa c_bb). */
 int sc_modes_dcc(sc_modes* modes, const int64_t* mode_idx, int64_t k, int norm, double* out);
 /* ANM only. out (n / 3, n / 3) row-major: sums of the squared 3x3 blocks of pinv(H, rcond) (numpy hermitian
@@ -452,10 +458,29 @@ int sc_dev_modes_aniso_f64(sc_ctx* ctx, const double* d_w, const double* d_v, in
 int sc_dev_modes_overlap_f64(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
                              const double* d_disp, int64_t q, const int64_t* d_counts, double* d_overlap,
                              double* d_collectivity);
+/* Fluctuations of the inter-atom distances over the selected rows: no reference counterpart (ProDy: calcDistFlucts, and
+ * calcMechStiff for k_B T over it; Bio3D derives it from the covariance); replaces copying d_v to the host or forming the
+ * 3N x 3N covariance for a (batch, N, N) result.  ANM only: m % 3 == 0 is required (SC_ERR_INVALID_ARG otherwise), N = m / 3.
+ *
+ *   F[b, a, c] = sum_r  s[b, r] * ( n_ac . (u_r[c] - u_r[a]) )^2,   n_ac = (x_c - x_a) / |x_c - x_a|
+ *
+ * with s and the selection as above, x = d_coord (batch, N, 3) -- the coordinates the matrices were assembled from -- and
+ * u_r[a] = d_atom_scale[b, a] * V[b, r, 3 a .. 3 a + 2]; d_atom_scale (batch, N) may be NULL (1): a mass-weighted solve
+ * passes its 1 / sqrt(mass) to get Cartesian distances.  d_out (batch, N, N): F[a, c] and F[c, a] are the same bits, F[a,
+ * a] is exactly 0 (also in a structure whose other entries are NaN), F >= 0 for positive weights; two distinct atoms at
+ * one position give NaN for that pair (0 / 0 has no direction).  The sum is taken directly, pair by pair on the float64
+ * vector unit with the unit vectors and the sums in registers (the expanded form over covariance blocks cancels for
+ * neighbours): one fixed sequence over the listed rows per pair, no atomics, no partial sums, so a structure's result does
+ * not depend on the batch size or on its position, bit for bit.  A row without weight is not read, nor is a listed row
+ * outside 0..nvec-1, which turns the structure's result into NaN.  Enqueue only. */
+int sc_dev_modes_distfluct_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                               const sc_mode_selection* sel, const int64_t* d_counts, const double* d_coord,
+                               const double* d_atom_scale, double* d_out);
 /* Bytes of device workspace the three entries above hold for such a call (allocated lazily, cached, grown on demand --
  * the one step of a first call that waits for the stream).  n_sel: rows that carry a weight (nvec - row0, n_rows, or
  * nvec for SC_SEL_PINV); what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3 and m % 3 == 0, else 0), 3 = overlaps /
- * collectivities (always 0: sc_dev_modes_overlap_f64 holds no workspace); budget_bytes as above. */
+ * collectivities (always 0: sc_dev_modes_overlap_f64 holds no workspace), 4 = distance fluctuations (the weights only; dim
+ * 3 and m % 3 == 0, else 0); budget_bytes as above. */
 int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
                                      int64_t budget_bytes);
 
@@ -503,6 +528,14 @@ int sc_batch_plan_modes_aniso_f64(sc_batch_plan* plan, const double* d_w, const 
 int sc_batch_plan_modes_overlap_f64(sc_batch_plan* plan, const double* d_v, int64_t nvec, int64_t first_row,
                                     const double* d_disp, int64_t q, const int64_t* d_counts, double* d_overlap,
                                     double* d_collectivity);
+/* distance fluctuations (a plan of dim 1: SC_ERR_INVALID_ARG), as sc_dev_modes_distfluct_f64 -- no reference counterpart
+ * (ProDy: calcDistFlucts / calcMechStiff): d_coord (sum n_atoms, 3) and d_atom_scale (sum n_atoms,) or NULL packed as
+ * sc_batch_plan_assemble_f64 takes its coordinates and weights, N the structure's own n_atoms, d_out (sum n_atoms^2,)
+ * packed like the dcc.  Pad rows never carry a weight, pad columns are never read.  A structure's bits depend on its own
+ * size and the selection, not on its neighbours or its position. */
+int sc_batch_plan_modes_distfluct_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
+                                      const sc_mode_selection* sel, const int64_t* d_counts, const double* d_coord,
+                                      const double* d_atom_scale, double* d_out);
 /* What sc_dev_modes_workspace_bytes answers for a uniform batch, for the plan's (count, order). */
 int64_t sc_batch_plan_modes_workspace_bytes(const sc_batch_plan* plan, int64_t nvec, int64_t n_sel, int what,
                                             int64_t budget_bytes);

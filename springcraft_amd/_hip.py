@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = [
     "sc_batch_plan_modes_dcc_f64", "sc_batch_plan_modes_workspace_bytes",
     "sc_modes_aniso", "sc_dev_modes_aniso_f64", "sc_batch_plan_modes_aniso_f64",
     "sc_modes_overlap", "sc_dev_modes_overlap_f64", "sc_batch_plan_modes_overlap_f64",
+    "sc_modes_distfluct", "sc_dev_modes_distfluct_f64", "sc_batch_plan_modes_distfluct_f64",
 ]
 
 SC_SEL_FROM_ROW = 0
@@ -232,6 +233,9 @@ def lib():
         "sc_modes_overlap": (i32, [vp, vp, i64, vp, i64, vp, vp]),
         "sc_dev_modes_overlap_f64": (i32, [vp, vp, i64, i64, i64, i32, vp, i64, vp, vp, vp]),
         "sc_batch_plan_modes_overlap_f64": (i32, [vp, vp, i64, i64, vp, i64, vp, vp, vp]),
+        "sc_modes_distfluct": (i32, [vp, vp, i64, vp, vp]),
+        "sc_dev_modes_distfluct_f64": (i32, [vp, vp, vp, i64, i64, i64, P(ModeSelection), vp, vp, vp, vp]),
+        "sc_batch_plan_modes_distfluct_f64": (i32, [vp, vp, vp, i64, P(ModeSelection), vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -329,7 +333,7 @@ class Context:
 class Modes:
     """
     Owns one ``sc_modes``: all eigenpairs of a model, resident in device memory, plus the consumers that
-    work on them there (msf, dcc, prs, anisotropic tensors, overlaps and collectivities).  ``dim`` is 1 for a GNM and 3 for an ANM.
+    work on them there (msf, dcc, prs, anisotropic tensors, overlaps and collectivities, distance fluctuations).  ``dim`` is 1 for a GNM and 3 for an ANM.
     """
 
     def __init__(self, ctx, handle, dim):
@@ -389,6 +393,17 @@ class Modes:
         idx = self._index_list(mode_idx)
         out = np.empty((self.order // 3, 6))
         self._ctx.check(self._L.sc_modes_aniso(self._h, ptr(idx), len(idx), ptr(out)))
+        return out
+
+    def distfluct(self, mode_idx, coord):
+        """(n_atoms, n_atoms) fluctuations of the inter-atom distances over the listed modes; ``coord`` (n_atoms, 3) (ANM only)."""
+        idx = self._index_list(mode_idx)
+        n = self.order // 3
+        coord = np.ascontiguousarray(coord, dtype=np.float64)
+        if coord.shape != (n, 3):
+            raise ValueError(f"Expected coordinates of shape {(n, 3)}, got {coord.shape}")
+        out = host_array((n, n))
+        self._ctx.check(self._L.sc_modes_distfluct(self._h, ptr(idx), len(idx), ptr(coord), ptr(out)))
         return out
 
     def overlap(self, mode_idx, disp=None, collectivity=False):

@@ -223,6 +223,26 @@ class _BatchSolver:
         self._rows_keep = keep      # (the device list outlives the enqueued call)
         return sel, (C.c_void_p(self.counts.data_ptr()) if self.window is not None else None)
 
+    def _device_f64(self, t, shape, name):
+        """A consumer's extra input, checked on the host: a contiguous CUDA float64 tensor of ``shape`` on the solver's device."""
+        torch = self.torch
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous CUDA float64 tensor of shape {shape}")
+        if t.device != torch.device(self.device):
+            raise ValueError(f"{name} is on {t.device}, the solver on {self.device}")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"Expected {name} of shape {tuple(shape)}, got {tuple(t.shape)}")
+        return C.c_void_p(t.data_ptr())
+
+    def _distance_fluctuation_args(self, coord, atoms_shape, projected, atom_scale):
+        """Host checks of ``distance_fluctuation``: (coordinate pointer, scale pointer or None); nothing is enqueued."""
+        if projected and self.dim != 3:
+            raise ValueError("projected distance fluctuations need an ANM solver (dim=3); use projected=False")
+        self._need_vectors()
+        cp = self._device_f64(coord, tuple(atoms_shape) + (3,), "coord")
+        sp = None if atom_scale is None else self._device_f64(atom_scale, atoms_shape, "atom_scale")
+        return cp, sp
+
     def _frequencies(self):
         """(batch, nvec) ``sqrt(lambda) / (2 pi)``; without a window the trivial rows enter as ``abs(lambda)``."""
         w = self.w.clone()
@@ -453,6 +473,46 @@ class DeviceBatchSolver(_BatchSolver):
         self._need_vectors()
         return self._overlap_call(None, 0, True)[1]
 
+    def distance_fluctuation(self, coord, mode_subset=None, projected=True, atom_scale=None, tem=None, tem_factors=K_B):
+        """
+        (batch, n_atoms, n_atoms) fluctuations of the inter-atom distances over the selected modes
+        (:func:`nma.distance_fluctuation`; no reference counterpart, ProDy: ``calcDistFlucts`` / ``calcMechStiff``):
+        ``F[b, a, c] = sum_k (n_ac . (u_k[c] - u_k[a]))^2 / lambda_k`` with ``n_ac`` the unit vector from atom a to atom c
+        of ``coord``, the (batch, n_atoms, 3) CUDA float64 tensor given to :meth:`solve`.  :func:`nma.effective_stiffness`
+        turns it into the distances' harmonic constants on the device.
+
+        ``mode_subset``, the window, ``subset_by_index`` and failed structures exactly as in
+        :meth:`mean_square_fluctuation`.  ``atom_scale``: None, or a (batch, n_atoms) CUDA float64 tensor with ``u_k[a] =
+        atom_scale[a] * v_k[a]``; None takes the rows of ``v`` as they are, like every other consumer, so a solver with
+        ``masses`` wants ``atom_scale=solver.inv_sqrt_mass`` for Cartesian distances.
+        ``projected=True`` (ANM solvers; ``dim != 3`` raises ValueError before anything is enqueued) sums every pair
+        directly on the device: ``F`` equals its transpose bit for bit, the diagonal is exactly 0 (also in a failed
+        structure, whose other entries are NaN), two distinct atoms at one position give NaN for that pair, and a
+        structure's bits do not depend on the batch size or its position.  ``projected=False`` is ``c_aa + c_cc - 2
+        c_ac`` of ``dcc(norm=False)`` over the same selection (GNM and ANM; ``coord`` is only checked).
+        Only enqueues.
+        """
+        n = self.n_atoms
+        cp, sp = self._distance_fluctuation_args(coord, (self.batch, n), projected, atom_scale)
+        sel, counts = self._selection(mode_subset, pinv_default=False)
+        out = self.torch.empty((self.batch, n, n), dtype=self.torch.float64, device=self.device)
+        wp, vp = C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr())
+        if projected:
+            self.ctx.check(self._L.sc_dev_modes_distfluct_f64(
+                self.ctx.handle, wp, vp, self.m, self.w.shape[1], self.batch, C.byref(sel), counts, cp, sp,
+                C.c_void_p(out.data_ptr())))
+        else:
+            self.ctx.check(self._L.sc_dev_modes_dcc_f64(
+                self.ctx.handle, wp, vp, self.m, self.w.shape[1], self.batch, self.dim, C.byref(sel), counts, 0,
+                int(self.consumer_budget_bytes or 0), C.c_void_p(out.data_ptr())))
+            if atom_scale is not None:
+                out *= atom_scale[:, :, None] * atom_scale[:, None, :]
+            diag = out.diagonal(dim1=1, dim2=2)
+            out = (diag[:, :, None] + diag[:, None, :]) - 2 * out
+        if tem is not None:
+            out *= tem * tem_factors
+        return out
+
     def dcc(self, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
         """
         (batch, n_atoms, n_atoms) dynamic cross-correlations over the selected modes (nma.py:233-359); ``norm`` divides by
@@ -512,8 +572,8 @@ class RaggedBatchSolver(_BatchSolver):
     ``results()`` cuts ``v_i`` to the structure's own ``dim * n_i`` columns and, behind a window solve, both to the first
     ``min(counts[i], K)`` rows.
 
-    :meth:`frequencies`, :meth:`mean_square_fluctuation`, :meth:`bfactor`, :meth:`dcc` and :meth:`anisotropic_fluctuation`
-    (and, per row instead of per atom, :meth:`overlap` and :meth:`collectivity`)
+    :meth:`frequencies`, :meth:`mean_square_fluctuation`, :meth:`bfactor`, :meth:`dcc`, :meth:`distance_fluctuation` and
+    :meth:`anisotropic_fluctuation` (and, per row instead of per atom, :meth:`overlap` and :meth:`collectivity`)
     have the meaning, defaults and trivial-mode rules of :class:`DeviceBatchSolver`'s, per structure: they only enqueue and
     return a list of CUDA tensors, (n_i,) / (n_i, n_i) / (n_i, 3, 3), views into one packed buffer.  Pad rows and columns are never read into a result, and the
     ``|lambda| > 1e-6 max|lambda|`` rule of the dcc default takes its maximum over the structure's own eigenvalues.
@@ -753,6 +813,40 @@ class RaggedBatchSolver(_BatchSolver):
         self._need_vectors()
         co = self._overlap_call(None, 0, True)[1]
         return [co[b, :r] for b, r in enumerate(self._subset_plan["row_limits"])]
+
+    def distance_fluctuation(self, coord, mode_subset=None, projected=True, atom_scale=None, tem=None, tem_factors=K_B):
+        """
+        [(n_i, n_i), ...] fluctuations of the inter-atom distances, as :meth:`DeviceBatchSolver.distance_fluctuation`
+        (no reference counterpart) with the selection of :meth:`mean_square_fluctuation`: views into one buffer packed
+        like :meth:`dcc`'s.  ``coord`` is the packed (sum(sizes), 3) tensor given to :meth:`solve`, ``atom_scale`` None or a
+        packed (sum(sizes),) tensor -- ``solver.inv_sqrt_mass`` for Cartesian distances behind ``masses``.  Every
+        structure is summed over its own atoms and rows: pad rows never carry a weight, pad columns are never read.
+        """
+        total = int(self.offsets[-1])
+        cp, sp = self._distance_fluctuation_args(coord, (total,), projected, atom_scale)
+        sel, counts = self._selection(mode_subset, pinv_default=False)
+        sq = np.concatenate([[0], np.cumsum(np.asarray(self.sizes, dtype=np.int64) ** 2)])
+        out = self.torch.empty((int(sq[-1]),), dtype=self.torch.float64, device=self.device)
+        wp, vp = C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr())
+        if projected:
+            self.ctx.check(self._L.sc_batch_plan_modes_distfluct_f64(
+                self._plan, wp, vp, self.w.shape[1], C.byref(sel), counts, cp, sp, C.c_void_p(out.data_ptr())))
+        else:
+            self.ctx.check(self._L.sc_batch_plan_modes_dcc_f64(
+                self._plan, wp, vp, self.w.shape[1], C.byref(sel), counts, 0, int(self.consumer_budget_bytes or 0),
+                C.c_void_p(out.data_ptr())))
+        views = [out[sq[b]: sq[b + 1]].view(n, n) for b, n in enumerate(self.sizes)]
+        if not projected:
+            for b, c in enumerate(views):
+                if atom_scale is not None:
+                    sc = atom_scale[self.offsets[b]: self.offsets[b + 1]]
+                    c *= sc[:, None] * sc[None, :]
+                diag = c.diagonal().clone()
+                c *= -2
+                c += diag[:, None] + diag[None, :]
+        if tem is not None:
+            out *= tem * tem_factors
+        return views
 
     def dcc(self, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
         """

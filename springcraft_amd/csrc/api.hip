@@ -961,6 +961,15 @@ int sc_dev_modes_aniso_f64(sc_ctx* ctx, const double* d_w, const double* d_v, in
   return batch_aniso_device(ctx, d_w, d_v, m, nvec, batch, *sel, d_counts, 0, d_out);
 }
 
+int sc_dev_modes_distfluct_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                               const sc_mode_selection* sel, const int64_t* d_counts, const double* d_coord,
+                               const double* d_atom_scale, double* d_out) {
+  SC_TRY(check_modes_args(ctx, d_w, d_v, m, nvec, batch, 3, sel, d_out));
+  if (!d_coord) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "distance fluctuations need the coordinates");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return batch_distfluct_device(ctx, d_w, d_v, m, nvec, batch, *sel, d_counts, d_coord, d_atom_scale, d_out);
+}
+
 // (shared with the plan entry: `padded` = m is a plan's slot order)
 static int check_overlap_args(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
                               const double* d_disp, int64_t q, const double* d_overlap, const double* d_collectivity,
@@ -993,7 +1002,7 @@ int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int
                                      int64_t budget_bytes) {
   if (m <= 0 || nvec <= 0 || batch <= 0 || n_sel < 0 || (dim != 1 && dim != 3) || budget_bytes < 0) return 0;
   if (what == 3) return 0;   // overlaps and collectivities hold no workspace
-  if (what == 2 && (dim != 3 || m % 3 != 0)) return 0;
+  if ((what == 2 || what == 4) && (dim != 3 || m % 3 != 0)) return 0;
   return (int64_t)batch_modes_workspace_bytes(m, nvec, batch, dim, n_sel, what, (size_t)budget_bytes);
 }
 
@@ -1369,6 +1378,19 @@ int sc_batch_plan_modes_aniso_f64(sc_batch_plan* plan, const double* d_w, const 
   return batch_aniso_device(ctx, d_w, d_v, plan->order, nvec, plan->count, *sel, d_counts, 0, d_out, &rv);
 }
 
+int sc_batch_plan_modes_distfluct_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
+                                      const sc_mode_selection* sel, const int64_t* d_counts, const double* d_coord,
+                                      const double* d_atom_scale, double* d_out) {
+  SC_TRY(check_plan_modes_args(plan, d_w, d_v, nvec, sel, d_out));
+  sc_ctx* ctx = plan->ctx;
+  if (plan->dim != 3) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "distance fluctuations need an ANM plan (dim 3)");
+  if (!d_coord) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "distance fluctuations need the coordinates");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const RaggedView rv = plan_view(plan, (int)sel->reserved);
+  return batch_distfluct_device(ctx, d_w, d_v, plan->order, nvec, plan->count, *sel, d_counts, d_coord, d_atom_scale,
+                                d_out, &rv);
+}
+
 int sc_batch_plan_modes_overlap_f64(sc_batch_plan* plan, const double* d_v, int64_t nvec, int64_t first_row,
                                     const double* d_disp, int64_t q, const int64_t* d_counts, double* d_overlap,
                                     double* d_collectivity) {
@@ -1389,7 +1411,7 @@ int64_t sc_batch_plan_modes_workspace_bytes(const sc_batch_plan* plan, int64_t n
                                             int64_t budget_bytes) {
   if (!plan || nvec <= 0 || n_sel < 0 || budget_bytes < 0) return 0;
   if (what == 3) return 0;
-  if (what == 2 && plan->dim != 3) return 0;
+  if ((what == 2 || what == 4) && plan->dim != 3) return 0;
   const RaggedView rv = plan_view(plan, 0);
   return (int64_t)batch_modes_workspace_bytes(plan->order, nvec, plan->count, plan->dim, n_sel, what, (size_t)budget_bytes,
                                               &rv);
@@ -1567,6 +1589,33 @@ int sc_modes_aniso(sc_modes* m, const int64_t* mode_idx, int64_t k, double* out)
   return modes_list_call(m, mode_idx, k, (size_t)(m->n / 3) * 6, out, [m](const sc_mode_selection& sel, double* d_out) {
     return batch_aniso_device(m->ctx, m->d_w, m->d_v, m->n, m->n, 1, sel, nullptr, 0, d_out);
   });
+}
+
+int sc_modes_distfluct(sc_modes* m, const int64_t* mode_idx, int64_t k, const double* coord, double* out) {
+  if (!m) return SC_ERR_INVALID_ARG;
+  sc_ctx* ctx = m->ctx;
+  if (m->dim != 3) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "distance fluctuations need an ANM (dim 3)");
+  if (k < 0 || k > INT32_MAX / 4 || (k > 0 && !mode_idx) || (m->n > 0 && (!coord || !out)))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t N = (size_t)(m->n / 3);
+  SC_TRY(sc_reserve_scratch(ctx, align_up((size_t)k * 4, 256) + align_up(N * 24, 256) + align_up(N * N * 8, 256) + 1024));
+  Bump bump{(char*)ctx->scratch};
+  int* d_sel = bump.take<int>((size_t)std::max<int64_t>(k, 1));
+  double* d_coord = bump.take<double>(std::max<size_t>(N * 3, 1));
+  double* d_out = bump.take<double>(std::max<size_t>(N * N, 1));
+  SC_TRY(stage_mode_list(m, mode_idx, k, d_sel));   // (the index errors come first, whatever else is empty)
+  if (m->n == 0) return SC_OK;
+  SC_HIP(ctx, hipMemcpyAsync(d_coord, coord, N * 24, hipMemcpyHostToDevice, ctx->stream));
+  sc_mode_selection sel{};
+  sel.kind = SC_SEL_ROWS;
+  sel.d_rows = d_sel;
+  sel.n_rows = k;
+  // the batch kernel with a batch of one: one arithmetic order for a model, a batch and a ragged batch
+  SC_TRY(batch_distfluct_device(ctx, m->d_w, m->d_v, m->n, m->n, 1, sel, nullptr, d_coord, nullptr, d_out));
+  SC_HIP(ctx, hipMemcpyAsync(out, d_out, N * N * 8, hipMemcpyDeviceToHost, ctx->stream));
+  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SC_OK;
 }
 
 int sc_modes_overlap(sc_modes* m, const int64_t* mode_idx, int64_t k, const double* disp, int64_t q, double* overlap_out,

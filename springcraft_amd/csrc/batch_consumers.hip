@@ -370,8 +370,11 @@ int64_t aniso_slab(int64_t m, int64_t nsel, int64_t batch, size_t budget) {
   return std::min(slab, std::max<int64_t>(batch, 1));
 }
 
-int launch_weights(sc_ctx* ctx, const double* d_w, int64_t nvec, int64_t batch, const sc_mode_selection& sel,
-                   int64_t nsel, const int64_t* d_counts, double* d_s, const RaggedView* rv) {
+}  // namespace
+
+// (declared in eigh_internal.h: dist_fluct.hip takes its weights from here too)
+int launch_mode_weights(sc_ctx* ctx, const double* d_w, int64_t nvec, int64_t batch, const sc_mode_selection& sel,
+                        int64_t nsel, const int64_t* d_counts, double* d_s, const RaggedView* rv) {
   hipLaunchKernelGGL(k_mode_weights, dim3((unsigned)batch), dim3(256), 0, ctx->stream, d_w, (int)nvec,
                      sel.kind == SC_SEL_PINV ? 1 : 0, sel.kind == SC_SEL_FROM_ROW ? (int)sel.row0 : 0,
                      sel.kind == SC_SEL_ROWS ? sel.d_rows : nullptr, (int)nsel, sel.rcond,
@@ -380,8 +383,6 @@ int launch_weights(sc_ctx* ctx, const double* d_w, int64_t nvec, int64_t batch, 
   SC_HIP(ctx, hipGetLastError());
   return SC_OK;
 }
-
-}  // namespace
 
 size_t modes_budget_default() {
   static const size_t v = [] {
@@ -400,7 +401,8 @@ int64_t batch_modes_nsel(const sc_mode_selection& sel, int64_t nvec) {
   }
 }
 
-// weights (batch, n_sel) | msf, tensors: partial sums of one slab | dcc: P and S of one slab, diagonals (batch, N), records
+// weights (batch, n_sel) | msf, tensors: partial sums of one slab | dcc: P and S of one slab, diagonals (batch, N), records |
+// distance fluctuations: nothing more
 // (ragged: m is the slot order, the diagonals are packed over all atoms)
 size_t batch_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t nsel, int what,
                                    size_t budget, const RaggedView* rv) {
@@ -413,6 +415,8 @@ size_t batch_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int d
   } else if (what == 2) {
     const int chunk = msf_chunk(nsel);
     bytes += align_up((size_t)aniso_slab(m, nsel, batch, budget) * ((nsel + chunk - 1) / chunk) * 6 * (m / 3) * 8, 256);
+  } else if (what == 4) {
+    // distance fluctuations (dist_fluct.hip): the weights alone, a pair's sum never leaves its lane
   } else {
     const DccPlan pl = dcc_plan(m, nsel, batch, budget);
     const size_t diag = (size_t)(rv ? rv->total_atoms : batch * (m / dim));
@@ -439,7 +443,7 @@ int batch_msf_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
   char* base = (char*)ctx->modes_ws;
   double* d_s = reinterpret_cast<double*>(base);
   double* d_part = reinterpret_cast<double*>(base + align_up((size_t)batch * nsel * 8, 256));
-  SC_TRY(launch_weights(ctx, d_w, nvec, batch, sel, nsel, d_counts, d_s, rv));
+  SC_TRY(launch_mode_weights(ctx, d_w, nvec, batch, sel, nsel, d_counts, d_s, rv));
   const int chunk = msf_chunk(nsel);
   const int nchunk = (int)((nsel + chunk - 1) / chunk);
   const int64_t slab = msf_slab(m, nsel, batch, budget);
@@ -480,7 +484,7 @@ int batch_aniso_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_
   char* base = (char*)ctx->modes_ws;
   double* d_s = reinterpret_cast<double*>(base);
   double* d_part = reinterpret_cast<double*>(base + align_up((size_t)batch * nsel * 8, 256));
-  SC_TRY(launch_weights(ctx, d_w, nvec, batch, sel, nsel, d_counts, d_s, rv));
+  SC_TRY(launch_mode_weights(ctx, d_w, nvec, batch, sel, nsel, d_counts, d_s, rv));
   const int chunk = msf_chunk(nsel);
   const int nchunk = (int)((nsel + chunk - 1) / chunk);
   const int64_t slab = aniso_slab(m, nsel, batch, budget);
@@ -520,7 +524,7 @@ int batch_dcc_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
   if (nsel == 0) {
     SC_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(double) * (rv ? (size_t)rv->total_sq : (size_t)batch * N * N), st));
   } else {
-    SC_TRY(launch_weights(ctx, d_w, nvec, batch, sel, nsel, d_counts, d_s, rv));
+    SC_TRY(launch_mode_weights(ctx, d_w, nvec, batch, sel, nsel, d_counts, d_s, rv));
     const int* rows = sel.kind == SC_SEL_ROWS ? sel.d_rows : nullptr;
     const int row0 = sel.kind == SC_SEL_FROM_ROW ? (int)sel.row0 : 0;
     // one block tile for every launch of this call, the short last slab included: a structure rounds the same way in

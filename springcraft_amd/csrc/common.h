@@ -296,7 +296,7 @@ int modes_prs_device(sc_ctx* ctx, const double* d_v, const double* d_w, int64_t 
                      char* scratch, double* d_out);
 
 // ---- the same quantities for a batch, on the solver's own (w, v, counts) tensors (batch_consumers.hip) ----------
-// what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3).  n_sel: weighted rows per structure (batch_modes_nsel).  budget: bytes the partial sums (msf) /
+// what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3), 4 = distance fluctuations (dim 3; dist_fluct.hip).  n_sel: weighted rows per structure (batch_modes_nsel).  budget: bytes the partial sums (msf) /
 // the packed GEMM operands (dcc) may take, 0 = modes_budget_default().  ragged: null for a uniform batch (d_out (batch,
 // m / dim[, m / dim])), or the plan's records: m is then the slot order and d_out is packed.
 // Ragged batches (sc_batch_plan): one record per structure in the plan's device blob, read by the window count and the
@@ -326,6 +326,14 @@ int batch_dcc_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
 int batch_aniso_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
                        const sc_mode_selection& sel, const int64_t* d_counts, size_t budget, double* d_out,
                        const RaggedView* ragged = nullptr);
+
+// ---- fluctuations of the inter-atom distances (dist_fluct.hip) ----------------------------------------------------
+// dim 3 only: d_out[b, a, c] = sum_r s[b, r] (n_ac . (u_r[c] - u_r[a]))^2, n_ac the unit vector from atom a to atom c of
+// d_coord (batch, m / 3, 3), u_r[a] = d_atom_scale[b, a] (null: 1) times the atom's three components of row r.  Exactly
+// symmetric, the diagonal exactly 0.  Ragged: coordinates and scales packed at atom_off, d_out packed at sq_off.
+int batch_distfluct_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                           const sc_mode_selection& sel, const int64_t* d_counts, const double* d_coord,
+                           const double* d_atom_scale, double* d_out, const RaggedView* ragged = nullptr);
 
 // ---- overlaps with displacement vectors and collectivities of the modes (mode_overlap.hip) -----------------------
 // One pass over the rows of d_v (batch, nvec, m): d_overlap (batch, q, nout) and d_coll (batch, nout), either may be null

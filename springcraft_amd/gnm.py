@@ -76,6 +76,10 @@ class GNM(ElasticNetworkModel):
         """Overlap of the selected modes with one or q displacements, (k,) / (q, k) (:func:`nma.overlap`)."""
         return nma.overlap(self, displacement, mode_subset)
 
+    def distance_fluctuation(self, mode_subset=None, projected=True, tem=None, tem_factors=K_B):
+        """Fluctuations of the inter-atom distances, (n, n) (:func:`nma.distance_fluctuation`; no reference counterpart)."""
+        return nma.distance_fluctuation(self, mode_subset, projected, tem, tem_factors)
+
     def collectivity(self, mode_subset=None):
         """Collectivity of the selected modes, (k,) (:func:`nma.collectivity`)."""
         return nma.collectivity(self, mode_subset)

@@ -11,6 +11,8 @@ kernels of ``csrc/batch_consumers.hip`` with a batch of one, ``prs`` is ``csrc/c
 tensors on the host.
 ``overlap`` and ``collectivity`` (no reference counterpart: which modes carry a displacement, and how many atoms a mode
 moves) are one pass along the selected rows (``csrc/mode_overlap.hip``); ``cumulative_overlap`` is array arithmetic.
+``distance_fluctuation`` (no reference counterpart: how much every inter-atom distance fluctuates) is the pair kernel of
+``csrc/dist_fluct.hip`` with a batch of one; ``effective_stiffness`` is array arithmetic on its result.
 ``normal_mode``, ``linear_response`` and ``effector_sensor`` are O(n) / O(n^2) host arithmetic on
 results that are already on the host.
 """
@@ -23,7 +25,7 @@ from . import _hip
 __all__ = [
     "eigen", "eigh", "pinvh", "frequencies", "mean_square_fluctuation", "bfactor", "dcc",
     "normal_mode", "linear_response", "prs", "effector_sensor", "anisotropic_fluctuation", "anisotropy",
-    "overlap", "collectivity", "cumulative_overlap",
+    "overlap", "collectivity", "cumulative_overlap", "distance_fluctuation", "effective_stiffness",
 ]
 
 K_B = 1.380649e-23
@@ -295,6 +297,63 @@ def cumulative_overlap(overlap):
         return (overlap * overlap).cumsum(-1).sqrt()
     o = np.asarray(overlap, dtype=np.float64)
     return np.sqrt(np.cumsum(o * o, axis=-1))
+
+
+def distance_fluctuation(enm, mode_subset=None, projected=True, tem=None, tem_factors=K_B):
+    """
+    Fluctuation of every inter-atom distance over the selected modes, (N, N), symmetric with a zero diagonal:
+
+        ``F[a, c] = <(delta d_ac)^2> = sum_k (n_ac . (v_k[c] - v_k[a]))^2 / lambda_k``,  ``n_ac = (x_c - x_a) / |x_c - x_a|``
+
+    the relative displacement of the two atoms projected on the line between them.  ``k_B T / F`` is the harmonic constant
+    of that distance's potential of mean force (:func:`effective_stiffness`): contact-stability and mechanical-resistance
+    maps, comparison with distance restraints.  No reference counterpart (ProDy: ``calcDistFlucts``, ``calcMechStiff``;
+    Bio3D derives it from the covariance).
+
+    ``mode_subset``, ``tem`` and ``tem_factors`` as in :func:`mean_square_fluctuation`: None takes every non-trivial mode,
+    trivial indices raise ValueError.  ``projected=True`` (ANM only; a GNM has no directions and raises ValueError) sums
+    the pairs directly on the device-resident eigenvectors (``csrc/dist_fluct.hip``): only non-negative terms, ``F`` and
+    ``F.T`` equal bit for bit, the diagonal exactly 0, NaN for two distinct atoms at one position.  The modes enter as
+    they are: for a model with masses they are mass-weighted, and the Cartesian figure is what a batch solver returns for
+    ``atom_scale=solver.inv_sqrt_mass`` (:meth:`DeviceBatchSolver.distance_fluctuation`).
+    ``projected=False`` is ProDy's ``calcDistFlucts``, ``c_aa + c_cc - 2 c_ac`` of the unnormalised :func:`dcc` over the
+    same explicit selection, the mean square of the whole relative displacement (for an ANM the sum of the projected
+    figure over three orthogonal directions); it works for GNM and ANM and is array arithmetic on the dcc kernel's result.
+    """
+    kind, _ = _model_kind(enm)
+    if projected and kind != "anm":
+        raise ValueError("projected distance fluctuations need the directions of an ANM; use projected=False for a GNM")
+    if mode_subset is not None:
+        mode_subset = _mode_selection(enm, mode_subset, None)   # (the trivial-mode error needs no device)
+    modes = enm._modes_device()
+    if mode_subset is None:
+        mode_subset = _mode_selection(enm, None, modes.order)
+    if projected:
+        fluct = modes.distfluct(mode_subset, np.asarray(enm._coord, dtype=np.float64))
+    else:
+        cov = modes.dcc(mode_subset, False)
+        diag = np.diag(cov)
+        fluct = (diag[:, None] + diag[None, :]) - 2 * cov
+    if tem is not None:
+        fluct = fluct * (tem * tem_factors)
+    return fluct
+
+
+def effective_stiffness(fluct, tem=None, tem_factors=K_B):
+    """
+    Harmonic constant of every distance's potential of mean force, ``(tem * tem_factors) / F`` for the fluctuations ``F``
+    of :func:`distance_fluctuation` taken without ``tem`` (``1 / F`` when ``tem`` is None, in the units of the force
+    constants).  Where ``F`` is 0 -- the diagonal -- the result is exactly 0; NaN stays NaN.  Pure array arithmetic on a
+    NumPy array or a torch tensor (which stays on its device).  No reference counterpart (ProDy: ``calcMechStiff``, this
+    on the projected fluctuations).
+    """
+    kt = 1.0 if tem is None else tem * tem_factors
+    if hasattr(fluct, "masked_fill") and not isinstance(fluct, np.ndarray):   # a torch tensor
+        return (kt / fluct).masked_fill(fluct == 0, 0.0)
+    f = np.asarray(fluct, dtype=np.float64)
+    out = np.zeros_like(f)
+    np.divide(kt, f, out=out, where=f != 0)
+    return out
 
 
 def normal_mode(anm, index, amplitude, frames, movement="sine"):
