@@ -124,25 +124,6 @@ def _aniso_expand(solver, packed):
     return packed.index_select(-1, solver._aniso_index).view(*packed.shape[:-1], 3, 3)
 
 
-def _device_displacement(solver, displacement, lead, tail, names):
-    """
-    Checks a displacement tensor for ``overlap`` on the host: CUDA float64 contiguous on the solver's device, shape
-    ``lead + tail`` (one vector per structure) or ``lead + (q,) + tail``.  Returns (tensor, q, whether it was one vector).
-    """
-    torch = solver.torch
-    d = displacement
-    if not isinstance(d, torch.Tensor) or not d.is_cuda or d.dtype != torch.float64 or not d.is_contiguous():
-        raise ValueError(f"displacement must be a contiguous CUDA float64 tensor of shape {names}")
-    if d.device != torch.device(solver.device):
-        raise ValueError(f"displacement is on {d.device}, the solver on {solver.device}")
-    shape = tuple(d.shape)
-    if shape == lead + tail:
-        return d, 1, True
-    if len(shape) == len(lead) + 1 + len(tail) and shape[:len(lead)] == lead and shape[len(lead) + 1:] == tail:
-        return d, shape[len(lead)], False
-    raise ValueError(f"Expected a displacement of shape {names}, got {shape}")
-
-
 def _trivial_rows(ntriv, first_row, nvec):
     """
     How many of a solver's ``nvec`` rows, row r being global mode ``first_row + r``, are trivial modes: the first row of
@@ -151,15 +132,136 @@ def _trivial_rows(ntriv, first_row, nvec):
     return min(max(ntriv - first_row, 0), nvec)
 
 
+class _Layout:
+    """
+    Where the consumers' results of a batch lie in their buffers and how they are handed back: what differs between
+    :class:`DeviceBatchSolver` (:class:`_UniformLayout`) and :class:`RaggedBatchSolver` (:class:`_RaggedLayout`).  Pure host
+    arithmetic on shapes, no device context.  A layout answers:
+
+    atoms_shape(tail)   shape of a per-atom result buffer with ``tail`` values per atom; also the shape ``coord``
+                        (``tail=(3,)``) and ``atom_scale`` (``tail=()``) must have, and how error messages name it
+    pairs_shape()       shape of a per-pair result buffer
+    atoms_out(buf), pairs_out(buf), rows_out(t, single)
+                        the caller's form of a per-atom / per-pair buffer and of a per-row (batch, [q,] nvec) tensor;
+                        ``single``: the q axis holds the one vector that was given without it and is dropped
+    pair_blocks(out, atom_scale)
+                        (pairs, scale or None) blocks, the last two axes of ``pairs`` being (atom, atom), in which
+                        ``pairs_out``'s result ``out`` is post-processed
+    displacement()      (lead, tail, wording): a displacement has shape ``lead + tail`` or ``lead + (q,) + tail``
+    """
+
+    def displacement_q(self, shape):
+        """(q, whether it is one vector without a q axis) of a displacement of ``shape``; ValueError for any other shape."""
+        lead, tail, names = self.displacement()
+        shape = tuple(shape)
+        if shape == lead + tail:
+            return 1, True
+        if len(shape) == len(lead) + 1 + len(tail) and shape[:len(lead)] == lead and shape[len(lead) + 1:] == tail:
+            return shape[len(lead)], False
+        raise ValueError(f"Expected a displacement of shape {names}, got {shape}")
+
+
+class _UniformLayout(_Layout):
+    """``batch`` structures of ``n_atoms`` atoms: every result is one tensor with a leading batch axis, handed back as it is."""
+
+    ragged = False
+
+    def __init__(self, batch, n_atoms, dim):
+        self.batch, self.n_atoms, self.dim = int(batch), int(n_atoms), int(dim)
+
+    def atoms_shape(self, tail=()):
+        return (self.batch, self.n_atoms) + tuple(tail)
+
+    def pairs_shape(self):
+        return (self.batch, self.n_atoms, self.n_atoms)
+
+    def atoms_out(self, buf):
+        return buf
+
+    pairs_out = atoms_out
+
+    def rows_out(self, t, single=False):
+        return t[:, 0] if single else t
+
+    def pair_blocks(self, out, atom_scale):
+        return [(out, atom_scale)]
+
+    def displacement(self):
+        names = "(batch, N, 3) or (batch, q, N, 3)" if self.dim == 3 else "(batch, N) or (batch, q, N)"
+        tail = (self.n_atoms, 3) if self.dim == 3 else (self.n_atoms,)
+        return (self.batch,), tail, f"{names} with batch = {self.batch}, N = {self.n_atoms}"
+
+
+class _RaggedLayout(_Layout):
+    """
+    Structures of ``sizes`` atoms back to back in one packed buffer, handed back as a list of views: structure b's atoms
+    start at ``atom_off[b] = sum(sizes[:b])``, its (n_b, n_b) block at ``sq_off[b] = sum(sizes[:b] ** 2)``, and of a per-row
+    tensor it gets its first ``row_limits[b]`` rows (:func:`ragged_subset_plan`).
+    """
+
+    ragged = True
+
+    def __init__(self, sizes, dim, row_limits):
+        self.sizes, self.dim, self.row_limits = [int(n) for n in sizes], int(dim), [int(r) for r in row_limits]
+        self.atom_off = [0] + [int(x) for x in np.cumsum(self.sizes)]
+        self.sq_off = [0] + [int(x) for x in np.cumsum(np.asarray(self.sizes, dtype=np.int64) ** 2)]
+
+    def atoms_shape(self, tail=()):
+        return (self.atom_off[-1],) + tuple(tail)
+
+    def pairs_shape(self):
+        return (self.sq_off[-1],)
+
+    def atoms_out(self, buf):
+        return [buf[a:b] for a, b in zip(self.atom_off, self.atom_off[1:])]
+
+    def pairs_out(self, buf):
+        return [buf[self.sq_off[b]: self.sq_off[b + 1]].view(n, n) for b, n in enumerate(self.sizes)]
+
+    def rows_out(self, t, single=False):
+        return [t[b, 0, :r] if single else t[b, ..., :r] for b, r in enumerate(self.row_limits)]
+
+    def pair_blocks(self, out, atom_scale):
+        return zip(out, [None] * len(out) if atom_scale is None else self.atoms_out(atom_scale))
+
+    def displacement(self):
+        total = self.atom_off[-1]
+        names = "(S, 3) or (q, S, 3)" if self.dim == 3 else "(S,) or (q, S)"
+        return (), ((total, 3) if self.dim == 3 else (total,)), f"{names} with S = sum(sizes) = {total}"
+
+
+_DEV, _PLAN = ("ctx", "w", "v", "m", "nvec", "batch"), ("plan", "w", "v", "nvec")
+# consumer -> (C entry of a uniform batch, its argument prefix, C entry of a plan's slots, its argument prefix):
+# _BatchSolver._call fills the prefix from the solver and appends the consumer's own arguments
+_CONSUMER_ENTRIES = {
+    "msf": ("sc_dev_modes_msf_f64", _DEV + ("dim",), "sc_batch_plan_modes_msf_f64", _PLAN),
+    "dcc": ("sc_dev_modes_dcc_f64", _DEV + ("dim",), "sc_batch_plan_modes_dcc_f64", _PLAN),
+    "aniso": ("sc_dev_modes_aniso_f64", _DEV, "sc_batch_plan_modes_aniso_f64", _PLAN),
+    "distfluct": ("sc_dev_modes_distfluct_f64", _DEV, "sc_batch_plan_modes_distfluct_f64", _PLAN),
+    "overlap": ("sc_dev_modes_overlap_f64", ("ctx", "v", "m", "nvec", "batch", "dim"),
+                "sc_batch_plan_modes_overlap_f64", ("plan", "v", "nvec", "first_row")),
+}
+
+
 class _BatchSolver:
     """
-    What :class:`DeviceBatchSolver` and :class:`RaggedBatchSolver` share.  A subclass sets ``_first_row`` (global mode index
-    of row 0 of ``w`` / ``v``) and ``_common_modes`` (modes every member has: an explicit ``mode_subset`` is checked against
-    them) and implements ``assemble``, ``eigh`` and ``_overlap_entry``.
+    What :class:`DeviceBatchSolver` and :class:`RaggedBatchSolver` share, the consumers of the solved modes included.  A
+    subclass sets ``_first_row`` (global mode index of row 0 of ``w`` / ``v``), ``_common_modes`` (modes every member has: an
+    explicit ``mode_subset`` is checked against them), ``_layout`` (where results lie and how they are handed back:
+    :class:`_Layout`) and, for the plan's C entries, ``_plan``; it implements ``assemble`` and ``eigh``.
     """
 
     #: bytes the packed GEMM operands of :meth:`dcc` may take at a time (None: SPRINGCRAFT_MODES_BUDGET_BYTES, else 1 GiB)
     consumer_budget_bytes = None
+    _plan = None
+
+    def _allocate(self, m, nvec, want_vectors):
+        """The tensors of a solve: ``counts`` (behind a window), ``matrix`` (batch, m, m), ``w`` (batch, nvec), ``v`` (batch, nvec, m)."""
+        torch, f64 = self.torch, self.torch.float64
+        self.counts = torch.zeros((self.batch,), dtype=torch.int64, device=self.device) if self.window is not None else None
+        self.matrix = torch.empty((self.batch, m, m), dtype=f64, device=self.device)
+        self.w = torch.empty((self.batch, nvec), dtype=f64, device=self.device)
+        self.v = torch.empty((self.batch, nvec, m), dtype=f64, device=self.device) if want_vectors else None
 
     def set_profiling(self, on):
         self.ctx.check(self._L.sc_ctx_set_profiling(self.ctx.handle, 1 if on else 0))
@@ -206,6 +308,8 @@ class _BatchSolver:
         self._need_vectors()
         rows = batch_mode_rows(mode_subset, self._ntriv, self.subset, self._common_modes, self.window)
         sel = _hip.ModeSelection()
+        # (how the sc_batch_plan_modes_* entries learn the global index of row 0; the sc_dev_modes_* entries never read it)
+        sel.reserved = self._first_row
         nvec = self.w.shape[1]
         keep = None
         if self.window is not None:
@@ -234,33 +338,101 @@ class _BatchSolver:
             raise ValueError(f"Expected {name} of shape {tuple(shape)}, got {tuple(t.shape)}")
         return C.c_void_p(t.data_ptr())
 
-    def _distance_fluctuation_args(self, coord, atoms_shape, projected, atom_scale):
-        """Host checks of ``distance_fluctuation``: (coordinate pointer, scale pointer or None); nothing is enqueued."""
-        if projected and self.dim != 3:
-            raise ValueError("projected distance fluctuations need an ANM solver (dim=3); use projected=False")
-        self._need_vectors()
-        cp = self._device_f64(coord, tuple(atoms_shape) + (3,), "coord")
-        sp = None if atom_scale is None else self._device_f64(atom_scale, atoms_shape, "atom_scale")
-        return cp, sp
+    def _empty(self, shape):
+        return self.torch.empty(shape, dtype=self.torch.float64, device=self.device)
 
-    def _frequencies(self):
-        """(batch, nvec) ``sqrt(lambda) / (2 pi)``; without a window the trivial rows enter as ``abs(lambda)``."""
+    def _call(self, consumer, *args):
+        """Enqueues ``consumer``'s C entry for this solver's layout: the entry's argument prefix, then ``args``."""
+        entry, prefix = _CONSUMER_ENTRIES[consumer][2:] if self._layout.ragged else _CONSUMER_ENTRIES[consumer][:2]
+        have = {"ctx": self.ctx.handle, "plan": self._plan, "w": C.c_void_p(self.w.data_ptr()),
+                "v": C.c_void_p(self.v.data_ptr()), "m": self.v.shape[2], "nvec": self.w.shape[1], "batch": self.batch,
+                "dim": self.dim, "first_row": self._first_row}
+        self.ctx.check(getattr(self._L, entry)(*[have[k] for k in prefix], *args))
+
+    # ---- consumers of the solved modes (reference: nma.py:66-359, there for one model) --------------------------------
+    # One body each for both solvers: self._layout says where the results lie, _CONSUMER_ENTRIES which C entry runs.  Like
+    # solve() they ONLY ENQUEUE on the solver's stream and return CUDA tensors that are valid in stream order: no
+    # synchronisation, no host copy of w.  The one exception is the first call of a kind, which allocates its workspace.
+    # The docstrings give the result of a DeviceBatchSolver first; a RaggedBatchSolver returns, per structure, a list of
+    # views into one packed buffer (see its class docstring for the packing), with n_atoms the structure's own n_i.
+
+    def frequencies(self):
+        """
+        (batch, nvec) frequencies ``sqrt(lambda) / (2 pi)`` of the solved modes; rows whose global mode index is trivial
+        enter as ``abs(lambda)`` (nma.py:66-105).  With ``subset_by_value`` the mode indices are not known, so no row is
+        treated as trivial (a negative rounding-level eigenvalue gives NaN, as do the padding rows).
+        Ragged: [(rows_i,), ...], (dim n_i,) for a full-spectrum solver, else all ``nvec`` rows (with ``subset_by_value``
+        the rows behind the count are NaN).
+        """
         w = self.w.clone()
         if self.window is None:
             k = _trivial_rows(self._ntriv, self._first_row, w.shape[1])
             w[:, :k] = w[:, :k].abs()
-        return self.torch.sqrt(w) / (2 * np.pi)
+        return self._layout.rows_out(self.torch.sqrt(w) / (2 * np.pi))
+
+    def _per_atom(self, consumer, tail, mode_subset, tem, tem_factors):
+        """The packed per-atom buffer of ``consumer`` ("msf" / "aniso": ``tail`` values per atom), ``tem`` applied."""
+        sel, counts = self._selection(mode_subset, pinv_default=False)
+        out = self._empty(self._layout.atoms_shape(tail))
+        self._call(consumer, C.byref(sel), counts, C.c_void_p(out.data_ptr()))
+        if tem is not None:
+            out *= tem * tem_factors
+        return out
+
+    def mean_square_fluctuation(self, mode_subset=None, tem=None, tem_factors=K_B):
+        """
+        (batch, n_atoms) mean square fluctuations ``sum_k v_k^2 / lambda_k`` over the selected modes (nma.py:108-184), one
+        pass over the selected rows of ``v`` on the device.  Ragged: [(n_i,), ...].
+
+        ``mode_subset`` holds GLOBAL ascending mode indices as in the reference, never row numbers of ``v``
+        (:func:`batch_mode_rows`); None takes every solved mode that is not trivial (ragged: every own non-trivial solved
+        mode of each structure; an explicit ``mode_subset`` holds global mode indices below ``dim * min(sizes)``).  With
+        ``subset_by_value`` it must be None and the selection is the window: the first ``min(counts[b], max_modes)`` rows
+        of structure b, read from ``counts`` on the device; a structure with an empty window gives zeros.  Whether the
+        window contains trivial modes is the caller's choice of ``vl``: an ANM's six trivial eigenvalues are ~0 at rounding
+        level, of either sign, so ``vl = -inf`` includes them and a small positive ``vl`` (e.g. 1e-6 lambda_max) leaves
+        them out.
+        A structure whose solve failed (NaN eigenvalues) gives NaN, its neighbours are unaffected; behind a window solve such
+        a structure has count 0 and gives the empty window's result.
+        """
+        return self._layout.atoms_out(self._per_atom("msf", (), mode_subset, tem, tem_factors))
+
+    def bfactor(self, mode_subset=None, tem=None, tem_factors=K_B):
+        """
+        (batch, n_atoms) isotropic B-factors, ``8 pi^2 / 3`` times :meth:`mean_square_fluctuation` (nma.py:187-230).
+        Ragged: [(n_i,), ...].
+        """
+        out = self._per_atom("msf", (), mode_subset, tem, tem_factors)
+        out *= (8 * np.pi**2) / 3
+        return self._layout.atoms_out(out)
+
+    def _aniso_packed(self, mode_subset=None, tem=None, tem_factors=K_B):
+        """
+        (batch, n_atoms, 6): every tensor's six distinct entries xx yy zz xy xz yz, as the kernel leaves them.  Ragged:
+        (sum(sizes), 6), the structures back to back.
+        """
+        if self.dim != 3:
+            raise ValueError("anisotropic fluctuation tensors need an ANM solver (dim=3)")
+        return self._per_atom("aniso", (6,), mode_subset, tem, tem_factors)
+
+    def anisotropic_fluctuation(self, mode_subset=None, tem=None, tem_factors=K_B):
+        """
+        (batch, n_atoms, 3, 3) anisotropic fluctuation tensors ``sum_k v_k[a] v_k[a]^T / lambda_k`` over the selected
+        modes (:func:`nma.anisotropic_fluctuation`): symmetric, and their traces are :meth:`mean_square_fluctuation` of
+        the same selection, whose ``mode_subset``, window and failed-structure rules apply unchanged.  One pass over the
+        selected rows of ``v``; ANM solvers only (``dim != 3`` raises ValueError before anything is enqueued).
+        Ragged: [(n_i, 3, 3), ...], views into one packed tensor.
+        """
+        return self._layout.atoms_out(_aniso_expand(self, self._aniso_packed(mode_subset, tem, tem_factors)))
 
     def _overlap_call(self, d, q, want_collectivity):
         nvec = self.w.shape[1]
-        f64 = self.torch.float64
-        ov = self.torch.empty((self.batch, q, nvec), dtype=f64, device=self.device) if q else None
-        co = self.torch.empty((self.batch, nvec), dtype=f64, device=self.device) if want_collectivity else None
+        ov = self._empty((self.batch, q, nvec)) if q else None
+        co = self._empty((self.batch, nvec)) if want_collectivity else None
         if ov is not None or co is not None:
-            self.ctx.check(self._overlap_entry(
-                C.c_void_p(self.v.data_ptr()), nvec, C.c_void_p(d.data_ptr()) if q else None, q,
-                C.c_void_p(self.counts.data_ptr()) if self.window is not None else None,
-                C.c_void_p(ov.data_ptr()) if q else None, C.c_void_p(co.data_ptr()) if want_collectivity else None))
+            self._call("overlap", C.c_void_p(d.data_ptr()) if q else None, q,
+                       C.c_void_p(self.counts.data_ptr()) if self.window is not None else None,
+                       C.c_void_p(ov.data_ptr()) if q else None, C.c_void_p(co.data_ptr()) if want_collectivity else None)
             # a structure whose solve failed is solved as the zero matrix: its eigenvalues are NaN, its rows of v some
             # finite basis without a meaning.  The kernel does not read w, so a row is NaN here where its eigenvalue is
             # (also the rows behind a window's count, which the kernel has set already); enqueued, like the kernel
@@ -270,6 +442,112 @@ class _BatchSolver:
             if co is not None:
                 co.masked_fill_(bad, float("nan"))
         return ov, co
+
+    def overlap(self, displacement):
+        """
+        Overlaps ``<v_r, d> / (|v_r| |d|)`` of every row of ``v`` with the structure's displacement(s): which modes carry
+        an observed change (:func:`nma.overlap`; no reference counterpart).  ``displacement`` is a contiguous CUDA float64
+        tensor (batch, n_atoms, 3) or (batch, q, n_atoms, 3) -- for a GNM solver (batch, n_atoms) or (batch, q, n_atoms)
+        -- in the coordinates of the modes: with ``masses`` pass ``sqrt(mass) * d``, it is not done for you.  Returns
+        (batch, nvec) / (batch, q, nvec), signed, for ALL rows of ``w`` / ``v``, trivial ones included: slice as needed.
+        A row is NaN where its eigenvalue in ``w`` is: behind a window's count, and everywhere in a structure whose solve
+        failed (its ``v`` holds a finite basis without a meaning); a zero displacement gives NaN too.
+        One pass along the rows of ``v``; only enqueues on the solver's stream.
+        Ragged: ``displacement`` is packed like the coordinates :meth:`solve` takes, (sum(sizes), 3) or (q, sum(sizes), 3)
+        -- for a GNM solver (sum(sizes),) or (q, sum(sizes)) -- structure i's atoms at ``offsets[i]``; returns
+        [(rows_i,), ...] or [(q, rows_i), ...], the views cut as :meth:`frequencies` cuts them ((dim n_i,) on a
+        full-spectrum solver, else all ``nvec`` rows, NaN behind a window's count); only a structure's own columns are read.
+        """
+        self._need_vectors()
+        torch, d = self.torch, displacement
+        names = self._layout.displacement()[2]
+        if not isinstance(d, torch.Tensor) or not d.is_cuda or d.dtype != torch.float64 or not d.is_contiguous():
+            raise ValueError(f"displacement must be a contiguous CUDA float64 tensor of shape {names}")
+        if d.device != torch.device(self.device):
+            raise ValueError(f"displacement is on {d.device}, the solver on {self.device}")
+        q, single = self._layout.displacement_q(d.shape)
+        ov = self._empty((self.batch, 0, self.w.shape[1])) if q == 0 else self._overlap_call(d, q, False)[0]
+        return self._layout.rows_out(ov, single)
+
+    def collectivity(self):
+        """
+        (batch, nvec) collectivities ``exp(-sum_a p_a ln p_a) / n_atoms`` of every row of ``v`` (:func:`nma.collectivity`;
+        no reference counterpart): 1 for a rigid translation, 1 / n_atoms for a mode on one atom.  All rows, NaN behind a
+        window's count.  Only enqueues.  Ragged: [(rows_i,), ...], cut as :meth:`frequencies` cuts them; n_atoms is the
+        structure's own size.
+        """
+        self._need_vectors()
+        return self._layout.rows_out(self._overlap_call(None, 0, True)[1])
+
+    def distance_fluctuation(self, coord, mode_subset=None, projected=True, atom_scale=None, tem=None, tem_factors=K_B):
+        """
+        (batch, n_atoms, n_atoms) fluctuations of the inter-atom distances over the selected modes
+        (:func:`nma.distance_fluctuation`; no reference counterpart, ProDy: ``calcDistFlucts`` / ``calcMechStiff``):
+        ``F[b, a, c] = sum_k (n_ac . (u_k[c] - u_k[a]))^2 / lambda_k`` with ``n_ac`` the unit vector from atom a to atom c
+        of ``coord``, the (batch, n_atoms, 3) CUDA float64 tensor given to :meth:`solve`.  :func:`nma.effective_stiffness`
+        turns it into the distances' harmonic constants on the device.
+
+        ``mode_subset``, the window, ``subset_by_index`` and failed structures exactly as in
+        :meth:`mean_square_fluctuation`.  ``atom_scale``: None, or a (batch, n_atoms) CUDA float64 tensor with ``u_k[a] =
+        atom_scale[a] * v_k[a]``; None takes the rows of ``v`` as they are, like every other consumer, so a solver with
+        ``masses`` wants ``atom_scale=solver.inv_sqrt_mass`` for Cartesian distances.
+        ``projected=True`` (ANM solvers; ``dim != 3`` raises ValueError before anything is enqueued) sums every pair
+        directly on the device: ``F`` equals its transpose bit for bit, the diagonal is exactly 0 (also in a failed
+        structure, whose other entries are NaN), two distinct atoms at one position give NaN for that pair, and a
+        structure's bits do not depend on the batch size or its position.  ``projected=False`` is ``c_aa + c_cc - 2
+        c_ac`` of ``dcc(norm=False)`` over the same selection (GNM and ANM; ``coord`` is only checked).
+        Only enqueues.
+        Ragged: [(n_i, n_i), ...], views into one buffer packed like :meth:`dcc`'s.  ``coord`` is the packed (sum(sizes), 3)
+        tensor given to :meth:`solve`, ``atom_scale`` None or a packed (sum(sizes),) tensor.  Every structure is summed
+        over its own atoms and rows: pad rows never carry a weight, pad columns are never read.
+        """
+        lay = self._layout
+        if projected and self.dim != 3:
+            raise ValueError("projected distance fluctuations need an ANM solver (dim=3); use projected=False")
+        self._need_vectors()
+        cp = self._device_f64(coord, lay.atoms_shape((3,)), "coord")
+        sp = None if atom_scale is None else self._device_f64(atom_scale, lay.atoms_shape(), "atom_scale")
+        sel, counts = self._selection(mode_subset, pinv_default=False)
+        buf = self._empty(lay.pairs_shape())
+        out = lay.pairs_out(buf)
+        if projected:
+            self._call("distfluct", C.byref(sel), counts, cp, sp, C.c_void_p(buf.data_ptr()))
+        else:
+            self._call("dcc", C.byref(sel), counts, 0, int(self.consumer_budget_bytes or 0), C.c_void_p(buf.data_ptr()))
+            # in place, so that a ragged result stays views of one buffer; (-2 c) + (d_a + d_c) has the bits of
+            # (d_a + d_c) - 2 c: the doubling is exact and IEEE addition commutes
+            for c, scale in lay.pair_blocks(out, atom_scale):
+                if scale is not None:
+                    c *= scale[..., :, None] * scale[..., None, :]
+                diag = c.diagonal(dim1=-2, dim2=-1).clone()
+                c *= -2
+                c += diag[..., :, None] + diag[..., None, :]
+        if tem is not None:
+            buf *= tem * tem_factors
+        return out
+
+    def dcc(self, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
+        """
+        (batch, n_atoms, n_atoms) dynamic cross-correlations over the selected modes (nma.py:233-359); ``norm`` divides by
+        ``sqrt(c_aa c_bb)``, ``tem`` is applied after the normalisation as the reference does (nma.py:355-357).
+        Ragged: [(n_i, n_i), ...].
+
+        ``mode_subset`` as in :meth:`mean_square_fluctuation`.  None on a full-spectrum solver takes, per structure, every
+        mode with ``|lambda| > 1e-6 max|lambda|`` of THAT structure -- the reference's covariance rule, see :func:`nma.dcc`
+        -- with the maximum found on the device (ragged: taken over the structure's OWN eigenvalues; the slot's pads are
+        larger and never enter).  None on a ``subset_by_index`` solver takes every solved mode that is not
+        trivial: the covariance rule needs ``lambda_max``, which such a solve does not compute.  With ``subset_by_value``
+        the selection is the window (see :meth:`mean_square_fluctuation`, also for trivial modes inside it); an empty
+        window gives zeros, and NaN under ``norm=True`` as 0 / 0 does in NumPy.
+        """
+        sel, counts = self._selection(mode_subset, pinv_default=True)
+        buf = self._empty(self._layout.pairs_shape())
+        self._call("dcc", C.byref(sel), counts, int(bool(norm)), int(self.consumer_budget_bytes or 0),
+                   C.c_void_p(buf.data_ptr()))
+        if tem is not None:
+            buf *= tem
+            buf *= tem_factors
+        return self._layout.pairs_out(buf)
 
 
 class DeviceBatchSolver(_BatchSolver):
@@ -288,6 +566,10 @@ class DeviceBatchSolver(_BatchSolver):
     ``min(counts[b], K)`` rows are its window in ascending order, the rest NaN (``w``) / zero (``v``).  :meth:`finish`
     raises ValueError for structures whose window held more than K eigenpairs (their slots keep the K lowest).
     Structures of different sizes, patched or tabulated force fields: :class:`RaggedBatchSolver`.
+
+    The consumers of the solved modes (:meth:`frequencies` ... :meth:`dcc`, documented on the shared base) return one CUDA
+    tensor each with a leading batch axis: (batch, n_atoms[, 3, 3]) per atom, (batch, n_atoms, n_atoms) per pair and
+    (batch, [q,] nvec) per row of ``v``.
     """
 
     def __init__(self, n_atoms, batch, force_field, dim=3, device=None, want_vectors=True, masses=None,
@@ -320,6 +602,7 @@ class DeviceBatchSolver(_BatchSolver):
         m = self.n_atoms * self.dim
         self.m = m
         f64 = torch.float64
+        self._layout = _UniformLayout(self.batch, self.n_atoms, self.dim)
         self.subset = None
         nvec = m
         if subset_by_index is not None:
@@ -330,13 +613,7 @@ class DeviceBatchSolver(_BatchSolver):
             nvec = hi - lo + 1
         self._first_row, self._common_modes = (self.subset[0] if self.subset else 0), m
         self.max_modes = max_modes
-        self.counts = None
-        if self.window is not None:
-            nvec = max_modes
-            self.counts = torch.zeros((self.batch,), dtype=torch.int64, device=self.device)
-        self.matrix = torch.empty((self.batch, m, m), dtype=f64, device=self.device)
-        self.w = torch.empty((self.batch, nvec), dtype=f64, device=self.device)
-        self.v = torch.empty((self.batch, nvec, m), dtype=f64, device=self.device) if want_vectors else None
+        self._allocate(m, max_modes if self.window is not None else nvec, want_vectors)
         self.inv_sqrt_mass = None
         if masses is not None:
             mm = torch.as_tensor(np.asarray(masses, dtype=np.float64) if not torch.is_tensor(masses) else masses,
@@ -376,167 +653,6 @@ class DeviceBatchSolver(_BatchSolver):
                                                          C.c_void_p(self.w.data_ptr()), vp))
         return self.w, self.v
 
-    # ---- consumers of the solved modes (reference: nma.py:66-359, there for one model) --------------------------------
-    # Like solve() they ONLY ENQUEUE on the solver's stream and return CUDA tensors that are valid in stream order: no
-    # synchronisation, no host copy of w.  The one exception is the first call of a kind, which allocates its workspace.
-
-    def frequencies(self):
-        """
-        (batch, nvec) frequencies ``sqrt(lambda) / (2 pi)`` of the solved modes; rows whose global mode index is trivial
-        enter as ``abs(lambda)`` (nma.py:66-105).  With ``subset_by_value`` the mode indices are not known, so no row is
-        treated as trivial (a negative rounding-level eigenvalue gives NaN, as do the padding rows).
-        """
-        return self._frequencies()
-
-    def mean_square_fluctuation(self, mode_subset=None, tem=None, tem_factors=K_B):
-        """
-        (batch, n_atoms) mean square fluctuations ``sum_k v_k^2 / lambda_k`` over the selected modes (nma.py:108-184), one
-        pass over the selected rows of ``v`` on the device.
-
-        ``mode_subset`` holds GLOBAL ascending mode indices as in the reference, never row numbers of ``v``
-        (:func:`batch_mode_rows`); None takes every solved mode that is not trivial.  With ``subset_by_value`` it must be
-        None and the selection is the window: the first ``min(counts[b], max_modes)`` rows of structure b, read from
-        ``counts`` on the device; a structure with an empty window gives zeros.  Whether the window contains trivial modes
-        is the caller's choice of ``vl``: an ANM's six trivial eigenvalues are ~0 at rounding level, of either sign, so
-        ``vl = -inf`` includes them and a small positive ``vl`` (e.g. 1e-6 lambda_max) leaves them out.
-        A structure whose solve failed (NaN eigenvalues) gives NaN, its neighbours are unaffected; behind a window solve such
-        a structure has count 0 and gives the empty window's result.
-        """
-        sel, counts = self._selection(mode_subset, pinv_default=False)
-        out = self.torch.empty((self.batch, self.n_atoms), dtype=self.torch.float64, device=self.device)
-        self.ctx.check(self._L.sc_dev_modes_msf_f64(
-            self.ctx.handle, C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr()), self.m, self.w.shape[1],
-            self.batch, self.dim, C.byref(sel), counts, C.c_void_p(out.data_ptr())))
-        if tem is not None:
-            out *= tem * tem_factors
-        return out
-
-    def bfactor(self, mode_subset=None, tem=None, tem_factors=K_B):
-        """(batch, n_atoms) isotropic B-factors, ``8 pi^2 / 3`` times :meth:`mean_square_fluctuation` (nma.py:187-230)."""
-        out = self.mean_square_fluctuation(mode_subset, tem, tem_factors)
-        out *= (8 * np.pi**2) / 3
-        return out
-
-    def _aniso_packed(self, mode_subset=None, tem=None, tem_factors=K_B):
-        """(batch, n_atoms, 6): every tensor's six distinct entries xx yy zz xy xz yz, as the kernel leaves them."""
-        if self.dim != 3:
-            raise ValueError("anisotropic fluctuation tensors need an ANM solver (dim=3)")
-        sel, counts = self._selection(mode_subset, pinv_default=False)
-        out = self.torch.empty((self.batch, self.n_atoms, 6), dtype=self.torch.float64, device=self.device)
-        self.ctx.check(self._L.sc_dev_modes_aniso_f64(
-            self.ctx.handle, C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr()), self.m, self.w.shape[1],
-            self.batch, C.byref(sel), counts, C.c_void_p(out.data_ptr())))
-        if tem is not None:
-            out *= tem * tem_factors
-        return out
-
-    def anisotropic_fluctuation(self, mode_subset=None, tem=None, tem_factors=K_B):
-        """
-        (batch, n_atoms, 3, 3) anisotropic fluctuation tensors ``sum_k v_k[a] v_k[a]^T / lambda_k`` over the selected
-        modes (:func:`nma.anisotropic_fluctuation`): symmetric, and their traces are :meth:`mean_square_fluctuation` of
-        the same selection, whose ``mode_subset``, window and failed-structure rules apply unchanged.  One pass over the
-        selected rows of ``v``; ANM solvers only (``dim != 3`` raises ValueError before anything is enqueued).
-        """
-        return _aniso_expand(self, self._aniso_packed(mode_subset, tem, tem_factors))
-
-    def _overlap_entry(self, vp, nvec, dp, q, counts, ovp, cop):
-        return self._L.sc_dev_modes_overlap_f64(self.ctx.handle, vp, self.m, nvec, self.batch, self.dim, dp, q, counts, ovp,
-                                                cop)
-
-    def overlap(self, displacement):
-        """
-        Overlaps ``<v_r, d> / (|v_r| |d|)`` of every row of ``v`` with the structure's displacement(s): which modes carry
-        an observed change (:func:`nma.overlap`; no reference counterpart).  ``displacement`` is a contiguous CUDA float64
-        tensor (batch, n_atoms, 3) or (batch, q, n_atoms, 3) -- for a GNM solver (batch, n_atoms) or (batch, q, n_atoms)
-        -- in the coordinates of the modes: with ``masses`` pass ``sqrt(mass) * d``, it is not done for you.  Returns
-        (batch, nvec) / (batch, q, nvec), signed, for ALL rows of ``w`` / ``v``, trivial ones included: slice as needed.
-        A row is NaN where its eigenvalue in ``w`` is: behind a window's count, and everywhere in a structure whose solve
-        failed (its ``v`` holds a finite basis without a meaning); a zero displacement gives NaN too.
-        One pass along the rows of ``v``; only enqueues on the solver's stream.
-        """
-        self._need_vectors()
-        tail = (self.n_atoms, 3) if self.dim == 3 else (self.n_atoms,)
-        names = "(batch, N, 3) or (batch, q, N, 3)" if self.dim == 3 else "(batch, N) or (batch, q, N)"
-        d, q, single = _device_displacement(self, displacement, (self.batch,), tail,
-                                            f"{names} with batch = {self.batch}, N = {self.n_atoms}")
-        if q == 0:
-            return self.torch.empty((self.batch, 0, self.w.shape[1]), dtype=self.torch.float64, device=self.device)
-        ov, _ = self._overlap_call(d, q, False)
-        return ov[:, 0] if single else ov
-
-    def collectivity(self):
-        """
-        (batch, nvec) collectivities ``exp(-sum_a p_a ln p_a) / n_atoms`` of every row of ``v`` (:func:`nma.collectivity`;
-        no reference counterpart): 1 for a rigid translation, 1 / n_atoms for a mode on one atom.  All rows, NaN behind a
-        window's count.  Only enqueues.
-        """
-        self._need_vectors()
-        return self._overlap_call(None, 0, True)[1]
-
-    def distance_fluctuation(self, coord, mode_subset=None, projected=True, atom_scale=None, tem=None, tem_factors=K_B):
-        """
-        (batch, n_atoms, n_atoms) fluctuations of the inter-atom distances over the selected modes
-        (:func:`nma.distance_fluctuation`; no reference counterpart, ProDy: ``calcDistFlucts`` / ``calcMechStiff``):
-        ``F[b, a, c] = sum_k (n_ac . (u_k[c] - u_k[a]))^2 / lambda_k`` with ``n_ac`` the unit vector from atom a to atom c
-        of ``coord``, the (batch, n_atoms, 3) CUDA float64 tensor given to :meth:`solve`.  :func:`nma.effective_stiffness`
-        turns it into the distances' harmonic constants on the device.
-
-        ``mode_subset``, the window, ``subset_by_index`` and failed structures exactly as in
-        :meth:`mean_square_fluctuation`.  ``atom_scale``: None, or a (batch, n_atoms) CUDA float64 tensor with ``u_k[a] =
-        atom_scale[a] * v_k[a]``; None takes the rows of ``v`` as they are, like every other consumer, so a solver with
-        ``masses`` wants ``atom_scale=solver.inv_sqrt_mass`` for Cartesian distances.
-        ``projected=True`` (ANM solvers; ``dim != 3`` raises ValueError before anything is enqueued) sums every pair
-        directly on the device: ``F`` equals its transpose bit for bit, the diagonal is exactly 0 (also in a failed
-        structure, whose other entries are NaN), two distinct atoms at one position give NaN for that pair, and a
-        structure's bits do not depend on the batch size or its position.  ``projected=False`` is ``c_aa + c_cc - 2
-        c_ac`` of ``dcc(norm=False)`` over the same selection (GNM and ANM; ``coord`` is only checked).
-        Only enqueues.
-        """
-        n = self.n_atoms
-        cp, sp = self._distance_fluctuation_args(coord, (self.batch, n), projected, atom_scale)
-        sel, counts = self._selection(mode_subset, pinv_default=False)
-        out = self.torch.empty((self.batch, n, n), dtype=self.torch.float64, device=self.device)
-        wp, vp = C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr())
-        if projected:
-            self.ctx.check(self._L.sc_dev_modes_distfluct_f64(
-                self.ctx.handle, wp, vp, self.m, self.w.shape[1], self.batch, C.byref(sel), counts, cp, sp,
-                C.c_void_p(out.data_ptr())))
-        else:
-            self.ctx.check(self._L.sc_dev_modes_dcc_f64(
-                self.ctx.handle, wp, vp, self.m, self.w.shape[1], self.batch, self.dim, C.byref(sel), counts, 0,
-                int(self.consumer_budget_bytes or 0), C.c_void_p(out.data_ptr())))
-            if atom_scale is not None:
-                out *= atom_scale[:, :, None] * atom_scale[:, None, :]
-            diag = out.diagonal(dim1=1, dim2=2)
-            out = (diag[:, :, None] + diag[:, None, :]) - 2 * out
-        if tem is not None:
-            out *= tem * tem_factors
-        return out
-
-    def dcc(self, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
-        """
-        (batch, n_atoms, n_atoms) dynamic cross-correlations over the selected modes (nma.py:233-359); ``norm`` divides by
-        ``sqrt(c_aa c_bb)``, ``tem`` is applied after the normalisation as the reference does (nma.py:355-357).
-
-        ``mode_subset`` as in :meth:`mean_square_fluctuation`.  None on a full-spectrum solver takes, per structure, every
-        mode with ``|lambda| > 1e-6 max|lambda|`` of THAT structure -- the reference's covariance rule, see :func:`nma.dcc`
-        -- with the maximum found on the device.  None on a ``subset_by_index`` solver takes every solved mode that is not
-        trivial: the covariance rule needs ``lambda_max``, which such a solve does not compute.  With ``subset_by_value``
-        the selection is the window (see :meth:`mean_square_fluctuation`, also for trivial modes inside it); an empty
-        window gives zeros, and NaN under ``norm=True`` as 0 / 0 does in NumPy.
-        """
-        sel, counts = self._selection(mode_subset, pinv_default=True)
-        n = self.n_atoms
-        out = self.torch.empty((self.batch, n, n), dtype=self.torch.float64, device=self.device)
-        self.ctx.check(self._L.sc_dev_modes_dcc_f64(
-            self.ctx.handle, C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr()), self.m, self.w.shape[1],
-            self.batch, self.dim, C.byref(sel), counts, int(bool(norm)), int(self.consumer_budget_bytes or 0),
-            C.c_void_p(out.data_ptr())))
-        if tem is not None:
-            out *= tem
-            out *= tem_factors
-        return out
-
 
 class RaggedBatchSolver(_BatchSolver):
     """
@@ -574,9 +690,13 @@ class RaggedBatchSolver(_BatchSolver):
 
     :meth:`frequencies`, :meth:`mean_square_fluctuation`, :meth:`bfactor`, :meth:`dcc`, :meth:`distance_fluctuation` and
     :meth:`anisotropic_fluctuation` (and, per row instead of per atom, :meth:`overlap` and :meth:`collectivity`)
-    have the meaning, defaults and trivial-mode rules of :class:`DeviceBatchSolver`'s, per structure: they only enqueue and
-    return a list of CUDA tensors, (n_i,) / (n_i, n_i) / (n_i, 3, 3), views into one packed buffer.  Pad rows and columns are never read into a result, and the
-    ``|lambda| > 1e-6 max|lambda|`` rule of the dcc default takes its maximum over the structure's own eigenvalues.
+    have the meaning, defaults and trivial-mode rules of :class:`DeviceBatchSolver`'s, per structure (they are the same
+    methods, documented on the shared base): they only enqueue (the first call of a kind allocates its workspace) and
+    return a list of CUDA tensors, (n_i,) / (n_i, n_i) / (n_i, 3, 3) / (rows_i,), views into one packed buffer: structure
+    b's atoms start at ``sum(sizes[:b])`` (``offsets[b]``), its (n_b, n_b) block at ``sum(sizes[:b] ** 2)``; per-row results
+    are cut to the structure's own ``dim * n_b`` rows on a full-spectrum solver, else hold all ``nvec`` rows.  Pad rows and
+    columns are never read into a result, and the ``|lambda| > 1e-6 max|lambda|`` rule of the dcc default takes its maximum
+    over the structure's own eigenvalues.
     """
 
     def __init__(self, sizes, force_fields, dim=3, masses=None, device=None, want_vectors=True, order=None,
@@ -630,13 +750,8 @@ class RaggedBatchSolver(_BatchSolver):
         self._plan = h
         self.order = int(self._L.sc_batch_plan_order(h))
         self.offsets = np.concatenate([[0], np.cumsum(self.sizes)]).astype(np.int64)
-        f64 = torch.float64
-        m = self.order
-        nvec = self._subset_plan["nvec"] or m
-        self.counts = torch.zeros((self.batch,), dtype=torch.int64, device=self.device) if self.window is not None else None
-        self.matrix = torch.empty((self.batch, m, m), dtype=f64, device=self.device)
-        self.w = torch.empty((self.batch, nvec), dtype=f64, device=self.device)
-        self.v = torch.empty((self.batch, nvec, m), dtype=f64, device=self.device) if want_vectors else None
+        self._layout = _RaggedLayout(self.sizes, self.dim, self._subset_plan["row_limits"])
+        self._allocate(self.order, self._subset_plan["nvec"] or self.order, want_vectors)
         self.inv_sqrt_mass = None
         if masses is not None:
             if len(masses) != self.batch:
@@ -722,149 +837,6 @@ class RaggedBatchSolver(_BatchSolver):
             m = self.dim * n
             out.append((self.w[b, :rows[b]], self.v[b, :rows[b], :m] if self.v is not None else None))
         return out
-
-    # ---- consumers of the solved modes: DeviceBatchSolver's, per structure ------------------------------------------------
-    # They ONLY ENQUEUE on the solver's stream (the first call of a kind allocates its workspace) and return lists of views
-    # into one packed buffer: structure b's atoms start at sum(sizes[:b]), its (n_b, n_b) block at sum(sizes[:b] ** 2).
-
-    def _selection(self, mode_subset, pinv_default):
-        sel, counts = super()._selection(mode_subset, pinv_default)
-        sel.reserved = self._first_row      # (how the sc_batch_plan_modes_* entries learn the global index of row 0)
-        return sel, counts
-
-    def frequencies(self):
-        """
-        Per structure the frequencies ``sqrt(lambda) / (2 pi)`` of its solved modes, trivial ones entering as
-        ``abs(lambda)`` (nma.py:66-105): (dim n_i,) for a full-spectrum solver, else all ``nvec`` rows (with
-        ``subset_by_value`` no row is treated as trivial and the rows behind the count are NaN).
-        """
-        f = self._frequencies()
-        return [f[b, :r] for b, r in enumerate(self._subset_plan["row_limits"])]
-
-    def mean_square_fluctuation(self, mode_subset=None, tem=None, tem_factors=K_B):
-        """
-        [(n_i,), ...] mean square fluctuations (nma.py:108-184), as :meth:`DeviceBatchSolver.mean_square_fluctuation`.
-        ``mode_subset=None``: every own non-trivial solved mode of each structure (behind a window solve: the window).  An
-        explicit ``mode_subset`` holds global mode indices below ``dim * min(sizes)``.
-        """
-        sel, counts = self._selection(mode_subset, pinv_default=False)
-        out = self.torch.empty((int(self.offsets[-1]),), dtype=self.torch.float64, device=self.device)
-        self.ctx.check(self._L.sc_batch_plan_modes_msf_f64(
-            self._plan, C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr()), self.w.shape[1], C.byref(sel),
-            counts, C.c_void_p(out.data_ptr())))
-        if tem is not None:
-            out *= tem * tem_factors
-        return [out[self.offsets[b]: self.offsets[b + 1]] for b in range(self.batch)]
-
-    def bfactor(self, mode_subset=None, tem=None, tem_factors=K_B):
-        """[(n_i,), ...] isotropic B-factors, ``8 pi^2 / 3`` times :meth:`mean_square_fluctuation` (nma.py:187-230)."""
-        out = self.mean_square_fluctuation(mode_subset, tem, tem_factors)
-        for o in out:
-            o *= (8 * np.pi**2) / 3
-        return out
-
-    def _aniso_packed(self, mode_subset=None, tem=None, tem_factors=K_B):
-        """(sum(sizes), 6): every tensor's six distinct entries xx yy zz xy xz yz, the structures back to back."""
-        if self.dim != 3:
-            raise ValueError("anisotropic fluctuation tensors need an ANM solver (dim=3)")
-        sel, counts = self._selection(mode_subset, pinv_default=False)
-        out = self.torch.empty((int(self.offsets[-1]), 6), dtype=self.torch.float64, device=self.device)
-        self.ctx.check(self._L.sc_batch_plan_modes_aniso_f64(
-            self._plan, C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr()), self.w.shape[1], C.byref(sel),
-            counts, C.c_void_p(out.data_ptr())))
-        if tem is not None:
-            out *= tem * tem_factors
-        return out
-
-    def anisotropic_fluctuation(self, mode_subset=None, tem=None, tem_factors=K_B):
-        """
-        [(n_i, 3, 3), ...] anisotropic fluctuation tensors, as :meth:`DeviceBatchSolver.anisotropic_fluctuation`, with the
-        selection of :meth:`mean_square_fluctuation`: views into one packed tensor.  ANM solvers only.
-        """
-        out = _aniso_expand(self, self._aniso_packed(mode_subset, tem, tem_factors))
-        return [out[self.offsets[b]: self.offsets[b + 1]] for b in range(self.batch)]
-
-    def _overlap_entry(self, vp, nvec, dp, q, counts, ovp, cop):
-        return self._L.sc_batch_plan_modes_overlap_f64(self._plan, vp, nvec, self._first_row, dp, q, counts, ovp, cop)
-
-    def overlap(self, displacement):
-        """
-        [(rows_i,), ...] or [(q, rows_i), ...] overlaps of every structure's rows with its displacement(s), as
-        :meth:`DeviceBatchSolver.overlap`.  ``displacement`` is packed like the coordinates :meth:`solve` takes: a
-        contiguous CUDA float64 tensor (sum(sizes), 3) or (q, sum(sizes), 3) -- for a GNM solver (sum(sizes),) or
-        (q, sum(sizes)) -- structure i's atoms at ``offsets[i]``.  The views are cut as :meth:`frequencies` cuts them
-        ((dim n_i,) on a full-spectrum solver, else all ``nvec`` rows, NaN behind a window's count); only a structure's own
-        columns are read.
-        """
-        self._need_vectors()
-        total = int(self.offsets[-1])
-        tail = (total, 3) if self.dim == 3 else (total,)
-        names = "(S, 3) or (q, S, 3)" if self.dim == 3 else "(S,) or (q, S)"
-        d, q, single = _device_displacement(self, displacement, (), tail, f"{names} with S = sum(sizes) = {total}")
-        limits = self._subset_plan["row_limits"]
-        if q == 0:
-            ov = self.torch.empty((self.batch, 0, self.w.shape[1]), dtype=self.torch.float64, device=self.device)
-        else:
-            ov, _ = self._overlap_call(d, q, False)
-        return [ov[b, 0, :r] if single else ov[b, :, :r] for b, r in enumerate(limits)]
-
-    def collectivity(self):
-        """[(rows_i,), ...] collectivities, as :meth:`DeviceBatchSolver.collectivity`; N is the structure's own size."""
-        self._need_vectors()
-        co = self._overlap_call(None, 0, True)[1]
-        return [co[b, :r] for b, r in enumerate(self._subset_plan["row_limits"])]
-
-    def distance_fluctuation(self, coord, mode_subset=None, projected=True, atom_scale=None, tem=None, tem_factors=K_B):
-        """
-        [(n_i, n_i), ...] fluctuations of the inter-atom distances, as :meth:`DeviceBatchSolver.distance_fluctuation`
-        (no reference counterpart) with the selection of :meth:`mean_square_fluctuation`: views into one buffer packed
-        like :meth:`dcc`'s.  ``coord`` is the packed (sum(sizes), 3) tensor given to :meth:`solve`, ``atom_scale`` None or a
-        packed (sum(sizes),) tensor -- ``solver.inv_sqrt_mass`` for Cartesian distances behind ``masses``.  Every
-        structure is summed over its own atoms and rows: pad rows never carry a weight, pad columns are never read.
-        """
-        total = int(self.offsets[-1])
-        cp, sp = self._distance_fluctuation_args(coord, (total,), projected, atom_scale)
-        sel, counts = self._selection(mode_subset, pinv_default=False)
-        sq = np.concatenate([[0], np.cumsum(np.asarray(self.sizes, dtype=np.int64) ** 2)])
-        out = self.torch.empty((int(sq[-1]),), dtype=self.torch.float64, device=self.device)
-        wp, vp = C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr())
-        if projected:
-            self.ctx.check(self._L.sc_batch_plan_modes_distfluct_f64(
-                self._plan, wp, vp, self.w.shape[1], C.byref(sel), counts, cp, sp, C.c_void_p(out.data_ptr())))
-        else:
-            self.ctx.check(self._L.sc_batch_plan_modes_dcc_f64(
-                self._plan, wp, vp, self.w.shape[1], C.byref(sel), counts, 0, int(self.consumer_budget_bytes or 0),
-                C.c_void_p(out.data_ptr())))
-        views = [out[sq[b]: sq[b + 1]].view(n, n) for b, n in enumerate(self.sizes)]
-        if not projected:
-            for b, c in enumerate(views):
-                if atom_scale is not None:
-                    sc = atom_scale[self.offsets[b]: self.offsets[b + 1]]
-                    c *= sc[:, None] * sc[None, :]
-                diag = c.diagonal().clone()
-                c *= -2
-                c += diag[:, None] + diag[None, :]
-        if tem is not None:
-            out *= tem * tem_factors
-        return views
-
-    def dcc(self, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
-        """
-        [(n_i, n_i), ...] dynamic cross-correlations (nma.py:233-359), as :meth:`DeviceBatchSolver.dcc`.
-        ``mode_subset=None`` on a full-spectrum solver: per structure every mode with ``|lambda| > 1e-6 max|lambda|``, the
-        maximum taken over the structure's OWN eigenvalues (the slot's pads are larger and never enter); on a
-        ``subset_by_index`` solver every solved non-trivial mode; behind a window solve the window.
-        """
-        sel, counts = self._selection(mode_subset, pinv_default=True)
-        sq = np.concatenate([[0], np.cumsum(np.asarray(self.sizes, dtype=np.int64) ** 2)])
-        out = self.torch.empty((int(sq[-1]),), dtype=self.torch.float64, device=self.device)
-        self.ctx.check(self._L.sc_batch_plan_modes_dcc_f64(
-            self._plan, C.c_void_p(self.w.data_ptr()), C.c_void_p(self.v.data_ptr()), self.w.shape[1], C.byref(sel),
-            counts, int(bool(norm)), int(self.consumer_budget_bytes or 0), C.c_void_p(out.data_ptr())))
-        if tem is not None:
-            out *= tem
-            out *= tem_factors
-        return [out[sq[b]: sq[b + 1]].view(n, n) for b, n in enumerate(self.sizes)]
 
     def close(self):
         if getattr(self, "_plan", None) is not None and self._plan.value:

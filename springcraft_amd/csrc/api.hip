@@ -909,103 +909,6 @@ int64_t sc_eigh_workspace_bytes(int64_t n, int64_t batch, int want_vectors) {
   return (int64_t)eigh_workspace_bytes(n, batch, want_vectors != 0);
 }
 
-// ---- batch consumers (batch_consumers.hip) -------------------------------------------------------------------------
-static int check_modes_args(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
-                            int dim, const sc_mode_selection* sel, const double* d_out, bool padded = false) {
-  if (!ctx) return SC_ERR_INVALID_ARG;
-  if (m <= 0 || nvec <= 0 || batch <= 0 || !d_w || !d_v || !sel || !d_out)
-    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
-  if ((dim != 1 && dim != 3) || (!padded && m % dim != 0))   // (padded: m is a plan's slot order)
-    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "dim must be 1 or 3 and divide m = %lld", (long long)m);
-  if (m > INT32_MAX || nvec > m || batch > INT32_MAX || (size_t)batch * nvec > (size_t)INT32_MAX)
-    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "(batch, nvec, m) = (%lld, %lld, %lld) is not a solver's result shape",
-                        (long long)batch, (long long)nvec, (long long)m);
-  switch (sel->kind) {
-    case SC_SEL_FROM_ROW:
-      if (sel->row0 < 0 || sel->row0 > nvec)
-        return sc_set_error(ctx, SC_ERR_INDEX, "row0 %lld outside 0..%lld", (long long)sel->row0, (long long)nvec);
-      break;
-    case SC_SEL_ROWS:
-      if (sel->n_rows < 0 || sel->n_rows > INT32_MAX / 4 || (sel->n_rows > 0 && !sel->d_rows))
-        return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad row list");
-      break;
-    case SC_SEL_PINV:
-      if (!(sel->rcond >= 0.0)) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "rcond must be >= 0");
-      break;
-    default:
-      return sc_set_error(ctx, SC_ERR_INVALID_ARG, "unknown selection kind %d", (int)sel->kind);
-  }
-  return SC_OK;
-}
-
-int sc_dev_modes_msf_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
-                         int dim, const sc_mode_selection* sel, const int64_t* d_counts, double* d_out) {
-  SC_TRY(check_modes_args(ctx, d_w, d_v, m, nvec, batch, dim, sel, d_out));
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  return batch_msf_device(ctx, d_w, d_v, m, nvec, batch, dim, *sel, d_counts, 0, d_out);
-}
-
-int sc_dev_modes_dcc_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
-                         int dim, const sc_mode_selection* sel, const int64_t* d_counts, int norm, int64_t budget_bytes,
-                         double* d_out) {
-  SC_TRY(check_modes_args(ctx, d_w, d_v, m, nvec, batch, dim, sel, d_out));
-  if (budget_bytes < 0) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "budget_bytes must be >= 0");
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  return batch_dcc_device(ctx, d_w, d_v, m, nvec, batch, dim, *sel, d_counts, norm, (size_t)budget_bytes, d_out);
-}
-
-int sc_dev_modes_aniso_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
-                           const sc_mode_selection* sel, const int64_t* d_counts, double* d_out) {
-  SC_TRY(check_modes_args(ctx, d_w, d_v, m, nvec, batch, 3, sel, d_out));
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  return batch_aniso_device(ctx, d_w, d_v, m, nvec, batch, *sel, d_counts, 0, d_out);
-}
-
-int sc_dev_modes_distfluct_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
-                               const sc_mode_selection* sel, const int64_t* d_counts, const double* d_coord,
-                               const double* d_atom_scale, double* d_out) {
-  SC_TRY(check_modes_args(ctx, d_w, d_v, m, nvec, batch, 3, sel, d_out));
-  if (!d_coord) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "distance fluctuations need the coordinates");
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  return batch_distfluct_device(ctx, d_w, d_v, m, nvec, batch, *sel, d_counts, d_coord, d_atom_scale, d_out);
-}
-
-// (shared with the plan entry: `padded` = m is a plan's slot order)
-static int check_overlap_args(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
-                              const double* d_disp, int64_t q, const double* d_overlap, const double* d_collectivity,
-                              bool padded = false) {
-  if (!ctx) return SC_ERR_INVALID_ARG;
-  if (m <= 0 || nvec <= 0 || batch <= 0 || !d_v) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
-  if ((dim != 1 && dim != 3) || (!padded && m % dim != 0))
-    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "dim must be 1 or 3 and divide m = %lld", (long long)m);
-  if (m > INT32_MAX || nvec > m || batch > INT32_MAX || (size_t)batch * nvec > (size_t)INT32_MAX)
-    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "(batch, nvec, m) = (%lld, %lld, %lld) is not a solver's result shape",
-                        (long long)batch, (long long)nvec, (long long)m);
-  if (q < 0 || q > INT32_MAX / 4) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "q = %lld displacement vectors", (long long)q);
-  if (!d_overlap && !d_collectivity) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "both outputs are NULL");
-  if ((q > 0 && (!d_disp || !d_overlap)) || (q == 0 && !d_collectivity))
-    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "q = %lld needs %s", (long long)q,
-                        q > 0 ? "d_disp and d_overlap" : "d_collectivity");
-  return SC_OK;
-}
-
-int sc_dev_modes_overlap_f64(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
-                             const double* d_disp, int64_t q, const int64_t* d_counts, double* d_overlap,
-                             double* d_collectivity) {
-  SC_TRY(check_overlap_args(ctx, d_v, m, nvec, batch, dim, d_disp, q, d_overlap, d_collectivity));
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  return modes_overlap_device(ctx, d_v, m, nvec, batch, dim, nullptr, nvec, d_disp, q, d_counts, d_overlap,
-                              d_collectivity);
-}
-
-int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
-                                     int64_t budget_bytes) {
-  if (m <= 0 || nvec <= 0 || batch <= 0 || n_sel < 0 || (dim != 1 && dim != 3) || budget_bytes < 0) return 0;
-  if (what == 3) return 0;   // overlaps and collectivities hold no workspace
-  if ((what == 2 || what == 4) && (dim != 3 || m % 3 != 0)) return 0;
-  return (int64_t)batch_modes_workspace_bytes(m, nvec, batch, dim, n_sel, what, (size_t)budget_bytes);
-}
-
 // ---- ragged / decorated batches ---------------------------------------------------------------------------------
 }  // extern "C"
 
@@ -1041,6 +944,129 @@ struct Blob {
     return off;
   }
 };
+
+// ---- mode consumers of a batch (batch_consumers.hip, dist_fluct.hip, mode_overlap.hip) ---------------------------------
+// Whose modes a consumer works on: the (batch, nvec, m) results of a uniform batch (sc_dev_modes_*: m = dim * n_atoms) or
+// of a plan's padded slots (sc_batch_plan_modes_*).  Each consumer has ONE body, modes_* below, which runs every check and
+// calls the launcher; its two entries only build this description.
+struct ModesOf {
+  sc_ctx* ctx = nullptr;
+  int64_t m = 0, nvec = 0, batch = 0;
+  int dim = 0;
+  RaggedView view{};       // a plan's records: m is then the slot order (dim need not divide it) and d_out is packed
+  int64_t first_row = 0;   // a plan's global mode index of row 0 of (w, v), as the caller gave it: checked after the rest
+  const RaggedView* ragged() const { return view.d_rec ? &view : nullptr; }
+};
+
+const RaggedRec* plan_records(const sc_batch_plan* plan) {
+  return reinterpret_cast<const RaggedRec*>(plan->d_blob + plan->off_ragged);
+}
+
+// (a NULL plan gives the empty description, which every body answers as it answers a NULL ctx)
+ModesOf plan_modes_of(const sc_batch_plan* plan, int64_t nvec, int64_t first_row) {
+  if (!plan) return ModesOf{};
+  const RaggedView rv{plan_records(plan), (int)first_row, plan->max_atoms, plan->atom_off.back(), plan->total_sq};
+  return ModesOf{plan->ctx, plan->order, nvec, plan->count, plan->dim, rv, first_row};
+}
+
+// The (m, nvec, batch, dim) checks of every consumer; `pointers`: the consumer's required pointers are all there
+int check_modes_shape(const ModesOf& who, bool pointers) {
+  sc_ctx* ctx = who.ctx;
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  if (who.m <= 0 || who.nvec <= 0 || who.batch <= 0 || !pointers) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  if ((who.dim != 1 && who.dim != 3) || (!who.ragged() && who.m % who.dim != 0))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "dim must be 1 or 3 and divide m = %lld", (long long)who.m);
+  if (who.m > INT32_MAX || who.nvec > who.m || who.batch > INT32_MAX || (size_t)who.batch * who.nvec > (size_t)INT32_MAX)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "(batch, nvec, m) = (%lld, %lld, %lld) is not a solver's result shape",
+                        (long long)who.batch, (long long)who.nvec, (long long)who.m);
+  return SC_OK;
+}
+
+int check_first_row(const ModesOf& who) {
+  if (!who.ragged() || (who.first_row >= 0 && who.first_row < who.m)) return SC_OK;
+  return sc_set_error(who.ctx, SC_ERR_INDEX, "first row %lld outside 0..%lld", (long long)who.first_row, (long long)who.m - 1);
+}
+
+int check_modes_args(const ModesOf& who, const double* d_w, const double* d_v, const sc_mode_selection* sel,
+                     const double* d_out) {
+  SC_TRY(check_modes_shape(who, d_w && d_v && sel && d_out));
+  switch (sel->kind) {
+    case SC_SEL_FROM_ROW:
+      if (sel->row0 < 0 || sel->row0 > who.nvec)
+        return sc_set_error(who.ctx, SC_ERR_INDEX, "row0 %lld outside 0..%lld", (long long)sel->row0, (long long)who.nvec);
+      break;
+    case SC_SEL_ROWS:
+      if (sel->n_rows < 0 || sel->n_rows > INT32_MAX / 4 || (sel->n_rows > 0 && !sel->d_rows))
+        return sc_set_error(who.ctx, SC_ERR_INVALID_ARG, "bad row list");
+      break;
+    case SC_SEL_PINV:
+      if (!(sel->rcond >= 0.0)) return sc_set_error(who.ctx, SC_ERR_INVALID_ARG, "rcond must be >= 0");
+      break;
+    default:
+      return sc_set_error(who.ctx, SC_ERR_INVALID_ARG, "unknown selection kind %d", (int)sel->kind);
+  }
+  return check_first_row(who);
+}
+
+int modes_msf(const ModesOf& who, const double* d_w, const double* d_v, const sc_mode_selection* sel,
+              const int64_t* d_counts, double* d_out) {
+  SC_TRY(check_modes_args(who, d_w, d_v, sel, d_out));
+  SC_HIP(who.ctx, hipSetDevice(who.ctx->device));
+  return batch_msf_device(who.ctx, d_w, d_v, who.m, who.nvec, who.batch, who.dim, *sel, d_counts, 0, d_out, who.ragged());
+}
+
+int modes_dcc(const ModesOf& who, const double* d_w, const double* d_v, const sc_mode_selection* sel,
+              const int64_t* d_counts, int norm, int64_t budget_bytes, double* d_out) {
+  SC_TRY(check_modes_args(who, d_w, d_v, sel, d_out));
+  if (budget_bytes < 0) return sc_set_error(who.ctx, SC_ERR_INVALID_ARG, "budget_bytes must be >= 0");
+  SC_HIP(who.ctx, hipSetDevice(who.ctx->device));
+  return batch_dcc_device(who.ctx, d_w, d_v, who.m, who.nvec, who.batch, who.dim, *sel, d_counts, norm,
+                          (size_t)budget_bytes, d_out, who.ragged());
+}
+
+// (aniso, distfluct: the sc_dev entries have no dim argument and describe dim 3, so only a plan can fail the dim check)
+int modes_aniso(const ModesOf& who, const double* d_w, const double* d_v, const sc_mode_selection* sel,
+                const int64_t* d_counts, double* d_out) {
+  SC_TRY(check_modes_args(who, d_w, d_v, sel, d_out));
+  if (who.dim != 3)
+    return sc_set_error(who.ctx, SC_ERR_INVALID_ARG, "anisotropic fluctuation tensors need an ANM plan (dim 3)");
+  SC_HIP(who.ctx, hipSetDevice(who.ctx->device));
+  return batch_aniso_device(who.ctx, d_w, d_v, who.m, who.nvec, who.batch, *sel, d_counts, 0, d_out, who.ragged());
+}
+
+int modes_distfluct(const ModesOf& who, const double* d_w, const double* d_v, const sc_mode_selection* sel,
+                    const int64_t* d_counts, const double* d_coord, const double* d_atom_scale, double* d_out) {
+  SC_TRY(check_modes_args(who, d_w, d_v, sel, d_out));
+  if (who.dim != 3) return sc_set_error(who.ctx, SC_ERR_INVALID_ARG, "distance fluctuations need an ANM plan (dim 3)");
+  if (!d_coord) return sc_set_error(who.ctx, SC_ERR_INVALID_ARG, "distance fluctuations need the coordinates");
+  SC_HIP(who.ctx, hipSetDevice(who.ctx->device));
+  return batch_distfluct_device(who.ctx, d_w, d_v, who.m, who.nvec, who.batch, *sel, d_counts, d_coord, d_atom_scale,
+                                d_out, who.ragged());
+}
+
+int modes_overlap(const ModesOf& who, const double* d_v, const double* d_disp, int64_t q, const int64_t* d_counts,
+                  double* d_overlap, double* d_collectivity) {
+  SC_TRY(check_modes_shape(who, d_v != nullptr));
+  sc_ctx* ctx = who.ctx;
+  if (q < 0 || q > INT32_MAX / 4) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "q = %lld displacement vectors", (long long)q);
+  if (!d_overlap && !d_collectivity) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "both outputs are NULL");
+  if ((q > 0 && (!d_disp || !d_overlap)) || (q == 0 && !d_collectivity))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "q = %lld needs %s", (long long)q,
+                        q > 0 ? "d_disp and d_overlap" : "d_collectivity");
+  SC_TRY(check_first_row(who));
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return modes_overlap_device(ctx, d_v, who.m, who.nvec, who.batch, who.dim, nullptr, who.nvec, d_disp, q, d_counts,
+                              d_overlap, d_collectivity, who.ragged());
+}
+
+int64_t modes_workspace_bytes(const ModesOf& who, int64_t n_sel, int what, int64_t budget_bytes) {
+  if (who.m <= 0 || who.nvec <= 0 || who.batch <= 0 || n_sel < 0 || (who.dim != 1 && who.dim != 3) || budget_bytes < 0)
+    return 0;
+  if (what == 3) return 0;   // overlaps and collectivities hold no workspace
+  if ((what == 2 || what == 4) && (who.dim != 3 || (!who.ragged() && who.m % 3 != 0))) return 0;
+  return (int64_t)batch_modes_workspace_bytes(who.m, who.nvec, who.batch, who.dim, n_sel, what, (size_t)budget_bytes,
+                                              who.ragged());
+}
 
 }  // namespace
 
@@ -1301,15 +1327,7 @@ int sc_batch_plan_fill_from_pairs_f64(sc_batch_plan* plan, const double* d_coord
 
 int64_t sc_batch_plan_order(const sc_batch_plan* plan) { return plan ? plan->order : 0; }
 
-// ---- partial spectrum and mode consumers of a plan's padded slots ------------------------------------------------------
-static const RaggedRec* plan_records(const sc_batch_plan* plan) {
-  return reinterpret_cast<const RaggedRec*>(plan->d_blob + plan->off_ragged);
-}
-
-static RaggedView plan_view(const sc_batch_plan* plan, int first_row) {
-  return RaggedView{plan_records(plan), first_row, plan->max_atoms, plan->atom_off.back(), plan->total_sq};
-}
-
+// ---- partial spectrum of a plan's padded slots -----------------------------------------------------------------------------
 int sc_batch_plan_eigh_range_f64(sc_batch_plan* plan, double* d_a, int64_t il, int64_t iu, double* d_w, double* d_v) {
   if (!plan) return SC_ERR_INVALID_ARG;
   sc_ctx* ctx = plan->ctx;
@@ -1336,85 +1354,66 @@ int sc_batch_plan_eigh_window_f64(sc_batch_plan* plan, double* d_a, double vl, d
                                    plan_records(plan));
 }
 
-static int check_plan_modes_args(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
-                                 const sc_mode_selection* sel, const double* d_out) {
-  if (!plan) return SC_ERR_INVALID_ARG;
-  SC_TRY(check_modes_args(plan->ctx, d_w, d_v, plan->order, nvec, plan->count, plan->dim, sel, d_out, true));
-  if (sel->reserved < 0 || sel->reserved >= plan->order)
-    return sc_set_error(plan->ctx, SC_ERR_INDEX, "first row %d outside 0..%lld", (int)sel->reserved,
-                        (long long)plan->order - 1);
-  return SC_OK;
+// ---- mode consumers of a uniform batch and of a plan's slots (first_row in sel->reserved): the bodies are modes_* above --
+int sc_dev_modes_msf_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                         int dim, const sc_mode_selection* sel, const int64_t* d_counts, double* d_out) {
+  return modes_msf(ModesOf{ctx, m, nvec, batch, dim}, d_w, d_v, sel, d_counts, d_out);
 }
-
 int sc_batch_plan_modes_msf_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
                                 const sc_mode_selection* sel, const int64_t* d_counts, double* d_out) {
-  SC_TRY(check_plan_modes_args(plan, d_w, d_v, nvec, sel, d_out));
-  sc_ctx* ctx = plan->ctx;
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  const RaggedView rv = plan_view(plan, (int)sel->reserved);
-  return batch_msf_device(ctx, d_w, d_v, plan->order, nvec, plan->count, plan->dim, *sel, d_counts, 0, d_out, &rv);
+  return modes_msf(plan_modes_of(plan, nvec, sel ? sel->reserved : 0), d_w, d_v, sel, d_counts, d_out);
 }
 
+int sc_dev_modes_dcc_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                         int dim, const sc_mode_selection* sel, const int64_t* d_counts, int norm, int64_t budget_bytes,
+                         double* d_out) {
+  return modes_dcc(ModesOf{ctx, m, nvec, batch, dim}, d_w, d_v, sel, d_counts, norm, budget_bytes, d_out);
+}
 int sc_batch_plan_modes_dcc_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
                                 const sc_mode_selection* sel, const int64_t* d_counts, int norm, int64_t budget_bytes,
                                 double* d_out) {
-  SC_TRY(check_plan_modes_args(plan, d_w, d_v, nvec, sel, d_out));
-  sc_ctx* ctx = plan->ctx;
-  if (budget_bytes < 0) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "budget_bytes must be >= 0");
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  const RaggedView rv = plan_view(plan, (int)sel->reserved);
-  return batch_dcc_device(ctx, d_w, d_v, plan->order, nvec, plan->count, plan->dim, *sel, d_counts, norm,
-                          (size_t)budget_bytes, d_out, &rv);
+  return modes_dcc(plan_modes_of(plan, nvec, sel ? sel->reserved : 0), d_w, d_v, sel, d_counts, norm, budget_bytes, d_out);
 }
 
+int sc_dev_modes_aniso_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                           const sc_mode_selection* sel, const int64_t* d_counts, double* d_out) {
+  return modes_aniso(ModesOf{ctx, m, nvec, batch, 3}, d_w, d_v, sel, d_counts, d_out);
+}
 int sc_batch_plan_modes_aniso_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
                                   const sc_mode_selection* sel, const int64_t* d_counts, double* d_out) {
-  SC_TRY(check_plan_modes_args(plan, d_w, d_v, nvec, sel, d_out));
-  sc_ctx* ctx = plan->ctx;
-  if (plan->dim != 3)
-    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "anisotropic fluctuation tensors need an ANM plan (dim 3)");
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  const RaggedView rv = plan_view(plan, (int)sel->reserved);
-  return batch_aniso_device(ctx, d_w, d_v, plan->order, nvec, plan->count, *sel, d_counts, 0, d_out, &rv);
+  return modes_aniso(plan_modes_of(plan, nvec, sel ? sel->reserved : 0), d_w, d_v, sel, d_counts, d_out);
 }
 
+int sc_dev_modes_distfluct_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                               const sc_mode_selection* sel, const int64_t* d_counts, const double* d_coord,
+                               const double* d_atom_scale, double* d_out) {
+  return modes_distfluct(ModesOf{ctx, m, nvec, batch, 3}, d_w, d_v, sel, d_counts, d_coord, d_atom_scale, d_out);
+}
 int sc_batch_plan_modes_distfluct_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
                                       const sc_mode_selection* sel, const int64_t* d_counts, const double* d_coord,
                                       const double* d_atom_scale, double* d_out) {
-  SC_TRY(check_plan_modes_args(plan, d_w, d_v, nvec, sel, d_out));
-  sc_ctx* ctx = plan->ctx;
-  if (plan->dim != 3) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "distance fluctuations need an ANM plan (dim 3)");
-  if (!d_coord) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "distance fluctuations need the coordinates");
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  const RaggedView rv = plan_view(plan, (int)sel->reserved);
-  return batch_distfluct_device(ctx, d_w, d_v, plan->order, nvec, plan->count, *sel, d_counts, d_coord, d_atom_scale,
-                                d_out, &rv);
+  return modes_distfluct(plan_modes_of(plan, nvec, sel ? sel->reserved : 0), d_w, d_v, sel, d_counts, d_coord,
+                         d_atom_scale, d_out);
 }
 
+int sc_dev_modes_overlap_f64(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
+                             const double* d_disp, int64_t q, const int64_t* d_counts, double* d_overlap,
+                             double* d_collectivity) {
+  return modes_overlap(ModesOf{ctx, m, nvec, batch, dim}, d_v, d_disp, q, d_counts, d_overlap, d_collectivity);
+}
 int sc_batch_plan_modes_overlap_f64(sc_batch_plan* plan, const double* d_v, int64_t nvec, int64_t first_row,
                                     const double* d_disp, int64_t q, const int64_t* d_counts, double* d_overlap,
                                     double* d_collectivity) {
-  if (!plan) return SC_ERR_INVALID_ARG;
-  sc_ctx* ctx = plan->ctx;
-  SC_TRY(check_overlap_args(ctx, d_v, plan->order, nvec, plan->count, plan->dim, d_disp, q, d_overlap, d_collectivity,
-                            true));
-  if (first_row < 0 || first_row >= plan->order)
-    return sc_set_error(ctx, SC_ERR_INDEX, "first row %lld outside 0..%lld", (long long)first_row,
-                        (long long)plan->order - 1);
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  const RaggedView rv = plan_view(plan, (int)first_row);
-  return modes_overlap_device(ctx, d_v, plan->order, nvec, plan->count, plan->dim, nullptr, nvec, d_disp, q, d_counts,
-                              d_overlap, d_collectivity, &rv);
+  return modes_overlap(plan_modes_of(plan, nvec, first_row), d_v, d_disp, q, d_counts, d_overlap, d_collectivity);
 }
 
+int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
+                                     int64_t budget_bytes) {
+  return modes_workspace_bytes(ModesOf{nullptr, m, nvec, batch, dim}, n_sel, what, budget_bytes);
+}
 int64_t sc_batch_plan_modes_workspace_bytes(const sc_batch_plan* plan, int64_t nvec, int64_t n_sel, int what,
                                             int64_t budget_bytes) {
-  if (!plan || nvec <= 0 || n_sel < 0 || budget_bytes < 0) return 0;
-  if (what == 3) return 0;
-  if ((what == 2 || what == 4) && plan->dim != 3) return 0;
-  const RaggedView rv = plan_view(plan, 0);
-  return (int64_t)batch_modes_workspace_bytes(plan->order, nvec, plan->count, plan->dim, n_sel, what, (size_t)budget_bytes,
-                                              &rv);
+  return modes_workspace_bytes(plan_modes_of(plan, nvec, 0), n_sel, what, budget_bytes);
 }
 
 void sc_batch_plan_destroy(sc_batch_plan* plan) {
