@@ -381,6 +381,20 @@ int sc_modes_overlap(sc_modes* modes, const int64_t* mode_idx, int64_t k, const 
  * from a to c; symmetric bit for bit, the diagonal exactly 0, NaN for two distinct atoms at one position.  Computed by
  * sc_dev_modes_distfluct_f64's kernel with a batch of one (no atom scale: a mass-weighted model's modes enter as they are). */
 int sc_modes_distfluct(sc_modes* modes, const int64_t* mode_idx, int64_t k, const double* coord, double* out);
+/* Linear response of the model to q forces (nma.py:422-473 linear_response = covariance @ force) in mode space, without
+ * the (n, n) covariance.  Host pointers.  force (q, n), out (q, n): out_j = S sum_i v_i <v_i, S f_j> / w_i over the selected
+ * modes, S = diag(atom_scale) per atom (atom_scale (n / dim) or NULL for 1: a mass-weighted model passes 1 / sqrt(mass)
+ * for the Cartesian response).  mode_idx != NULL: the k listed modes (rcond is not read).  mode_idx == NULL (k must be 0):
+ * every mode with |w| > rcond max|w|, the rule of numpy.linalg.pinv(hermitian=True) behind the reference's covariance
+ * (anm.py:114-117), as sc_modes_prs takes it; out is then pinv(H, rcond) f.  A mode index outside 0..n-1 (negative ones
+ * count from the end): SC_ERR_INDEX.  Computed by sc_dev_mode_response_f64's kernels with a batch of one. */
+int sc_modes_response(sc_modes* modes, const int64_t* mode_idx, int64_t k, double rcond, const double* force, int64_t q,
+                      const double* atom_scale, double* out);
+/* Displacements built from the modes: no reference counterpart (ProDy: deformAtoms / traverseMode / sampleModes).  Host
+ * pointers.  coef (q, k), out (q, n): out_j = sum_i coef[j, i] v_(mode_idx[i]) over the k listed modes, added in the order
+ * of the list; the inverse of sc_modes_overlap over a complete set.  GNM and ANM; k = 0 gives zeros.  Computed by
+ * sc_dev_mode_combine_f64's kernels with a batch of one. */
+int sc_modes_combine(sc_modes* modes, const int64_t* mode_idx, int64_t k, const double* coef, int64_t q, double* out);
 /* out (n / dim, n / dim): sum over the listed modes of <v_a, v_b> / w; norm != 0 divides by sqrt(c_aa c_bb). */
 int sc_modes_dcc(sc_modes* modes, const int64_t* mode_idx, int64_t k, int norm, double* out);
 /* ANM only. out (n / 3, n / 3) row-major: sums of the squared 3x3 blocks of pinv(H, rcond) (numpy hermitian
@@ -476,11 +490,41 @@ int sc_dev_modes_overlap_f64(sc_ctx* ctx, const double* d_v, int64_t m, int64_t 
 int sc_dev_modes_distfluct_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
                                const sc_mode_selection* sel, const int64_t* d_counts, const double* d_coord,
                                const double* d_atom_scale, double* d_out);
-/* Bytes of device workspace the three entries above hold for such a call (allocated lazily, cached, grown on demand --
+/* Linear response to q forces per structure over the selected rows (nma.py:422-473 linear_response = covariance @ force,
+ * there for one model and through the (3N, 3N) pseudo-inverse), in mode space: no covariance and no m x m workspace.
+ *
+ *   c[b, j, r] = <v_r, g_j> s[b, r],  g_j[dim a + d] = t_a f_j[dim a + d]             (one pass ALONG the listed rows)
+ *   X[b, j, dim a + d] = t_a sum_r c[b, j, r] V[b, r, dim a + d]                        (one pass ACROSS them)
+ *
+ * with s and the selection as above and t = d_atom_scale (batch, m / dim), NULL for 1.  d_force and d_out (batch, q, m).
+ * With SC_SEL_PINV on a full spectrum and t = 1 this is pinv(H, rcond) f; with t = 1 / sqrt(mass) behind a mass-weighted
+ * solve the Cartesian response.  A row without weight is not read and contributes nothing, a listed row outside
+ * 0..nvec-1 turns the structure's result into NaN, and so do NaN eigenvalues (a failed structure).  Both passes read the
+ * listed rows once per group of four forces.  No atomics: the first pass adds a row's atoms in a fixed order given by (m,
+ * dim), the second the rows in ascending order within chunks cut by the number of listed rows alone, then the chunks in
+ * ascending order: X[b, j] does not depend, bit for bit, on the batch size, the structure's position, its neighbours, q
+ * or the forces beside f_j.  The partial sums of a slab of structures take at most SPRINGCRAFT_MODES_BUDGET_BYTES (else 1
+ * GiB).  q = 0 does nothing.  Enqueue only. */
+int sc_dev_mode_response_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                             int dim, const sc_mode_selection* sel, const int64_t* d_counts, const double* d_force,
+                             int64_t q, const double* d_atom_scale, double* d_out);
+/* The second pass on coefficients the caller chose -- displacements along modes, samples, and the inverse of
+ * sc_dev_modes_overlap_f64's result; no reference counterpart (ProDy: deformAtoms / traverseMode / sampleModes):
+ *   X[b, j, dim a + d] = t_a sum_r d_coef[b, j, r] V[b, r, dim a + d]
+ * over EVERY row r below the structure's row limit, min(d_counts[b], nvec) or nvec without counts, trivial rows included:
+ * what is not wanted gets the coefficient 0.  d_coef (batch, q, nvec), d_out (batch, q, m).  Rows at or behind the limit
+ * are never read, and neither are their coefficients, whatever they hold.  d_w is not read: a structure whose solve
+ * failed is the caller's to mask, as for the overlaps.  Order of the sums and bit-for-bit independence as above.  Enqueue
+ * only. */
+int sc_dev_mode_combine_f64(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
+                            const double* d_coef, int64_t q, const int64_t* d_counts, const double* d_atom_scale,
+                            double* d_out);
+/* Bytes of device workspace the entries above hold for such a call (allocated lazily, cached, grown on demand --
  * the one step of a first call that waits for the stream).  n_sel: rows that carry a weight (nvec - row0, n_rows, or
  * nvec for SC_SEL_PINV); what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3 and m % 3 == 0, else 0), 3 = overlaps /
  * collectivities (always 0: sc_dev_modes_overlap_f64 holds no workspace), 4 = distance fluctuations (the weights only; dim
- * 3 and m % 3 == 0, else 0); budget_bytes as above. */
+ * 3 and m % 3 == 0, else 0), 5 = response (weights, the coefficients of four forces and the partial sums of a slab), 6 =
+ * combine (the partial sums of a slab); budget_bytes as above. */
 int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
                                      int64_t budget_bytes);
 
@@ -536,6 +580,21 @@ int sc_batch_plan_modes_overlap_f64(sc_batch_plan* plan, const double* d_v, int6
 int sc_batch_plan_modes_distfluct_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
                                       const sc_mode_selection* sel, const int64_t* d_counts, const double* d_coord,
                                       const double* d_atom_scale, double* d_out);
+/* sc_dev_mode_response_f64 for the plan's padded slots (GNM and ANM plans; sel->reserved holds first_row as for the
+ * sc_batch_plan_modes_* entries above): d_force and d_out (q, dim * sum n_atoms)
+ * packed as sc_batch_plan_modes_overlap_f64's displacement is, structure b's vector j at j * dim * sum n + dim *
+ * atom_off_b; d_atom_scale (sum n_atoms,) packed or NULL.  Only a structure's own columns are read and written; pad rows
+ * never carry a weight and are not read.  A structure's bits depend on the slot order, its own size and the selection,
+ * not on its neighbours or its position. */
+int sc_batch_plan_mode_response_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
+                                    const sc_mode_selection* sel, const int64_t* d_counts, const double* d_force,
+                                    int64_t q, const double* d_atom_scale, double* d_out);
+/* sc_dev_mode_combine_f64 for the plan's padded slots: d_coef (count, q, nvec); first_row as for
+ * sc_batch_plan_modes_overlap_f64.  Structure b's row limit is min(d_counts[b], nvec, own_b - first_row): pad rows and
+ * their coefficients are never read, pad columns neither read nor written.  d_out and d_atom_scale packed as above. */
+int sc_batch_plan_mode_combine_f64(sc_batch_plan* plan, const double* d_v, int64_t nvec, int64_t first_row,
+                                   const double* d_coef, int64_t q, const int64_t* d_counts, const double* d_atom_scale,
+                                   double* d_out);
 /* What sc_dev_modes_workspace_bytes answers for a uniform batch, for the plan's (count, order). */
 int64_t sc_batch_plan_modes_workspace_bytes(const sc_batch_plan* plan, int64_t nvec, int64_t n_sel, int what,
                                             int64_t budget_bytes);

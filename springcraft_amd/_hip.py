@@ -52,6 +52,8 @@ EXPORTED_SYMBOLS = [
     "sc_modes_aniso", "sc_dev_modes_aniso_f64", "sc_batch_plan_modes_aniso_f64",
     "sc_modes_overlap", "sc_dev_modes_overlap_f64", "sc_batch_plan_modes_overlap_f64",
     "sc_modes_distfluct", "sc_dev_modes_distfluct_f64", "sc_batch_plan_modes_distfluct_f64",
+    "sc_modes_response", "sc_dev_mode_response_f64", "sc_batch_plan_mode_response_f64",
+    "sc_modes_combine", "sc_dev_mode_combine_f64", "sc_batch_plan_mode_combine_f64",
 ]
 
 SC_SEL_FROM_ROW = 0
@@ -236,6 +238,12 @@ def lib():
         "sc_modes_distfluct": (i32, [vp, vp, i64, vp, vp]),
         "sc_dev_modes_distfluct_f64": (i32, [vp, vp, vp, i64, i64, i64, P(ModeSelection), vp, vp, vp, vp]),
         "sc_batch_plan_modes_distfluct_f64": (i32, [vp, vp, vp, i64, P(ModeSelection), vp, vp, vp, vp]),
+        "sc_modes_response": (i32, [vp, vp, i64, dbl, vp, i64, vp, vp]),
+        "sc_dev_mode_response_f64": (i32, [vp, vp, vp, i64, i64, i64, i32, P(ModeSelection), vp, vp, i64, vp, vp]),
+        "sc_batch_plan_mode_response_f64": (i32, [vp, vp, vp, i64, P(ModeSelection), vp, vp, i64, vp, vp]),
+        "sc_modes_combine": (i32, [vp, vp, i64, vp, i64, vp]),
+        "sc_dev_mode_combine_f64": (i32, [vp, vp, i64, i64, i64, i32, vp, i64, vp, vp, vp]),
+        "sc_batch_plan_mode_combine_f64": (i32, [vp, vp, i64, i64, vp, i64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -333,7 +341,8 @@ class Context:
 class Modes:
     """
     Owns one ``sc_modes``: all eigenpairs of a model, resident in device memory, plus the consumers that
-    work on them there (msf, dcc, prs, anisotropic tensors, overlaps and collectivities, distance fluctuations).  ``dim`` is 1 for a GNM and 3 for an ANM.
+    work on them there (msf, dcc, prs, anisotropic tensors, overlaps and collectivities, distance fluctuations,
+    linear response and linear combinations of modes).  ``dim`` is 1 for a GNM and 3 for an ANM.
     """
 
     def __init__(self, ctx, handle, dim):
@@ -419,6 +428,30 @@ class Modes:
             self._ctx.check(self._L.sc_modes_overlap(self._h, ptr(idx), len(idx), ptr(disp) if q else None, q, ptr(ov),
                                                      ptr(co)))
         return ov, co
+
+    def response(self, mode_idx, force, rcond=1e-6, atom_scale=None):
+        """
+        (q, order) linear response to the forces ``force`` (q, order), C-contiguous float64, over the listed modes;
+        ``mode_idx=None``: every mode with ``|w| > rcond max|w|``, the covariance rule.  ``atom_scale`` (n_atoms,) or None.
+        """
+        idx = None if mode_idx is None else self._index_list(mode_idx)
+        out = np.empty(force.shape)
+        if atom_scale is not None:
+            atom_scale = np.ascontiguousarray(atom_scale, dtype=np.float64)
+        if idx is not None and len(idx) == 0:   # (a NULL list means the pinv rule to the C entry)
+            out[...] = 0.0
+            return out
+        self._ctx.check(self._L.sc_modes_response(self._h, None if idx is None else ptr(idx),
+                                                  0 if idx is None else len(idx), float(rcond), ptr(force),
+                                                  force.shape[0], ptr(atom_scale), ptr(out)))
+        return out
+
+    def combine(self, mode_idx, coef):
+        """(q, order) sums ``sum_i coef[j, i] v[mode_idx[i]]``; ``coef`` (q, k) C-contiguous float64."""
+        idx = self._index_list(mode_idx)
+        out = np.empty((coef.shape[0], self.order))
+        self._ctx.check(self._L.sc_modes_combine(self._h, ptr(idx), len(idx), ptr(coef), coef.shape[0], ptr(out)))
+        return out
 
     def prs(self, rcond, norm):
         n = self.order // 3

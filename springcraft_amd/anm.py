@@ -65,9 +65,16 @@ class ANM(ElasticNetworkModel):
         """Displacements (frames, n, 3) animating mode ``index`` (anm.py:169-207)."""
         return nma.normal_mode(self, index, amplitude, frames, movement)
 
-    def linear_response(self, force):
-        """Displacement (n,3) induced by ``force`` via linear response theory (anm.py:209-238)."""
-        return nma.linear_response(self, force)
+    def linear_response(self, force, mode_subset=None):
+        """
+        Displacement (n,3) induced by ``force`` via linear response theory (anm.py:209-238); q forces (q,n,3) give
+        (q,n,3), ``mode_subset`` the response carried by those modes alone (:func:`nma.linear_response`).
+        """
+        return nma.linear_response(self, force, mode_subset)
+
+    def mode_displacement(self, coefficients, mode_subset=None):
+        """Displacement field(s) (n,3) / (q,n,3) ``sum_k c_k v_k`` over the selected modes (:func:`nma.mode_displacement`)."""
+        return nma.mode_displacement(self, coefficients, mode_subset)
 
     def frequencies(self):
         """Mode frequencies in arbitrary units, ascending (anm.py:240-256)."""

@@ -148,17 +148,27 @@ class _Layout:
                         (pairs, scale or None) blocks, the last two axes of ``pairs`` being (atom, atom), in which
                         ``pairs_out``'s result ``out`` is post-processed
     displacement()      (lead, tail, wording): a displacement has shape ``lead + tail`` or ``lead + (q,) + tail``
+    vectors_shape(q), vectors_out(buf, single)
+                        shape of a result buffer of q displacement-shaped vectors per structure, ``lead + (q,) + tail``,
+                        and the caller's form of it; ``single`` as for ``rows_out``
     """
 
-    def displacement_q(self, shape):
-        """(q, whether it is one vector without a q axis) of a displacement of ``shape``; ValueError for any other shape."""
+    def displacement_q(self, shape, what="displacement"):
+        """
+        (q, whether it is one vector without a q axis) of a displacement of ``shape``; ValueError for any other shape.
+        ``what``: how the message names the vector (a force has a displacement's shapes).
+        """
         lead, tail, names = self.displacement()
         shape = tuple(shape)
         if shape == lead + tail:
             return 1, True
         if len(shape) == len(lead) + 1 + len(tail) and shape[:len(lead)] == lead and shape[len(lead) + 1:] == tail:
             return shape[len(lead)], False
-        raise ValueError(f"Expected a displacement of shape {names}, got {shape}")
+        raise ValueError(f"Expected a {what} of shape {names}, got {shape}")
+
+    def vectors_shape(self, q):
+        lead, tail, _ = self.displacement()
+        return lead + (int(q),) + tail
 
 
 class _UniformLayout(_Layout):
@@ -182,6 +192,9 @@ class _UniformLayout(_Layout):
 
     def rows_out(self, t, single=False):
         return t[:, 0] if single else t
+
+    def vectors_out(self, buf, single=False):
+        return buf[:, 0] if single else buf
 
     def pair_blocks(self, out, atom_scale):
         return [(out, atom_scale)]
@@ -221,6 +234,10 @@ class _RaggedLayout(_Layout):
     def rows_out(self, t, single=False):
         return [t[b, 0, :r] if single else t[b, ..., :r] for b, r in enumerate(self.row_limits)]
 
+    def vectors_out(self, buf, single=False):
+        """``buf`` (q, sum(sizes)[, 3]) packed like the coordinates -> per structure the view (n_b[, 3]) or (q, n_b[, 3])."""
+        return [buf[0, a:b] if single else buf[:, a:b] for a, b in zip(self.atom_off, self.atom_off[1:])]
+
     def pair_blocks(self, out, atom_scale):
         return zip(out, [None] * len(out) if atom_scale is None else self.atoms_out(atom_scale))
 
@@ -240,6 +257,13 @@ _CONSUMER_ENTRIES = {
     "distfluct": ("sc_dev_modes_distfluct_f64", _DEV, "sc_batch_plan_modes_distfluct_f64", _PLAN),
     "overlap": ("sc_dev_modes_overlap_f64", ("ctx", "v", "m", "nvec", "batch", "dim"),
                 "sc_batch_plan_modes_overlap_f64", ("plan", "v", "nvec", "first_row")),
+}
+# the same for the consumers that return displacement fields (csrc/mode_response.hip): their C entries are named
+# sc_dev_mode_* / sc_batch_plan_mode_*
+_FIELD_ENTRIES = {
+    "response": ("sc_dev_mode_response_f64", _DEV + ("dim",), "sc_batch_plan_mode_response_f64", _PLAN),
+    "combine": ("sc_dev_mode_combine_f64", ("ctx", "v", "m", "nvec", "batch", "dim"),
+                "sc_batch_plan_mode_combine_f64", ("plan", "v", "nvec", "first_row")),
 }
 
 
@@ -338,19 +362,33 @@ class _BatchSolver:
             raise ValueError(f"Expected {name} of shape {tuple(shape)}, got {tuple(t.shape)}")
         return C.c_void_p(t.data_ptr())
 
+    def _vectors_in(self, t, what):
+        """
+        (q, single) of one or q displacement-shaped vectors per structure (``what``: "displacement" / "force"), checked
+        on the host: a contiguous CUDA float64 tensor on the solver's device with one of the layout's two shapes.
+        """
+        torch = self.torch
+        names = self._layout.displacement()[2]
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous CUDA float64 tensor of shape {names}")
+        if t.device != torch.device(self.device):
+            raise ValueError(f"{what} is on {t.device}, the solver on {self.device}")
+        return self._layout.displacement_q(t.shape, what)
+
     def _empty(self, shape):
         return self.torch.empty(shape, dtype=self.torch.float64, device=self.device)
 
     def _call(self, consumer, *args):
         """Enqueues ``consumer``'s C entry for this solver's layout: the entry's argument prefix, then ``args``."""
-        entry, prefix = _CONSUMER_ENTRIES[consumer][2:] if self._layout.ragged else _CONSUMER_ENTRIES[consumer][:2]
+        row = _CONSUMER_ENTRIES[consumer] if consumer in _CONSUMER_ENTRIES else _FIELD_ENTRIES[consumer]
+        entry, prefix = row[2:] if self._layout.ragged else row[:2]
         have = {"ctx": self.ctx.handle, "plan": self._plan, "w": C.c_void_p(self.w.data_ptr()),
                 "v": C.c_void_p(self.v.data_ptr()), "m": self.v.shape[2], "nvec": self.w.shape[1], "batch": self.batch,
                 "dim": self.dim, "first_row": self._first_row}
         self.ctx.check(getattr(self._L, entry)(*[have[k] for k in prefix], *args))
 
     # ---- consumers of the solved modes (reference: nma.py:66-359, there for one model) --------------------------------
-    # One body each for both solvers: self._layout says where the results lie, _CONSUMER_ENTRIES which C entry runs.  Like
+    # One body each for both solvers: self._layout says where the results lie, _CONSUMER_ENTRIES / _FIELD_ENTRIES which C entry runs.  Like
     # solve() they ONLY ENQUEUE on the solver's stream and return CUDA tensors that are valid in stream order: no
     # synchronisation, no host copy of w.  The one exception is the first call of a kind, which allocates its workspace.
     # The docstrings give the result of a DeviceBatchSolver first; a RaggedBatchSolver returns, per structure, a list of
@@ -459,13 +497,8 @@ class _BatchSolver:
         full-spectrum solver, else all ``nvec`` rows, NaN behind a window's count); only a structure's own columns are read.
         """
         self._need_vectors()
-        torch, d = self.torch, displacement
-        names = self._layout.displacement()[2]
-        if not isinstance(d, torch.Tensor) or not d.is_cuda or d.dtype != torch.float64 or not d.is_contiguous():
-            raise ValueError(f"displacement must be a contiguous CUDA float64 tensor of shape {names}")
-        if d.device != torch.device(self.device):
-            raise ValueError(f"displacement is on {d.device}, the solver on {self.device}")
-        q, single = self._layout.displacement_q(d.shape)
+        d = displacement
+        q, single = self._vectors_in(d, "displacement")
         ov = self._empty((self.batch, 0, self.w.shape[1])) if q == 0 else self._overlap_call(d, q, False)[0]
         return self._layout.rows_out(ov, single)
 
@@ -526,6 +559,104 @@ class _BatchSolver:
             buf *= tem * tem_factors
         return out
 
+    def linear_response(self, force, mode_subset=None, atom_scale=None):
+        """
+        (batch, n_atoms, 3) displacements ``sum_k v_k <v_k, f> / lambda_k`` over the selected modes in answer to the
+        structure's force(s) (nma.py:422-473, there ``covariance @ force`` for one model): computed in mode space, one
+        pass along and one across the selected rows of ``v`` per four forces, without a covariance.  ``force`` is a
+        contiguous CUDA float64 tensor (batch, n_atoms, 3) or (batch, q, n_atoms, 3); the result has its shape.  ANM solvers
+        only (``dim != 3`` raises ValueError before anything is enqueued).
+
+        ``mode_subset``, the window, ``subset_by_index`` and failed structures (NaN) exactly as in
+        :meth:`mean_square_fluctuation`, except that None on a full-spectrum solver takes the reference's covariance rule
+        as :meth:`dcc` does: every mode with ``|lambda| > 1e-6 max|lambda|`` of that structure -- the result is
+        ``pinv(H, rcond=1e-6) @ f``.  ``atom_scale``: None, or a (batch, n_atoms) CUDA float64 tensor ``s`` for
+        ``s_a sum_k v_k[a] <v_k, s f> / lambda_k``; with ``masses``, ``atom_scale=solver.inv_sqrt_mass`` gives the Cartesian
+        response ``M^-1/2 pinv(H_mw) M^-1/2 f`` (None: the modes as they are, the reference's ``covariance @ force``).
+        A structure's bits do not depend on the batch size, its position, its neighbours or q.  Only enqueues.
+        Ragged: ``force`` is packed like the coordinates :meth:`solve` takes, (sum(sizes), 3) or (q, sum(sizes), 3), and
+        ``atom_scale`` (sum(sizes),); returns [(n_i, 3), ...] or [(q, n_i, 3), ...], views into one packed buffer.
+        """
+        lay = self._layout
+        if self.dim != 3:
+            raise ValueError("linear_response needs an ANM solver (dim=3): the reference defines it for an ANM only")
+        self._need_vectors()
+        q, single = self._vectors_in(force, "force")
+        sp = None if atom_scale is None else self._device_f64(atom_scale, lay.atoms_shape(), "atom_scale")
+        sel, counts = self._selection(mode_subset, pinv_default=True)
+        buf = self._empty(lay.vectors_shape(q))
+        if q:
+            self._call("response", C.byref(sel), counts, C.c_void_p(force.data_ptr()), q, sp, C.c_void_p(buf.data_ptr()))
+        return lay.vectors_out(buf, single)
+
+    def _failed_structures(self):
+        """(batch,) bool tensor: ``w`` holds a NaN before the structure's row limit (its solve failed).  Enqueue only."""
+        torch, lay = self.torch, self._layout
+        nvec = self.w.shape[1]
+        lim = None
+        if lay.ragged:
+            if getattr(self, "_row_limits_dev", None) is None:
+                host = torch.tensor(lay.row_limits, dtype=torch.int64).pin_memory()
+                self._row_limits_dev = host.to(self.device, non_blocking=True)
+            lim = self._row_limits_dev
+        if self.window is not None:
+            c = self.counts.clamp(max=nvec)
+            lim = c if lim is None else torch.minimum(lim, c)
+        bad = torch.isnan(self.w)
+        if lim is not None:
+            bad = bad & (torch.arange(nvec, device=self.device)[None, :] < lim[:, None])
+        return bad.any(dim=1)
+
+    def mode_displacement(self, coefficients, atom_scale=None):
+        """
+        (batch, n_atoms, 3) displacements ``sum_r c_r v_r`` built from the rows of ``v`` with the caller's coefficients
+        (:func:`nma.mode_displacement`; no reference counterpart, ProDy: ``deformAtoms`` / ``traverseMode`` /
+        ``sampleModes``) -- for a GNM solver (batch, n_atoms).  ``coefficients`` is a contiguous CUDA float64 tensor
+        (batch, nvec) or (batch, q, nvec), the shape :meth:`overlap` returns, one coefficient per row of ``w`` / ``v``,
+        trivial rows included (give them 0); the result is (batch, [q,] n_atoms, 3).  ``|d| * overlap(d)`` over a
+        full spectrum gives ``d`` back.  Rows behind a window's count (and a ragged slot's pad rows) are never read,
+        whatever their coefficients hold.  ``atom_scale`` as in :meth:`linear_response`: the result is ``s_a`` times the
+        sum (with ``masses``, ``solver.inv_sqrt_mass`` turns mass-weighted modes into Cartesian displacements).
+        A structure whose solve failed (NaN eigenvalues before its row limit; its ``v`` is a finite basis without a
+        meaning) gives NaN.  One pass across the rows of ``v`` per four coefficient vectors; only enqueues.
+        Ragged: ``coefficients`` is (batch, nvec) or (batch, q, nvec) all the same -- of structure i the first rows_i
+        count, as :meth:`frequencies` cuts them -- and the result [(n_i, 3), ...] or [(q, n_i, 3), ...], views into one
+        packed buffer; ``atom_scale`` (sum(sizes),).
+        """
+        lay = self._layout
+        self._need_vectors()
+        torch, c = self.torch, coefficients
+        nvec = self.w.shape[1]
+        names = f"(batch, nvec) or (batch, q, nvec) with batch = {self.batch}, nvec = {nvec}"
+        if not isinstance(c, torch.Tensor) or not c.is_cuda or c.dtype != torch.float64 or not c.is_contiguous():
+            raise ValueError(f"coefficients must be a contiguous CUDA float64 tensor of shape {names}")
+        if c.device != torch.device(self.device):
+            raise ValueError(f"coefficients is on {c.device}, the solver on {self.device}")
+        shape = tuple(c.shape)
+        if shape == (self.batch, nvec):
+            q, single = 1, True
+        elif len(shape) == 3 and shape[0] == self.batch and shape[2] == nvec:
+            q, single = shape[1], False
+        else:
+            raise ValueError(f"Expected coefficients of shape {names}, got {shape}")
+        sp = None if atom_scale is None else self._device_f64(atom_scale, lay.atoms_shape(), "atom_scale")
+        buf = self._empty(lay.vectors_shape(q))
+        if q:
+            self._call("combine", C.c_void_p(c.data_ptr()), q,
+                       C.c_void_p(self.counts.data_ptr()) if self.window is not None else None, sp,
+                       C.c_void_p(buf.data_ptr()))
+            # the kernel does not read w: a failed structure is masked here, enqueued like the kernel (see _overlap_call)
+            bad = self._failed_structures()
+            if lay.ragged:
+                if getattr(self, "_sizes_dev", None) is None:
+                    host = torch.tensor(lay.sizes, dtype=torch.int64).pin_memory()
+                    self._sizes_dev = host.to(self.device, non_blocking=True)
+                per_atom = torch.repeat_interleave(bad, self._sizes_dev, output_size=lay.atom_off[-1])
+                buf.masked_fill_(per_atom.view((1, -1) + (1,) * (buf.ndim - 2)), float("nan"))
+            else:
+                buf.masked_fill_(bad.view((-1,) + (1,) * (buf.ndim - 1)), float("nan"))
+        return lay.vectors_out(buf, single)
+
     def dcc(self, mode_subset=None, norm=True, tem=None, tem_factors=K_B):
         """
         (batch, n_atoms, n_atoms) dynamic cross-correlations over the selected modes (nma.py:233-359); ``norm`` divides by
@@ -568,8 +699,8 @@ class DeviceBatchSolver(_BatchSolver):
     Structures of different sizes, patched or tabulated force fields: :class:`RaggedBatchSolver`.
 
     The consumers of the solved modes (:meth:`frequencies` ... :meth:`dcc`, documented on the shared base) return one CUDA
-    tensor each with a leading batch axis: (batch, n_atoms[, 3, 3]) per atom, (batch, n_atoms, n_atoms) per pair and
-    (batch, [q,] nvec) per row of ``v``.
+    tensor each with a leading batch axis: (batch, n_atoms[, 3, 3]) per atom, (batch, n_atoms, n_atoms) per pair,
+    (batch, [q,] nvec) per row of ``v`` and (batch, [q,] n_atoms, 3) per displacement field.
     """
 
     def __init__(self, n_atoms, batch, force_field, dim=3, device=None, want_vectors=True, masses=None,

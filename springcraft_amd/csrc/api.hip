@@ -945,7 +945,7 @@ struct Blob {
   }
 };
 
-// ---- mode consumers of a batch (batch_consumers.hip, dist_fluct.hip, mode_overlap.hip) ---------------------------------
+// ---- mode consumers of a batch (batch_consumers.hip, dist_fluct.hip, mode_overlap.hip, mode_response.hip) -------------
 // Whose modes a consumer works on: the (batch, nvec, m) results of a uniform batch (sc_dev_modes_*: m = dim * n_atoms) or
 // of a plan's padded slots (sc_batch_plan_modes_*).  Each consumer has ONE body, modes_* below, which runs every check and
 // calls the launcher; its two entries only build this description.
@@ -1057,6 +1057,29 @@ int modes_overlap(const ModesOf& who, const double* d_v, const double* d_disp, i
   SC_HIP(ctx, hipSetDevice(ctx->device));
   return modes_overlap_device(ctx, d_v, who.m, who.nvec, who.batch, who.dim, nullptr, who.nvec, d_disp, q, d_counts,
                               d_overlap, d_collectivity, who.ragged());
+}
+
+// (response: dim 1 is a GNM's, for which the reference defines no linear response; the Python layer refuses it, the
+// arithmetic here is the same for both)
+int modes_response(const ModesOf& who, const double* d_w, const double* d_v, const sc_mode_selection* sel,
+                   const int64_t* d_counts, const double* d_force, int64_t q, const double* d_atom_scale, double* d_out) {
+  SC_TRY(check_modes_args(who, d_w, d_v, sel, d_out));
+  if (q < 0 || q > INT32_MAX / 4 || (q > 0 && !d_force))
+    return sc_set_error(who.ctx, SC_ERR_INVALID_ARG, "q = %lld force vectors", (long long)q);
+  SC_HIP(who.ctx, hipSetDevice(who.ctx->device));
+  return modes_response_device(who.ctx, d_w, d_v, who.m, who.nvec, who.batch, who.dim, *sel, d_counts, d_force, q,
+                               d_atom_scale, 0, d_out, who.ragged());
+}
+
+int modes_combine(const ModesOf& who, const double* d_v, const double* d_coef, int64_t q, const int64_t* d_counts,
+                  const double* d_atom_scale, double* d_out) {
+  SC_TRY(check_modes_shape(who, d_v && d_out));
+  if (q < 0 || q > INT32_MAX / 4 || (q > 0 && !d_coef))
+    return sc_set_error(who.ctx, SC_ERR_INVALID_ARG, "q = %lld coefficient vectors", (long long)q);
+  SC_TRY(check_first_row(who));
+  SC_HIP(who.ctx, hipSetDevice(who.ctx->device));
+  return modes_combine_device(who.ctx, d_v, who.m, who.nvec, who.batch, who.dim, nullptr, who.nvec, d_coef, q, d_counts,
+                              d_atom_scale, 0, d_out, who.ragged());
 }
 
 int64_t modes_workspace_bytes(const ModesOf& who, int64_t n_sel, int what, int64_t budget_bytes) {
@@ -1407,6 +1430,29 @@ int sc_batch_plan_modes_overlap_f64(sc_batch_plan* plan, const double* d_v, int6
   return modes_overlap(plan_modes_of(plan, nvec, first_row), d_v, d_disp, q, d_counts, d_overlap, d_collectivity);
 }
 
+int sc_dev_mode_response_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                             int dim, const sc_mode_selection* sel, const int64_t* d_counts, const double* d_force,
+                             int64_t q, const double* d_atom_scale, double* d_out) {
+  return modes_response(ModesOf{ctx, m, nvec, batch, dim}, d_w, d_v, sel, d_counts, d_force, q, d_atom_scale, d_out);
+}
+int sc_batch_plan_mode_response_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
+                                    const sc_mode_selection* sel, const int64_t* d_counts, const double* d_force,
+                                    int64_t q, const double* d_atom_scale, double* d_out) {
+  return modes_response(plan_modes_of(plan, nvec, sel ? sel->reserved : 0), d_w, d_v, sel, d_counts, d_force, q,
+                        d_atom_scale, d_out);
+}
+
+int sc_dev_mode_combine_f64(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
+                            const double* d_coef, int64_t q, const int64_t* d_counts, const double* d_atom_scale,
+                            double* d_out) {
+  return modes_combine(ModesOf{ctx, m, nvec, batch, dim}, d_v, d_coef, q, d_counts, d_atom_scale, d_out);
+}
+int sc_batch_plan_mode_combine_f64(sc_batch_plan* plan, const double* d_v, int64_t nvec, int64_t first_row,
+                                   const double* d_coef, int64_t q, const int64_t* d_counts, const double* d_atom_scale,
+                                   double* d_out) {
+  return modes_combine(plan_modes_of(plan, nvec, first_row), d_v, d_coef, q, d_counts, d_atom_scale, d_out);
+}
+
 int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
                                      int64_t budget_bytes) {
   return modes_workspace_bytes(ModesOf{nullptr, m, nvec, batch, dim}, n_sel, what, budget_bytes);
@@ -1641,6 +1687,66 @@ int sc_modes_overlap(sc_modes* m, const int64_t* mode_idx, int64_t k, const doub
                               collectivity_out ? d_co : nullptr));
   if (q > 0) SC_HIP(ctx, hipMemcpyAsync(overlap_out, d_ov, Q * K * 8, hipMemcpyDeviceToHost, ctx->stream));
   if (collectivity_out) SC_HIP(ctx, hipMemcpyAsync(collectivity_out, d_co, K * 8, hipMemcpyDeviceToHost, ctx->stream));
+  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SC_OK;
+}
+
+int sc_modes_response(sc_modes* m, const int64_t* mode_idx, int64_t k, double rcond, const double* force, int64_t q,
+                      const double* atom_scale, double* out) {
+  if (!m) return SC_ERR_INVALID_ARG;
+  sc_ctx* ctx = m->ctx;
+  const bool pinv = mode_idx == nullptr;
+  if (k < 0 || k > INT32_MAX / 4 || (pinv && (k != 0 || !(rcond >= 0.0))) || q < 0 || q > INT32_MAX / 4 ||
+      (q > 0 && m->n > 0 && (!force || !out)))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t n = (size_t)m->n, K = (size_t)k, Q = (size_t)q, N = n / (size_t)m->dim;
+  SC_TRY(sc_reserve_scratch(ctx, align_up(K * 4, 256) + 2 * align_up(Q * n * 8, 256) + align_up(N * 8, 256) + 1024));
+  Bump bump{(char*)ctx->scratch};
+  int* d_sel = bump.take<int>(std::max<size_t>(K, 1));
+  double* d_force = bump.take<double>(std::max<size_t>(Q * n, 1));
+  double* d_out = bump.take<double>(std::max<size_t>(Q * n, 1));
+  double* d_scale = bump.take<double>(std::max<size_t>(N, 1));
+  SC_TRY(stage_mode_list(m, mode_idx, k, d_sel));   // (the index errors come first, whatever else is empty)
+  if (m->n == 0 || q == 0) return SC_OK;
+  SC_HIP(ctx, hipMemcpyAsync(d_force, force, Q * n * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (atom_scale) SC_HIP(ctx, hipMemcpyAsync(d_scale, atom_scale, N * 8, hipMemcpyHostToDevice, ctx->stream));
+  sc_mode_selection sel{};
+  if (pinv) {
+    sel.kind = SC_SEL_PINV;
+    sel.rcond = rcond;
+  } else {
+    sel.kind = SC_SEL_ROWS;
+    sel.d_rows = d_sel;
+    sel.n_rows = k;
+  }
+  // the batch kernels with a batch of one: one arithmetic order for a model, a batch and a ragged batch
+  SC_TRY(modes_response_device(ctx, m->d_w, m->d_v, m->n, m->n, 1, m->dim, sel, nullptr, d_force, q,
+                               atom_scale ? d_scale : nullptr, 0, d_out));
+  SC_HIP(ctx, hipMemcpyAsync(out, d_out, Q * n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SC_OK;
+}
+
+int sc_modes_combine(sc_modes* m, const int64_t* mode_idx, int64_t k, const double* coef, int64_t q, double* out) {
+  if (!m) return SC_ERR_INVALID_ARG;
+  sc_ctx* ctx = m->ctx;
+  if (k < 0 || k > INT32_MAX / 4 || (k > 0 && !mode_idx) || q < 0 || q > INT32_MAX / 4 ||
+      (q > 0 && ((k > 0 && !coef) || (m->n > 0 && !out))))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t n = (size_t)m->n, K = (size_t)k, Q = (size_t)q;
+  SC_TRY(sc_reserve_scratch(ctx, align_up(K * 4, 256) + align_up(Q * K * 8, 256) + align_up(Q * n * 8, 256) + 1024));
+  Bump bump{(char*)ctx->scratch};
+  int* d_sel = bump.take<int>(std::max<size_t>(K, 1));
+  double* d_coef = bump.take<double>(std::max<size_t>(Q * K, 1));
+  double* d_out = bump.take<double>(std::max<size_t>(Q * n, 1));
+  SC_TRY(stage_mode_list(m, mode_idx, k, d_sel));   // (the index errors come first, whatever else is empty)
+  if (m->n == 0 || q == 0) return SC_OK;
+  if (k > 0) SC_HIP(ctx, hipMemcpyAsync(d_coef, coef, Q * K * 8, hipMemcpyHostToDevice, ctx->stream));
+  // the batch kernels with a batch of one: one arithmetic order for a model, a batch and a ragged batch
+  SC_TRY(modes_combine_device(ctx, m->d_v, m->n, m->n, 1, m->dim, d_sel, k, d_coef, q, nullptr, nullptr, 0, d_out));
+  SC_HIP(ctx, hipMemcpyAsync(out, d_out, Q * n * 8, hipMemcpyDeviceToHost, ctx->stream));
   SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SC_OK;
 }

@@ -172,10 +172,6 @@ __global__ __launch_bounds__(256) void k_bmsf_reduce(const double* __restrict__ 
   out[(rag ? (size_t)rag[b].atom_off : (size_t)b * N) + a] = acc;
 }
 
-// listed rows per chunk: from the number of listed rows alone.  20 rows -> 5 chunks of 4 (64 structures of m = 6000:
-// 3840 workgroups), 6000 rows -> 48 chunks of 125 (36864 workgroups, partial sums 1.6 % of the bytes read).
-int msf_chunk(int64_t nsel) { return (int)std::min<int64_t>(128, std::max<int64_t>(4, (nsel + 47) / 48)); }
-
 // ---- anisotropic fluctuation tensors (ANM, dim 3) ----------------------------------------------------------------
 // The 3 x 3 diagonal blocks of the covariance over the selected modes, what crystallography records as ANISOU: six
 // values per atom in that record's order, e = xx yy zz xy xz yz; xx + yy + zz is the msf of the same selection.
@@ -333,6 +329,15 @@ __global__ __launch_bounds__(256) void k_bdcc_norm(double* __restrict__ c, const
   cb[(size_t)r * N + a] = cb[(size_t)r * N + a] / (sqrt(db[a]) * sqrt(db[r]));
 }
 
+}  // namespace
+
+// listed rows per chunk: from the number of listed rows alone.  20 rows -> 5 chunks of 4 (64 structures of m = 6000:
+// 3840 workgroups), 6000 rows -> 48 chunks of 125 (36864 workgroups, partial sums 1.6 % of the bytes read).
+// (declared in eigh_internal.h: mode_response.hip cuts its rows the same way)
+int msf_chunk(int64_t nsel) { return (int)std::min<int64_t>(128, std::max<int64_t>(4, (nsel + 47) / 48)); }
+
+namespace {
+
 struct DccPlan {
   int64_t kc;      // listed rows per GEMM
   int64_t slab;    // structures per GEMM launch
@@ -402,7 +407,7 @@ int64_t batch_modes_nsel(const sc_mode_selection& sel, int64_t nvec) {
 }
 
 // weights (batch, n_sel) | msf, tensors: partial sums of one slab | dcc: P and S of one slab, diagonals (batch, N), records |
-// distance fluctuations: nothing more
+// distance fluctuations: nothing more | response, combine (mode_response.hip): coefficients and partial sums, partial sums
 // (ragged: m is the slot order, the diagonals are packed over all atoms)
 size_t batch_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t nsel, int what,
                                    size_t budget, const RaggedView* rv) {
@@ -417,6 +422,10 @@ size_t batch_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int d
     bytes += align_up((size_t)aniso_slab(m, nsel, batch, budget) * ((nsel + chunk - 1) / chunk) * 6 * (m / 3) * 8, 256);
   } else if (what == 4) {
     // distance fluctuations (dist_fluct.hip): the weights alone, a pair's sum never leaves its lane
+  } else if (what == 5) {
+    bytes += modes_response_workspace_bytes(m, batch, nsel, 5, budget);
+  } else if (what == 6) {
+    bytes = modes_response_workspace_bytes(m, batch, nsel, 6, budget);   // (no weights: the caller's coefficients)
   } else {
     const DccPlan pl = dcc_plan(m, nsel, batch, budget);
     const size_t diag = (size_t)(rv ? rv->total_atoms : batch * (m / dim));

@@ -296,7 +296,7 @@ int modes_prs_device(sc_ctx* ctx, const double* d_v, const double* d_w, int64_t 
                      char* scratch, double* d_out);
 
 // ---- the same quantities for a batch, on the solver's own (w, v, counts) tensors (batch_consumers.hip) ----------
-// what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3), 4 = distance fluctuations (dim 3; dist_fluct.hip).  n_sel: weighted rows per structure (batch_modes_nsel).  budget: bytes the partial sums (msf) /
+// what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3), 4 = distance fluctuations (dim 3; dist_fluct.hip), 5 = response, 6 = combine (mode_response.hip).  n_sel: weighted rows per structure (batch_modes_nsel).  budget: bytes the partial sums (msf) /
 // the packed GEMM operands (dcc) may take, 0 = modes_budget_default().  ragged: null for a uniform batch (d_out (batch,
 // m / dim[, m / dim])), or the plan's records: m is then the slot order and d_out is packed.
 // Ragged batches (sc_batch_plan): one record per structure in the plan's device blob, read by the window count and the
@@ -344,6 +344,23 @@ int batch_distfluct_device(sc_ctx* ctx, const double* d_w, const double* d_v, in
 int modes_overlap_device(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
                          const int* d_rows, int64_t nout, const double* d_disp, int64_t q, const int64_t* d_counts,
                          double* d_overlap, double* d_coll, const RaggedView* ragged = nullptr);
+
+// ---- linear response and linear combinations of modes (mode_response.hip) ------------------------------------------
+// Response: d_out[b, j] = S V_sel^T diag(wt) V_sel S f_j over the rows `sel` selects (wt = 1 / lambda from k_mode_weights,
+// S = diag(d_atom_scale) per atom, null: 1), in mode space: one pass along the listed rows for the coefficients, one
+// across them for the sum, per group of four forces; no covariance.  d_force and d_out (batch, q, m); ragged: (q, dim *
+// sum n_atoms) packed, structure b's vector j at j * dim * sum n + dim * atom_off_b.  A row with weight 0.0 is not read.
+// Combine: d_out[b, j] = S sum_kk d_coef[b, j, kk] v[b, row(kk)] over the nsel listed rows, row(kk) = d_rows[kk] (a
+// validated device list: one model's mode subset) or kk (d_rows null, nsel = nvec): of those only the rows below
+// min(counts[b], nvec) / a slot's own rows are read, and only their coefficients.  d_coef (batch, q, nsel).
+// budget: bytes the partial sums may take at a time, 0 = modes_budget_default().  Enqueue only.
+size_t modes_response_workspace_bytes(int64_t m, int64_t batch, int64_t nsel, int what, size_t budget);
+int modes_response_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                          int dim, const sc_mode_selection& sel, const int64_t* d_counts, const double* d_force, int64_t q,
+                          const double* d_atom_scale, size_t budget, double* d_out, const RaggedView* ragged = nullptr);
+int modes_combine_device(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
+                         const int* d_rows, int64_t nsel, const double* d_coef, int64_t q, const int64_t* d_counts,
+                         const double* d_atom_scale, size_t budget, double* d_out, const RaggedView* ragged = nullptr);
 
 // Raises a kernel's dynamic LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) once per (device, kernel).  The
 // attribute belongs to the device that is current when it is set: a function-local static done-flag (rounds 2-5) served

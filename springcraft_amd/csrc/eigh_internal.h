@@ -166,9 +166,13 @@ int window_count_batched(sc_ctx* ctx, int batch, const double* d_tri_ws, const T
 int window_compact_batched(sc_ctx* ctx, int n, int batch, int K, const WinCount* d_win, double* d_w, double* d_v,
                            double* d_w_copy, double* d_v_copy);
 
-// ---- mode consumers (batch_consumers.hip, dist_fluct.hip) ----------------------------------------------------------
+// ---- mode consumers (batch_consumers.hip, dist_fluct.hip, mode_response.hip) ----------------------------------------------------------
 // d_s (batch, nsel) <- the weight of every (structure, listed row): 1 / lambda for a selected row, exactly 0.0 for one
 // that is not (behind a window's count, a ragged slot's pad rows, under the pinv threshold), NaN for a listed row outside
 // 0..nvec-1.  nsel = batch_modes_nsel(sel, nvec) > 0.  One launch of k_mode_weights; every consumer reads its rows through it.
 int launch_mode_weights(sc_ctx* ctx, const double* d_w, int64_t nvec, int64_t batch, const sc_mode_selection& sel,
                         int64_t nsel, const int64_t* d_counts, double* d_s, const RaggedView* rv);
+// Listed rows per chunk of the consumers that sum across rows and add their chunks in a fixed order (msf, tensors,
+// mode_response.hip's combine): a function of the number of listed rows alone, so that a structure's bits are the same
+// in any batch.
+int msf_chunk(int64_t nsel);

@@ -80,6 +80,10 @@ class GNM(ElasticNetworkModel):
         """Fluctuations of the inter-atom distances, (n, n) (:func:`nma.distance_fluctuation`; no reference counterpart)."""
         return nma.distance_fluctuation(self, mode_subset, projected, tem, tem_factors)
 
+    def mode_displacement(self, coefficients, mode_subset=None):
+        """Displacement field(s) (n,) / (q,n) ``sum_k c_k v_k`` over the selected modes (:func:`nma.mode_displacement`)."""
+        return nma.mode_displacement(self, coefficients, mode_subset)
+
     def collectivity(self, mode_subset=None):
         """Collectivity of the selected modes, (k,) (:func:`nma.collectivity`)."""
         return nma.collectivity(self, mode_subset)

@@ -13,8 +13,10 @@ tensors on the host.
 moves) are one pass along the selected rows (``csrc/mode_overlap.hip``); ``cumulative_overlap`` is array arithmetic.
 ``distance_fluctuation`` (no reference counterpart: how much every inter-atom distance fluctuates) is the pair kernel of
 ``csrc/dist_fluct.hip`` with a batch of one; ``effective_stiffness`` is array arithmetic on its result.
-``normal_mode``, ``linear_response`` and ``effector_sensor`` are O(n) / O(n^2) host arithmetic on
-results that are already on the host.
+``linear_response`` (reference: nma.py:422-473) and ``mode_displacement`` (no reference counterpart: a displacement field
+built from chosen modes) are the two passes of ``csrc/mode_response.hip`` over the selected rows, in mode space: no
+covariance is formed and only (q, 3N) numbers cross PCIe; ``sample_displacements`` draws the coefficients on the host.
+``normal_mode`` and ``effector_sensor`` are O(n) / O(n^2) host arithmetic on results that are already on the host.
 """
 
 
@@ -26,6 +28,7 @@ __all__ = [
     "eigen", "eigh", "pinvh", "frequencies", "mean_square_fluctuation", "bfactor", "dcc",
     "normal_mode", "linear_response", "prs", "effector_sensor", "anisotropic_fluctuation", "anisotropy",
     "overlap", "collectivity", "cumulative_overlap", "distance_fluctuation", "effective_stiffness",
+    "mode_displacement", "sample_displacements",
 ]
 
 K_B = 1.380649e-23
@@ -376,15 +379,32 @@ def normal_mode(anm, index, amplitude, frames, movement="sine"):
     return scale[:, None, None] * mode[None, :, :]
 
 
-def linear_response(anm, force):
-    """Linear-response displacement covariance . force, reshaped to (n,3) (nma.py:422-473)."""
+def linear_response(anm, force, mode_subset=None):
+    """
+    Linear-response displacement covariance . force (nma.py:422-473).  ``force`` is (N, 3) or (3N,) and the result
+    (N, 3); q forces at once as (q, N, 3) give (q, N, 3) (extension).
+
+    ``mode_subset=None`` is the reference: the covariance is ``pinv(hessian, rcond=1e-6)`` (anm.py:114-117), every mode
+    with ``|lambda| > 1e-6 max|lambda|``.  It is applied in mode space, ``sum_k v_k <v_k, f> / lambda_k`` on the
+    device-resident eigenpairs (``csrc/mode_response.hip``): the (3N, 3N) matrix is neither formed nor copied.  A
+    covariance that is already on the model -- assigned by the caller or fetched earlier -- is used as it is, like
+    :func:`prs` does.  ``mode_subset`` (extension) restricts the sum to the listed modes, as in
+    :func:`mean_square_fluctuation`: the response carried by those modes alone; trivial indices raise ValueError.
+    For a model with masses the modes enter as they are (the reference's ``covariance @ force`` of the mass-weighted
+    Hessian); the Cartesian response is what a batch solver returns for ``atom_scale=solver.inv_sqrt_mass``.
+    """
     from .anm import ANM
 
     if not isinstance(anm, ANM):
         raise ValueError("Instance of ANM class expected.")
     force = np.asarray(force)
-    n3 = anm.covariance.shape[0]
-    if force.ndim == 2:
+    n3 = 3 * len(anm._coord)
+    single = force.ndim != 3
+    if force.ndim == 3:
+        if force.shape[1:] != (n3 // 3, 3):
+            raise ValueError(f"Expected forces with shape {('q', n3 // 3, 3)}, got {force.shape}")
+        force = force.reshape(force.shape[0], n3)
+    elif force.ndim == 2:
         if force.shape != (n3 // 3, 3):
             raise ValueError(f"Expected force with shape {(n3 // 3, 3)}, got {force.shape}")
         force = force.ravel()
@@ -393,7 +413,70 @@ def linear_response(anm, force):
             raise ValueError(f"Expected force with length {n3}, got {len(force)}")
     else:
         raise ValueError(f"Expected 1D or 2D array, got {force.ndim} dimensions")
-    return (anm.covariance @ force).reshape(-1, 3)
+    if mode_subset is not None:
+        mode_subset = _mode_selection(anm, mode_subset, None)   # (the trivial-mode error needs no device)
+    if mode_subset is None and anm._covariance is not None:
+        # a covariance the caller assigned (or already fetched): apply that very matrix
+        out = force @ anm._covariance.T if force.ndim == 2 else anm._covariance @ force
+    else:
+        f = np.ascontiguousarray(force.reshape(-1, n3), dtype=np.float64)
+        out = anm._modes_device().response(mode_subset, f, rcond=1e-6) if len(f) else np.empty((0, n3))
+    return out.reshape(n3 // 3, 3) if single else out.reshape(len(out), n3 // 3, 3)
+
+
+def _subset_indices(enm, mode_subset):
+    """The selected mode indices as an int64 array (None: every non-trivial mode); host arithmetic only."""
+    _, ntriv = _model_kind(enm)
+    if mode_subset is None:
+        return np.arange(ntriv, len(enm._coord) * enm._dim)
+    return np.asarray(_mode_selection(enm, mode_subset, None)).astype(np.int64).reshape(-1)
+
+
+def mode_displacement(enm, coefficients, mode_subset=None):
+    """
+    Displacement field ``sum_k c_k v_k`` over the k selected modes: a structure moved along chosen modes, a sample of
+    the ensemble (:func:`sample_displacements`), or a displacement put together again from its projections -- with
+    ``|d| * overlap(d)`` as coefficients over all modes it is the inverse of :func:`overlap`.  ``coefficients`` is (k,)
+    or (q, k), one per mode of ``mode_subset`` in its order (None: every non-trivial mode; trivial indices raise
+    ValueError, as in :func:`mean_square_fluctuation`); a wrong length raises ValueError.  Returns (N, 3) or (q, N, 3)
+    for an ANM and (N,) or (q, N) for a GNM, in the coordinates of the modes: for a model with masses the modes are
+    mass-weighted and ``d / sqrt(mass)[:, None]`` is the Cartesian displacement.  No reference counterpart (ProDy:
+    ``deformAtoms``, ``traverseMode``, ``sampleModes``); one pass across the selected device-resident eigenvectors
+    (``csrc/mode_response.hip``), only (q, k) numbers go to the device and (q, dim N) come back.
+    """
+    kind, _ = _model_kind(enm)
+    idx = _subset_indices(enm, mode_subset)
+    c = np.asarray(coefficients, dtype=np.float64)
+    if c.ndim not in (1, 2) or c.shape[-1] != len(idx):
+        raise ValueError(f"Expected coefficients of shape ({len(idx)},) or (q, {len(idx)}), one per selected mode, "
+                         f"got {c.shape}")
+    single = c.ndim == 1
+    c = np.ascontiguousarray(c[None] if single else c)
+    n = len(enm._coord)
+    out = enm._modes_device().combine(idx, c) if len(c) else np.empty((0, n * enm._dim))
+    out = out.reshape((len(c), n, 3) if kind == "anm" else (len(c), n))
+    return out[0] if single else out
+
+
+def sample_displacements(enm, n_samples, mode_subset=None, tem=None, tem_factors=K_B, rng=None):
+    """
+    ``n_samples`` displacement fields drawn from the harmonic ensemble of the selected modes: :func:`mode_displacement`
+    of the coefficients ``xi_k sqrt(kT / lambda_k)`` with ``xi`` standard normal, ``kT = tem * tem_factors`` (1 when
+    ``tem`` is None).  Their covariance is kT times the covariance matrix restricted to those modes, so the mean square
+    displacement per atom tends to :func:`mean_square_fluctuation`.  ``rng``: a seed or ``numpy.random.Generator``
+    (``numpy.random.default_rng(rng)``); the numbers are drawn on the host.  ``mode_subset`` as in
+    :func:`mode_displacement`.  Returns (n_samples, N, 3) for an ANM, (n_samples, N) for a GNM.
+    No reference counterpart (ProDy: ``sampleModes``).
+    """
+    _model_kind(enm)
+    idx = _subset_indices(enm, mode_subset)
+    n_samples = int(n_samples)
+    if n_samples < 0:
+        raise ValueError(f"n_samples must not be negative, got {n_samples}")
+    kt = 1.0 if tem is None else tem * tem_factors
+    lam = enm._modes_device().values()[idx]
+    xi = np.random.default_rng(rng).standard_normal((n_samples, len(idx)))
+    return mode_displacement(enm, xi * np.sqrt(kt / lam), idx)
 
 
 def prs(anm, norm=True):
