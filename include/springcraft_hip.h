@@ -599,6 +599,38 @@ int sc_batch_plan_mode_combine_f64(sc_batch_plan* plan, const double* d_v, int64
 int64_t sc_batch_plan_modes_workspace_bytes(const sc_batch_plan* plan, int64_t nvec, int64_t n_sel, int what,
                                             int64_t budget_bytes);
 
+/* ---- rotation-translation blocks (RTB): the lowest modes of a network without its (3N, 3N) Hessian -------------------
+ * No reference counterpart (Durand / Tama / Sanejouand; ProDy: RTB, Bio3D: rtb).  Atoms are grouped into rigid blocks;
+ * block b has dof_b <= 6 orthonormal rigid-body fields, the columns offset[b] .. offset[b + 1] - 1 of the (3N, nr)
+ * projector, nr = offset[n_blocks].  The projector is passed as d_P (N, 3, 6) row-major -- atom a's three rows of its
+ * block's columns, unused columns 0.0 -- with d_block_of_atom (N) int32 and d_offset (n_blocks + 1) int64.  Device
+ * pointers, enqueue only.
+ *
+ * sc_dev_rtb_hessian_f64: d_hb (nr, nr) row-major = P^T H P for the H that sc_hessian_from_pairs_f64 builds from the
+ * ordered directed pair list d_pairs (k, 2) and d_gamma (k), times outer(s, s) with s = d_inv_sqrt_mass (N) repeated per
+ * coordinate (NULL: 1): with d = r_j - r_i, g = gamma_p / |d|^2 and t_a = s_a P[a]^T d, pair p = (i, j) adds -g t_i t_j^T
+ * to the block (block(i), block(j)) and +g t_j t_j^T to the diagonal block of block(j) -- off-diagonal from gamma(i, j),
+ * diagonal summed over the first index, as that entry does for asymmetric constants.  The caller supplies the order of
+ * the sums: d_order (k) lists the pairs sorted by (block(j), block(i)), stable; d_seg_start (n_seg + 1) the starts of
+ * the n_seg runs of equal (block(j), block(i)) in that order, d_seg_start[n_seg] = k; d_block_start (n_blocks + 1) where
+ * the pairs with block(j) = b start, d_block_start[n_blocks] = k (a block no pair ends in has an empty range).  One
+ * wavefront sums a run in a fixed order and stores its 6 x 6 block once: no atomics, the bits of d_hb depend on the inputs
+ * alone.  Every entry of d_hb is written, zero where no contact; blocks need not be contiguous in atom order nor fit a
+ * workgroup, atoms need not have contacts.  k = 0 gives the zero matrix (the pair arrays may then be NULL).  No buffer
+ * beyond the arguments.  SC_ERR_INVALID_ARG: a non-positive n_atoms / n_blocks / nr, a negative k, a NULL required
+ * pointer, n_blocks > n_atoms, nr > 6 n_blocks or n_seg > k.  Entries of the index arrays outside their ranges are
+ * skipped, not reported. */
+int sc_dev_rtb_hessian_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, const int64_t* d_pairs, int64_t k,
+                           const double* d_gamma, const double* d_inv_sqrt_mass, const double* d_P,
+                           const int32_t* d_block_of_atom, const int64_t* d_offset, int64_t n_blocks, int64_t nr,
+                           const int64_t* d_order, const int64_t* d_seg_start, int64_t n_seg,
+                           const int64_t* d_block_start, double* d_hb);
+/* d_v (nvec, 3 n_atoms) = d_u (nvec, nr) P^T: V[r, 3 a + al] = sum_c P[a, al, c] U[r, offset[block(a)] + c], one
+ * streaming pass, every entry written, no mass factor (the modes stay in the coordinates of the Hessian).  nvec at most
+ * 524280.  SC_ERR_INVALID_ARG for non-positive sizes or a NULL pointer. */
+int sc_dev_rtb_expand_f64(sc_ctx* ctx, const double* d_u, int64_t nvec, int64_t nr, const double* d_P,
+                          const int32_t* d_block_of_atom, const int64_t* d_offset, int64_t n_atoms, double* d_v);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = [
     "sc_modes_distfluct", "sc_dev_modes_distfluct_f64", "sc_batch_plan_modes_distfluct_f64",
     "sc_modes_response", "sc_dev_mode_response_f64", "sc_batch_plan_mode_response_f64",
     "sc_modes_combine", "sc_dev_mode_combine_f64", "sc_batch_plan_mode_combine_f64",
+    "sc_dev_rtb_hessian_f64", "sc_dev_rtb_expand_f64",
 ]
 
 SC_SEL_FROM_ROW = 0
@@ -244,6 +245,8 @@ def lib():
         "sc_modes_combine": (i32, [vp, vp, i64, vp, i64, vp]),
         "sc_dev_mode_combine_f64": (i32, [vp, vp, i64, i64, i64, i32, vp, i64, vp, vp, vp]),
         "sc_batch_plan_mode_combine_f64": (i32, [vp, vp, i64, i64, vp, i64, vp, vp, vp]),
+        "sc_dev_rtb_hessian_f64": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp]),
+        "sc_dev_rtb_expand_f64": (i32, [vp, vp, i64, i64, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -1462,6 +1462,38 @@ int64_t sc_batch_plan_modes_workspace_bytes(const sc_batch_plan* plan, int64_t n
   return modes_workspace_bytes(plan_modes_of(plan, nvec, 0), n_sel, what, budget_bytes);
 }
 
+// ---- rotation-translation blocks (rtb.hip) --------------------------------------------------------------------------
+int sc_dev_rtb_hessian_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, const int64_t* d_pairs, int64_t k,
+                           const double* d_gamma, const double* d_inv_sqrt_mass, const double* d_P,
+                           const int32_t* d_block_of_atom, const int64_t* d_offset, int64_t n_blocks, int64_t nr,
+                           const int64_t* d_order, const int64_t* d_seg_start, int64_t n_seg,
+                           const int64_t* d_block_start, double* d_hb) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  if (n_atoms <= 0 || n_blocks <= 0 || nr <= 0 || k < 0 || n_seg < 0)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "rtb: sizes must be positive (k, n_seg: not negative)");
+  if (n_blocks > n_atoms || nr > 6 * n_blocks || n_seg > k)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "rtb: %lld blocks / %lld rows / %lld segments do not fit %lld atoms, %lld pairs",
+                        (long long)n_blocks, (long long)nr, (long long)n_seg, (long long)n_atoms, (long long)k);
+  if (!d_coord || !d_P || !d_block_of_atom || !d_offset || !d_hb)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "rtb: a required pointer is NULL");
+  if (k > 0 && (!d_pairs || !d_gamma || !d_order || !d_seg_start || !d_block_start || n_seg == 0))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "rtb: pairs / gamma / order / segment starts are required with k > 0");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return launch_rtb_hessian(ctx, d_coord, n_atoms, d_pairs, k, d_gamma, d_inv_sqrt_mass, d_P, d_block_of_atom, d_offset,
+                            n_blocks, nr, d_order, d_seg_start, n_seg, d_block_start, d_hb);
+}
+
+int sc_dev_rtb_expand_f64(sc_ctx* ctx, const double* d_u, int64_t nvec, int64_t nr, const double* d_P,
+                          const int32_t* d_block_of_atom, const int64_t* d_offset, int64_t n_atoms, double* d_v) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  if (nvec <= 0 || nr <= 0 || n_atoms <= 0 || nvec > 8 * (int64_t)65535)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "rtb: sizes must be positive (nvec at most 524280)");
+  if (!d_u || !d_P || !d_block_of_atom || !d_offset || !d_v)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "rtb: a required pointer is NULL");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return launch_rtb_expand(ctx, d_u, nvec, nr, d_P, d_block_of_atom, d_offset, n_atoms, d_v);
+}
+
 void sc_batch_plan_destroy(sc_batch_plan* plan) {
   if (!plan) return;
   (void)hipSetDevice(plan->ctx->device);

@@ -362,6 +362,19 @@ int modes_combine_device(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec
                          const int* d_rows, int64_t nsel, const double* d_coef, int64_t q, const int64_t* d_counts,
                          const double* d_atom_scale, size_t budget, double* d_out, const RaggedView* ragged = nullptr);
 
+// ---- rotation-translation blocks (rtb.hip) ---------------------------------------------------------------------------
+// d_hb (nr, nr) = P^T H P from the ordered pair list, H as launch_hessian_from_pairs fills it times outer(s, s); d_order
+// (k): the pairs sorted by (block of the second atom, block of the first), stable; d_seg_start (n_seg + 1): the segments of
+// equal block pairs in that order; d_blk_start (n_blocks + 1): per block of the second atom, where its pairs start.  Every
+// entry of d_hb is written.  No atomics, no workspace; enqueue only.
+int launch_rtb_hessian(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, const int64_t* d_pairs, int64_t k,
+                       const double* d_gamma, const double* d_ism, const double* d_P, const int32_t* d_boa,
+                       const int64_t* d_offset, int64_t n_blocks, int64_t nr, const int64_t* d_order,
+                       const int64_t* d_seg_start, int64_t n_seg, const int64_t* d_blk_start, double* d_hb);
+// d_v (nvec, 3 n_atoms) = d_u (nvec, nr) P^T; every entry is written.  Enqueue only.
+int launch_rtb_expand(sc_ctx* ctx, const double* d_u, int64_t nvec, int64_t nr, const double* d_P, const int32_t* d_boa,
+                      const int64_t* d_offset, int64_t n_atoms, double* d_v);
+
 // Raises a kernel's dynamic LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) once per (device, kernel).  The
 // attribute belongs to the device that is current when it is set: a function-local static done-flag (rounds 2-5) served
 // the first device a process used and left contexts on a second GPU with refused launches.  Returns

@@ -1,0 +1,288 @@
+"""
+Rotation-translation blocks (RTB; Durand, Trinquier & Sanejouand 1994, Tama et al. 2000; ProDy's ``RTB``, Bio3D's ``rtb``):
+the lowest normal modes of a network too large for its dense Hessian.  Atoms are grouped into rigid blocks, the Hessian is
+projected onto the <= 6 rigid-body motions of every block, ``H_b = P^T H P``, the small matrix is solved and its modes are
+expanded back, ``v = P u``.  The reference has no counterpart.
+
+:func:`rtb_projector` builds ``P`` on the host (NumPy only); :class:`RTB` projects on the device straight from the pair
+list (``csrc/rtb.hip``: the (3N, 3N) Hessian is never formed), solves with the device eigensolver and hands the expanded
+modes to the mode consumers it shares with the batch solvers.
+"""
+
+import ctypes as C
+
+import numpy as np
+
+from . import _hip, atoms as _atoms
+from .batch import _BatchSolver, _UniformLayout
+
+__all__ = ["RTB", "rtb_projector", "blocks_of_consecutive"]
+
+
+def blocks_of_consecutive(n_atoms, size):
+    """Block labels ``arange(n_atoms) // size``: runs of ``size`` consecutive atoms (the last one may be shorter)."""
+    n_atoms, size = int(n_atoms), int(size)
+    if n_atoms < 0:
+        raise ValueError(f"n_atoms must not be negative, got {n_atoms}")
+    if size < 1:
+        raise ValueError(f"the block size must be at least 1, got {size}")
+    return np.arange(n_atoms) // size
+
+
+def rtb_projector(coord, blocks, masses=None):
+    """
+    The block projector of the rotation-translation-block method.
+
+    Parameters
+    ----------
+    coord : ndarray, shape=(n,3), dtype=float
+    blocks : ndarray, shape=(n,)
+        Block labels, any integers or strings; atoms with equal labels form a block, contiguous in atom order or not.
+        Blocks are numbered in the order of their first appearance.
+    masses : ndarray, shape=(n,), dtype=float, optional
+        Atomic masses (1 when None).  ``P`` is then orthonormal in mass-weighted coordinates, the space of
+        ``ANM(masses=...).hessian``.
+
+    Returns
+    -------
+    P : ndarray, shape=(n,3,6), dtype=float
+        Atom a's three rows of its block's columns: ``P[a, :, c]`` is the atom's part of the block's c-th rigid-body field.
+        Per block with atoms A, masses m_a, total mass M and centre of mass c the raw fields are three translations
+        ``sqrt(m_a / M) e_x`` and three rotations ``sqrt(m_a) e_x x (r_a - c)``; the rotations, orthogonal to the
+        translations about the centre of mass, are orthonormalised by the SVD of their (3 |A|, 3) matrix.  Unused
+        columns are exactly 0.0.
+    block_of_atom : ndarray, shape=(n,), dtype=int32
+    dof : ndarray, shape=(nb,), dtype=int64
+        Columns per block: 3 for a one-atom block (decided by the atom count, not by a threshold), else 3 plus the number
+        of rotational singular values above ``1e-8 * sqrt(M) * max_a |r_a - c|``: 5 for collinear atoms, 6 otherwise.
+    offset : ndarray, shape=(nb+1,), dtype=int64
+        Exclusive scan of ``dof``: block b owns the rows ``offset[b] .. offset[b + 1] - 1`` of the projected matrix,
+        whose order is ``offset[-1]``.
+    """
+    coord = np.asarray(coord, dtype=np.float64)
+    if coord.ndim != 2 or coord.shape[1] != 3:
+        raise ValueError(f"Expected coordinates with shape (n,3), got {coord.shape}")
+    n = len(coord)
+    if not np.all(np.isfinite(coord)):
+        raise ValueError("coordinates must be finite")
+    labels = np.asarray(blocks)
+    if labels.ndim != 1 or len(labels) != n:
+        raise IndexError(f"{labels.shape} block labels for {n} atoms given")
+    if masses is None:
+        m = np.ones(n)
+    else:
+        m = np.asarray(masses, dtype=np.float64)
+        if m.shape != (n,):
+            raise IndexError(f"{m.shape} masses for {n} atoms given")
+        if not np.all(m > 0) or not np.all(np.isfinite(m)):
+            raise ValueError("Masses must be positive and finite")
+
+    _, first, inverse = np.unique(labels, return_index=True, return_inverse=True)
+    rank = np.empty(len(first), dtype=np.int64)
+    rank[np.argsort(first, kind="stable")] = np.arange(len(first))
+    block_of_atom = rank[inverse.reshape(-1)]
+    nb = len(first)
+
+    P = np.zeros((n, 3, 6))
+    dof = np.full(nb, 3, dtype=np.int64)
+    members = np.argsort(block_of_atom, kind="stable")
+    bounds = np.concatenate([[0], np.cumsum(np.bincount(block_of_atom, minlength=nb))])
+    for b in range(nb):
+        idx = members[bounds[b]: bounds[b + 1]]
+        mb = m[idx]
+        total = mb.sum()
+        P[idx[:, None], [0, 1, 2], [0, 1, 2]] = np.sqrt(mb / total)[:, None]
+        if len(idx) == 1:
+            continue
+        x = coord[idx] - (mb[:, None] * coord[idx]).sum(axis=0) / total
+        # rot[a, :, k] = sqrt(m_a) e_k x x_a
+        rot = np.zeros((len(idx), 3, 3))
+        rot[:, 1, 0], rot[:, 2, 0] = -x[:, 2], x[:, 1]
+        rot[:, 0, 1], rot[:, 2, 1] = x[:, 2], -x[:, 0]
+        rot[:, 0, 2], rot[:, 1, 2] = -x[:, 1], x[:, 0]
+        rot *= np.sqrt(mb)[:, None, None]
+        u, s, _ = np.linalg.svd(rot.reshape(-1, 3), full_matrices=False)
+        r = int(np.count_nonzero(s > 1e-8 * np.sqrt(total) * np.sqrt((x * x).sum(axis=1)).max()))
+        P[idx, :, 3: 3 + r] = u[:, :r].reshape(len(idx), 3, r)
+        dof[b] = 3 + r
+    offset = np.concatenate([[0], np.cumsum(dof)]).astype(np.int64)
+    return P, block_of_atom.astype(np.int32), dof, offset
+
+
+class RTB(_BatchSolver):
+    """
+    Rotation-translation-block normal modes of one structure on the device.
+
+    Parameters
+    ----------
+    atoms : AtomArray, shape=(n,) or ndarray, shape=(n,3), dtype=float
+    force_field : ForceField, natoms=n
+        Any force field, patched and tabulated ones included: the device scans the contacts, ``force_constant()`` gives
+        the constants of the ordered pairs on the host, as ``compute_hessian`` does for a user-defined force field.
+    blocks : ndarray, shape=(n,)
+        Block labels (:func:`rtb_projector`, :func:`blocks_of_consecutive`), e.g. ``chain_id`` joined with ``res_id // 5``.
+    masses : bool or ndarray, shape=(n,), dtype=float, optional
+        As for :class:`ANM`: the Hessian is mass-weighted and so are the modes.
+    device : int, optional
+
+    ``projected_hessian()`` is the (nr, nr) matrix ``P^T H P`` as a CUDA tensor, summed from the pair list in a fixed
+    order (two calls agree bit for bit); no (3N, 3N) buffer exists anywhere.  ``solve(subset_by_index=None)`` enqueues
+    projection, eigensolve and expansion on torch's current stream and leaves ``w`` (1, nvec) and ``v`` (1, nvec, 3N), rows =
+    modes in the Hessian's own (mass-weighted) coordinates, the six rigid-body modes first as for an :class:`ANM`;
+    ``eigen()`` returns them as host arrays.  The modes are the Ritz pairs of the Hessian in the block space: ``w[k]`` is
+    never below the k-th eigenvalue of the full Hessian.
+
+    After a solve every mode consumer of the batch solvers works on the RTB modes, with a leading batch axis of one:
+    ``frequencies``, ``mean_square_fluctuation``, ``bfactor``, ``dcc``, ``anisotropic_fluctuation``, ``overlap``,
+    ``collectivity``, ``distance_fluctuation``, ``linear_response``, ``mode_displacement``.  ``mode_subset`` holds global
+    mode indices of the block spectrum, 6 .. nr - 1.
+
+    ``projector`` (n, 3, 6), ``block_of_atom`` (n,), ``dof`` (nb,) and ``offset`` (nb + 1,) are the host arrays of
+    :func:`rtb_projector`; ``nr = offset[-1]``.
+    """
+
+    def __init__(self, atoms, force_field, blocks, masses=None, device=None):
+        from .forcefield import device_plan
+        from .interaction import _normalised_patch, _pair_list, _validated_coord
+
+        coord = _validated_coord(_atoms.coord(atoms), force_field)
+        n = len(coord)
+        if masses is None or masses is False:
+            mass = None
+        elif masses is True:
+            from ._model import residue_mass
+
+            if not _atoms.is_atom_array(atoms):
+                raise TypeError("An AtomArray is required to automatically infer masses")
+            mass = np.array([residue_mass(r) for r in atoms.res_name], dtype=np.float64)
+        else:
+            mass = np.array(masses, dtype=np.float64)
+            if mass.shape != (n,):
+                raise IndexError(f"{mass.shape} masses for {n} atoms given")
+        self.projector, self.block_of_atom, self.dof, self.offset = rtb_projector(coord, blocks, mass)
+        self.masses = mass
+        self.coord = coord
+        self.n_atoms, self.n_blocks, self.nr = n, len(self.dof), int(self.offset[-1])
+
+        import torch
+
+        self.torch = torch
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        self._L = _hip.lib()
+        self.ctx = _hip.Context(self.device.index, stream=torch.cuda.current_stream(self.device).cuda_stream)
+        self.batch, self.dim, self.m = 1, 3, 3 * n
+        self.window, self.max_modes, self.counts = None, None, None
+        self.subset, self.nvec = None, self.nr
+        self._first_row, self._common_modes = 0, self.nr
+        self._layout = _UniformLayout(1, n, 3)
+        self.matrix = self.w = self.v = self._u = None
+
+        # contacts from the device scan, constants from the force field on the host (interaction.py:96)
+        ff_desc, patch, _ = device_plan(force_field)
+        keep = []
+        patch_desc = _normalised_patch(patch, n, keep)
+        pairs, sq_dist = _pair_list(self.ctx, coord, ff_desc, patch_desc, want_sq_dist=True)
+        gamma = np.ascontiguousarray(force_field.force_constant(pairs[:, 0], pairs[:, 1], sq_dist), dtype=np.float64)
+        if gamma.shape != (len(pairs),):
+            raise ValueError(f"force_constant() returned shape {gamma.shape} for {len(pairs)} pairs")
+        self.n_pairs = len(pairs)
+        self._isolated = np.nonzero(np.bincount(pairs[:, 0], minlength=n) == 0)[0]
+
+        with torch.cuda.device(self.device):
+            dev, i64 = self.device, torch.int64
+            self._coord = torch.from_numpy(coord).to(dev)
+            self._P = torch.from_numpy(self.projector).to(dev)
+            self._boa = torch.from_numpy(self.block_of_atom).to(dev)
+            self._offset = torch.from_numpy(self.offset).to(dev)
+            self._pairs = torch.from_numpy(pairs).to(dev)
+            self._gamma = torch.from_numpy(gamma).to(dev)
+            self.inv_sqrt_mass = None if mass is None else torch.from_numpy(1.0 / np.sqrt(mass)).to(dev)[None, :].contiguous()
+            # the order of the sums: pairs sorted by (block of the second atom, block of the first), stable, with the
+            # starts of the runs of equal keys and of every block of the second atom
+            nb = self.n_blocks
+            boa = self._boa.to(i64)
+            key = boa[self._pairs[:, 1]] * nb + boa[self._pairs[:, 0]]
+            key, self._order = torch.sort(key, stable=True)
+            first = torch.ones(len(key), dtype=torch.bool, device=dev)
+            first[1:] = key[1:] != key[:-1]
+            seg = torch.nonzero(first).flatten()
+            self._seg_start = torch.cat([seg, torch.tensor([len(key)], dtype=i64, device=dev)])
+            self.n_segments = len(seg)
+            self._block_start = torch.searchsorted(key, torch.arange(nb + 1, dtype=i64, device=dev) * nb)
+
+    def _need_vectors(self):
+        if self.v is None:
+            raise ValueError("the mode consumers need the modes: call solve() first")
+
+    # ---- projection, eigensolve, expansion -------------------------------------------------------------------------
+    def _project(self, out):
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+        self.ctx.check(self._L.sc_dev_rtb_hessian_f64(
+            self.ctx.handle, p(self._coord), self.n_atoms, p(self._pairs), self.n_pairs, p(self._gamma),
+            p(self.inv_sqrt_mass), p(self._P), p(self._boa), p(self._offset), self.n_blocks, self.nr, p(self._order),
+            p(self._seg_start), self.n_segments, p(self._block_start), p(out)))
+        return out
+
+    def projected_hessian(self):
+        """(nr, nr) CUDA tensor ``P^T H P``, every entry written; only enqueues."""
+        return self._project(self._empty((self.nr, self.nr)))
+
+    def _allocate(self, m, nvec, want_vectors=True):
+        """The tensors of a solve; ``m`` is the block order nr: no (3N, 3N) tensor exists."""
+        if self.matrix is None:
+            self.matrix = self._empty((1, m, m))
+        if self.w is None or self.w.shape[1] != nvec:
+            self.w = self._empty((1, nvec))
+            self._u = self._empty((1, nvec, m))
+            self.v = self._empty((1, nvec, 3 * self.n_atoms))
+
+    def assemble(self):
+        """``self.matrix`` (1, nr, nr) <- the projected Hessian."""
+        self._allocate(self.nr, self.nvec)
+        self._project(self.matrix)
+        return self.matrix
+
+    def eigh(self):
+        """Eigendecomposes ``self.matrix`` (destroyed) and expands the block modes: (w (1, nvec), v (1, nvec, 3N))."""
+        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        if self.subset is None:
+            self.ctx.check(self._L.sc_dev_eigh_f64(self.ctx.handle, p(self.matrix), self.nr, 1, p(self.w), p(self._u)))
+        else:
+            self.ctx.check(self._L.sc_dev_eigh_range_f64(self.ctx.handle, p(self.matrix), self.nr, 1, self.subset[0],
+                                                         self.subset[1], p(self.w), p(self._u)))
+        self.ctx.check(self._L.sc_dev_rtb_expand_f64(self.ctx.handle, p(self._u), self.nvec, self.nr, p(self._P),
+                                                     p(self._boa), p(self._offset), self.n_atoms, p(self.v)))
+        return self.w, self.v
+
+    def solve(self, subset_by_index=None):
+        """
+        Projection, eigensolve and expansion, all enqueued on the device: ``w`` (1, nvec), ``v`` (1, nvec, 3N).  Call
+        :meth:`finish` before trusting them on the host.  ``subset_by_index=(lo, hi)``: only the block modes lo..hi
+        (inclusive, ascending) through the partial-spectrum solver; row r is then mode ``lo + r``.
+
+        An atom without a contact makes more than six modes trivial, and the consumers would divide by rounding-level
+        eigenvalues: that raises ValueError naming the atoms, before anything is enqueued.  (Only atoms without any
+        contact are looked for; a network of several connected parts is the caller's to avoid, as for an :class:`ANM`.)
+        """
+        if len(self._isolated):
+            shown = ", ".join(str(a) for a in self._isolated[:10]) + (", ..." if len(self._isolated) > 10 else "")
+            raise ValueError(f"{len(self._isolated)} atom(s) without any contact ({shown}): the block network has more "
+                             "than six trivial modes")
+        if subset_by_index is None:
+            self.subset, self.nvec, self._first_row = None, self.nr, 0
+        else:
+            lo, hi = (int(x) for x in subset_by_index)
+            if not 0 <= lo <= hi < self.nr:
+                raise ValueError(f"subset_by_index {tuple(subset_by_index)} outside 0..{self.nr - 1}")
+            self.subset, self.nvec, self._first_row = (lo, hi), hi - lo + 1, lo
+        self.assemble()
+        return self.eigh()
+
+    def eigen(self, subset_by_index=None):
+        """
+        Eigenvalues (ascending, shape (nvec,)) and modes (rows, shape (nvec, 3n)) of the block-projected Hessian as host
+        arrays, like ``ANM.eigen()``: the first six belong to rigid-body motions.
+        """
+        self.solve(subset_by_index)
+        w, v = self.finish()
+        return w[0].cpu().numpy(), v[0].cpu().numpy()
