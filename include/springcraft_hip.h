@@ -631,6 +631,39 @@ int sc_dev_rtb_hessian_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, 
 int sc_dev_rtb_expand_f64(sc_ctx* ctx, const double* d_u, int64_t nvec, int64_t nr, const double* d_P,
                           const int32_t* d_block_of_atom, const int64_t* d_offset, int64_t n_atoms, double* d_v);
 
+/* ---- the network as an operator: Hessian products, deformation energies and spring strain from the pair list ---------
+ * No reference counterpart (Hinsen's deformation energy; Bio3D: deformation.nma).  The network is the ordered directed
+ * pair list d_pairs (k, 2) int64 -- sorted by first then second atom, both directions, as the pair-list entry returns
+ * it -- with d_gamma (k), d_coord (N, 3) (NULL for dim 1) and d_atom_scale (N) = 1 / sqrt(mass) or NULL for 1.  With
+ * d = r_j - r_i, n = d / |d| and, for a row x of length dim N, u[a] = scale_a x[dim a .. dim a + dim - 1], pair p = (i, j)
+ * has the elongation e_p = n . (u[i] - u[j]) (dim 1: u[i] - u[j]).  gamma must be symmetric, gamma(i, j) = gamma(j, i):
+ * then the sums below belong to the matrix sc_hessian_from_pairs_f64 / sc_kirchhoff_from_pairs_f64 build, times
+ * outer(s, s) with s the scale repeated per coordinate; the entries do not check it.  Device pointers, enqueue only on the
+ * context's stream, no atomics, no buffer beyond the arguments.
+ *
+ * sc_dev_pairs_apply_f64: for each of the q rows of d_x (q, dim N)
+ *     d_y (q, dim N)   Y[i] = scale_i sum_{p = (i, .)} gamma_p e_p n_p   (dim 1: without n_p), the product (T H T) x
+ *     d_energy (q, N)  E[i] = 1/2 sum_{p = (i, .)} gamma_p e_p^2, whose sum over the atoms is x^T (T H T) x
+ * either may be NULL, not both.  d_row_start (N + 1) int64: atom i's pairs are the rows row_start[i] ..
+ * row_start[i + 1] - 1 of the list.  Every entry of the outputs is written; an atom without pairs gets exactly 0.0.  One
+ * wavefront sums an atom's pairs in an order its own pair range fixes: a row's bits depend neither on q nor on the row's
+ * position nor on the other rows (a NaN row gives NaN for that row only), and two calls agree bit for bit.  Two atoms of
+ * a pair at one position give NaN, as the Hessian entry does.  q = 0 is valid, and so is k = 0 (zeros; the pair arrays
+ * and d_row_start may then be NULL).  SC_ERR_INVALID_ARG before anything is launched: both outputs NULL, dim not 1 or 3,
+ * dim 3 without d_coord, a non-positive n_atoms, a negative k or q, a NULL required pointer.  Rows of the list whose first
+ * atom is not i or whose second lies outside 0 .. N - 1 are skipped, not reported. */
+int sc_dev_pairs_apply_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs,
+                           int64_t k, const double* d_gamma, const int64_t* d_row_start, const double* d_atom_scale,
+                           const double* d_x, int64_t q, double* d_y, double* d_energy);
+/* d_out (q, ks): the strain S = gamma_p e_p^2 of the pairs p = d_pair_idx[s] (ks) int64 for every row of d_x, the energy
+ * mode x stores in that spring twice over (both directions of a spring carry it; the sum over all directed rows is
+ * 2 x^T (T H T) x) and, for an eigenvector, the derivative of its eigenvalue by ln gamma of the directed row.  One thread
+ * per (pair, row) term.  An index outside 0 .. k - 1 gives NaN in its column and is not read; a listed pair with an atom
+ * outside 0 .. N - 1 gives 0.0.  q = 0 and ks = 0 are valid.  SC_ERR_INVALID_ARG as above, and for a negative ks. */
+int sc_dev_pairs_strain_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs,
+                            int64_t k, const double* d_gamma, const double* d_atom_scale, const int64_t* d_pair_idx,
+                            int64_t ks, const double* d_x, int64_t q, double* d_out);
+
 #ifdef __cplusplus
 }
 #endif

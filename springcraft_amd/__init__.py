@@ -14,4 +14,5 @@ from .forcefield import *  # noqa: F401,F403
 from .gnm import *  # noqa: F401,F403
 from .interaction import *  # noqa: F401,F403
 from . import nma  # noqa: F401
+from .pair_operator import PairOperator  # noqa: F401
 from .rtb import RTB, blocks_of_consecutive, rtb_projector  # noqa: F401

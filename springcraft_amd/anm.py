@@ -104,6 +104,14 @@ class ANM(ElasticNetworkModel):
         """Fluctuations of the inter-atom distances, (n, n) (:func:`nma.distance_fluctuation`; no reference counterpart)."""
         return nma.distance_fluctuation(self, mode_subset, projected, tem, tem_factors)
 
+    def deformation_energy(self, mode_subset=None):
+        """Per-atom deformation energies of the selected modes, (k, n); a row sums to its eigenvalue (:func:`nma.deformation_energy`)."""
+        return nma.deformation_energy(self, mode_subset)
+
+    def spring_strain(self, mode_subset=None):
+        """(springs (P, 2), strain (k, P)): what every spring stores in the selected modes (:func:`nma.spring_strain`)."""
+        return nma.spring_strain(self, mode_subset)
+
     def collectivity(self, mode_subset=None):
         """Collectivity of the selected modes, (k,) (:func:`nma.collectivity`)."""
         return nma.collectivity(self, mode_subset)

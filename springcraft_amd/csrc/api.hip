@@ -1494,6 +1494,47 @@ int sc_dev_rtb_expand_f64(sc_ctx* ctx, const double* d_u, int64_t nvec, int64_t 
   return launch_rtb_expand(ctx, d_u, nvec, nr, d_P, d_block_of_atom, d_offset, n_atoms, d_v);
 }
 
+// ---- the network as an operator on the pair list (pair_operator.hip) -------------------------------------------------
+static int pairs_network_check(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs,
+                               int64_t k, const double* d_gamma, const double* d_x, int64_t q) {
+  if (dim != 1 && dim != 3) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: dim must be 1 or 3, got %d", dim);
+  if (n_atoms <= 0 || k < 0 || q < 0)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: n_atoms must be positive, k and q not negative");
+  if (n_atoms > ((int64_t)1 << 32))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: at most 2^32 atoms");
+  if (dim == 3 && !d_coord) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: dim 3 needs the coordinates");
+  if (k > 0 && (!d_pairs || !d_gamma))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: pairs and gamma are required with k > 0");
+  if (q > 0 && !d_x) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: the rows are required with q > 0");
+  return SC_OK;
+}
+
+int sc_dev_pairs_apply_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs,
+                           int64_t k, const double* d_gamma, const int64_t* d_row_start, const double* d_atom_scale,
+                           const double* d_x, int64_t q, double* d_y, double* d_energy) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  if (!d_y && !d_energy) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: neither a product nor energies asked for");
+  SC_TRY(pairs_network_check(ctx, d_coord, n_atoms, dim, d_pairs, k, d_gamma, d_x, q));
+  if (k > 0 && !d_row_start) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: row starts are required with k > 0");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return launch_pairs_apply(ctx, d_coord, n_atoms, dim, d_pairs, k, d_gamma, d_row_start, d_atom_scale, d_x, q, d_y,
+                            d_energy);
+}
+
+int sc_dev_pairs_strain_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs,
+                            int64_t k, const double* d_gamma, const double* d_atom_scale, const int64_t* d_pair_idx,
+                            int64_t ks, const double* d_x, int64_t q, double* d_out) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  SC_TRY(pairs_network_check(ctx, d_coord, n_atoms, dim, d_pairs, k, d_gamma, d_x, q));
+  if (ks < 0 || ks > ((int64_t)1 << 38))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: the number of listed pairs must lie in 0 .. 2^38");
+  if (ks > 0 && q > 0 && (!d_pair_idx || !d_out))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: the pair indices and the result are required");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return launch_pairs_strain(ctx, d_coord, n_atoms, dim, d_pairs, k, d_gamma, d_atom_scale, d_pair_idx, ks, d_x, q,
+                             d_out);
+}
+
 void sc_batch_plan_destroy(sc_batch_plan* plan) {
   if (!plan) return;
   (void)hipSetDevice(plan->ctx->device);

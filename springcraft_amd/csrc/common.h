@@ -375,6 +375,19 @@ int launch_rtb_hessian(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, cons
 int launch_rtb_expand(sc_ctx* ctx, const double* d_u, int64_t nvec, int64_t nr, const double* d_P, const int32_t* d_boa,
                       const int64_t* d_offset, int64_t n_atoms, double* d_v);
 
+// ---- the network as an operator on the pair list (pair_operator.hip) ------------------------------------------------
+// Y = (T H T) x and E (per-atom deformation energies) for the q rows of d_x, H as launch_hessian_from_pairs /
+// launch_kirchhoff_from_pairs fill it for symmetric constants: d_row_start (N + 1), atom i's pairs are the rows
+// row_start[i] .. row_start[i + 1] - 1 of the list; d_y (q, dim N) or null, d_energy (q, N) or null, every entry written.
+// One wavefront per atom, a fixed order of the sums.  No atomics, no workspace; enqueue only.
+int launch_pairs_apply(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs, int64_t k,
+                       const double* d_gamma, const int64_t* d_row_start, const double* d_atom_scale, const double* d_x,
+                       int64_t q, double* d_y, double* d_energy);
+// d_out (q, ks): the strain gamma_p e_p^2 of the listed pairs p = d_pair_idx[s]; NaN for an index outside 0 .. k - 1.
+int launch_pairs_strain(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs, int64_t k,
+                        const double* d_gamma, const double* d_atom_scale, const int64_t* d_pair_idx, int64_t ks,
+                        const double* d_x, int64_t q, double* d_out);
+
 // Raises a kernel's dynamic LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) once per (device, kernel).  The
 // attribute belongs to the device that is current when it is set: a function-local static done-flag (rounds 2-5) served
 // the first device a process used and left contexts on a second GPU with refused launches.  Returns

@@ -16,6 +16,8 @@ moves) are one pass along the selected rows (``csrc/mode_overlap.hip``); ``cumul
 ``linear_response`` (reference: nma.py:422-473) and ``mode_displacement`` (no reference counterpart: a displacement field
 built from chosen modes) are the two passes of ``csrc/mode_response.hip`` over the selected rows, in mode space: no
 covariance is formed and only (q, 3N) numbers cross PCIe; ``sample_displacements`` draws the coefficients on the host.
+``deformation_energy`` and ``spring_strain`` (no reference counterpart: where a mode strains the network) run the selected
+modes through the pair-list operator of ``csrc/pair_operator.hip`` (:class:`~springcraft_amd.PairOperator`).
 ``normal_mode`` and ``effector_sensor`` are O(n) / O(n^2) host arithmetic on results that are already on the host.
 """
 
@@ -28,7 +30,7 @@ __all__ = [
     "eigen", "eigh", "pinvh", "frequencies", "mean_square_fluctuation", "bfactor", "dcc",
     "normal_mode", "linear_response", "prs", "effector_sensor", "anisotropic_fluctuation", "anisotropy",
     "overlap", "collectivity", "cumulative_overlap", "distance_fluctuation", "effective_stiffness",
-    "mode_displacement", "sample_displacements",
+    "mode_displacement", "sample_displacements", "deformation_energy", "spring_strain",
 ]
 
 K_B = 1.380649e-23
@@ -477,6 +479,64 @@ def sample_displacements(enm, n_samples, mode_subset=None, tem=None, tem_factors
     lam = enm._modes_device().values()[idx]
     xi = np.random.default_rng(rng).standard_normal((n_samples, len(idx)))
     return mode_displacement(enm, xi * np.sqrt(kt / lam), idx)
+
+
+def _pair_operator(enm):
+    """The model's :class:`~springcraft_amd.PairOperator`, built once from its coordinates, force field and masses."""
+    op = getattr(enm, "_pair_operator", None)
+    if op is None:
+        from .pair_operator import PairOperator
+
+        op = enm._pair_operator = PairOperator(enm._coord, enm._ff, dim=enm._dim, masses=enm._masses)
+    return op
+
+
+def _selected_modes(enm, mode_subset):
+    """Rows (k, dim N) of the selected modes on the host; the selection is :func:`mean_square_fluctuation`'s."""
+    _model_kind(enm)
+    if mode_subset is not None:
+        mode_subset = _mode_selection(enm, mode_subset, None)   # (the trivial-mode error needs no device)
+    modes = enm._modes_device()
+    if mode_subset is None:
+        mode_subset = _mode_selection(enm, None, modes.order)
+    _, v = modes.eigen()
+    return np.ascontiguousarray(v[np.asarray(mode_subset, dtype=np.int64).reshape(-1)])
+
+
+def deformation_energy(enm, mode_subset=None):
+    """
+    Hinsen's per-atom deformation energy of the k selected modes, (k, N):
+
+        ``E_k[a] = 1/2 sum_c gamma_ac (n_ac . (u_k[a] - u_k[c]))^2``  (GNM: without the direction ``n_ac``)
+
+    over the contacts c of atom a, ``u_k`` the mode (divided by ``sqrt(mass)`` for a model with masses): where mode k
+    deforms the network rather than moving it rigidly -- hinges and strained regions score high, rigid domains low.  A row
+    sums to its eigenvalue.  ``mode_subset`` as in :func:`mean_square_fluctuation` (None: every non-trivial mode; trivial
+    indices raise ValueError).  No reference counterpart (Bio3D: ``deformation.nma``).  The sums run on the device from
+    the model's own pair list (``csrc/pair_operator.hip``); the operator is built from the model's coordinates, force
+    field and masses -- not from a matrix the caller assigned -- and is kept on the model.  Asymmetric force constants
+    raise ValueError.
+    """
+    v = _selected_modes(enm, mode_subset)
+    n = len(enm._coord)
+    if not len(v):
+        return np.empty((0, n))
+    return _pair_operator(enm).energy(v).cpu().numpy()
+
+
+def spring_strain(enm, mode_subset=None):
+    """
+    What every spring stores in the k selected modes: ``(springs, strain)``, ``springs`` (P, 2) the contacts with
+    ``i < j`` and ``strain[k, s] = gamma_s (n_s . (u_k[i] - u_k[j]))^2`` (k, P).  A row sums to its eigenvalue, and
+    ``strain[k, s]`` is the first-order change of eigenvalue k per relative change of spring s' constant,
+    ``d lambda_k / d ln gamma_s``: which contacts the mode depends on.  Selection, operator and errors as for
+    :func:`deformation_energy`.  No reference counterpart.
+    """
+    v = _selected_modes(enm, mode_subset)
+    op = _pair_operator(enm)
+    if not len(v):
+        return op.springs, np.empty((0, len(op.springs)))
+    return op.springs, op.strain(v).cpu().numpy()
 
 
 def prs(anm, norm=True):

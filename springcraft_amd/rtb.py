@@ -137,6 +137,12 @@ class RTB(_BatchSolver):
     ``collectivity``, ``distance_fluctuation``, ``linear_response``, ``mode_displacement``.  ``mode_subset`` holds global
     mode indices of the block spectrum, 6 .. nr - 1.
 
+    How good the block modes are can be read without the dense problem: ``operator`` is the Hessian as a
+    :class:`~springcraft_amd.PairOperator` on the solver's own pair list (no second contact scan), ``residuals()`` gives
+    ``|H v_k - w_k v_k|`` per solved row -- some exact eigenvalue of the full Hessian lies within it of ``w[k]`` --
+    and ``deformation_energy()`` / ``spring_strain()`` say where a mode strains the network.  They need symmetric force
+    constants (ValueError otherwise).
+
     ``projector`` (n, 3, 6), ``block_of_atom`` (n,), ``dof`` (nb,) and ``offset`` (nb + 1,) are the host arrays of
     :func:`rtb_projector`; ``nr = offset[-1]``.
     """
@@ -176,6 +182,7 @@ class RTB(_BatchSolver):
         self._first_row, self._common_modes = 0, self.nr
         self._layout = _UniformLayout(1, n, 3)
         self.matrix = self.w = self.v = self._u = None
+        self._operator = None
 
         # contacts from the device scan, constants from the force field on the host (interaction.py:96)
         ff_desc, patch, _ = device_plan(force_field)
@@ -286,3 +293,51 @@ class RTB(_BatchSolver):
         self.solve(subset_by_index)
         w, v = self.finish()
         return w[0].cpu().numpy(), v[0].cpu().numpy()
+
+    # ---- the Hessian as an operator on the solver's pair list (pair_operator.py) ------------------------------------------
+    @property
+    def operator(self):
+        """The (mass-weighted) Hessian as a :class:`~springcraft_amd.PairOperator` on this solver's pairs, constants and context."""
+        if self._operator is None:
+            from .pair_operator import PairOperator
+
+            ism = None if self.inv_sqrt_mass is None else self.inv_sqrt_mass[0]
+            self._operator = PairOperator.from_pairs(self._coord, self._pairs, self._gamma, dim=3, inv_sqrt_mass=ism,
+                                                     _ctx=self.ctx)
+        return self._operator
+
+    def _mode_rows(self, mode_subset, trivial=False):
+        """(w, v) of the rows a mode_subset names; None: every solved row, the trivial ones only with ``trivial``."""
+        self._need_vectors()
+        if mode_subset is None and trivial:
+            return self.w[0], self.v[0]
+        from .batch import batch_mode_rows
+
+        rows = batch_mode_rows(mode_subset, self._ntriv, self.subset, self._common_modes, self.window)
+        rows = self.torch.from_numpy(rows.astype(np.int64)).to(self.device)
+        return self.w[0][rows], self.v[0][rows]
+
+    def residuals(self, mode_subset=None):
+        """
+        ``|H v_k - w_k v_k|_2`` of the solved pairs against the full Hessian, a CUDA tensor (nvec,) for ``mode_subset=None``
+        (every solved row, the trivial ones included), else one per listed mode (global indices as for the other
+        consumers).  The modes are unit vectors, so an exact eigenvalue lies within ``residuals()[k]`` of ``w[k]``; a
+        small residual also bounds the mode's angle to the exact eigenspace by residual / gap.  Only enqueues.
+        """
+        w, v = self._mode_rows(mode_subset, trivial=True)
+        return self.operator.residual(w, v)
+
+    def deformation_energy(self, mode_subset=None):
+        """
+        (k, n_atoms) CUDA tensor of Hinsen's per-atom deformation energies of the selected block modes
+        (:func:`nma.deformation_energy`); a row sums to ``<v_k, H v_k> = w[k]``.  None: every solved non-trivial mode.
+        """
+        return self.operator.energy(self._mode_rows(mode_subset)[1])
+
+    def spring_strain(self, mode_subset=None):
+        """
+        ``(springs, strain)``: ``springs`` (P, 2) host array of the contacts with ``i < j``, ``strain`` (k, P) CUDA tensor
+        ``gamma_s e_s^2`` of the selected block modes (:func:`nma.spring_strain`); a row sums to ``w[k]``.
+        """
+        op = self.operator
+        return op.springs, op.strain(self._mode_rows(mode_subset)[1])
