@@ -663,6 +663,25 @@ int sc_dev_pairs_apply_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, 
 int sc_dev_pairs_strain_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs,
                             int64_t k, const double* d_gamma, const double* d_atom_scale, const int64_t* d_pair_idx,
                             int64_t ks, const double* d_x, int64_t q, double* d_out);
+/* One fused step of a polynomial in T H T on a column panel: Z <- alpha (T H T) X + beta X + gamma_c Z, the three-term
+ * recurrence of a Chebyshev filter in one pass.  T H T is exactly the matrix of sc_dev_pairs_apply_f64, from the same pair
+ * list, d_row_start, d_gamma, d_coord and d_atom_scale.  A panel has m = dim N rows and q columns with the leading
+ * dimension ld >= q: element (row dim a + c, column r) of d_x / d_z lies at [(dim a + c) ld + r]; the columns are the
+ * vectors (the transpose of the rows sc_dev_pairs_apply_f64 takes).  d_z must not be d_x (nor overlap it; two panels may
+ * interleave in one buffer of a larger ld).  d_z is read only when gamma_c != 0: with gamma_c = 0 it is overwritten and a
+ * NaN in it does not propagate.  Columns q .. ld - 1 of d_z are never written and those of d_x never read.  One wavefront
+ * owns an atom and 64 columns and adds the atom's pairs in list order, lane = column: a column's bits depend neither on
+ * q nor on ld nor on the column's position nor on the other columns (a NaN column gives NaN in that column only), and two
+ * calls agree bit for bit; the sum order differs from sc_dev_pairs_apply_f64, whose result it matches to rounding only.
+ * An atom without pairs gets beta X + gamma_c Z with the H term exactly 0.0.  q = 0 is valid (nothing is launched), and so
+ * is k = 0 (Z <- beta X + gamma_c Z; the pair arrays and d_row_start may then be NULL).  SC_ERR_INVALID_ARG before anything
+ * is launched: ld < q, d_z == d_x, dim not 1 or 3, dim 3 without d_coord, a non-positive n_atoms, a negative k, q or ld,
+ * q above 4194240 (65535 chunks of 64 columns), a NULL required pointer.  Rows of the list whose first atom is not i or
+ * whose second lies outside 0 .. N - 1 are skipped, not reported. */
+int sc_dev_pairs_panel_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs,
+                           int64_t k, const double* d_gamma, const int64_t* d_row_start, const double* d_atom_scale,
+                           const double* d_x, double* d_z, int64_t ld, int64_t q, double alpha, double beta,
+                           double gamma_c);
 
 #ifdef __cplusplus
 }

@@ -55,7 +55,7 @@ EXPORTED_SYMBOLS = [
     "sc_modes_response", "sc_dev_mode_response_f64", "sc_batch_plan_mode_response_f64",
     "sc_modes_combine", "sc_dev_mode_combine_f64", "sc_batch_plan_mode_combine_f64",
     "sc_dev_rtb_hessian_f64", "sc_dev_rtb_expand_f64",
-    "sc_dev_pairs_apply_f64", "sc_dev_pairs_strain_f64",
+    "sc_dev_pairs_apply_f64", "sc_dev_pairs_strain_f64", "sc_dev_pairs_panel_f64",
 ]
 
 SC_SEL_FROM_ROW = 0
@@ -250,6 +250,7 @@ def lib():
         "sc_dev_rtb_expand_f64": (i32, [vp, vp, i64, i64, vp, vp, vp, i64, vp]),
         "sc_dev_pairs_apply_f64": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, i64, vp, vp]),
         "sc_dev_pairs_strain_f64": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp, i64, vp, i64, vp]),
+        "sc_dev_pairs_panel_f64": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, i64, i64, dbl, dbl, dbl]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -1535,6 +1535,23 @@ int sc_dev_pairs_strain_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms,
                              d_out);
 }
 
+int sc_dev_pairs_panel_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs,
+                           int64_t k, const double* d_gamma, const int64_t* d_row_start, const double* d_atom_scale,
+                           const double* d_x, double* d_z, int64_t ld, int64_t q, double alpha, double beta,
+                           double gamma_c) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  SC_TRY(pairs_network_check(ctx, d_coord, n_atoms, dim, d_pairs, k, d_gamma, d_x, q));
+  if (k > 0 && !d_row_start) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: row starts are required with k > 0");
+  if (ld < q) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: the leading dimension %lld is below the %lld columns",
+                                  (long long)ld, (long long)q);
+  if (q > 65535 * (int64_t)64) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: at most 4194240 columns per panel");
+  if (q > 0 && !d_z) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: the result panel is required with q > 0");
+  if (d_z && d_z == d_x) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: the result panel must not be the input panel");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return launch_pairs_panel(ctx, d_coord, n_atoms, dim, d_pairs, k, d_gamma, d_row_start, d_atom_scale, d_x, d_z, ld, q,
+                            alpha, beta, gamma_c);
+}
+
 void sc_batch_plan_destroy(sc_batch_plan* plan) {
   if (!plan) return;
   (void)hipSetDevice(plan->ctx->device);

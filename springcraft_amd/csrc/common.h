@@ -387,6 +387,11 @@ int launch_pairs_apply(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int 
 int launch_pairs_strain(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs, int64_t k,
                         const double* d_gamma, const double* d_atom_scale, const int64_t* d_pair_idx, int64_t ks,
                         const double* d_x, int64_t q, double* d_out);
+// (pair_panel.hip) Z <- alpha (T H T) X + beta X + gamma_c Z on column panels (dim N, q) of leading dimension ld, the same
+// matrix as launch_pairs_apply: one wavefront per (atom, 64 columns), lane = column, no sum across lanes.  Enqueue only.
+int launch_pairs_panel(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs, int64_t k,
+                       const double* d_gamma, const int64_t* d_row_start, const double* d_atom_scale, const double* d_x,
+                       double* d_z, int64_t ld, int64_t q, double alpha, double beta, double gamma_c);
 
 // Raises a kernel's dynamic LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) once per (device, kernel).  The
 // attribute belongs to the device that is current when it is set: a function-local static done-flag (rounds 2-5) served

@@ -1,0 +1,177 @@
+// One fused Chebyshev step of the pair-list operator on a column panel: Z <- alpha (T H T) X + beta X + gamma_c Z.
+// No reference counterpart.  The matrix T H T is the one of k_pairs_apply (pair_operator.hip, whose header has the pair
+// list, d_p, n_p, t_a and the formulas); what differs is the arrangement, made for an iteration that applies H hundreds of
+// times to a block of 30 .. 200 vectors.
+//
+// Layout.  A panel has m = dim N rows and q columns with leading dimension ld >= q: element (row dim a + c, column r) at
+// X[(dim a + c) ld + r].  Columns are the vectors.
+//
+// k_pairs_panel: one wavefront owns (atom i, a chunk of 64 columns), lane = column.  It walks the atom's pairs
+// row_start[i] .. row_start[i + 1] - 1 in list order, 64 at a time: every lane loads ONE pair of the 64 (j, gamma, t_j) and
+// computes its n_p -- the square root and the three divisions cost a pair one lane-instruction instead of one per column
+// -- and the wavefront then takes the 64 pairs one after the other, each broadcast from its lane into scalar registers
+// (v_readlane, a uniform lane index).  Per pair and component a lane gathers X[dim j + c, r]: the wavefront reads 64
+// consecutive doubles, one fully used 512-byte row segment.  A lane adds its own dim sums in registers, sequentially in
+// pair order, and stores alpha (t_i sum) + beta X[i] (+ gamma_c Z[i]).  No LDS, no atomics, no workspace, and no sum
+// across lanes: a column's bits depend on the atom's pair range alone, not on q, ld, the column's position or the other
+// columns (the file is compiled with -ffp-contract=off, build.py, so every operation is the one written, and a pair's
+// geometry is the same number whichever lane computed it).
+//
+// Workgroup: 256 threads = four wavefronts that take four consecutive ATOMS of one column chunk, not one atom's four
+// chunks.  (1) Neighbours in the list are neighbours in space: consecutive atoms share most of their partners j, so
+// the four wavefronts gather the same rows of X and the second to fourth find them in the CU's vector L1.  Four chunks of
+// one atom share only the pair data, 40 bytes per pair against 1536 per pair and chunk of X.  (2) The solver's panels
+// have 30 .. 200 columns, one to four chunks: four chunks per workgroup would leave one to three wavefronts of every
+// workgroup without work, four atoms keep all of them busy at every q.  The kernel uses some 40 VGPRs, so eight
+// wavefronts per SIMD hide the latency of the gathers.
+//
+// Edge rules.  An atom without pairs: the H term is exactly 0.0, the result beta X + gamma_c Z.  Rows of the list whose
+// first atom is not i or whose second lies outside 0 .. N - 1 are skipped, as in k_pairs_apply.  Z is read only when
+// gamma_c != 0 (with gamma_c = 0 it is overwritten, whatever it held); lanes beyond q load pair data like the others,
+// read no column beyond q and write nothing, so the columns q .. ld - 1 of Z keep their bits.
+#include "common.h"
+
+namespace {
+
+__device__ __forceinline__ double lane_value(double v, int l) {   // v of lane l (uniform) in every lane
+  const long long bits = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_readlane((int)bits, l);
+  const int hi = __builtin_amdgcn_readlane((int)(bits >> 32), l);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256) void k_pairs_panel(const double* __restrict__ coord, long long n_atoms,
+                                                     const long long* __restrict__ pairs, long long k,
+                                                     const double* __restrict__ gamma,
+                                                     const long long* __restrict__ row_start,
+                                                     const double* __restrict__ scale, const double* __restrict__ x,
+                                                     double* __restrict__ z, long long ld, long long q, double alpha,
+                                                     double beta, double gamma_c) {
+  const int lane = threadIdx.x & 63;
+  const long long i = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (i >= n_atoms) return;
+  const long long col = (long long)blockIdx.y * 64 + lane;
+  const bool live = col < q;
+  long long lo = 0, hi = 0;
+  if (k > 0) {
+    lo = row_start[i];
+    hi = row_start[i + 1];
+    if (lo < 0) lo = 0;
+    if (hi > k) hi = k;
+  }
+
+  const double ti = scale ? scale[i] : 1.0;
+  double ci[3] = {0.0, 0.0, 0.0};
+  if (DIM == 3 && lo < hi) {
+    ci[0] = coord[3 * i + 0];
+    ci[1] = coord[3 * i + 1];
+    ci[2] = coord[3 * i + 2];
+  }
+  // a lane beyond q reads the chunk's first column in place of its own (the same addresses, no further traffic) and stores
+  // nothing: the loop below then has no divergent branch
+  const double* __restrict__ xc = x + (live ? col : (long long)blockIdx.y * 64);
+  double xi[DIM], ui[DIM], s[DIM];
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) {
+    xi[c] = xc[(DIM * i + c) * ld];
+    ui[c] = ti * xi[c];
+    s[c] = 0.0;
+  }
+
+  for (long long c0 = lo; c0 < hi; c0 += 64) {
+    // this lane's pair of the 64: j, gamma, t_j, n_p (skipped: an entry whose first atom is not i or whose second lies
+    // outside 0 .. N - 1)
+    const long long p = c0 + lane;
+    bool valid = p < hi;
+    long long j = 0;
+    double g = 0.0, tj = 1.0, n[3] = {0.0, 0.0, 0.0};
+    if (valid) {
+      const long long pi = pairs[2 * p];
+      j = pairs[2 * p + 1];
+      valid = pi == i && j >= 0 && j < n_atoms;
+      if (!valid) j = 0;
+    }
+    if (valid) {
+      g = gamma[p];
+      if (scale) tj = scale[j];
+      if (DIM == 3) {
+        const double dx = coord[3 * j + 0] - ci[0];
+        const double dy = coord[3 * j + 1] - ci[1];
+        const double dz = coord[3 * j + 2] - ci[2];
+        const double len = sqrt((dx * dx + dy * dy) + dz * dz);
+        n[0] = dx / len;   // (two atoms at one position: 0 / 0 = NaN, as the Hessian entry)
+        n[1] = dy / len;
+        n[2] = dz / len;
+      }
+    }
+    const unsigned long long listed = __ballot(valid);
+    const int count = (int)(hi - c0 < 64 ? hi - c0 : 64);
+
+    // the pair of lane l (uniform; every lane of the wavefront is active here) from scalar registers; j < 2^32 (the entry
+    // refuses more atoms)
+    auto add_pair = [&](int l) {
+      const long long jl = (long long)(unsigned int)__builtin_amdgcn_readlane((int)j, l);
+      const double gl = lane_value(g, l);
+      const double tl = lane_value(tj, l);
+      if (DIM == 3) {
+        const double n0 = lane_value(n[0], l), n1 = lane_value(n[1], l), n2 = lane_value(n[2], l);
+        const double ex = ui[0] - tl * xc[(3 * jl + 0) * ld];
+        const double ey = ui[1] - tl * xc[(3 * jl + 1) * ld];
+        const double ez = ui[2] - tl * xc[(3 * jl + 2) * ld];
+        const double e = (n0 * ex + n1 * ey) + n2 * ez;
+        const double ge = gl * e;
+        s[0] += ge * n0;
+        s[1] += ge * n1;
+        s[2] += ge * n2;
+      } else {
+        const double e = ui[0] - tl * xc[jl * ld];
+        s[0] += gl * e;
+      }
+    };
+    // All loops add the listed pairs in list order.  The first, for a chunk without a skipped row (every chunk of a
+    // checked list), takes four pairs per step without a branch between them, so that their gathers are in flight
+    // together (unrolled by hand: the compiler does not unroll a loop of convergent operations with a remainder).
+    if (listed == (count == 64 ? ~0ull : (1ull << count) - 1)) {
+      int l = 0;
+      for (; l + 4 <= count; l += 4) {
+        add_pair(l);
+        add_pair(l + 1);
+        add_pair(l + 2);
+        add_pair(l + 3);
+      }
+      for (; l < count; ++l) add_pair(l);
+    } else {
+      for (unsigned long long rest = listed; rest; rest &= rest - 1) add_pair(__builtin_ctzll(rest));
+    }
+  }
+
+  if (!live) return;
+  double* __restrict__ zc = z + col;
+#pragma unroll
+  for (int c = 0; c < DIM; ++c) {
+    const long long at = (DIM * i + c) * ld;
+    double v = alpha * (ti * s[c]) + beta * xi[c];
+    if (gamma_c != 0.0) v += gamma_c * zc[at];
+    zc[at] = v;
+  }
+}
+
+}  // namespace
+
+int launch_pairs_panel(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs, int64_t k,
+                       const double* d_gamma, const int64_t* d_row_start, const double* d_atom_scale, const double* d_x,
+                       double* d_z, int64_t ld, int64_t q, double alpha, double beta, double gamma_c) {
+  if (q == 0) return SC_OK;
+  const dim3 grid((unsigned)((n_atoms + 3) / 4), (unsigned)((q + 63) / 64));
+  if (dim == 3)
+    hipLaunchKernelGGL(k_pairs_panel<3>, grid, dim3(256), 0, ctx->stream, d_coord, (long long)n_atoms,
+                       (const long long*)d_pairs, (long long)k, d_gamma, (const long long*)d_row_start, d_atom_scale,
+                       d_x, d_z, (long long)ld, (long long)q, alpha, beta, gamma_c);
+  else
+    hipLaunchKernelGGL(k_pairs_panel<1>, grid, dim3(256), 0, ctx->stream, d_coord, (long long)n_atoms,
+                       (const long long*)d_pairs, (long long)k, d_gamma, (const long long*)d_row_start, d_atom_scale,
+                       d_x, d_z, (long long)ld, (long long)q, alpha, beta, gamma_c);
+  SC_HIP(ctx, hipGetLastError());
+  return SC_OK;
+}

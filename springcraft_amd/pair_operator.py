@@ -11,6 +11,10 @@ and the directed pair p = (i, j) with constant ``gamma_p`` and direction ``n_p =
     E[i]  = 1/2 sum_{p = (i, .)} gamma_p e_p^2                              sum_i E[i] = x^T (T H T) x
     S[p]  = gamma_p e_p^2                                                   sum_p S[p] = 2 x^T (T H T) x
 
+``panel_step`` is one fused step ``Z <- alpha (T H T) X + beta X + gamma_c Z`` on column panels (``csrc/pair_panel.hip``),
+``lowest_modes`` the Chebyshev-filtered subspace iteration built on it (:mod:`springcraft_amd.iterative`): the exact lowest
+eigenpairs of the matrix to a requested tolerance, in memory of order (dim N, k).
+
 The constants must be symmetric, ``gamma(i, j) = gamma(j, i)``: the reference's rule for asymmetric ones (off-diagonal
 from ``gamma(i, j)``, diagonal summed over the first index) has no energy reading, and :class:`PairOperator` raises
 ValueError for them.
@@ -324,3 +328,81 @@ class PairOperator:
             raise ValueError(f"Expected {len(xr)} eigenvalues, one per row, got {len(w)}")
         r = torch.linalg.vector_norm(self.apply(xr) - w[:, None] * xr, dim=1)
         return r[0] if single else r
+
+    # ---- column panels and the iterative solver (iterative.py, csrc/pair_panel.hip) -------------------------------------
+    def spectral_bound(self):
+        """``b = 2 max_i t_i^2 sum_{p = (i, .)} |gamma_p|``, an upper bound of the largest eigenvalue (:func:`iterative.spectral_bound`)."""
+        from .iterative import spectral_bound
+
+        scale = None if self._scale is None else self._scale.cpu().numpy()
+        return spectral_bound(self.pairs, self.gamma, self.n_atoms, scale)
+
+    def panel_step(self, X, Z, alpha, beta, gamma_c):
+        """
+        ``Z <- alpha (T H T) X + beta X + gamma_c Z`` in place, one kernel; returns ``Z``.  ``X`` and ``Z`` are CUDA float64
+        tensors of shape (dim n, q) with strides (ld, 1), ld >= q, the same ld for both: columns are the vectors, the
+        transpose of what :meth:`apply` takes.  ``Z`` must not share memory with ``X`` and is read only when
+        ``gamma_c != 0``.  A column's bits depend neither on q nor on ld nor on the other columns; the sums run in another
+        order than :meth:`apply`'s, whose result they match to rounding.  Only enqueues.
+        """
+        torch = self.torch
+        for name, t in (("X", X), ("Z", Z)):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == self.device and t.dtype == torch.float64):
+                raise ValueError(f"{name} must be a CUDA float64 tensor on {self.device}")
+            if t.ndim != 2 or t.shape[0] != self.m:
+                raise ValueError(f"Expected a panel of shape ({self.m}, q), got {tuple(t.shape)}")
+        q = X.shape[1]
+        if Z.shape[1] != q:
+            raise ValueError(f"X has {q} columns, Z {Z.shape[1]}")
+        ld = X.stride(0) if self.m > 1 else max(q, 1)
+        if q == 0:
+            return Z
+        if (q > 1 and (X.stride(1) != 1 or Z.stride(1) != 1)) or (self.m > 1 and (Z.stride(0) != ld or ld < q)):
+            raise ValueError(f"panels need strides (ld, 1) with one ld >= q, got {X.stride()} and {Z.stride()}")
+        p, have = self._p, self.n_pairs > 0
+        with torch.cuda.device(self.device):
+            self.ctx.check(self._L.sc_dev_pairs_panel_f64(
+                self.ctx.handle, p(self._coord), self.n_atoms, self.dim, p(self._pairs) if have else None, self.n_pairs,
+                p(self._gamma) if have else None, p(self._row_start), p(self._scale), p(X), p(Z), ld, q, float(alpha),
+                float(beta), float(gamma_c)))
+        return Z
+
+    def _small_eigh(self, a):
+        """(w, U) of a symmetric (n, n) CUDA tensor through the device eigensolver; eigenvectors as columns; ``a`` is destroyed."""
+        n, p = len(a), self._p
+        a = a.contiguous()
+        w, v = self._empty((n,)), self._empty((n, n))
+        self.ctx.check(self._L.sc_dev_eigh_f64(self.ctx.handle, p(a), n, 1, p(w), p(v)))
+        return w, v.T
+
+    def lowest_modes(self, k, start=None, tol=1e-8, degree=20, guard=None, max_iter=100, seed=0):
+        """
+        The k lowest eigenpairs of ``T H T`` by Chebyshev-filtered subspace iteration
+        (:func:`iterative.chebyshev_subspace_iteration`), to residuals ``|H v - w v| <= tol * b`` with ``b`` the
+        :meth:`spectral_bound`: ``(w (k,), v (k, dim n), info)``, CUDA tensors, ``w`` ascending, the modes as orthonormal
+        rows with the trivial ones first, as everywhere in the package.  No (dim n, dim n) matrix exists; the memory is a
+        few panels of ``nb = k + guard`` columns.
+
+        ``start`` (k', dim n), k' >= 1: rows to start from (an array or a tensor), e.g. RTB modes; they are truncated to
+        nb, or padded with standard-normal columns of ``RandomState(seed)``; None: all random.  ``guard`` columns beyond
+        k keep the wanted end of the block converging (default ``max(8, ceil(k / 4))``, :func:`iterative.default_guard`),
+        ``degree`` is that of the filter, ``max_iter`` the most filter passes.  ``info`` holds ``iterations``,
+        ``panel_steps``, ``residuals`` (k,), ``b``, ``tol`` and ``converged``; a solve that runs out of passes returns what
+        it has with ``converged = False`` and does not raise.  The same arguments give the same bits.
+        """
+        from . import iterative
+
+        k, guard, nb = iterative.checked_block(k, guard, self.m)
+        if int(degree) < 1 or int(max_iter) < 0:
+            raise ValueError(f"degree must be at least 1 and max_iter not negative, got {degree} and {max_iter}")
+        import torch
+
+        if isinstance(start, torch.Tensor):
+            start = start.detach().cpu().numpy()
+        x0 = iterative.start_block(start, self.m, nb, seed)   # (every refusal above and here needs no device)
+        b = self.spectral_bound()
+        with torch.cuda.device(self.device):
+            w, x, info = iterative.chebyshev_subspace_iteration(self.panel_step, self._small_eigh,
+                                                                torch.from_numpy(x0).to(self.device), k, b, tol=tol,
+                                                                degree=int(degree), max_iter=int(max_iter))
+            return w.contiguous(), x.T.contiguous(), info

@@ -341,3 +341,23 @@ class RTB(_BatchSolver):
         """
         op = self.operator
         return op.springs, op.strain(self._mode_rows(mode_subset)[1])
+
+    def refine(self, tol=1e-8, **options):
+        """
+        Replaces the block modes of the last :meth:`solve` by eigenpairs of the full (mass-weighted) Hessian for the same
+        rows: :meth:`PairOperator.lowest_modes` started from ``self.v``, to residuals ``<= tol * b``
+        (``options``: ``degree``, ``guard``, ``max_iter``, ``seed``).  ``self.w`` (1, nvec) and ``self.v`` (1, nvec, 3N)
+        are replaced, so every mode consumer and :meth:`residuals` then work on the refined modes; ``eigen()`` and
+        ``solve()`` give block modes again.  Returns the solver's info record (``converged``, ``iterations``,
+        ``panel_steps``, ``residuals``, ``b``).  The iteration finds the LOWEST modes: it is defined for a solve whose rows
+        start at mode 0, ``subset_by_index=(0, hi)`` or the full block spectrum, and raises ValueError otherwise.
+        """
+        self._need_vectors()
+        if self._first_row != 0:
+            raise ValueError(f"refine() finds the lowest modes and needs a solve whose rows start at mode 0, not at "
+                             f"{self._first_row}: solve(subset_by_index=(0, hi))")
+        if "start" in options:
+            raise ValueError("refine() starts from the block modes")
+        w, v, info = self.operator.lowest_modes(self.nvec, start=self.v[0], tol=tol, **options)
+        self.w, self.v = w[None, :], v[None, :, :]
+        return info
