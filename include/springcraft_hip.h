@@ -683,6 +683,41 @@ int sc_dev_pairs_panel_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, 
                            const double* d_x, double* d_z, int64_t ld, int64_t q, double alpha, double beta,
                            double gamma_c);
 
+/* ---- conjugate gradients on the pair list: (T H T)^+ f for q right-hand sides at once -------------------------------------
+ * The matrix is the one of sc_dev_pairs_panel_f64, from the same network arguments.  Panels d_x, d_r, d_p, d_q are (dim N,
+ * q) with leading dimension ld >= q, columns are the vectors.  d_state holds seven rows of ld 8-byte words, row r of column
+ * c at [r ld + c]: 0 rho = <r, r>, 1 stop = (tol |f|)^2, 2 alpha, 3 beta as doubles; 4 status (0 running, 1 converged, 2
+ * broken down: <p, (T H T) p> was not a finite positive number) and 5 iters as int64; 6 pq = <p, (T H T) p> of the column's
+ * last iteration as a double.  d_work is a workspace of the size
+ * sc_dev_pairs_cg_workspace returns, one partial sum per (four atoms, column).  Device pointers, enqueue only on the
+ * context's stream: no atomics, no host synchronisation inside or between iterations.  Columns q .. ld - 1 of the panels and
+ * of the state are never written.  A column's bits in d_x, d_r, d_p, rho and iters depend on its own right-hand side and the
+ * network only: not on q, ld, the column's position, the other columns, or the iterations enqueued after it stopped; a column
+ * with status != 0 is frozen (its column of d_q is still overwritten).  The right-hand sides must lie in the range of the
+ * matrix (the caller projects the null space out).
+ *
+ * sc_dev_pairs_cg_workspace: No reference counterpart.  *bytes = 8 q ceil(n_atoms / 4).  SC_ERR_INVALID_ARG for a NULL
+ * bytes, a non-positive n_atoms, a negative q or sizes above the limits of the step. */
+int sc_dev_pairs_cg_workspace(int64_t n_atoms, int64_t q, size_t* bytes);
+/* No reference counterpart.  Starts a solve from the projected right-hand sides in d_r: X = 0, P = R, rho = <r, r>, stop =
+ * tol^2 rho, alpha = beta = 0, iters = 0, status 0 -- or 1 at once for |f| = 0 (x = 0 is the solution), 2 for a non-finite
+ * |f|.  The sum <r, r> runs in an order that depends on n_atoms alone.  q = 0 is valid.  SC_ERR_INVALID_ARG before anything
+ * is launched: dim not 1 or 3, a non-positive n_atoms, a negative q, ld < q, q above 4194240, tol not positive, a NULL
+ * pointer, two panels at one address, a workspace that is too small. */
+int sc_dev_pairs_cg_init_f64(sc_ctx* ctx, int64_t n_atoms, int dim, double* d_x, const double* d_r, double* d_p, int64_t ld,
+                             int64_t q, double tol, double* d_state, void* d_work, size_t work_bytes);
+/* No reference counterpart.  Enqueues `iterations` CG iterations on the state sc_dev_pairs_cg_init_f64 left: per column
+ *     Q = (T H T) P (the bits of sc_dev_pairs_panel_f64 with alpha 1, beta 0, gamma_c 0), alpha = rho / <p, q>,
+ *     X += alpha P, R -= alpha Q, rho_new = <r, r>, beta = rho_new / rho, rho = rho_new, iters += 1,
+ *     status 1 when rho_new <= stop, P = R + beta P for the columns still running.
+ * An atom without pairs contributes exactly 0.0 to Q and to the sums.  iterations = 0 and q = 0 are valid.
+ * SC_ERR_INVALID_ARG before anything is launched: what sc_dev_pairs_panel_f64 refuses of the network and of ld and q, a
+ * negative number of iterations, a NULL panel, state or workspace, two panels at one address, a workspace that is too small. */
+int sc_dev_pairs_cg_step_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs,
+                             int64_t k, const double* d_gamma, const int64_t* d_row_start, const double* d_atom_scale,
+                             double* d_x, double* d_r, double* d_p, double* d_q, int64_t ld, int64_t q, double* d_state,
+                             void* d_work, size_t work_bytes, int64_t iterations);
+
 #ifdef __cplusplus
 }
 #endif

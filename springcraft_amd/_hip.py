@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "sc_modes_combine", "sc_dev_mode_combine_f64", "sc_batch_plan_mode_combine_f64",
     "sc_dev_rtb_hessian_f64", "sc_dev_rtb_expand_f64",
     "sc_dev_pairs_apply_f64", "sc_dev_pairs_strain_f64", "sc_dev_pairs_panel_f64",
+    "sc_dev_pairs_cg_workspace", "sc_dev_pairs_cg_init_f64", "sc_dev_pairs_cg_step_f64",
 ]
 
 SC_SEL_FROM_ROW = 0
@@ -251,6 +252,10 @@ def lib():
         "sc_dev_pairs_apply_f64": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, i64, vp, vp]),
         "sc_dev_pairs_strain_f64": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp, i64, vp, i64, vp]),
         "sc_dev_pairs_panel_f64": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, i64, i64, dbl, dbl, dbl]),
+        "sc_dev_pairs_cg_workspace": (i32, [i64, i64, P(C.c_size_t)]),
+        "sc_dev_pairs_cg_init_f64": (i32, [vp, i64, i32, vp, vp, vp, i64, i64, dbl, vp, vp, C.c_size_t]),
+        "sc_dev_pairs_cg_step_f64": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp,
+                                           C.c_size_t, i64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

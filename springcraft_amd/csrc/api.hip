@@ -1552,6 +1552,59 @@ int sc_dev_pairs_panel_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, 
                             alpha, beta, gamma_c);
 }
 
+// ---- conjugate gradients on the pair list (pair_cg.hip) ---------------------------------------------------------------
+static int pairs_cg_panel_check(sc_ctx* ctx, int64_t n_atoms, int64_t ld, int64_t q, const void* const* panels, int count,
+                                const void* d_state, const void* d_work, size_t work_bytes) {
+  if (ld < q) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: the leading dimension %lld is below the %lld columns",
+                                  (long long)ld, (long long)q);
+  if (q > 65535 * (int64_t)64) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: at most 4194240 columns per panel");
+  if (q == 0) return SC_OK;
+  for (int a = 0; a < count; ++a) {
+    if (!panels[a]) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: the X, R, P and Q panels are required with q > 0");
+    for (int b = 0; b < a; ++b)
+      if (panels[a] == panels[b]) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: the X, R, P and Q panels must be distinct");
+  }
+  if (!d_state || !d_work) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: the state and the workspace are required");
+  if (work_bytes < pairs_cg_workspace_bytes(n_atoms, q))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: the workspace holds %zu bytes, %zu are needed", work_bytes,
+                        pairs_cg_workspace_bytes(n_atoms, q));
+  return SC_OK;
+}
+
+int sc_dev_pairs_cg_workspace(int64_t n_atoms, int64_t q, size_t* bytes) {
+  if (!bytes || n_atoms <= 0 || q < 0 || n_atoms > ((int64_t)1 << 32) || q > 65535 * (int64_t)64) return SC_ERR_INVALID_ARG;
+  *bytes = pairs_cg_workspace_bytes(n_atoms, q);
+  return SC_OK;
+}
+
+int sc_dev_pairs_cg_init_f64(sc_ctx* ctx, int64_t n_atoms, int dim, double* d_x, const double* d_r, double* d_p, int64_t ld,
+                             int64_t q, double tol, double* d_state, void* d_work, size_t work_bytes) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  if (dim != 1 && dim != 3) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: dim must be 1 or 3, got %d", dim);
+  if (n_atoms <= 0 || q < 0 || n_atoms > ((int64_t)1 << 32))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: n_atoms must lie in 1 .. 2^32, q must not be negative");
+  if (!(tol > 0.0)) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: tol must be positive");
+  const void* panels[3] = {d_x, d_r, d_p};
+  SC_TRY(pairs_cg_panel_check(ctx, n_atoms, ld, q, panels, 3, d_state, d_work, work_bytes));
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return launch_pairs_cg_init(ctx, n_atoms, dim, d_x, d_r, d_p, ld, q, tol, d_state, (double*)d_work);
+}
+
+int sc_dev_pairs_cg_step_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs,
+                             int64_t k, const double* d_gamma, const int64_t* d_row_start, const double* d_atom_scale,
+                             double* d_x, double* d_r, double* d_p, double* d_q, int64_t ld, int64_t q, double* d_state,
+                             void* d_work, size_t work_bytes, int64_t iterations) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  SC_TRY(pairs_network_check(ctx, d_coord, n_atoms, dim, d_pairs, k, d_gamma, d_p, q));
+  if (k > 0 && !d_row_start) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: row starts are required with k > 0");
+  if (iterations < 0) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "pairs: the number of iterations must not be negative");
+  const void* panels[4] = {d_x, d_r, d_p, d_q};
+  SC_TRY(pairs_cg_panel_check(ctx, n_atoms, ld, q, panels, 4, d_state, d_work, work_bytes));
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  return launch_pairs_cg_step(ctx, d_coord, n_atoms, dim, d_pairs, k, d_gamma, d_row_start, d_atom_scale, d_x, d_r, d_p,
+                              d_q, ld, q, d_state, (double*)d_work, iterations);
+}
+
 void sc_batch_plan_destroy(sc_batch_plan* plan) {
   if (!plan) return;
   (void)hipSetDevice(plan->ctx->device);

@@ -393,6 +393,17 @@ int launch_pairs_panel(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int 
                        const double* d_gamma, const int64_t* d_row_start, const double* d_atom_scale, const double* d_x,
                        double* d_z, int64_t ld, int64_t q, double alpha, double beta, double gamma_c);
 
+// (pair_cg.hip) Conjugate gradients on the same matrix for q columns at once; the state is seven rows of ld words (rho, stop,
+// alpha, beta, status, iters, pq), the workspace pairs_cg_workspace_bytes(n_atoms, q).  init: X = 0, P = R, rho, stop, status;
+// step: `iterations` iterations of five kernels each.  No atomics, no host synchronisation; enqueue only.
+size_t pairs_cg_workspace_bytes(int64_t n_atoms, int64_t q);
+int launch_pairs_cg_init(sc_ctx* ctx, int64_t n_atoms, int dim, double* d_x, const double* d_r, double* d_p, int64_t ld,
+                         int64_t q, double tol, double* d_state, double* d_work);
+int launch_pairs_cg_step(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs, int64_t k,
+                         const double* d_gamma, const int64_t* d_row_start, const double* d_atom_scale, double* d_x,
+                         double* d_r, double* d_p, double* d_q, int64_t ld, int64_t q, double* d_state, double* d_work,
+                         int64_t iterations);
+
 // Raises a kernel's dynamic LDS limit (hipFuncAttributeMaxDynamicSharedMemorySize) once per (device, kernel).  The
 // attribute belongs to the device that is current when it is set: a function-local static done-flag (rounds 2-5) served
 // the first device a process used and left contexts on a second GPU with refused launches.  Returns

@@ -29,16 +29,9 @@
 // first atom is not i or whose second lies outside 0 .. N - 1 are skipped, as in k_pairs_apply.  Z is read only when
 // gamma_c != 0 (with gamma_c = 0 it is overwritten, whatever it held); lanes beyond q load pair data like the others,
 // read no column beyond q and write nothing, so the columns q .. ld - 1 of Z keep their bits.
-#include "common.h"
+#include "pair_walk.h"   // the walk itself, shared with k_cg_apply_dot (pair_cg.hip)
 
 namespace {
-
-__device__ __forceinline__ double lane_value(double v, int l) {   // v of lane l (uniform) in every lane
-  const long long bits = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)bits, l);
-  const int hi = __builtin_amdgcn_readlane((int)(bits >> 32), l);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
 
 template <int DIM>
 __global__ __launch_bounds__(256) void k_pairs_panel(const double* __restrict__ coord, long long n_atoms,
@@ -53,23 +46,9 @@ __global__ __launch_bounds__(256) void k_pairs_panel(const double* __restrict__ 
   if (i >= n_atoms) return;
   const long long col = (long long)blockIdx.y * 64 + lane;
   const bool live = col < q;
-  long long lo = 0, hi = 0;
-  if (k > 0) {
-    lo = row_start[i];
-    hi = row_start[i + 1];
-    if (lo < 0) lo = 0;
-    if (hi > k) hi = k;
-  }
-
   const double ti = scale ? scale[i] : 1.0;
-  double ci[3] = {0.0, 0.0, 0.0};
-  if (DIM == 3 && lo < hi) {
-    ci[0] = coord[3 * i + 0];
-    ci[1] = coord[3 * i + 1];
-    ci[2] = coord[3 * i + 2];
-  }
   // a lane beyond q reads the chunk's first column in place of its own (the same addresses, no further traffic) and stores
-  // nothing: the loop below then has no divergent branch
+  // nothing: the walk then has no divergent branch
   const double* __restrict__ xc = x + (live ? col : (long long)blockIdx.y * 64);
   double xi[DIM], ui[DIM], s[DIM];
 #pragma unroll
@@ -78,73 +57,7 @@ __global__ __launch_bounds__(256) void k_pairs_panel(const double* __restrict__ 
     ui[c] = ti * xi[c];
     s[c] = 0.0;
   }
-
-  for (long long c0 = lo; c0 < hi; c0 += 64) {
-    // this lane's pair of the 64: j, gamma, t_j, n_p (skipped: an entry whose first atom is not i or whose second lies
-    // outside 0 .. N - 1)
-    const long long p = c0 + lane;
-    bool valid = p < hi;
-    long long j = 0;
-    double g = 0.0, tj = 1.0, n[3] = {0.0, 0.0, 0.0};
-    if (valid) {
-      const long long pi = pairs[2 * p];
-      j = pairs[2 * p + 1];
-      valid = pi == i && j >= 0 && j < n_atoms;
-      if (!valid) j = 0;
-    }
-    if (valid) {
-      g = gamma[p];
-      if (scale) tj = scale[j];
-      if (DIM == 3) {
-        const double dx = coord[3 * j + 0] - ci[0];
-        const double dy = coord[3 * j + 1] - ci[1];
-        const double dz = coord[3 * j + 2] - ci[2];
-        const double len = sqrt((dx * dx + dy * dy) + dz * dz);
-        n[0] = dx / len;   // (two atoms at one position: 0 / 0 = NaN, as the Hessian entry)
-        n[1] = dy / len;
-        n[2] = dz / len;
-      }
-    }
-    const unsigned long long listed = __ballot(valid);
-    const int count = (int)(hi - c0 < 64 ? hi - c0 : 64);
-
-    // the pair of lane l (uniform; every lane of the wavefront is active here) from scalar registers; j < 2^32 (the entry
-    // refuses more atoms)
-    auto add_pair = [&](int l) {
-      const long long jl = (long long)(unsigned int)__builtin_amdgcn_readlane((int)j, l);
-      const double gl = lane_value(g, l);
-      const double tl = lane_value(tj, l);
-      if (DIM == 3) {
-        const double n0 = lane_value(n[0], l), n1 = lane_value(n[1], l), n2 = lane_value(n[2], l);
-        const double ex = ui[0] - tl * xc[(3 * jl + 0) * ld];
-        const double ey = ui[1] - tl * xc[(3 * jl + 1) * ld];
-        const double ez = ui[2] - tl * xc[(3 * jl + 2) * ld];
-        const double e = (n0 * ex + n1 * ey) + n2 * ez;
-        const double ge = gl * e;
-        s[0] += ge * n0;
-        s[1] += ge * n1;
-        s[2] += ge * n2;
-      } else {
-        const double e = ui[0] - tl * xc[jl * ld];
-        s[0] += gl * e;
-      }
-    };
-    // All loops add the listed pairs in list order.  The first, for a chunk without a skipped row (every chunk of a
-    // checked list), takes four pairs per step without a branch between them, so that their gathers are in flight
-    // together (unrolled by hand: the compiler does not unroll a loop of convergent operations with a remainder).
-    if (listed == (count == 64 ? ~0ull : (1ull << count) - 1)) {
-      int l = 0;
-      for (; l + 4 <= count; l += 4) {
-        add_pair(l);
-        add_pair(l + 1);
-        add_pair(l + 2);
-        add_pair(l + 3);
-      }
-      for (; l < count; ++l) add_pair(l);
-    } else {
-      for (unsigned long long rest = listed; rest; rest &= rest - 1) add_pair(__builtin_ctzll(rest));
-    }
-  }
+  pair_walk<DIM>(coord, n_atoms, pairs, k, gamma, row_start, scale, xc, ld, i, lane, ui, s);
 
   if (!live) return;
   double* __restrict__ zc = z + col;

@@ -13,7 +13,9 @@ and the directed pair p = (i, j) with constant ``gamma_p`` and direction ``n_p =
 
 ``panel_step`` is one fused step ``Z <- alpha (T H T) X + beta X + gamma_c Z`` on column panels (``csrc/pair_panel.hip``),
 ``lowest_modes`` the Chebyshev-filtered subspace iteration built on it (:mod:`springcraft_amd.iterative`): the exact lowest
-eigenpairs of the matrix to a requested tolerance, in memory of order (dim N, k).
+eigenpairs of the matrix to a requested tolerance, in memory of order (dim N, k).  ``solve`` is the inverse direction,
+``(T H T)^+ f`` by conjugate gradients on the range of the matrix (``csrc/pair_cg.hip``, :func:`iterative.conjugate_gradient`);
+``linear_response`` and ``covariance_columns`` are its consumers.
 
 The constants must be symmetric, ``gamma(i, j) = gamma(j, i)``: the reference's rule for asymmetric ones (off-diagonal
 from ``gamma(i, j)``, diagonal summed over the first index) has no energy reading, and :class:`PairOperator` raises
@@ -406,3 +408,154 @@ class PairOperator:
                                                                 torch.from_numpy(x0).to(self.device), k, b, tol=tol,
                                                                 degree=int(degree), max_iter=int(max_iter))
             return w.contiguous(), x.T.contiguous(), info
+
+    # ---- the pseudo-inverse by conjugate gradients (iterative.py, csrc/pair_cg.hip) --------------------------------------
+    #: The most columns one CG run holds: two chunks of 64 lanes, the width the panel step was measured at.  A solve of q
+    #: right-hand sides runs ceil(q / 128) times on five panels (X, R, P, Q and one temporary of the projections) of
+    #: ``8 * dim n * 128`` bytes each -- 770 MB at n = 50 000 -- whatever q is.
+    SOLVE_COLUMNS = 128
+
+    def null_space(self):
+        """The orthonormal null space of a connected network, a CUDA tensor (dim n, z) (:func:`iterative.null_space`); cached."""
+        if getattr(self, "_null", None) is None:
+            from .iterative import null_space
+
+            coord = self.n_atoms if self._coord is None else self._coord.cpu().numpy()
+            scale = None if self._scale is None else self._scale.cpu().numpy()
+            self._null = self.torch.from_numpy(null_space(coord, self.dim, scale)).to(self.device)
+        return self._null
+
+    def _cg_callables(self, q):
+        """(init, step) of :func:`iterative.conjugate_gradient` for panels of q columns on the C entries."""
+        torch, L, p = self.torch, self._L, self._p
+        size = C.c_size_t()
+        if L.sc_dev_pairs_cg_workspace(self.n_atoms, q, C.byref(size)) != _hip.SC_OK:
+            raise ValueError(f"no CG workspace for {self.n_atoms} atoms and {q} columns")
+        work = torch.empty(max(size.value // 8, 1), dtype=torch.float64, device=self.device)
+        state = torch.zeros((7, max(q, 1)), dtype=torch.float64, device=self.device)
+        panels, have = {}, self.n_pairs > 0
+
+        def init(r, tol):
+            panels["R"] = r
+            panels["X"], panels["P"], panels["Q"] = (torch.empty_like(r) for _ in range(3))
+            self.ctx.check(L.sc_dev_pairs_cg_init_f64(self.ctx.handle, self.n_atoms, self.dim, p(panels["X"]), p(r),
+                                                      p(panels["P"]), q, q, float(tol), p(state), p(work), size.value))
+
+            def read():
+                host = state.cpu()   # (the synchronisation)
+                return host[4].view(torch.int64).numpy().copy(), host[5].view(torch.int64).numpy().copy(), host[0].numpy().copy()
+
+            return panels["X"], read
+
+        def step(iterations):
+            self.ctx.check(L.sc_dev_pairs_cg_step_f64(
+                self.ctx.handle, p(self._coord), self.n_atoms, self.dim, p(self._pairs) if have else None, self.n_pairs,
+                p(self._gamma) if have else None, p(self._row_start), p(self._scale), p(panels["X"]), p(panels["R"]),
+                p(panels["P"]), p(panels["Q"]), q, q, p(state), p(work), size.value, int(iterations)))
+
+        return init, step
+
+    def solve(self, f, tol=1e-8, max_iter=2000, check_every=10, deflate=None):
+        """
+        The minimum-norm solutions ``x = (T H T)^+ f`` by conjugate gradients on the range of the matrix
+        (:func:`iterative.conjugate_gradient`, ``csrc/pair_cg.hip``): ``(x, info)``.  ``f`` is (dim n,) or (q, dim n), an array
+        or a tensor, rows in the coordinates of the matrix; ``x`` is a CUDA tensor of the same shape.  No (dim n, dim n) matrix
+        exists; the right-hand sides run in chunks of at most :attr:`SOLVE_COLUMNS` columns, which bounds the memory.
+
+        The null space -- six rigid-body fields, or the constant vector, each divided by ``t`` -- is projected out of ``f``
+        and ``x``; a network of several parts has more zero modes than these, and a right-hand side with a component along
+        them does not converge.  A column stops at ``|f_p - H x| <= tol |f_p|``, ``f_p`` the projected right-hand side, which
+        bounds its error by ``tol |f_p| / lambda_nz``, ``lambda_nz`` the lowest non-zero eigenvalue.  The status is read on
+        the host every ``check_every`` iterations, the only synchronisations; at most ``max_iter`` iterations run.
+
+        ``deflate = (w, v)``: exact eigenpairs as :meth:`lowest_modes` returns them, the trivial rows first; their part of
+        the solution is added in closed form and the iteration runs on the rest of the spectrum, condition ``b / w[-1]``
+        in place of ``b / lambda_nz``.  What the modes' own residuals leave of ``f_p - H x`` above ``tol |f_p|`` is removed
+        by a short second iteration (:func:`iterative.conjugate_gradient`), so the stopping rule holds for computed modes.
+
+        ``info``: ``iterations`` (q,), ``residuals`` (q,) relative to ``|f_p|``, ``status`` (q,) (0 still running, 1
+        converged, 2 broken down), ``converged``, ``b``, ``tol``.  Running out of iterations or a breakdown returns what
+        there is with ``converged = False``; nothing is raised.  The same arguments give the same bits, and without
+        deflation a right-hand side's solution has the same bits alone and in any batch.
+        """
+        from . import iterative
+
+        shape = tuple(f.shape) if hasattr(f, "shape") else np.shape(f)
+        if len(shape) not in (1, 2) or shape[-1] != self.m:
+            raise ValueError(f"Expected right-hand sides of shape ({self.m},) or (q, {self.m}), got {shape}")
+        tol, max_iter, check_every, deflate = iterative.checked_solve(self.m, tol, max_iter, check_every, deflate)
+        torch = self.torch
+        rows, single = self._rows(f)   # (every refusal above needs no device)
+        b = self.spectral_bound()
+        with torch.cuda.device(self.device):
+            if deflate is not None:
+                deflate = tuple((t if isinstance(t, torch.Tensor) else torch.from_numpy(np.asarray(t, dtype=np.float64)))
+                                .to(device=self.device, dtype=torch.float64) for t in deflate)
+            null = self.null_space()
+            out = self._empty((len(rows), self.m))
+            infos = []
+            for lo in range(0, len(rows), self.SOLVE_COLUMNS):
+                chunk = rows[lo: lo + self.SOLVE_COLUMNS]
+                init, step = self._cg_callables(len(chunk))
+                panel = chunk.T.clone(memory_format=torch.contiguous_format)   # (the driver overwrites it)
+                x, info = iterative.conjugate_gradient(init, step, panel, null, b, tol=tol, max_iter=max_iter,
+                                                       check_every=check_every, deflate=deflate,
+                                                       apply=lambda t: self.panel_step(t, torch.empty_like(t), 1.0, 0.0, 0.0))
+                out[lo: lo + len(chunk)] = x.T
+                infos.append(info)
+        info = {key: np.concatenate([i[key] for i in infos]) if infos else np.zeros(0, dtype=kind)
+                for key, kind in (("iterations", np.int64), ("residuals", np.float64), ("status", np.int64))}
+        info.update(converged=all(i["converged"] for i in infos), b=b, tol=tol)
+        return (out[0] if single else out), info
+
+    def linear_response(self, force, atom_scale=None, **solve_options):
+        """
+        The displacement a force induces (linear response theory, :func:`nma.linear_response`) from the exact pseudo-inverse,
+        ``s (T H T)^+ s f`` with ``s`` the operator's own ``t`` repeated per coordinate -- the Cartesian response of a
+        mass-weighted network -- or ``atom_scale`` (n,) when given.  ``force`` is (n, 3), (3n,) or (q, n, 3); returns a CUDA
+        tensor (n, 3) or (q, n, 3) and the ``info`` of :meth:`solve`, whose options ``solve_options`` are.
+        """
+        if self.dim != 3:
+            raise ValueError("linear_response needs the Hessian, dim 3")
+        n = self.n_atoms
+        shape = tuple(force.shape) if hasattr(force, "shape") else np.shape(force)
+        if shape not in ((n, 3), (3 * n,)) and not (len(shape) == 3 and shape[1:] == (n, 3)):
+            raise ValueError(f"Expected a force of shape ({n}, 3), ({3 * n},) or (q, {n}, 3), got {shape}")
+        if atom_scale is not None and tuple(np.shape(atom_scale)) != (n,):
+            raise IndexError(f"{tuple(np.shape(atom_scale))} scale factors for {n} atoms given")
+        from . import iterative
+
+        iterative.checked_solve(self.m, solve_options.get("tol", 1e-8), solve_options.get("max_iter", 2000),
+                                solve_options.get("check_every", 10), solve_options.get("deflate"))
+        torch = self.torch
+        if not isinstance(force, torch.Tensor):
+            force = torch.from_numpy(np.ascontiguousarray(force, dtype=np.float64))
+        f = force.to(device=self.device, dtype=torch.float64).reshape(-1, 3 * n)
+        if atom_scale is None:
+            s = self._scale
+        elif isinstance(atom_scale, torch.Tensor):
+            s = atom_scale.to(device=self.device, dtype=torch.float64)
+        else:
+            s = torch.from_numpy(np.asarray(atom_scale, dtype=np.float64)).to(self.device)
+        s3 = None if s is None else s.repeat_interleave(3)[None, :]
+        x, info = self.solve(f if s3 is None else f * s3, **solve_options)
+        if s3 is not None:
+            x = x * s3
+        return (x.reshape(-1, n, 3) if len(shape) == 3 else x.reshape(n, 3)), info
+
+    def covariance_columns(self, atom_index, **solve_options):
+        """
+        The rows ``dim a .. dim a + dim - 1`` of the pseudo-inverse ``(T H T)^+`` for the listed atoms, a CUDA tensor
+        (dim len(atom_index), dim n), and the ``info`` of :meth:`solve`: the exact covariance of these atoms with every atom,
+        so their mean-square fluctuations (the traces of the diagonal blocks), their rows of a perturbation response scan
+        and their cross-correlations, without the (dim n, dim n) matrix.
+        """
+        idx = np.asarray(atom_index)
+        if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+            raise IndexError("atom_index must be a list of integer atom indices")
+        if idx.size and (idx.min() < 0 or idx.max() >= self.n_atoms):
+            raise IndexError(f"atom_index holds an atom outside 0..{self.n_atoms - 1}")
+        rows = (self.dim * idx.astype(np.int64)[:, None] + np.arange(self.dim)[None, :]).reshape(-1)
+        unit = np.zeros((len(rows), self.m))
+        unit[np.arange(len(rows)), rows] = 1.0
+        return self.solve(unit, **solve_options)

@@ -183,6 +183,7 @@ class RTB(_BatchSolver):
         self._layout = _UniformLayout(1, n, 3)
         self.matrix = self.w = self.v = self._u = None
         self._operator = None
+        self._refined = False   # whether w and v are exact eigenpairs: after a refine() that converged
 
         # contacts from the device scan, constants from the force field on the host (interaction.py:96)
         ff_desc, patch, _ = device_plan(force_field)
@@ -283,6 +284,7 @@ class RTB(_BatchSolver):
                 raise ValueError(f"subset_by_index {tuple(subset_by_index)} outside 0..{self.nr - 1}")
             self.subset, self.nvec, self._first_row = (lo, hi), hi - lo + 1, lo
         self.assemble()
+        self._refined = False   # (block modes again)
         return self.eigh()
 
     def eigen(self, subset_by_index=None):
@@ -360,4 +362,19 @@ class RTB(_BatchSolver):
             raise ValueError("refine() starts from the block modes")
         w, v, info = self.operator.lowest_modes(self.nvec, start=self.v[0], tol=tol, **options)
         self.w, self.v = w[None, :], v[None, :, :]
+        self._refined = bool(info["converged"])
         return info
+
+    def exact_response(self, force, tol=1e-8, deflate=True, **options):
+        """
+        The Cartesian displacement a force induces from the EXACT pseudo-inverse of the full Hessian,
+        :meth:`PairOperator.linear_response` on :attr:`operator` (conjugate gradients on the pair list): ``(x, info)``, ``x`` a
+        CUDA tensor (n, 3) or (q, n, 3) for a force (n, 3), (3n,) or (q, n, 3).  :meth:`linear_response` sums over the solved
+        modes only and leaves out every mode above them.  With ``deflate`` the solver's own ``w`` and ``v`` serve as the
+        deflation space when they are exact eigenpairs, that is after a :meth:`refine` that converged; block modes are
+        not, and the solve then runs undeflated.  ``options``: ``max_iter``, ``check_every``.
+        """
+        if "deflate" in options:
+            raise ValueError("exact_response() deflates with the solver's own modes: deflate=True or False")
+        space = (self.w[0], self.v[0]) if deflate and self._refined and self.v is not None else None
+        return self.operator.linear_response(force, tol=tol, deflate=space, **options)
