@@ -23,9 +23,38 @@ int sc_dbg_gemm_bench(sc_ctx* ctx, int m, int n, int k, int mode, int tile, int 
 
 /* ONE launch of one GEMM record on host data (a, b laid out as in sc_dbg_gemm_bench for `mode`; c: m x n column-major,
  * in / out; with split_k > 1 the K slices are summed into c on the host and beta must be 0; lower_grid as the launcher
- * takes it).  The GPU unit tests of the launch paths compare the result with NumPy.  tests/test_gemm_gpu.py */
+ * takes it).  alpha == 0 with beta != 0 is SC_ERR_INVALID_ARG: the kernel does not take such a record.  The GPU unit
+ * tests of the launch paths compare the result with NumPy.  tests/test_gemm_gpu.py */
 int sc_dbg_gemm_host(sc_ctx* ctx, const double* a, const double* b, double* c, int m, int n, int k, int mode, int tile,
                      int split_k, double alpha, double beta, int lower_grid);
+
+/* One record of a grouped GEMM launch as the host describes it: the kernel's record (GemmDesc, csrc/gemm_f64.h) with
+ * element offsets in place of pointers -- a, b, c into an arena of doubles, a_kidx, b_kidx, c_jidx into an arena of ints
+ * (-1: no list).  Every other field is handed to the kernel unchanged.  144 bytes, no padding. */
+typedef struct sc_dbg_gemm_record {
+  long long a, b, c;
+  long long a_kidx, b_kidx, c_jidx;
+  long long sa_i, sa_k, sb_k, sb_j, ldc, split_stride;
+  double alpha, beta;
+  int m, n, k;
+  int lower_only, row_off, col_off;
+  int a_tri;
+  int reserved;
+} sc_dbg_gemm_record;
+
+/* ONE grouped launch (launch_gemm_f64) of `count` records on host data: triangular operands, gather lists, several
+ * records of different sizes, sub-matrix views, record lists longer than one grid.  arena (arena_len doubles, in / out)
+ * is copied whole to the device and whole back; idx (idx_len ints) holds the index lists.  count, max_m, max_n, split_k,
+ * gather, tri, layout (0 = A m-contiguous / B k-contiguous, 1 = both k-contiguous, 2 = A m-contiguous / B n-contiguous)
+ * and lower_grid as the launcher takes them; tile 10..13 as sc_dbg_gemm_host (gather launches: 12 = 128 x 64, 13 =
+ * 64 x 64, else by size).  With split_k > 1 the K slices stay where the kernel wrote them (c + s * split_stride).
+ * SC_ERR_INVALID_ARG, and no launch, when a record could make the kernel touch an address outside its arena (offsets,
+ * strides, list entries), when its unit strides do not match the layout, when it carries a_tri or lists the launch does
+ * not read, or for alpha == 0 with beta != 0.  The device copy of the arena lies between two guard areas; a launch that
+ * changed them is SC_ERR_HIP.  tests/test_gemm_records_gpu.py */
+int sc_dbg_gemm_records_host(sc_ctx* ctx, double* arena, long long arena_len, const int* idx, long long idx_len,
+                             const sc_dbg_gemm_record* recs, int count, int max_m, int max_n, int split_k, int gather,
+                             int tri, int layout, int lower_grid, int tile);
 
 /* `count` products of ONE shape on host data through k_gemm3, the role-split persistent kernel of the short-K updates
  * (csrc/gemm3.hip), whatever their size: a count x (m x k) column-major; b count x (k x n) column-major (layout 0,

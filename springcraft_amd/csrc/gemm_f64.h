@@ -6,6 +6,9 @@
 // arbitrary strides, so NN / NT / TN products and sub-matrix views need no copies.  One of
 // (sa_i, sa_k) and one of (sb_k, sb_j) must be 1 (the loader runs its lanes along that axis).
 //
+// alpha must not be 0 when beta != 0: the kernel carries beta * C through its accumulators as (beta / alpha) * C and
+// would store 0 instead of beta * C.  No caller scales C alone; the debug entries refuse such a record.
+//
 // Problems are described by GemmDesc records in DEVICE memory, so sizes may be produced by a
 // previous kernel (the divide & conquer merges: the number of non-deflated eigenvalues is only
 // known on the device).  blockIdx.z selects the record; blocks outside m x n exit at once.

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "gemm_f64.h"
+#include "springcraft_hip_debug.h"   // sc_dbg_gemm_record
 
 namespace {
 
@@ -111,7 +112,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm2(const GemmDesc* __restrict__ d
   const int M = D.m, N = D.n, K = D.k;
   const int m0 = t_x * BM, n0 = t_y * BN;
   if (m0 >= M || n0 >= N) return;   // K == 0 still runs: it stores beta*C (zeros for beta = 0)
-  if (D.lower_only && (m0 + BM - 1 + D.row_off) < (n0 + D.col_off)) return;
+  // (lower_only = 2 stores up to (row | 1): with an odd row_off the tile's last row reaches one column further)
+  if (D.lower_only && ((m0 + BM - 1 + D.row_off) | (D.lower_only == 2 ? 1 : 0)) < (n0 + D.col_off)) return;
 
   GEMM_STAMP(t_start)
   int k_begin = 0, k_end = K;
@@ -472,7 +474,9 @@ int launch_gemm_f64(sc_ctx* ctx, const GemmDesc* d_desc, int count, int max_m, i
     const long long cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
     const long long gz = (long long)count * split_k;
     if (gz > 65535) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "GEMM launch with %lld records x slices (max 65535)", gz);
-    const bool big = max_m > 64 && (long long)((max_m + 127) / 128) * ((max_n + 63) / 64) * gz >= 2 * cus;
+    const bool by_size = max_m > 64 && (long long)((max_m + 127) / 128) * ((max_n + 63) / 64) * gz >= 2 * cus;
+    // (the debug entries' tile override picks the instantiation whatever the size: 2 = 128 x 64, 3 = 64 x 64)
+    const bool big = g_gemm2_force_tile == 2 ? true : (g_gemm2_force_tile == 3 ? false : by_size);
     const int bm = big ? 128 : 64;
     dim3 grid((unsigned)((max_m + bm - 1) / bm), (unsigned)((max_n + 63) / 64), (unsigned)gz);
     if (big) launch_gemm2_inst<128, 64, true, false, false, true>(st, grid, d_desc, split_k);
@@ -608,11 +612,13 @@ extern "C" int sc_dbg_gemm_bench(sc_ctx* ctx, int m, int n, int k, int mode, int
 
 // ---- debug entry point for the GPU unit tests of the launch paths (tests/test_gemm_gpu.py): ONE launch of one record
 // on host data.  a, b as sc_dbg_gemm_bench lays them out for `mode`; c: m x n column-major, in / out (with split_k > 1
-// the slices are summed into c on the host and beta must be 0).  lower_grid as launch_gemm_f64 takes it.
+// the slices are summed into c on the host and beta must be 0).  lower_grid as launch_gemm_f64 takes it.  alpha == 0
+// with beta != 0 is refused (gemm_f64.h).
 extern "C" int sc_dbg_gemm_host(sc_ctx* ctx, const double* a, const double* b, double* c, int m, int n, int k, int mode,
                                 int tile, int split_k, double alpha, double beta, int lower_grid) {
   if (!ctx || !a || !b || !c || m <= 0 || n <= 0 || k < 0 || split_k < 1) return SC_ERR_INVALID_ARG;
   if (split_k > 1 && beta != 0.0) return SC_ERR_INVALID_ARG;
+  if (alpha == 0.0 && beta != 0.0) return SC_ERR_INVALID_ARG;   // not a record the kernel takes (gemm_f64.h)
   SC_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const size_t ea = (size_t)m * std::max(k, 1), eb = (size_t)std::max(k, 1) * n, ec = (size_t)m * n * split_k;
@@ -657,6 +663,130 @@ extern "C" int sc_dbg_gemm_host(sc_ctx* ctx, const double* a, const double* b, d
           c[i] = sum;
         }
     }
+  }
+  (void)hipFree(base);
+  return rc;
+}
+
+// ---- debug entry point for the GPU unit tests of the record-level launch paths (tests/test_gemm_records_gpu.py): ONE
+// launch_gemm_f64 call on records the host describes -- triangular operands, gather lists, grouped launches, sub-matrix
+// views, chunked record lists.  Operands live in one arena of doubles (in / out: copied whole to the device and whole
+// back), index lists in one arena of ints; a record holds element offsets into them in place of pointers.  Nothing is
+// launched unless every address a record can make the kernel touch lies inside its arena.
+static_assert(sizeof(sc_dbg_gemm_record) == 144, "the tests mirror this layout as a NumPy record type");
+namespace {
+constexpr long long kRecGuard = 4096;                // doubles in front of and behind the device copy of the arena
+constexpr unsigned long long kRecGuardBits = 0x7ff8a5a5a5a5a5a5ull;   // a quiet NaN that no operand holds
+
+// nullptr, or what is wrong with record r of the launch
+const char* gemm_record_problem(const sc_dbg_gemm_record& R, long long arena_len, const int* idx, long long idx_len,
+                                int max_m, int max_n, int split_k, bool gather, bool tri, int layout, bool lower_grid) {
+  typedef __int128 wide;
+  if (R.m < 0 || R.n < 0 || R.k < 0) return "negative size";
+  if (R.m > max_m || R.n > max_n) return "larger than max_m x max_n";
+  if (R.sa_i < 0 || R.sa_k < 0 || R.sb_k < 0 || R.sb_j < 0 || R.ldc < 0 || R.split_stride < 0) return "negative stride";
+  if (layout == kGemmAmBk && (R.sa_i != 1 || R.sb_k != 1)) return "strides do not match layout kGemmAmBk";
+  if (layout == kGemmAkBk && (R.sa_k != 1 || R.sb_k != 1)) return "strides do not match layout kGemmAkBk";
+  if (layout == kGemmAmBn && (R.sa_i != 1 || R.sb_j != 1)) return "strides do not match layout kGemmAmBn";
+  if (R.lower_only < 0 || R.lower_only > 2) return "lower_only not 0, 1 or 2";
+  if (R.a_tri < 0 || R.a_tri > 2 || (R.a_tri != 0 && !tri)) return "a_tri without a tri launch, or not 0, 1 or 2";
+  if (!gather && (R.a_kidx != -1 || R.b_kidx != -1 || R.c_jidx != -1)) return "index list without a gather launch";
+  if (R.alpha == 0.0 && R.beta != 0.0) return "alpha == 0 with beta != 0";
+  if (!(R.alpha == R.alpha) || !(R.beta == R.beta)) return "alpha or beta is NaN";
+  if (lower_grid && (R.lower_only == 0 || R.row_off != 0 || R.col_off != 0)) return "lower_grid needs lower_only records without offsets";
+  if (R.a < 0 || R.a > arena_len || R.b < 0 || R.b > arena_len || R.c < 0 || R.c > arena_len) return "operand offset outside the arena";
+  // index lists: [off, off + length) inside the int arena, entries >= 0; *last = the largest entry
+  auto list = [&](long long off, int len, long long* last) -> bool {
+    *last = (long long)len - 1;
+    if (off == -1) return true;
+    if (off < 0 || off > idx_len || (long long)len > idx_len - off) return false;
+    long long mx = -1;
+    for (int t = 0; t < len; ++t) {
+      if (idx[off + t] < 0) return false;
+      mx = std::max<long long>(mx, idx[off + t]);
+    }
+    *last = mx;
+    return true;
+  };
+  long long ka = 0, kb = 0, jc = 0;
+  if (!list(R.a_kidx, R.k, &ka) || !list(R.b_kidx, R.k, &kb) || !list(R.c_jidx, R.n, &jc))
+    return "index list outside the int arena, or with a negative entry";
+  if (R.m == 0 || R.n == 0) return nullptr;   // every workgroup of the record exits before it touches an operand
+  if (R.ldc < R.m) return "ldc < m";
+  if (R.k > 0) {
+    if ((wide)R.a + (wide)(R.m - 1) * R.sa_i + (wide)ka * R.sa_k >= (wide)arena_len) return "A reaches outside the arena";
+    if ((wide)R.b + (wide)kb * R.sb_k + (wide)(R.n - 1) * R.sb_j >= (wide)arena_len) return "B reaches outside the arena";
+  }
+  if ((wide)R.c + (wide)(split_k - 1) * R.split_stride + (wide)jc * R.ldc + (R.m - 1) >= (wide)arena_len)
+    return "C reaches outside the arena";
+  return nullptr;
+}
+}  // namespace
+
+extern "C" int sc_dbg_gemm_records_host(sc_ctx* ctx, double* arena, long long arena_len, const int* idx, long long idx_len,
+                                        const sc_dbg_gemm_record* recs, int count, int max_m, int max_n, int split_k,
+                                        int gather, int tri, int layout, int lower_grid, int tile) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  if (!arena || arena_len <= 0 || arena_len > (1ll << 34) || idx_len < 0 || idx_len > (1ll << 34) || (idx_len > 0 && !idx) ||
+      !recs || count < 0 || count > (1 << 24) || max_m <= 0 || max_n <= 0 || split_k < 1 || split_k > 65535)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "GEMM records: bad launch argument");
+  if (tile < 10 || tile > 13) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "tile id %d (10 .. 13)", tile);
+  if (layout < 0 || layout > 2 || (gather && (tri || layout != kGemmAmBk)) || (tri && layout == kGemmAmBn))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "GEMM records: no kernel for layout %d, gather %d, tri %d", layout, gather, tri);
+  if (lower_grid && (layout != kGemmAmBn || tri || gather || split_k > 1 || max_m != max_n))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "GEMM records: lower_grid is for square launches of layout kGemmAmBn without split-K");
+  for (int r = 0; r < count; ++r) {
+    const char* what = gemm_record_problem(recs[r], arena_len, idx, idx_len, max_m, max_n, split_k, gather != 0, tri != 0,
+                                           layout, lower_grid != 0);
+    if (what) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "GEMM record %d: %s", r, what);
+  }
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  // device image: [guard | arena | guard] [records] [index lists], each part on a 256-byte boundary
+  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+  const size_t b_arena = up((size_t)(arena_len + 2 * kRecGuard) * 8), b_desc = up((size_t)std::max(count, 1) * sizeof(GemmDesc));
+  const size_t b_idx = up((size_t)std::max<long long>(idx_len, 1) * 4);
+  char* base = nullptr;
+  SC_HIP(ctx, hipMalloc((void**)&base, b_arena + b_desc + b_idx));
+  double* d_front = (double*)base;
+  double* d_arena = d_front + kRecGuard;
+  double* d_back = d_arena + arena_len;
+  GemmDesc* d_desc = (GemmDesc*)(base + b_arena);
+  int* d_idx = (int*)(base + b_arena + b_desc);
+  int rc = SC_OK;
+  auto fail = [&](hipError_t e) { if (e != hipSuccess && rc == SC_OK) rc = sc_set_error(ctx, SC_ERR_HIP, "%s", hipGetErrorString(e)); };
+  std::vector<unsigned long long> guard((size_t)kRecGuard, kRecGuardBits), got((size_t)kRecGuard);
+  fail(hipMemcpy(d_front, guard.data(), (size_t)kRecGuard * 8, hipMemcpyHostToDevice));
+  fail(hipMemcpy(d_back, guard.data(), (size_t)kRecGuard * 8, hipMemcpyHostToDevice));
+  fail(hipMemcpy(d_arena, arena, (size_t)arena_len * 8, hipMemcpyHostToDevice));
+  if (idx_len > 0) fail(hipMemcpy(d_idx, idx, (size_t)idx_len * 4, hipMemcpyHostToDevice));
+  std::vector<GemmDesc> h_desc((size_t)count);
+  for (int r = 0; r < count; ++r) {
+    const sc_dbg_gemm_record& R = recs[r];
+    GemmDesc& D = h_desc[(size_t)r];
+    D = GemmDesc{};
+    D.a = d_arena + R.a; D.b = d_arena + R.b; D.c = d_arena + R.c;
+    D.m = R.m; D.n = R.n; D.k = R.k;
+    D.sa_i = R.sa_i; D.sa_k = R.sa_k; D.sb_k = R.sb_k; D.sb_j = R.sb_j; D.ldc = R.ldc;
+    D.alpha = R.alpha; D.beta = R.beta;
+    D.a_kidx = R.a_kidx >= 0 ? d_idx + R.a_kidx : nullptr;
+    D.b_kidx = R.b_kidx >= 0 ? d_idx + R.b_kidx : nullptr;
+    D.c_jidx = R.c_jidx >= 0 ? d_idx + R.c_jidx : nullptr;
+    D.lower_only = R.lower_only; D.row_off = R.row_off; D.col_off = R.col_off;
+    D.split_stride = R.split_stride; D.a_tri = R.a_tri;
+  }
+  if (count > 0) fail(hipMemcpy(d_desc, h_desc.data(), (size_t)count * sizeof(GemmDesc), hipMemcpyHostToDevice));
+  if (rc == SC_OK) {
+    g_gemm2_force_tile = tile - 10;
+    rc = launch_gemm_f64(ctx, d_desc, count, max_m, max_n, kGemmTile, split_k, gather != 0, tri != 0, layout, lower_grid != 0);
+    g_gemm2_force_tile = 0;
+    fail(hipStreamSynchronize(st));
+  }
+  if (rc == SC_OK) fail(hipMemcpy(arena, d_arena, (size_t)arena_len * 8, hipMemcpyDeviceToHost));
+  for (double* g : {d_front, d_back}) {
+    if (rc != SC_OK) break;
+    fail(hipMemcpy(got.data(), g, (size_t)kRecGuard * 8, hipMemcpyDeviceToHost));
+    if (rc == SC_OK && got != guard) rc = sc_set_error(ctx, SC_ERR_HIP, "GEMM records: the launch wrote outside the arena");
   }
   (void)hipFree(base);
   return rc;

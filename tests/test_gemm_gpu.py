@@ -1,8 +1,9 @@
 """
 GPU unit tests of the f64 MFMA GEMM launch paths (csrc/gemm_f64.hip) against NumPy: every block tile of k_gemm2, the
 three operand layouts, split-K, the lower-triangle launch grid of the band reduction's SYR2K (entries above the diagonal
-must stay untouched), the XCD pairing of launches with 2-4 row tiles, ragged sizes, K = 0.  The triangular-operand and gather launches are covered through the solvers that use them
-(tests/test_two_stage_gpu.py, tests/test_eigh_gpu.py).  Tolerance: K * 4 ulp of the largest partial product sum.
+must stay untouched), the XCD pairing of launches with 2-4 row tiles, ragged sizes, K = 0.  One record per launch, dense
+operands.  The triangular-operand, gather and grouped launches, sub-matrix views and lower_only with offsets have their own
+record-level tests in tests/test_gemm_records_gpu.py.  Tolerance: K * 4 ulp of the largest partial product sum.
 """
 import ctypes as C
 
