@@ -92,9 +92,33 @@ int sc_dbg_gemm_stamps(unsigned long long* out4, int reset);
  * the last reset; returns the number of records written through *count.  tools/gemm_trace.py */
 int sc_dbg_gemm_trace(unsigned long long* out, int max_records, int* count, int reset);
 
-/* Band (128 x n, AB(i,j) at [(i-j) + 128 j]) after stage 1 and the tridiagonal (d, e) after stage 2 of ONE host matrix
- * (n x n, NumPy layout, lower triangle read; n >= 256).  tools/check_two_stage.py */
-int sc_dbg_two_stage(sc_ctx* ctx, const double* a, int n, double* band_out, double* d_out, double* e_out);
+/* The reduction stage of a full-spectrum solve on host data, with its factors: `batch` matrices a (batch x n x n, NumPy
+ * layout, lower triangle read) go through the scaling pass and the tridiagonalisation the product would choose for (ctx, n,
+ * batch) -- the plan of sc_dev_eigh_f64, with sc_ctx_set_two_stage, sc_dbg_set_chase, sc_dbg_set_panel_coop[_fail] and
+ * sc_dbg_set_resident honoured -- and the product's back-transformation is applied to Z = I.  No kernel of its own.
+ *   d_out, e_out   batch x n each: the tridiagonal T (e[n - 1] = 0)
+ *   scale_out      null, or batch: the power of two s the matrix was multiplied by, so that  s A = Q T Q^T
+ *   band_out       null, or batch x (128 x n), two-stage path only: the band B after stage 1, B(i, j) at [(i - j) + 128 j]
+ *                  for 0 <= i - j <= 64 (the rows beyond 64 are zero); untouched on the one-stage path
+ *   q_out          null (no back-transformation), or batch x n x n: the orthogonal factor `which`, its COLUMNS as the rows
+ *                  of the NumPy array (the layout of the eigenvectors of sc_eigh_f64: q_out[k] = Q e_k):
+ *                  which 0: Q = Q1 Q2 (bt2_prepare + bt2_batched, then backtransform_batched; one-stage: its only factor),
+ *                        1: Q1, the stage-1 reflectors alone (backtransform_batched, off = 64),  s A = Q1 B Q1^T,
+ *                        2: Q2, the stage-2 reflectors alone (k_bt2_apply),  B = Q2 T Q2^T;
+ *                  1 and 2 on the one-stage path are SC_ERR_INVALID_ARG
+ *   two_stage_out  null, or the path taken (1 two-stage, 0 one-stage)
+ * SC_ERR_INVALID_ARG for n < 256 on a context whose two-stage path is forced on.  The call synchronises.
+ * tests/test_stage_ratios_gpu.py, tools/check_two_stage.py */
+int sc_dbg_reduce_host(sc_ctx* ctx, const double* a, int n, int batch, int which, double* d_out, double* e_out,
+                       double* scale_out, double* band_out, double* q_out, int* two_stage_out);
+
+/* stedc_batched, the tridiagonal divide & conquer of the full-spectrum solve, on `batch` tridiagonal matrices from the
+ * host: d, e batch x n each (e[n - 1] is not read; the layout sc_dbg_reduce_host returns).  w_out batch x n ascending;
+ * z_out batch x n x n, row k of the NumPy array = the eigenvector of w[k].  The call synchronises; a QL failure is
+ * SC_ERR_NOCONV.  tests/test_stage_ratios_gpu.py */
+int sc_dbg_stedc_host(sc_ctx* ctx, const double* d, const double* e, int n, int batch, double* w_out, double* z_out);
+/* Rows of the largest leaf the D&C solves by QL at order n (DcLayout::leaf_max of dc_slab_doubles). */
+int sc_dbg_stedc_leaf_max(int n);
 
 /* Per-wave s_memtime segment sums of k_bt2_apply (library built with -DBT2_STAMPS; returns 1 otherwise):
  * out[64 workgroups][8 waves][16 sums + diamond count].  tools/bt2_stamps.py */

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "eigh_internal.h"
+#include "springcraft_hip_debug.h"
 
 namespace {
 
@@ -117,6 +118,43 @@ Plan make_plan(const sc_ctx* ctx, int n, int batch, bool vectors) {
   return P;
 }
 
+// SYR2K records of the one-stage panels, one per (panel, matrix), uploaded to `descs`
+int upload_syr2k_records(sc_ctx* ctx, double* d_a, int n, int batch, double* tri_ws, const TriLayout& TL, GemmDesc* descs) {
+  const long long stride_a = (long long)n * n;
+  const int npanels = (n + kNb - 1) / kNb;
+  std::vector<GemmDesc> h((size_t)npanels * batch);
+  for (int p = 0; p < npanels; ++p) {
+    const int pend = std::min((p + 1) * kNb, n);
+    for (int b = 0; b < batch; ++b) {
+      double* ws = tri_ws + (size_t)b * TL.slab;
+      GemmDesc D{};
+      D.a = ws + TL.vw + pend; D.sa_i = 1; D.sa_k = n;
+      D.b = ws + TL.wv + pend; D.sb_k = n; D.sb_j = 1;
+      D.c = d_a + (size_t)b * stride_a + (size_t)pend * n + pend; D.ldc = n;
+      D.m = n - pend; D.n = n - pend; D.k = 2 * kNb;
+      D.alpha = -1.0; D.beta = 1.0;
+      D.lower_only = 1;
+      h[(size_t)p * batch + b] = D;
+    }
+  }
+  return sc_stage_upload(ctx, descs, h.data(), h.size() * sizeof(GemmDesc));
+}
+
+// Mirror + scaling, then the tridiagonalisation the plan chose (the records of upload_syr2k_records in place).  ms_a / ms_b:
+// SYMV / SYR2K sums, or the stage-1 / stage-2 times of the two-stage path; d_band_copy: null, or (batch, 128 x n), the
+// band of every matrix as stage 1 left it (two-stage path, debug entries).
+int tridiagonalise(sc_ctx* ctx, double* d_a, int n, int batch, const Plan& P, char* base, float* ms_a, float* ms_b,
+                   double* d_band_copy) {
+  const long long stride_a = (long long)n * n;
+  double* tri_ws = (double*)(base + P.off_tri);
+  GemmDesc* descs = (GemmDesc*)(base + P.off_desc);
+  SC_TRY(prepare_matrix_batched(ctx, d_a, stride_a, n, batch, tri_ws, P.TL));
+  if (P.two)
+    return sytrd_2stage_batched(ctx, d_a, stride_a, n, batch, tri_ws, P.TL, (double*)(base + P.off_sb), P.SL,
+                                (int*)(base + P.off_dia), descs, ms_a, ms_b, d_band_copy);
+  return tridiag_batched(ctx, d_a, stride_a, n, batch, tri_ws, P.TL, descs, ms_a, ms_b);
+}
+
 // ---- eigenvalues only: Sturm bisection, one thread per eigenvalue ------------------------------------------
 __global__ __launch_bounds__(256) void k_sturm(const double* __restrict__ tri_all, TriLayout TL,
                                                double* __restrict__ w_all, long long stride_w) {
@@ -220,24 +258,7 @@ int eigh_batched_async(sc_ctx* ctx, double* d_a, int64_t n64, int64_t batch64, d
   GemmDesc* descs = (GemmDesc*)(base + P.off_desc);
   const long long stride_a = (long long)n * n;
 
-  // SYR2K descriptors: one per (panel, matrix)
-  const int npanels = (n + kNb - 1) / kNb;
-  std::vector<GemmDesc> h((size_t)npanels * batch);
-  for (int p = 0; p < npanels; ++p) {
-    const int pend = std::min((p + 1) * kNb, n);
-    for (int b = 0; b < batch; ++b) {
-      double* ws = tri_ws + (size_t)b * P.TL.slab;
-      GemmDesc D{};
-      D.a = ws + P.TL.vw + pend; D.sa_i = 1; D.sa_k = n;
-      D.b = ws + P.TL.wv + pend; D.sb_k = n; D.sb_j = 1;
-      D.c = d_a + (size_t)b * stride_a + (size_t)pend * n + pend; D.ldc = n;
-      D.m = n - pend; D.n = n - pend; D.k = 2 * kNb;
-      D.alpha = -1.0; D.beta = 1.0;
-      D.lower_only = 1;
-      h[(size_t)p * batch + b] = D;
-    }
-  }
-  SC_TRY(sc_stage_upload(ctx, descs, h.data(), h.size() * sizeof(GemmDesc)));
+  SC_TRY(upload_syr2k_records(ctx, d_a, n, batch, tri_ws, P.TL, descs));
 
   ScopedEvents<4> ev;
   float ms_bt2 = 0.f;
@@ -250,14 +271,8 @@ int eigh_batched_async(sc_ctx* ctx, double* d_a, int64_t n64, int64_t batch64, d
   double* sb_ws = (double*)(base + P.off_sb);
   std::unique_ptr<PhaseTimer> t_tf;   // T factors of the stage-2 diamonds (second stream)
   if (prof) ctx->phases.clear();
-  SC_TRY(prepare_matrix_batched(ctx, d_a, stride_a, n, batch, tri_ws, P.TL));
-  if (P.two) {
-    // [3] / [4] then carry the stage-1 / stage-2 times
-    SC_TRY(sytrd_2stage_batched(ctx, d_a, stride_a, n, batch, tri_ws, P.TL, sb_ws, P.SL, (int*)(base + P.off_dia),
-                                descs, &ms_symv, &ms_syr2k));
-  } else {
-    SC_TRY(tridiag_batched(ctx, d_a, stride_a, n, batch, tri_ws, P.TL, descs, &ms_symv, &ms_syr2k));
-  }
+  // (two-stage: [3] / [4] then carry the stage-1 / stage-2 times)
+  SC_TRY(tridiagonalise(ctx, d_a, n, batch, P, base, &ms_symv, &ms_syr2k, nullptr));
   if (prof) SC_HIP(ctx, hipEventRecord(ev[1], st));
 
   if (!vectors) {
@@ -650,4 +665,109 @@ int pinvh_device(sc_ctx* ctx, double* d_a, int64_t n64, double rcond, double* d_
     if (rc == SC_OK) rc = sc_stage_end(ctx);
   }
   return rc;
+}
+
+
+// ---- debugging entry points (include/springcraft_hip_debug.h): the stages of a solve on host data --------------------
+// tests/test_stage_ratios_gpu.py, tools/check_two_stage.py
+extern "C" int sc_dbg_reduce_host(sc_ctx* ctx, const double* a, int n, int batch, int which, double* d_out, double* e_out,
+                                  double* scale_out, double* band_out, double* q_out, int* two_stage_out) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  if (!a || !d_out || !e_out || n < 1 || n > 46000 || batch < 1 || which < 0 || which > 2)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  if (ctx->two_stage == 1 && n < 4 * sb_band_width())
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "order %d is below the two-stage minimum %d", n, 4 * sb_band_width());
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const bool vectors = q_out != nullptr;
+  const Plan P = make_plan(ctx, n, batch, vectors);
+  if (!P.two && vectors && which != 0)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "the one-stage path has one orthogonal factor (which = 0)");
+  if (two_stage_out) *two_stage_out = P.two ? 1 : 0;
+  hipStream_t st = ctx->stream;
+  const size_t elems = (size_t)n * n, band_elems = (size_t)2 * sb_band_width() * n;
+  const size_t a_bytes = align_up(elems * 8 * batch, 256), band_bytes = P.two ? align_up(band_elems * 8 * batch, 256) : 0;
+  SC_TRY(sc_reserve_ws(ctx, P.total));
+  SC_TRY(sc_reserve_scratch(ctx, a_bytes * (vectors ? 2 : 1) + band_bytes));
+  char* base = (char*)ctx->ws;
+  double* d_a = (double*)ctx->scratch;
+  double* d_band = P.two ? (double*)((char*)ctx->scratch + a_bytes) : nullptr;
+  double* d_z = vectors ? (double*)((char*)ctx->scratch + a_bytes + band_bytes) : nullptr;
+  double* tri_ws = (double*)(base + P.off_tri);
+  GemmDesc* descs = (GemmDesc*)(base + P.off_desc);
+  const long long stride_a = (long long)elems;
+
+  SC_HIP(ctx, hipMemcpyAsync(d_a, a, elems * 8 * batch, hipMemcpyHostToDevice, st));
+  SC_TRY(upload_syr2k_records(ctx, d_a, n, batch, tri_ws, P.TL, descs));
+  float ms_a = 0.f, ms_b = 0.f;
+  SC_TRY(tridiagonalise(ctx, d_a, n, batch, P, base, &ms_a, &ms_b, d_band));
+  if (vectors) {
+    {   // Z = I for every matrix (the host copy must outlive its transfer)
+      std::vector<double> eye(elems, 0.0);
+      for (int i = 0; i < n; ++i) eye[(size_t)i * n + i] = 1.0;
+      SC_HIP(ctx, hipMemcpyAsync(d_z, eye.data(), elems * 8, hipMemcpyHostToDevice, st));
+      SC_HIP(ctx, hipStreamSynchronize(st));
+    }
+    for (int b = 1; b < batch; ++b)
+      SC_HIP(ctx, hipMemcpyAsync(d_z + (size_t)b * elems, d_z, elems * 8, hipMemcpyDeviceToDevice, st));
+    if (P.two && which != 1) {   // Z <- Q2 Z
+      double* sb_ws = (double*)(base + P.off_sb);
+      SC_TRY(bt2_prepare(ctx, n, batch, sb_ws, P.SL, st));
+      SC_TRY(bt2_batched(ctx, n, batch, sb_ws, P.SL, (const int*)(base + P.off_dia), d_z, stride_a, n));
+    }
+    if (which != 2)              // Z <- Q1 Z (one-stage: the only factor)
+      SC_TRY(backtransform_batched(ctx, d_a, stride_a, n, batch, tri_ws, P.TL, (double*)(base + P.off_bt), P.BL, d_z,
+                                   stride_a, n, (double*)(base + P.off_qtmp), descs + P.n_syr2k + P.n_merge,
+                                   P.two ? sb_band_width() : 1));
+  }
+  SC_TRY(sc_stage_end(ctx));
+  SC_HIP(ctx, hipStreamSynchronize(st));
+  SC_TRY(sc_deferred_status(ctx));
+  for (int b = 0; b < batch; ++b) {
+    const double* tri = tri_ws + (size_t)b * P.TL.slab;
+    SC_HIP(ctx, hipMemcpy(d_out + (size_t)b * n, tri + P.TL.d, sizeof(double) * n, hipMemcpyDeviceToHost));
+    SC_HIP(ctx, hipMemcpy(e_out + (size_t)b * n, tri + P.TL.e, sizeof(double) * n, hipMemcpyDeviceToHost));
+    e_out[(size_t)b * n + n - 1] = 0.0;
+    if (scale_out) SC_HIP(ctx, hipMemcpy(scale_out + b, tri + P.TL.hscale + 2, sizeof(double), hipMemcpyDeviceToHost));
+  }
+  if (P.two && band_out) SC_HIP(ctx, hipMemcpy(band_out, d_band, band_elems * 8 * batch, hipMemcpyDeviceToHost));
+  if (vectors) SC_HIP(ctx, hipMemcpy(q_out, d_z, elems * 8 * batch, hipMemcpyDeviceToHost));
+  return SC_OK;
+}
+
+extern "C" int sc_dbg_stedc_host(sc_ctx* ctx, const double* d, const double* e, int n, int batch, double* w_out,
+                                 double* z_out) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  if (!d || !e || !w_out || !z_out || n < 1 || n > 46000 || batch < 1)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const Plan P = make_plan(ctx, n, batch, true);
+  hipStream_t st = ctx->stream;
+  const size_t elems = (size_t)n * n;
+  const size_t z_bytes = align_up(elems * 8 * batch, 256);
+  SC_TRY(sc_reserve_ws(ctx, P.total));
+  SC_TRY(sc_reserve_scratch(ctx, z_bytes + (size_t)n * 8 * batch));
+  char* base = (char*)ctx->ws;
+  double* d_z = (double*)ctx->scratch;
+  double* d_w = (double*)((char*)ctx->scratch + z_bytes);
+  double* tri_ws = (double*)(base + P.off_tri);
+  for (int b = 0; b < batch; ++b) {
+    double* tri = tri_ws + (size_t)b * P.TL.slab;
+    SC_TRY(sc_stage_upload(ctx, tri + P.TL.d, d + (size_t)b * n, sizeof(double) * n));
+    SC_TRY(sc_stage_upload(ctx, tri + P.TL.e, e + (size_t)b * n, sizeof(double) * n));
+  }
+  SC_TRY(stedc_batched(ctx, n, batch, tri_ws, P.TL, (double*)(base + P.off_dc), P.DL, d_w, n, d_z,
+                       (double*)(base + P.off_qtmp), (double*)(base + P.off_u), (long long)elems,
+                       (GemmDesc*)(base + P.off_desc) + P.n_syr2k));
+  SC_TRY(sc_stage_end(ctx));
+  SC_HIP(ctx, hipStreamSynchronize(st));
+  SC_TRY(sc_deferred_status(ctx));
+  SC_HIP(ctx, hipMemcpy(w_out, d_w, sizeof(double) * n * batch, hipMemcpyDeviceToHost));
+  SC_HIP(ctx, hipMemcpy(z_out, d_z, elems * 8 * batch, hipMemcpyDeviceToHost));
+  return SC_OK;
+}
+
+extern "C" int sc_dbg_stedc_leaf_max(int n) {
+  DcLayout DL;
+  (void)dc_slab_doubles(n, &DL);
+  return DL.leaf_max;
 }

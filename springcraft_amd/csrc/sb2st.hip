@@ -1458,8 +1458,10 @@ int sb_stage2(sc_ctx* ctx, double* d_a, long long stride_a, int n, int batch, do
               double* d_sb_ws, const SbLayout& SL, double* d_band_copy, SbTimers& timers) {
   hipStream_t st = ctx->stream;
   hipLaunchKernelGGL(k_band_extract, dim3(256, (unsigned)batch), dim3(256), 0, st, d_a, stride_a, d_sb_ws, SL);
-  if (d_band_copy)   // debugging aid: the band as stage 1 left it (first matrix)
-    SC_HIP(ctx, hipMemcpyAsync(d_band_copy, d_sb_ws + SL.ab, sizeof(double) * kLdab * n, hipMemcpyDeviceToDevice, st));
+  if (d_band_copy)   // debugging aid: the band of every matrix as stage 1 left it, (batch, kLdab * n)
+    for (int b = 0; b < batch; ++b)
+      SC_HIP(ctx, hipMemcpyAsync(d_band_copy + (size_t)b * kLdab * n, d_sb_ws + (size_t)b * SL.slab + SL.ab,
+                                 sizeof(double) * kLdab * n, hipMemcpyDeviceToDevice, st));
   hipLaunchKernelGGL(k_sb_clean, dim3((unsigned)n, (unsigned)batch), dim3(256), 0, st, d_a, stride_a, n);
   for (int b = 0; b < batch; ++b) {
     double* sb = d_sb_ws + (size_t)b * SL.slab;

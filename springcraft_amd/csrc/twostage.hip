@@ -103,37 +103,3 @@ int sytrd_2stage_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, in
 }
 
 int sb_band_width() { return kB; }
-
-// ---- debugging entry point (not part of the public C ABI): band after stage 1 (128 x n, AB(i,j) at [(i-j) + 128 j])
-// and the tridiagonal after stage 2 of ONE host matrix (NumPy layout, lower triangle read).
-extern "C" int sc_dbg_two_stage(sc_ctx* ctx, const double* a, int n, double* band_out, double* d_out, double* e_out) {
-  if (!ctx || !a || n < 4 * kB) return SC_ERR_INVALID_ARG;
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  TriLayout TL{};
-  TL.n = n; TL.nb = kB;
-  TL.d = 0; TL.e = n; TL.tau = 2 * (long long)n; TL.slab = 3 * (long long)n + 64;
-  SbLayout SL;
-  const size_t sbd = sb_slab_doubles(n, 1, &SL);
-  double *d_a = nullptr, *d_tri = nullptr, *d_sb = nullptr, *d_band = nullptr;
-  int* d_off = nullptr;
-  GemmDesc* d_desc = nullptr;
-  SC_HIP(ctx, hipMalloc(&d_a, sizeof(double) * (size_t)n * n));
-  SC_HIP(ctx, hipMalloc(&d_tri, sizeof(double) * TL.slab));
-  SC_HIP(ctx, hipMalloc(&d_sb, sizeof(double) * sbd));
-  SC_HIP(ctx, hipMalloc(&d_band, sizeof(double) * kLdab * n));
-  SC_HIP(ctx, hipMalloc(&d_off, sizeof(int) * (n / 64 + 8)));
-  SC_HIP(ctx, hipMalloc(&d_desc, sizeof(GemmDesc) * sb_desc_count(n, 1)));
-  SC_HIP(ctx, hipMemcpyAsync(d_a, a, sizeof(double) * (size_t)n * n, hipMemcpyHostToDevice, ctx->stream));
-  int rc = mirror_lower_batched(ctx, d_a, (long long)n * n, n, 1);
-  if (rc == SC_OK)
-    rc = sytrd_2stage_batched(ctx, d_a, (long long)n * n, n, 1, d_tri, TL, d_sb, SL, d_off, d_desc, nullptr, nullptr,
-                              d_band);
-  if (rc == SC_OK) {
-    (void)hipMemcpy(band_out, d_band, sizeof(double) * kLdab * n, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(d_out, d_tri + TL.d, sizeof(double) * n, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(e_out, d_tri + TL.e, sizeof(double) * n, hipMemcpyDeviceToHost);
-  }
-  (void)hipFree(d_a); (void)hipFree(d_tri); (void)hipFree(d_sb); (void)hipFree(d_band); (void)hipFree(d_off);
-  (void)hipFree(d_desc);
-  return rc;
-}

@@ -1,0 +1,286 @@
+"""
+Stage-level backward-error tests of the eigensolver: the reconstruction and orthogonality ratios of LAPACK's test programs
+(tests/stage_ratios.py), in units of n ulp, for every stage on every kernel form the product can take -- the band
+reduction (A = Q1 B Q1^T), the bulge chase with the diamond back-transformation (B = Q2 T Q2^T), both together
+(A = Q T Q^T), the one-stage reductions, and the tridiagonal divide & conquer (T = Z diag(w) Z^T) -- through the staged
+debug entries sc_dbg_reduce_host / sc_dbg_stedc_host, which launch the product's kernels through the product's host
+functions.  Private contexts; path and form forced as in tests/test_two_stage_gpu.py and
+tests/test_batched_degenerate_gpu.py and confirmed by the same counters; every member of every batch is checked; the
+figures are printed before anything is asserted.  Every ratio is gated at 50, a thousand to ten thousand times tighter than
+the end-to-end max-abs gates at these orders; LAPACK's own factors stay below 5 on the same inputs
+(tests/test_stage_ratios_host.py).  profiles/stage_ratios.txt holds the figures of the first run.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+from tests import stage_ratios as sr
+
+pytestmark = pytest.mark.gpu
+
+CHASE_COUNTERS = ("chase_launches", "chase_timeouts", "chase_incomplete", "chase_resumed", "chase_sweeps", "stepwise_chases",
+                  "chase_pair_launches", "chase_pair_fallbacks")
+
+
+@pytest.fixture()
+def lib_ctx():
+    from springcraft_amd import _hip
+
+    L = sr.debug_lib()
+    ctx = _hip.Context(0)
+    try:
+        yield L, ctx
+    finally:
+        ctx.close()
+
+
+def batch_of(kind, n):
+    """(member names, batch) -- a batch of one random matrix, or the mixed batch."""
+    if kind == "one":
+        return ["random"], sr.random_sym(n)[None]
+    return sr.mixed_batch(n)
+
+
+def scaled(a, s):
+    """s A with s the power of two the solver scaled the matrix by (exact)."""
+    assert s > 0.0 and np.frexp(s)[0] == 0.5, s
+    return a * s
+
+
+def report(label, rows):
+    """rows: (member, {figure: value}); prints all of them, then asserts every one against the gate."""
+    failures = []
+    for name, figures in rows:
+        print(f"[{label}] {name:<10s} " + "  ".join(f"{k} {v:.3g}" for k, v in figures.items()))
+        for k, v in figures.items():
+            if k == "beyond_band":
+                if v != 0.0:
+                    failures.append((name, k, v))
+            elif not v <= sr.GATE:
+                failures.append((name, k, v))
+    assert not failures, (label, failures)
+
+
+def check_two_stage(L, ctx, label, names, mats, counters):
+    """The three factors of the two-stage path; `counters(call)` confirms the forced form after each call."""
+    n = mats.shape[1]
+    out = {}
+    for which in (sr.Q_ONE, sr.Q_TWO, sr.Q_ALL):
+        out[which] = sr.reduce_host(L, ctx, mats, which)
+        assert out[which][5], "the two-stage path was forced"
+        counters(len(out))
+    rows = []
+    for b, name in enumerate(names):
+        fig = {}
+        d, e, s, band, q1, _ = (x[b] if isinstance(x, np.ndarray) else x for x in out[sr.Q_ONE])
+        a = scaled(mats[b], s)
+        fig["recon(A,Q1,B)"] = sr.recon(a, q1, sr.band_matrix(band))
+        fig["orth(Q1)"] = sr.orth(q1)
+        fig["beyond_band"] = sr.band_beyond(band)
+        d, e, s, band, q2, _ = (x[b] if isinstance(x, np.ndarray) else x for x in out[sr.Q_TWO])
+        fig["recon(B,Q2,T)"] = sr.recon(sr.band_matrix(band), q2, sr.tridiagonal(d, e))
+        fig["orth(Q2)"] = sr.orth(q2)
+        fig["beyond_band"] = max(fig["beyond_band"], sr.band_beyond(band))
+        d, e, s, band, q, _ = (x[b] if isinstance(x, np.ndarray) else x for x in out[sr.Q_ALL])
+        fig["recon(A,Q,T)"] = sr.recon(scaled(mats[b], s), q, sr.tridiagonal(d, e))
+        fig["orth(Q)"] = sr.orth(q)
+        rows.append((name, fig))
+    report(label, rows)
+
+
+def check_one_stage(L, ctx, label, names, mats):
+    d, e, s, band, q, two = sr.reduce_host(L, ctx, mats, sr.Q_ALL)
+    assert not two and band is None
+    rows = []
+    for b, name in enumerate(names):
+        rows.append((name, {"recon(A,Q,T)": sr.recon(scaled(mats[b], s[b]), q[b], sr.tridiagonal(d[b], e[b])),
+                            "orth(Q)": sr.orth(q[b])}))
+    report(label, rows)
+    return d, e, s, q
+
+
+def chase_check(ctx, form, give_up, n, batch):
+    def check(calls):
+        cnt = {k: ctx.counter(k) for k in CHASE_COUNTERS}
+        assert cnt["chase_launches"] == calls and cnt["stepwise_chases"] == 0, cnt
+        assert cnt["chase_pair_launches"] == (calls if form == 3 else 0) and cnt["chase_pair_fallbacks"] == 0, cnt
+        assert cnt["chase_timeouts"] == 0 and cnt["chase_incomplete"] == 0, cnt
+        if give_up == 0:
+            assert cnt["chase_resumed"] == 0 and cnt["chase_sweeps"] == calls * batch * (n - 2), cnt
+        else:
+            assert cnt["chase_resumed"] == calls and cnt["chase_sweeps"] < calls * batch * (n - 2), cnt
+    return check
+
+
+# ---- two-stage ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,kind,give_up", [(256, "one", 0), (322, "one", 0), (322, "mixed", 0), (322, "one", 5),
+                                            (322, "mixed", 5), (1030, "one", 5)])
+@pytest.mark.parametrize("form", [3, 4, 5])
+def test_two_stage_chase_forms(lib_ctx, form, n, kind, give_up):
+    """
+    The persistent chase in the pair form (3), with one sweep per workgroup (4) and spread over all XCDs (5; the mixed
+    batch has seven members, fewer than the device has XCDs), stage 1 by the default panel kernels.  n = 256: the minimum;
+    322: partial last panel, diamond and sweep group; give_up = 5: every workgroup gives up after five tasks and
+    k_chase_finish takes over -- at n = 1030 with sixteen sweep groups behind it.
+    """
+    L, ctx = lib_ctx
+    names, mats = batch_of(kind, n)
+    ctx.set_two_stage(True)
+    ctx.check(L.sc_dbg_set_chase(ctx.handle, form, give_up))
+    check_two_stage(L, ctx, f"two-stage n={n} {kind} form={form} give_up={give_up}", names, mats,
+                    chase_check(ctx, form, give_up, n, len(names)))
+
+
+def coop_overridden():
+    return os.environ.get("SPRINGCRAFT_QR_COOP") == "0" or bool(os.environ.get("SPRINGCRAFT_QR_COOP_MIN")) or \
+        int(os.environ.get("SPRINGCRAFT_STAGE1_STREAMS") or 0) > 1
+
+
+@pytest.mark.parametrize("n,kind,min_rows,fail_panel", [(322, "one", 0, -1), (322, "mixed", 0, -1),
+                                                        (322, "one", 128, -1), (322, "mixed", 128, -1),
+                                                        (322, "one", 128, 1), (322, "mixed", 128, 1),
+                                                        (1030, "one", 200, -1), (1030, "one", 200, 2)])
+def test_two_stage_panel_kernels(lib_ctx, n, kind, min_rows, fail_panel):
+    """
+    Stage 1 by the single-workgroup panel kernels alone (k_panel_wg: min_rows 0 keeps k_panel_coop out), by k_panel_coop
+    (panels of at least min_rows rows: two workgroups per matrix at n = 322, four at n = 1030), and with its take-over
+    k_panel_serial from panel `fail_panel` on.
+    """
+    if min_rows and coop_overridden():
+        pytest.skip("the cooperative kernel's rule is overridden (tools/test_matrix.sh)")
+    L, ctx = lib_ctx
+    names, mats = batch_of(kind, n)
+    batch = len(names)
+    ctx.set_two_stage(True)
+    ctx.check(L.sc_dbg_set_panel_coop(ctx.handle, min_rows))
+    ctx.check(L.sc_dbg_set_panel_coop_fail(ctx.handle, fail_panel))
+    coop_panels = sum(1 for p in range(n // 64 + 1) if n - (p + 1) * 64 >= max(min_rows, 65)) if min_rows else 0
+
+    def counters(calls):
+        launches, timeouts = ctx.counter("panel_coop_launches"), ctx.counter("panel_coop_timeouts")
+        if fail_panel < 0:
+            assert launches == calls * coop_panels and timeouts == 0, (launches, timeouts)
+        else:
+            # the first call meets the hook, counts every panel behind it, and the context then keeps to the chunked
+            # launches until the hook is set again (below)
+            assert coop_panels > fail_panel
+            assert launches == calls * coop_panels and timeouts == calls * batch * (coop_panels - fail_panel), \
+                (launches, timeouts)
+            ctx.check(L.sc_dbg_set_panel_coop_fail(ctx.handle, fail_panel))
+        assert ctx.counter("chase_timeouts") == 0 and ctx.counter("chase_incomplete") == 0
+
+    check_two_stage(L, ctx, f"two-stage n={n} {kind} coop_min_rows={min_rows} fail_panel={fail_panel}", names, mats, counters)
+
+
+def test_two_stage_minimum_order(lib_ctx):
+    L, ctx = lib_ctx
+    ctx.set_two_stage(True)
+    rc, _ = sr.reduce_raw(L, ctx, sr.random_sym(130)[None], sr.Q_ALL)
+    assert rc == 1, rc          # SC_ERR_INVALID_ARG
+    ctx.set_two_stage(False)
+    rc, _ = sr.reduce_raw(L, ctx, sr.random_sym(130)[None], sr.Q_TWO)
+    assert rc == 1, rc          # the one-stage path has one factor
+
+
+# ---- one-stage ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [130, 322])
+def test_one_stage_batched(lib_ctx, n):
+    """The batched launch-per-column tridiagonalisation and the Q1 back-transformation with off = 1, on the mixed batch."""
+    L, ctx = lib_ctx
+    names, mats = sr.mixed_batch(n)
+    ctx.set_two_stage(False)
+    check_one_stage(L, ctx, f"one-stage n={n} mixed", names, mats)
+    assert ctx.counter("chase_launches") == 0 and ctx.counter("stepwise_chases") == 0
+    assert ctx.counter("resident_launches") == 0
+
+
+@pytest.mark.parametrize("n,hook", [(322, 0), (2050, 0), (322, 1), (322, 2 + 150)])
+def test_one_stage_resident(lib_ctx, n, hook):
+    """k_sytrd_resident on one matrix: the rows in LDS (n = 322) and in registers (n = 2050), and k_sytrd_takeover behind
+    a failed roll call (hook 1) and behind a wait lost at step 150 (hook 2 + 150)."""
+    if os.environ.get("SPRINGCRAFT_RESIDENT") == "0" or n > int(os.environ.get("SPRINGCRAFT_RESIDENT_MAX", "3072")):
+        pytest.skip("the kernel under test is switched off or limited (tools/test_matrix.sh)")
+    L, ctx = lib_ctx
+    ctx.set_two_stage(False)
+    ctx.check(L.sc_dbg_set_resident(ctx.handle, 1, hook, 0))
+    check_one_stage(L, ctx, f"one-stage resident n={n} hook={hook}", ["random"], sr.random_sym(n)[None])
+    assert ctx.counter("resident_launches") == 1
+    assert ctx.counter("resident_takeovers") == (1 if hook else 0)
+    print({k: ctx.counter(k) for k in ("resident_rollcall_failures", "resident_lost_waits")})
+
+
+# ---- tridiagonal solver ---------------------------------------------------------------------------------------------------
+def stedc_orders(L):
+    leaf = L.sc_dbg_stedc_leaf_max(1000)
+    return [2, leaf, leaf + 1, 322, 1000]
+
+
+@pytest.mark.parametrize("slot", range(5))
+def test_tridiagonal_solver(lib_ctx, slot):
+    """
+    stedc_batched alone, one batch per order with all the inputs together: n = 2, the largest leaf (QL only), one more (the
+    smallest merge), 322 and 1000.  T = Z diag(w) Z^T and Z orthogonal to the gate; by Weyl's theorem these two bound the
+    eigenvalue errors as well, so only the (1, 2, 1) Toeplitz matrix, whose spectrum is known exactly, has a gate on them.
+    """
+    L, ctx = lib_ctx
+    n = stedc_orders(L)[slot]
+    assert L.sc_dbg_stedc_leaf_max(n) == 32, "tests/test_stage_ratios_host.py checks LAPACK at orders 32 and 33"
+    inputs = sr.tridiagonal_inputs(n)
+    d = np.stack([inputs[k][0] for k in sr.TRIDIAGONALS])
+    e = np.stack([inputs[k][1] for k in sr.TRIDIAGONALS])
+    w, z = sr.stedc_host(L, ctx, d, e)
+    rows = []
+    for b, name in enumerate(sr.TRIDIAGONALS):
+        fig = {"recon(T,Z,w)": sr.recon(sr.tridiagonal(d[b], e[b]), z[b], np.diag(w[b])), "orth(Z)": sr.orth(z[b])}
+        if name == "toeplitz":
+            fig["eig/(4 n ulp)"] = np.abs(w[b] - sr.toeplitz_exact(n)).max() / (4 * n * sr.ULP)
+        assert np.all(np.diff(w[b]) >= 0.0), (name, "eigenvalues not ascending")
+        rows.append((name, fig))
+    report(f"stedc n={n}", rows)
+
+
+def test_tridiagonal_solver_is_independent_of_the_batch_slot(lib_ctx):
+    """Eight copies of one input in one batch: every Z and w is bit-identical, and passes the gate."""
+    L, ctx = lib_ctx
+    n = 322
+    d0, e0 = sr.tridiagonal_inputs(n)["glued1e-4"]
+    w, z = sr.stedc_host(L, ctx, np.tile(d0, (8, 1)), np.tile(e0, (8, 1)))
+    report(f"stedc n={n} x 8", [("glued1e-4", {"recon(T,Z,w)": sr.recon(sr.tridiagonal(d0, e0), z[0], np.diag(w[0])),
+                                               "orth(Z)": sr.orth(z[0])})])
+    for b in range(1, 8):
+        assert np.array_equal(w[b], w[0]) and np.array_equal(z[b], z[0]), b
+
+
+# ---- the staged entries against the product path ---------------------------------------------------------------------------
+@pytest.mark.parametrize("two_stage,n", [(True, 322), (False, 322)])
+def test_stages_compose_to_the_product(lib_ctx, two_stage, n):
+    """
+    V of sc_dev_eigh_f64 against (Q Z)^T built from the two staged entries, for a batch of two (the batched kernels on
+    both paths): |V - (Q Z)^T|_1 <= 50 n ulp, and the eigenvalues agree to 50 n ulp lambda_max.  Ties the stages to the
+    product.
+    """
+    import torch
+
+    L, ctx = lib_ctx
+    mats = np.stack([sr.random_sym(n), sr.mixed_batch(n)[1][sr.MIXED.index("band65")]])
+    ctx.set_two_stage(two_stage)
+    a = torch.from_numpy(mats.copy()).cuda()
+    w = torch.empty((2, n), dtype=torch.float64, device="cuda")
+    v = torch.empty((2, n, n), dtype=torch.float64, device="cuda")
+    ctx.check(L.sc_dev_eigh_f64(ctx.handle, C.c_void_p(a.data_ptr()), n, 2, C.c_void_p(w.data_ptr()),
+                                C.c_void_p(v.data_ptr())))
+    ctx.synchronize()
+    w, v = w.cpu().numpy(), v.cpu().numpy()
+    d, e, s, _, q, two = sr.reduce_host(L, ctx, mats, sr.Q_ALL)
+    assert two == two_stage
+    ws, z = sr.stedc_host(L, ctx, d, e)
+    figures = []
+    for b in range(2):
+        diff = sr.norm1(v[b] - (q[b] @ z[b]).T) / (n * sr.ULP)
+        eig = np.abs(w[b] - ws[b] / s[b]).max() / (np.abs(w[b]).max() * n * sr.ULP)
+        figures.append((diff, eig))
+        print(f"[compose two_stage={two_stage} n={n}] member {b}: |V - (Q Z)^T|_1 / (n ulp) = {diff:.3g}, "
+              f"eigenvalue difference / (n ulp lambda_max) = {eig:.3g}")
+    assert all(diff <= sr.GATE and eig <= sr.GATE for diff, eig in figures), figures

@@ -13,8 +13,8 @@ from springcraft_amd import _hip  # noqa: E402
 
 L = _hip.lib()
 ctx = _hip.context()
-L.sc_dbg_two_stage.restype = C.c_int
-L.sc_dbg_two_stage.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+L.sc_dbg_reduce_host.restype = C.c_int
+L.sc_dbg_reduce_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
 
 
 def stages(a):
@@ -22,7 +22,9 @@ def stages(a):
     band = np.zeros((n, 128))
     d = np.zeros(n)
     e = np.zeros(n)
-    rc = L.sc_dbg_two_stage(ctx.handle, _hip.ptr(np.ascontiguousarray(a)), n, _hip.ptr(band), _hip.ptr(d), _hip.ptr(e))
+    # (a batch of one, no orthogonal factor; random matrices of this size are not rescaled)
+    rc = L.sc_dbg_reduce_host(ctx.handle, _hip.ptr(np.ascontiguousarray(a)), n, 1, 0, _hip.ptr(d), _hip.ptr(e), None,
+                              _hip.ptr(band), None, None)
     assert rc == 0, (rc, L.sc_last_error(ctx.handle))
     # band[j, dd] = AB(j + dd, j)
     bm = np.zeros((n, n))
