@@ -26,7 +26,7 @@ struct FFDev {
   const unsigned char* bonded_next;
 };
 
-// One structure of a ragged / decorated batch (sc_batch_plan, api.hip): its own size, force field and patches; the
+// One structure of a ragged / decorated batch (sc_batch_plan, api_plan.hip): its own size, force field and patches; the
 // coordinates / weights / matrices of all structures sit in three buffers the launch gets as base pointers.
 struct AsmItem {
   long long atom_off;   // first atom of this structure in the packed coordinate / weight buffers
@@ -574,7 +574,7 @@ __global__ __launch_bounds__(256) void k_pad_fill(double* __restrict__ m_all, co
   }
 }
 
-// ff.tab, when set, has already been replaced by a descriptor holding DEVICE pointers (api.hip:stage_tab)
+// ff.tab, when set, has already been replaced by a descriptor holding DEVICE pointers (api_model.hip:upload_tab)
 FFDev make_ff(const sc_ff_desc& ff) {
   FFDev d{};
   d.kind = ff.kind;

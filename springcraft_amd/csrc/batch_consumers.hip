@@ -3,7 +3,7 @@
 // The reference derives these from nma.eigen for one model (nma.py:108-184 msf, :233-359 dcc).  Here the inputs are the
 // batch solver's own w (batch, nvec), v (batch, nvec, m) rows = modes and, behind a window solve, counts (batch): at the
 // benchmarked shape v is 18 GB that nobody wants to move or copy.  One model's device-resident eigenpairs (sc_modes_*,
-// api.hip) come through here as a batch of one with a row list.
+// api_modes.hip) come through here as a batch of one with a row list.
 //
 // One idea carries every selection: k_mode_weights turns (w, selection, counts) into a weight per (structure, listed
 // row), 1 / lambda for a selected row and exactly 0.0 for any other, and then

@@ -238,7 +238,7 @@ int launch_kirchhoff_from_pairs(sc_ctx* ctx, int64_t n, const int64_t* d_pairs, 
 int launch_hessian_from_pairs(sc_ctx* ctx, const double* d_coord, int64_t n,
                               const int64_t* d_pairs, int64_t k, const double* d_gamma,
                               double* d_h);
-// Ragged / decorated batches (sc_batch_plan, api.hip): records of one structure each, opaque outside assembly.hip.
+// Ragged / decorated batches (sc_batch_plan, api_plan.hip): records of one structure each, opaque outside assembly.hip.
 size_t asm_item_bytes();
 // ff_dev: descriptor whose .tab (if any) holds DEVICE pointers; patch: device tables (empty tables when unpatched)
 void asm_item_fill(void* dst, long long atom_off, int n, int ld, const sc_ff_desc& ff_dev, const PatchDev& patch);

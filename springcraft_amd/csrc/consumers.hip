@@ -1,7 +1,7 @@
 // Perturbation response scanning on device-resident eigenpairs.
 //
 // The reference evaluates it with NumPy on the (eig_values, eig_vectors) pair that nma.eigen returns, solving the
-// eigenproblem again (nma.py:476-524).  Here the eigenpairs stay in HBM (struct sc_modes, api.hip): two kernels and one
+// eigenproblem again (nma.py:476-524).  Here the eigenpairs stay in HBM (struct sc_modes, api_modes.hip): two kernels and one
 // MFMA GEMM, and only the (N, N) result crosses PCIe.
 //
 //   prs[a, b] = sum_{d, e} C[3a + d, 3b + e]^2,  C = pinv(H)                      (optionally / prs[a, a])

@@ -1,6 +1,6 @@
 // Host-side logic of the C ABI that needs no HIP: the contact-patch override table and the force-field descriptor
 // check.  Header-only so that tests/host_sanitize/ can compile exactly this code with g++ -fsanitize=address,undefined
-// (sanitizers run on the CPU build only); api.hip includes it and forwards the messages to
+// (sanitizers run on the CPU build only); the api_*.hip units include it and forward the messages to
 // sc_set_error.
 #pragma once
 #include <cmath>
@@ -12,11 +12,10 @@
 #include <utility>
 #include <vector>
 
+#include "scratch_arena.h"
 #include "springcraft_hip.h"
 
 namespace sc_host {
-
-static inline size_t align_up_sz(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // status code + message, printf style
 static inline int fail(std::string& err, int code, const char* fmt, ...) {
@@ -51,10 +50,17 @@ struct HostPatch {
   std::vector<int8_t> flag;
   std::vector<double> gam;
   int mask_gamma = 0;
+  // The device tables, as stage_inputs (api_model.hip) carves them (the +1: kernels may read one element past an empty
+  // table; braced lists are evaluated in order), and the bytes they occupy: the same takes, measured
+  struct Bufs { uint8_t* shut; int32_t* rp; int32_t* col; int8_t* flag; double* gam; };
+  Bufs layout(Arena& a) const {
+    return Bufs{a.take<uint8_t>(shut.size()), a.take<int32_t>(row_ptr.size()), a.take<int32_t>(col.size() + 1),
+                a.take<int8_t>(flag.size() + 1), a.take<double>(gam.size() + 1)};
+  }
   size_t device_bytes() const {
-    return align_up_sz(shut.size(), 256) + align_up_sz(row_ptr.size() * 4, 256) +
-           align_up_sz(col.size() * 4 + 4, 256) + align_up_sz(flag.size() + 1, 256) +
-           align_up_sz(gam.size() * 8 + 8, 256) + 2048;
+    Arena a;
+    layout(a);
+    return a.bytes();
   }
 };
 

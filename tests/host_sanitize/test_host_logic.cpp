@@ -1,4 +1,4 @@
-// Host-only logic of the C ABI (springcraft_amd/csrc/host_logic.h) under AddressSanitizer + UBSan:
+// Host-only logic of the C ABI (springcraft_amd/csrc/host_logic.h, scratch_arena.h) under AddressSanitizer + UBSan:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I include -I springcraft_amd/csrc \
 //       tests/host_sanitize/test_host_logic.cpp -o /tmp/test_host_logic && /tmp/test_host_logic
 // (built and run by tests/test_abi_and_host.py::test_host_logic_under_sanitizers).  Expected values restate
@@ -7,9 +7,11 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "host_logic.h"
+#include "scratch_arena.h"
 #include "twostage_policy.h"
 
 #define CHECK(cond) do { if (!(cond)) { std::fprintf(stderr, "CHECK failed: %s (line %d)\n", #cond, __LINE__); std::exit(1); } } while (0)
@@ -57,6 +59,81 @@ int main() {
     for (int i = 0; i < 8; ++i)
       for (int p = hp.row_ptr[i] + 1; p < hp.row_ptr[i + 1]; ++p) CHECK(hp.col[p - 1] < hp.col[p]);   // CSR rows sorted
     CHECK(hp.device_bytes() >= hp.shut.size() + hp.col.size() * 4);
+    // device_bytes is the measure of the tables' own layout: carved into exactly that many bytes, the last table ends the buffer
+    std::vector<char> buf(hp.device_bytes());
+    sc_host::Arena carve(buf.data(), buf.size());
+    const HostPatch::Bufs b = hp.layout(carve);
+    CHECK(!carve.overrun() && b.shut && b.rp && b.col && b.flag && (char*)(b.gam + hp.gam.size() + 1) == buf.data() + buf.size());
+  }
+  // ---- the scratch arena (csrc/scratch_arena.h): a layout measures what it carves
+  {
+    using sc_host::Arena;
+    struct Bufs { double* a; char* b; int32_t* c; int64_t* d; double* e; uint8_t* f; };
+    const size_t na = 33, nb = 257, nc = 0, nd = 5, ne = 64, nf = 0;   // mixed element types, zero counts in the middle and last
+    for (int with_e = 0; with_e < 2; ++with_e) {   // a conditional take (the `v ? take : nullptr` shape of the eigensolver entries)
+      auto layout = [&](Arena& s, Bufs& p) {
+        p.a = s.take<double>(na);
+        p.b = s.take<char>(nb);
+        p.c = s.take<int32_t>(nc);
+        p.d = s.take<int64_t>(nd);
+        p.e = with_e ? s.take<double>(ne) : nullptr;
+        p.f = s.take<uint8_t>(nf);
+      };
+      Arena measure;
+      Bufs none{};
+      layout(measure, none);
+      CHECK(!none.a && !none.b && !none.c && !none.d && !none.e && !none.f && !measure.overrun());   // measuring hands out nothing
+      const size_t need = measure.bytes();
+      CHECK(need >= na * 8 + nb + nd * 8 + (with_e ? ne * 8 : 0) && need <= 256 * 6 + na * 8 + nb + nd * 8 + ne * 8);
+      // a malloc of exactly the measured bytes, so that ASan sees an overrun (malloc aligns to 16 bytes only: the
+      // 256-byte alignment is checked on the offsets, which is what it means for a 256-aligned device buffer)
+      char* raw = static_cast<char*>(std::malloc(need));
+      CHECK(raw != nullptr);
+      Arena carve(raw, need);
+      Bufs p{};
+      layout(carve, p);
+      CHECK(!carve.overrun() && carve.bytes() == need);         // measure and carve agree
+      CHECK((p.e != nullptr) == (with_e != 0));
+      struct Reg { char* at; size_t bytes; };
+      const Reg regs[] = {{(char*)p.a, na * 8}, {p.b, nb}, {(char*)p.c, nc * 4}, {(char*)p.d, nd * 8}, {(char*)p.e, with_e ? ne * 8 : 0},
+                          {(char*)p.f, nf}};
+      char* prev_end = raw;
+      unsigned char fill = 1;
+      for (const Reg& r : regs) {
+        if (!r.at) continue;
+        CHECK((size_t)(r.at - raw) % 256 == 0);                 // every region starts on a 256-byte boundary of the buffer
+        CHECK(r.at >= prev_end && r.at < raw + need);           // disjoint, in order, and a valid address even when empty
+        std::memset(r.at, fill++, r.bytes);                     // written full: an overrun of the malloc is ASan's to report
+        prev_end = r.at + (r.bytes ? r.bytes : 1);              // an empty region keeps its address to itself
+      }
+      CHECK(prev_end == raw + need);
+      fill = 1;
+      for (const Reg& r : regs) {                               // nothing was overwritten by a later region
+        if (!r.at) continue;
+        for (size_t i = 0; i < r.bytes; ++i) CHECK((unsigned char)r.at[i] == fill);
+        ++fill;
+      }
+      // one byte short: reported, and the region that does not fit is not handed out
+      Arena tight(raw, need - 1);
+      Bufs q{};
+      layout(tight, q);
+      CHECK(tight.overrun() && q.f == nullptr && q.a == p.a && q.d == p.d);
+      std::free(raw);
+    }
+    // zero counts only: distinct valid addresses, one byte each
+    {
+      Arena m;
+      m.take<double>(0);
+      m.take<int>(0);
+      CHECK(m.bytes() == 257);
+      char buf[257];
+      Arena c(buf, sizeof(buf));
+      double* x = c.take<double>(0);
+      int* y = c.take<int>(0);
+      CHECK(x && y && (char*)y == (char*)x + 256 && !c.overrun());
+      Arena none(buf, 0);
+      CHECK(none.take<char>(0) == nullptr && none.overrun());
+    }
   }
   // ---- pair_on without force constants: NaN marks "use the base force field" (forcefield.py:221-224)
   {

@@ -213,7 +213,7 @@ def test_pdb_adaptor_and_residue_masses():
 def test_host_logic_under_sanitizers(tmp_path):
     """
     SURVEY section 5: sanitizers on the CPU build only.  The HIP-free host logic of the C ABI (contact-patch override
-    table, force-field descriptor checks: csrc/host_logic.h, included by api.hip) compiled with g++ under ASan + UBSan
+    table, force-field descriptor checks: csrc/host_logic.h, included by the api_*.hip units) compiled with g++ under ASan + UBSan
     and driven through its edge cases (tests/host_sanitize/test_host_logic.cpp).
     """
     import shutil

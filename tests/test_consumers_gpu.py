@@ -301,3 +301,82 @@ def test_model_msf_and_dcc_are_the_bits_of_a_batch_of_one(sc, n_atoms, dim):
     empty = np.array([], dtype=np.int64)
     assert np.array_equal(modes.msf(empty), np.zeros(n_atoms))
     assert np.array_equal(modes.dcc(empty, False), np.zeros((n_atoms, n_atoms)))
+
+
+def test_scratch_grown_to_each_calls_exact_measure(ca):
+    """
+    Every host entry sizes the context's scratch buffer by the same takes that carve it.  A fresh context's scratch starts
+    empty and is grown by each call to exactly what that call measured, so a carve that took more than it measured would
+    run past the allocation here.  Each result is compared with the same call on a context whose scratch an N = 60
+    ``sc_eigh_f64`` with vectors has grown far beyond every need: kernels and arithmetic order are the same, so the results
+    agree bit for bit.  1l2y ANM, 60 modes; the calls run in the order listed.
+    """
+    from springcraft_amd import _hip
+    from springcraft_amd.interaction import _pair_list
+
+    coord = np.ascontiguousarray(ca, dtype=np.float64)
+    n = len(coord)
+    h, _ = orc.compute_hessian(coord, orc.invariant_ff(13.0))
+    h = np.ascontiguousarray(h)
+    m = 3 * n
+    assert m == 60
+    rng = np.random.RandomState(11)
+    disp, force, coef = rng.standard_normal((1, m)), rng.standard_normal((3, m)), rng.standard_normal((2, 5))
+    scale = rng.rand(n) + 0.5
+    sel, five = np.arange(6, m), np.array([6, 9, 7, -1, 30])
+    ff = _hip.make_ff_desc(_hip.SC_FF_INVARIANT, 13.0)
+    L = _hip.lib()
+
+    def eigh_range(ctx, il, iu, vectors):
+        a = h.copy()
+        w = np.empty(iu - il + 1)
+        v = np.empty((iu - il + 1, m)) if vectors else None
+        ctx.check(L.sc_eigh_range_f64(ctx.handle, _hip.ptr(a), m, il, iu, _hip.ptr(w), _hip.ptr(v)))
+        return w, v
+
+    def run(ctx, grow_first):
+        if grow_first:
+            w, v = np.empty(m), np.empty((m, m))
+            ctx.check(L.sc_eigh_f64(ctx.handle, _hip.ptr(h.copy()), m, _hip.ptr(w), _hip.ptr(v)))
+        modes = _hip.Modes.from_matrix(ctx, h, 3)
+        out = [modes.msf(sel)]
+        out += modes.overlap(sel, disp, collectivity=True)
+        out.append(modes.response(sel, force, atom_scale=scale))
+        out.append(modes.combine(five, coef))
+        out.append(modes.distfluct(sel, coord))
+        out.append(modes.dcc(sel, True))
+        out.append(modes.prs(1e-6, True))
+        out += _pair_list(ctx, coord, ff, None, True)          # capacity = the pair count, squared distances asked for
+        out.append(_pair_list(ctx, coord, ff, None, False)[0])
+        out += eigh_range(ctx, 6, 25, True)
+        out.append(eigh_range(ctx, 0, m - 1, False)[0])
+        # the empty cases: no mode, no vector; the index error comes first, whatever else is empty
+        none = np.array([], dtype=np.int64)
+        assert np.array_equal(modes.msf(none), np.zeros(n))
+        assert modes.overlap(none, disp, collectivity=True)[0].shape == (1, 0)
+        assert modes.combine(none, np.empty((2, 0))).shape == (2, m) and modes.combine(five, np.empty((0, 5))).shape == (0, m)
+        assert modes.response(sel, np.empty((0, m))).shape == (0, m)
+        for bad in (np.array([m]), np.array([6, -m - 1])):
+            with pytest.raises(IndexError):
+                modes.msf(bad)
+            with pytest.raises(IndexError):
+                modes.overlap(bad, disp)
+            with pytest.raises(IndexError):
+                modes.response(bad, np.empty((0, m)))
+            with pytest.raises(IndexError):
+                modes.combine(bad, np.empty((0, 1)))
+            with pytest.raises(IndexError):
+                modes.distfluct(bad, coord)
+        modes.close()
+        return out
+
+    fresh, grown = _hip.Context(0), _hip.Context(0)
+    try:
+        a, b = run(fresh, False), run(grown, True)
+    finally:
+        fresh.close()
+        grown.close()
+    assert len(a) == len(b) == 14
+    for x, y in zip(a, b):
+        assert x.shape == y.shape and x.size > 0 and np.array_equal(x, y)
+    assert np.all(np.isfinite(a[0])) and np.all(a[0] > 0) and len(a[8]) == len(a[9]) > 0
