@@ -120,6 +120,25 @@ int sc_dbg_stedc_host(sc_ctx* ctx, const double* d, const double* e, int n, int 
 /* Rows of the largest leaf the D&C solves by QL at order n (DcLayout::leaf_max of dc_slab_doubles). */
 int sc_dbg_stedc_leaf_max(int n);
 
+/* The partial-spectrum stage (csrc/stein.hip) on `batch` tridiagonal matrices from the host, through the product's host
+ * functions: window_count_batched (window only), stein_batched, window_compact_batched (window only).  No kernel of its
+ * own, and no unscale_values_batched: the eigenvalues are those of the T that was given.
+ *   d, e           batch x n each (e[n - 1] is not read; the layout sc_dbg_reduce_host returns)
+ *   f              null (1.0), or batch: the power-of-two factor k_window_count multiplies the bounds by (TL.hscale + 2)
+ *   own            null, or batch: the own order of every matrix as a ragged window solve passes it (window only)
+ *   window == 0    eigenpairs il .. il + m - 1 (0-based) of every matrix; vl, vu are not read
+ *   window != 0    the window (vl, vu] into slots of K = m eigenpairs; il is not read
+ *   vectors == 0   values only (stein_batched's d_x = nullptr return); z_out is not written
+ *   w_out          batch x m; z_out batch x m x n, row k = the eigenvector of w[k] (the layout of sc_eigh_f64)
+ *   win_out        null, or batch x 4 ints: the WinCount records {il, count, start, 0} (window only)
+ *   count_out      null, or batch: the window's true counts (window only)
+ * SC_ERR_INVALID_ARG, and no launch, for a null required pointer, n outside 1..46000, batch < 1, a range outside
+ * 0 <= il, il + m <= n, m >= 1, a capacity outside 1..n, !(vl < vu), or own[b] outside K..n.  The call synchronises and
+ * returns the deferred status.  tests/test_partial_ratios_gpu.py */
+int sc_dbg_partial_tridiag_host(sc_ctx* ctx, const double* d, const double* e, const double* f, const int* own, int n,
+                                int batch, int window, int il, int m, double vl, double vu, int vectors, double* w_out,
+                                double* z_out, int* win_out, long long* count_out);
+
 /* Per-wave s_memtime segment sums of k_bt2_apply (library built with -DBT2_STAMPS; returns 1 otherwise):
  * out[64 workgroups][8 waves][16 sums + diamond count].  tools/bt2_stamps.py */
 int sc_dbg_bt2_stamps(unsigned long long* out);

@@ -8,6 +8,7 @@
 #include <memory>
 #include <vector>
 
+#include "api_internal.h"
 #include "eigh_internal.h"
 #include "springcraft_hip_debug.h"
 
@@ -763,6 +764,76 @@ extern "C" int sc_dbg_stedc_host(sc_ctx* ctx, const double* d, const double* e, 
   SC_TRY(sc_deferred_status(ctx));
   SC_HIP(ctx, hipMemcpy(w_out, d_w, sizeof(double) * n * batch, hipMemcpyDeviceToHost));
   SC_HIP(ctx, hipMemcpy(z_out, d_z, elems * 8 * batch, hipMemcpyDeviceToHost));
+  return SC_OK;
+}
+
+extern "C" int sc_dbg_partial_tridiag_host(sc_ctx* ctx, const double* d, const double* e, const double* f, const int* own,
+                                           int n, int batch, int window, int il, int m, double vl, double vu,
+                                           int vectors, double* w_out, double* z_out, int* win_out,
+                                           long long* count_out) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  if (!d || !e || !w_out || (vectors && !z_out) || n < 1 || n > 46000 || batch < 1)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  if (window) {   // m is the capacity K of every slot
+    SC_TRY(check_window(ctx, vl, vu));
+    if (m < 1 || m > n) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "window capacity %d outside 1..%d", m, n);
+    for (int b = 0; own && b < batch; ++b)
+      if (own[b] < m || own[b] > n)
+        return sc_set_error(ctx, SC_ERR_INVALID_ARG, "own order %d of matrix %d outside %d..%d", own[b], b, m, n);
+    il = 0;
+  } else if (il < 0 || m < 1 || m > n || il > n - m) {
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad eigenvalue index range [%d, %d) for order %d", il, il + m, n);
+  }
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  TriLayout TL;
+  const size_t slab = tri_slab_doubles(n, &TL);
+  const size_t rows = (size_t)batch * m;
+  double *tri_ws = nullptr, *d_stein = nullptr, *d_w = nullptr, *d_x = nullptr, *d_wcopy = nullptr, *d_xcopy = nullptr;
+  GemmDesc* descs = nullptr;
+  WinCount* d_win = nullptr;
+  long long* d_count = nullptr;
+  RaggedRec* d_own = nullptr;
+  SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) {
+    tri_ws = a.take<double>(slab * batch);
+    descs = a.take<GemmDesc>(2 * (size_t)batch);
+    d_w = a.take<double>(rows);
+    if (vectors) {
+      d_stein = a.take<double>(stein_workspace_doubles(n, m) * batch);
+      d_x = a.take<double>(rows * n);
+    }
+    if (window) {
+      d_win = a.take<WinCount>((size_t)batch);
+      d_count = a.take<long long>((size_t)batch);
+      d_wcopy = a.take<double>(rows);
+      if (vectors) d_xcopy = a.take<double>(rows * n);
+      if (own) d_own = a.take<RaggedRec>((size_t)batch);
+    }
+  }));
+  for (int b = 0; b < batch; ++b) {
+    double* tri = tri_ws + (size_t)b * TL.slab;
+    const double hscale[4] = {0.0, 0.0, f ? f[b] : 1.0, 0.0};   // [2] the factor k_window_count reads, [3] its "bad" word
+    SC_TRY(sc_stage_upload(ctx, tri + TL.d, d + (size_t)b * n, sizeof(double) * n));
+    SC_TRY(sc_stage_upload(ctx, tri + TL.e, e + (size_t)b * n, sizeof(double) * n));
+    SC_TRY(sc_stage_upload(ctx, tri + TL.hscale, hscale, sizeof(hscale)));
+  }
+  if (window) {
+    if (own) {
+      std::vector<RaggedRec> rec((size_t)batch, RaggedRec{});
+      for (int b = 0; b < batch; ++b) rec[(size_t)b].own = own[b];
+      SC_TRY(sc_stage_upload(ctx, d_own, rec.data(), sizeof(RaggedRec) * batch));
+    }
+    SC_TRY(window_count_batched(ctx, batch, tri_ws, TL, vl, vu, m, d_win, d_count, d_own));
+  }
+  SC_TRY(stein_batched(ctx, n, batch, tri_ws, TL, il, il + m - 1, d_w, m, d_x, (long long)n * m, d_stein, descs, d_win));
+  if (window) SC_TRY(window_compact_batched(ctx, n, batch, m, d_win, d_w, d_x, d_wcopy, d_xcopy));
+  SC_TRY(sc_stage_end(ctx));
+  SC_HIP(ctx, hipStreamSynchronize(st));
+  SC_TRY(sc_deferred_status(ctx));
+  SC_HIP(ctx, hipMemcpy(w_out, d_w, sizeof(double) * rows, hipMemcpyDeviceToHost));
+  if (vectors) SC_HIP(ctx, hipMemcpy(z_out, d_x, sizeof(double) * rows * n, hipMemcpyDeviceToHost));
+  if (window && win_out) SC_HIP(ctx, hipMemcpy(win_out, d_win, sizeof(WinCount) * batch, hipMemcpyDeviceToHost));
+  if (window && count_out) SC_HIP(ctx, hipMemcpy(count_out, d_count, sizeof(long long) * batch, hipMemcpyDeviceToHost));
   return SC_OK;
 }
 

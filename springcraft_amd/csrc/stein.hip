@@ -322,10 +322,12 @@ __global__ __launch_bounds__(64) void k_stein(const double* __restrict__ tri_all
   const double tiny = kEpsS * tnorm;
   double lam = w[j];
   {
-    // shift members of a run of (near-)equal eigenvalues apart by multiples of 10 eps |T|
-    int run = 0;
-    for (int q = j - 1; q >= 0 && fabs(w[q] - w[q + 1]) <= 10.0 * tiny; --q) ++run;
-    lam += run * 10.0 * tiny;
+    // keep every shift at least 10 eps |T| above the one before it, as dstein does (xj = xjm + pertol): members of a run
+    // of equal eigenvalues end up multiples of 10 eps |T| apart, and no shift passes the one behind it.  Every lane walks
+    // w[0 .. j]: O(m) cached reads per vector, next to its nine passes over n rows of records
+    double prev = w[0];
+    for (int q = 1; q <= j; ++q) prev = fmax(w[q], prev + 10.0 * tiny);
+    lam = prev;
   }
 #define FAT(k) F[(size_t)(k) * m + j]
 #define BAT(k) B[(size_t)(k) * m + j]

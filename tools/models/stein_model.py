@@ -4,7 +4,8 @@ NumPy restatement of the partial-spectrum eigenvectors of stein.hip: k_stein (in
 order, and the rules are the kernel's:
 
   - tnorm = max_i |d_i| + |e_i| + |e_{i-1}| (1 if 0), tiny = eps tnorm;
-  - a run of near-equal eigenvalues (|w_q - w_{q+1}| <= 10 tiny) shifts member j by (members before it in the run) x 10 tiny;
+  - every shift is kept at least 10 tiny above the one before it (lam_j = max(w_j, lam_{j-1} + 10 tiny), dstein's rule):
+    members of a run of equal eigenvalues end up multiples of 10 tiny apart;
   - LU of T - lam I with partial pivoting between rows k and k + 1 (swap when |e_k| > |p|), a kept pivot below tiny
     replaced by +-tiny (+tiny for an exact zero), the last one too;
   - the start vector hash_unit(j + 1, i + 1), 4 iterations of forward / backward substitution, each rescaled by its max
@@ -46,29 +47,24 @@ def tnorm(d, e):
 
 
 def shifts(w, tiny):
-    """The shifted eigenvalues k_stein factorises with: member j of a run moved up by (its place in the run) x 10 tiny."""
-    w = np.asarray(w, dtype=np.float64)
-    lam = w.copy()
-    for j in range(len(w)):
-        run = 0
-        q = j - 1
-        while q >= 0 and abs(w[q] - w[q + 1]) <= 10.0 * tiny:
-            run += 1
-            q -= 1
-        lam[j] += run * 10.0 * tiny
+    """The shifted eigenvalues k_stein factorises with: each at least 10 tiny above the one before it."""
+    lam = np.asarray(w, dtype=np.float64).copy()
+    for j in range(1, len(lam)):
+        lam[j] = max(lam[j], lam[j - 1] + 10.0 * tiny)
     return lam
 
 
-def stein(d, e, w, iterations=4):
+def stein(d, e, w, iterations=4, shift_rule=None):
     """
     k_stein: the vectors (n x m, columns) of the eigenvalues w (ascending, as k_sturm_range returns them) of the
     tridiagonal matrix (d, e), before the orthonormalisation.  Returns (X, replaced pivots per vector).
+    shift_rule(w, tiny): another rule than shifts() -- what the kernel would deliver with it.
     """
     d = np.asarray(d, dtype=np.float64)
     e = np.asarray(e, dtype=np.float64)
     n, m = len(d), len(w)
     tiny = EPS * tnorm(d, e)
-    lam = shifts(w, tiny)
+    lam = (shift_rule or shifts)(w, tiny)
     mult = np.zeros((max(n - 1, 0), m))
     swap = np.zeros((max(n - 1, 0), m), dtype=bool)
     b0, b1, b2 = np.zeros((n, m)), np.zeros((n, m)), np.zeros((n, m))
@@ -155,8 +151,8 @@ def cholqr2(x, rounds=2):
     return x, rel
 
 
-def eigenvectors(d, e, w, iterations=4, rounds=2):
+def eigenvectors(d, e, w, iterations=4, rounds=2, shift_rule=None):
     """The partial-spectrum vectors (n x m, columns) for the eigenvalues w of (d, e), and diagnostics."""
-    x, replaced = stein(d, e, w, iterations)
+    x, replaced = stein(d, e, w, iterations, shift_rule)
     q, rel = cholqr2(x, rounds)
     return q, {"replaced_pivots": int(replaced.sum()), "chol_min_pivot": rel}

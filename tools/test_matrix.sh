@@ -1,7 +1,7 @@
 #!/bin/bash
 # The eigensolver tests under every switch that selects an alternative code path (on the GPU box):  bash tools/test_matrix.sh
 set -u
-T="tests/test_two_stage_gpu.py tests/test_eigh_gpu.py tests/test_batched_configs_gpu.py tests/test_gemm_gpu.py tests/test_gemm_records_gpu.py tests/test_resident_gpu.py tests/test_partial_spectrum_gpu.py tests/test_stage_ratios_gpu.py"
+T="tests/test_two_stage_gpu.py tests/test_eigh_gpu.py tests/test_batched_configs_gpu.py tests/test_gemm_gpu.py tests/test_gemm_records_gpu.py tests/test_resident_gpu.py tests/test_partial_spectrum_gpu.py tests/test_stage_ratios_gpu.py tests/test_partial_ratios_gpu.py"
 # (in parts, a gpurun call is limited to 20 minutes:  bash tools/test_matrix.sh <part> [parts = 2]; no argument: everything)
 HALF=${1:-0}
 PARTS=${2:-2}
