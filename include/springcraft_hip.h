@@ -400,6 +400,11 @@ int sc_modes_dcc(sc_modes* modes, const int64_t* mode_idx, int64_t k, int norm, 
 /* ANM only. out (n / 3, n / 3) row-major: sums of the squared 3x3 blocks of pinv(H, rcond) (numpy hermitian
  * rule); norm != 0 divides row a by out[a, a]. */
 int sc_modes_prs(sc_modes* modes, double rcond, int norm, double* out);
+/* The same matrix over the k listed modes only (no reference counterpart: the reference scans the whole covariance):
+ * out[a, c] = sum over the 3 x 3 entries of (sum_i v_i[a] v_i[c]^T / w_i)^2, i over the list in its order, a mode listed
+ * twice counts twice.  ANM only; a mode index outside 0..n-1 (negative ones count from the end): SC_ERR_INDEX; k = 0 gives
+ * zeros (NaN under norm).  Computed by sc_dev_prs_f64's kernel with a batch of one: no (n, n) covariance is formed. */
+int sc_modes_prs_subset(sc_modes* modes, const int64_t* mode_idx, int64_t k, int norm, double* out);
 
 /* ---- the same consumers for a batch: device pointers in, device pointers out, enqueue only ------------------------
  * What nma.py:108-184 (mean_square_fluctuation) and nma.py:233-359 (dcc) derive from nma.eigen for ONE model, for every
@@ -490,6 +495,22 @@ int sc_dev_modes_overlap_f64(sc_ctx* ctx, const double* d_v, int64_t m, int64_t 
 int sc_dev_modes_distfluct_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
                                const sc_mode_selection* sel, const int64_t* d_counts, const double* d_coord,
                                const double* d_atom_scale, double* d_out);
+/* Perturbation-response scanning (nma.py:476-524 prs, there cov**2 of one model reduced by two reduceat) for a batch and
+ * over the selected rows.  ANM only: m = 3 N (m % 3 != 0: SC_ERR_INVALID_ARG), d_out (batch, N, N),
+ *
+ *   C_ac[d, e] = sum_r s[b, r] u_r[a][d] u_r[c][e],   u_r[a] = t_a V[b, r, 3 a .. 3 a + 2]
+ *   P[b, a, c] = sum_{d, e} C_ac[d, e]^2              norm != 0: P[b, a, c] / P[b, a, a]
+ *
+ * t = d_atom_scale (batch, N) or NULL for 1 (a mass-weighted solve passes 1 / sqrt(mass) for the Cartesian covariance).
+ * One kernel on the float64 matrix units: a block C_ac is accumulated and squared in registers, no covariance entry is
+ * written to memory and the only workspace is the weights and one diagonal per structure.  Every unordered pair is computed
+ * once, so without norm P equals its transpose bit for bit; no atomics and no partial sums, so a structure's result does
+ * not depend on the batch size, its position or its neighbours, bit for bit.  A row without weight is not read, nor is a
+ * listed row outside 0..nvec-1, which turns the structure's result into NaN; an empty selection gives zeros, and NaN
+ * under norm.  Enqueue only. */
+int sc_dev_prs_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                   const sc_mode_selection* sel, const int64_t* d_counts, const double* d_atom_scale, int norm,
+                   double* d_out);
 /* Linear response to q forces per structure over the selected rows (nma.py:422-473 linear_response = covariance @ force,
  * there for one model and through the (3N, 3N) pseudo-inverse), in mode space: no covariance and no m x m workspace.
  *
@@ -524,7 +545,8 @@ int sc_dev_mode_combine_f64(sc_ctx* ctx, const double* d_v, int64_t m, int64_t n
  * nvec for SC_SEL_PINV); what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3 and m % 3 == 0, else 0), 3 = overlaps /
  * collectivities (always 0: sc_dev_modes_overlap_f64 holds no workspace), 4 = distance fluctuations (the weights only; dim
  * 3 and m % 3 == 0, else 0), 5 = response (weights, the coefficients of four forces and the partial sums of a slab), 6 =
- * combine (the partial sums of a slab); budget_bytes as above. */
+ * combine (the partial sums of a slab), 7 = perturbation-response scanning (the weights and one diagonal per structure
+ * of a slab of at most 32768; dim 3 and m % 3 == 0, else 0); budget_bytes as above. */
 int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
                                      int64_t budget_bytes);
 
@@ -580,6 +602,13 @@ int sc_batch_plan_modes_overlap_f64(sc_batch_plan* plan, const double* d_v, int6
 int sc_batch_plan_modes_distfluct_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
                                       const sc_mode_selection* sel, const int64_t* d_counts, const double* d_coord,
                                       const double* d_atom_scale, double* d_out);
+/* perturbation-response scanning (a plan of dim 1: SC_ERR_INVALID_ARG), as sc_dev_prs_f64: d_atom_scale (sum n_atoms,)
+ * packed or NULL, N the structure's own n_atoms, d_out (sum n_atoms^2,) packed like the dcc.  Pad rows never carry a
+ * weight, pad columns are never read.  A structure's bits depend on its own size and the selection, not on its
+ * neighbours or its position. */
+int sc_batch_plan_prs_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
+                          const sc_mode_selection* sel, const int64_t* d_counts, const double* d_atom_scale, int norm,
+                          double* d_out);
 /* sc_dev_mode_response_f64 for the plan's padded slots (GNM and ANM plans; sel->reserved holds first_row as for the
  * sc_batch_plan_modes_* entries above): d_force and d_out (q, dim * sum n_atoms)
  * packed as sc_batch_plan_modes_overlap_f64's displacement is, structure b's vector j at j * dim * sum n + dim *

@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = [
     "sc_modes_distfluct", "sc_dev_modes_distfluct_f64", "sc_batch_plan_modes_distfluct_f64",
     "sc_modes_response", "sc_dev_mode_response_f64", "sc_batch_plan_mode_response_f64",
     "sc_modes_combine", "sc_dev_mode_combine_f64", "sc_batch_plan_mode_combine_f64",
+    "sc_modes_prs_subset", "sc_dev_prs_f64", "sc_batch_plan_prs_f64",
     "sc_dev_rtb_hessian_f64", "sc_dev_rtb_expand_f64",
     "sc_dev_pairs_apply_f64", "sc_dev_pairs_strain_f64", "sc_dev_pairs_panel_f64",
     "sc_dev_pairs_cg_workspace", "sc_dev_pairs_cg_init_f64", "sc_dev_pairs_cg_step_f64",
@@ -247,6 +248,9 @@ def lib():
         "sc_modes_combine": (i32, [vp, vp, i64, vp, i64, vp]),
         "sc_dev_mode_combine_f64": (i32, [vp, vp, i64, i64, i64, i32, vp, i64, vp, vp, vp]),
         "sc_batch_plan_mode_combine_f64": (i32, [vp, vp, i64, i64, vp, i64, vp, vp, vp]),
+        "sc_modes_prs_subset": (i32, [vp, vp, i64, i32, vp]),
+        "sc_dev_prs_f64": (i32, [vp, vp, vp, i64, i64, i64, P(ModeSelection), vp, vp, i32, vp]),
+        "sc_batch_plan_prs_f64": (i32, [vp, vp, vp, i64, P(ModeSelection), vp, vp, i32, vp]),
         "sc_dev_rtb_hessian_f64": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp]),
         "sc_dev_rtb_expand_f64": (i32, [vp, vp, i64, i64, vp, vp, vp, i64, vp]),
         "sc_dev_pairs_apply_f64": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, i64, vp, vp]),
@@ -469,6 +473,14 @@ class Modes:
         n = self.order // 3
         out = host_array((n, n))
         self._ctx.check(self._L.sc_modes_prs(self._h, float(rcond), int(bool(norm)), ptr(out)))
+        return out
+
+    def prs_subset(self, mode_idx, norm):
+        """(n_atoms, n_atoms) PRS matrix over the listed modes alone, from the batch kernel: no covariance is formed."""
+        idx = self._index_list(mode_idx)
+        n = self.order // 3
+        out = host_array((n, n))
+        self._ctx.check(self._L.sc_modes_prs_subset(self._h, ptr(idx), len(idx), int(bool(norm)), ptr(out)))
         return out
 
     def close(self):

@@ -116,8 +116,11 @@ class ANM(ElasticNetworkModel):
         """Collectivity of the selected modes, (k,) (:func:`nma.collectivity`)."""
         return nma.collectivity(self, mode_subset)
 
-    def prs_effector_sensor(self, norm=True):
-        """PRS matrix plus effector / sensor profiles (anm.py:384-445)."""
-        prs_mat = nma.prs(self, norm)
+    def prs_effector_sensor(self, norm=True, mode_subset=None):
+        """
+        PRS matrix plus effector / sensor profiles (anm.py:384-445); ``mode_subset`` (extension): over the listed modes
+        alone (:func:`nma.prs`).
+        """
+        prs_mat = nma.prs(self, norm, mode_subset)
         eff, sens = nma.effector_sensor(prs_mat)
         return prs_mat, eff, sens

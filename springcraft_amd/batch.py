@@ -124,6 +124,13 @@ def _aniso_expand(solver, packed):
     return packed.index_select(-1, solver._aniso_index).view(*packed.shape[:-1], 3, 3)
 
 
+def _effector_sensor(torch, prs):
+    """Means of the off-diagonal entries of (..., N, N) PRS matrices along every row and every column (nma.py:527-569)."""
+    n = prs.shape[-1]
+    off = prs - torch.diag_embed(prs.diagonal(dim1=-2, dim2=-1))
+    return off.sum(dim=-1) / (n - 1), off.sum(dim=-2) / (n - 1)
+
+
 def _trivial_rows(ntriv, first_row, nvec):
     """
     How many of a solver's ``nvec`` rows, row r being global mode ``first_row + r``, are trivial modes: the first row of
@@ -265,6 +272,10 @@ _FIELD_ENTRIES = {
     "combine": ("sc_dev_mode_combine_f64", ("ctx", "v", "m", "nvec", "batch", "dim"),
                 "sc_batch_plan_mode_combine_f64", ("plan", "v", "nvec", "first_row")),
 }
+# the same for perturbation-response scanning (csrc/mode_prs.hip): its C entries are named sc_dev_prs_f64 / sc_batch_plan_prs_f64
+_SCAN_ENTRIES = {
+    "prs": ("sc_dev_prs_f64", _DEV, "sc_batch_plan_prs_f64", _PLAN),
+}
 
 
 class _BatchSolver:
@@ -380,7 +391,7 @@ class _BatchSolver:
 
     def _call(self, consumer, *args):
         """Enqueues ``consumer``'s C entry for this solver's layout: the entry's argument prefix, then ``args``."""
-        row = _CONSUMER_ENTRIES[consumer] if consumer in _CONSUMER_ENTRIES else _FIELD_ENTRIES[consumer]
+        row = next(t[consumer] for t in (_CONSUMER_ENTRIES, _FIELD_ENTRIES, _SCAN_ENTRIES) if consumer in t)
         entry, prefix = row[2:] if self._layout.ragged else row[:2]
         have = {"ctx": self.ctx.handle, "plan": self._plan, "w": C.c_void_p(self.w.data_ptr()),
                 "v": C.c_void_p(self.v.data_ptr()), "m": self.v.shape[2], "nvec": self.w.shape[1], "batch": self.batch,
@@ -679,6 +690,46 @@ class _BatchSolver:
             buf *= tem
             buf *= tem_factors
         return self._layout.pairs_out(buf)
+
+    def prs(self, mode_subset=None, norm=True, atom_scale=None):
+        """
+        (batch, n_atoms, n_atoms) perturbation-response-scanning matrices (nma.py:476-524, there ``cov**2`` of one model
+        reduced over its 3 x 3 blocks): ``P[b, a, c] = sum_{d, e} C_ac[d, e]^2`` with ``C_ac = sum_k u_k[a] u_k[c]^T /
+        lambda_k`` over the selected modes; ``norm`` divides row a by ``P[b, a, a]``.  One kernel on the float64 matrix
+        units (``csrc/mode_prs.hip``): a block ``C_ac`` is summed and squared in registers and no covariance entry is
+        written to memory.  ANM solvers only (``dim != 3`` raises the reference's ValueError before anything is enqueued).
+
+        ``mode_subset``, the window, ``subset_by_index`` and failed structures (NaN) exactly as in :meth:`dcc`: None on a
+        full-spectrum solver takes the reference's covariance rule, every mode with ``|lambda| > 1e-6 max|lambda|`` of
+        that structure; an empty window gives zeros, and NaN under ``norm=True`` as 0 / 0 does in NumPy.  ``atom_scale``:
+        None, or a (batch, n_atoms) CUDA float64 tensor with ``u_k[a] = atom_scale[a] * v_k[a]``; None takes the rows of
+        ``v`` as they are, so a solver with ``masses`` wants ``atom_scale=solver.inv_sqrt_mass`` for the Cartesian
+        covariance.  With ``norm=False`` the result equals its transpose bit for bit and every entry is >= 0; a
+        structure's bits do not depend on the batch size, its position or its neighbours.  Only enqueues.
+        Ragged: [(n_i, n_i), ...], views into one buffer packed like :meth:`dcc`'s; ``atom_scale`` None or a packed
+        (sum(sizes),) tensor.
+        """
+        lay = self._layout
+        if self.dim != 3:
+            raise ValueError("Instance of ANM class expected.")
+        self._need_vectors()
+        sp = None if atom_scale is None else self._device_f64(atom_scale, lay.atoms_shape(), "atom_scale")
+        sel, counts = self._selection(mode_subset, pinv_default=True)
+        buf = self._empty(lay.pairs_shape())
+        self._call("prs", C.byref(sel), counts, sp, int(bool(norm)), C.c_void_p(buf.data_ptr()))
+        return lay.pairs_out(buf)
+
+    def prs_effector_sensor(self, mode_subset=None, norm=True, atom_scale=None):
+        """
+        ``(prs, effector, sensor)``: :meth:`prs` and the means of its off-diagonal entries along every row (effector) and
+        every column (sensor) (nma.py:527-569), (batch, n_atoms) each, computed with torch operations on the result and
+        left on the device.  Ragged: three lists, [(n_i, n_i), ...] and [(n_i,), ...] twice.
+        """
+        out = self.prs(mode_subset, norm, atom_scale)
+        if not self._layout.ragged:
+            return (out,) + _effector_sensor(self.torch, out)
+        profiles = [_effector_sensor(self.torch, p) for p in out]
+        return out, [e for e, _ in profiles], [s for _, s in profiles]
 
 
 class DeviceBatchSolver(_BatchSolver):

@@ -275,6 +275,15 @@ int sc_modes_combine(sc_modes* m, const int64_t* mode_idx, int64_t k, const doub
   });
 }
 
+int sc_modes_prs_subset(sc_modes* m, const int64_t* mode_idx, int64_t k, int norm, double* out) {
+  if (!m) return SC_ERR_INVALID_ARG;
+  if (m->dim != 3) return sc_set_error(m->ctx, SC_ERR_INVALID_ARG, "perturbation response scanning needs an ANM (dim 3)");
+  const size_t N = (size_t)(m->n / 3);
+  return modes_out_call(m, mode_idx, k, N * N, out, [m, norm](const sc_mode_selection& sel, double* d_out) {
+    return batch_prs_device(m->ctx, m->d_w, m->d_v, m->n, m->n, 1, sel, nullptr, nullptr, norm, d_out);
+  });
+}
+
 int sc_modes_prs(sc_modes* m, double rcond, int norm, double* out) {
   if (!m) return SC_ERR_INVALID_ARG;
   sc_ctx* ctx = m->ctx;

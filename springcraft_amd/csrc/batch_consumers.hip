@@ -408,6 +408,7 @@ int64_t batch_modes_nsel(const sc_mode_selection& sel, int64_t nvec) {
 
 // weights (batch, n_sel) | msf, tensors: partial sums of one slab | dcc: P and S of one slab, diagonals (batch, N), records |
 // distance fluctuations: nothing more | response, combine (mode_response.hip): coefficients and partial sums, partial sums
+// | scanning (mode_prs.hip): one diagonal per structure of a slab
 // (ragged: m is the slot order, the diagonals are packed over all atoms)
 size_t batch_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t nsel, int what,
                                    size_t budget, const RaggedView* rv) {
@@ -422,6 +423,8 @@ size_t batch_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int d
     bytes += align_up((size_t)aniso_slab(m, nsel, batch, budget) * ((nsel + chunk - 1) / chunk) * 6 * (m / 3) * 8, 256);
   } else if (what == 4) {
     // distance fluctuations (dist_fluct.hip): the weights alone, a pair's sum never leaves its lane
+  } else if (what == 7) {
+    bytes += modes_prs_diag_bytes(m, batch, rv);
   } else if (what == 5) {
     bytes += modes_response_workspace_bytes(m, batch, nsel, 5, budget);
   } else if (what == 6) {

@@ -296,7 +296,7 @@ int modes_prs_device(sc_ctx* ctx, const double* d_v, const double* d_w, int64_t 
                      char* scratch, double* d_out);
 
 // ---- the same quantities for a batch, on the solver's own (w, v, counts) tensors (batch_consumers.hip) ----------
-// what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3), 4 = distance fluctuations (dim 3; dist_fluct.hip), 5 = response, 6 = combine (mode_response.hip).  n_sel: weighted rows per structure (batch_modes_nsel).  budget: bytes the partial sums (msf) /
+// what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3), 4 = distance fluctuations (dim 3; dist_fluct.hip), 5 = response, 6 = combine (mode_response.hip), 7 = perturbation-response scanning (dim 3; mode_prs.hip).  n_sel: weighted rows per structure (batch_modes_nsel).  budget: bytes the partial sums (msf) /
 // the packed GEMM operands (dcc) may take, 0 = modes_budget_default().  ragged: null for a uniform batch (d_out (batch,
 // m / dim[, m / dim])), or the plan's records: m is then the slot order and d_out is packed.
 // Ragged batches (sc_batch_plan): one record per structure in the plan's device blob, read by the window count and the
@@ -334,6 +334,16 @@ int batch_aniso_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_
 int batch_distfluct_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
                            const sc_mode_selection& sel, const int64_t* d_counts, const double* d_coord,
                            const double* d_atom_scale, double* d_out, const RaggedView* ragged = nullptr);
+
+// ---- perturbation-response scanning over the selected rows (mode_prs.hip) --------------------------------------------
+// dim 3 only: d_out[b, a, c] = sum_{d, e} (sum_r s[b, r] u_r[a][d] u_r[c][e])^2, the sum of the squared entries of the 3 x 3
+// covariance block (a, c), u_r[a] = d_atom_scale[b, a] (null: 1) times the atom's three components of row r; no covariance
+// entry is written to memory.  Without norm exactly symmetric; norm != 0 divides row a by the original d_out[b, a, a].
+// Ragged: the scale packed at atom_off, d_out packed at sq_off.  Enqueue only.
+size_t modes_prs_diag_bytes(int64_t m, int64_t batch, const RaggedView* ragged);
+int batch_prs_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                     const sc_mode_selection& sel, const int64_t* d_counts, const double* d_atom_scale, int norm,
+                     double* d_out, const RaggedView* ragged = nullptr);
 
 // ---- overlaps with displacement vectors and collectivities of the modes (mode_overlap.hip) -----------------------
 // One pass over the rows of d_v (batch, nvec, m): d_overlap (batch, q, nout) and d_coll (batch, nout), either may be null

@@ -74,10 +74,8 @@ __global__ __launch_bounds__(256) void k_dist_fluct(const DistFluctArgs A) {
   __shared__ double lds[kRows * 2 * kSide];
   const int tid = threadIdx.x;
   const int t = blockIdx.x;
-  int ta = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-  while ((ta + 1) * (ta + 2) / 2 <= t) ++ta;
-  while (ta * (ta + 1) / 2 > t) --ta;
-  const int tc = t - ta * (ta + 1) / 2;
+  int ta, tc;
+  tri_tile_decode(t, ta, tc);
   const int b = A.b0 + blockIdx.y;
   const int N = A.rag ? A.rag[b].n_atoms : A.m / 3;
   const int a0 = ta * kTile, c0 = tc * kTile;   // c0 <= a0

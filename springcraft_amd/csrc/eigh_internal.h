@@ -176,3 +176,13 @@ int launch_mode_weights(sc_ctx* ctx, const double* d_w, int64_t nvec, int64_t ba
 // mode_response.hip's combine): a function of the number of listed rows alone, so that a structure's bits are the same
 // in any batch.
 int msf_chunk(int64_t nsel);
+#ifdef __HIPCC__
+// Tile t of the lower triangle of a square of tiles, rows first: t = ta (ta + 1) / 2 + tc with tc <= ta (dist_fluct.hip,
+// mode_prs.hip: every unordered pair of tiles has one workgroup).  The float root is a first guess, the loops make it exact.
+__device__ __forceinline__ void tri_tile_decode(int t, int& ta, int& tc) {
+  ta = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+  while ((ta + 1) * (ta + 2) / 2 <= t) ++ta;
+  while (ta * (ta + 1) / 2 > t) --ta;
+  tc = t - ta * (ta + 1) / 2;
+}
+#endif

@@ -539,12 +539,27 @@ def spring_strain(enm, mode_subset=None):
     return op.springs, op.strain(v).cpu().numpy()
 
 
-def prs(anm, norm=True):
-    """Perturbation-response-scanning matrix from the squared covariance (nma.py:476-524)."""
+def prs(anm, norm=True, mode_subset=None):
+    """
+    Perturbation-response-scanning matrix from the squared covariance (nma.py:476-524).
+
+    ``mode_subset=None`` is the reference: the covariance is ``pinv(hessian, rcond=1e-6)``, or the matrix the caller
+    assigned.  ``mode_subset`` (extension) scans the covariance restricted to the listed modes, ``sum_k v_k v_k^T /
+    lambda_k``, as in :func:`mean_square_fluctuation`: trivial indices raise ValueError, a mode listed twice counts twice.
+    That matrix is never formed: its 3 x 3 blocks are summed and squared in registers on the device-resident eigenpairs
+    (``csrc/mode_prs.hip``, the kernel of the batch solvers' ``prs``).  It cannot be combined with an assigned covariance,
+    which has no modes: ValueError.
+    """
     from .anm import ANM
 
     if not isinstance(anm, ANM):
         raise ValueError("Instance of ANM class expected.")
+    if mode_subset is not None:
+        mode_subset = _mode_selection(anm, mode_subset, None)   # (the trivial-mode error needs no device)
+        if anm._covariance is not None:
+            raise ValueError("mode_subset cannot be combined with a covariance that is already on the model: "
+                             "that matrix has no modes to select from")
+        return anm._modes_device().prs_subset(mode_subset, norm)
     if anm._covariance is not None:
         # a covariance the caller assigned (or already fetched): reduce that very matrix
         c2 = anm._covariance**2
