@@ -405,6 +405,18 @@ int sc_modes_prs(sc_modes* modes, double rcond, int norm, double* out);
  * twice counts twice.  ANM only; a mode index outside 0..n-1 (negative ones count from the end): SC_ERR_INDEX; k = 0 gives
  * zeros (NaN under norm).  Computed by sc_dev_prs_f64's kernel with a batch of one: no (n, n) covariance is formed. */
 int sc_modes_prs_subset(sc_modes* modes, const int64_t* mode_idx, int64_t k, int norm, double* out);
+/* How the modes of model a compare with those of model b: no reference counterpart (Bio3D: rmsip / covsoverlap; ProDy:
+ * calcSubspaceOverlap / calcCovOverlap / calcOverlap of two mode sets).  Host pointers.  The two objects must belong to one
+ * context and have the same dim and order (SC_ERR_INVALID_ARG otherwise: structures of different size have no common
+ * coordinates).  With G[i, j] = <v_a,i, v_b,j> over the k_a / k_b listed modes and S = sum_ij p_a,i p_b,j G[i, j]^2:
+ *   kind 0, RMSIP:              p = 1, t = k:                     *out_value = sqrt(S / sqrt(t_a t_b))   (Amadei's sqrt(sum G^2 / k) for k_a = k_b = k)
+ *   kind 1, covariance overlap: p = 1 / sqrt(w), t = sum 1 / w:   *out_value = 1 - sqrt(max(0, t_a + t_b - 2 S) / (t_a + t_b))       (Hess 2002)
+ * out_gram: NULL, or (k_a, k_b) for G itself, the table one matches modes with; out_value may be NULL when it is given.  A
+ * NULL list (its k must be 0, out_gram NULL): every mode with |w| > rcond max|w|, the covariance rule of sc_modes_prs; rcond
+ * is not read otherwise.  A mode index outside 0..n-1 (negative ones count from the end): SC_ERR_INDEX; a mode listed twice
+ * counts twice.  Computed by sc_dev_subspace_f64's kernel on two batches of one. */
+int sc_modes_subspace(sc_modes* a, sc_modes* b, const int64_t* mode_idx_a, int64_t k_a, const int64_t* mode_idx_b,
+                      int64_t k_b, double rcond, int kind, double* out_value, double* out_gram);
 
 /* ---- the same consumers for a batch: device pointers in, device pointers out, enqueue only ------------------------
  * What nma.py:108-184 (mean_square_fluctuation) and nma.py:233-359 (dcc) derive from nma.eigen for ONE model, for every
@@ -511,6 +523,37 @@ int sc_dev_modes_distfluct_f64(sc_ctx* ctx, const double* d_w, const double* d_v
 int sc_dev_prs_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
                    const sc_mode_selection* sel, const int64_t* d_counts, const double* d_atom_scale, int norm,
                    double* d_out);
+/* How the modes of structure a compare with those of structure b, for every pair of two uniform batches of one m: no
+ * reference counterpart (Bio3D: rmsip / covsoverlap; ProDy: calcSubspaceOverlap / calcCovOverlap); replaces copying d_v
+ * to the host.  Two operand sets (d_w, d_v, sel, d_counts, nvec, batch) as above, each with its own selection; GNM and ANM.
+ *
+ *   G_ab[i, j] = <V_a[row_a(i)], V_b[row_b(j)]>      S[a, b] = sum_ij p[a, i] p[b, j] G_ab[i, j]^2
+ *   kind 0, RMSIP:               p = 1 for a selected row,            t = sum_i p,      d_out[a, b] = sqrt(S / sqrt(t_a t_b))
+ *   kind 1, covariance overlap:  p = 1 / sqrt(w) for a selected row,  t = sum_i 1 / w,  d_out[a, b] = 1 - sqrt(max(0, t_a + t_b - 2 S) / (t_a + t_b))
+ *
+ * p is exactly 0 for every other row.  d_out (batch_a, batch_b); d_s NULL or the raw S of that shape; d_t_a (batch_a) and
+ * d_t_b (batch_b) NULL or t.  d_v_b NULL: the first set with itself -- every other argument of the second set must be NULL
+ * / is not read, only the pairs a >= b are computed and both places written from one value, so d_out equals its transpose
+ * bit for bit.  One kernel on the float64 matrix units: a tile of G_ab is accumulated along m, squared and summed in
+ * registers; no entry of G reaches memory, the workspace is the weights and one partial sum per (pair, tile).  No
+ * atomics, no split along m, one tile size per call from the numbers of listed rows alone: an entry's bits depend on
+ * the two structures' own (w, v, selection) and the side each is on, not on the batch sizes, their positions or their
+ * neighbours.  A row without weight is not read, nor is a listed row outside 0..nvec-1; such a row, and NaN eigenvalues (a
+ * failed structure), turn that structure's row and column of d_out into NaN and no other entry.  An empty selection gives
+ * S = 0 (RMSIP: 0 / 0 = NaN).  kind 1 wants positive eigenvalues: a selected w < 0 gives NaN.  Enqueue only. */
+int sc_dev_subspace_f64(sc_ctx* ctx, const double* d_w_a, const double* d_v_a, const sc_mode_selection* sel_a,
+                        const int64_t* d_counts_a, int64_t nvec_a, int64_t batch_a, const double* d_w_b,
+                        const double* d_v_b, const sc_mode_selection* sel_b, const int64_t* d_counts_b, int64_t nvec_b,
+                        int64_t batch_b, int64_t m, int kind, double* d_out, double* d_s, double* d_t_a, double* d_t_b);
+/* The raw G_ab above, the table one matches modes with, for the n_pairs listed pairs: d_pairs int32 (n_pairs, 2) in DEVICE
+ * memory, (structure of the first set, structure of the second); d_out (n_pairs, n_a, n_b) with n_a / n_b the listed rows of
+ * the two selections.  The same kernel with a store in place of the squared sum.  d_v_b NULL: both structures of a pair
+ * come from the first set.  A pair that names no structure gives NaN, as do NaN eigenvalues and a listed row outside
+ * 0..nvec-1; a row without weight gives zeros.  Enqueue only. */
+int sc_dev_subspace_gram_f64(sc_ctx* ctx, const double* d_w_a, const double* d_v_a, const sc_mode_selection* sel_a,
+                             int64_t nvec_a, int64_t batch_a, const double* d_w_b, const double* d_v_b,
+                             const sc_mode_selection* sel_b, int64_t nvec_b, int64_t batch_b, int64_t m,
+                             const int32_t* d_pairs, int64_t n_pairs, double* d_out);
 /* Linear response to q forces per structure over the selected rows (nma.py:422-473 linear_response = covariance @ force,
  * there for one model and through the (3N, 3N) pseudo-inverse), in mode space: no covariance and no m x m workspace.
  *

@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = [
     "sc_modes_response", "sc_dev_mode_response_f64", "sc_batch_plan_mode_response_f64",
     "sc_modes_combine", "sc_dev_mode_combine_f64", "sc_batch_plan_mode_combine_f64",
     "sc_modes_prs_subset", "sc_dev_prs_f64", "sc_batch_plan_prs_f64",
+    "sc_modes_subspace", "sc_dev_subspace_f64", "sc_dev_subspace_gram_f64",
     "sc_dev_rtb_hessian_f64", "sc_dev_rtb_expand_f64",
     "sc_dev_pairs_apply_f64", "sc_dev_pairs_strain_f64", "sc_dev_pairs_panel_f64",
     "sc_dev_pairs_cg_workspace", "sc_dev_pairs_cg_init_f64", "sc_dev_pairs_cg_step_f64",
@@ -251,6 +252,11 @@ def lib():
         "sc_modes_prs_subset": (i32, [vp, vp, i64, i32, vp]),
         "sc_dev_prs_f64": (i32, [vp, vp, vp, i64, i64, i64, P(ModeSelection), vp, vp, i32, vp]),
         "sc_batch_plan_prs_f64": (i32, [vp, vp, vp, i64, P(ModeSelection), vp, vp, i32, vp]),
+        "sc_modes_subspace": (i32, [vp, vp, vp, i64, vp, i64, dbl, i32, vp, vp]),
+        "sc_dev_subspace_f64": (i32, [vp, vp, vp, P(ModeSelection), vp, i64, i64, vp, vp, P(ModeSelection), vp, i64, i64,
+                                      i64, i32, vp, vp, vp, vp]),
+        "sc_dev_subspace_gram_f64": (i32, [vp, vp, vp, P(ModeSelection), i64, i64, vp, vp, P(ModeSelection), i64, i64, i64,
+                                           vp, i64, vp]),
         "sc_dev_rtb_hessian_f64": (i32, [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, i64, i64, vp, vp, i64, vp, vp]),
         "sc_dev_rtb_expand_f64": (i32, [vp, vp, i64, i64, vp, vp, vp, i64, vp]),
         "sc_dev_pairs_apply_f64": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, i64, vp, vp]),
@@ -482,6 +488,21 @@ class Modes:
         out = host_array((n, n))
         self._ctx.check(self._L.sc_modes_prs_subset(self._h, ptr(idx), len(idx), int(bool(norm)), ptr(out)))
         return out
+
+    def subspace(self, other, idx_a, idx_b, kind, rcond=1e-6, gram=False):
+        """
+        ``(value, G)`` of this model's modes against ``other``'s (``sc_modes_subspace``): ``kind`` 0 the RMSIP, 1 the
+        covariance overlap over the listed modes, None for every mode with ``|w| > rcond max|w|``; ``gram``: G (k_a, k_b),
+        the raw overlaps of the two lists, else None.
+        """
+        ia = None if idx_a is None else self._index_list(idx_a)
+        ib = None if idx_b is None else self._index_list(idx_b)
+        val = np.full(1, np.nan)
+        g = np.empty((len(ia), len(ib))) if gram else None
+        self._ctx.check(self._L.sc_modes_subspace(self._h, other._h, ptr(ia), 0 if ia is None else len(ia), ptr(ib),
+                                                  0 if ib is None else len(ib), float(rcond), int(kind), ptr(val),
+                                                  ptr(g) if gram and g.size else None))
+        return float(val[0]), g
 
     def close(self):
         if self._h is not None and self._h.value:

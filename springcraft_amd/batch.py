@@ -131,6 +131,28 @@ def _effector_sensor(torch, prs):
     return off.sum(dim=-1) / (n - 1), off.sum(dim=-2) / (n - 1)
 
 
+def _rmsip_pick(n_modes, mode_subset):
+    """
+    ``pick(solver)`` -> (sel, counts, device list) of :meth:`_BatchSolver.rmsip`'s selection on that solver: ``mode_subset``,
+    else the first ``n_modes`` non-trivial solved modes, behind a window the window.
+    """
+    def pick(s):
+        subset = mode_subset if (mode_subset is not None or s.window is not None) else s._first_modes(n_modes)
+        sel, counts = s._selection(subset, pinv_default=False)
+        return sel, counts, s._rows_keep
+
+    return pick
+
+
+def _listed_pick(mode_subset, pinv_default):
+    """``pick(solver)`` -> (sel, counts, device list) of the selection :meth:`_BatchSolver.dcc` (``pinv_default``) / ``msf`` makes."""
+    def pick(s):
+        sel, counts = s._selection(mode_subset, pinv_default=pinv_default)
+        return sel, counts, s._rows_keep
+
+    return pick
+
+
 def _trivial_rows(ntriv, first_row, nvec):
     """
     How many of a solver's ``nvec`` rows, row r being global mode ``first_row + r``, are trivial modes: the first row of
@@ -731,6 +753,148 @@ class _BatchSolver:
         profiles = [_effector_sensor(self.torch, p) for p in out]
         return out, [e for e, _ in profiles], [s for _, s in profiles]
 
+    # ---- how the modes of member a compare with those of member b (csrc/mode_subspace.hip) ---------------------------------
+    # No reference counterpart (Bio3D: rmsip / covsoverlap; ProDy: calcSubspaceOverlap / calcCovOverlap / calcOverlap of two
+    # mode sets).  Uniform layout only; like the consumers above they only enqueue.
+
+    def _subspace_partner(self, other):
+        """The second operand set of a comparison, checked on the host: ``other`` or, for None, this solver itself."""
+        if self._layout.ragged:
+            raise ValueError("mode subspaces can only be compared within a uniform batch: members of different size have "
+                             "no common coordinates (they need an alignment first)")
+        self._need_vectors()
+        if other is None or other is self:
+            return self
+        if not isinstance(other, _BatchSolver) or other._layout.ragged:
+            raise ValueError("other must be a uniform batch solver (DeviceBatchSolver): members of different size have no "
+                             "common coordinates")
+        if other.dim != self.dim or other.n_atoms != self.n_atoms:
+            raise ValueError(f"other holds structures of {other.n_atoms} atoms with dim = {other.dim}, this solver of "
+                             f"{self.n_atoms} atoms with dim = {self.dim}: their modes have no common coordinates")
+        if self.torch.device(other.device) != self.torch.device(self.device):
+            raise ValueError(f"other is on {other.device}, this solver on {self.device}")
+        if getattr(other, "_stream", None) != getattr(self, "_stream", None):
+            raise ValueError("other was built on another stream: the two solvers' contexts must enqueue on one stream")
+        other._need_vectors()
+        return other
+
+    def _subspace_sets(self, other, pick):
+        """
+        ((sel, counts pointer) of this solver, the same of the partner or None for a self-comparison, partner); ``pick(s)``
+        makes solver s's (sel, counts).  The selections' device lists are kept on their solvers.
+        """
+        partner = self._subspace_partner(other)
+        mine = pick(self)
+        return mine, (pick(partner) if partner is not self else None), partner
+
+    def _subspace_call(self, entry, mine, theirs, partner, with_counts, *args):
+        vp = C.c_void_p
+        first = [vp(self.w.data_ptr()), vp(self.v.data_ptr()), C.byref(mine[0])] + ([mine[1]] if with_counts else []) + \
+                [self.w.shape[1], self.batch]
+        if theirs is None:
+            second = [None, None, None] + ([None] if with_counts else []) + [0, 0]
+        else:
+            second = [vp(partner.w.data_ptr()), vp(partner.v.data_ptr()), C.byref(theirs[0])] + \
+                     ([theirs[1]] if with_counts else []) + [partner.w.shape[1], partner.batch]
+        self.ctx.check(getattr(self._L, entry)(self.ctx.handle, *first, *second, self.v.shape[2], *args))
+
+    def _first_modes(self, n_modes):
+        """Global indices of the first ``n_modes`` non-trivial solved modes, or of as many as were solved."""
+        n_modes = int(n_modes)
+        if n_modes < 0:
+            raise ValueError(f"n_modes must not be negative, got {n_modes}")
+        nvec = self.w.shape[1]
+        r0 = _trivial_rows(self._ntriv, self._first_row, nvec)
+        return self._first_row + np.arange(r0, min(r0 + n_modes, nvec))
+
+    def rmsip(self, n_modes=10, mode_subset=None, other=None):
+        """
+        (batch, batch) root mean square inner products of the members' mode subspaces (Amadei 1999; Bio3D ``rmsip``, ProDy
+        ``calcSubspaceOverlap``): ``RMSIP[a, b] = sqrt(sum_ij <v_a,i, v_b,j>^2 / sqrt(k_a k_b))`` over the k selected modes
+        of each member -- ``sqrt(1/k sum ...)`` whenever both carry k -- 1 for equal subspaces, 0 for orthogonal ones.
+        ``other``: another uniform solver of the same ``dim``, ``n_atoms``, device and stream; the result is then
+        (batch, other.batch), member a of this solver against member b of ``other``, and the selection is taken on each.
+
+        Selection: ``mode_subset`` (global mode indices as in :meth:`mean_square_fluctuation`) if given; otherwise the
+        first ``n_modes`` non-trivial solved modes, or fewer if fewer were solved; behind ``subset_by_value`` the window
+        itself (``n_modes`` is not read, ``mode_subset`` must be None), where the counts may differ between members and the
+        formula stays defined; an empty window gives NaN, 0 / 0.  A member whose solve failed (NaN eigenvalues) turns its
+        row and column into NaN and no other entry.  One kernel on the float64 matrix units (``csrc/mode_subspace.hip``):
+        the inner products are accumulated, squared and summed in registers, none is written to memory.  Without ``other``
+        only the pairs a >= b are computed and the result equals its transpose bit for bit; an entry's bits do not depend on
+        the batch sizes, the members' positions or their neighbours.  Only enqueues.
+
+        The rows of ``v`` are compared as they are.  There is no ``atom_scale``: the Cartesian modes of a mass-weighted
+        solve are not orthonormal and an RMSIP of non-orthonormal sets is not defined without a renormalisation, which is
+        out of scope; with ``masses`` this compares the mass-weighted modes.  A :class:`RaggedBatchSolver` raises
+        ValueError: members of different size have no common coordinates.
+        """
+        return self._subspace_matrix(0, _rmsip_pick(n_modes, mode_subset), other)
+
+    def covariance_overlap(self, mode_subset=None, other=None):
+        """
+        (batch, batch) covariance overlaps of the members (Hess 2002; Bio3D ``covsoverlap``, ProDy ``calcCovOverlap``):
+        ``1 - sqrt(max(0, T_a + T_b - 2 S_ab) / (T_a + T_b))`` with ``T = sum_i 1 / lambda_i`` the trace of a member's
+        covariance over the selected modes and ``S_ab = sum_ij <v_a,i, v_b,j>^2 / sqrt(lambda_a,i lambda_b,j)`` the trace of
+        the product of the two covariances' square roots: 1 for equal covariances, 0 for orthogonal ones.  ``other`` as in
+        :meth:`rmsip`: (batch, other.batch).
+
+        Selection exactly as :meth:`dcc` / :meth:`prs`: None on a full-spectrum solver takes the covariance rule, every
+        mode with ``|lambda| > 1e-6 max|lambda|`` of that member; behind ``subset_by_index`` every non-trivial solved mode;
+        behind ``subset_by_value`` the window; or an explicit ``mode_subset``.  A selected mode with a negative eigenvalue
+        (a window that reaches below 0) gives NaN.  Kernel, failed members, bits and ``atom_scale`` as in :meth:`rmsip`.
+        Only enqueues.
+        """
+        return self._subspace_matrix(1, _listed_pick(mode_subset, True), other)
+
+    def _subspace_matrix(self, kind, pick, other, raw=False):
+        """
+        The (batch, partner.batch) result of kind 0 (RMSIP) / 1 (covariance overlap); ``raw``: (result, S, t of this
+        solver's members, t of the partner's), the sums the result is formed from (the tests gate S itself).
+        """
+        mine, theirs, partner = self._subspace_sets(other, pick)
+        out = self._empty((self.batch, partner.batch))
+        s_raw = self._empty((self.batch, partner.batch)) if raw else None
+        t_a = self._empty((self.batch,)) if raw else None
+        t_b = self._empty((partner.batch,)) if raw and theirs is not None else None
+        self._call_keep = (mine, theirs)      # (the selections' device lists outlive the enqueued call)
+        vp = C.c_void_p
+        self._subspace_call("sc_dev_subspace_f64", mine, theirs, partner, True, kind, vp(out.data_ptr()),
+                            vp(s_raw.data_ptr()) if raw else None, vp(t_a.data_ptr()) if raw else None,
+                            vp(t_b.data_ptr()) if t_b is not None else None)
+        return (out, s_raw, t_a, t_a if t_b is None else t_b) if raw else out
+
+    def mode_overlap_matrix(self, pairs, mode_subset, other=None):
+        """
+        (n_pairs, k, k) raw overlaps ``G[p, i, j] = <v_a,i, v_b,j>`` of the k modes of ``mode_subset`` (global mode
+        indices, required: the table has one row per listed mode) for the listed member pairs ``pairs`` = [(a, b), ...]:
+        the table one matches the modes of two members with (ProDy ``calcOverlap(modesA, modesB)``).  ``other`` as in
+        :meth:`rmsip`: b then counts ``other``'s members.  A pair index outside the batch raises ValueError on the host.
+        The kernel of :meth:`rmsip` with a store in place of the squared sum; a failed member gives NaN.  Not available
+        behind ``subset_by_value`` (the modes' indices are only known on the device).  Only enqueues.
+        """
+        if mode_subset is None:
+            raise ValueError("mode_overlap_matrix needs an explicit mode_subset: the table has one row per listed mode")
+
+        pick = _listed_pick(mode_subset, False)
+        partner = self._subspace_partner(other)
+        pr = np.asarray(pairs)
+        if pr.size and (pr.dtype.kind not in "iu" or pr.ndim != 2 or pr.shape[1] != 2):
+            raise ValueError("pairs must be (n_pairs, 2) integer member indices")
+        pr = pr.astype(np.int64) if pr.size else np.zeros((0, 2), dtype=np.int64)
+        if pr.size and (pr.min() < 0 or pr[:, 0].max() >= self.batch or pr[:, 1].max() >= partner.batch):
+            raise ValueError(f"pairs must name members (a, b) with 0 <= a < {self.batch} and 0 <= b < {partner.batch}")
+        mine, theirs, partner = self._subspace_sets(other, pick)
+        k = int(mine[0].n_rows)
+        out = self._empty((len(pr), k, k))
+        if len(pr) and k:
+            host = self.torch.from_numpy(np.ascontiguousarray(pr, dtype=np.int32)).pin_memory()
+            dev = host.to(self.device, non_blocking=True)
+            self._call_keep = (mine, theirs, dev)
+            self._subspace_call("sc_dev_subspace_gram_f64", mine, theirs, partner, False, C.c_void_p(dev.data_ptr()),
+                                len(pr), C.c_void_p(out.data_ptr()))
+        return out
+
 
 class DeviceBatchSolver(_BatchSolver):
     """
@@ -781,6 +945,7 @@ class DeviceBatchSolver(_BatchSolver):
         self._L = _hip.lib()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         self.ctx = _hip.Context(self.device.index, stream=stream)
+        self._stream = stream     # (two solvers are compared on one stream: _subspace_partner)
         m = self.n_atoms * self.dim
         self.m = m
         f64 = torch.float64

@@ -1,6 +1,7 @@
 // C ABI (include/springcraft_hip.h), the mode consumers of a batch (batch_consumers.hip, dist_fluct.hip, mode_overlap.hip,
 // mode_response.hip, mode_prs.hip) on device tensors: the sc_dev_modes_* entries of a uniform batch and the sc_batch_plan_modes_* entries
-// of a plan's padded slots.
+// of a plan's padded slots; and the pairwise comparison of two uniform batches' modes (mode_subspace.hip: sc_dev_subspace_*,
+// no plan entry -- members of different size have no common coordinates).
 #include "api_internal.h"
 
 namespace {
@@ -147,6 +148,27 @@ int modes_combine(const ModesOf& who, const double* d_v, const double* d_coef, i
                               d_atom_scale, 0, d_out, who.ragged());
 }
 
+// (subspace: uniform batches only, two operand sets of one m; d_v_b NULL compares the first set with itself and then
+// takes no other argument of the second)
+int modes_subspace(sc_ctx* ctx, const double* d_w_a, const double* d_v_a, const sc_mode_selection* sel_a,
+                   const int64_t* d_counts_a, int64_t nvec_a, int64_t batch_a, const double* d_w_b, const double* d_v_b,
+                   const sc_mode_selection* sel_b, const int64_t* d_counts_b, int64_t nvec_b, int64_t batch_b, int64_t m,
+                   int kind, const int32_t* d_pairs, int64_t n_pairs, double* d_out, double* d_s, double* d_t_a,
+                   double* d_t_b) {
+  SC_TRY(check_modes_args(ModesOf{ctx, m, nvec_a, batch_a, 1}, d_w_a, d_v_a, sel_a, d_out));
+  const bool self = d_v_b == nullptr;
+  if (self && (d_w_b || sel_b || d_counts_b || d_t_b))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "a self-comparison (d_v_b NULL) takes no second operand set");
+  if (!self) SC_TRY(check_modes_args(ModesOf{ctx, m, nvec_b, batch_b, 1}, d_w_b, d_v_b, sel_b, d_out));
+  if (kind < 0 || kind > 2) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "unknown kind %d", kind);
+  if (kind == 2 && (n_pairs < 0 || n_pairs > INT32_MAX / 4 || (n_pairs > 0 && !d_pairs)))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "n_pairs = %lld pairs", (long long)n_pairs);
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const SubspaceSet a{d_w_a, d_v_a, sel_a, d_counts_a, nvec_a, batch_a};
+  const SubspaceSet b{d_w_b, d_v_b, sel_b, d_counts_b, nvec_b, batch_b};
+  return modes_subspace_device(ctx, a, self ? nullptr : &b, m, kind, d_pairs, n_pairs, d_out, d_s, d_t_a, d_t_b);
+}
+
 int64_t modes_workspace_bytes(const ModesOf& who, int64_t n_sel, int what, int64_t budget_bytes) {
   if (who.m <= 0 || who.nvec <= 0 || who.batch <= 0 || n_sel < 0 || (who.dim != 1 && who.dim != 3) || budget_bytes < 0)
     return 0;
@@ -245,6 +267,22 @@ int sc_batch_plan_mode_combine_f64(sc_batch_plan* plan, const double* d_v, int64
                                    const double* d_coef, int64_t q, const int64_t* d_counts, const double* d_atom_scale,
                                    double* d_out) {
   return modes_combine(plan_modes_of(plan, nvec, first_row), d_v, d_coef, q, d_counts, d_atom_scale, d_out);
+}
+
+int sc_dev_subspace_f64(sc_ctx* ctx, const double* d_w_a, const double* d_v_a, const sc_mode_selection* sel_a,
+                        const int64_t* d_counts_a, int64_t nvec_a, int64_t batch_a, const double* d_w_b,
+                        const double* d_v_b, const sc_mode_selection* sel_b, const int64_t* d_counts_b, int64_t nvec_b,
+                        int64_t batch_b, int64_t m, int kind, double* d_out, double* d_s, double* d_t_a, double* d_t_b) {
+  if (ctx && kind != 0 && kind != 1) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "kind must be 0 or 1, got %d", kind);
+  return modes_subspace(ctx, d_w_a, d_v_a, sel_a, d_counts_a, nvec_a, batch_a, d_w_b, d_v_b, sel_b, d_counts_b, nvec_b,
+                        batch_b, m, kind, nullptr, 0, d_out, d_s, d_t_a, d_t_b);
+}
+int sc_dev_subspace_gram_f64(sc_ctx* ctx, const double* d_w_a, const double* d_v_a, const sc_mode_selection* sel_a,
+                             int64_t nvec_a, int64_t batch_a, const double* d_w_b, const double* d_v_b,
+                             const sc_mode_selection* sel_b, int64_t nvec_b, int64_t batch_b, int64_t m,
+                             const int32_t* d_pairs, int64_t n_pairs, double* d_out) {
+  return modes_subspace(ctx, d_w_a, d_v_a, sel_a, nullptr, nvec_a, batch_a, d_w_b, d_v_b, sel_b, nullptr, nvec_b, batch_b,
+                        m, 2, d_pairs, n_pairs, d_out, nullptr, nullptr, nullptr);
 }
 
 int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,

@@ -284,6 +284,60 @@ int sc_modes_prs_subset(sc_modes* m, const int64_t* mode_idx, int64_t k, int nor
   });
 }
 
+int sc_modes_subspace(sc_modes* a, sc_modes* b, const int64_t* mode_idx_a, int64_t k_a, const int64_t* mode_idx_b,
+                      int64_t k_b, double rcond, int kind, double* out_value, double* out_gram) {
+  if (!a || !b) return SC_ERR_INVALID_ARG;
+  sc_ctx* ctx = a->ctx;
+  if (b->ctx != ctx || b->dim != a->dim || b->n != a->n)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "the two models differ in context, dim or order (%lld, %lld)",
+                        (long long)a->n, (long long)b->n);
+  // a NULL list (its k must be 0): every mode with |w| > rcond max|w|, the covariance rule; the table needs both lists
+  const bool pinv_a = mode_idx_a == nullptr, pinv_b = mode_idx_b == nullptr;
+  if ((kind != 0 && kind != 1) || k_a < 0 || k_a > INT32_MAX / 4 || k_b < 0 || k_b > INT32_MAX / 4 ||
+      (pinv_a && k_a != 0) || (pinv_b && k_b != 0) || ((pinv_a || pinv_b) && (!(rcond >= 0.0) || out_gram)) ||
+      (!out_value && !out_gram))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t gram_elems = out_gram ? (size_t)k_a * (size_t)k_b : 0;
+  int *d_sel_a = nullptr, *d_sel_b = nullptr, *d_pair = nullptr;
+  double *d_val = nullptr, *d_gram = nullptr;
+  SC_TRY(carve_scratch(ctx, [&](Arena& s) {
+    d_sel_a = s.take<int>((size_t)std::max<int64_t>(k_a, 1));
+    d_sel_b = s.take<int>((size_t)std::max<int64_t>(k_b, 1));
+    d_pair = s.take<int>(2);
+    d_val = s.take<double>(1);
+    d_gram = s.take<double>(std::max<size_t>(gram_elems, 1));
+  }));
+  SC_TRY(stage_mode_list(a, mode_idx_a, k_a, d_sel_a));
+  SC_TRY(stage_mode_list(b, mode_idx_b, k_b, d_sel_b));
+  if (a->n == 0) return SC_OK;
+  auto selection = [rcond](bool pinv, const int* d_sel, int64_t k) {
+    sc_mode_selection sel{};
+    if (pinv) {
+      sel.kind = SC_SEL_PINV;
+      sel.rcond = rcond;
+    } else {
+      sel.kind = SC_SEL_ROWS;
+      sel.d_rows = d_sel;
+      sel.n_rows = k;
+    }
+    return sel;
+  };
+  const sc_mode_selection sel_a = selection(pinv_a, d_sel_a, k_a), sel_b = selection(pinv_b, d_sel_b, k_b);
+  const SubspaceSet sa{a->d_w, a->d_v, &sel_a, nullptr, a->n, 1}, sb{b->d_w, b->d_v, &sel_b, nullptr, b->n, 1};
+  if (out_value) {
+    SC_TRY(modes_subspace_device(ctx, sa, &sb, a->n, kind, nullptr, 0, d_val, nullptr, nullptr, nullptr));
+    SC_HIP(ctx, hipMemcpyAsync(out_value, d_val, 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  if (gram_elems) {
+    SC_HIP(ctx, hipMemsetAsync(d_pair, 0, 8, ctx->stream));   // the one pair (0, 0)
+    SC_TRY(modes_subspace_device(ctx, sa, &sb, a->n, 2, d_pair, 1, d_gram, nullptr, nullptr, nullptr));
+    SC_HIP(ctx, hipMemcpyAsync(out_gram, d_gram, gram_elems * 8, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  SC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SC_OK;
+}
+
 int sc_modes_prs(sc_modes* m, double rcond, int norm, double* out) {
   if (!m) return SC_ERR_INVALID_ARG;
   sc_ctx* ctx = m->ctx;

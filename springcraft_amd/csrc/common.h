@@ -345,6 +345,24 @@ int batch_prs_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
                      const sc_mode_selection& sel, const int64_t* d_counts, const double* d_atom_scale, int norm,
                      double* d_out, const RaggedView* ragged = nullptr);
 
+// ---- pairwise comparison of mode subspaces (mode_subspace.hip) ---------------------------------------------------------
+// One operand set: a uniform batch's (w, v, counts) with the selection of its rows.
+struct SubspaceSet {
+  const double* d_w;              // (batch, nvec)
+  const double* d_v;              // (batch, nvec, m)
+  const sc_mode_selection* sel;   // validated by the caller
+  const int64_t* d_counts;        // null, or (batch) of a window solve
+  int64_t nvec, batch;
+};
+// kind 0 (RMSIP) / 1 (covariance overlap): d_out (a.batch, b.batch) for every pair of a structure of `a` with one of `b`;
+// b null: `a` with itself, only the pairs a >= b are computed and both places written from one value.  d_s: null or the raw
+// S of the same shape; d_t_a / d_t_b: null or the sums of the weights per structure.  kind 2: d_out (n_pairs, nsel_a,
+// nsel_b), the raw table G of the n_pairs listed (structure of a, structure of b) pairs, d_pairs int32 (n_pairs, 2) in
+// device memory; a pair that names no structure gives NaN.  Workspace: ctx->modes_ws.  Enqueue only.
+int modes_subspace_device(sc_ctx* ctx, const SubspaceSet& a, const SubspaceSet* b, int64_t m, int kind,
+                          const int32_t* d_pairs, int64_t n_pairs, double* d_out, double* d_s, double* d_t_a,
+                          double* d_t_b);
+
 // ---- overlaps with displacement vectors and collectivities of the modes (mode_overlap.hip) -----------------------
 // One pass over the rows of d_v (batch, nvec, m): d_overlap (batch, q, nout) and d_coll (batch, nout), either may be null
 // (d_overlap only with q = 0).  Output row kk is row kk of v (d_rows null, nout = nvec) or row d_rows[kk] (a validated

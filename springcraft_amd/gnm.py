@@ -95,3 +95,15 @@ class GNM(ElasticNetworkModel):
     def collectivity(self, mode_subset=None):
         """Collectivity of the selected modes, (k,) (:func:`nma.collectivity`)."""
         return nma.collectivity(self, mode_subset)
+
+    def rmsip(self, other, n_modes=10, mode_subset=None):
+        """RMSIP of this model's mode subspace with ``other``'s (:func:`nma.rmsip`; no reference counterpart)."""
+        return nma.rmsip(self, other, n_modes, mode_subset)
+
+    def covariance_overlap(self, other, mode_subset=None):
+        """Covariance overlap (Hess 2002) of this model with ``other`` (:func:`nma.covariance_overlap`)."""
+        return nma.covariance_overlap(self, other, mode_subset)
+
+    def mode_overlap_matrix(self, other, mode_subset_a, mode_subset_b=None):
+        """(k_a, k_b) overlaps of this model's listed modes with ``other``'s (:func:`nma.mode_overlap_matrix`)."""
+        return nma.mode_overlap_matrix(self, other, mode_subset_a, mode_subset_b)

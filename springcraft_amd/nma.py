@@ -18,6 +18,8 @@ built from chosen modes) are the two passes of ``csrc/mode_response.hip`` over t
 covariance is formed and only (q, 3N) numbers cross PCIe; ``sample_displacements`` draws the coefficients on the host.
 ``deformation_energy`` and ``spring_strain`` (no reference counterpart: where a mode strains the network) run the selected
 modes through the pair-list operator of ``csrc/pair_operator.hip`` (:class:`~springcraft_amd.PairOperator`).
+``rmsip``, ``covariance_overlap`` and ``mode_overlap_matrix`` (no reference counterpart: how the modes of one model compare
+with those of another) run the pair kernel of ``csrc/mode_subspace.hip`` on the two models' device-resident eigenpairs.
 ``normal_mode`` and ``effector_sensor`` are O(n) / O(n^2) host arithmetic on results that are already on the host.
 """
 
@@ -31,6 +33,7 @@ __all__ = [
     "normal_mode", "linear_response", "prs", "effector_sensor", "anisotropic_fluctuation", "anisotropy",
     "overlap", "collectivity", "cumulative_overlap", "distance_fluctuation", "effective_stiffness",
     "mode_displacement", "sample_displacements", "deformation_energy", "spring_strain",
+    "rmsip", "covariance_overlap", "mode_overlap_matrix",
 ]
 
 K_B = 1.380649e-23
@@ -570,6 +573,84 @@ def prs(anm, norm=True, mode_subset=None):
         return mat
     # covariance = pinv(hessian, rcond=1e-6) (anm.py:114-117) formed and reduced on the device
     return anm._modes_device().prs(1e-6, norm)
+
+
+def _comparable(enm_a, enm_b):
+    """Two models whose modes share their coordinates: the same class and atom count, else ValueError (host only)."""
+    _model_kind(enm_a)
+    _model_kind(enm_b)
+    if type(enm_a) is not type(enm_b):
+        raise ValueError(f"Cannot compare the modes of a {type(enm_a).__name__} with those of a {type(enm_b).__name__}")
+    if len(enm_a._coord) != len(enm_b._coord):
+        raise ValueError(f"Cannot compare the modes of models with {len(enm_a._coord)} and {len(enm_b._coord)} atoms: "
+                         "structures of different size have no common coordinates")
+
+
+def _two_modes(enm_a, enm_b):
+    """The device-resident eigenpairs of both models at once (one object when the models are one)."""
+    ma = enm_a._modes_device()
+    mb = ma if enm_b is enm_a else enm_b._modes_device()
+    if not ma._h:
+        # (the byte-bounded cache of _model.py released the first model's eigenpairs to keep the second's)
+        raise MemoryError("the eigenpairs of both models do not fit the device cache together: raise "
+                          "SPRINGCRAFT_MODES_CACHE_BYTES")
+    return ma, mb
+
+
+def _checked_subset(enm, mode_subset):
+    """``mode_subset`` as an int64 list with the trivial-mode error of :func:`mean_square_fluctuation`; host only."""
+    return np.asarray(_mode_selection(enm, mode_subset, None)).astype(np.int64).reshape(-1)
+
+
+def rmsip(enm_a, enm_b, n_modes=10, mode_subset=None):
+    """
+    Root mean square inner product of two models' mode subspaces (Amadei 1999; Bio3D ``rmsip``, ProDy
+    ``calcSubspaceOverlap``): ``sqrt(1/k sum_ij <a_i, b_j>^2)`` over the first ``n_modes`` non-trivial modes of each
+    (fewer if a model has fewer), or over ``mode_subset`` of both (trivial indices raise ValueError); 1 for equal
+    subspaces.  The two models must be of one class and atom count (ValueError).  The modes are compared as they are: for
+    models with masses these are the mass-weighted modes (Cartesian modes are not orthonormal; no renormalisation is
+    done).  No reference counterpart.  One kernel on the two models' device-resident eigenpairs
+    (``csrc/mode_subspace.hip``); one number crosses PCIe.
+    """
+    _comparable(enm_a, enm_b)
+    _, ntriv = _model_kind(enm_a)
+    if mode_subset is None:
+        n_modes = int(n_modes)
+        if n_modes < 0:
+            raise ValueError(f"n_modes must not be negative, got {n_modes}")
+        idx = np.arange(ntriv, min(ntriv + n_modes, len(enm_a._coord) * enm_a._dim))
+    else:
+        idx = _checked_subset(enm_a, mode_subset)
+    ma, mb = _two_modes(enm_a, enm_b)
+    return ma.subspace(mb, idx, idx, 0)[0]
+
+
+def covariance_overlap(enm_a, enm_b, mode_subset=None):
+    """
+    Covariance overlap of two models (Hess 2002; Bio3D ``covsoverlap``, ProDy ``calcCovOverlap``): ``1 - sqrt(max(0, tr A +
+    tr B - 2 tr(sqrt(A) sqrt(B))) / (tr A + tr B))`` for the covariances ``A = sum_i a_i a_i^T / lambda_i`` over the selected
+    modes; 1 for equal covariances.  ``mode_subset=None`` takes, per model, the covariance rule of :func:`dcc`: every mode
+    with ``|lambda| > 1e-6 max|lambda|``.  Models, masses and kernel as in :func:`rmsip`.
+    """
+    _comparable(enm_a, enm_b)
+    idx = None if mode_subset is None else _checked_subset(enm_a, mode_subset)
+    ma, mb = _two_modes(enm_a, enm_b)
+    return ma.subspace(mb, idx, idx, 1, rcond=1e-6)[0]
+
+
+def mode_overlap_matrix(enm_a, enm_b, mode_subset_a, mode_subset_b=None):
+    """
+    (k_a, k_b) table of the overlaps ``<a_i, b_j>`` of the listed modes of two models, the table one matches modes with
+    (ProDy ``calcOverlap(modesA, modesB)``); ``mode_subset_b=None`` takes ``mode_subset_a`` for both.  Signed; the rows of
+    a model's modes are unit vectors.  Models and kernel as in :func:`rmsip`; only (k_a, k_b) numbers cross PCIe.
+    """
+    _comparable(enm_a, enm_b)
+    ia = _checked_subset(enm_a, mode_subset_a)
+    ib = ia if mode_subset_b is None else _checked_subset(enm_b, mode_subset_b)
+    if not len(ia) or not len(ib):
+        return np.empty((len(ia), len(ib)))
+    ma, mb = _two_modes(enm_a, enm_b)
+    return ma.subspace(mb, ia, ib, 0, gram=True)[1]
 
 
 def effector_sensor(prs_matrix):

@@ -175,7 +175,8 @@ class RTB(_BatchSolver):
         self.torch = torch
         self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
         self._L = _hip.lib()
-        self.ctx = _hip.Context(self.device.index, stream=torch.cuda.current_stream(self.device).cuda_stream)
+        self._stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.ctx = _hip.Context(self.device.index, stream=self._stream)
         self.batch, self.dim, self.m = 1, 3, 3 * n
         self.window, self.max_modes, self.counts = None, None, None
         self.subset, self.nvec = None, self.nr
