@@ -336,6 +336,25 @@ int sc_ctx_get_counter(sc_ctx* ctx, const char* name, int64_t* value) {
   else if (k == "chase_resumed") *value = ctx->cnt_chase_resumed;
   else if (k == "chase_sweeps") *value = ctx->cnt_chase_sweeps;
   else if (k == "stepwise_chases") *value = ctx->cnt_stepwise_chases;
+  else if (k == "panel_wg1_launches") *value = ctx->cnt_panel_form[0];
+  else if (k == "panel_wg2_launches") *value = ctx->cnt_panel_form[1];
+  else if (k == "panel_wg3_launches") *value = ctx->cnt_panel_form[2];
+  else if (k == "panel_wg4_launches") *value = ctx->cnt_panel_form[3];
+  else if (k == "panel_wg10_launches") *value = ctx->cnt_panel_form[4];
+  else if (k == "panel_wg12_launches") *value = ctx->cnt_panel_form[5];
+  else if (k == "panel_blocked_launches") *value = ctx->cnt_panel_form[6];
+  else if (k == "panel_unblocked_launches") *value = ctx->cnt_panel_form[7];
+  else if (k == "panel_pair_first") *value = ctx->cnt_panel_role[0];
+  else if (k == "panel_pair_second") *value = ctx->cnt_panel_role[1];
+  else if (k == "symm_tri_launches") *value = ctx->cnt_symm_tri;
+  else if (k == "symm_slices") *value = ctx->last_symm_slices;
+  else if (k == "gemm3_declined") *value = ctx->cnt_gemm3_declined;
+  else if (k == "stage1_parts") *value = ctx->last_stage1_parts;
+  else if (k == "chase_stream_parts") *value = ctx->last_chase_stream_parts;
+  else if (k == "bt2_wave_solves") *value = ctx->cnt_bt2_form[0];
+  else if (k == "bt2_apply4_solves") *value = ctx->cnt_bt2_form[1];
+  else if (k == "bt2_apply8_solves") *value = ctx->cnt_bt2_form[2];
+  else if (k == "bt2_xcd_launches") *value = ctx->cnt_bt2_xcd;
   else if (k == "chase_xcd_min") *value = tmin;
   else if (k == "chase_xcd_max") *value = tmax;
   else if (k == "chase_xcd_total") *value = tsum;

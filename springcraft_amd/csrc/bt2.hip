@@ -811,6 +811,7 @@ int bt2_batched(sc_ctx* ctx, int n, int batch, double* d_sb_ws, const SbLayout& 
     SC_HIP(ctx, hipEventRecord(ev[0], st));
   }
   const sc_host::Bt2Plan P = sc_host::bt2_plan(sc_host::two_stage_env(), n, batch, ncols, ctx->num_cus);
+  ++ctx->cnt_bt2_form[P.wave ? 0 : (P.nw == 8 ? 2 : 1)];
   if (P.wave) {
     int nk0 = 0;
     {
@@ -832,6 +833,7 @@ int bt2_batched(sc_ctx* ctx, int n, int batch, double* d_sb_ws, const SbLayout& 
         !sc_raise_dyn_lds(reinterpret_cast<const void*>(&k_bt2_apply<4>), (int)lds))
       return sc_set_error(ctx, SC_ERR_HIP, "k_bt2_apply: the device refuses %zu bytes of dynamic LDS", lds);
     const dim3 grid(P.grid_x, P.grid_y);
+    if (P.xcd) ++ctx->cnt_bt2_xcd;
     if (P.nw == 8)
       hipLaunchKernelGGL(k_bt2_apply<8>, grid, dim3(512), lds, st, d_sb_ws, SL, d_dia_off, d_z, stride_z, ncols, batch,
                          P.xcd ? 1 : 0);

@@ -109,6 +109,18 @@ struct sc_ctx {
   int* last_chase_ctl = nullptr;
   int chase_ctl_xcds = 8;
   long long cnt_coop_launches = 0, cnt_coop_timeouts = 0;
+  // which form the policy (twostage_policy.h) chose, counted on the host where the form is launched (sc_ctx_get_counter):
+  // calls of run_panel by panel-QR form ([0..3] k_panel_wg<1,8> <2,8> <3,4> <4,2>, [4] <10,1,512>, [5] <12,1,512>,
+  // [6] the blocked and [7] the unblocked chunked launches; k_panel_coop: cnt_coop_launches) and by role (first / second of
+  // a pair), with the SYMM on the two triangular-operand launches (k_symm3: cnt_symm3_launches), trailing updates
+  // k_gemm3 declined; the K slices, stage-1 parts and per-wavefront stream parts of the most recent solve (0: it did not
+  // chase by the per-wavefront launches); bt2_batched by kernel ([0] k_bt2_wave, [1] k_bt2_apply<4>, [2] k_bt2_apply<8>)
+  // and its launches with the workgroups dealt to the XCDs
+  long long cnt_panel_form[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  long long cnt_panel_role[2] = {0, 0};
+  long long cnt_symm_tri = 0, cnt_gemm3_declined = 0;
+  int last_symm_slices = 0, last_stage1_parts = 0, last_chase_stream_parts = 0;
+  long long cnt_bt2_form[3] = {0, 0, 0}, cnt_bt2_xcd = 0;
   // event counters since the context was created (sc_ctx_get_counter)
   long long cnt_chase_launches = 0, cnt_chase_timeouts = 0, cnt_chase_incomplete = 0, cnt_chase_resumed = 0,
             cnt_chase_sweeps = 0, cnt_stepwise_chases = 0, cnt_pair_launches = 0;

@@ -1429,6 +1429,7 @@ static int chase_stepwise(sc_ctx* ctx, int n, int batch, double* d_sb_ws, const 
   const int t_max = 2 * (n - 3) + chase_len(n, n - 3) - 1;
   const int gx = chase_len(n, 0) / 2 + 1;
   const int nparts = sc_host::bulge_stream_parts(E, batch);
+  ctx->last_chase_stream_parts = nparts;
   if (nparts > 1) {
     SC_TRY(sc_aux_stream(ctx));            // (its fork event)
     SC_TRY(sc_side_streams(ctx, nparts - 1));
@@ -1457,6 +1458,7 @@ static int chase_stepwise(sc_ctx* ctx, int n, int batch, double* d_sb_ws, const 
 int sb_stage2(sc_ctx* ctx, double* d_a, long long stride_a, int n, int batch, double* d_tri_ws, const TriLayout& TL,
               double* d_sb_ws, const SbLayout& SL, double* d_band_copy, SbTimers& timers) {
   hipStream_t st = ctx->stream;
+  ctx->last_chase_stream_parts = 0;   // (chase_stepwise sets it)
   hipLaunchKernelGGL(k_band_extract, dim3(256, (unsigned)batch), dim3(256), 0, st, d_a, stride_a, d_sb_ws, SL);
   if (d_band_copy)   // debugging aid: the band of every matrix as stage 1 left it, (batch, kLdab * n)
     for (int b = 0; b < batch; ++b)

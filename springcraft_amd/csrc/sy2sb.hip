@@ -1353,6 +1353,7 @@ static int run_panel(const PanelRun& R, int p, int lo, int hi, hipStream_t ps, b
     case PanelQr::Wg1024: {
       const size_t lds_wg = sizeof(double) * (size_t)(2 * kWgWaves * 8 + 16 + 8 + 8 * kB + kWgWaves * kB * 8);
       const dim3 g1((unsigned)nb), b1((unsigned)kWgThreads);
+      ++ctx->cnt_panel_form[std::max(1, std::min(F.ru, 4)) - 1];
       if (F.ru == 1) hipLaunchKernelGGL((k_panel_wg<1, 8>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
       else if (F.ru == 2) hipLaunchKernelGGL((k_panel_wg<2, 8>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
       else if (F.ru == 3) hipLaunchKernelGGL((k_panel_wg<3, 4>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
@@ -1363,6 +1364,7 @@ static int run_panel(const PanelRun& R, int p, int lo, int hi, hipStream_t ps, b
       constexpr int kW = 512 / 64;
       const size_t lds_wg = sizeof(double) * (size_t)(2 * kW * 8 + 16 + 8 + 8 * kB + kW * kB * 8);
       const dim3 g1((unsigned)nb), b1(512u);
+      ++ctx->cnt_panel_form[F.ru == 10 ? 4 : 5];
       if (F.ru == 10) hipLaunchKernelGGL((k_panel_wg<10, 1, 512>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
       else hipLaunchKernelGGL((k_panel_wg<12, 1, 512>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
       break;
@@ -1372,6 +1374,7 @@ static int run_panel(const PanelRun& R, int p, int lo, int hi, hipStream_t ps, b
       const size_t lds_qr_blk = sizeof(double) * ((size_t)(kIb + 1) * (kQrRows + 1) + kB + kQrRows + 4 * kB);
       const size_t lds_blk_a = sizeof(double) * ((size_t)kB * (kQrRows + 1) + kQrRows + 8 * kB);
       const size_t lds_blk_b = sizeof(double) * ((size_t)kB * (kQrRows + 1) + kIb * kB + 4 * kB);
+      ++ctx->cnt_panel_form[6];
       hipLaunchKernelGGL(k_panel_qr, qgrid, dim3(256), lds_qr_blk, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, 0, nr, kIb);
       for (int c0 = 0; c0 < kB; c0 += kIb) {
         for (int j = c0 + 1; j < c0 + kIb; ++j)
@@ -1387,12 +1390,14 @@ static int run_panel(const PanelRun& R, int p, int lo, int hi, hipStream_t ps, b
     }
     case PanelQr::Unblocked: {
       const size_t lds_qr = sizeof(double) * ((size_t)kB * (kQrRows + 1) + kB + kQrRows + 4 * kB);
+      ++ctx->cnt_panel_form[7];
       for (int j = 0; j <= nr; ++j)
         hipLaunchKernelGGL(k_panel_qr, qgrid, dim3(256), lds_qr, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, j, nr, kB);
       break;
     }
   }
   if (timed) R.t.qr.stop();
+  if (rl != 0) ++ctx->cnt_panel_role[rl - 1];
   const GemmDesc* g = R.d_descs + (size_t)p * kDescKinds * batch;   // [kind][batch]
   if (timed) R.t.symm.start();
   // X = A22 V: one launch of k_symm3 (X into X1; X2 was zeroed for the whole solve) while the panel has enough tiles
@@ -1402,6 +1407,7 @@ static int run_panel(const PanelRun& R, int p, int lo, int hi, hipStream_t ps, b
     if (SL.symm_split > 1)
       hipLaunchKernelGGL(k_sum_xslices, dim3((unsigned)((m + 255) / 256), kB, (unsigned)nb), dim3(256), 0, ps, sb_h, SL, r0);
   } else {
+    ++ctx->cnt_symm_tri;
     SC_TRY(launch_gemm_f64(ctx, g + lo, nb, m, kB, kGemmTile, SL.symm_split, false, true, kGemmAmBk));           // X1 = L V
     SC_TRY(launch_gemm_f64(ctx, g + batch + lo, nb, m, kB, kGemmTile, SL.symm_split, false, true, kGemmAkBk));   // X2 = strict(L)^T V
     if (SL.symm_split > 1)
@@ -1428,8 +1434,10 @@ static int run_panel(const PanelRun& R, int p, int lo, int hi, hipStream_t ps, b
   else
     // (records of one launch share (m, m, K); operands start at even rows of buffers with even leading dimension n)
     if (launch_gemm3_uniform(ctx, g + 5 * batch + lo, nb, m, m, rl == 2 ? 4 * kB : 2 * kB, kGemmAmBn, /*lower=*/R.use_symm3 ? 2 : 1, 1.0, 1.0,
-                             /*aligned16=*/(n & 1) == 0 && (r0 & 1) == 0) != SC_OK)
+                             /*aligned16=*/(n & 1) == 0 && (r0 & 1) == 0) != SC_OK) {
+      ++ctx->cnt_gemm3_declined;
       SC_TRY(launch_gemm_f64(ctx, g + 5 * batch + lo, nb, m, m, kGemmTile, 1, false, false, kGemmAmBn, /*lower_grid=*/true));
+    }
   if (timed) R.t.syr2k.stop();
   return SC_OK;
 }
@@ -1447,6 +1455,8 @@ int sb_stage1(sc_ctx* ctx, double* d_a, long long stride_a, int n, int batch, do
     SC_HIP(ctx, hipMemsetAsync(d_tri_ws + (size_t)b * TL.slab + TL.tau, 0, sizeof(double) * n, st));
 
   const int s1_parts = sc_host::stage1_parts(E, batch, prof);
+  ctx->last_stage1_parts = s1_parts;
+  ctx->last_symm_slices = SL.symm_split;
   const sc_host::CoopPlan coop = sc_host::coop_plan(E, n, batch, ctx->num_cus, prof, ctx->coop_min_rows, ctx->coop_ok);
   v4i* coop_recs = nullptr;
   int* coop_ctl = nullptr;

@@ -326,6 +326,87 @@ int main() {
       Es.symm_split = 40;
       CHECK(symm_split_for(Es, 6000, 1) == 16);
     }
+    // ---- the shapes of the stage cases of tests/test_stage_ratios_gpu.py (test_form_*): the form of every decision, the
+    // counts written out by hand from the rules above; the GPU tests assert the same literals on the context's counters.
+    // Panels of order n: p = 0 .. while n - 64 (p + 1) >= 2, of m = n - 64 (p + 1) rows; a pair while n - 64 (p + 2) >= 256;
+    // k_panel_wg<ru> for 1024 (ru - 1) < m <= 1024 ru, <10,1,512> for 4096 < m <= 5120, <12,1,512> up to 6144 (four and
+    // more matrices), one matrix above 4096 rows: blocked; the last panel of fewer than 65 rows: unblocked.
+    {
+      struct Shape {
+        const char* name;
+        int n, batch, coop_min_rows;
+        // per solve, summed over the stage-1 parts: Coop, Wg1024 ru 1..4, Wg512 ru 10, 12, Blocked, Unblocked
+        int qr[9];
+        int role1, role2, slices, s1_parts, chase_parts;
+        ChaseForm chase_default;
+        int bt2_nw; bool bt2_xcd; unsigned gx, gy;   // (no case takes k_bt2_wave: all n columns)
+      };
+      const Shape shapes[] = {
+          // a: 17 panels of 1036, 972, .., 76, 12 rows; pairs while n - 64 (p + 2) >= 256: p = 0 .. 11; 9 x 1 items: 16 slices
+          {"a", 1100, 1, 0, {0, 15, 1, 0, 0, 0, 0, 0, 1}, 6, 6, 16, 1, 1, ChaseForm::Sweep, 4, false, 18u, 1u},
+          // b: 33 panels from 2056 rows: one above 2048, 16 above 1024; pairs p = 0 .. 27
+          {"b", 2120, 1, 0, {0, 15, 16, 1, 0, 0, 0, 0, 1}, 14, 14, 16, 1, 1, ChaseForm::Sweep, 4, false, 34u, 1u},
+          // c: 49 panels from 3076 rows; pairs p = 0 .. 43
+          {"c", 3140, 1, 0, {0, 15, 16, 16, 1, 0, 0, 0, 1}, 22, 22, 16, 1, 1, ChaseForm::Sweep, 4, false, 50u, 1u},
+          // d: 65 panels from 4098 rows (one matrix: the chunked launches), then 4034 .. 3074: 16 of <4,2>; pairs p = 0 .. 59
+          {"d", 4162, 1, 0, {0, 15, 16, 16, 16, 0, 0, 1, 1}, 30, 30, 16, 1, 1, ChaseForm::Sweep, 4, false, 66u, 1u},
+          // e: the same panels, four matrices: 4098 rows = 9 x 512 -> <10,1,512>; 33 x 4 = 132 items: ceil(1536 / 132) = 12
+          {"e", 4162, 4, -1, {0, 15, 16, 16, 16, 1, 0, 0, 1}, 30, 30, 12, 1, 1, ChaseForm::Sweep, 4, false, 66u, 4u},
+          // f: 81 panels from 5126 rows = 11 x 512 -> <12,1,512>, then 5062 .. 4102: 16 of <10,1,512>; pairs p = 0 .. 75;
+          // 41 x 4 = 164 items: ceil(1536 / 164) = 10; n > 4500 with fewer matrices than XCDs: the spread chase
+          {"f", 5190, 4, -1, {0, 15, 16, 16, 16, 16, 1, 0, 1}, 38, 38, 10, 1, 1, ChaseForm::Spread, 4, false, 82u, 4u},
+          // g: 7 panels of 386 .. 66, 2 rows; 450 - 128 = 322 >= 256: one pair, 450 - 256 = 194: no second
+          {"g", 450, 7, -1, {0, 6, 0, 0, 0, 0, 0, 0, 1}, 1, 1, 1, 1, 1, ChaseForm::Sweep, 4, false, 8u, 7u},
+          // h: 31 panels of 1985 .. 65 rows (the last one full: 64 reflectors), one matrix: k_panel_coop from 300 rows
+          // (p = 0 .. 26); odd order: no k_symm3, 33 tiles -> ceil(2048 / 33) >= 6 -> 9 slices; pairs p = 0 .. 27
+          {"h", 2049, 1, -1, {27, 4, 0, 0, 0, 0, 0, 0, 0}, 14, 14, 9, 1, 1, ChaseForm::Sweep, 4, false, 33u, 1u},
+          // i .. l: 5 panels of 258, 194, 130, 66, 2 rows, no pair (322 - 128 < 256); from 32 matrices on two parts
+          {"i", 322, 33, -1, {0, 8, 0, 0, 0, 0, 0, 0, 2}, 0, 0, 1, 2, 2, ChaseForm::Sweep, 4, true, 8u * 5u * 6u, 1u},
+          {"j16", 322, 16, -1, {0, 4, 0, 0, 0, 0, 0, 0, 1}, 0, 0, 1, 1, 2, ChaseForm::Sweep, 4, true, 8u * 2u * 6u, 1u},
+          {"j48", 322, 48, -1, {0, 8, 0, 0, 0, 0, 0, 0, 2}, 0, 0, 1, 2, 3, ChaseForm::Sweep, 4, true, 8u * 6u * 6u, 1u},
+          {"k", 322, 9, -1, {0, 4, 0, 0, 0, 0, 0, 0, 1}, 0, 0, 1, 1, 1, ChaseForm::Sweep, 4, true, 8u * 2u * 6u, 1u},
+          // l: 3 x 86 = 258 >= 256 workgroups of 128 columns: eight waves, 3 chunks; 85 matrices would stay on four
+          {"l", 322, 86, -1, {0, 8, 0, 0, 0, 0, 0, 0, 2}, 0, 0, 1, 2, 3, ChaseForm::Sweep, 8, true, 8u * 11u * 3u, 1u},
+      };
+      for (const Shape& S : shapes) {
+        const int parts = stage1_parts(E, S.batch, false);
+        const CoopPlan C = coop_plan(E, S.n, S.batch, 256, false, S.coop_min_rows, 1);
+        const bool recs = C.ask && C.nb_max >= 1;   // (the LDS attribute granted)
+        const std::vector<int> role = panel_roles(E, S.n);
+        int qr[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, r1 = 0, r2 = 0;
+        for (int p = 0; p < (int)role.size(); ++p) {
+          r1 += role[(size_t)p] == 1;
+          r2 += role[(size_t)p] == 2;
+          for (int q = 0; q < parts; ++q) {
+            const int lo = (int)((long long)S.batch * q / parts), hi = (int)((long long)S.batch * (q + 1) / parts);
+            const PanelQrForm F = panel_qr_form(E, C, recs, S.n - (p + 1) * kBand, hi - lo, q == 0);
+            switch (F.kind) {
+              case PanelQr::Coop: ++qr[0]; break;
+              case PanelQr::Wg1024: CHECK(F.ru >= 1 && F.ru <= 4 && F.cu == (F.ru <= 2 ? 8 : (F.ru == 3 ? 4 : 2))); ++qr[F.ru]; break;
+              case PanelQr::Wg512: CHECK((F.ru == 10 || F.ru == 12) && F.cu == 1); ++qr[F.ru == 10 ? 5 : 6]; break;
+              case PanelQr::Blocked: ++qr[7]; break;
+              case PanelQr::Unblocked: ++qr[8]; break;
+            }
+          }
+        }
+        bool same = true;
+        for (int k = 0; k < 9; ++k) same = same && qr[k] == S.qr[k];
+        if (!same) std::fprintf(stderr, "shape %s: panel QR forms %d %d %d %d %d %d %d %d %d\n", S.name, qr[0], qr[1], qr[2], qr[3],
+                                qr[4], qr[5], qr[6], qr[7], qr[8]);
+        CHECK(same);
+        CHECK(r1 == S.role1 && r2 == S.role2);
+        CHECK(symm_split_for(E, S.n, S.batch) == S.slices);
+        CHECK(parts == S.s1_parts && bulge_stream_parts(E, S.batch) == S.chase_parts);
+        // sc_dbg_set_chase(ctx, 0, 0): the per-wavefront launches; left alone: what the size gives
+        CHECK(chase_form_for(E, S.n, S.batch, 8, 256, true, /*chase_mode=*/0, -1, 1) == ChaseForm::Stepwise);
+        CHECK(chase_form_for(E, S.n, S.batch, 8, 256, true, -1, -1, 1) == S.chase_default);
+        const Bt2Plan P = bt2_plan(E, S.n, S.batch, S.n, 256);
+        CHECK(!P.wave && P.nw == S.bt2_nw && P.xcd == S.bt2_xcd && P.grid_x == S.gx && P.grid_y == S.gy);
+      }
+      // the first stage-1 part of 33 matrices has 16, the second 17
+      CHECK((int)(33LL * 1 / 2) == 16 && 33 - 16 == 17);
+      CHECK(bt2_plan(E, 322, 85, 322, 256).nw == 4 && bt2_plan(E, 322, 7, 322, 256).xcd == false);
+    }
     // the environment is read in one place; unset, it is the default-constructed struct
     if (!getenv("SPRINGCRAFT_STAGE1_STREAMS") && !getenv("SPRINGCRAFT_BULGE_PAIR")) {
       const TwoStageEnv R = read_two_stage_env();

@@ -49,6 +49,33 @@ def orth(q):
     return norm1(np.eye(n) - q @ q.T) / (n * ULP)
 
 
+# ---- the same two formulas on float64 torch tensors (torch.matmul: on a device tensor rocBLAS, which shares nothing with the
+# kernels under test), for orders at which the NumPy triple products take too long
+def norm1_t(a):
+    return float(a.abs().sum(dim=0).max()) if a.numel() else 0.0
+
+
+def recon_t(a, q, m):
+    """recon(a, q, m) of float64 torch tensors on one device; q holds the factor's columns as columns."""
+    import torch
+
+    assert a.dtype == q.dtype == m.dtype == torch.float64
+    n = a.shape[0]
+    na = norm1_t(a)
+    diff = norm1_t(a - q @ m @ q.T)
+    if na == 0.0:
+        return 0.0 if diff == 0.0 else np.inf
+    return diff / na / (n * ULP)
+
+
+def orth_t(q):
+    import torch
+
+    assert q.dtype == torch.float64
+    n = q.shape[0]
+    return norm1_t(torch.eye(n, dtype=q.dtype, device=q.device) - q @ q.T) / (n * ULP)
+
+
 def tridiagonal(d, e):
     """Dense T from d (n) and e (n or n - 1 entries; only the first n - 1 count)."""
     n = len(d)
@@ -158,9 +185,9 @@ def debug_lib():
     return L
 
 
-def reduce_raw(L, ctx, a, which, want_q=True):
+def reduce_raw(L, ctx, a, which, want_q=True, transpose=True):
     """The library's return code and (d, e, scale, band or None, Q or None, two_stage) of a batch a (batch, n, n); Q with
-    the factor's columns as columns."""
+    the factor's columns as columns (transpose = False: as the entry returns it, the columns as rows -- no copy)."""
     a = np.ascontiguousarray(a, dtype=np.float64)
     batch, n, _ = a.shape
     d, e, scale = np.zeros((batch, n)), np.zeros((batch, n)), np.zeros(batch)
@@ -171,13 +198,13 @@ def reduce_raw(L, ctx, a, which, want_q=True):
     rc = L.sc_dbg_reduce_host(ctx.handle, p(a), n, batch, which, p(d), p(e), p(scale), p(band), p(q), C.byref(two))
     if rc != 0:
         return rc, None
-    if q is not None:
+    if q is not None and transpose:
         q = np.ascontiguousarray(q.transpose(0, 2, 1))
     return rc, (d, e, scale, band if two.value == 1 else None, q, two.value == 1)
 
 
-def reduce_host(L, ctx, a, which, want_q=True):
-    rc, out = reduce_raw(L, ctx, a, which, want_q)
+def reduce_host(L, ctx, a, which, want_q=True, transpose=True):
+    rc, out = reduce_raw(L, ctx, a, which, want_q, transpose)
     ctx.check(rc)
     return out
 

@@ -9,9 +9,16 @@ tests/test_batched_degenerate_gpu.py and confirmed by the same counters; every m
 figures are printed before anything is asserted.  Every ratio is gated at 50, a thousand to ten thousand times tighter than
 the end-to-end max-abs gates at these orders; LAPACK's own factors stay below 5 on the same inputs
 (tests/test_stage_ratios_host.py).  profiles/stage_ratios.txt holds the figures of the first run.
+
+The test_form_* cases at the end hold one kernel form each to the same gate, at the smallest shape at which the policy
+(csrc/twostage_policy.h) selects it, and prove by the context's form counters that it ran: the expected counts are the
+literals of tests/host_sanitize/test_host_logic.cpp, derived by hand from the rules.  Not covered there:
+k_bt2_apply<8> on the (chunk, matrix) grid (it needs n >= 4609 at batch 7, and there is no in-process override), the
+partial-spectrum Q2 (ncols < n: tests/test_partial_ratios_gpu.py), and stedc above n = 1000.
 """
 import ctypes as C
 import os
+import time
 
 import numpy as np
 import pytest
@@ -88,6 +95,7 @@ def check_two_stage(L, ctx, label, names, mats, counters):
         fig["orth(Q)"] = sr.orth(q)
         rows.append((name, fig))
     report(label, rows)
+    return out
 
 
 def check_one_stage(L, ctx, label, names, mats):
@@ -284,3 +292,247 @@ def test_stages_compose_to_the_product(lib_ctx, two_stage, n):
         print(f"[compose two_stage={two_stage} n={n}] member {b}: |V - (Q Z)^T|_1 / (n ulp) = {diff:.3g}, "
               f"eigenvalue difference / (n ulp lambda_max) = {eig:.3g}")
     assert all(diff <= sr.GATE and eig <= sr.GATE for diff, eig in figures), figures
+
+
+# ---- one kernel form per case, proven by the form counters ------------------------------------------------------------------
+# Calls of run_panel by panel-QR form and by role, SYMM and trailing-update forms: per call of the staged entry.
+PER_CALL = ("panel_coop_launches", "panel_wg1_launches", "panel_wg2_launches", "panel_wg3_launches", "panel_wg4_launches",
+            "panel_wg10_launches", "panel_wg12_launches", "panel_blocked_launches", "panel_unblocked_launches",
+            "panel_pair_first", "panel_pair_second", "symm3_launches", "symm_tri_launches", "gemm3_declined")
+LAST = ("symm_slices", "stage1_parts", "chase_stream_parts")                   # of the most recent solve
+BT2 = ("bt2_wave_solves", "bt2_apply4_solves", "bt2_apply8_solves", "bt2_xcd_launches")
+QUIET = ("panel_coop_timeouts", "chase_timeouts", "chase_incomplete", "chase_resumed", "chase_pair_fallbacks")
+# every switch of tools/test_matrix.sh that moves a shape to another form
+FORM_SWITCHES = ("QR_UNBLOCKED", "QR_WG", "QR_COOP", "QR_COOP_MIN", "STAGE1_STREAMS", "PANEL_PAIRS", "SYMM3", "SYMM_SPLIT",
+                 "GEMM3", "GEMM3_LOWER", "BULGE_PERSISTENT", "BULGE_STREAMS", "BULGE_PAIR", "BULGE_SPREAD", "BT2_WAVE", "BT2_NW")
+
+
+def skip_if_forms_overridden():
+    hit = [k for k in FORM_SWITCHES if os.environ.get("SPRINGCRAFT_" + k)]
+    if hit:
+        pytest.skip(f"the form under test is overridden by {hit} (tools/test_matrix.sh)")
+
+
+def wrong_forms(ctx, label, calls, per_call, last, bt2, stepwise):
+    """Every form counter against its literal: those named, and zero for all the others; prints them and returns the
+    mismatches {counter: (got, expected)}."""
+    got = {k: ctx.counter(k) for k in PER_CALL + LAST + BT2 + QUIET + ("chase_launches", "stepwise_chases", "gemm3_launches")}
+    print(f"[{label}] call {calls}: " + " ".join(f"{k}={v}" for k, v in got.items() if v))
+    assert set(per_call) <= set(PER_CALL) and set(last) == set(LAST) and set(bt2) <= set(BT2)
+    want = {k: calls * per_call.get(k, 0) for k in PER_CALL}
+    want.update(last)
+    want.update({k: bt2.get(k, 0) for k in BT2})
+    want.update({k: 0 for k in QUIET})
+    want["chase_launches"], want["stepwise_chases"] = (0, calls) if stepwise else (calls, 0)
+    return {k: (got[k], v) for k, v in want.items() if got[k] != v}
+
+
+def check_forms(ctx, label, calls, per_call, last, bt2, stepwise):
+    wrong = wrong_forms(ctx, label, calls, per_call, last, bt2, stepwise)
+    assert not wrong, (label, "counter: (got, expected)", wrong)
+
+
+def cycled_batch(n, batch, copies):
+    """`batch` members of order n: random_sym(n) at the positions `copies`, the mixed batch's members in turn elsewhere."""
+    _, mixed = sr.mixed_batch(n)
+    names, mats = [], []
+    for k in range(batch):
+        if k in copies:
+            names.append(f"copy@{k}")
+            mats.append(sr.random_sym(n))
+        else:
+            names.append(f"{sr.MIXED[k % len(sr.MIXED)]}@{k}")
+            mats.append(mixed[k % len(sr.MIXED)])
+    return names, np.stack(mats)
+
+
+def members_batch(n, names):
+    if ("members", n, tuple(names)) not in sr._cache:
+        members, _ = sr.degenerate_members(n, sr.SEED, names=names)
+        by_name = dict(members)
+        sr._cache["members", n, tuple(names)] = np.stack([by_name[k] for k in names])
+    return [f"{k}@{i}" for i, k in enumerate(names)], sr._cache["members", n, tuple(names)]
+
+
+def stage1_on_device(L, ctx, label, names, mats, per_call, slices):
+    """which = Q_ONE of a large order: recon(A,Q1,B), orth(Q1) by the torch twins on the device, beyond_band."""
+    import torch
+
+    t0 = time.perf_counter()
+    d, e, s, band, qt, two = sr.reduce_host(L, ctx, mats, sr.Q_ONE, transpose=False)
+    t1 = time.perf_counter()
+    assert two, "the two-stage path was forced"
+    rows = []
+    for b, name in enumerate(names):
+        a = torch.from_numpy(scaled(mats[b], s[b])).cuda()
+        q = torch.from_numpy(qt[b]).cuda().T          # (the entry returns the factor's columns as rows)
+        bm = torch.from_numpy(sr.band_matrix(band[b])).cuda()
+        rows.append((name, {"recon(A,Q1,B)": sr.recon_t(a, q, bm), "orth(Q1)": sr.orth_t(q),
+                            "beyond_band": sr.band_beyond(band[b])}))
+    print(f"[{label}] solve {t1 - t0:.2f} s, ratios {time.perf_counter() - t1:.2f} s")
+    wrong = wrong_forms(ctx, label, 1, per_call, {"symm_slices": slices, "stage1_parts": 1, "chase_stream_parts": 0}, {}, False)
+    report(label, rows)
+    assert not wrong, (label, "counter: (got, expected)", wrong)
+
+
+# (the literals: tests/host_sanitize/test_host_logic.cpp, shapes a .. h; k_symm3 takes a panel of m even rows while
+# ceil(m / 128) x slices x matrices >= 256 and every slice has four K steps, k_gemm3 a trailing update of fewer than eight
+# matrices while its lower triangle has 1024 tiles of 128 x 64 over the batch)
+STAGE1_CASES = {
+    # one matrix of 1036 rows: <2,8> once; 9 x 16 = 144 items: k_symm3 declines every panel, its 16 slices go through the
+    # triangular-operand launches and k_sum_xslices over 2 x 64 columns
+    "a": (1100, ["random"], False, dict(panel_wg2_launches=1, panel_wg1_launches=15, panel_unblocked_launches=1, panel_pair_first=6,
+                                        panel_pair_second=6, symm_tri_launches=17, gemm3_declined=11), 16),
+    # k_symm3 with 16 slices on the panels of 2056, 1992 and 1928 rows (17, 16, 16 tile rows)
+    "b": (2120, ["random"], False, dict(panel_wg3_launches=1, panel_wg2_launches=16, panel_wg1_launches=15, panel_unblocked_launches=1,
+                                        panel_pair_first=14, panel_pair_second=14, symm3_launches=3, symm_tri_launches=30,
+                                        gemm3_declined=19), 16),
+    "c": (3140, ["random"], False, dict(panel_wg4_launches=1, panel_wg3_launches=16, panel_wg2_launches=16, panel_wg1_launches=15,
+                                        panel_unblocked_launches=1, panel_pair_first=22, panel_pair_second=22, symm3_launches=19,
+                                        symm_tri_launches=30, gemm3_declined=27), 16),
+    # (k_gemm3 takes the joint update of 4034 rows: 32 x 64 - 32 x 31 = 1056 tiles; 3906 rows have 992)
+    "d": (4162, ["random"], False, dict(panel_blocked_launches=1, panel_wg4_launches=16, panel_wg3_launches=16, panel_wg2_launches=16,
+                                        panel_wg1_launches=15, panel_unblocked_launches=1, panel_pair_first=30,
+                                        panel_pair_second=30, symm3_launches=35, symm_tri_launches=30, gemm3_declined=34), 16),
+    "e": (4162, ["random", "rank1", "gluedW", "big"], True,
+          dict(panel_wg10_launches=1, panel_wg4_launches=16, panel_wg3_launches=16, panel_wg2_launches=16, panel_wg1_launches=15,
+               panel_unblocked_launches=1, panel_pair_first=30, panel_pair_second=30, symm3_launches=55, symm_tri_launches=10,
+               gemm3_declined=18), 12),
+    "f": (5190, ["random", "rank1", "gluedW", "big"], True,
+          dict(panel_wg12_launches=1, panel_wg10_launches=16, panel_wg4_launches=16, panel_wg3_launches=16, panel_wg2_launches=16,
+               panel_wg1_launches=15, panel_unblocked_launches=1, panel_pair_first=38, panel_pair_second=38, symm3_launches=69,
+               symm_tri_launches=12, gemm3_declined=18), 10),
+    # odd order: no k_symm3, the triangular-operand launches with 9 slices on every panel; no 16-byte alignment: k_gemm3
+    # declines all 17 trailing updates (31 panels, 14 of them first of a pair); one matrix: k_panel_coop from 300 rows
+    "h": (2049, ["random"], True, dict(panel_coop_launches=27, panel_wg1_launches=4, panel_pair_first=14, panel_pair_second=14,
+                                       symm_tri_launches=31, gemm3_declined=17), 9),
+}
+
+
+@pytest.mark.parametrize("case", sorted(STAGE1_CASES))
+def test_form_stage1(lib_ctx, case):
+    """
+    Stage 1 alone (which = Q_ONE) at the smallest order that selects k_panel_wg<2,8> (a), <3,4> (b), <4,2> (c), the blocked
+    chunked launches followed by every 1024-thread instance (d: one matrix of 4098 rows), <10,1,512> (e) and <12,1,512>
+    (e, f: four matrices, random / rank1 / gluedW / big), and the triangular-operand SYMM with 9 K slices under trailing updates
+    k_gemm3 declines (h: odd order).  a - d with k_panel_coop switched off, which would take their panels from 300 rows.
+    """
+    skip_if_forms_overridden()
+    n, members, coop, per_call, slices = STAGE1_CASES[case]
+    L, ctx = lib_ctx
+    names, mats = (["random"], sr.random_sym(n)[None]) if members == ["random"] else members_batch(n, members)
+    ctx.set_two_stage(True)
+    if not coop:
+        ctx.check(L.sc_dbg_set_panel_coop(ctx.handle, 0))
+    stage1_on_device(L, ctx, f"form {case}: stage 1 n={n} x {len(names)}", names, mats, per_call, slices)
+
+
+def identical(out, which, copies, label):
+    first = copies[0]
+    for k in copies[1:]:
+        for x, what in zip(out[which][:5], ("d", "e", "scale", "band", "Q")):
+            assert np.array_equal(x[k], x[first], equal_nan=True), (label, f"{what} of member {k} differs from member {first}'s")
+
+
+def test_form_panel_pairs_on_the_mixed_batch(lib_ctx):
+    """g: n = 450, the smallest order region with a panel pair (450 - 128 >= 256 > 450 - 256) on the members with tau = 0
+    reflectors and exact zeros: record D, the Corr records and the K = 256 joint update; all three factors."""
+    skip_if_forms_overridden()
+    L, ctx = lib_ctx
+    names, mats = sr.mixed_batch(450)
+    ctx.set_two_stage(True)
+    label = "form g: pairs n=450 mixed"
+    per_call = dict(panel_wg1_launches=6, panel_unblocked_launches=1, panel_pair_first=1, panel_pair_second=1, symm_tri_launches=7,
+                    gemm3_declined=6)
+
+    def counters(calls):
+        check_forms(ctx, label, calls, per_call, {"symm_slices": 1, "stage1_parts": 1, "chase_stream_parts": 0},
+                    {"bt2_apply4_solves": calls - 1}, False)
+
+    t0 = time.perf_counter()
+    check_two_stage(L, ctx, label, names, mats, counters)
+    print(f"[{label}] {time.perf_counter() - t0:.2f} s")
+
+
+def test_form_two_stage1_parts(lib_ctx):
+    """i: 33 matrices, the band reduction in two parts of 16 and 17 on two streams; one matrix at positions 0, 16 (the first
+    of the second part) and 32: d, e, the band and Q1 of the three copies are bit-identical."""
+    skip_if_forms_overridden()
+    L, ctx = lib_ctx
+    n, copies = 322, (0, 16, 32)
+    names, mats = cycled_batch(n, 33, copies)
+    ctx.set_two_stage(True)
+    label = "form i: two stage-1 parts n=322 x 33"
+    t0 = time.perf_counter()
+    out = {sr.Q_ONE: sr.reduce_host(L, ctx, mats, sr.Q_ONE)}
+    assert out[sr.Q_ONE][5]
+    d, e, s, band, q1, _ = out[sr.Q_ONE]
+    rows = [(name, {"recon(A,Q1,B)": sr.recon(scaled(mats[b], s[b]), q1[b], sr.band_matrix(band[b])), "orth(Q1)": sr.orth(q1[b]),
+                    "beyond_band": sr.band_beyond(band[b])}) for b, name in enumerate(names)]
+    print(f"[{label}] {time.perf_counter() - t0:.2f} s")
+    wrong = wrong_forms(ctx, label, 1, dict(panel_wg1_launches=8, panel_unblocked_launches=2, symm_tri_launches=10,
+                                            gemm3_declined=10),
+                        {"symm_slices": 1, "stage1_parts": 2, "chase_stream_parts": 0}, {}, False)
+    report(label, rows)
+    assert not wrong, (label, "counter: (got, expected)", wrong)
+    identical(out, sr.Q_ONE, copies, label)
+
+
+@pytest.mark.parametrize("batch,parts,s1_parts,copies", [(16, 2, 1, (0, 8, 15)), (48, 3, 2, (0, 16, 32, 47))])
+def test_form_stepwise_chase(lib_ctx, batch, parts, s1_parts, copies):
+    """j: k_bulge_step, one launch per wavefront of tasks (sc_dbg_set_chase mode 0), the batch in two (16 matrices) and three
+    (48) parts on separate streams; copies of one matrix in every part are bit-identical in all three factors."""
+    skip_if_forms_overridden()
+    L, ctx = lib_ctx
+    n = 322
+    names, mats = cycled_batch(n, batch, copies)
+    ctx.set_two_stage(True)
+    ctx.check(L.sc_dbg_set_chase(ctx.handle, 0, 0))
+    label = f"form j: stepwise chase n={n} x {batch}"
+    per_call = dict(panel_wg1_launches=4 * s1_parts, panel_unblocked_launches=s1_parts, symm_tri_launches=5 * s1_parts,
+                    gemm3_declined=5 * s1_parts)
+
+    def counters(calls):
+        check_forms(ctx, label, calls, per_call, {"symm_slices": 1, "stage1_parts": s1_parts, "chase_stream_parts": parts},
+                    {"bt2_apply4_solves": calls - 1, "bt2_xcd_launches": calls - 1}, True)
+
+    t0 = time.perf_counter()
+    out = check_two_stage(L, ctx, label, names, mats, counters)
+    print(f"[{label}] {time.perf_counter() - t0:.2f} s")
+    for which in (sr.Q_ONE, sr.Q_TWO, sr.Q_ALL):
+        identical(out, which, copies, label)
+
+
+@pytest.mark.parametrize("batch,nw", [(9, 4), (86, 8)])
+def test_form_bt2_xcd_deal(lib_ctx, batch, nw):
+    """k, l: the Q2 back-transformation with the workgroups dealt to the XCDs by matrix (eight matrices and more; neither batch a
+    multiple of eight): k_bt2_apply<4> (9 matrices) and k_bt2_apply<8> (86: 3 x 86 = 258 workgroups of 128 columns reach the
+    256 CUs; 85 would not).  Q2 alone and the whole factor (which = 0) of every member."""
+    skip_if_forms_overridden()
+    L, ctx = lib_ctx
+    n = 322
+    s1_parts = 2 if batch >= 32 else 1
+    names, mats = cycled_batch(n, batch, (0,))
+    ctx.set_two_stage(True)
+    label = f"form {'k' if nw == 4 else 'l'}: bt2 XCD deal n={n} x {batch}"
+    per_call = dict(panel_wg1_launches=4 * s1_parts, panel_unblocked_launches=s1_parts, symm_tri_launches=5 * s1_parts,
+                    gemm3_declined=5 * s1_parts)
+    t0 = time.perf_counter()
+    out, wrong = {}, {}
+    for calls, which in enumerate((sr.Q_TWO, sr.Q_ALL), 1):
+        out[which] = sr.reduce_host(L, ctx, mats, which)
+        assert out[which][5]
+        wrong[calls] = wrong_forms(ctx, label, calls, per_call, {"symm_slices": 1, "stage1_parts": s1_parts, "chase_stream_parts": 0},
+                                   {f"bt2_apply{nw}_solves": calls, "bt2_xcd_launches": calls}, False)
+    rows = []
+    for b, name in enumerate(names):
+        d, e, s, band, q2, _ = (x[b] if isinstance(x, np.ndarray) else x for x in out[sr.Q_TWO])
+        fig = {"recon(B,Q2,T)": sr.recon(sr.band_matrix(band), q2, sr.tridiagonal(d, e)), "orth(Q2)": sr.orth(q2),
+               "beyond_band": sr.band_beyond(band)}
+        d, e, s, band, q, _ = (x[b] if isinstance(x, np.ndarray) else x for x in out[sr.Q_ALL])
+        fig["recon(A,Q,T)"] = sr.recon(scaled(mats[b], s), q, sr.tridiagonal(d, e))
+        fig["orth(Q)"] = sr.orth(q)
+        rows.append((name, fig))
+    print(f"[{label}] {time.perf_counter() - t0:.2f} s")
+    report(label, rows)
+    assert not any(wrong.values()), (label, "call: counter: (got, expected)", wrong)

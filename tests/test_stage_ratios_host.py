@@ -22,10 +22,20 @@ def lapack_reduction(a):
     return q, sr.tridiagonal(np.diag(h).copy(), np.diag(h, -1).copy())
 
 
+_factors = {}
+
+
+def lapack_factors(label, a):
+    """(Q, T, w, V) of one input, computed once for the NumPy ratios and their torch twins."""
+    key = (label, hash(a.tobytes()))      # (the mixed batch has a member called random too)
+    if key not in _factors:
+        _factors[key] = lapack_reduction(a) + tuple(np.linalg.eigh(a))
+    return _factors[key]
+
+
 def check_dense(label, a):
     """(reduction recon, orth; eigh recon, orth) of one matrix, all at most LAPACK_GATE."""
-    q, t = lapack_reduction(a)
-    w, v = np.linalg.eigh(a)
+    q, t, w, v = lapack_factors(label, a)
     figures = (sr.recon(a, q, t), sr.orth(q), sr.recon(a, v, np.diag(w)), sr.orth(v))
     print(f"[{label}] dgehrd recon {figures[0]:.3f} orth {figures[1]:.3f}   eigh recon {figures[2]:.3f} orth {figures[3]:.3f}")
     assert max(figures) <= sr.LAPACK_GATE, (label, figures)
@@ -42,6 +52,49 @@ def test_lapack_on_the_mixed_batch(n):
     names, mats = sr.mixed_batch(n)
     for name, a in zip(names, mats):
         check_dense(f"{name} n={n}", a)
+
+
+def check_dense_t(label, a):
+    """The same four figures by recon_t / orth_t on CPU tensors: the same gate, and the NumPy figures to rounding."""
+    import torch
+
+    q, t, w, v = lapack_factors(label, a)
+    ta, tq, tt, tv = (torch.tensor(x) for x in (a, q, t, v))
+    figures = (sr.recon_t(ta, tq, tt), sr.orth_t(tq), sr.recon_t(ta, tv, torch.diag(torch.from_numpy(w))), sr.orth_t(tv))
+    ref = (sr.recon(a, q, t), sr.orth(q), sr.recon(a, v, np.diag(w)), sr.orth(v))
+    print(f"[{label}] torch: dgehrd recon {figures[0]:.3f} orth {figures[1]:.3f}   eigh recon {figures[2]:.3f} "
+          f"orth {figures[3]:.3f}   (NumPy {ref[0]:.3f} {ref[1]:.3f} {ref[2]:.3f} {ref[3]:.3f})")
+    assert max(figures) <= sr.LAPACK_GATE, (label, figures)
+    # the two evaluate one formula with other summation orders: they differ by the rounding of the products, about
+    # sqrt(n) ulp per entry, i.e. n^-1/2 <= 0.09 of a unit at these orders (n >= 130) -- further apart is another formula
+    assert all(abs(f - r) <= 0.1 for f, r in zip(figures, ref)), (label, figures, ref)
+
+
+@pytest.mark.parametrize("n", DENSE_ORDERS)
+def test_torch_ratios_on_random_matrices(n):
+    check_dense_t(f"random n={n}", sr.random_sym(n))
+
+
+@pytest.mark.parametrize("n", MIXED_ORDERS)
+def test_torch_ratios_on_the_mixed_batch(n):
+    names, mats = sr.mixed_batch(n)
+    for name, a in zip(names, mats):
+        check_dense_t(f"{name} n={n}", a)
+
+
+def test_torch_ratios_see_planted_perturbations():
+    import torch
+
+    n = 256
+    a = sr.random_sym(n)
+    q, t, _, _ = lapack_factors(f"random n={n}", a)
+    bad_q = torch.from_numpy(q + 1e-13 * np.random.RandomState(5).randn(n, n))
+    assert sr.orth_t(bad_q) > sr.GATE
+    bad_t = t.copy()
+    bad_t[n // 2, n // 2] += 2 * sr.GATE * n * sr.ULP * sr.norm1(a)
+    assert sr.recon_t(torch.from_numpy(a.copy()), torch.from_numpy(q), torch.from_numpy(bad_t)) > sr.GATE
+    z = torch.zeros((4, 4), dtype=torch.float64)
+    assert sr.recon_t(z, torch.eye(4, dtype=torch.float64), z) == 0.0
 
 
 @pytest.mark.parametrize("n", TRIDIAGONAL_ORDERS)
