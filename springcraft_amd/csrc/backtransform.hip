@@ -161,9 +161,10 @@ int backtransform_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, i
   // W = V^T Z on k_gemm3 (the role-split kernel; its K loop runs at 0.84 of the MFMA peak against k_gemm2's 0.74) when the
   // batch gives every CU a few of the 2 x ceil(ncols / 64) tiles per matrix without K slices; decided here because the
   // records say where W goes (a single slice writes straight to where the update reads it)
-  static const bool env_w3 = [] { const char* e = getenv("SPRINGCRAFT_GEMM3_W"); return !e || atoi(e) != 0; }();
   const bool al16 = (n & 1) == 0 && (off & 1) == 0 && (stride_z & 1) == 0 && (stride_a & 1) == 0 && (nbt & 1) == 0;
-  const bool w_gemm3 = env_w3 && al16 && gemm3_would_take(ctx, batch, nbt, ncols, n - off, kGemmAkBk, false, 1.0, 0.0, al16);
+  const bool w_gemm3 = sc_host::gemm_env().gemm3_w && al16 &&
+                       gemm3_would_take(ctx, {.count = batch, .m = nbt, .n = ncols, .k = n - off, .layout = kGemmAkBk, .lower = 0,
+                                              .alpha = 1.0, .beta = 0.0, .aligned16 = al16});
   if (w_gemm3) w1s = 1;
 
   // descriptor table: [gram | vt | w1 | update | x = G12 T2 | T12 = -T1 x] x npanels x batch  (each group contiguous
@@ -233,17 +234,17 @@ int backtransform_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, i
   if (phase == 0 || phase == 2) {
   hipLaunchKernelGGL(k_bt_clean, dim3((unsigned)npanels, (unsigned)batch), dim3(256), 0, st, d_a, stride_a, n, nbt,
                      nref, off);
-  SC_TRY(launch_gemm_f64(ctx, d_descs, (int)grp, nbt, nbt, kGemmTile, BL.splits_g, false, false, kGemmAkBk));
+  SC_TRY(launch_gemm_f64(ctx, d_descs, {.count = (int)grp, .max_m = nbt, .max_n = nbt, .layout = kGemmAkBk, .split_k = BL.splits_g}));
   hipLaunchKernelGGL(k_bt_tfactor, dim3((unsigned)(2 * npanels), (unsigned)batch), dim3(256),
                      sizeof(double) * (kNbtT * kNbtT + kNbtT), st, d_tri_ws, TL, d_bt_ws, BL, nref);
-  SC_TRY(launch_gemm_f64(ctx, d_descs + 4 * grp, (int)grp, kNbtT, kNbtT, kGemmTile, 1, false, false, kGemmAmBk));
-  SC_TRY(launch_gemm_f64(ctx, d_descs + 5 * grp, (int)grp, kNbtT, kNbtT, kGemmTile, 1, false, false, kGemmAmBk));
+  SC_TRY(launch_gemm_f64(ctx, d_descs + 4 * grp, {.count = (int)grp, .max_m = kNbtT, .max_n = kNbtT, .layout = kGemmAmBk}));
+  SC_TRY(launch_gemm_f64(ctx, d_descs + 5 * grp, {.count = (int)grp, .max_m = kNbtT, .max_n = kNbtT, .layout = kGemmAmBk}));
   }
   if (phase == 2) {
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
   }
-  SC_TRY(launch_gemm_f64(ctx, d_descs + grp, (int)grp, n, nbt, kGemmTile, 1, false, false, kGemmAmBk));
+  SC_TRY(launch_gemm_f64(ctx, d_descs + grp, {.count = (int)grp, .max_m = n, .max_n = nbt, .layout = kGemmAmBk}));
 
   PhaseTimer t_w(ctx, "bt1_w", st), t_u(ctx, "bt1_update", st);
   for (int p = npanels - 1; p >= 0; --p) {
@@ -252,10 +253,10 @@ int backtransform_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, i
     {
       const int pc = std::min(nbt, n - p * nbt);
       const bool al = al16 && ((p * nbt) & 1) == 0;
-      if (!w_gemm3 || launch_gemm3_uniform(ctx, d_descs + 2 * grp + (size_t)p * batch, batch, pc, ncols, mrow, kGemmAkBk, false,
-                                           1.0, 0.0, al) != SC_OK)
-        SC_TRY(launch_gemm_f64(ctx, d_descs + 2 * grp + (size_t)p * batch, batch, nbt, ncols, kGemmTile, w1s, false, false,
-                               kGemmAkBk));
+      const GemmDesc* w = d_descs + 2 * grp + (size_t)p * batch;
+      if (!w_gemm3 || launch_gemm3_uniform(ctx, w, {.count = batch, .m = pc, .n = ncols, .k = mrow, .layout = kGemmAkBk, .lower = 0,
+                                                    .alpha = 1.0, .beta = 0.0, .aligned16 = al}) != SC_OK)
+        SC_TRY(launch_gemm_f64(ctx, w, {.count = batch, .max_m = nbt, .max_n = ncols, .layout = kGemmAkBk, .split_k = w1s}));
     }
     if (w1s > 1) hipLaunchKernelGGL(k_bt_sum, dim3(256, (unsigned)batch), dim3(256), 0, st, d_bt_ws, BL, w1s, ncols);
     t_w.stop();
@@ -263,10 +264,10 @@ int backtransform_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, i
     {
       const int pc = std::min(nbt, n - p * nbt);
       const bool al = (n & 1) == 0 && ((p * nbt + off) & 1) == 0 && (stride_z & 1) == 0 && (stride_a & 1) == 0 && (nbt & 1) == 0;
-      if (launch_gemm3_uniform(ctx, d_descs + 3 * grp + (size_t)p * batch, batch, mrow, ncols, pc, kGemmAmBk, false, 1.0, 1.0,
-                               al) != SC_OK)
-        SC_TRY(launch_gemm_f64(ctx, d_descs + 3 * grp + (size_t)p * batch, batch, mrow, ncols, kGemmTile, 1, false, false,
-                               kGemmAmBk));
+      const GemmDesc* u = d_descs + 3 * grp + (size_t)p * batch;
+      if (launch_gemm3_uniform(ctx, u, {.count = batch, .m = mrow, .n = ncols, .k = pc, .layout = kGemmAmBk, .lower = 0, .alpha = 1.0,
+                                        .beta = 1.0, .aligned16 = al}) != SC_OK)
+        SC_TRY(launch_gemm_f64(ctx, u, {.count = batch, .max_m = mrow, .max_n = ncols, .layout = kGemmAmBk}));
     }
     t_u.stop();
   }

@@ -553,7 +553,7 @@ int batch_dcc_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
                            pl.stride, rag ? d_out : d_out + (size_t)b0 * N * N, N, kc * dim, k0 == 0 ? 0.0 : 1.0, rag,
                            (int)b0);
         SC_HIP(ctx, hipGetLastError());
-        SC_TRY(launch_gemm_f64(ctx, d_desc, nb, N, N, kGemmTile, 1, false, false, kGemmAmBn, false, pin));
+        SC_TRY(launch_gemm_f64(ctx, d_desc, {.count = nb, .max_m = N, .max_n = N, .layout = kGemmAmBn, .pin_tile = pin}));
       }
     }
   }

@@ -662,7 +662,7 @@ int pinvh_device(sc_ctx* ctx, double* d_a, int64_t n64, double rcond, double* d_
     D.c = d_out; D.ldc = n; D.m = n; D.n = n; D.k = n;
     D.alpha = 1.0; D.beta = 0.0;
     rc = sc_stage_upload(ctx, d_desc, &D, sizeof(D));
-    if (rc == SC_OK) rc = launch_gemm_f64(ctx, d_desc, 1, n, n, kGemmTile, 1, false, false, kGemmAmBn);
+    if (rc == SC_OK) rc = launch_gemm_f64(ctx, d_desc, {.count = 1, .max_m = n, .max_n = n, .layout = kGemmAmBn});
     if (rc == SC_OK) rc = sc_stage_end(ctx);
   }
   return rc;

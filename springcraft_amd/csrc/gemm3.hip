@@ -34,10 +34,6 @@
 //                                       holds columns 16 q .. 16 q + 15 (all 16 k of the step)
 //     A k-contiguous ("TN"): pieces like those of a k-contiguous B: 8 rows x 16 k each, quarter q holds rows 32 q .. + 31
 //   C image: column c at c * kRow, 128 rows each.
-#include <algorithm>
-#include <cstdlib>
-#include <vector>
-
 #include "gemm_f64.h"
 
 namespace {
@@ -513,48 +509,14 @@ __global__ __launch_bounds__(1024, 1) void k_gemm3(G3Args P) {
 
 }  // namespace
 
-namespace {
-bool g_gemm3_any_size = false;   // debugging (sc_dbg_gemm3_host): take every launch that qualifies, whatever its size
-int g_gemm3_order = -1;          // debugging (sc_dbg_gemm3_bench): tile order, -1 = SPRINGCRAFT_GEMM3_ORDER / the default
+// Launch L.count records with the same (m, n, k) on k_gemm3, or say that the launch is not one it takes (returns 1: the
+// caller uses launch_gemm_f64).  What is taken: sc_host::gemm3_takes.  lower: as launch_gemm_f64's lower_grid.
+bool gemm3_would_take(sc_ctx* ctx, const Gemm3Launch& L) {
+  return sc_host::gemm3_takes(sc_host::gemm_env(), gemm_device(ctx), L);
 }
 
-// Launch `count` records with the same (m, n, k) on k_gemm3, or say that the launch is not one it takes (returns 1: the
-// caller uses launch_gemm_f64).  Taken: layout kGemmAmBn / kGemmAmBk, alpha = 1, beta in {0, 1}, k a multiple of 16 and
-// >= 128, m (and n for kGemmAmBn) even, pointers and leading dimensions that keep 16-byte alignment (aligned16: the
-// caller knows its records), enough tiles to give every CU a few.  lower: as launch_gemm_f64's lower_grid.
-bool gemm3_would_take(sc_ctx* ctx, int count, int m, int n, int k, int layout, int lower, double alpha, double beta,
-                      bool aligned16) {
-  static const int env = [] { const char* e = getenv("SPRINGCRAFT_GEMM3"); return e ? atoi(e) : 1; }();
-  if (env == 0 || count <= 0) return false;
-  if (layout != kGemmAmBn && layout != kGemmAmBk && layout != kGemmAkBk) return false;
-  if (alpha != 1.0 || (beta != 0.0 && beta != 1.0)) return false;
-  if (!aligned16 || k < 128 || (k & 15) || (m & 1) || m < 2 || n < 1) return false;
-  if (layout == kGemmAmBn && (n & 1)) return false;
-  if (lower && m != n) return false;
-  // (the lower-only trailing update of the band reduction: 0.66 against k_gemm2's 0.65 of the MFMA peak on 32 matrices
-  // alone, 192 against 187 ms inside the C3 step -- its diagonal tiles store under lane predicates and its strips start
-  // with few tiles --: left to k_gemm2 unless SPRINGCRAFT_GEMM3_LOWER = 1)
-  // For a few large matrices it wins (one n = 24000 matrix, config C5: 186 -> 178 ms of trailing updates per solve): there
-  // the two half batches on two streams, whose panel QRs hide beside k_gemm2's workgroups, do not exist.
-  // Round 6: with the two half batches on two streams (ctx->gemm3_side_by_side, set by the band reduction) it takes the
-  // update after all -- on 224 workgroups instead of 256, which leaves an eighth of the CUs to the other half's panel QR
-  // and small products: C3 step 2200 -> 2150-2160 ms (same box, tools/quick_env_ab.sh: 208 / 216 / 224 workgroups 2157-2177 /
-  // 2149-2169 / 2145-2166, 232 / 240: 2190-2210, 256: 2191-2196; profiles/r06_syr2k_wgs.txt).
-  static const int env_lower = [] { const char* e = getenv("SPRINGCRAFT_GEMM3_LOWER"); return e ? atoi(e) : -1; }();
-  if (lower && !g_gemm3_any_size && (env_lower == 0 || (env_lower < 0 && count >= 8 && !ctx->gemm3_side_by_side))) return false;
-  // (the kernel's tile order is built on 8 XCDs x 32 workgroups: a device -- or a partition -- with fewer CUs stays on k_gemm2)
-  if (ctx->num_cus < 256 || ctx->gemm3_attr == 0) return false;
-  const long long TM = (m + 127) / 128, TN = (n + 63) / 64;
-  const long long hN = TN / 2;
-  const long long T1 = lower ? TM * TN - hN * (hN - 1) - ((TN & 1) ? hN : 0) : TM * TN;
-  const long long total = T1 * count;
-  if (env != 2 && !g_gemm3_any_size && total < 4LL * 256) return false;   // (SPRINGCRAFT_GEMM3 = 2: every launch that qualifies, for the tests)
-  return total <= 0x3fffffffLL;
-}
-
-int launch_gemm3_uniform(sc_ctx* ctx, const GemmDesc* d_desc, int count, int m, int n, int k, int layout, int lower,
-                         double alpha, double beta, bool aligned16) {
-  if (!gemm3_would_take(ctx, count, m, n, k, layout, lower, alpha, beta, aligned16)) return 1;
+int launch_gemm3_uniform(sc_ctx* ctx, const GemmDesc* d_desc, const Gemm3Launch& L) {
+  if (!gemm3_would_take(ctx, L)) return 1;
   if (ctx->gemm3_attr < 0) {   // per device, hence per context
     const bool ok0 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm3<kGemmAmBk>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, kG3Lds) == hipSuccess &&
@@ -565,15 +527,11 @@ int launch_gemm3_uniform(sc_ctx* ctx, const GemmDesc* d_desc, int count, int m, 
     ctx->gemm3_attr = (ok0 && ok2) ? 1 : 0;
   }
   if (ctx->gemm3_attr != 1) return 1;
-  static const int env_order = [] { const char* e = getenv("SPRINGCRAFT_GEMM3_ORDER"); return e ? atoi(e) : 1; }();
-  // Workgroups of a lower-only launch (the band reduction's trailing update), SPRINGCRAFT_GEMM3_LOWER_WGS (a multiple of
-  // 8, default 256): fewer than one per CU leaves CUs to the other half batch's panel QR that runs beside it
-  static const int env_lower_wgs = [] { const char* e = getenv("SPRINGCRAFT_GEMM3_LOWER_WGS"); return e ? std::max(8, std::min(256, atoi(e) / 8 * 8)) : 0; }();
-  const int nwg = lower ? (env_lower_wgs > 0 ? env_lower_wgs : (ctx->gemm3_side_by_side ? 224 : 256)) : 256;
-  G3Args A{d_desc, count, m, n, k, lower, beta != 0.0 ? 1 : 0, g_gemm3_order >= 0 ? g_gemm3_order : env_order, nwg};
+  const auto [nwg, order] = sc_host::gemm3_workgroups(sc_host::gemm_env(), gemm_device(ctx), L);
+  G3Args A{d_desc, L.count, L.m, L.n, L.k, L.lower, L.beta != 0.0 ? 1 : 0, order, nwg};
   const unsigned grid = (unsigned)nwg;
-  if (layout == kGemmAmBn) hipLaunchKernelGGL(k_gemm3<kGemmAmBn>, dim3(grid), dim3(1024), kG3Lds, ctx->stream, A);
-  else if (layout == kGemmAkBk) hipLaunchKernelGGL(k_gemm3<kGemmAkBk>, dim3(grid), dim3(1024), kG3Lds, ctx->stream, A);
+  if (L.layout == kGemmAmBn) hipLaunchKernelGGL(k_gemm3<kGemmAmBn>, dim3(grid), dim3(1024), kG3Lds, ctx->stream, A);
+  else if (L.layout == kGemmAkBk) hipLaunchKernelGGL(k_gemm3<kGemmAkBk>, dim3(grid), dim3(1024), kG3Lds, ctx->stream, A);
   else hipLaunchKernelGGL(k_gemm3<kGemmAmBk>, dim3(grid), dim3(1024), kG3Lds, ctx->stream, A);
   if (hipGetLastError() != hipSuccess) {
     ctx->gemm3_attr = 0;   // refused once: this context stays on k_gemm2
@@ -581,119 +539,4 @@ int launch_gemm3_uniform(sc_ctx* ctx, const GemmDesc* d_desc, int count, int m, 
   }
   ++ctx->cnt_gemm3_launches;
   return SC_OK;
-}
-
-// ---- debug entry for the GPU unit tests (tests/test_gemm_gpu.py; not part of the public C ABI): `count` products of one
-// shape on host data through k_gemm3, whatever their size.  a: count x (m x k) column-major; b: count x (k x n)
-// column-major (layout kGemmAmBk) or count x (n x k) column-major (kGemmAmBn); c: count x (m x n) column-major, in / out.
-// Returns SC_OK, or SC_ERR_INVALID_ARG when the kernel does not take the shape.
-extern "C" int sc_dbg_gemm3_host(sc_ctx* ctx, const double* a, const double* b, double* c, int count, int m, int n, int k,
-                                 int layout, int lower, double beta) {
-  if (!ctx || !a || !b || !c || count < 1 || m < 1 || n < 1 || k < 1) return SC_ERR_INVALID_ARG;
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t ea = (size_t)m * k, eb = (size_t)k * n, ec = (size_t)m * n;
-  char* base = nullptr;
-  SC_HIP(ctx, hipMalloc((void**)&base, (ea + eb + ec) * count * 8 + sizeof(GemmDesc) * (size_t)count + 256));
-  double* da = (double*)base;
-  double* db = da + ea * count;
-  double* dc = db + eb * count;
-  GemmDesc* dd = (GemmDesc*)(dc + ec * count);
-  int rc = SC_OK;
-  auto fail = [&](hipError_t e) { if (e != hipSuccess && rc == SC_OK) rc = sc_set_error(ctx, SC_ERR_HIP, "%s", hipGetErrorString(e)); };
-  fail(hipMemcpy(da, a, ea * count * 8, hipMemcpyHostToDevice));
-  fail(hipMemcpy(db, b, eb * count * 8, hipMemcpyHostToDevice));
-  fail(hipMemcpy(dc, c, ec * count * 8, hipMemcpyHostToDevice));
-  std::vector<GemmDesc> h((size_t)count);
-  for (int z = 0; z < count; ++z) {
-    GemmDesc D{};
-    D.a = da + ea * z; D.b = db + eb * z; D.c = dc + ec * z;
-    D.m = m; D.n = n; D.k = k; D.ldc = m; D.alpha = 1.0; D.beta = beta;
-    D.sa_i = 1; D.sa_k = m;
-    if (layout == kGemmAkBk) { D.sa_i = k; D.sa_k = 1; }   // a: count x (k x m) column-major
-    if (layout == kGemmAmBn) { D.sb_k = n; D.sb_j = 1; } else { D.sb_k = 1; D.sb_j = k; }
-    D.lower_only = lower;
-    h[(size_t)z] = D;
-  }
-  fail(hipMemcpy(dd, h.data(), sizeof(GemmDesc) * (size_t)count, hipMemcpyHostToDevice));
-  if (rc == SC_OK) {
-    g_gemm3_any_size = true;
-    const int took = launch_gemm3_uniform(ctx, dd, count, m, n, k, layout, lower, 1.0, beta, true);
-    g_gemm3_any_size = false;
-    if (took != SC_OK) rc = sc_set_error(ctx, SC_ERR_INVALID_ARG, "k_gemm3 does not take m %d n %d k %d layout %d", m, n, k, layout);
-    fail(hipStreamSynchronize(ctx->stream));
-  }
-  if (rc == SC_OK) fail(hipMemcpy(c, dc, ec * count * 8, hipMemcpyDeviceToHost));
-  (void)hipFree(base);
-  return rc;
-}
-
-// ---- debug / tuning entry (not part of the public C ABI): `count` matrices of one shape on freshly allocated buffers, timed
-// through k_gemm3 (kernel 3; order: its tile order) or k_gemm2 (kernel 2) with the SAME records.  C += A B, or with
-// lower != 0 the lower triangle of it (m == n).  tools/gemm3_shapes.py
-extern "C" int sc_dbg_gemm3_bench(sc_ctx* ctx, int count, int m, int n, int k, int layout, int lower, int kernel, int order,
-                                  int iters, double* ms_out) {
-  if (!ctx || count < 1 || iters < 1) return SC_ERR_INVALID_ARG;
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  // (experiments: leading dimensions of A / C and of an n-contiguous B other than m / n)
-  static const int ld_a = [] { const char* e = getenv("SC_DBG_LDA"); return e ? atoi(e) : 0; }();
-  static const int ld_c = [] { const char* e = getenv("SC_DBG_LDC"); return e ? atoi(e) : 0; }();
-  static const int ld_b = [] { const char* e = getenv("SC_DBG_LDB"); return e ? atoi(e) : 0; }();
-  const int lda = std::max(m, ld_a), ldc = std::max(m, ld_c), ldbn = std::max(n, ld_b);
-  const size_t ea = (size_t)lda * k, eb = layout == kGemmAmBn ? (size_t)ldbn * k : (size_t)k * n, ec = (size_t)ldc * n;
-  char* base = nullptr;
-  SC_HIP(ctx, hipMalloc((void**)&base, (ea + eb + ec) * count * 8 + sizeof(GemmDesc) * (size_t)count + 256));
-  double* da = (double*)base;
-  double* db = da + ea * count;
-  double* dc = db + eb * count;
-  GemmDesc* dd = (GemmDesc*)(dc + ec * count);
-  std::vector<double> hv(std::max(ea, eb));
-  unsigned long long sd = 88172645463325252ull;
-  for (auto& x : hv) { sd ^= sd << 13; sd ^= sd >> 7; sd ^= sd << 17; x = (double)((long long)(sd % 2001) - 1000) / 1000.0; }
-  int rc = SC_OK;
-  auto fail = [&](hipError_t e) { if (e != hipSuccess && rc == SC_OK) rc = sc_set_error(ctx, SC_ERR_HIP, "%s", hipGetErrorString(e)); };
-  for (int z = 0; z < count; ++z) {
-    fail(hipMemcpy(da + ea * z, hv.data(), ea * 8, hipMemcpyHostToDevice));
-    fail(hipMemcpy(db + eb * z, hv.data(), eb * 8, hipMemcpyHostToDevice));
-  }
-  fail(hipMemset(dc, 0, ec * count * 8));
-  std::vector<GemmDesc> h((size_t)count);
-  for (int z = 0; z < count; ++z) {
-    GemmDesc D{};
-    D.a = da + ea * z; D.b = db + eb * z; D.c = dc + ec * z;
-    D.m = m; D.n = n; D.k = k; D.ldc = ldc; D.alpha = 1.0; D.beta = 1.0;
-    D.sa_i = 1; D.sa_k = lda;
-    if (layout == kGemmAkBk) { D.sa_i = k; D.sa_k = 1; }
-    if (layout == kGemmAmBn) { D.sb_k = ldbn; D.sb_j = 1; } else { D.sb_k = 1; D.sb_j = k; }
-    D.lower_only = lower;
-    h[(size_t)z] = D;
-  }
-  fail(hipMemcpy(dd, h.data(), sizeof(GemmDesc) * (size_t)count, hipMemcpyHostToDevice));
-  auto launch = [&]() -> int {
-    if (kernel == 3) {
-      g_gemm3_any_size = true;
-      g_gemm3_order = order;
-      const int took = launch_gemm3_uniform(ctx, dd, count, m, n, k, layout, lower, 1.0, 1.0, true);
-      g_gemm3_any_size = false;
-      g_gemm3_order = -1;
-      return took == SC_OK ? SC_OK : SC_ERR_INVALID_ARG;
-    }
-    return launch_gemm_f64(ctx, dd, count, m, n, kGemmTile, 1, false, false, layout, lower != 0 && layout == kGemmAmBn);
-  };
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (rc == SC_OK) {
-    fail(hipEventCreate(&e0));
-    fail(hipEventCreate(&e1));
-    for (int it = 0; it < 2 && rc == SC_OK; ++it) rc = launch();
-    fail(hipEventRecord(e0, ctx->stream));
-    for (int it = 0; it < iters && rc == SC_OK; ++it) rc = launch();
-    fail(hipEventRecord(e1, ctx->stream));
-    fail(hipEventSynchronize(e1));
-    float ms = 0.f;
-    if (rc == SC_OK) fail(hipEventElapsedTime(&ms, e0, e1));
-    if (ms_out) *ms_out = ms / iters;
-  }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(base);
-  return rc;
 }

@@ -17,6 +17,7 @@
 #include <cstdint>
 
 #include "common.h"
+#include "gemm_policy.h"
 
 struct GemmDesc {
   const double* a;
@@ -36,45 +37,39 @@ struct GemmDesc {
   int a_tri;              // launches with tri = true: 1: A(i,k) counts only for i >= k; 2: only for k > i
 };
 
-// (`tile` argument of launch_gemm_f64: a leftover of round 1's kernel, ignored; k_gemm2 picks its block tile from the
-// launch size)
-constexpr int kGemmTile = 3;
-
-// Launch `count` problems (records d_desc[0..count)); max_m / max_n bound the grid.
-// tile: ignored (see kGemmTile).
+// One launch of `count` problems (records d_desc[0..count)) on k_gemm2; max_m / max_n bound the grid.  The policy --
+// block tile, grid order, chunks of at most 65535 records x slices -- is gemm_policy.h's.
+// layout (no default, every caller names it): kGemmAmBk / kGemmAkBk / kGemmAmBn, the records live in device memory.
 // split_k > 1: every record is cut into split_k K-slices (all records of a launch share it).
 // gather: the records carry a_kidx / b_kidx lists (D&C merges; layout kGemmAmBk only).
 // tri: the records carry a_tri masks (lower-stored symmetric A; band reduction; layouts kGemmAmBk / kGemmAkBk), no gathers.
-// layout (required): which axis of each operand has stride 1 in ALL records of the launch (the records live in device
-// memory, the host cannot look): kGemmAmBk "NN" (sa_i = 1, sb_k = 1), kGemmAkBk "TN" (sa_k = 1, sb_k = 1), kGemmAmBn
-// "NT" (sa_i = 1, sb_j = 1).  The block tile is chosen from the launch size.
 // lower_grid: every record of the launch is square, lower_only with row_off = col_off = 0 (the SYR2K of the band
 // reduction): only the tiles on and below the diagonal are launched (layout kGemmAmBn, no split-K).
-constexpr int kGemmAmBk = 0, kGemmAkBk = 1, kGemmAmBn = 2;
 // pin_tile: 0 = the block tile follows the launch size; 1 / 2 / 3 = 128 x 128 / 128 x 64 / 64 x 64 whatever the size, for
 // callers that cut one piece of work into several launches and want every piece to round alike (gemm_f64_tile returns
 // the code the size rule picks for a launch).
-int launch_gemm_f64(sc_ctx* ctx, const GemmDesc* d_desc, int count, int max_m, int max_n, int tile,
-                    int split_k = 1, bool gather = false, bool tri = false, int layout = -1, bool lower_grid = false,
-                    int pin_tile = 0);
+// dbg: the debug entries' overrides (gemm_debug.hip); every other caller leaves it alone.
+using sc_host::GemmLaunch, sc_host::Gemm3Launch, sc_host::GemmOverrides;
+int launch_gemm_f64(sc_ctx* ctx, const GemmDesc* d_desc, const GemmLaunch& L);
 int gemm_f64_tile(const sc_ctx* ctx, int count, int max_m, int max_n, int layout);
+// (what the policy needs to know of a context)
+inline sc_host::GemmDevice gemm_device(const sc_ctx* ctx) { return {ctx->num_cus, ctx->gemm3_attr, ctx->gemm3_side_by_side}; }
 
-// The role-split persistent kernel k_gemm3 (gemm3.hip) for launches whose records share (m, n, k): returns SC_OK when it
-// took the launch, 1 when the launch is not one it takes (the caller then uses launch_gemm_f64).  alpha must be 1 and beta
-// 0 or 1 -- callers fold a sign into an operand --; aligned16: every operand pointer and leading dimension of the
-// records keeps 16-byte alignment (the host built them).  SPRINGCRAFT_GEMM3 = 0 switches it off, = 2 takes every
+// The role-split persistent kernel k_gemm3 (gemm3.hip) for launches whose `count` records share (m, n, k): returns SC_OK
+// when it took the launch, 1 when the launch is not one it takes (the caller then uses launch_gemm_f64).  alpha must be 1
+// and beta 0 or 1 -- callers fold a sign into an operand --; aligned16: every operand pointer and leading dimension of
+// the records keeps 16-byte alignment (the host built them).  SPRINGCRAFT_GEMM3 = 0 switches it off, = 2 takes every
 // launch that qualifies whatever its size (tests).
 // lower: 0 all of C; 1 the lower triangle (as lower_only = 1 with row_off = col_off = 0, m == n); 2 as lower_only = 2.
-int launch_gemm3_uniform(sc_ctx* ctx, const GemmDesc* d_desc, int count, int m, int n, int k, int layout, int lower,
-                         double alpha, double beta, bool aligned16);
+int launch_gemm3_uniform(sc_ctx* ctx, const GemmDesc* d_desc, const Gemm3Launch& L);
 // (the launcher's decision without the launch: callers that lay out their records differently for the two kernels)
-bool gemm3_would_take(sc_ctx* ctx, int count, int m, int n, int k, int layout, int lower, double alpha, double beta,
-                      bool aligned16);
+bool gemm3_would_take(sc_ctx* ctx, const Gemm3Launch& L);
 
 // The symmetric product X = A V (A lower stored, V and X with 64 columns) of the band reduction on k_symm3 (symm3.hip):
-// SC_OK when it took the launch, 1 when the launch is not one it takes (m a multiple of 16, 16-byte aligned operands,
+// SC_OK when it took the launch, 1 when the launch is not one it takes (m even and >= 256, 16-byte aligned operands,
 // enough tiles; SPRINGCRAFT_SYMM3 = 0 switches it off, = 2 takes every launch that qualifies).  split: K slices, slice s
 // into c + s * split_stride.  The kernel reads A where (row | 1) >= col: see its header for what the writers of A keep.
-// any_size: skip the "enough work items" part of the decision (the caller made it for another record count).
-int launch_symm3(sc_ctx* ctx, const GemmDesc* d_desc, int count, int m, int split, bool aligned16, bool any_size = false);
+// any_size: skip the "enough work items" part of the decision (the caller made it with symm3_would_take for another
+// record count -- the parts of a split batch --, or is a debug entry).
+int launch_symm3(sc_ctx* ctx, const GemmDesc* d_desc, int count, int m, int split, bool aligned16, bool any_size);
 bool symm3_would_take(sc_ctx* ctx, int count, int m, int split, bool aligned16);

@@ -3,11 +3,9 @@
 // of the solver states its operand layout and runs k_gemm2.)
 #include <algorithm>
 #include <cmath>
-#include <cstdlib>
-#include <vector>
 
 #include "gemm_f64.h"
-#include "springcraft_hip_debug.h"   // sc_dbg_gemm_record
+#include "springcraft_hip_debug.h"   // the stamp and trace readers
 
 namespace {
 
@@ -388,26 +386,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm2(const GemmDesc* __restrict__ d
 template <int BM, int BN, bool AM, bool BNC, bool TRI, bool GATHER = false>
 void launch_gemm2_inst(hipStream_t st, dim3 grid, const GemmDesc* d_desc, int split_k, bool lower = false) {
   constexpr size_t lds = sizeof(double) * 2 * (size_t)(StageImage<BM, AM>::kSize + StageImage<BN, BNC>::kSize);
+  static_assert(BM % BN == 0, "row tiles are whole multiples of column tiles (the lower-triangle grid)");
   // (per device: sc_raise_dyn_lds; a refusal surfaces as the launch error the caller checks)
   (void)sc_raise_dyn_lds(reinterpret_cast<const void*>(&k_gemm2<BM, BN, AM, BNC, TRI, GATHER>), (int)lds);
-  if (lower) {   // square launch: only the tiles of the lower triangle
-    static_assert(BM % BN == 0, "row tiles are whole multiples of column tiles");
-    const unsigned tiles = (unsigned)((long long)(BM / BN) * grid.x * (grid.x + 1) / 2);
-    grid = dim3(tiles, grid.z, 1);
-  }
-  int mode = lower ? 1 : 0;
-  const int gx = (int)grid.x, gy = (int)grid.y, gz = (int)grid.z;
-  static const bool no_balance = getenv("SPRINGCRAFT_GEMM_NO_BALANCE") != nullptr;
-  if (TRI && !lower && !no_balance && (long long)grid.x * grid.y * grid.z < 0x7fffffffLL) {
-    mode = 2;   // longest tiles first, over all records
-    grid = dim3(grid.x * grid.y * grid.z, 1, 1);
-  }
-  static const bool no_pair = getenv("SPRINGCRAFT_GEMM_NO_PAIR") != nullptr;
-  if (!TRI && !lower && !no_pair && gx >= 2 && gx <= 4 && (long long)(gy * gz + 8) * gx < 0x7fffffffLL) {
-    mode = 3;   // the row tiles of one B panel on one XCD
-    grid = dim3((unsigned)(((long long)gy * gz + 7) / 8 * 8 * gx), 1, 1);
-  }
-  hipLaunchKernelGGL((k_gemm2<BM, BN, AM, BNC, TRI, GATHER>), grid, dim3(256), lds, st, d_desc, split_k, mode, gx, gy, gz);
+  const sc_host::GemmGrid G = sc_host::gemm2_grid(sc_host::gemm_env(), BM, BN, grid.x, grid.y, grid.z, TRI, lower);
+  hipLaunchKernelGGL((k_gemm2<BM, BN, AM, BNC, TRI, GATHER>), dim3(G.x, G.y, G.z), dim3(256), lds, st, d_desc, split_k, G.mode,
+                     G.gx, G.gy, G.gz);
 }
 
 template <int BM, int BN, bool TRI>
@@ -424,72 +408,40 @@ void launch_gemm2_layout(hipStream_t st, dim3 grid, const GemmDesc* d_desc, int 
 
 }  // namespace
 
-namespace {
-int g_gemm2_force_tile = 0;   // debugging (sc_dbg_gemm_bench): 1 = 128 x 128, 2 = 128 x 64, 3 = 64 x 64
-// block tile of k_gemm2: 128-wide in a dimension when the problem is at least that wide there and the launch still has
-// >= 2 workgroups per CU (lower-only launches: about half of the square grid does work)
-void gemm2_tile(const sc_ctx* ctx, int count, int max_m, int max_n, int split_k, int layout, int* bm, int* bn,
-                int pin_tile = 0) {
-  static const int env_force = [] { const char* e = getenv("SPRINGCRAFT_GEMM2_TILE"); return e ? atoi(e) : 0; }();
-  const int force = g_gemm2_force_tile ? g_gemm2_force_tile : env_force ? env_force : pin_tile;
-  if (force == 1 && layout != kGemmAkBk) { *bm = 128; *bn = 128; return; }
-  if (force == 1) { *bm = 128; *bn = 64; return; }
-  if (force == 2) { *bm = 128; *bn = 64; return; }
-  if (force == 3) { *bm = 64; *bn = 64; return; }
-  const long long cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-  auto blocks = [&](int a, int b) {
-    return (long long)((max_m + a - 1) / a) * ((max_n + b - 1) / b) * count * split_k;
-  };
-  *bm = 64; *bn = 64;
-  if (max_m > 64 && blocks(128, 64) >= 2 * cus) *bm = 128;
-  if (*bm == 128 && max_n > 64 && layout != kGemmAkBk && blocks(128, 128) >= 3 * cus) *bn = 128;
-}
-}  // namespace
-
 int gemm_f64_tile(const sc_ctx* ctx, int count, int max_m, int max_n, int layout) {
-  int bm, bn;
-  gemm2_tile(ctx, count, max_m, max_n, 1, layout, &bm, &bn);
-  return bm == 128 ? (bn == 128 ? 1 : 2) : 3;
+  const sc_host::GemmTile T = sc_host::gemm2_tile(sc_host::gemm_env(), ctx->num_cus, {.count = count, .max_m = max_m, .max_n = max_n, .layout = layout});
+  return T.bm == 128 ? (T.bn == 128 ? 1 : 2) : 3;
 }
 
-int launch_gemm_f64(sc_ctx* ctx, const GemmDesc* d_desc, int count, int max_m, int max_n, int tile,
-                    int split_k, bool gather, bool tri, int layout, bool lower_grid, int pin_tile) {
-  static const bool no_lower = getenv("SPRINGCRAFT_GEMM_NO_LOWER_GRID") != nullptr;
-  const bool lower = lower_grid && !no_lower && layout == kGemmAmBn && !tri && !gather && split_k <= 1 && max_m == max_n;
-  if (count <= 0 || max_m <= 0 || max_n <= 0) return SC_OK;
-  if (split_k < 1) split_k = 1;
-  if (split_k > 65535) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "split_k %d too large", split_k);
-  // grid.z (records x K slices) is limited to 65535: longer record lists go out in chunks (the D&C merges of a batch of
-  // some thousand matrices get there)
-  if ((long long)count * split_k > 65535) {
-    const int max_rec = 65535 / split_k;
-    for (int r0 = 0; r0 < count; r0 += max_rec)
-      SC_TRY(launch_gemm_f64(ctx, d_desc + r0, std::min(max_rec, count - r0), max_m, max_n, tile, split_k, gather, tri,
-                             layout, lower_grid, pin_tile));
+int launch_gemm_f64(sc_ctx* ctx, const GemmDesc* d_desc, const GemmLaunch& launch) {
+  const sc_host::GemmEnv& E = sc_host::gemm_env();
+  const bool lower = sc_host::gemm2_lower_grid_allowed(E, launch);
+  if (launch.count <= 0 || launch.max_m <= 0 || launch.max_n <= 0) return SC_OK;
+  GemmLaunch L = launch;
+  if (L.split_k < 1) L.split_k = 1;
+  if (L.split_k > 65535) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "split_k %d too large", L.split_k);
+  const int max_rec = sc_host::gemm2_records_per_launch(L.count, L.split_k);
+  if (max_rec < L.count) {
+    for (int r0 = 0; r0 < launch.count; r0 += max_rec) {
+      L.count = std::min(max_rec, launch.count - r0);
+      SC_TRY(launch_gemm_f64(ctx, d_desc + r0, L));
+    }
     return SC_OK;
   }
+  const int max_m = L.max_m, max_n = L.max_n, split_k = L.split_k, layout = L.layout, tri = L.tri;
+  const unsigned gz = (unsigned)(L.count * split_k);   // (<= 65535: gemm2_records_per_launch)
   hipStream_t st = ctx->stream;
-  if (gather && !tri && layout == kGemmAmBk) {
-    // merges of the divide & conquer: 128 x 64 tiles while they fill the chip, else 64 x 64
-    const long long cus = ctx->num_cus > 0 ? ctx->num_cus : 256;
-    const long long gz = (long long)count * split_k;
-    if (gz > 65535) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "GEMM launch with %lld records x slices (max 65535)", gz);
-    const bool by_size = max_m > 64 && (long long)((max_m + 127) / 128) * ((max_n + 63) / 64) * gz >= 2 * cus;
-    // (the debug entries' tile override picks the instantiation whatever the size: 2 = 128 x 64, 3 = 64 x 64)
-    const bool big = g_gemm2_force_tile == 2 ? true : (g_gemm2_force_tile == 3 ? false : by_size);
-    const int bm = big ? 128 : 64;
-    dim3 grid((unsigned)((max_m + bm - 1) / bm), (unsigned)((max_n + 63) / 64), (unsigned)gz);
-    if (big) launch_gemm2_inst<128, 64, true, false, false, true>(st, grid, d_desc, split_k);
+  if (L.gather && !tri && layout == kGemmAmBk) {   // merges of the divide & conquer
+    const int bm = sc_host::gemm2_gather_tile(ctx->num_cus, L).bm;
+    dim3 grid((unsigned)((max_m + bm - 1) / bm), (unsigned)((max_n + 63) / 64), gz);
+    if (bm == 128) launch_gemm2_inst<128, 64, true, false, false, true>(st, grid, d_desc, split_k);
     else launch_gemm2_inst<64, 64, true, false, false, true>(st, grid, d_desc, split_k);
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
   }
-  if (!gather && layout >= 0 && layout <= 2 && !(tri && layout == kGemmAmBn)) {
-    int bm, bn;
-    gemm2_tile(ctx, count, max_m, max_n, split_k, layout, &bm, &bn, pin_tile);
-    const long long gz = (long long)count * split_k;
-    if (gz > 65535) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "GEMM launch with %lld records x slices (max 65535)", gz);
-    dim3 grid((unsigned)((max_m + bm - 1) / bm), (unsigned)((max_n + bn - 1) / bn), (unsigned)gz);
+  if (!L.gather && layout >= 0 && layout <= 2 && !(tri && layout == kGemmAmBn)) {
+    const auto [bm, bn] = sc_host::gemm2_tile(E, ctx->num_cus, L);
+    dim3 grid((unsigned)((max_m + bm - 1) / bm), (unsigned)((max_n + bn - 1) / bn), gz);
     if (bm == 128 && bn == 128) {
       if (tri) launch_gemm2_layout<128, 128, true>(st, grid, d_desc, split_k, layout, lower);
       else launch_gemm2_layout<128, 128, false>(st, grid, d_desc, split_k, layout, lower);
@@ -503,9 +455,8 @@ int launch_gemm_f64(sc_ctx* ctx, const GemmDesc* d_desc, int count, int max_m, i
     SC_HIP(ctx, hipGetLastError());
     return SC_OK;
   }
-  (void)tile;
   return sc_set_error(ctx, SC_ERR_INVALID_ARG, "GEMM launch without a supported operand layout (layout %d, gather %d, tri %d)",
-                      layout, (int)gather, (int)tri);
+                      layout, (int)L.gather, (int)tri);
 }
 
 extern "C" int sc_dbg_gemm_stamps(unsigned long long* out4, int reset) {
@@ -538,256 +489,4 @@ extern "C" int sc_dbg_gemm_trace(unsigned long long* out, int max_records, int* 
   (void)out; (void)max_records; (void)count; (void)reset;
   return 1;
 #endif
-}
-
-// ---- debug / tuning entry point (not part of the public C ABI) ----------------------------------------------
-// Times `iters` launches of one GEMM shape on freshly allocated buffers.  mode: 0 = NN (A m x k col-major,
-// B k x n col-major), 1 = NT lower-only (SYR2K shape: B stored n x k), 2 = TN (A stored k x m).
-extern "C" int sc_dbg_gemm_bench(sc_ctx* ctx, int m, int n, int k, int mode, int tile, int split_k, int iters,
-                                 int beta_one, double* ms_out, double* max_err_out) {
-  if (!ctx) return SC_ERR_INVALID_ARG;
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const size_t ea = (size_t)m * k, eb = (size_t)k * n, ec = (size_t)m * n * (split_k > 1 ? split_k : 1);
-  double *a, *b, *c;
-  GemmDesc* dd;
-  SC_HIP(ctx, hipMalloc(&a, ea * 8));
-  SC_HIP(ctx, hipMalloc(&b, eb * 8));
-  SC_HIP(ctx, hipMalloc(&c, ec * 8));
-  SC_HIP(ctx, hipMalloc(&dd, sizeof(GemmDesc)));
-  std::vector<double> ha(ea), hb(eb), hc(ec, 0.0);
-  unsigned long long s = 88172645463325252ull;
-  auto rnd = [&]() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (double)((long long)(s % 2001) - 1000) / 1000.0; };
-  for (auto& x : ha) x = rnd();
-  for (auto& x : hb) x = rnd();
-  SC_HIP(ctx, hipMemcpy(a, ha.data(), ea * 8, hipMemcpyHostToDevice));
-  SC_HIP(ctx, hipMemcpy(b, hb.data(), eb * 8, hipMemcpyHostToDevice));
-  SC_HIP(ctx, hipMemset(c, 0, ec * 8));
-  GemmDesc D{};
-  D.a = a; D.b = b; D.c = c; D.m = m; D.n = n; D.k = k; D.ldc = m;
-  D.alpha = 1.0; D.beta = beta_one ? 1.0 : 0.0;
-  if (mode == 0) { D.sa_i = 1; D.sa_k = m; D.sb_k = 1; D.sb_j = k; }
-  if (mode == 1) { D.sa_i = 1; D.sa_k = m; D.sb_k = n; D.sb_j = 1; D.lower_only = 1; }
-  if (mode == 2) { D.sa_i = k; D.sa_k = 1; D.sb_k = 1; D.sb_j = k; }
-  D.split_stride = (long long)m * n;
-  SC_HIP(ctx, hipMemcpy(dd, &D, sizeof(D), hipMemcpyHostToDevice));
-  // tile 10 .. 13: k_gemm2 (10: automatic block tile, 11: 128 x 128, 12: 128 x 64, 13: 64 x 64)
-  if (tile < 10 || tile > 13) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "tile id %d (10 .. 13)", tile);
-  const int layout = mode == 0 ? kGemmAmBk : (mode == 1 ? kGemmAmBn : kGemmAkBk);
-  g_gemm2_force_tile = tile - 10;
-  SC_TRY(launch_gemm_f64(ctx, dd, 1, m, n, tile, split_k, false, false, layout, mode == 1 && m == n));
-  SC_HIP(ctx, hipStreamSynchronize(st));
-  // spot check 64 entries against a host dot product (beta path: C was 0 before the first launch)
-  SC_HIP(ctx, hipMemcpy(hc.data(), c, ec * 8, hipMemcpyDeviceToHost));
-  double maxerr = 0.0;
-  for (int t = 0; t < 64; ++t) {
-    int i = (int)((t * 7919ull) % m), j = (int)((t * 104729ull) % n);
-    if (mode == 1 && i < j) { int tmp = i; i = j; j = tmp; if (i >= m || j >= n) continue; }
-    double ref = 0.0;
-    for (int kk = 0; kk < k; ++kk) {
-      const double av = mode == 2 ? ha[(size_t)i * k + kk] : ha[(size_t)kk * m + i];
-      const double bv = mode == 1 ? hb[(size_t)kk * n + j] : hb[(size_t)j * k + kk];
-      ref += av * bv;
-    }
-    double got = 0.0;
-    for (int sl = 0; sl < (split_k > 1 ? split_k : 1); ++sl) got += hc[(size_t)sl * m * n + (size_t)j * m + i];
-    maxerr = fmax(maxerr, fabs(got - ref));
-  }
-  if (max_err_out) *max_err_out = maxerr;
-  hipEvent_t e0, e1;
-  SC_HIP(ctx, hipEventCreate(&e0));
-  SC_HIP(ctx, hipEventCreate(&e1));
-  SC_HIP(ctx, hipEventRecord(e0, st));
-  for (int it = 0; it < iters; ++it) SC_TRY(launch_gemm_f64(ctx, dd, 1, m, n, tile, split_k, false, false, layout, mode == 1 && m == n));
-  SC_HIP(ctx, hipEventRecord(e1, st));
-  SC_HIP(ctx, hipEventSynchronize(e1));
-  float ms = 0.f;
-  SC_HIP(ctx, hipEventElapsedTime(&ms, e0, e1));
-  if (ms_out) *ms_out = ms / iters;
-  g_gemm2_force_tile = 0;
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(dd);
-  return SC_OK;
-}
-
-// ---- debug entry point for the GPU unit tests of the launch paths (tests/test_gemm_gpu.py): ONE launch of one record
-// on host data.  a, b as sc_dbg_gemm_bench lays them out for `mode`; c: m x n column-major, in / out (with split_k > 1
-// the slices are summed into c on the host and beta must be 0).  lower_grid as launch_gemm_f64 takes it.  alpha == 0
-// with beta != 0 is refused (gemm_f64.h).
-extern "C" int sc_dbg_gemm_host(sc_ctx* ctx, const double* a, const double* b, double* c, int m, int n, int k, int mode,
-                                int tile, int split_k, double alpha, double beta, int lower_grid) {
-  if (!ctx || !a || !b || !c || m <= 0 || n <= 0 || k < 0 || split_k < 1) return SC_ERR_INVALID_ARG;
-  if (split_k > 1 && beta != 0.0) return SC_ERR_INVALID_ARG;
-  if (alpha == 0.0 && beta != 0.0) return SC_ERR_INVALID_ARG;   // not a record the kernel takes (gemm_f64.h)
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  const size_t ea = (size_t)m * std::max(k, 1), eb = (size_t)std::max(k, 1) * n, ec = (size_t)m * n * split_k;
-  char* base = nullptr;
-  SC_HIP(ctx, hipMalloc((void**)&base, (ea + eb + ec) * 8 + 256));
-  double* da = (double*)base;
-  double* db = da + ea;
-  double* dc = db + eb;
-  GemmDesc* dd = (GemmDesc*)(dc + ec);
-  int rc = SC_OK;
-  auto fail = [&](hipError_t e) { if (e != hipSuccess && rc == SC_OK) rc = sc_set_error(ctx, SC_ERR_HIP, "%s", hipGetErrorString(e)); };
-  if (k > 0) { fail(hipMemcpy(da, a, (size_t)m * k * 8, hipMemcpyHostToDevice)); fail(hipMemcpy(db, b, (size_t)k * n * 8, hipMemcpyHostToDevice)); }
-  for (int sl = 0; sl < split_k; ++sl) fail(hipMemcpy(dc + (size_t)sl * m * n, c, (size_t)m * n * 8, hipMemcpyHostToDevice));
-  GemmDesc D{};
-  D.a = da; D.b = db; D.c = dc; D.m = m; D.n = n; D.k = k; D.ldc = m;
-  D.alpha = alpha; D.beta = beta;
-  if (mode == 0) { D.sa_i = 1; D.sa_k = m; D.sb_k = 1; D.sb_j = k; }
-  if (mode == 1) { D.sa_i = 1; D.sa_k = m; D.sb_k = n; D.sb_j = 1; D.lower_only = 1; }
-  if (mode == 2) { D.sa_i = k; D.sa_k = 1; D.sb_k = 1; D.sb_j = k; }
-  D.split_stride = (long long)m * n;
-  fail(hipMemcpy(dd, &D, sizeof(D), hipMemcpyHostToDevice));
-  if (rc == SC_OK) {
-    const int layout = mode == 0 ? kGemmAmBk : (mode == 1 ? kGemmAmBn : kGemmAkBk);
-    if (tile < 10 || tile > 13) {
-      rc = sc_set_error(ctx, SC_ERR_INVALID_ARG, "tile id %d (10 .. 13)", tile);
-    } else {
-      g_gemm2_force_tile = tile - 10;
-      rc = launch_gemm_f64(ctx, dd, 1, m, n, tile, split_k, false, false, layout, lower_grid != 0);
-      g_gemm2_force_tile = 0;
-    }
-    fail(hipStreamSynchronize(st));
-  }
-  if (rc == SC_OK) {
-    std::vector<double> h(ec);
-    fail(hipMemcpy(h.data(), dc, ec * 8, hipMemcpyDeviceToHost));
-    if (rc == SC_OK) {
-      if (split_k == 1) std::copy(h.begin(), h.end(), c);
-      else
-        for (size_t i = 0; i < (size_t)m * n; ++i) {
-          double sum = 0.0;
-          for (int sl = 0; sl < split_k; ++sl) sum += h[(size_t)sl * m * n + i];
-          c[i] = sum;
-        }
-    }
-  }
-  (void)hipFree(base);
-  return rc;
-}
-
-// ---- debug entry point for the GPU unit tests of the record-level launch paths (tests/test_gemm_records_gpu.py): ONE
-// launch_gemm_f64 call on records the host describes -- triangular operands, gather lists, grouped launches, sub-matrix
-// views, chunked record lists.  Operands live in one arena of doubles (in / out: copied whole to the device and whole
-// back), index lists in one arena of ints; a record holds element offsets into them in place of pointers.  Nothing is
-// launched unless every address a record can make the kernel touch lies inside its arena.
-static_assert(sizeof(sc_dbg_gemm_record) == 144, "the tests mirror this layout as a NumPy record type");
-namespace {
-constexpr long long kRecGuard = 4096;                // doubles in front of and behind the device copy of the arena
-constexpr unsigned long long kRecGuardBits = 0x7ff8a5a5a5a5a5a5ull;   // a quiet NaN that no operand holds
-
-// nullptr, or what is wrong with record r of the launch
-const char* gemm_record_problem(const sc_dbg_gemm_record& R, long long arena_len, const int* idx, long long idx_len,
-                                int max_m, int max_n, int split_k, bool gather, bool tri, int layout, bool lower_grid) {
-  typedef __int128 wide;
-  if (R.m < 0 || R.n < 0 || R.k < 0) return "negative size";
-  if (R.m > max_m || R.n > max_n) return "larger than max_m x max_n";
-  if (R.sa_i < 0 || R.sa_k < 0 || R.sb_k < 0 || R.sb_j < 0 || R.ldc < 0 || R.split_stride < 0) return "negative stride";
-  if (layout == kGemmAmBk && (R.sa_i != 1 || R.sb_k != 1)) return "strides do not match layout kGemmAmBk";
-  if (layout == kGemmAkBk && (R.sa_k != 1 || R.sb_k != 1)) return "strides do not match layout kGemmAkBk";
-  if (layout == kGemmAmBn && (R.sa_i != 1 || R.sb_j != 1)) return "strides do not match layout kGemmAmBn";
-  if (R.lower_only < 0 || R.lower_only > 2) return "lower_only not 0, 1 or 2";
-  if (R.a_tri < 0 || R.a_tri > 2 || (R.a_tri != 0 && !tri)) return "a_tri without a tri launch, or not 0, 1 or 2";
-  if (!gather && (R.a_kidx != -1 || R.b_kidx != -1 || R.c_jidx != -1)) return "index list without a gather launch";
-  if (R.alpha == 0.0 && R.beta != 0.0) return "alpha == 0 with beta != 0";
-  if (!(R.alpha == R.alpha) || !(R.beta == R.beta)) return "alpha or beta is NaN";
-  if (lower_grid && (R.lower_only == 0 || R.row_off != 0 || R.col_off != 0)) return "lower_grid needs lower_only records without offsets";
-  if (R.a < 0 || R.a > arena_len || R.b < 0 || R.b > arena_len || R.c < 0 || R.c > arena_len) return "operand offset outside the arena";
-  // index lists: [off, off + length) inside the int arena, entries >= 0; *last = the largest entry
-  auto list = [&](long long off, int len, long long* last) -> bool {
-    *last = (long long)len - 1;
-    if (off == -1) return true;
-    if (off < 0 || off > idx_len || (long long)len > idx_len - off) return false;
-    long long mx = -1;
-    for (int t = 0; t < len; ++t) {
-      if (idx[off + t] < 0) return false;
-      mx = std::max<long long>(mx, idx[off + t]);
-    }
-    *last = mx;
-    return true;
-  };
-  long long ka = 0, kb = 0, jc = 0;
-  if (!list(R.a_kidx, R.k, &ka) || !list(R.b_kidx, R.k, &kb) || !list(R.c_jidx, R.n, &jc))
-    return "index list outside the int arena, or with a negative entry";
-  if (R.m == 0 || R.n == 0) return nullptr;   // every workgroup of the record exits before it touches an operand
-  if (R.ldc < R.m) return "ldc < m";
-  if (R.k > 0) {
-    if ((wide)R.a + (wide)(R.m - 1) * R.sa_i + (wide)ka * R.sa_k >= (wide)arena_len) return "A reaches outside the arena";
-    if ((wide)R.b + (wide)kb * R.sb_k + (wide)(R.n - 1) * R.sb_j >= (wide)arena_len) return "B reaches outside the arena";
-  }
-  if ((wide)R.c + (wide)(split_k - 1) * R.split_stride + (wide)jc * R.ldc + (R.m - 1) >= (wide)arena_len)
-    return "C reaches outside the arena";
-  return nullptr;
-}
-}  // namespace
-
-extern "C" int sc_dbg_gemm_records_host(sc_ctx* ctx, double* arena, long long arena_len, const int* idx, long long idx_len,
-                                        const sc_dbg_gemm_record* recs, int count, int max_m, int max_n, int split_k,
-                                        int gather, int tri, int layout, int lower_grid, int tile) {
-  if (!ctx) return SC_ERR_INVALID_ARG;
-  if (!arena || arena_len <= 0 || arena_len > (1ll << 34) || idx_len < 0 || idx_len > (1ll << 34) || (idx_len > 0 && !idx) ||
-      !recs || count < 0 || count > (1 << 24) || max_m <= 0 || max_n <= 0 || split_k < 1 || split_k > 65535)
-    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "GEMM records: bad launch argument");
-  if (tile < 10 || tile > 13) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "tile id %d (10 .. 13)", tile);
-  if (layout < 0 || layout > 2 || (gather && (tri || layout != kGemmAmBk)) || (tri && layout == kGemmAmBn))
-    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "GEMM records: no kernel for layout %d, gather %d, tri %d", layout, gather, tri);
-  if (lower_grid && (layout != kGemmAmBn || tri || gather || split_k > 1 || max_m != max_n))
-    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "GEMM records: lower_grid is for square launches of layout kGemmAmBn without split-K");
-  for (int r = 0; r < count; ++r) {
-    const char* what = gemm_record_problem(recs[r], arena_len, idx, idx_len, max_m, max_n, split_k, gather != 0, tri != 0,
-                                           layout, lower_grid != 0);
-    if (what) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "GEMM record %d: %s", r, what);
-  }
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  // device image: [guard | arena | guard] [records] [index lists], each part on a 256-byte boundary
-  auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t b_arena = up((size_t)(arena_len + 2 * kRecGuard) * 8), b_desc = up((size_t)std::max(count, 1) * sizeof(GemmDesc));
-  const size_t b_idx = up((size_t)std::max<long long>(idx_len, 1) * 4);
-  char* base = nullptr;
-  SC_HIP(ctx, hipMalloc((void**)&base, b_arena + b_desc + b_idx));
-  double* d_front = (double*)base;
-  double* d_arena = d_front + kRecGuard;
-  double* d_back = d_arena + arena_len;
-  GemmDesc* d_desc = (GemmDesc*)(base + b_arena);
-  int* d_idx = (int*)(base + b_arena + b_desc);
-  int rc = SC_OK;
-  auto fail = [&](hipError_t e) { if (e != hipSuccess && rc == SC_OK) rc = sc_set_error(ctx, SC_ERR_HIP, "%s", hipGetErrorString(e)); };
-  std::vector<unsigned long long> guard((size_t)kRecGuard, kRecGuardBits), got((size_t)kRecGuard);
-  fail(hipMemcpy(d_front, guard.data(), (size_t)kRecGuard * 8, hipMemcpyHostToDevice));
-  fail(hipMemcpy(d_back, guard.data(), (size_t)kRecGuard * 8, hipMemcpyHostToDevice));
-  fail(hipMemcpy(d_arena, arena, (size_t)arena_len * 8, hipMemcpyHostToDevice));
-  if (idx_len > 0) fail(hipMemcpy(d_idx, idx, (size_t)idx_len * 4, hipMemcpyHostToDevice));
-  std::vector<GemmDesc> h_desc((size_t)count);
-  for (int r = 0; r < count; ++r) {
-    const sc_dbg_gemm_record& R = recs[r];
-    GemmDesc& D = h_desc[(size_t)r];
-    D = GemmDesc{};
-    D.a = d_arena + R.a; D.b = d_arena + R.b; D.c = d_arena + R.c;
-    D.m = R.m; D.n = R.n; D.k = R.k;
-    D.sa_i = R.sa_i; D.sa_k = R.sa_k; D.sb_k = R.sb_k; D.sb_j = R.sb_j; D.ldc = R.ldc;
-    D.alpha = R.alpha; D.beta = R.beta;
-    D.a_kidx = R.a_kidx >= 0 ? d_idx + R.a_kidx : nullptr;
-    D.b_kidx = R.b_kidx >= 0 ? d_idx + R.b_kidx : nullptr;
-    D.c_jidx = R.c_jidx >= 0 ? d_idx + R.c_jidx : nullptr;
-    D.lower_only = R.lower_only; D.row_off = R.row_off; D.col_off = R.col_off;
-    D.split_stride = R.split_stride; D.a_tri = R.a_tri;
-  }
-  if (count > 0) fail(hipMemcpy(d_desc, h_desc.data(), (size_t)count * sizeof(GemmDesc), hipMemcpyHostToDevice));
-  if (rc == SC_OK) {
-    g_gemm2_force_tile = tile - 10;
-    rc = launch_gemm_f64(ctx, d_desc, count, max_m, max_n, kGemmTile, split_k, gather != 0, tri != 0, layout, lower_grid != 0);
-    g_gemm2_force_tile = 0;
-    fail(hipStreamSynchronize(st));
-  }
-  if (rc == SC_OK) fail(hipMemcpy(arena, d_arena, (size_t)arena_len * 8, hipMemcpyDeviceToHost));
-  for (double* g : {d_front, d_back}) {
-    if (rc != SC_OK) break;
-    fail(hipMemcpy(got.data(), g, (size_t)kRecGuard * 8, hipMemcpyDeviceToHost));
-    if (rc == SC_OK && got != guard) rc = sc_set_error(ctx, SC_ERR_HIP, "GEMM records: the launch wrote outside the arena");
-  }
-  (void)hipFree(base);
-  return rc;
 }

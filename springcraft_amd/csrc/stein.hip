@@ -547,13 +547,13 @@ int stein_batched(sc_ctx* ctx, int n, int batch, const double* d_tri_ws, const T
       h[batch + b] = U;
     }
     SC_TRY(sc_stage_upload(ctx, d_descs, h.data(), h.size() * sizeof(GemmDesc)));
-    SC_TRY(launch_gemm_f64(ctx, d_descs, batch, m, m, kGemmTile, splits, false, false, kGemmAkBk));
+    SC_TRY(launch_gemm_f64(ctx, d_descs, {.count = batch, .max_m = m, .max_n = m, .layout = kGemmAkBk, .split_k = splits}));
     {
       double* gram0 = d_ws + 7 * stein_nm4(n, m);
       hipLaunchKernelGGL(k_chol_inv, dim3((unsigned)batch), dim3(256), 0, st, gram0, stride_ws, m, splits,
                          gram0 + (size_t)32 * m * m, stride_ws);
     }
-    SC_TRY(launch_gemm_f64(ctx, d_descs + batch, batch, n, m, kGemmTile, 1, false, false, kGemmAmBk));
+    SC_TRY(launch_gemm_f64(ctx, d_descs + batch, {.count = batch, .max_m = n, .max_n = m, .layout = kGemmAmBk}));
     (void)x_cur;
   }
   t_qr.stop();

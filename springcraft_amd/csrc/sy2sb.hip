@@ -1408,35 +1408,37 @@ static int run_panel(const PanelRun& R, int p, int lo, int hi, hipStream_t ps, b
       hipLaunchKernelGGL(k_sum_xslices, dim3((unsigned)((m + 255) / 256), kB, (unsigned)nb), dim3(256), 0, ps, sb_h, SL, r0);
   } else {
     ++ctx->cnt_symm_tri;
-    SC_TRY(launch_gemm_f64(ctx, g + lo, nb, m, kB, kGemmTile, SL.symm_split, false, true, kGemmAmBk));           // X1 = L V
-    SC_TRY(launch_gemm_f64(ctx, g + batch + lo, nb, m, kB, kGemmTile, SL.symm_split, false, true, kGemmAkBk));   // X2 = strict(L)^T V
+    // X1 = L V, X2 = strict(L)^T V
+    SC_TRY(launch_gemm_f64(ctx, g + lo, {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBk, .split_k = SL.symm_split, .tri = true}));
+    SC_TRY(launch_gemm_f64(ctx, g + batch + lo, {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAkBk, .split_k = SL.symm_split, .tri = true}));
     if (SL.symm_split > 1)
       hipLaunchKernelGGL(k_sum_xslices, dim3((unsigned)((m + 255) / 256), 2 * kB, (unsigned)nb), dim3(256), 0, ps, sb_h, SL, r0);
   }
   if (rl == 2) {   // the trailing matrix has not seen the first panel's update yet: X1 -= [V1|W1] ([W1|V1]^T V2)
-    SC_TRY(launch_gemm_f64(ctx, g + 7 * batch + lo, nb, 2 * kB, kB, kGemmTile, kSmallSplit, false, false, kGemmAkBk));
+    SC_TRY(launch_gemm_f64(ctx, g + 7 * batch + lo, {.count = nb, .max_m = 2 * kB, .max_n = kB, .layout = kGemmAkBk, .split_k = kSmallSplit}));
     hipLaunchKernelGGL(k_sum_p2, dim3((unsigned)(2 * kB * kB / 256), (unsigned)nb), dim3(256), 0, ps, sb_h, SL);
-    SC_TRY(launch_gemm_f64(ctx, g + 8 * batch + lo, nb, m, kB, kGemmTile, 1, false, false, kGemmAmBk));
+    SC_TRY(launch_gemm_f64(ctx, g + 8 * batch + lo, {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBk}));
   }
   if (timed) R.t.symm.stop();
-  SC_TRY(launch_gemm_f64(ctx, g + 2 * batch + lo, nb, kB, 3 * kB, kGemmTile, kSmallSplit, false, false, kGemmAkBk));
+  SC_TRY(launch_gemm_f64(ctx, g + 2 * batch + lo, {.count = nb, .max_m = kB, .max_n = 3 * kB, .layout = kGemmAkBk, .split_k = kSmallSplit}));
   const size_t lds_small = sizeof(double) * 4 * kB * (kB + 1);
   hipLaunchKernelGGL(k_sb_small, dim3((unsigned)nb), dim3(1024), lds_small, ps, tri_h, TL, sb_h, SL, j0);
   if (nb == batch) {
-    SC_TRY(launch_gemm_f64(ctx, g + 3 * batch, 2 * batch, m, kB, kGemmTile, 1, false, false, kGemmAmBk));
+    SC_TRY(launch_gemm_f64(ctx, g + 3 * batch, {.count = 2 * batch, .max_m = m, .max_n = kB, .layout = kGemmAmBk}));
   } else {
-    SC_TRY(launch_gemm_f64(ctx, g + 3 * batch + lo, nb, m, kB, kGemmTile, 1, false, false, kGemmAmBk));
-    SC_TRY(launch_gemm_f64(ctx, g + 4 * batch + lo, nb, m, kB, kGemmTile, 1, false, false, kGemmAmBk));
+    SC_TRY(launch_gemm_f64(ctx, g + 3 * batch + lo, {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBk}));
+    SC_TRY(launch_gemm_f64(ctx, g + 4 * batch + lo, {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBk}));
   }
   if (timed) R.t.syr2k.start();
   if (rl == 1)
-    SC_TRY(launch_gemm_f64(ctx, g + 6 * batch + lo, nb, m, kB, kGemmTile, 1, false, false, kGemmAmBn));
+    SC_TRY(launch_gemm_f64(ctx, g + 6 * batch + lo, {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBn}));
   else
     // (records of one launch share (m, m, K); operands start at even rows of buffers with even leading dimension n)
-    if (launch_gemm3_uniform(ctx, g + 5 * batch + lo, nb, m, m, rl == 2 ? 4 * kB : 2 * kB, kGemmAmBn, /*lower=*/R.use_symm3 ? 2 : 1, 1.0, 1.0,
-                             /*aligned16=*/(n & 1) == 0 && (r0 & 1) == 0) != SC_OK) {
+    if (launch_gemm3_uniform(ctx, g + 5 * batch + lo,
+                             {.count = nb, .m = m, .n = m, .k = rl == 2 ? 4 * kB : 2 * kB, .layout = kGemmAmBn, .lower = R.use_symm3 ? 2 : 1,
+                              .alpha = 1.0, .beta = 1.0, .aligned16 = (n & 1) == 0 && (r0 & 1) == 0}) != SC_OK) {
       ++ctx->cnt_gemm3_declined;
-      SC_TRY(launch_gemm_f64(ctx, g + 5 * batch + lo, nb, m, m, kGemmTile, 1, false, false, kGemmAmBn, /*lower_grid=*/true));
+      SC_TRY(launch_gemm_f64(ctx, g + 5 * batch + lo, {.count = nb, .max_m = m, .max_n = m, .layout = kGemmAmBn, .lower_grid = true}));
     }
   if (timed) R.t.syr2k.stop();
   return SC_OK;

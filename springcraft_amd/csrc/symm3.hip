@@ -42,10 +42,6 @@
 //
 // Requires: m even and 16-byte aligned operands (the callers: n even, even offsets); a K range that is not a multiple of
 // 16 ends in one more per-lane-address step.
-#include <algorithm>
-#include <cstdlib>
-#include <vector>
-
 #include "gemm_f64.h"
 #include "twostage_policy.h"
 
@@ -495,95 +491,26 @@ __global__ __launch_bounds__(1024, 1) void k_symm3(S3Args P) {
 
 }  // namespace
 
-namespace {
-bool g_symm3_any_size = false;   // debugging (sc_dbg_symm3_host): take every launch that qualifies, whatever its size
-}
-
-// Whether launch_symm3 takes X = A V for `count` symmetric matrices of order m with `split` K slices (see the header).
-static bool symm3_takes(sc_ctx* ctx, int count, int m, int split, bool aligned16, bool any_size) {
-  const int env = sc_host::two_stage_env().symm3;   // SPRINGCRAFT_SYMM3, read with the rest of the two-stage environment
-  if (env == 0 || count <= 0 || !aligned16) return false;
-  if (m < 256 || (m & 1)) return false;
-  if (split < 1 || split > 16 || ((m + 15) / 16 + 8) / split < 4) return false;   // (every item has a few K steps)
-  if (ctx->num_cus < 256) return false;   // (the item order is built on 8 XCDs x 32 workgroups)
-  const long long items = (long long)((m + 127) / 128) * split * count;
-  if (env != 2 && !any_size && items < 256) return false;
-  return items <= 0x3fffffffLL;
+// (SPRINGCRAFT_SYMM3 is read with the rest of the two-stage environment)
+bool symm3_would_take(sc_ctx* ctx, int count, int m, int split, bool aligned16) {
+  return sc_host::symm3_takes(sc_host::two_stage_env().symm3, ctx->num_cus, count, m, split, aligned16, /*any_size=*/false);
 }
 
 // X = A V on k_symm3 (records: a = A(0, 0), sa_i = 1, sa_k = lda; b = V, sb_k = 1, sb_j = ldb; c = X, ldc; split_stride);
 // returns SC_OK when the launch went out, 1 when it is not one the kernel takes.
-bool symm3_would_take(sc_ctx* ctx, int count, int m, int split, bool aligned16) {
-  return symm3_takes(ctx, count, m, split, aligned16, g_symm3_any_size);
-}
-
 int launch_symm3(sc_ctx* ctx, const GemmDesc* d_desc, int count, int m, int split, bool aligned16, bool any_size) {
-  // (any_size: the caller has decided with symm3_would_take for another record count -- the parts of a split batch)
-  if (!symm3_takes(ctx, count, m, split, aligned16, any_size || g_symm3_any_size)) return 1;
+  if (!sc_host::symm3_takes(sc_host::two_stage_env().symm3, ctx->num_cus, count, m, split, aligned16, any_size)) return 1;
   if (!sc_raise_dyn_lds(reinterpret_cast<const void*>(&k_symm3), kS3Lds)) return 1;
   if (!ctx->d_zeros) return 1;   // (16 KB of zeros, allocated with the context; the kernel is handed its middle)
-  // (workgroups: one per CU, or 224 while the caller runs parts of the batch on several streams -- the other part's panel
-  // QR and small products then find CUs beside this launch, as for k_gemm3's trailing update; SPRINGCRAFT_SYMM3_WGS)
-  static const int env_wgs = [] { const char* e = getenv("SPRINGCRAFT_SYMM3_WGS"); return e ? std::max(8, std::min(256, atoi(e) / 8 * 8)) : 0; }();
-  const int nwg = env_wgs > 0 ? env_wgs : (ctx->gemm3_side_by_side ? 224 : 256);
+  const sc_host::GemmEnv& E = sc_host::gemm_env();
+  const int nwg = sc_host::symm3_workgroups(E, ctx->gemm3_side_by_side);
   S3Args A{d_desc, count, m, split, nwg, reinterpret_cast<const double*>(reinterpret_cast<const char*>(ctx->d_zeros) + 8192), {0}, 0};
-  const int ks_all = (m + 15) / 16 + 8;   // (a last step that reaches beyond the matrix takes its pieces from the zeros)
-  for (int q = 0; q <= split; ++q) A.gb[q] = (int)((long long)ks_all * q / split);
-  static const int env_hot = [] { const char* e = getenv("SPRINGCRAFT_SYMM3_DBG_HOT"); return e ? atoi(e) : 0; }();
-  A.hot = env_hot;
+  sc_host::symm3_slice_bounds(m, split, A.gb);
+  A.hot = E.symm3_hot;
   hipLaunchKernelGGL(k_symm3, dim3((unsigned)nwg), dim3(1024), kS3Lds, ctx->stream, A);
   if (hipGetLastError() != hipSuccess) return 1;
   ++ctx->cnt_symm3_launches;
   return SC_OK;
-}
-
-// ---- debug entry for the GPU unit tests (tests/test_gemm_gpu.py; not part of the public C ABI): x = sym(a) v for `count`
-// matrices on host data.  a: count x (m x m) column-major, only (row | 1) >= col is read; v, x: count x (m x 64).
-extern "C" int sc_dbg_symm3_host(sc_ctx* ctx, const double* a, const double* v, double* x, int count, int m, int split) {
-  if (!ctx || !a || !v || !x || count < 1 || m < 1 || split < 1) return SC_ERR_INVALID_ARG;
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t ea = (size_t)m * m, ev = (size_t)m * 64;
-  char* base = nullptr;
-  SC_HIP(ctx, hipMalloc((void**)&base, (ea + ev + ev * split) * count * 8 + sizeof(GemmDesc) * (size_t)count + 256));
-  double* da = (double*)base;
-  double* dv = da + ea * count;
-  double* dx = dv + ev * count;
-  GemmDesc* dd = (GemmDesc*)(dx + ev * split * count);
-  int rc = SC_OK;
-  auto fail = [&](hipError_t e) { if (e != hipSuccess && rc == SC_OK) rc = sc_set_error(ctx, SC_ERR_HIP, "%s", hipGetErrorString(e)); };
-  fail(hipMemcpy(da, a, ea * count * 8, hipMemcpyHostToDevice));
-  fail(hipMemcpy(dv, v, ev * count * 8, hipMemcpyHostToDevice));
-  fail(hipMemset(dx, 0xff, ev * split * count * 8));
-  std::vector<GemmDesc> h((size_t)count);
-  for (int z = 0; z < count; ++z) {
-    GemmDesc D{};
-    D.a = da + ea * z; D.b = dv + ev * z; D.c = dx + ev * split * z;
-    D.m = m; D.n = 64; D.k = m; D.ldc = m; D.alpha = 1.0; D.beta = 0.0;
-    D.sa_i = 1; D.sa_k = m; D.sb_k = 1; D.sb_j = m;
-    D.split_stride = (long long)ev;
-    h[(size_t)z] = D;
-  }
-  fail(hipMemcpy(dd, h.data(), sizeof(GemmDesc) * (size_t)count, hipMemcpyHostToDevice));
-  if (rc == SC_OK) {
-    g_symm3_any_size = true;
-    const int took = launch_symm3(ctx, dd, count, m, split, true, true);
-    g_symm3_any_size = false;
-    if (took != SC_OK) rc = sc_set_error(ctx, SC_ERR_INVALID_ARG, "k_symm3 does not take m %d split %d", m, split);
-    fail(hipStreamSynchronize(ctx->stream));
-  }
-  if (rc == SC_OK) {
-    // the slices summed on the host
-    std::vector<double> hx(ev * split * count);
-    fail(hipMemcpy(hx.data(), dx, hx.size() * 8, hipMemcpyDeviceToHost));
-    for (int z = 0; z < count; ++z)
-      for (size_t e = 0; e < ev; ++e) {
-        double s = 0.0;
-        for (int q = 0; q < split; ++q) s += hx[(size_t)z * ev * split + (size_t)q * ev + e];
-        x[(size_t)z * ev + e] = s;
-      }
-  }
-  (void)hipFree(base);
-  return rc;
 }
 
 extern "C" int sc_dbg_symm3_stamps(unsigned long long* out4) {
@@ -595,59 +522,4 @@ extern "C" int sc_dbg_symm3_stamps(unsigned long long* out4) {
   (void)out4;
   return 1;
 #endif
-}
-
-// ---- debug / tuning entry (not part of the public C ABI): `count` matrices of order m on freshly allocated buffers, X = A V
-// timed through k_symm3.  tools/symm3_bench.py
-extern "C" int sc_dbg_symm3_bench(sc_ctx* ctx, int count, int m, int split, int iters, double* ms_out) {
-  if (!ctx || count < 1 || iters < 1 || m < 256) return SC_ERR_INVALID_ARG;
-  SC_HIP(ctx, hipSetDevice(ctx->device));
-  const size_t ea = (size_t)m * m, ev = (size_t)m * 64;
-  char* base = nullptr;
-  SC_HIP(ctx, hipMalloc((void**)&base, (ea + ev + ev * split) * count * 8 + sizeof(GemmDesc) * (size_t)count + 256));
-  double* da = (double*)base;
-  double* dv = da + ea * count;
-  double* dx = dv + ev * count;
-  GemmDesc* dd = (GemmDesc*)(dx + ev * split * count);
-  int rc = SC_OK;
-  auto fail = [&](hipError_t e) { if (e != hipSuccess && rc == SC_OK) rc = sc_set_error(ctx, SC_ERR_HIP, "%s", hipGetErrorString(e)); };
-  {
-    // (random operands: the clock a launch holds depends on what the matrix pipes multiply -- zeros run ~10 % faster)
-    std::vector<double> hv(std::max(ea, ev));
-    unsigned long long sd = 88172645463325252ull;
-    for (auto& x : hv) { sd ^= sd << 13; sd ^= sd >> 7; sd ^= sd << 17; x = (double)((long long)(sd % 2001) - 1000) / 1000.0; }
-    for (int z = 0; z < count; ++z) {
-      fail(hipMemcpy(da + ea * z, hv.data(), ea * 8, hipMemcpyHostToDevice));
-      fail(hipMemcpy(dv + ev * z, hv.data(), ev * 8, hipMemcpyHostToDevice));
-    }
-  }
-  std::vector<GemmDesc> h((size_t)count);
-  for (int z = 0; z < count; ++z) {
-    GemmDesc D{};
-    D.a = da + ea * z; D.b = dv + ev * z; D.c = dx + ev * split * z;
-    D.m = m; D.n = 64; D.k = m; D.ldc = m; D.alpha = 1.0; D.beta = 0.0;
-    D.sa_i = 1; D.sa_k = m; D.sb_k = 1; D.sb_j = m;
-    D.split_stride = (long long)ev;
-    h[(size_t)z] = D;
-  }
-  fail(hipMemcpy(dd, h.data(), sizeof(GemmDesc) * (size_t)count, hipMemcpyHostToDevice));
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (rc == SC_OK) {
-    fail(hipEventCreate(&e0));
-    fail(hipEventCreate(&e1));
-    g_symm3_any_size = true;
-    for (int it = 0; it < 2 && rc == SC_OK; ++it) rc = launch_symm3(ctx, dd, count, m, split, true, true) == SC_OK ? SC_OK : SC_ERR_INVALID_ARG;
-    fail(hipEventRecord(e0, ctx->stream));
-    for (int it = 0; it < iters && rc == SC_OK; ++it) rc = launch_symm3(ctx, dd, count, m, split, true, true) == SC_OK ? SC_OK : SC_ERR_INVALID_ARG;
-    fail(hipEventRecord(e1, ctx->stream));
-    g_symm3_any_size = false;
-    fail(hipEventSynchronize(e1));
-    float ms = 0.f;
-    if (rc == SC_OK) fail(hipEventElapsedTime(&ms, e0, e1));
-    if (ms_out) *ms_out = ms / iters;
-  }
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  (void)hipFree(base);
-  return rc;
 }

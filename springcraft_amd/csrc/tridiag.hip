@@ -1345,8 +1345,7 @@ int tridiag_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, int bat
       }
       const int mt = n - pend;
       if (prof) SC_HIP(ctx, hipEventRecord(ev[2], st));
-      SC_TRY(launch_gemm_f64(ctx, d_syr2k_descs + (size_t)panel * batch, batch, mt, mt, kGemmTile, 1, false, false,
-                             kGemmAmBn));
+      SC_TRY(launch_gemm_f64(ctx, d_syr2k_descs + (size_t)panel * batch, {.count = batch, .max_m = mt, .max_n = mt, .layout = kGemmAmBn}));
       if (prof) {
         SC_HIP(ctx, hipEventRecord(ev[3], st));
         SC_HIP(ctx, hipEventSynchronize(ev[3]));

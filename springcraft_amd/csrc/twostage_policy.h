@@ -3,7 +3,7 @@
 // runtime answered (occupancy, granted attributes) are INPUTS.  No HIP, header-only, same rules as host_logic.h:
 // tests/host_sanitize/ compiles exactly this code with g++ -fsanitize=address,undefined.  sy2sb.hip, sb2st.hip, twostage.hip
 // and bt2.hip call each function once per solve (or per panel) and launch what it says; the measurements that justify a
-// rule stand beside it.
+// rule stand beside it.  The float64 GEMMs every stage launches have their policy and environment in gemm_policy.h.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -30,7 +30,8 @@ static inline size_t policy_align_up(size_t x, size_t a) { return (x + a - 1) / 
 // tasks of sweep s of an order-n band (one per 64 rows the bulge is chased through)
 SC_POLICY_HD inline int chase_len(int n, int s) { return (n - 1 - s + kBand - 1) / kBand; }
 
-// ---- every SPRINGCRAFT_* value the two-stage path reads, read once per process
+// ---- every SPRINGCRAFT_* value the two-stage path reads, read once per process; those of its GEMM
+// launches (SPRINGCRAFT_GEMM*, SPRINGCRAFT_SYMM3_WGS): GemmEnv, gemm_policy.h
 struct TwoStageEnv {
   int symm3 = 1;                    // SPRINGCRAFT_SYMM3: 0 never k_symm3, 2 every launch that qualifies
   int symm_split = 0;               // SPRINGCRAFT_SYMM_SPLIT: 1 .. 16 K slices of the SYMM (0: automatic)

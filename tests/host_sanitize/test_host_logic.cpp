@@ -1,4 +1,5 @@
-// Host-only logic of the C ABI (springcraft_amd/csrc/host_logic.h, scratch_arena.h) under AddressSanitizer + UBSan:
+// Host-only logic of the C ABI (springcraft_amd/csrc/host_logic.h, scratch_arena.h, twostage_policy.h, gemm_policy.h) under
+// AddressSanitizer + UBSan:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I include -I springcraft_amd/csrc \
 //       tests/host_sanitize/test_host_logic.cpp -o /tmp/test_host_logic && /tmp/test_host_logic
 // (built and run by tests/test_abi_and_host.py::test_host_logic_under_sanitizers).  Expected values restate
@@ -10,6 +11,7 @@
 #include <cstring>
 #include <vector>
 
+#include "gemm_policy.h"
 #include "host_logic.h"
 #include "scratch_arena.h"
 #include "twostage_policy.h"
@@ -411,6 +413,208 @@ int main() {
     if (!getenv("SPRINGCRAFT_STAGE1_STREAMS") && !getenv("SPRINGCRAFT_BULGE_PAIR")) {
       const TwoStageEnv R = read_two_stage_env();
       CHECK(R.stage1_streams == 0 && R.bulge_pair == -1 && R.bulge_pair_max == 6000 && R.bulge_burst >= 1);
+    }
+  }
+  // ---- the launch policy of the float64 GEMMs (csrc/gemm_policy.h) on a device of 256 CUs with the default environment
+  // (a default-constructed GemmEnv): every expected value written out by hand from the launchers' rules
+  {
+    using namespace sc_host;
+    const GemmEnv E;
+    auto same = [](GemmTile t, int bm, int bn) { return t.bm == bm && t.bn == bn; };
+    // block tile: 128 rows from 2 x 256 workgroups of 128 x 64 on, 128 columns from 3 x 256 workgroups of 128 x 128 on
+    CHECK(same(gemm2_tile(E, 256, {.count = 511, .max_m = 128, .max_n = 64, .layout = kGemmAmBk}), 64, 64));
+    CHECK(same(gemm2_tile(E, 256, {.count = 512, .max_m = 128, .max_n = 64, .layout = kGemmAmBk}), 128, 64));
+    CHECK(same(gemm2_tile(E, 256, {.count = 767, .max_m = 128, .max_n = 128, .layout = kGemmAmBk}), 128, 64));
+    CHECK(same(gemm2_tile(E, 256, {.count = 768, .max_m = 128, .max_n = 128, .layout = kGemmAmBk}), 128, 128));
+    CHECK(same(gemm2_tile(E, 256, {.count = 256, .max_m = 128, .max_n = 128, .layout = kGemmAmBn, .split_k = 3}), 128, 128));   // slices count
+    CHECK(same(gemm2_tile(E, 256, {.count = 4096, .max_m = 64, .max_n = 128, .layout = kGemmAmBk}), 64, 64));   // not wider than 64 rows
+    // a context that reports no CUs plans for 256; one of 128 CUs has half the thresholds
+    CHECK(same(gemm2_tile(E, 0, {.count = 511, .max_m = 128, .max_n = 64, .layout = kGemmAmBk}), 64, 64));
+    CHECK(same(gemm2_tile(E, 0, {.count = 512, .max_m = 128, .max_n = 64, .layout = kGemmAmBk}), 128, 64));
+    CHECK(same(gemm2_tile(E, 128, {.count = 256, .max_m = 128, .max_n = 64, .layout = kGemmAmBk}), 128, 64));
+    // never 128 x 128 with both operands k-contiguous, by size or forced
+    CHECK(same(gemm2_tile(E, 256, {.count = 768, .max_m = 128, .max_n = 128, .layout = kGemmAkBk}), 128, 64));
+    CHECK(same(gemm2_tile(E, 256, {.count = 1, .max_m = 64, .max_n = 64, .layout = kGemmAkBk, .pin_tile = 1}), 128, 64));
+    // precedence: the debug override, then SPRINGCRAFT_GEMM2_TILE, then pin_tile, then the size
+    GemmEnv E2;
+    E2.gemm2_tile = 2;
+    CHECK(same(gemm2_tile(E2, 256, {.count = 1, .max_m = 64, .max_n = 64, .layout = kGemmAmBk, .pin_tile = 1, .dbg = {.force_tile = 3}}), 64, 64));
+    CHECK(same(gemm2_tile(E2, 256, {.count = 1, .max_m = 64, .max_n = 64, .layout = kGemmAmBk, .pin_tile = 1}), 128, 64));
+    CHECK(same(gemm2_tile(E, 256, {.count = 1, .max_m = 64, .max_n = 64, .layout = kGemmAmBk, .pin_tile = 1}), 128, 128));
+    CHECK(same(gemm2_tile(E, 256, {.count = 768, .max_m = 128, .max_n = 128, .layout = kGemmAmBk, .pin_tile = 3}), 64, 64));
+    CHECK(same(gemm2_tile(E, 256, {.count = 1, .max_m = 64, .max_n = 64, .layout = kGemmAmBk}), 64, 64));
+    // gather launches: by size; only the debug override 2 / 3 forces them, the environment and pin_tile do not
+    CHECK(same(gemm2_gather_tile(256, {.count = 511, .max_m = 128, .max_n = 64, .layout = kGemmAmBk, .gather = true}), 64, 64));
+    CHECK(same(gemm2_gather_tile(256, {.count = 512, .max_m = 128, .max_n = 64, .layout = kGemmAmBk, .gather = true}), 128, 64));
+    CHECK(same(gemm2_gather_tile(0, {.count = 512, .max_m = 128, .max_n = 64, .layout = kGemmAmBk, .gather = true}), 128, 64));
+    CHECK(same(gemm2_gather_tile(256, {.count = 512, .max_m = 128, .max_n = 64, .layout = kGemmAmBk, .gather = true, .pin_tile = 3}), 128, 64));
+    CHECK(same(gemm2_gather_tile(256, {.count = 512, .max_m = 128, .max_n = 64, .layout = kGemmAmBk, .gather = true, .dbg = {.force_tile = 3}}), 64, 64));
+    CHECK(same(gemm2_gather_tile(256, {.count = 1, .max_m = 128, .max_n = 64, .layout = kGemmAmBk, .gather = true, .dbg = {.force_tile = 2}}), 128, 64));
+    CHECK(same(gemm2_gather_tile(256, {.count = 1, .max_m = 128, .max_n = 64, .layout = kGemmAmBk, .gather = true, .dbg = {.force_tile = 1}}), 64, 64));
+    // grid: (mode; tile grid the kernel decodes against; grid of the launch)
+    auto grid_is = [](GemmGrid g, int mode, int gx, int gy, int gz, unsigned x, unsigned y, unsigned z) {
+      return g.mode == mode && g.gx == gx && g.gy == gy && g.gz == gz && g.x == x && g.y == y && g.z == z;
+    };
+    // lower triangle of 5 row tiles: 5 * 6 / 2 = 15 tiles of 64 x 64 or 128 x 128, twice as many of 128 x 64; 7 records on y
+    CHECK(grid_is(gemm2_grid(E, 64, 64, 5, 5, 7, false, true), 1, 15, 7, 1, 15u, 7u, 1u));
+    CHECK(grid_is(gemm2_grid(E, 128, 128, 5, 5, 7, false, true), 1, 15, 7, 1, 15u, 7u, 1u));
+    CHECK(grid_is(gemm2_grid(E, 128, 64, 5, 10, 7, false, true), 1, 30, 7, 1, 30u, 7u, 1u));
+    CHECK(grid_is(gemm2_grid(E, 128, 64, 1, 2, 3, false, true), 1, 2, 3, 1, 2u, 3u, 1u));   // (2 tiles: a lower grid never pairs)
+    // triangular operands: one flat grid, longest tiles first, below 0x7fffffff blocks
+    CHECK(grid_is(gemm2_grid(E, 64, 64, 4, 3, 5, true, false), 2, 4, 3, 5, 60u, 1u, 1u));
+    CHECK(grid_is(gemm2_grid(E, 64, 64, 0x7ffffffeu, 1, 1, true, false), 2, 0x7ffffffe, 1, 1, 0x7ffffffeu, 1u, 1u));
+    CHECK(grid_is(gemm2_grid(E, 64, 64, 0x7fffffffu, 1, 1, true, false), 0, 0x7fffffff, 1, 1, 0x7fffffffu, 1u, 1u));
+    CHECK(grid_is(gemm2_grid(E, 64, 64, 65536, 32768, 1, true, false), 0, 65536, 32768, 1, 65536u, 32768u, 1u));   // 2^31 blocks
+    // 2 .. 4 row tiles: the records x column tiles rounded up to the 8 XCDs, times the row tiles
+    CHECK(grid_is(gemm2_grid(E, 128, 64, 1, 3, 5, false, false), 0, 1, 3, 5, 1u, 3u, 5u));
+    CHECK(grid_is(gemm2_grid(E, 128, 64, 2, 3, 5, false, false), 3, 2, 3, 5, 32u, 1u, 1u));
+    CHECK(grid_is(gemm2_grid(E, 128, 64, 4, 3, 5, false, false), 3, 4, 3, 5, 64u, 1u, 1u));
+    CHECK(grid_is(gemm2_grid(E, 128, 64, 4, 2, 8, false, false), 3, 4, 2, 8, 64u, 1u, 1u));   // 16 is a multiple of 8 already
+    CHECK(grid_is(gemm2_grid(E, 128, 64, 5, 3, 5, false, false), 0, 5, 3, 5, 5u, 3u, 5u));
+    {
+      GemmEnv En;
+      En.no_pair = true;
+      CHECK(grid_is(gemm2_grid(En, 128, 64, 2, 3, 5, false, false), 0, 2, 3, 5, 2u, 3u, 5u));
+      CHECK(grid_is(gemm2_grid(En, 64, 64, 4, 3, 5, true, false), 2, 4, 3, 5, 60u, 1u, 1u));
+      En = GemmEnv{};
+      En.no_balance = true;
+      CHECK(grid_is(gemm2_grid(En, 64, 64, 4, 3, 5, true, false), 0, 4, 3, 5, 4u, 3u, 5u));   // (a tri launch never pairs)
+      CHECK(grid_is(gemm2_grid(En, 128, 64, 2, 3, 5, false, false), 3, 2, 3, 5, 32u, 1u, 1u));
+    }
+    // lower_grid: square launches of layout kGemmAmBn without K slices, masks or gathers
+    CHECK(gemm2_lower_grid_allowed(E, {.count = 4, .max_m = 256, .max_n = 256, .layout = kGemmAmBn, .lower_grid = true}));
+    CHECK(gemm2_lower_grid_allowed(E, {.count = 4, .max_m = 256, .max_n = 256, .layout = kGemmAmBn, .split_k = 0, .lower_grid = true}));
+    CHECK(!gemm2_lower_grid_allowed(E, {.count = 4, .max_m = 256, .max_n = 256, .layout = kGemmAmBn}));
+    CHECK(!gemm2_lower_grid_allowed(E, {.count = 4, .max_m = 256, .max_n = 256, .layout = kGemmAmBn, .split_k = 2, .lower_grid = true}));
+    CHECK(!gemm2_lower_grid_allowed(E, {.count = 4, .max_m = 256, .max_n = 255, .layout = kGemmAmBn, .lower_grid = true}));
+    CHECK(!gemm2_lower_grid_allowed(E, {.count = 4, .max_m = 256, .max_n = 256, .layout = kGemmAmBn, .tri = true, .lower_grid = true}));
+    CHECK(!gemm2_lower_grid_allowed(E, {.count = 4, .max_m = 256, .max_n = 256, .layout = kGemmAmBn, .gather = true, .lower_grid = true}));
+    CHECK(!gemm2_lower_grid_allowed(E, {.count = 4, .max_m = 256, .max_n = 256, .layout = kGemmAmBk, .lower_grid = true}));
+    {
+      GemmEnv En;
+      En.no_lower_grid = true;
+      CHECK(!gemm2_lower_grid_allowed(En, {.count = 4, .max_m = 256, .max_n = 256, .layout = kGemmAmBn, .lower_grid = true}));
+    }
+    // chunks of at most 65535 records x slices
+    CHECK(gemm2_records_per_launch(65535, 1) == 65535 && gemm2_records_per_launch(65536, 1) == 65535);
+    CHECK(gemm2_records_per_launch(21845, 3) == 21845 && gemm2_records_per_launch(21846, 3) == 21845);   // 65535, 65538
+    CHECK(gemm2_records_per_launch(32768, 2) == 32767 && gemm2_records_per_launch(1 << 24, 65535) == 1);
+
+    // ---- k_gemm3: 1024 records of one 128 x 64 tile each are the least it takes
+    const GemmDevice D{256, 1, false}, Dside{256, 1, true};
+    const Gemm3Launch base{.count = 1024, .m = 128, .n = 64, .k = 128, .layout = kGemmAmBk, .lower = 0, .alpha = 1.0, .beta = 0.0, .aligned16 = true};
+    auto with = [&](auto change) { Gemm3Launch l = base; change(l); return l; };
+    CHECK(gemm3_takes(E, D, base) && gemm3_takes(E, GemmDevice{256, -1, false}, base));
+    CHECK(gemm3_takes(E, D, with([](Gemm3Launch& l) { l.layout = kGemmAkBk; })) && gemm3_takes(E, D, with([](Gemm3Launch& l) { l.beta = 1.0; })));
+    CHECK(!gemm3_takes(E, D, with([](Gemm3Launch& l) { l.k = 112; })));
+    CHECK(!gemm3_takes(E, D, with([](Gemm3Launch& l) { l.k = 136; })) && gemm3_takes(E, D, with([](Gemm3Launch& l) { l.k = 144; })));
+    CHECK(!gemm3_takes(E, D, with([](Gemm3Launch& l) { l.m = 129; })));
+    CHECK(!gemm3_takes(E, D, with([](Gemm3Launch& l) { l.n = 65; l.layout = kGemmAmBn; })));
+    CHECK(gemm3_takes(E, D, with([](Gemm3Launch& l) { l.n = 65; })) && gemm3_takes(E, D, with([](Gemm3Launch& l) { l.layout = kGemmAmBn; })));
+    CHECK(!gemm3_takes(E, D, with([](Gemm3Launch& l) { l.lower = 1; l.count = 7; })));   // 128 x 64 is not square
+    {
+      // ... and nothing but "lower needs m == n" declines it: 1024 records of one tile, lower-only launches always taken
+      // (SPRINGCRAFT_GEMM3_LOWER = 1), or as a debug entry launches it; the square 128 x 128 (2 tiles each) is taken
+      GemmEnv E_l1;
+      E_l1.gemm3_lower = 1;
+      CHECK(!gemm3_takes(E_l1, D, with([](Gemm3Launch& l) { l.lower = 1; })));
+      CHECK(!gemm3_takes(E, D, with([](Gemm3Launch& l) { l.lower = 2; l.dbg.any_size = true; })));
+      CHECK(gemm3_takes(E_l1, D, with([](Gemm3Launch& l) { l.lower = 1; l.n = 128; })));
+      CHECK(gemm3_takes(E, D, with([](Gemm3Launch& l) { l.lower = 2; l.n = 128; l.dbg.any_size = true; })));
+    }
+    // no rows or no columns: declined before the tile count (0 tiles would pass a debug entry's any_size)
+    CHECK(!gemm3_takes(E, D, with([](Gemm3Launch& l) { l.m = 0; l.dbg.any_size = true; })));
+    CHECK(!gemm3_takes(E, D, with([](Gemm3Launch& l) { l.m = -2; l.dbg.any_size = true; })));
+    CHECK(!gemm3_takes(E, D, with([](Gemm3Launch& l) { l.n = 0; l.dbg.any_size = true; })));
+    CHECK(gemm3_takes(E, D, with([](Gemm3Launch& l) { l.m = 2; l.n = 1; l.count = 1; l.dbg.any_size = true; })));
+    CHECK(!gemm3_takes(E, D, with([](Gemm3Launch& l) { l.alpha = -1.0; })));
+    CHECK(!gemm3_takes(E, D, with([](Gemm3Launch& l) { l.beta = 0.5; })));
+    CHECK(!gemm3_takes(E, D, with([](Gemm3Launch& l) { l.aligned16 = false; })));
+    CHECK(!gemm3_takes(E, D, with([](Gemm3Launch& l) { l.layout = 3; })) && !gemm3_takes(E, D, with([](Gemm3Launch& l) { l.count = 0; })));
+    CHECK(!gemm3_takes(E, GemmDevice{255, 1, false}, base));
+    CHECK(!gemm3_takes(E, GemmDevice{256, 0, false}, base));
+    // 1023 tiles: only for SPRINGCRAFT_GEMM3 = 2 and the debug entries; SPRINGCRAFT_GEMM3 = 0 takes nothing
+    const Gemm3Launch small = with([](Gemm3Launch& l) { l.count = 1023; });
+    GemmEnv E_all, E_off;
+    E_all.gemm3 = 2;
+    E_off.gemm3 = 0;
+    CHECK(!gemm3_takes(E, D, small) && gemm3_takes(E_all, D, small) && !gemm3_takes(E_off, D, base));
+    CHECK(gemm3_takes(E, D, with([](Gemm3Launch& l) { l.count = 1023; l.dbg.any_size = true; })));
+    // lower-only, m = n = 2048: 16 x 32 tiles of which 16 * 15 lie above the diagonal: 272 per record
+    GemmEnv E_low0, E_low1;
+    E_low0.gemm3_lower = 0;
+    E_low1.gemm3_lower = 1;
+    auto lower = [&](int count) {
+      return Gemm3Launch{.count = count, .m = 2048, .n = 2048, .k = 128, .layout = kGemmAmBn, .lower = 1, .alpha = 1.0, .beta = 1.0, .aligned16 = true};
+    };
+    CHECK(gemm3_takes(E, D, lower(7)) && !gemm3_takes(E, D, lower(8)) && gemm3_takes(E, Dside, lower(7)) && gemm3_takes(E, Dside, lower(8)));
+    CHECK(!gemm3_takes(E_low0, D, lower(7)) && !gemm3_takes(E_low0, Dside, lower(8)));
+    CHECK(gemm3_takes(E_low1, D, lower(7)) && gemm3_takes(E_low1, D, lower(8)));
+    CHECK(!gemm3_takes(E, D, lower(3)) && gemm3_takes(E, D, lower(4)));   // 816, 1088 tiles
+    {
+      Gemm3Launch l = lower(8);
+      l.dbg.any_size = true;
+      CHECK(gemm3_takes(E_low0, D, l));
+      // an odd number of column tiles: m = n = 192 has 2 + 3 = 5 tiles; m = n = 256 has 2 + 4 = 6
+      l = lower(204); l.m = l.n = 192;
+      CHECK(!gemm3_takes(E_low1, D, l));   // 1020
+      l.count = 205;
+      CHECK(gemm3_takes(E_low1, D, l));    // 1025
+      l = lower(170); l.m = l.n = 256; l.lower = 2;
+      CHECK(!gemm3_takes(E_low1, D, l));   // 1020
+      l.count = 171;
+      CHECK(gemm3_takes(E_low1, D, l));    // 1026
+    }
+    // workgroups and tile order
+    auto wgs_is = [](Gemm3Grid g, int nwg, int order) { return g.nwg == nwg && g.order == order; };
+    CHECK(wgs_is(gemm3_workgroups(E, D, base), 256, 1) && wgs_is(gemm3_workgroups(E, Dside, base), 256, 1));
+    CHECK(wgs_is(gemm3_workgroups(E, D, lower(8)), 256, 1) && wgs_is(gemm3_workgroups(E, Dside, lower(8)), 224, 1));
+    CHECK(gemm_wgs_clamp(100) == 96 && gemm_wgs_clamp(4) == 8 && gemm_wgs_clamp(999) == 256 && gemm_wgs_clamp(224) == 224);
+    {
+      GemmEnv Ew;
+      Ew.gemm3_lower_wgs = gemm_wgs_clamp(100);
+      Ew.gemm3_order = 0;
+      CHECK(wgs_is(gemm3_workgroups(Ew, Dside, lower(8)), 96, 0) && wgs_is(gemm3_workgroups(Ew, D, base), 256, 0));
+      CHECK(wgs_is(gemm3_workgroups(Ew, D, with([](Gemm3Launch& l) { l.dbg.order = 1; })), 256, 1));
+      CHECK(wgs_is(gemm3_workgroups(E, D, with([](Gemm3Launch& l) { l.dbg.order = 0; })), 256, 0));
+    }
+
+    // ---- k_symm3 (SPRINGCRAFT_SYMM3's value, CUs, count, m, split, aligned16, any_size)
+    CHECK(!symm3_takes(1, 256, 128, 254, 1, true, false) && !symm3_takes(1, 256, 128, 255, 1, true, false));
+    CHECK(symm3_takes(1, 256, 128, 256, 1, true, false) && !symm3_takes(1, 256, 128, 257, 1, true, false));   // 2 x 128 = 256 items
+    CHECK(!symm3_takes(1, 256, 128, 256, 0, true, false) && !symm3_takes(1, 256, 128, 256, 17, true, false));
+    // m = 256: 16 + 8 = 24 K steps: six slices of 4, seven of 3
+    CHECK(symm3_takes(1, 256, 128, 256, 6, true, false) && !symm3_takes(1, 256, 128, 256, 7, true, false));
+    CHECK(symm3_takes(1, 256, 8, 3840, 16, true, false));   // 248 K steps: 16 slices of 15; 30 x 16 x 8 items
+    // m = 640: 5 tile rows x 51 matrices = 255 items
+    CHECK(!symm3_takes(1, 256, 51, 640, 1, true, false) && symm3_takes(1, 256, 52, 640, 1, true, false));
+    CHECK(symm3_takes(1, 256, 51, 640, 1, true, /*any_size=*/true) && symm3_takes(2, 256, 51, 640, 1, true, false));
+    CHECK(!symm3_takes(0, 256, 128, 256, 1, true, true) && !symm3_takes(1, 255, 128, 256, 1, true, true));
+    CHECK(!symm3_takes(1, 256, 128, 256, 1, /*aligned16=*/false, true) && !symm3_takes(1, 256, 0, 256, 1, true, true));
+    CHECK(symm3_workgroups(E, false) == 256 && symm3_workgroups(E, true) == 224);
+    {
+      GemmEnv Ew;
+      Ew.symm3_wgs = gemm_wgs_clamp(250);
+      CHECK(symm3_workgroups(Ew, false) == 248 && symm3_workgroups(Ew, true) == 248);
+    }
+    {
+      // m = 2000: 125 + 8 = 133 K steps
+      int gb[17];
+      for (int& g : gb) g = -1;
+      symm3_slice_bounds(2000, 5, gb);
+      CHECK(gb[0] == 0 && gb[1] == 26 && gb[2] == 53 && gb[3] == 79 && gb[4] == 106 && gb[5] == 133 && gb[6] == -1);
+      for (int q = 0; q < 5; ++q) CHECK(gb[q] < gb[q + 1]);
+      for (int& g : gb) g = -1;
+      symm3_slice_bounds(2000, 1, gb);
+      CHECK(gb[0] == 0 && gb[1] == 133 && gb[2] == -1);
+      symm3_slice_bounds(256, 16, gb);   // the most slices: all 17 bounds
+      CHECK(gb[0] == 0 && gb[1] == 1 && gb[2] == 3 && gb[15] == 22 && gb[16] == 24);
+    }
+    // the environment is read in one place; unset, it is the default-constructed struct
+    if (!getenv("SPRINGCRAFT_GEMM3") && !getenv("SPRINGCRAFT_GEMM3_LOWER_WGS") && !getenv("SPRINGCRAFT_GEMM3_W") &&
+        !getenv("SPRINGCRAFT_GEMM2_TILE") && !getenv("SPRINGCRAFT_SYMM3_WGS")) {
+      const GemmEnv R = read_gemm_env();
+      CHECK(R.gemm3 == 1 && R.gemm3_lower_wgs == 0 && R.gemm3_w && R.gemm2_tile == 0 && R.symm3_wgs == 0);
     }
   }
   std::puts("host logic ok");
