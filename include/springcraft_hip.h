@@ -790,6 +790,48 @@ int sc_dev_pairs_cg_step_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms
                              double* d_x, double* d_r, double* d_p, double* d_q, int64_t ld, int64_t q, double* d_state,
                              void* d_work, size_t work_bytes, int64_t iterations);
 
+/* ---- conformational ensembles: superposition, mean frame and principal components on the device ------------------------
+ * No reference counterpart (its callers superimpose with biotite; Bio3D: fit.xyz / pca.xyz, ProDy: superpose / iterpose /
+ * PCA).  An ensemble is d_frames (M, N, 3), contiguous float64 in device memory: M frames of the same N atoms.  Device
+ * pointers, enqueue only on the context's stream, no atomics, every sum in a fixed order: two calls agree bit for bit.
+ * Conditions the device finds (a non-finite matrix in the eigensolve) surface at the next sc_ctx_synchronize.
+ *
+ * sc_superpose_form: which kernel form sc_dev_superpose_f64 takes for frames of n_atoms atoms: 0, one workgroup keeps the
+ * frame in LDS (one read and one write of the frame; up to 2560 atoms), or 1, the streaming form (three reads, one write).
+ * SPRINGCRAFT_SUPERPOSE_FORM = stream forces 1; = lds and = auto leave the size rule.  Read at every call. */
+int sc_superpose_form(int64_t n_atoms);
+/* Least-squares superposition of every frame on d_target (N, 3) with the atom weights d_weights (N), non-negative with a
+ * positive sum, or NULL for 1: the proper rotation R (det = +1, Horn's quaternion method; a mirror image gets the best
+ * rotation, never a reflection; a degenerate frame -- one or two atoms, collinear, planar -- gets one of its minimisers) and
+ * the translation t that minimise sum_a w_a |R x_a + t - target_a|^2.
+ *     d_out   (M, N, 3)  R x + t, zero-weight atoms included; may be d_frames (in place)
+ *     d_rot   (M, 3, 3)  row-major R, or NULL
+ *     d_trans (M, 3)     t, or NULL
+ *     d_rmsd  (M)        sqrt(sum_a w_a |d_out_a - target_a|^2 / sum w), summed from the residuals, or NULL
+ * A frame's bits depend on that frame, the target and the weights alone: not on M, the frame's position or its neighbours.
+ * A non-finite coordinate makes that frame's outputs NaN and no other frame's.  Weights that sum to 0 give NaN.
+ * SC_ERR_INVALID_ARG: non-positive sizes, more than 2^31 - 1 frames or coordinates per frame, a NULL required pointer. */
+int sc_dev_superpose_f64(sc_ctx* ctx, const double* d_frames, int64_t n_frames, int64_t n_atoms, const double* d_target,
+                         const double* d_weights, double* d_out, double* d_rot, double* d_trans, double* d_rmsd);
+/* d_mean (N, 3) = sum_f p_f x_f / sum p and, unless NULL, d_msd (N) = sum_f p_f |x_f[a] - mean[a]|^2 / sum p, the
+ * per-atom mean-square deviation from the mean frame, with the frame weights d_frame_weights (M) or NULL for 1.  Two-level
+ * sums: chunks of 64 consecutive frames, then the chunks.  At most 4194240 frames.  SC_ERR_INVALID_ARG as above. */
+int sc_dev_ensemble_mean_f64(sc_ctx* ctx, const double* d_frames, int64_t n_frames, int64_t n_atoms,
+                             const double* d_frame_weights, double* d_mean, double* d_msd);
+/* The n_modes largest principal components of the (fitted) frames about d_mean (N, 3): with Xc (M, 3 N) the frames minus
+ * the mean, atom a's columns times d_sqrt_mass[a] (N; NULL: 1), the eigenpairs of the covariance Xc^T Xc / (M - 1) -- from
+ * the Gram matrix Xc Xc^T / (M - 1) of order M while M - 1 < 3 N, else from the covariance of order 3 N.
+ *     d_var   (n_modes)        the variances, descending
+ *     d_w     (n_modes)        1 / variance, ascending: the eigenvalues of the quasi-harmonic Hessian in units of kT
+ *     d_v     (n_modes, 3 N)   the components, unit rows in the order of d_var (their signs are not fixed)
+ *     d_total (1)              the trace of the covariance, sum Xc^2 / (M - 1)
+ * A rank-deficient ensemble gives variances at rounding level (also negative ones) and rows without meaning: the caller
+ * compares d_var with its largest entry.  1 <= n_modes <= min(M - 1, 3 N), n_modes <= 65535, the order of the eigenproblem
+ * at most 46000.  SC_ERR_INVALID_ARG otherwise, and for what sc_dev_superpose_f64 refuses. */
+int sc_dev_ensemble_pca_f64(sc_ctx* ctx, const double* d_frames, int64_t n_frames, int64_t n_atoms, const double* d_mean,
+                            const double* d_sqrt_mass, int64_t n_modes, double* d_w, double* d_var, double* d_v,
+                            double* d_total);
+
 #ifdef __cplusplus
 }
 #endif

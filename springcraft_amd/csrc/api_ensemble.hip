@@ -1,0 +1,72 @@
+// C ABI (include/springcraft_hip.h), device-pointer entries of the conformational ensembles: superposition and the mean frame
+// (superpose.hip), ensemble PCA (ensemble_pca.hip).  Argument checks, the scratch carve, the launcher call.
+#include "api_internal.h"
+#include "ensemble_internal.h"
+
+namespace {
+
+int ensemble_sizes_check(sc_ctx* ctx, const char* what, int64_t n_frames, int64_t n_atoms) {
+  if (n_frames <= 0 || n_atoms <= 0)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "%s: the numbers of frames and atoms must be positive", what);
+  if (n_frames > 0x7fffffffLL || n_atoms > 0x7fffffffLL / 3)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "%s: at most 2^31 - 1 frames and coordinates per frame", what);
+  return SC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sc_superpose_form(int64_t n_atoms) {
+  return sc_host::superpose_form(sc_host::read_superpose_env(), n_atoms);
+}
+
+int sc_dev_superpose_f64(sc_ctx* ctx, const double* d_frames, int64_t n_frames, int64_t n_atoms, const double* d_target,
+                         const double* d_weights, double* d_out, double* d_rot, double* d_trans, double* d_rmsd) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  SC_TRY(ensemble_sizes_check(ctx, "superpose", n_frames, n_atoms));
+  if (!d_frames || !d_target || !d_out)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "superpose: the frames, the target and the output are required");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  sc_host::SuperposeBufs B{};
+  SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) { B = sc_host::superpose_layout(a); }));
+  return launch_superpose(ctx, sc_superpose_form(n_atoms), d_frames, n_frames, n_atoms, d_target, d_weights,
+                          B.target_centre, d_out, d_rot, d_trans, d_rmsd);
+}
+
+int sc_dev_ensemble_mean_f64(sc_ctx* ctx, const double* d_frames, int64_t n_frames, int64_t n_atoms,
+                             const double* d_frame_weights, double* d_mean, double* d_msd) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  SC_TRY(ensemble_sizes_check(ctx, "ensemble mean", n_frames, n_atoms));
+  if (sc_host::mean_chunks(n_frames) > 65535)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "ensemble mean: at most %d frames", 65535 * sc_host::kMeanChunk);
+  if (!d_frames || !d_mean)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "ensemble mean: the frames and the mean are required");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  sc_host::MeanBufs B{};
+  SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) { B = sc_host::mean_layout(a, n_frames, n_atoms); }));
+  return launch_ensemble_mean(ctx, d_frames, n_frames, n_atoms, d_frame_weights, B.partial, d_mean, d_msd);
+}
+
+int sc_dev_ensemble_pca_f64(sc_ctx* ctx, const double* d_frames, int64_t n_frames, int64_t n_atoms, const double* d_mean,
+                            const double* d_sqrt_mass, int64_t n_modes, double* d_w, double* d_var, double* d_v,
+                            double* d_total) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  SC_TRY(ensemble_sizes_check(ctx, "ensemble pca", n_frames, n_atoms));
+  const int64_t most = std::min<int64_t>(n_frames - 1, 3 * n_atoms);
+  if (n_modes < 1 || n_modes > most)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "ensemble pca: %lld components asked for, %lld frames of %lld atoms have at most %lld",
+                        (long long)n_modes, (long long)n_frames, (long long)n_atoms, (long long)most);
+  if (n_modes > 65535) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "ensemble pca: at most 65535 components");
+  if (!d_frames || !d_mean || !d_w || !d_var || !d_v || !d_total)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "ensemble pca: a required pointer is NULL");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const sc_host::PcaPlan P = sc_host::pca_plan(n_frames, n_atoms, n_modes, ctx->num_cus);
+  sc_host::PcaBufs B{};
+  SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) {
+    B = sc_host::pca_layout(a, P, n_frames, n_atoms, n_modes, ensemble_pca_desc_bytes());
+  }));
+  return launch_ensemble_pca(ctx, P, B, d_frames, n_frames, n_atoms, d_mean, d_sqrt_mass, n_modes, d_w, d_var, d_v, d_total);
+}
+
+}  // extern "C"

@@ -415,6 +415,18 @@ int launch_rtb_hessian(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, cons
 int launch_rtb_expand(sc_ctx* ctx, const double* d_u, int64_t nvec, int64_t nr, const double* d_P, const int32_t* d_boa,
                       const int64_t* d_offset, int64_t n_atoms, double* d_v);
 
+// ---- conformational ensembles (superpose.hip, ensemble_pca.hip; the host decisions: ensemble_policy.h) ---------------------
+// form: sc_host::kSuperposeFormLds (n_atoms <= kSuperposeLdsMaxAtoms) / kSuperposeFormStream; d_tc: 4 doubles of scratch (the
+// target's centroid and the sum of the weights); d_out (M, N, 3) may be d_frames; d_rot (M, 3, 3), d_trans (M, 3) and d_rmsd
+// (M) may be null.  Enqueue only.
+int launch_superpose(sc_ctx* ctx, int form, const double* d_frames, int64_t n_frames, int64_t n_atoms,
+                     const double* d_target, const double* d_weights, double* d_tc, double* d_out, double* d_rot,
+                     double* d_trans, double* d_rmsd);
+// d_mean (N, 3) and, unless null, d_msd (N) over the frames with the frame weights d_fw (M) or null; d_partial:
+// mean_chunks(M) x 3 N doubles of scratch.  Enqueue only.
+int launch_ensemble_mean(sc_ctx* ctx, const double* d_frames, int64_t n_frames, int64_t n_atoms, const double* d_fw,
+                         double* d_partial, double* d_mean, double* d_msd);
+
 // ---- the network as an operator on the pair list (pair_operator.hip) ------------------------------------------------
 // Y = (T H T) x and E (per-atom deformation energies) for the q rows of d_x, H as launch_hessian_from_pairs /
 // launch_kirchhoff_from_pairs fill it for symmetric constants: d_row_start (N + 1), atom i's pairs are the rows
