@@ -405,6 +405,12 @@ int sc_modes_prs(sc_modes* modes, double rcond, int norm, double* out);
  * twice counts twice.  ANM only; a mode index outside 0..n-1 (negative ones count from the end): SC_ERR_INDEX; k = 0 gives
  * zeros (NaN under norm).  Computed by sc_dev_prs_f64's kernel with a batch of one: no (n, n) covariance is formed. */
 int sc_modes_prs_subset(sc_modes* modes, const int64_t* mode_idx, int64_t k, int norm, double* out);
+/* Generalized correlation of every atom pair from the linear mutual information (Lange & Grubmueller 2006; no reference
+ * counterpart, Bio3D: lmi) over the k listed modes, or with a NULL list (its k must be 0) over every mode with |w| > rcond
+ * max|w|, the covariance rule of sc_modes_prs.  out (n / 3, n / 3): r in [0, 1], or with information != 0 the mutual
+ * information in nats; see sc_dev_lmi_f64, whose kernels compute it with a batch of one.  ANM only; a mode index outside
+ * 0..n-1 (negative ones count from the end): SC_ERR_INDEX; fewer than three modes give NaN everywhere. */
+int sc_modes_lmi(sc_modes* modes, const int64_t* mode_idx, int64_t k, double rcond, int information, double* out);
 /* How the modes of model a compare with those of model b: no reference counterpart (Bio3D: rmsip / covsoverlap; ProDy:
  * calcSubspaceOverlap / calcCovOverlap / calcOverlap of two mode sets).  Host pointers.  The two objects must belong to one
  * context and have the same dim and order (SC_ERR_INVALID_ARG otherwise: structures of different size have no common
@@ -523,6 +529,30 @@ int sc_dev_modes_distfluct_f64(sc_ctx* ctx, const double* d_w, const double* d_v
 int sc_dev_prs_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
                    const sc_mode_selection* sel, const int64_t* d_counts, const double* d_atom_scale, int norm,
                    double* d_out);
+/* Generalized correlation of atom pairs from the linear mutual information (Lange & Grubmueller 2006; no reference
+ * counterpart, Bio3D: lmi, correlationplus) for a batch and over the selected rows.  ANM only: m = 3 N (m % 3 != 0:
+ * SC_ERR_INVALID_ARG), d_out (batch, N, N),
+ *
+ *   C_ac  = sum_r s[b, r] v_r[a] v_r[c]^T,   v_r[a] = V[b, r, 3 a .. 3 a + 2]          (3 x 3)
+ *   P_a C_aa P_a^T = L_a L_a^T (Cholesky with diagonal pivoting),  W_a = L_a^-1 P_a,  M = W_a C_ac W_c^T
+ *   delta = det(I - M M^T) clamped to [0, 1]
+ *   r[b, a, c] = sqrt(1 - delta^(1/3))          information != 0: I[b, a, c] = -1/2 ln(delta), in nats
+ *
+ * Both are invariant under any invertible linear map per atom, so there is no temperature and no per-atom scale: a
+ * mass-weighted solve gives the Cartesian result.  [a, a] is 1.0 / +inf by definition.  A block C_aa with a Cholesky pivot
+ * that is not finite or is <= 2^-40 times its own diagonal entry (fewer than three selected rows, an atom at rest in the
+ * selection) cannot be whitened: row and column a are NaN, [a, a] included; so an empty selection gives NaN.  With exactly
+ * three rows delta is 0 up to rounding: r = 1 up to rounding and I is large or +inf, never NaN.
+ * The diagonal blocks are the tensors of sc_dev_modes_aniso_f64's kernels, summed in chunks of 128 listed rows and whitened
+ * in the workspace (nine doubles per atom); then one kernel on the float64 matrix units with the data flow of
+ * sc_dev_prs_f64's: a block C_ac is accumulated in registers and reduced to its value there, no covariance entry is
+ * written to memory.  Every unordered pair is computed once, so the result equals its transpose bit for bit.  No atomics,
+ * no partial sums across workgroups, and the tensors' chunks are cut at fixed rows: a structure's result does not depend
+ * on the batch size, its position or its neighbours, bit for bit, and rows without weight behind its last weighted row
+ * (the padding of a window, the pad rows of a plan's slot) do not change it either.  A row without weight is not read, nor
+ * is a listed row outside 0..nvec-1, which turns the structure's result into NaN, as NaN eigenvalues do.  Enqueue only. */
+int sc_dev_lmi_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                   const sc_mode_selection* sel, const int64_t* d_counts, int information, double* d_out);
 /* How the modes of structure a compare with those of structure b, for every pair of two uniform batches of one m: no
  * reference counterpart (Bio3D: rmsip / covsoverlap; ProDy: calcSubspaceOverlap / calcCovOverlap); replaces copying d_v
  * to the host.  Two operand sets (d_w, d_v, sel, d_counts, nvec, batch) as above, each with its own selection; GNM and ANM.
@@ -589,7 +619,9 @@ int sc_dev_mode_combine_f64(sc_ctx* ctx, const double* d_v, int64_t m, int64_t n
  * collectivities (always 0: sc_dev_modes_overlap_f64 holds no workspace), 4 = distance fluctuations (the weights only; dim
  * 3 and m % 3 == 0, else 0), 5 = response (weights, the coefficients of four forces and the partial sums of a slab), 6 =
  * combine (the partial sums of a slab), 7 = perturbation-response scanning (the weights and one diagonal per structure
- * of a slab of at most 32768; dim 3 and m % 3 == 0, else 0); budget_bytes as above. */
+ * of a slab of at most 32768; dim 3 and m % 3 == 0, else 0), 8 = generalized correlation (the weights, the tensors'
+ * partial sums of a slab in chunks of 128 rows, and six plus nine doubles per atom of the batch: tensors and whitening
+ * factors; dim 3 and m % 3 == 0, else 0); budget_bytes as above. */
 int64_t sc_dev_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t n_sel, int what,
                                      int64_t budget_bytes);
 
@@ -652,6 +684,13 @@ int sc_batch_plan_modes_distfluct_f64(sc_batch_plan* plan, const double* d_w, co
 int sc_batch_plan_prs_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
                           const sc_mode_selection* sel, const int64_t* d_counts, const double* d_atom_scale, int norm,
                           double* d_out);
+/* generalized correlation (a plan of dim 1: SC_ERR_INVALID_ARG), as sc_dev_lmi_f64: N the structure's own n_atoms, d_out
+ * (sum n_atoms^2,) packed like the dcc.  Pad rows never carry a weight, pad columns are never read.  A structure's bits
+ * depend on its own size and the selection, not on its neighbours, its position or the slot order (the tensors' chunks
+ * are cut at fixed rows, where sc_batch_plan_modes_aniso_f64 cuts them by the slot's row count): they are those of its
+ * uniform solve by sc_dev_lmi_f64. */
+int sc_batch_plan_lmi_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
+                          const sc_mode_selection* sel, const int64_t* d_counts, int information, double* d_out);
 /* sc_dev_mode_response_f64 for the plan's padded slots (GNM and ANM plans; sel->reserved holds first_row as for the
  * sc_batch_plan_modes_* entries above): d_force and d_out (q, dim * sum n_atoms)
  * packed as sc_batch_plan_modes_overlap_f64's displacement is, structure b's vector j at j * dim * sum n + dim *

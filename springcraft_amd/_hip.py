@@ -55,6 +55,7 @@ EXPORTED_SYMBOLS = [
     "sc_modes_response", "sc_dev_mode_response_f64", "sc_batch_plan_mode_response_f64",
     "sc_modes_combine", "sc_dev_mode_combine_f64", "sc_batch_plan_mode_combine_f64",
     "sc_modes_prs_subset", "sc_dev_prs_f64", "sc_batch_plan_prs_f64",
+    "sc_modes_lmi", "sc_dev_lmi_f64", "sc_batch_plan_lmi_f64",
     "sc_modes_subspace", "sc_dev_subspace_f64", "sc_dev_subspace_gram_f64",
     "sc_dev_rtb_hessian_f64", "sc_dev_rtb_expand_f64",
     "sc_dev_pairs_apply_f64", "sc_dev_pairs_strain_f64", "sc_dev_pairs_panel_f64",
@@ -253,6 +254,9 @@ def lib():
         "sc_modes_prs_subset": (i32, [vp, vp, i64, i32, vp]),
         "sc_dev_prs_f64": (i32, [vp, vp, vp, i64, i64, i64, P(ModeSelection), vp, vp, i32, vp]),
         "sc_batch_plan_prs_f64": (i32, [vp, vp, vp, i64, P(ModeSelection), vp, vp, i32, vp]),
+        "sc_modes_lmi": (i32, [vp, vp, i64, dbl, i32, vp]),
+        "sc_dev_lmi_f64": (i32, [vp, vp, vp, i64, i64, i64, P(ModeSelection), vp, i32, vp]),
+        "sc_batch_plan_lmi_f64": (i32, [vp, vp, vp, i64, P(ModeSelection), vp, i32, vp]),
         "sc_modes_subspace": (i32, [vp, vp, vp, i64, vp, i64, dbl, i32, vp, vp]),
         "sc_dev_subspace_f64": (i32, [vp, vp, vp, P(ModeSelection), vp, i64, i64, vp, vp, P(ModeSelection), vp, i64, i64,
                                       i64, i32, vp, vp, vp, vp]),
@@ -368,8 +372,8 @@ class Context:
 class Modes:
     """
     Owns one ``sc_modes``: all eigenpairs of a model, resident in device memory, plus the consumers that
-    work on them there (msf, dcc, prs, anisotropic tensors, overlaps and collectivities, distance fluctuations,
-    linear response and linear combinations of modes).  ``dim`` is 1 for a GNM and 3 for an ANM.
+    work on them there (msf, dcc, prs, generalized correlation, anisotropic tensors, overlaps and collectivities,
+    distance fluctuations, linear response and linear combinations of modes).  ``dim`` is 1 for a GNM and 3 for an ANM.
     """
 
     def __init__(self, ctx, handle, dim):
@@ -492,6 +496,21 @@ class Modes:
         n = self.order // 3
         out = host_array((n, n))
         self._ctx.check(self._L.sc_modes_prs_subset(self._h, ptr(idx), len(idx), int(bool(norm)), ptr(out)))
+        return out
+
+    def lmi(self, mode_idx, information, rcond=1e-6):
+        """
+        (n_atoms, n_atoms) generalized correlation coefficients (``information``: the mutual information in nats) over the
+        listed modes; ``mode_idx=None``: every mode with ``|w| > rcond max|w|``, the covariance rule.  ANM only.
+        """
+        idx = None if mode_idx is None else self._index_list(mode_idx)
+        n = self.order // 3
+        out = host_array((n, n))
+        if idx is not None and len(idx) == 0:   # (a NULL list means the pinv rule to the C entry)
+            out[...] = np.nan
+            return out
+        self._ctx.check(self._L.sc_modes_lmi(self._h, None if idx is None else ptr(idx), 0 if idx is None else len(idx),
+                                             float(rcond), int(bool(information)), ptr(out)))
         return out
 
     def subspace(self, other, idx_a, idx_b, kind, rcond=1e-6, gram=False):

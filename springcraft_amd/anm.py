@@ -128,6 +128,10 @@ class ANM(ElasticNetworkModel):
         """(k_a, k_b) overlaps of this model's listed modes with ``other``'s (:func:`nma.mode_overlap_matrix`)."""
         return nma.mode_overlap_matrix(self, other, mode_subset_a, mode_subset_b)
 
+    def generalized_correlation(self, mode_subset=None, information=False):
+        """Generalized correlation (n, n) from the linear mutual information (:func:`nma.generalized_correlation`)."""
+        return nma.generalized_correlation(self, mode_subset, information)
+
     def prs_effector_sensor(self, norm=True, mode_subset=None):
         """
         PRS matrix plus effector / sensor profiles (anm.py:384-445); ``mode_subset`` (extension): over the listed modes

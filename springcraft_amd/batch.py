@@ -297,6 +297,8 @@ _FIELD_ENTRIES = {
 # the same for perturbation-response scanning (csrc/mode_prs.hip): its C entries are named sc_dev_prs_f64 / sc_batch_plan_prs_f64
 _SCAN_ENTRIES = {
     "prs": ("sc_dev_prs_f64", _DEV, "sc_batch_plan_prs_f64", _PLAN),
+    # the generalized correlation (csrc/mode_lmi.hip)
+    "lmi": ("sc_dev_lmi_f64", _DEV, "sc_batch_plan_lmi_f64", _PLAN),
 }
 
 
@@ -752,6 +754,42 @@ class _BatchSolver:
             return (out,) + _effector_sensor(self.torch, out)
         profiles = [_effector_sensor(self.torch, p) for p in out]
         return out, [e for e, _ in profiles], [s for _, s in profiles]
+
+    def generalized_correlation(self, mode_subset=None, information=False):
+        """
+        (batch, n_atoms, n_atoms) generalized correlation coefficients of Lange & Grubmueller from the linear mutual
+        information (:func:`nma.generalized_correlation`; no reference counterpart, Bio3D: ``lmi``, correlationplus): how
+        much atom c knows about atom a's motion whatever the directions, where :meth:`dcc` is 0 for two atoms in lockstep
+        along perpendicular lines.  With ``C_ac = sum_k v_k[a] v_k[c]^T / lambda_k`` over the selected modes, ``C_aa = L_a
+        L_a^T`` (Cholesky, pivoted on the diagonal) and ``M = L_a^-1 C_ac L_c^-T``: ``delta = det(I - M M^T)`` clamped to
+        [0, 1], ``r = sqrt(1 - delta^(1/3))`` in [0, 1]; ``information=True`` returns the mutual information
+        ``-1/2 ln(delta)`` in nats instead.  The diagonal
+        blocks are :meth:`anisotropic_fluctuation`'s tensors; every other block is summed on the float64 matrix units and
+        reduced to its value in registers (``csrc/mode_lmi.hip``), no covariance entry is written to memory.  ANM solvers
+        only: for a GNM r is ``|dcc(norm=True)|``, and ``dim != 3`` raises ValueError before anything is enqueued.
+
+        r and I do not change under any invertible linear map per atom, so there is no ``tem`` and no ``atom_scale``: a
+        solver with ``masses`` gives the Cartesian result as it is.  ``r[a, a]`` is 1.0 and ``I[a, a]`` +inf by
+        definition.  An atom whose own block cannot be whitened -- a Cholesky pivot not finite or <= 2^-40 times the
+        block's diagonal entry: fewer than three selected modes, an atom at rest in the selection -- has NaN in its row and
+        column, diagonal included.  With exactly three selected modes every pair is perfectly correlated: r = 1 up to
+        rounding, I large or +inf, never NaN.
+
+        ``mode_subset``, the window, ``subset_by_index`` and failed structures (NaN) exactly as in :meth:`dcc`: None on a
+        full-spectrum solver takes the covariance rule, every mode with ``|lambda| > 1e-6 max|lambda|`` of that structure;
+        an empty selection or window gives NaN for that structure and no other.  The result equals its transpose bit for
+        bit, and a structure's bits do not depend on the batch size, its position or its neighbours.  Only enqueues.
+        Ragged: [(n_i, n_i), ...], views into one buffer packed like :meth:`dcc`'s; a member's bits are those of its
+        uniform solve, whatever the other members and the slot order.
+        """
+        lay = self._layout
+        if self.dim != 3:
+            raise ValueError("generalized_correlation needs an ANM solver (dim=3): for a GNM it is abs(dcc(norm=True))")
+        self._need_vectors()
+        sel, counts = self._selection(mode_subset, pinv_default=True)
+        buf = self._empty(lay.pairs_shape())
+        self._call("lmi", C.byref(sel), counts, int(bool(information)), C.c_void_p(buf.data_ptr()))
+        return lay.pairs_out(buf)
 
     # ---- how the modes of member a compare with those of member b (csrc/mode_subspace.hip) ---------------------------------
     # No reference counterpart (Bio3D: rmsip / covsoverlap; ProDy: calcSubspaceOverlap / calcCovOverlap / calcOverlap of two

@@ -1,5 +1,5 @@
 // C ABI (include/springcraft_hip.h), the mode consumers of a batch (batch_consumers.hip, dist_fluct.hip, mode_overlap.hip,
-// mode_response.hip, mode_prs.hip) on device tensors: the sc_dev_modes_* entries of a uniform batch and the sc_batch_plan_modes_* entries
+// mode_response.hip, mode_prs.hip, mode_lmi.hip) on device tensors: the sc_dev_modes_* entries of a uniform batch and the sc_batch_plan_modes_* entries
 // of a plan's padded slots; and the pairwise comparison of two uniform batches' modes (mode_subspace.hip: sc_dev_subspace_*,
 // no plan entry -- members of different size have no common coordinates).
 #include "api_internal.h"
@@ -110,6 +110,15 @@ int modes_prs(const ModesOf& who, const double* d_w, const double* d_v, const sc
                           who.ragged());
 }
 
+int modes_lmi(const ModesOf& who, const double* d_w, const double* d_v, const sc_mode_selection* sel,
+              const int64_t* d_counts, int information, double* d_out) {
+  SC_TRY(check_modes_args(who, d_w, d_v, sel, d_out));
+  if (who.dim != 3 || (!who.ragged() && who.m % 3 != 0))
+    return sc_set_error(who.ctx, SC_ERR_INVALID_ARG, "the generalized correlation needs an ANM (dim 3, m = 3 N)");
+  SC_HIP(who.ctx, hipSetDevice(who.ctx->device));
+  return batch_lmi_device(who.ctx, d_w, d_v, who.m, who.nvec, who.batch, *sel, d_counts, information, d_out, who.ragged());
+}
+
 int modes_overlap(const ModesOf& who, const double* d_v, const double* d_disp, int64_t q, const int64_t* d_counts,
                   double* d_overlap, double* d_collectivity) {
   SC_TRY(check_modes_shape(who, d_v != nullptr));
@@ -173,7 +182,7 @@ int64_t modes_workspace_bytes(const ModesOf& who, int64_t n_sel, int what, int64
   if (who.m <= 0 || who.nvec <= 0 || who.batch <= 0 || n_sel < 0 || (who.dim != 1 && who.dim != 3) || budget_bytes < 0)
     return 0;
   if (what == 3) return 0;   // overlaps and collectivities hold no workspace
-  if ((what == 2 || what == 4 || what == 7) && (who.dim != 3 || (!who.ragged() && who.m % 3 != 0))) return 0;
+  if ((what == 2 || what == 4 || what == 7 || what == 8) && (who.dim != 3 || (!who.ragged() && who.m % 3 != 0))) return 0;
   return (int64_t)batch_modes_workspace_bytes(who.m, who.nvec, who.batch, who.dim, n_sel, what, (size_t)budget_bytes,
                                               who.ragged());
 }
@@ -233,6 +242,15 @@ int sc_batch_plan_prs_f64(sc_batch_plan* plan, const double* d_w, const double* 
                           const sc_mode_selection* sel, const int64_t* d_counts, const double* d_atom_scale, int norm,
                           double* d_out) {
   return modes_prs(plan_modes_of(plan, nvec, sel ? sel->reserved : 0), d_w, d_v, sel, d_counts, d_atom_scale, norm, d_out);
+}
+
+int sc_dev_lmi_f64(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                   const sc_mode_selection* sel, const int64_t* d_counts, int information, double* d_out) {
+  return modes_lmi(ModesOf{ctx, m, nvec, batch, 3}, d_w, d_v, sel, d_counts, information, d_out);
+}
+int sc_batch_plan_lmi_f64(sc_batch_plan* plan, const double* d_w, const double* d_v, int64_t nvec,
+                          const sc_mode_selection* sel, const int64_t* d_counts, int information, double* d_out) {
+  return modes_lmi(plan_modes_of(plan, nvec, sel ? sel->reserved : 0), d_w, d_v, sel, d_counts, information, d_out);
 }
 
 int sc_dev_modes_overlap_f64(sc_ctx* ctx, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,

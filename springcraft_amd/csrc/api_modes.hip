@@ -284,6 +284,26 @@ int sc_modes_prs_subset(sc_modes* m, const int64_t* mode_idx, int64_t k, int nor
   });
 }
 
+int sc_modes_lmi(sc_modes* m, const int64_t* mode_idx, int64_t k, double rcond, int information, double* out) {
+  if (!m) return SC_ERR_INVALID_ARG;
+  sc_ctx* ctx = m->ctx;
+  if (m->dim != 3) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "the generalized correlation needs an ANM (dim 3)");
+  const bool pinv = mode_idx == nullptr;
+  if (k < 0 || k > INT32_MAX / 4 || (pinv && (k != 0 || !(rcond >= 0.0))) || (m->n > 0 && !out))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "bad arguments");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t N = (size_t)(m->n / 3);
+  double* d_out = nullptr;
+  return modes_list_call(m, mode_idx, k, m->n == 0, {{&d_out, N * N, nullptr, out}}, [&](sc_mode_selection sel) {
+    if (pinv) {   // no list: every mode above rcond
+      sel = sc_mode_selection{};
+      sel.kind = SC_SEL_PINV;
+      sel.rcond = rcond;
+    }
+    return batch_lmi_device(ctx, m->d_w, m->d_v, m->n, m->n, 1, sel, nullptr, information, d_out);
+  });
+}
+
 int sc_modes_subspace(sc_modes* a, sc_modes* b, const int64_t* mode_idx_a, int64_t k_a, const int64_t* mode_idx_b,
                       int64_t k_b, double rcond, int kind, double* out_value, double* out_gram) {
   if (!a || !b) return SC_ERR_INVALID_ARG;

@@ -369,8 +369,8 @@ int64_t msf_slab(int64_t m, int64_t nsel, int64_t batch, size_t budget) {
 }
 
 // six partial sums per atom and chunk where the msf keeps three
-int64_t aniso_slab(int64_t m, int64_t nsel, int64_t batch, size_t budget) {
-  const size_t per = (size_t)((nsel + msf_chunk(nsel) - 1) / msf_chunk(nsel)) * 6 * (m / 3) * 8;
+int64_t aniso_slab(int64_t m, int64_t nsel, int64_t batch, size_t budget, int chunk) {
+  const size_t per = (size_t)((nsel + chunk - 1) / chunk) * 6 * (m / 3) * 8;
   const int64_t slab = std::min<int64_t>(kMaxSlab, (int64_t)std::max<size_t>(1, budget / std::max<size_t>(per, 1)));
   return std::min(slab, std::max<int64_t>(batch, 1));
 }
@@ -408,7 +408,8 @@ int64_t batch_modes_nsel(const sc_mode_selection& sel, int64_t nvec) {
 
 // weights (batch, n_sel) | msf, tensors: partial sums of one slab | dcc: P and S of one slab, diagonals (batch, N), records |
 // distance fluctuations: nothing more | response, combine (mode_response.hip): coefficients and partial sums, partial sums
-// | scanning (mode_prs.hip): one diagonal per structure of a slab
+// | scanning (mode_prs.hip): one diagonal per structure of a slab | generalized correlation (mode_lmi.hip): the tensors'
+// partial sums of one slab, tensors (batch, N, 6), whitening factors (batch, N, 9)
 // (ragged: m is the slot order, the diagonals are packed over all atoms)
 size_t batch_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int dim, int64_t nsel, int what,
                                    size_t budget, const RaggedView* rv) {
@@ -420,11 +421,17 @@ size_t batch_modes_workspace_bytes(int64_t m, int64_t nvec, int64_t batch, int d
     bytes += align_up((size_t)msf_slab(m, nsel, batch, budget) * ((nsel + chunk - 1) / chunk) * m * 8, 256);
   } else if (what == 2) {
     const int chunk = msf_chunk(nsel);
-    bytes += align_up((size_t)aniso_slab(m, nsel, batch, budget) * ((nsel + chunk - 1) / chunk) * 6 * (m / 3) * 8, 256);
+    bytes += align_up((size_t)aniso_slab(m, nsel, batch, budget, chunk) * ((nsel + chunk - 1) / chunk) * 6 * (m / 3) * 8, 256);
   } else if (what == 4) {
     // distance fluctuations (dist_fluct.hip): the weights alone, a pair's sum never leaves its lane
   } else if (what == 7) {
     bytes += modes_prs_diag_bytes(m, batch, rv);
+  } else if (what == 8) {
+    // generalized correlation (mode_lmi.hip): the tensors' partial sums in chunks of kLmiTensorChunk rows, then the
+    // tensors and the factors
+    const int chunk = kLmiTensorChunk;
+    bytes += align_up((size_t)aniso_slab(m, nsel, batch, budget, chunk) * ((nsel + chunk - 1) / chunk) * 6 * (m / 3) * 8, 256);
+    bytes += modes_lmi_whiten_bytes(m, batch, rv);
   } else if (what == 5) {
     bytes += modes_response_workspace_bytes(m, batch, nsel, 5, budget);
   } else if (what == 6) {
@@ -480,7 +487,7 @@ int batch_msf_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
 // dim 3 only (the callers check): d_out (batch, m / 3, 6), ragged (sum n_atoms, 6) packed
 int batch_aniso_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
                        const sc_mode_selection& sel, const int64_t* d_counts, size_t budget, double* d_out,
-                       const RaggedView* rv) {
+                       const RaggedView* rv, int chunk_rows) {
   if (budget == 0) budget = modes_budget_default();
   hipStream_t st = ctx->stream;
   const int64_t nsel = batch_modes_nsel(sel, nvec);
@@ -492,14 +499,15 @@ int batch_aniso_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_
     SC_HIP(ctx, hipMemsetAsync(d_out, 0, sizeof(double) * 6 * (size_t)(rv ? rv->total_atoms : batch * N), st));
     return SC_OK;
   }
-  SC_TRY(sc_reserve_modes(ctx, batch_modes_workspace_bytes(m, nvec, batch, 3, nsel, 2, budget, rv)));
+  // (chunk_rows: mode_lmi.hip's call, which has reserved its own workspace, what = 8, with this one's layout at its head)
+  if (!chunk_rows) SC_TRY(sc_reserve_modes(ctx, batch_modes_workspace_bytes(m, nvec, batch, 3, nsel, 2, budget, rv)));
   char* base = (char*)ctx->modes_ws;
   double* d_s = reinterpret_cast<double*>(base);
   double* d_part = reinterpret_cast<double*>(base + align_up((size_t)batch * nsel * 8, 256));
   SC_TRY(launch_mode_weights(ctx, d_w, nvec, batch, sel, nsel, d_counts, d_s, rv));
-  const int chunk = msf_chunk(nsel);
+  const int chunk = chunk_rows ? chunk_rows : msf_chunk(nsel);
   const int nchunk = (int)((nsel + chunk - 1) / chunk);
-  const int64_t slab = aniso_slab(m, nsel, batch, budget);
+  const int64_t slab = aniso_slab(m, nsel, batch, budget, chunk);
   const int* rows = sel.kind == SC_SEL_ROWS ? sel.d_rows : nullptr;
   const int row0 = sel.kind == SC_SEL_FROM_ROW ? (int)sel.row0 : 0;
   const long long* cnt = reinterpret_cast<const long long*>(d_counts);

@@ -308,7 +308,7 @@ int modes_prs_device(sc_ctx* ctx, const double* d_v, const double* d_w, int64_t 
                      char* scratch, double* d_out);
 
 // ---- the same quantities for a batch, on the solver's own (w, v, counts) tensors (batch_consumers.hip) ----------
-// what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3), 4 = distance fluctuations (dim 3; dist_fluct.hip), 5 = response, 6 = combine (mode_response.hip), 7 = perturbation-response scanning (dim 3; mode_prs.hip).  n_sel: weighted rows per structure (batch_modes_nsel).  budget: bytes the partial sums (msf) /
+// what: 0 = msf, 1 = dcc, 2 = anisotropic tensors (dim 3), 4 = distance fluctuations (dim 3; dist_fluct.hip), 5 = response, 6 = combine (mode_response.hip), 7 = perturbation-response scanning (dim 3; mode_prs.hip), 8 = generalized correlation (dim 3; mode_lmi.hip).  n_sel: weighted rows per structure (batch_modes_nsel).  budget: bytes the partial sums (msf) /
 // the packed GEMM operands (dcc) may take, 0 = modes_budget_default().  ragged: null for a uniform batch (d_out (batch,
 // m / dim[, m / dim])), or the plan's records: m is then the slot order and d_out is packed.
 // Ragged batches (sc_batch_plan): one record per structure in the plan's device blob, read by the window count and the
@@ -334,10 +334,11 @@ int batch_msf_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
 int batch_dcc_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch, int dim,
                      const sc_mode_selection& sel, const int64_t* d_counts, int norm, size_t budget, double* d_out,
                      const RaggedView* ragged = nullptr);
-// dim 3 only: d_out (batch, m / 3, 6), six values per atom in ANISOU order; ragged: packed at 6 * atom_off
+// dim 3 only: d_out (batch, m / 3, 6), six values per atom in ANISOU order; ragged: packed at 6 * atom_off.  chunk_rows: 0
+// cuts the listed rows by msf_chunk; mode_lmi.hip passes its constant and reserves the workspace (what = 8) itself
 int batch_aniso_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
                        const sc_mode_selection& sel, const int64_t* d_counts, size_t budget, double* d_out,
-                       const RaggedView* ragged = nullptr);
+                       const RaggedView* ragged = nullptr, int chunk_rows = 0);
 
 // ---- fluctuations of the inter-atom distances (dist_fluct.hip) ----------------------------------------------------
 // dim 3 only: d_out[b, a, c] = sum_r s[b, r] (n_ac . (u_r[c] - u_r[a]))^2, n_ac the unit vector from atom a to atom c of
@@ -356,6 +357,20 @@ size_t modes_prs_diag_bytes(int64_t m, int64_t batch, const RaggedView* ragged);
 int batch_prs_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
                      const sc_mode_selection& sel, const int64_t* d_counts, const double* d_atom_scale, int norm,
                      double* d_out, const RaggedView* ragged = nullptr);
+
+// ---- generalized correlation from the linear mutual information over the selected rows (mode_lmi.hip) -----------------
+// dim 3 only: with C_ac = sum_r s[b, r] v_r[a] v_r[c]^T the 3 x 3 covariance block (a, c) and W_a the inverse Cholesky factor
+// of C_aa (diagonal pivoting), delta = det(I - M M^T) of M = W_a C_ac W_c^T clamped to [0, 1]; d_out[b, a, c] = sqrt(1 - cbrt(delta)), or with
+// information != 0 the mutual information -1/2 ln(delta) in nats.  Exactly symmetric; [a, a] is 1.0 / +inf by definition; an
+// atom whose C_aa fails the pivot rule (mode_lmi.hip) has NaN in its row and column.  No covariance entry is written to
+// memory.  Ragged: d_out packed at sq_off.  Enqueue only.
+// Listed rows per chunk of the tensors that mode_lmi.hip whitens: a constant, so that a chunk's rows do not move when rows
+// without weight follow (a ragged slot's pad rows): a structure's bits are the same in a uniform and in a ragged batch.
+constexpr int kLmiTensorChunk = 128;
+size_t modes_lmi_whiten_bytes(int64_t m, int64_t batch, const RaggedView* ragged);
+int batch_lmi_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t m, int64_t nvec, int64_t batch,
+                     const sc_mode_selection& sel, const int64_t* d_counts, int information, double* d_out,
+                     const RaggedView* ragged = nullptr);
 
 // ---- pairwise comparison of mode subspaces (mode_subspace.hip) ---------------------------------------------------------
 // One operand set: a uniform batch's (w, v, counts) with the selection of its rows.

@@ -33,7 +33,7 @@ __all__ = [
     "normal_mode", "linear_response", "prs", "effector_sensor", "anisotropic_fluctuation", "anisotropy",
     "overlap", "collectivity", "cumulative_overlap", "distance_fluctuation", "effective_stiffness",
     "mode_displacement", "sample_displacements", "deformation_energy", "spring_strain",
-    "rmsip", "covariance_overlap", "mode_overlap_matrix",
+    "rmsip", "covariance_overlap", "mode_overlap_matrix", "generalized_correlation",
 ]
 
 K_B = 1.380649e-23
@@ -573,6 +573,36 @@ def prs(anm, norm=True, mode_subset=None):
         return mat
     # covariance = pinv(hessian, rcond=1e-6) (anm.py:114-117) formed and reduced on the device
     return anm._modes_device().prs(1e-6, norm)
+
+
+def generalized_correlation(anm, mode_subset=None, information=False):
+    """
+    (n, n) generalized correlation coefficients of Lange & Grubmueller (2006) from the linear mutual information of every
+    atom pair: how much atom c knows about atom a's motion, whatever the directions.  :func:`dcc` keeps the trace of the
+    3 x 3 covariance block ``C_ac`` and is 0 for two atoms that move in lockstep along perpendicular lines; here
+
+        ``C_ac = sum_k v_k[a] v_k[c]^T / lambda_k``,  ``C_aa = L_a L_a^T``,  ``M = L_a^-1 C_ac L_c^-T``
+        ``delta = det(I - M M^T)`` clamped to [0, 1],  ``I = -1/2 ln(delta)`` (nats),  ``r = sqrt(1 - delta^(1/3))``
+
+    which is ``1/2 [ln det C_aa + ln det C_cc - ln det C_(ac)]`` on the 6 x 6 block and ``r = sqrt(1 - exp(-2 I / 3))``.
+    ``information=True`` returns I instead of r.  No reference counterpart (Bio3D: ``lmi`` / ``dccm(method="lmi")``,
+    correlationplus).  The selection is :func:`dcc`'s: ``mode_subset=None`` takes the covariance rule, every mode with
+    ``|lambda| > 1e-6 max|lambda|``; trivial indices raise ValueError.
+
+    r and I do not change under any invertible linear map per atom, so there is no ``tem`` / ``tem_factors`` and a model
+    with masses gives the Cartesian result as it is.  ``r[a, a]`` is 1.0 and ``I[a, a]`` +inf by definition; an atom whose
+    own block cannot be whitened (a Cholesky pivot not finite or <= 2^-40 times the block's diagonal entry: fewer than
+    three modes, an atom at rest in the selection) has NaN in its row and column; exactly three modes give r = 1 up to
+    rounding.  ANM only -- for a GNM r is ``abs(dcc(norm=True))``.  Computed on the device-resident eigenpairs by the
+    batch solvers' kernel (``csrc/mode_lmi.hip``) with a batch of one: no covariance is formed.
+    """
+    from .anm import ANM
+
+    if not isinstance(anm, ANM):
+        raise ValueError("Instance of ANM class expected: for a GNM the generalized correlation is abs(dcc(norm=True))")
+    if mode_subset is not None:
+        mode_subset = _mode_selection(anm, mode_subset, None)   # (the trivial-mode error needs no device)
+    return anm._modes_device().lmi(mode_subset, information)
 
 
 def _comparable(enm_a, enm_b):
