@@ -871,6 +871,56 @@ int sc_dev_ensemble_pca_f64(sc_ctx* ctx, const double* d_frames, int64_t n_frame
                             const double* d_sqrt_mass, int64_t n_modes, double* d_w, double* d_var, double* d_v,
                             double* d_total);
 
+/* ---- dense Cholesky solver on the device (csrc/potrf.hip) ----------------------------------------------------------------
+ * No reference counterpart (LAPACK: dpotrf / dpotrs).  `batch` symmetric positive definite matrices of one order n, float64,
+ * LOWER triangle, column-major, leading dimension ld >= n, matrix b at d_a + b * stride.  The strict upper triangle is never
+ * written and no result depends on it.  All entries only enqueue on the context's stream; there are no atomics, and the bits
+ * of one matrix' results do not depend on the batch or the matrix' place in it.
+ *
+ * sc_dev_potrf_workspace: *bytes = the context scratch a factorisation (or a one-vector solve) of this shape occupies; the
+ * context allocates it itself at the first call.  SC_ERR_INVALID_ARG for a NULL pointer or sizes the entries below refuse.
+ *
+ * sc_dev_potrf_f64: d_a <- L with A = L L^T, in place.  d_info (batch) int64: 0, or 1 + the first column whose pivot was <= 0
+ * or NaN (LAPACK's info).  The whole lower triangle of such a matrix becomes NaN, as does everything solved with it; the
+ * other matrices are not affected, and the next synchronising call of the context returns SC_ERR_NOCONV once (LinAlgError in
+ * the Python layer), as for a failed eigensolve.  SC_ERR_INVALID_ARG before anything is launched: n <= 0, batch <= 0 or
+ * above 65535, ld < n, a stride below a matrix' extent with batch > 1, a NULL pointer.
+ *
+ * sc_dev_potrs_f64: triangular solves with the factor d_l on the right-hand sides d_b, (n, q) column-major with leading
+ * dimension ldb >= n, matrix b's at d_b + b * strideb, in place.  mode 0: L Y = B (forward); 1: L^T X = B (backward); 2: both,
+ * A X = B.  q = 0 is valid.  SC_ERR_INVALID_ARG as above, and for another mode, q < 0, ldb < n. */
+int sc_dev_potrf_workspace(int64_t n, int64_t batch, size_t* bytes);
+int sc_dev_potrf_f64(sc_ctx* ctx, double* d_a, int64_t n, int64_t ld, int64_t stride, int64_t batch, int64_t* d_info);
+int sc_dev_potrs_f64(sc_ctx* ctx, const double* d_l, int64_t n, int64_t ld, int64_t stride, int64_t batch, double* d_b,
+                     int64_t q, int64_t ldb, int64_t strideb, int mode);
+
+/* ---- vibrational subsystem analysis (csrc/subsystem.hip) -------------------------------------------------------------------
+ * No reference counterpart (Hinsen 2000; Zheng & Brooks 2005; ProDy: reduceModel).  The N atoms are split into n_s system and
+ * n_e environment atoms: d_group (N) int32 0 / 1, d_pos (N) int32 the atom's place in its group.  ms = dim n_s, me = dim n_e.
+ *
+ * sc_dev_subsystem_blocks_f64: d_hss (ms, ms), d_hes (me, ms) row-major and d_hee (me, me), the blocks of the matrix that
+ * sc_hessian_from_pairs_f64 (dim 3) / sc_kirchhoff_from_pairs_f64 (dim 1) builds from the same ordered pair list with
+ * symmetric constants; d_row_start (N + 1): atom i owns the rows row_start[i] .. row_start[i + 1] - 1 of the list.
+ * d_inv_sqrt_mass (n_s) or NULL scales the rows and columns of H_ss and the columns of H_es; the environment is massless.
+ * Every entry is written; no atomics, two calls agree bit for bit, H_ss and H_ee equal their transposes bit for bit.
+ *
+ * sc_dev_subsystem_reduce_f64: d_hee <- its Cholesky factor L (lower, column-major; d_info (1) as for sc_dev_potrf_f64),
+ * d_hes <- Y = L^-1 H_es, d_hss <- H_eff = H_ss - Y^T Y, equal to its transpose bit for bit.
+ *
+ * sc_dev_subsystem_follow_f64: d_xe (q, me) <- -L^-T (Y x_s) for the q rows d_xs (q, ms), the environment's motion that
+ * follows the system's, with d_l and d_y as the reduction left them.
+ *
+ * All three only enqueue.  SC_ERR_INVALID_ARG before anything is launched: dim not 1 or 3, n_s or n_e not positive or not
+ * summing to n_atoms, a negative k, q < 1, a NULL required pointer. */
+int sc_dev_subsystem_blocks_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs,
+                                int64_t k, const double* d_gamma, const int64_t* d_row_start, const int32_t* d_group,
+                                const int32_t* d_pos, int64_t n_s, int64_t n_e, const double* d_inv_sqrt_mass, double* d_hss,
+                                double* d_hes, double* d_hee);
+int sc_dev_subsystem_reduce_f64(sc_ctx* ctx, double* d_hss, double* d_hes, double* d_hee, int64_t ms, int64_t me,
+                                int64_t* d_info);
+int sc_dev_subsystem_follow_f64(sc_ctx* ctx, const double* d_l, const double* d_y, int64_t ms, int64_t me, const double* d_xs,
+                                int64_t q, double* d_xe);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,15 @@ class ANM(ElasticNetworkModel):
         """Generalized correlation (n, n) from the linear mutual information (:func:`nma.generalized_correlation`)."""
         return nma.generalized_correlation(self, mode_subset, information)
 
+    def subsystem(self, system, device=None):
+        """
+        The modes of the ``system`` atoms inside their relaxing environment, a :class:`~springcraft_amd.Subsystem` built
+        from this model's atoms, force field and masses (vibrational subsystem analysis; no reference counterpart).
+        """
+        from .subsystem import Subsystem
+
+        return Subsystem(self._coord, self._ff, system, masses=self._masses, dim=3, device=device)
+
     def prs_effector_sensor(self, norm=True, mode_subset=None):
         """
         PRS matrix plus effector / sensor profiles (anm.py:384-445); ``mode_subset`` (extension): over the listed modes

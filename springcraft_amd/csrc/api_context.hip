@@ -106,6 +106,7 @@ int sc_collect_events(sc_ctx* ctx) {
   ctx->cnt_resident_rollcalls += (long long)h[8];
   ctx->cnt_resident_lost += (long long)h[9];
   if (h[7]) ctx->resident_lost_at = (long long)h[10];
+  if (h[11]) ctx->potrf_failed = (long long)h[11];
   // (one failed roll call can be a launch whose workgroups were dispatched late; the context gives the kernel up at the third)
   ctx->resident_strikes += (int)h[8];
   if (h[9] || (h[8] && ctx->resident_strikes >= 3)) ctx->resident_ok = 0;
@@ -127,8 +128,15 @@ int sc_deferred_status(sc_ctx* ctx) {
   SC_TRY(sc_collect_events(ctx));
   unsigned long long h[2] = {0, 0};
   SC_HIP(ctx, hipMemcpy(h, ctx->d_status, sizeof(h), hipMemcpyDeviceToHost));
-  if (h[0] == 0 && h[1] == 0) return SC_OK;
-  SC_HIP(ctx, hipMemset(ctx->d_status, 0, sizeof(h)));
+  const long long potrf_failed = ctx->potrf_failed;
+  ctx->potrf_failed = 0;
+  if (h[0] == 0 && h[1] == 0 && potrf_failed == 0) return SC_OK;
+  if (h[0] || h[1]) SC_HIP(ctx, hipMemset(ctx->d_status, 0, sizeof(h)));
+  // np.linalg.cholesky raises LinAlgError("Matrix is not positive definite"); the NaN that a failed factor hands to an
+  // eigensolve behind it is the same failure, named by its cause
+  if (potrf_failed)
+    return sc_set_error(ctx, SC_ERR_NOCONV, "Matrix is not positive definite: the Cholesky factorisation of matrix %lld of the batch "
+                        "met a pivot that is not positive", potrf_failed - 1);
   if (h[0])   // np.linalg.eigh raises LinAlgError("Eigenvalues did not converge") for such input (nma.py:61)
     return sc_set_error(ctx, SC_ERR_NOCONV, "Eigenvalues did not converge: matrix %llu of the batch contains NaN or Inf",
                         h[0] - 1ull);

@@ -68,6 +68,9 @@ struct sc_ctx {
   // matrices received no workgroup), [7] tridiagonalisations k_sytrd_takeover did after k_sytrd_resident gave up ([8] of
   // those after an aborted roll call, [9] after a wait lost in mid-run, [10] where).
   unsigned long long* d_status = nullptr;
+  // [11] = 1 + number of a matrix whose Cholesky factorisation met a pivot <= 0 or NaN (potrf.hip); sc_collect_events moves it
+  // here, where it waits for sc_deferred_status
+  long long potrf_failed = 0;
 
   int two_stage = -1;   // eigensolver path: -1 automatic, 0 one-stage, 1 two-stage tridiagonalisation
   // persistent bulge chase (sb2st.hip): chase_ok = 0 once a chase of this context ran into its time-out (never

@@ -1,0 +1,34 @@
+// Declarations shared by potrf.hip, subsystem.hip and api_potrf.hip; the host decisions are potrf_policy.h's.
+#pragma once
+#include "common.h"
+#include "potrf_policy.h"
+
+// word of sc_ctx::d_status a failed factorisation stores 1 + the matrix' number in (sc_collect_events keeps it for
+// sc_deferred_status)
+constexpr int kStatusPotrf = 11;
+constexpr int kTrsmForward = 0, kTrsmBackward = 1, kTrsmRight = 2;
+
+size_t potrf_desc_bytes();
+int potrf_outer_block(int64_t n);   // sc_host::potrf_outer_block with SPRINGCRAFT_POTRF_OUTER
+// d_a (batch matrices, lower, column-major, ld, stride) <- L; d_info (batch) int64: 0, or 1 + the failing column.  Enqueue only.
+int launch_potrf(sc_ctx* ctx, const sc_host::PotrfBufs& B, double* d_a, int64_t n, int64_t ld, int64_t stride,
+                 int64_t batch, int outer, long long* d_info);
+// One pass of block substitution with the factor d_l.  kTrsmForward / kTrsmBackward: d_b (n, vectors) column-major <-
+// L^-1 d_b / L^-T d_b; kTrsmRight: d_b (vectors, n) column-major <- d_b L^-T.  pass: 0 inverts the factor's diagonal blocks
+// into B.dinv first; 1 (the second half of a `both` solve) reuses them and takes the second half of B.descs.  Enqueue only.
+int launch_trsm(sc_ctx* ctx, const sc_host::TrsmBufs& B, int pass, int kind, const double* d_l, int64_t n, int64_t ld,
+                int64_t stride, int64_t batch, double* d_b, int64_t vectors, int64_t ldb, int64_t strideb);
+
+// ---- subsystem.hip -----------------------------------------------------------------------------------------------------------
+// H_ss (ms, ms), H_es (me, ms) row-major and H_ee (me, me) of the partitioned network, ms = dim n_s, me = dim n_e, from the
+// ordered pair list; every entry is written.  d_group (N) int32: 0 system, 1 environment; d_pos (N) int32: the atom's place in
+// its group; d_ism (n_s) or null: 1 / sqrt(mass) of the system atoms.  No atomics, no workspace; enqueue only.
+int launch_subsystem_blocks(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs, int64_t k,
+                            const double* d_gamma, const int64_t* d_row_start, const int32_t* d_group, const int32_t* d_pos,
+                            int64_t n_s, int64_t n_e, const double* d_ism, double* d_hss, double* d_hes, double* d_hee);
+// d_hee <- L (lower, column-major), d_hes <- Y = L^-1 H_es (me, ms) row-major, d_hss <- H_eff = H_ss - Y^T Y, mirrored.
+int launch_subsystem_reduce(sc_ctx* ctx, const sc_host::ReduceBufs& B, double* d_hss, double* d_hes, double* d_hee,
+                            int64_t ms, int64_t me, int outer, long long* d_info);
+// d_xe (q, me) <- -L^-T (Y x_s) for the q rows d_xs (q, ms)
+int launch_subsystem_follow(sc_ctx* ctx, const sc_host::FollowBufs& B, const double* d_l, const double* d_y, int64_t ms,
+                            int64_t me, const double* d_xs, int64_t q, double* d_xe);

@@ -107,3 +107,12 @@ class GNM(ElasticNetworkModel):
     def mode_overlap_matrix(self, other, mode_subset_a, mode_subset_b=None):
         """(k_a, k_b) overlaps of this model's listed modes with ``other``'s (:func:`nma.mode_overlap_matrix`)."""
         return nma.mode_overlap_matrix(self, other, mode_subset_a, mode_subset_b)
+
+    def subsystem(self, system, device=None):
+        """
+        The modes of the ``system`` atoms inside their relaxing environment, a :class:`~springcraft_amd.Subsystem` (dim 1)
+        built from this model's atoms, force field and masses (vibrational subsystem analysis; no reference counterpart).
+        """
+        from .subsystem import Subsystem
+
+        return Subsystem(self._coord, self._ff, system, masses=self._masses, dim=1, device=device)
