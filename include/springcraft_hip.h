@@ -921,6 +921,42 @@ int sc_dev_subsystem_reduce_f64(sc_ctx* ctx, double* d_hss, double* d_hes, doubl
 int sc_dev_subsystem_follow_f64(sc_ctx* ctx, const double* d_l, const double* d_y, int64_t ms, int64_t me, const double* d_xs,
                                 int64_t q, double* d_xe);
 
+/* ---- batched subsystem reduction on a common core (csrc/subsystem.hip) ---------------------------------------------------------
+ * No reference counterpart (Bio3D: nma.pdbs with rm.gaps = TRUE; ProDy: reduceModel over an ensemble).  `batch` members keep
+ * all their atoms; every member has the same n_s system atoms (the aligned core) and its own n_e(b) <= env_order environment
+ * atoms.  ms = dim n_s; me = dim env_order is the order of every environment slot.
+ *
+ * The members' inputs are packed back to back: d_coord (sum n_b, 3), d_pairs (sum k_b, 2) with LOCAL atom indices, d_gamma
+ * (sum k_b), d_group / d_pos (sum n_b) and d_row_start, n_b + 1 entries per member counting from the member's own first pair.
+ * `members` is a HOST array (batch, 5) int64: atom offset, atom count, pair offset, pair count, n_e; the offsets must follow
+ * the member before.  Member b's row starts begin at entry (atom offset + b).  d_inv_sqrt_mass (batch, n_s) or NULL.
+ *
+ * sc_dev_vsa_batch_blocks_f64: d_hss (batch, ms, ms), d_hes (batch, me, ms) row-major, d_hee (batch, me, me).  The unpadded
+ * region of slot b has the bits sc_dev_subsystem_blocks_f64 gives for that member alone.  The pad of a slot is 1.0 on the pad
+ * diagonal of H_ee and exactly 0.0 everywhere else, the pad rows of H_es included: the slot of H_ee is diag(H_ee(b), I).
+ * Every entry of every slot is written; no atomics; two calls agree bit for bit.  With env_order = 0, d_hes and d_hee are not
+ * touched and may be NULL.
+ *
+ * sc_dev_vsa_batch_reduce_f64: per slot as sc_dev_subsystem_reduce_f64 -- d_hee <- diag(L_b, I), d_hes <- Y (pad rows 0),
+ * d_hss <- H_eff, equal to its transpose bit for bit -- in one batched factorisation, one batched substitution and one
+ * grouped product.  d_info (batch) as for sc_dev_potrf_f64: a failed member's H_eff is NaN, the others are not affected, and
+ * the failure is reported once by the next synchronising call.  For a given me, a member's bits do not depend on the batch,
+ * its place in it or its neighbours (they may depend on me: the block plan of the factorisation does).  me = 0: nothing is
+ * reduced, H_eff = H_ss, d_info <- 0.
+ *
+ * sc_dev_vsa_batch_workspace: *bytes = the context scratch the reduction occupies (0 for env_order = 0).
+ *
+ * SC_ERR_INVALID_ARG before anything is launched: dim not 1 or 3, n_s < 1 (ms < 1), batch < 1 or above 65535, a negative
+ * env_order (me), a member with n_e outside 0 .. env_order or n_s + n_e != its atom count or offsets out of sequence, a NULL
+ * required pointer. */
+int sc_dev_vsa_batch_workspace(int dim, int64_t n_s, int64_t env_order, int64_t batch, size_t* bytes);
+int sc_dev_vsa_batch_blocks_f64(sc_ctx* ctx, const int64_t* members, int64_t batch, int dim, int64_t n_s, int64_t env_order,
+                                const double* d_coord, const int64_t* d_pairs, const double* d_gamma,
+                                const int64_t* d_row_start, const int32_t* d_group, const int32_t* d_pos,
+                                const double* d_inv_sqrt_mass, double* d_hss, double* d_hes, double* d_hee);
+int sc_dev_vsa_batch_reduce_f64(sc_ctx* ctx, double* d_hss, double* d_hes, double* d_hee, int64_t ms, int64_t me,
+                                int64_t batch, int64_t* d_info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,4 +18,4 @@ from .ensemble import Ensemble, EssentialDynamics, superimpose  # noqa: F401
 from .iterative import filter_coefficients, spectral_bound  # noqa: F401
 from .pair_operator import PairOperator  # noqa: F401
 from .rtb import RTB, blocks_of_consecutive, rtb_projector  # noqa: F401
-from .subsystem import Subsystem, subsystem_partition  # noqa: F401
+from .subsystem import Subsystem, SubsystemBatch, aligned_core, subsystem_partition  # noqa: F401

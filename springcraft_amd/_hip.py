@@ -63,6 +63,7 @@ EXPORTED_SYMBOLS = [
     "sc_superpose_form", "sc_dev_superpose_f64", "sc_dev_ensemble_mean_f64", "sc_dev_ensemble_pca_f64",
     "sc_dev_potrf_workspace", "sc_dev_potrf_f64", "sc_dev_potrs_f64",
     "sc_dev_subsystem_blocks_f64", "sc_dev_subsystem_reduce_f64", "sc_dev_subsystem_follow_f64",
+    "sc_dev_vsa_batch_workspace", "sc_dev_vsa_batch_blocks_f64", "sc_dev_vsa_batch_reduce_f64",
 ]
 
 SC_SEL_FROM_ROW = 0
@@ -283,6 +284,9 @@ def lib():
         "sc_dev_subsystem_blocks_f64": (i32, [vp, vp, i64, i32, vp, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp]),
         "sc_dev_subsystem_reduce_f64": (i32, [vp, vp, vp, vp, i64, i64, vp]),
         "sc_dev_subsystem_follow_f64": (i32, [vp, vp, vp, i64, i64, vp, i64, vp]),
+        "sc_dev_vsa_batch_workspace": (i32, [i32, i64, i64, i64, P(C.c_size_t)]),
+        "sc_dev_vsa_batch_blocks_f64": (i32, [vp, vp, i64, i32, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "sc_dev_vsa_batch_reduce_f64": (i32, [vp, vp, vp, vp, i64, i64, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

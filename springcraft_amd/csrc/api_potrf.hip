@@ -119,4 +119,67 @@ int sc_dev_subsystem_follow_f64(sc_ctx* ctx, const double* d_l, const double* d_
   return sc_stage_end(ctx);
 }
 
+int sc_dev_vsa_batch_workspace(int dim, int64_t n_s, int64_t env_order, int64_t batch, size_t* bytes) {
+  if (!bytes || sc_host::sub_batch_shape_error(dim, n_s, env_order, batch)) return SC_ERR_INVALID_ARG;
+  const int64_t me = sc_host::sub_slot_order(dim, env_order);
+  *bytes = sc_host::batch_reduce_scratch_bytes(me, dim * n_s, batch, potrf_outer_block(me), potrf_desc_bytes());
+  return SC_OK;
+}
+
+int sc_dev_vsa_batch_blocks_f64(sc_ctx* ctx, const int64_t* members, int64_t batch, int dim, int64_t n_s, int64_t env_order,
+                                const double* d_coord, const int64_t* d_pairs, const double* d_gamma,
+                                const int64_t* d_row_start, const int32_t* d_group, const int32_t* d_pos,
+                                const double* d_inv_sqrt_mass, double* d_hss, double* d_hes, double* d_hee) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  static const char* const kRule[] = {"", "dim must be 1 or 3", "the system needs at least one atom",
+                                      "the batch must hold 1 .. 65535 members", "env_order must not be negative",
+                                      "the orders exceed the solver's limit"};
+  if (const int e = sc_host::sub_batch_shape_error(dim, n_s, env_order, batch))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "subsystem batch: %s (dim = %d, n_s = %lld, env_order = %lld, batch = %lld)", kRule[e],
+                        dim, (long long)n_s, (long long)env_order, (long long)batch);
+  if (!members) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "subsystem batch: the member records are required");
+  static_assert(sizeof(sc_host::SubMember) == 5 * sizeof(int64_t), "the C ABI passes a member as five int64");
+  const sc_host::SubMember* mem = reinterpret_cast<const sc_host::SubMember*>(members);
+  const int64_t bad = sc_host::sub_batch_member_error(mem, batch, n_s, env_order);
+  if (bad >= 0)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "subsystem batch: member %lld does not fit (n_atoms = %lld, n_e = %lld with n_s = %lld and env_order = %lld, %lld pairs, offsets %lld / %lld)",
+                        (long long)bad, (long long)mem[bad].n_atoms, (long long)mem[bad].n_e, (long long)n_s, (long long)env_order,
+                        (long long)mem[bad].n_pairs, (long long)mem[bad].atom0, (long long)mem[bad].pair0);
+  const int64_t total_pairs = mem[batch - 1].pair0 + mem[batch - 1].n_pairs;
+  if (mem[batch - 1].atom0 + mem[batch - 1].n_atoms > 0x7fffffffLL / 3)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "subsystem batch: at most %lld atoms in all", 0x7fffffffLL / 3);
+  if (!d_row_start || !d_group || !d_pos || !d_hss || (env_order > 0 && (!d_hes || !d_hee)) || (dim == 3 && !d_coord))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "subsystem batch: a required pointer is NULL");
+  if (total_pairs > 0 && (!d_pairs || !d_gamma))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "subsystem batch: pairs and gamma are required with pairs");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  sc_host::BatchBlocksBufs B{};
+  SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) { B = sc_host::batch_blocks_layout(a, batch); }));
+  SC_TRY(launch_subsystem_batch_blocks(ctx, B, mem, batch, sc_host::sub_batch_max_pairs(mem, batch), d_coord, dim, d_pairs,
+                                       d_gamma, d_row_start, d_group, d_pos, n_s, env_order, d_inv_sqrt_mass, d_hss, d_hes,
+                                       d_hee));
+  return sc_stage_end(ctx);
+}
+
+int sc_dev_vsa_batch_reduce_f64(sc_ctx* ctx, double* d_hss, double* d_hes, double* d_hee, int64_t ms, int64_t me,
+                                int64_t batch, int64_t* d_info) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  if (ms <= 0 || me < 0 || ms > sc_host::kPotrfMaxOrder || me > sc_host::kPotrfMaxOrder)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "subsystem batch: the system's order must be positive, the slot's not negative");
+  if (batch < 1 || batch > sc_host::kSubBatchMax)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "subsystem batch: the batch must hold 1 .. 65535 members, got %lld", (long long)batch);
+  if (!d_hss || !d_info || (me > 0 && (!d_hes || !d_hee)))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "subsystem batch: a required pointer is NULL");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  if (me == 0) {   // every member is exactly the core: H_eff = H_ss
+    SC_HIP(ctx, hipMemsetAsync(d_info, 0, sizeof(int64_t) * (size_t)batch, ctx->stream));
+    return SC_OK;
+  }
+  const int outer = potrf_outer_block(me);
+  sc_host::BatchReduceBufs B{};
+  SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) { B = sc_host::batch_reduce_layout(a, me, ms, batch, outer, potrf_desc_bytes()); }));
+  SC_TRY(launch_subsystem_batch_reduce(ctx, B, d_hss, d_hes, d_hee, ms, me, batch, outer, (long long*)d_info));
+  return sc_stage_end(ctx);
+}
+
 }  // extern "C"

@@ -32,3 +32,15 @@ int launch_subsystem_reduce(sc_ctx* ctx, const sc_host::ReduceBufs& B, double* d
 // d_xe (q, me) <- -L^-T (Y x_s) for the q rows d_xs (q, ms)
 int launch_subsystem_follow(sc_ctx* ctx, const sc_host::FollowBufs& B, const double* d_l, const double* d_y, int64_t ms,
                             int64_t me, const double* d_xs, int64_t q, double* d_xe);
+// The batch: `batch` members with n_s system atoms each and environments of up to env_order atoms, inputs packed back to back
+// (h_members: the host records, staged into B.members).  d_hss (batch, ms, ms), d_hes (batch, me, ms) row-major and d_hee
+// (batch, me, me), me = dim env_order; a member with a smaller environment gets diag(H_ee, I), zero pad rows of H_es.  d_ism
+// (batch, n_s) or null.  Every entry of every slot is written; no atomics; enqueue only.
+int launch_subsystem_batch_blocks(sc_ctx* ctx, const sc_host::BatchBlocksBufs& B, const sc_host::SubMember* h_members,
+                                  int64_t batch, int64_t max_pairs, const double* d_coord, int dim, const int64_t* d_pairs,
+                                  const double* d_gamma, const int64_t* d_row_start, const int32_t* d_group,
+                                  const int32_t* d_pos, int64_t n_s, int64_t env_order, const double* d_ism, double* d_hss,
+                                  double* d_hes, double* d_hee);
+// launch_subsystem_reduce on every slot: one batched factorisation, one batched substitution, one grouped product, one mirror
+int launch_subsystem_batch_reduce(sc_ctx* ctx, const sc_host::BatchReduceBufs& B, double* d_hss, double* d_hes, double* d_hee,
+                                  int64_t ms, int64_t me, int64_t batch, int outer, long long* d_info);

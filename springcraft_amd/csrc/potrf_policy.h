@@ -148,4 +148,77 @@ static inline FollowBufs follow_layout(Arena& a, int64_t me, int64_t q, size_t d
 // flops of a reduction: me^3 / 3 + me^2 ms + me ms^2
 static inline double reduce_flops(double me, double ms) { return me * me * me / 3.0 + me * me * ms + me * ms * ms; }
 
+// ---- the batched reduction: B members with one system size and environments of different size in slots of one order -----------
+// One member of the packed inputs (coordinates, LOCAL pair indices, gamma, row starts, group / pos back to back).  Atom a of
+// the member is packed atom atom0 + a; its n_atoms + 1 row starts are at atom0 + (the member's number) and count from the
+// member's own first pair, which is packed pair pair0.
+struct SubMember {
+  int64_t atom0, n_atoms, pair0, n_pairs, n_e;
+};
+constexpr int64_t kSubBatchMax = 65535;   // (the member is a grid's y index, as the matrix of a batched factorisation)
+
+// Order of the environment slot.  env_order atoms per slot; a member with fewer gets diag(H_ee, I).
+static inline int64_t sub_slot_order(int dim, int64_t env_order) { return (int64_t)dim * env_order; }
+// 0 when the shapes can be launched, else the number of the rule they break (api_potrf.hip turns it into a message):
+// 1 dim, 2 n_s, 3 batch, 4 env_order, 5 an order above the solver's limit
+static inline int sub_batch_shape_error(int dim, int64_t n_s, int64_t env_order, int64_t batch) {
+  if (dim != 1 && dim != 3) return 1;
+  if (n_s < 1) return 2;
+  if (batch < 1 || batch > kSubBatchMax) return 3;
+  if (env_order < 0) return 4;
+  if (n_s > kPotrfMaxOrder / 3 || env_order > kPotrfMaxOrder / 3) return 5;
+  return 0;
+}
+// -1 when every member fits its slot, else the first member that does not: n_e outside 0 .. env_order, n_s + n_e != n_atoms,
+// a negative pair count, or offsets that do not follow the member before (the arrays are packed back to back)
+static inline int64_t sub_batch_member_error(const SubMember* mem, int64_t batch, int64_t n_s, int64_t env_order) {
+  int64_t atom0 = 0, pair0 = 0;
+  for (int64_t b = 0; b < batch; ++b) {
+    const SubMember& m = mem[b];
+    if (m.n_e < 0 || m.n_e > env_order || m.n_atoms != n_s + m.n_e || m.n_pairs < 0) return b;
+    if (m.atom0 != atom0 || m.pair0 != pair0) return b;
+    atom0 += m.n_atoms;
+    pair0 += m.n_pairs;
+  }
+  return -1;
+}
+// the x extent of the two assembly grids: the longest pair list, and every atom of a member plus its slot's pad atoms
+static inline int64_t sub_batch_max_pairs(const SubMember* mem, int64_t batch) {
+  int64_t k = 0;
+  for (int64_t b = 0; b < batch; ++b) k = std::max(k, mem[b].n_pairs);
+  return k;
+}
+static inline int64_t sub_batch_atom_threads(int64_t n_s, int64_t env_order) { return n_s + env_order; }
+
+struct BatchBlocksBufs {
+  char* members;   // (batch) SubMember
+};
+static inline BatchBlocksBufs batch_blocks_layout(Arena& a, int64_t batch) {
+  BatchBlocksBufs B{};
+  B.members = a.take<char>((size_t)batch * sizeof(SubMember));
+  return B;
+}
+struct BatchReduceBufs {
+  PotrfBufs potrf;
+  TrsmBufs trsm;
+  char* descs;   // (batch) records of the H_eff products
+};
+// me = sub_slot_order(...) > 0
+static inline BatchReduceBufs batch_reduce_layout(Arena& a, int64_t me, int64_t ms, int64_t batch, int outer, size_t desc_bytes) {
+  BatchReduceBufs B{};
+  B.potrf = potrf_layout(a, me, batch, potrf_record_count(potrf_plan(me, outer), batch), desc_bytes);
+  B.trsm = trsm_layout(a, me, batch, ms, 1, desc_bytes);
+  B.descs = a.take<char>((size_t)batch * desc_bytes);
+  return B;
+}
+// what sc_dev_vsa_batch_workspace reports: the reduction's scratch, 0 for env_order = 0 (there is no reduction)
+static inline size_t batch_reduce_scratch_bytes(int64_t me, int64_t ms, int64_t batch, int outer, size_t desc_bytes) {
+  if (me == 0) return 0;
+  Arena a;
+  batch_reduce_layout(a, me, ms, batch, outer, desc_bytes);
+  return a.bytes();
+}
+// flops the pad adds to member b's reduction: what a slot of order me costs beyond the member's own me_b
+static inline double reduce_pad_flops(double me, double me_b, double ms) { return reduce_flops(me, ms) - reduce_flops(me_b, ms); }
+
 }  // namespace sc_host
