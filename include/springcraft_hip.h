@@ -870,6 +870,26 @@ int sc_dev_ensemble_mean_f64(sc_ctx* ctx, const double* d_frames, int64_t n_fram
 int sc_dev_ensemble_pca_f64(sc_ctx* ctx, const double* d_frames, int64_t n_frames, int64_t n_atoms, const double* d_mean,
                             const double* d_sqrt_mass, int64_t n_modes, double* d_w, double* d_var, double* d_v,
                             double* d_total);
+/* The pairwise least-squares RMSD of conformations.  No reference counterpart (Bio3D: rmsd(xyz, fit = TRUE); ProDy, MDTraj
+ * and MDAnalysis have their own pairwise RMSD matrices).  d_out (n_a, n_b): every frame of d_a (n_a, N, 3) with every frame
+ * of d_b (n_b, N, 3); d_b NULL: d_a with itself, n_b = n_a.  With W = sum w, c_f = sum w x_f / W, y_f = x_f - c_f, G_f =
+ * sum_a w_a |y_f[a]|^2 and S = sum_a w_a y_f[a] y_g[a]^T:
+ *     msd(f, g) = max(0, (G_f + G_g) - 2 lambda) / W,   lambda the largest eigenvalue of Horn's 4 x 4 matrix of S
+ * (the proper rotation's, also for a mirror image), from one Gram product over the atoms on the matrix pipe: no rotation is
+ * formed, no frame written.  flags bit 0: fit (unset: the frames as they are, lambda = tr S about the weighted centroid of
+ * d_a's first frame -- 0 where that is not finite); bit 1: squared, d_out = msd, else rmsd = sqrt(msd).
+ * A self-comparison equals its transpose bit for bit and its diagonal is exactly 0.0.  A non-finite coordinate turns that
+ * frame's row and column into NaN (the diagonal entry included) and no other entry.  An entry's bits depend on its two
+ * frames, the weights and the flags alone: not on n_a, n_b, the frames' positions or their neighbours.  Enqueue only.
+ * SC_ERR_INVALID_ARG: non-positive sizes, d_b NULL with n_b != n_a, unknown flag bits, a NULL d_a or d_out, sizes for which
+ * sc_rmsd_matrix_workspace answers -1.
+ *
+ * sc_rmsd_matrix_workspace: bytes of context scratch a call occupies, n_b = 0 for a self-comparison: per ensemble a
+ * transposed centred copy (8 ceil(N / 8), 3, 64 ceil(M / 64)) and 64 ceil(M / 64) sums, each region rounded up to 256
+ * bytes, and one double more.  -1 for non-positive n_a or n_atoms, a negative n_b, or sizes beyond the index range. */
+int64_t sc_rmsd_matrix_workspace(int64_t n_a, int64_t n_b, int64_t n_atoms);
+int sc_dev_rmsd_matrix_f64(sc_ctx* ctx, const double* d_a, int64_t n_a, const double* d_b, int64_t n_b, int64_t n_atoms,
+                           const double* d_weights, int flags, double* d_out);
 
 /* ---- dense Cholesky solver on the device (csrc/potrf.hip) ----------------------------------------------------------------
  * No reference counterpart (LAPACK: dpotrf / dpotrs).  `batch` symmetric positive definite matrices of one order n, float64,

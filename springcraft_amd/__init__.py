@@ -14,7 +14,7 @@ from .forcefield import *  # noqa: F401,F403
 from .gnm import *  # noqa: F401,F403
 from .interaction import *  # noqa: F401,F403
 from . import ensemble, iterative, nma  # noqa: F401
-from .ensemble import Ensemble, EssentialDynamics, superimpose  # noqa: F401
+from .ensemble import Ensemble, EssentialDynamics, rmsd_matrix, superimpose  # noqa: F401
 from .iterative import filter_coefficients, spectral_bound  # noqa: F401
 from .pair_operator import PairOperator  # noqa: F401
 from .rtb import RTB, blocks_of_consecutive, rtb_projector  # noqa: F401

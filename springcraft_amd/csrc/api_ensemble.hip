@@ -1,5 +1,5 @@
 // C ABI (include/springcraft_hip.h), device-pointer entries of the conformational ensembles: superposition and the mean frame
-// (superpose.hip), ensemble PCA (ensemble_pca.hip).  Argument checks, the scratch carve, the launcher call.
+// (superpose.hip), ensemble PCA (ensemble_pca.hip), the pairwise RMSD matrix (rmsd_matrix.hip).  Argument checks, the scratch carve, the launcher call.
 #include "api_internal.h"
 #include "ensemble_internal.h"
 
@@ -67,6 +67,30 @@ int sc_dev_ensemble_pca_f64(sc_ctx* ctx, const double* d_frames, int64_t n_frame
     B = sc_host::pca_layout(a, P, n_frames, n_atoms, n_modes, ensemble_pca_desc_bytes());
   }));
   return launch_ensemble_pca(ctx, P, B, d_frames, n_frames, n_atoms, d_mean, d_sqrt_mass, n_modes, d_w, d_var, d_v, d_total);
+}
+
+int64_t sc_rmsd_matrix_workspace(int64_t n_a, int64_t n_b, int64_t n_atoms) {
+  if (sc_host::rmsd_shape_error(n_a, n_b, n_atoms)) return -1;
+  return (int64_t)sc_host::rmsd_scratch_bytes(n_a, n_b, n_atoms);
+}
+
+int sc_dev_rmsd_matrix_f64(sc_ctx* ctx, const double* d_a, int64_t n_a, const double* d_b, int64_t n_b, int64_t n_atoms,
+                           const double* d_weights, int flags, double* d_out) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  if (n_a <= 0 || n_b <= 0 || n_atoms <= 0)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "rmsd matrix: the numbers of frames and atoms must be positive");
+  if (!d_b && n_b != n_a)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "rmsd matrix: a self-comparison (d_b NULL) has n_b = n_a, got %lld and %lld",
+                        (long long)n_b, (long long)n_a);
+  if (flags & ~3) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "rmsd matrix: flags has bits 0 (fit) and 1 (squared) only");
+  if (sc_host::rmsd_shape_error(n_a, d_b ? n_b : 0, n_atoms))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "rmsd matrix: %lld x %lld frames of %lld atoms are beyond the kernels' index range",
+                        (long long)n_a, (long long)n_b, (long long)n_atoms);
+  if (!d_a || !d_out) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "rmsd matrix: the frames and the output are required");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  sc_host::RmsdBufs B{};
+  SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) { B = sc_host::rmsd_layout(a, n_a, d_b ? n_b : 0, n_atoms); }));
+  return launch_rmsd_matrix(ctx, B, d_a, n_a, d_b, n_b, n_atoms, d_weights, (flags & 1) != 0, (flags & 2) != 0, d_out);
 }
 
 }  // extern "C"

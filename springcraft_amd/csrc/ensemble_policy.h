@@ -1,7 +1,7 @@
-// The host decisions of the conformational-ensemble entries (superpose.hip, ensemble_pca.hip, api_ensemble.hip): which
-// kernel form a superposition takes, which product an ensemble PCA forms and with how many K slices, and the layout of
-// their scratch.  Same rules as gemm_policy.h: closed-form functions of their inputs, no HIP, header-only;
-// tests/host_sanitize/test_ensemble_logic.cpp compiles exactly this code with g++ -fsanitize=address,undefined.
+// The host decisions of the conformational-ensemble entries (superpose.hip, ensemble_pca.hip, rmsd_matrix.hip,
+// api_ensemble.hip): which kernel form a superposition takes, which product an ensemble PCA forms and with how many K
+// slices, the pads and tiles of the pairwise RMSD matrix, and the layout of their scratch.  Same rules as gemm_policy.h:
+// closed-form functions of their inputs, no HIP, header-only; tests/host_sanitize/test_ensemble_logic.cpp compiles exactly this code with g++ -fsanitize=address,undefined.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -54,6 +54,52 @@ static inline int64_t mean_chunks(int64_t n_frames) { return (n_frames + kMeanCh
 struct MeanBufs { double* partial; };   // (chunks, 3 N)
 static inline MeanBufs mean_layout(Arena& a, int64_t n_frames, int64_t n_atoms) {
   return MeanBufs{a.take<double>((size_t)mean_chunks(n_frames) * 3 * (size_t)n_atoms)};
+}
+
+// ---- pairwise RMSD matrix (rmsd_matrix.hip) ----------------------------------------------------------------------------------
+// A workgroup of the product kernel owns kRmsdTile x kRmsdTile frame pairs and stages kRmsdRows atoms at a time.  The
+// transposed copy Y (N_pad, 3, M_pad) is padded to both with exact zeros, so the product has no tail code.
+constexpr int kRmsdTile = 64;
+constexpr int kRmsdRows = 8;
+static inline int64_t rmsd_pad_frames(int64_t n_frames) { return (n_frames + kRmsdTile - 1) / kRmsdTile * kRmsdTile; }
+static inline int64_t rmsd_pad_atoms(int64_t n_atoms) { return (n_atoms + kRmsdRows - 1) / kRmsdRows * kRmsdRows; }
+// workgroups of the product: the lower triangle of tiles for a self-comparison (n_b = 0), else the rectangle
+static inline int64_t rmsd_tiles(int64_t n_a, int64_t n_b) {
+  const int64_t ta = rmsd_pad_frames(n_a) / kRmsdTile, tb = rmsd_pad_frames(n_b) / kRmsdTile;
+  return n_b == 0 ? ta * (ta + 1) / 2 : ta * tb;
+}
+struct RmsdBufs {
+  double* ya;     // (N_pad, 3, Ma_pad) sqrt(w) times the centred frames of the first ensemble, frame index fastest
+  double* ga;     // (Ma_pad) G_f, NaN for a non-finite frame, 0 for a pad frame
+  double* yb;     // the same of the second ensemble; a self-comparison takes neither
+  double* gb;
+  double* wsum;   // (1) W
+};
+static inline RmsdBufs rmsd_layout(Arena& a, int64_t n_a, int64_t n_b, int64_t n_atoms) {
+  const size_t rows = 3 * (size_t)rmsd_pad_atoms(n_atoms);
+  const size_t ma = (size_t)rmsd_pad_frames(n_a), mb = (size_t)rmsd_pad_frames(n_b);
+  RmsdBufs B{};
+  B.ya = a.take<double>(rows * ma);
+  B.ga = a.take<double>(ma);
+  B.yb = a.take<double>(n_b > 0 ? rows * mb : 0);
+  B.gb = a.take<double>(n_b > 0 ? mb : 0);
+  B.wsum = a.take<double>(1);
+  return B;
+}
+static inline size_t rmsd_scratch_bytes(int64_t n_a, int64_t n_b, int64_t n_atoms) {
+  Arena a;
+  rmsd_layout(a, n_a, n_b, n_atoms);
+  return a.bytes();
+}
+// 0: fits; else which rule it breaks.  The sizes are positive here (n_b = 0: self).  The copies must be addressable and the
+// tiles fit a grid; the output's own size is the caller's.
+static inline int rmsd_shape_error(int64_t n_a, int64_t n_b, int64_t n_atoms) {
+  if (n_a <= 0 || n_b < 0 || n_atoms <= 0) return 1;
+  if (n_a > 0x7fffffffLL - kRmsdTile || n_b > 0x7fffffffLL - kRmsdTile || n_atoms > 0x7fffffffLL / 3 - kRmsdRows) return 2;
+  const long double cells = 3.0L * (long double)rmsd_pad_atoms(n_atoms) * (long double)rmsd_pad_frames(n_a > n_b ? n_a : n_b);
+  if (cells > 0x1p58L) return 3;                       // (bytes of one copy stay far inside size_t)
+  if (rmsd_tiles(n_a, n_b) > 0x3fffffffLL) return 4;   // (one grid axis, and the triangle decode's int arithmetic)
+  return 0;
 }
 
 // ---- ensemble PCA ----------------------------------------------------------------------------------------------------------

@@ -5,7 +5,7 @@ superimpose with biotite; Bio3D: ``fit.xyz`` / ``pca.xyz``, ProDy: ``superpose``
 
 :func:`superimpose` is the host convenience for one or a few conformers, e.g. before ``nma.overlap(enm, fitted - fixed)``.
 :class:`Ensemble` keeps the frames on the device, fits them on a frame or iteratively on their mean
-(``csrc/superpose.hip``) and turns them into :class:`EssentialDynamics`, the quasi-harmonic modes of the ensemble
+(``csrc/superpose.hip``), gives the least-squares RMSD of every pair of frames (``csrc/rmsd_matrix.hip``) and turns them into :class:`EssentialDynamics`, the quasi-harmonic modes of the ensemble
 (``csrc/ensemble_pca.hip``): a mode source like :class:`~springcraft_amd.RTB`, with every mode consumer of the batch
 solvers and the comparisons ``rmsip`` / ``covariance_overlap`` / ``mode_overlap_matrix`` against an elastic network's modes.
 """
@@ -17,7 +17,7 @@ import numpy as np
 from . import _hip, atoms as _atoms
 from .batch import _BatchSolver, _UniformLayout
 
-__all__ = ["Ensemble", "EssentialDynamics", "superimpose"]
+__all__ = ["Ensemble", "EssentialDynamics", "superimpose", "rmsd_matrix"]
 
 
 # ---- host-side argument checks (before any device call) -----------------------------------------------------------------
@@ -100,6 +100,30 @@ def rank_check(variances, n_frames, n_atoms):
     if usable < len(var) or not var[0] > 0:
         raise ValueError(f"the ensemble is rank-deficient: only {usable} of the {len(var)} selected components have a "
                          f"variance above rounding level ({floor:.3e}); ask for n_modes <= {usable}")
+
+
+_MAX_SIDE = 2 ** 31 - 1
+
+
+def _checked_matrix_shape(n_a, n_b, n_atoms, workspace_bytes):
+    """
+    ValueError for an RMSD matrix the kernels cannot index: a side above 2^31 - 1 entries, or sizes for which the library's
+    ``sc_rmsd_matrix_workspace`` (``workspace_bytes(n_a, n_b or 0, n_atoms)``) answers -1.  ``n_b`` None: self-comparison.
+    """
+    n_a, n_atoms = int(n_a), int(n_atoms)
+    side_b = n_a if n_b is None else int(n_b)
+    if n_a > _MAX_SIDE or side_b > _MAX_SIDE:
+        raise ValueError(f"an RMSD matrix of {n_a} x {side_b} frames has more than 2^31 - 1 entries per side")
+    if workspace_bytes(n_a, 0 if n_b is None else side_b, n_atoms) < 0:
+        raise ValueError(f"an RMSD matrix of {n_a} x {side_b} frames of {n_atoms} atoms is beyond the kernels' index range")
+    return n_a, side_b
+
+
+def _same_weights(a, b):
+    """Whether two ensembles' host weights (None or (N,) arrays) are the same."""
+    if a is None or b is None:
+        return a is None and b is None
+    return a.shape == b.shape and bool(np.array_equal(a, b))
 
 
 def _upload(torch, host, device):
@@ -316,6 +340,58 @@ class Ensemble:
             self._fit(target, out, rmsd)
             return rmsd
 
+    # ---- frame against frame ------------------------------------------------------------------------------------------------
+    def _checked_other(self, other):
+        if other is None:
+            return None
+        if not isinstance(other, Ensemble):
+            raise ValueError(f"other must be an Ensemble, got {type(other).__name__}")
+        if other.n_atoms != self.n_atoms:
+            raise ValueError(f"other has {other.n_atoms} atoms, this ensemble {self.n_atoms}")
+        if not _same_weights(self.weights, other.weights):
+            raise ValueError("other must have the same atom weights as this ensemble")
+        if other.device != self.device:
+            raise ValueError(f"other is on {other.device}, this ensemble on {self.device}")
+        return other
+
+    def rmsd_matrix(self, other=None, fit=True, squared=False):
+        """
+        (M, M) CUDA tensor, the weighted RMSD of every pair of frames after the least-squares superposition of the pair
+        (``fit=False``: of the frames as they are); with ``other``, an :class:`Ensemble` of the same atoms, weights and
+        device, (M, other.n_frames).  ``squared``: the mean-square deviation.  One Gram product over the atoms gives the
+        3 x 3 cross-covariance of every pair, and the RMSD follows from its Horn matrix's largest eigenvalue: no frame is
+        rotated or written, the ensemble is not moved.  The rotation is proper also for a mirror image.
+
+        The self-comparison equals its transpose bit for bit and has an exactly zero diagonal; a frame with a non-finite
+        coordinate gives a NaN row and column (its diagonal entry too) and nothing else; an entry's bits depend on its two
+        frames and the weights alone.  Only enqueues.
+        """
+        other = self._checked_other(other)
+        n_a, n_b = _checked_matrix_shape(self.n_frames, None if other is None else other.n_frames, self.n_atoms,
+                                         self._L.sc_rmsd_matrix_workspace)
+        p = self._p
+        with self.torch.cuda.device(self.device):
+            out = self._empty((n_a, n_b))
+            self.ctx.check(self._L.sc_dev_rmsd_matrix_f64(
+                self.ctx.handle, p(self.frames), n_a, None if other is None else p(other.frames), n_b, self.n_atoms,
+                p(self._w), (1 if fit else 0) | (2 if squared else 0), p(out)))
+        return out
+
+    def medoid(self, fit=True):
+        """
+        0-dim CUDA integer tensor: the index of the frame with the smallest sum of squared RMSD to all other frames, the
+        first one among equals; frames with a non-finite coordinate neither count nor are counted.  Computed with torch
+        from ``rmsd_matrix(squared=True)``; nothing is read back.  (All frames non-finite: 0.)
+        """
+        torch = self.torch
+        msd = self.rmsd_matrix(fit=fit, squared=True)
+        bad = torch.isnan(torch.diagonal(msd))
+        total = torch.where(bad[None, :], torch.zeros_like(msd), msd).sum(dim=1)
+        total = torch.where(bad, torch.full_like(total, float("inf")), total)
+        # the first index of the minimum (argmin's choice among equals is not specified)
+        index = torch.arange(self.n_frames, device=self.device)
+        return torch.where(total == total.min(), index, torch.full_like(index, self.n_frames)).min().clamp(max=self.n_frames - 1)
+
     def deviations(self):
         """(M, N, 3) CUDA tensor, every frame minus the mean frame: displacement vectors for ``overlap()``."""
         return (self.frames - self.mean()[None, :, :]).contiguous()
@@ -361,3 +437,19 @@ def superimpose(fixed, mobile, weights=None, return_transform=False, device=None
     if single:
         fitted, rmsd, rot, trans = fitted[0], float(rmsd[0]), rot[0], trans[0]
     return (fitted, rmsd, (rot, trans)) if return_transform else (fitted, rmsd)
+
+
+def rmsd_matrix(coords, other=None, weights=None, fit=True, squared=False, device=None):
+    """
+    The pairwise RMSD matrix of host arrays on the device, like :func:`superimpose`: ``coords`` (M, N, 3) against itself, or
+    against ``other`` (K, N, 3).  Returns an (M, M) or (M, K) ndarray; see :meth:`Ensemble.rmsd_matrix`.
+    """
+    a = _host_frames(coords)
+    b = None if other is None else _host_frames(other, "other")
+    if b is not None and b.shape[1] != a.shape[1]:
+        raise ValueError(f"other has {b.shape[1]} atoms, coords {a.shape[1]}")
+    w = _checked_weights(weights, a.shape[1])
+    ens = Ensemble(a, weights=w, device=device)
+    out = ens.rmsd_matrix(None if b is None else Ensemble(b, weights=w, device=ens.device.index), fit=fit, squared=squared)
+    ens.ctx.synchronize()
+    return out.cpu().numpy()
