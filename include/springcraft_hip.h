@@ -930,6 +930,9 @@ int sc_dev_potrs_f64(sc_ctx* ctx, const double* d_l, int64_t n, int64_t ld, int6
  * sc_dev_subsystem_follow_f64: d_xe (q, me) <- -L^-T (Y x_s) for the q rows d_xs (q, ms), the environment's motion that
  * follows the system's, with d_l and d_y as the reduction left them.
  *
+ * The first two are the batched entries below for one member whose slot is exactly its environment (batch = 1, env_order =
+ * n_e): the same kernels and launches, so the same bits.
+ *
  * All three only enqueue.  SC_ERR_INVALID_ARG before anything is launched: dim not 1 or 3, n_s or n_e not positive or not
  * summing to n_atoms, a negative k, q < 1, a NULL required pointer. */
 int sc_dev_subsystem_blocks_f64(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs,
@@ -952,10 +955,10 @@ int sc_dev_subsystem_follow_f64(sc_ctx* ctx, const double* d_l, const double* d_
  * the member before.  Member b's row starts begin at entry (atom offset + b).  d_inv_sqrt_mass (batch, n_s) or NULL.
  *
  * sc_dev_vsa_batch_blocks_f64: d_hss (batch, ms, ms), d_hes (batch, me, ms) row-major, d_hee (batch, me, me).  The unpadded
- * region of slot b has the bits sc_dev_subsystem_blocks_f64 gives for that member alone.  The pad of a slot is 1.0 on the pad
- * diagonal of H_ee and exactly 0.0 everywhere else, the pad rows of H_es included: the slot of H_ee is diag(H_ee(b), I).
- * Every entry of every slot is written; no atomics; two calls agree bit for bit.  With env_order = 0, d_hes and d_hee are not
- * touched and may be NULL.
+ * region of slot b has the bits sc_dev_subsystem_blocks_f64 gives for that member alone: it runs this code.  The pad of a
+ * slot is 1.0 on the pad diagonal of H_ee and exactly 0.0 everywhere else, the pad rows of H_es included: the slot of H_ee is
+ * diag(H_ee(b), I).  Every entry of every slot is written; no atomics; two calls agree bit for bit.  With env_order = 0,
+ * d_hes and d_hee are not touched and may be NULL.
  *
  * sc_dev_vsa_batch_reduce_f64: per slot as sc_dev_subsystem_reduce_f64 -- d_hee <- diag(L_b, I), d_hes <- Y (pad rows 0),
  * d_hss <- H_eff, equal to its transpose bit for bit -- in one batched factorisation, one batched substitution and one

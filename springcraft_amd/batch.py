@@ -934,6 +934,73 @@ class _BatchSolver:
         return out
 
 
+class _ReducedSolver(_BatchSolver):
+    """
+    What the reduced-model solvers share (:class:`RTB`, :class:`Subsystem`, :class:`SubsystemBatch`): each builds networks
+    from the device's contact scan and the force field's constants, reduces them to ``self.matrix`` (batch, order, order) of a
+    smaller order than ``m`` and solves that, fully or for an index range.
+    """
+
+    def _device_setup(self, device, batch, n_atoms, dim, order):
+        """The device, the context on torch's current stream and the state of a solver of ``batch`` matrices of ``order``."""
+        import torch
+
+        self.torch = torch
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        self._L = _hip.lib()
+        self._stream = torch.cuda.current_stream(self.device).cuda_stream
+        self.ctx = _hip.Context(self.device.index, stream=self._stream)
+        self.batch, self.dim, self.n_atoms, self.m, self._solve_order = batch, dim, n_atoms, dim * n_atoms, order
+        self.window, self.max_modes, self.counts = None, None, None
+        self.subset, self.nvec = None, order
+        self._first_row, self._common_modes = 0, order
+        self._layout = _UniformLayout(batch, n_atoms, dim)
+        self.matrix = self.w = self.v = None
+        self._plans = {}
+
+    def _scan_network(self, coord, force_field, who=""):
+        """
+        ``(pairs, gamma)`` of one structure: the device scans the contacts, ``force_constant()`` gives the constants of the
+        ordered pairs on the host (as ``compute_hessian`` does for a user-defined force field).  ``who`` opens the message.
+        """
+        from .interaction import _normalised_patch, _pair_list
+
+        if id(force_field) not in self._plans:
+            self._plans[id(force_field)] = device_plan(force_field)[:2]
+        ff_desc, patch = self._plans[id(force_field)]
+        keep = []
+        patch_desc = _normalised_patch(patch, len(coord), keep)
+        pairs, sq_dist = _pair_list(self.ctx, coord, ff_desc, patch_desc, want_sq_dist=True)
+        gamma = np.ascontiguousarray(force_field.force_constant(pairs[:, 0], pairs[:, 1], sq_dist), dtype=np.float64)
+        if gamma.shape != (len(pairs),):
+            raise ValueError(f"{who}force_constant() returned shape {gamma.shape} for {len(pairs)} pairs")
+        return pairs, gamma
+
+    def _need_vectors(self):
+        if self.v is None:
+            raise ValueError("the mode consumers need the modes: call solve() first")
+
+    def _index_subset(self, subset_by_index):
+        """What ``solve(subset_by_index)`` asks for: every mode of the reduced matrix, or the modes lo..hi (inclusive)."""
+        if subset_by_index is None:
+            self.subset, self.nvec, self._first_row = None, self._solve_order, 0
+        else:
+            lo, hi = (int(x) for x in subset_by_index)
+            if not 0 <= lo <= hi < self._solve_order:
+                raise ValueError(f"subset_by_index {tuple(subset_by_index)} outside 0..{self._solve_order - 1}")
+            self.subset, self.nvec, self._first_row = (lo, hi), hi - lo + 1, lo
+
+    def _eigh_reduced(self, vectors):
+        """Eigendecomposes ``self.matrix`` (destroyed) into ``self.w`` (batch, nvec) and ``vectors`` (batch, nvec, order)."""
+        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
+        if self.subset is None:
+            self.ctx.check(self._L.sc_dev_eigh_f64(self.ctx.handle, p(self.matrix), self._solve_order, self.batch, p(self.w),
+                                                   p(vectors)))
+        else:
+            self.ctx.check(self._L.sc_dev_eigh_range_f64(self.ctx.handle, p(self.matrix), self._solve_order, self.batch,
+                                                         self.subset[0], self.subset[1], p(self.w), p(vectors)))
+
+
 class DeviceBatchSolver(_BatchSolver):
     """
     ANM (dim=3) or GNM (dim=1) eigensolves for a batch of equally sized structures whose

@@ -86,8 +86,20 @@ int sc_dev_subsystem_blocks_f64(sc_ctx* ctx, const double* d_coord, int64_t n_at
   if (k > 0 && (!d_pairs || !d_gamma || !d_row_start))
     return sc_set_error(ctx, SC_ERR_INVALID_ARG, "subsystem: pairs, gamma and row starts are required with k > 0");
   SC_HIP(ctx, hipSetDevice(ctx->device));
-  return launch_subsystem_blocks(ctx, d_coord, n_atoms, dim, d_pairs, k, d_gamma, d_row_start, d_group, d_pos, n_s, n_e,
-                                 d_inv_sqrt_mass, d_hss, d_hes, d_hee);
+  if (k == 0) {   // no spring at all: three zero blocks (the row starts may be absent, so the atom kernel must not run)
+    const size_t ms = (size_t)dim * (size_t)n_s, me = (size_t)dim * (size_t)n_e;
+    SC_HIP(ctx, hipMemsetAsync(d_hss, 0, sizeof(double) * ms * ms, ctx->stream));
+    SC_HIP(ctx, hipMemsetAsync(d_hes, 0, sizeof(double) * me * ms, ctx->stream));
+    SC_HIP(ctx, hipMemsetAsync(d_hee, 0, sizeof(double) * me * me, ctx->stream));
+    return SC_OK;
+  }
+  // one structure is a batch of one whose slot is exactly its environment
+  const sc_host::SubMember one{0, n_atoms, 0, k, n_e};
+  sc_host::BatchBlocksBufs B{};
+  SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) { B = sc_host::batch_blocks_layout(a, 1); }));
+  SC_TRY(launch_subsystem_assembly(ctx, B, &one, 1, k, d_coord, dim, d_pairs, d_gamma, d_row_start, d_group, d_pos, n_s, n_e,
+                                   d_inv_sqrt_mass, d_hss, d_hes, d_hee));
+  return sc_stage_end(ctx);
 }
 
 int sc_dev_subsystem_reduce_f64(sc_ctx* ctx, double* d_hss, double* d_hes, double* d_hee, int64_t ms, int64_t me,
@@ -98,9 +110,9 @@ int sc_dev_subsystem_reduce_f64(sc_ctx* ctx, double* d_hss, double* d_hes, doubl
   if (!d_hss || !d_hes || !d_hee || !d_info) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "subsystem: a required pointer is NULL");
   SC_HIP(ctx, hipSetDevice(ctx->device));
   const int outer = potrf_outer_block(me);
-  sc_host::ReduceBufs B{};
-  SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) { B = sc_host::reduce_layout(a, me, ms, outer, potrf_desc_bytes()); }));
-  SC_TRY(launch_subsystem_reduce(ctx, B, d_hss, d_hes, d_hee, ms, me, outer, (long long*)d_info));
+  sc_host::BatchReduceBufs B{};
+  SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) { B = sc_host::batch_reduce_layout(a, me, ms, 1, outer, potrf_desc_bytes()); }));
+  SC_TRY(launch_subsystem_reduction(ctx, B, d_hss, d_hes, d_hee, ms, me, 1, outer, (long long*)d_info));
   return sc_stage_end(ctx);
 }
 
@@ -155,9 +167,9 @@ int sc_dev_vsa_batch_blocks_f64(sc_ctx* ctx, const int64_t* members, int64_t bat
   SC_HIP(ctx, hipSetDevice(ctx->device));
   sc_host::BatchBlocksBufs B{};
   SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) { B = sc_host::batch_blocks_layout(a, batch); }));
-  SC_TRY(launch_subsystem_batch_blocks(ctx, B, mem, batch, sc_host::sub_batch_max_pairs(mem, batch), d_coord, dim, d_pairs,
-                                       d_gamma, d_row_start, d_group, d_pos, n_s, env_order, d_inv_sqrt_mass, d_hss, d_hes,
-                                       d_hee));
+  SC_TRY(launch_subsystem_assembly(ctx, B, mem, batch, sc_host::sub_batch_max_pairs(mem, batch), d_coord, dim, d_pairs,
+                                   d_gamma, d_row_start, d_group, d_pos, n_s, env_order, d_inv_sqrt_mass, d_hss, d_hes,
+                                   d_hee));
   return sc_stage_end(ctx);
 }
 
@@ -178,7 +190,7 @@ int sc_dev_vsa_batch_reduce_f64(sc_ctx* ctx, double* d_hss, double* d_hes, doubl
   const int outer = potrf_outer_block(me);
   sc_host::BatchReduceBufs B{};
   SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) { B = sc_host::batch_reduce_layout(a, me, ms, batch, outer, potrf_desc_bytes()); }));
-  SC_TRY(launch_subsystem_batch_reduce(ctx, B, d_hss, d_hes, d_hee, ms, me, batch, outer, (long long*)d_info));
+  SC_TRY(launch_subsystem_reduction(ctx, B, d_hss, d_hes, d_hee, ms, me, batch, outer, (long long*)d_info));
   return sc_stage_end(ctx);
 }
 

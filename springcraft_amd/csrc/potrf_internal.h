@@ -20,27 +20,23 @@ int launch_trsm(sc_ctx* ctx, const sc_host::TrsmBufs& B, int pass, int kind, con
                 int64_t stride, int64_t batch, double* d_b, int64_t vectors, int64_t ldb, int64_t strideb);
 
 // ---- subsystem.hip -----------------------------------------------------------------------------------------------------------
-// H_ss (ms, ms), H_es (me, ms) row-major and H_ee (me, me) of the partitioned network, ms = dim n_s, me = dim n_e, from the
-// ordered pair list; every entry is written.  d_group (N) int32: 0 system, 1 environment; d_pos (N) int32: the atom's place in
-// its group; d_ism (n_s) or null: 1 / sqrt(mass) of the system atoms.  No atomics, no workspace; enqueue only.
-int launch_subsystem_blocks(sc_ctx* ctx, const double* d_coord, int64_t n_atoms, int dim, const int64_t* d_pairs, int64_t k,
-                            const double* d_gamma, const int64_t* d_row_start, const int32_t* d_group, const int32_t* d_pos,
-                            int64_t n_s, int64_t n_e, const double* d_ism, double* d_hss, double* d_hes, double* d_hee);
-// d_hee <- L (lower, column-major), d_hes <- Y = L^-1 H_es (me, ms) row-major, d_hss <- H_eff = H_ss - Y^T Y, mirrored.
-int launch_subsystem_reduce(sc_ctx* ctx, const sc_host::ReduceBufs& B, double* d_hss, double* d_hes, double* d_hee,
-                            int64_t ms, int64_t me, int outer, long long* d_info);
-// d_xe (q, me) <- -L^-T (Y x_s) for the q rows d_xs (q, ms)
+// One path for one structure and for many: `batch` members with n_s system atoms each and environments of up to env_order
+// atoms, inputs packed back to back (h_members: the host records, staged into B.members); a single structure is a batch of
+// one with env_order = n_e.  ms = dim n_s, me = dim env_order.
+//
+// d_hss (batch, ms, ms), d_hes (batch, me, ms) row-major and d_hee (batch, me, me) of the partitioned networks from the ordered
+// pair lists; a member with a smaller environment gets diag(H_ee, I) and zero pad rows of H_es.  d_group int32: 0 system, 1
+// environment; d_pos int32: the atom's place in its group; d_ism (batch, n_s) or null: 1 / sqrt(mass) of the system atoms.
+// Every entry of every slot is written; no atomics; enqueue only.
+int launch_subsystem_assembly(sc_ctx* ctx, const sc_host::BatchBlocksBufs& B, const sc_host::SubMember* h_members,
+                              int64_t batch, int64_t max_pairs, const double* d_coord, int dim, const int64_t* d_pairs,
+                              const double* d_gamma, const int64_t* d_row_start, const int32_t* d_group,
+                              const int32_t* d_pos, int64_t n_s, int64_t env_order, const double* d_ism, double* d_hss,
+                              double* d_hes, double* d_hee);
+// Every slot: d_hee <- L (lower, column-major), d_hes <- Y = L^-1 H_es (me, ms) row-major, d_hss <- H_eff = H_ss - Y^T Y,
+// mirrored.  One batched factorisation, one batched substitution, one grouped product, one mirror.
+int launch_subsystem_reduction(sc_ctx* ctx, const sc_host::BatchReduceBufs& B, double* d_hss, double* d_hes, double* d_hee,
+                               int64_t ms, int64_t me, int64_t batch, int outer, long long* d_info);
+// One slot: d_xe (q, me) <- -L^-T (Y x_s) for the q rows d_xs (q, ms)
 int launch_subsystem_follow(sc_ctx* ctx, const sc_host::FollowBufs& B, const double* d_l, const double* d_y, int64_t ms,
                             int64_t me, const double* d_xs, int64_t q, double* d_xe);
-// The batch: `batch` members with n_s system atoms each and environments of up to env_order atoms, inputs packed back to back
-// (h_members: the host records, staged into B.members).  d_hss (batch, ms, ms), d_hes (batch, me, ms) row-major and d_hee
-// (batch, me, me), me = dim env_order; a member with a smaller environment gets diag(H_ee, I), zero pad rows of H_es.  d_ism
-// (batch, n_s) or null.  Every entry of every slot is written; no atomics; enqueue only.
-int launch_subsystem_batch_blocks(sc_ctx* ctx, const sc_host::BatchBlocksBufs& B, const sc_host::SubMember* h_members,
-                                  int64_t batch, int64_t max_pairs, const double* d_coord, int dim, const int64_t* d_pairs,
-                                  const double* d_gamma, const int64_t* d_row_start, const int32_t* d_group,
-                                  const int32_t* d_pos, int64_t n_s, int64_t env_order, const double* d_ism, double* d_hss,
-                                  double* d_hes, double* d_hee);
-// launch_subsystem_reduce on every slot: one batched factorisation, one batched substitution, one grouped product, one mirror
-int launch_subsystem_batch_reduce(sc_ctx* ctx, const sc_host::BatchReduceBufs& B, double* d_hss, double* d_hes, double* d_hee,
-                                  int64_t ms, int64_t me, int64_t batch, int outer, long long* d_info);

@@ -123,18 +123,7 @@ static inline size_t potrf_scratch_bytes(int64_t n, int64_t batch, int outer, si
 }
 
 // ---- the subsystem reduction: potrf(H_ee), Y^T = H_se L^-T, H_eff = H_ss - Y^T Y --------------------------------------------
-struct ReduceBufs {
-  PotrfBufs potrf;
-  TrsmBufs trsm;
-  char* desc;   // the record of the H_eff product
-};
-static inline ReduceBufs reduce_layout(Arena& a, int64_t me, int64_t ms, int outer, size_t desc_bytes) {
-  ReduceBufs B{};
-  B.potrf = potrf_layout(a, me, 1, potrf_record_count(potrf_plan(me, outer), 1), desc_bytes);
-  B.trsm = trsm_layout(a, me, 1, ms, 1, desc_bytes);
-  B.desc = a.take<char>(desc_bytes);
-  return B;
-}
+// (the reduction's own scratch is batch_reduce_layout below, for one structure as for many)
 struct FollowBufs {
   TrsmBufs trsm;
   char* desc;
@@ -203,7 +192,8 @@ struct BatchReduceBufs {
   TrsmBufs trsm;
   char* descs;   // (batch) records of the H_eff products
 };
-// me = sub_slot_order(...) > 0
+// me = sub_slot_order(...) > 0.  A single structure reduces with batch = 1: the carve is then potrf_layout(me, 1, ...),
+// trsm_layout(me, 1, ms, 1, ...) and one record, take for take.
 static inline BatchReduceBufs batch_reduce_layout(Arena& a, int64_t me, int64_t ms, int64_t batch, int outer, size_t desc_bytes) {
   BatchReduceBufs B{};
   B.potrf = potrf_layout(a, me, batch, potrf_record_count(potrf_plan(me, outer), batch), desc_bytes);

@@ -13,8 +13,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import _hip, atoms as _atoms
-from .batch import _BatchSolver, _UniformLayout
+from . import atoms as _atoms
+from .batch import _ReducedSolver
 
 __all__ = ["RTB", "rtb_projector", "blocks_of_consecutive"]
 
@@ -109,7 +109,7 @@ def rtb_projector(coord, blocks, masses=None):
     return P, block_of_atom.astype(np.int32), dof, offset
 
 
-class RTB(_BatchSolver):
+class RTB(_ReducedSolver):
     """
     Rotation-translation-block normal modes of one structure on the device.
 
@@ -148,8 +148,7 @@ class RTB(_BatchSolver):
     """
 
     def __init__(self, atoms, force_field, blocks, masses=None, device=None):
-        from .forcefield import device_plan
-        from .interaction import _normalised_patch, _pair_list, _validated_coord
+        from .interaction import _validated_coord
 
         coord = _validated_coord(_atoms.coord(atoms), force_field)
         n = len(coord)
@@ -170,33 +169,16 @@ class RTB(_BatchSolver):
         self.coord = coord
         self.n_atoms, self.n_blocks, self.nr = n, len(self.dof), int(self.offset[-1])
 
-        import torch
-
-        self.torch = torch
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-        self._L = _hip.lib()
-        self._stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.ctx = _hip.Context(self.device.index, stream=self._stream)
-        self.batch, self.dim, self.m = 1, 3, 3 * n
-        self.window, self.max_modes, self.counts = None, None, None
-        self.subset, self.nvec = None, self.nr
-        self._first_row, self._common_modes = 0, self.nr
-        self._layout = _UniformLayout(1, n, 3)
-        self.matrix = self.w = self.v = self._u = None
+        self._device_setup(device, 1, n, 3, self.nr)
+        self._u = None
         self._operator = None
         self._refined = False   # whether w and v are exact eigenpairs: after a refine() that converged
 
-        # contacts from the device scan, constants from the force field on the host (interaction.py:96)
-        ff_desc, patch, _ = device_plan(force_field)
-        keep = []
-        patch_desc = _normalised_patch(patch, n, keep)
-        pairs, sq_dist = _pair_list(self.ctx, coord, ff_desc, patch_desc, want_sq_dist=True)
-        gamma = np.ascontiguousarray(force_field.force_constant(pairs[:, 0], pairs[:, 1], sq_dist), dtype=np.float64)
-        if gamma.shape != (len(pairs),):
-            raise ValueError(f"force_constant() returned shape {gamma.shape} for {len(pairs)} pairs")
+        pairs, gamma = self._scan_network(coord, force_field)
         self.n_pairs = len(pairs)
         self._isolated = np.nonzero(np.bincount(pairs[:, 0], minlength=n) == 0)[0]
 
+        torch = self.torch
         with torch.cuda.device(self.device):
             dev, i64 = self.device, torch.int64
             self._coord = torch.from_numpy(coord).to(dev)
@@ -218,10 +200,6 @@ class RTB(_BatchSolver):
             self._seg_start = torch.cat([seg, torch.tensor([len(key)], dtype=i64, device=dev)])
             self.n_segments = len(seg)
             self._block_start = torch.searchsorted(key, torch.arange(nb + 1, dtype=i64, device=dev) * nb)
-
-    def _need_vectors(self):
-        if self.v is None:
-            raise ValueError("the mode consumers need the modes: call solve() first")
 
     # ---- projection, eigensolve, expansion -------------------------------------------------------------------------
     def _project(self, out):
@@ -254,11 +232,7 @@ class RTB(_BatchSolver):
     def eigh(self):
         """Eigendecomposes ``self.matrix`` (destroyed) and expands the block modes: (w (1, nvec), v (1, nvec, 3N))."""
         p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        if self.subset is None:
-            self.ctx.check(self._L.sc_dev_eigh_f64(self.ctx.handle, p(self.matrix), self.nr, 1, p(self.w), p(self._u)))
-        else:
-            self.ctx.check(self._L.sc_dev_eigh_range_f64(self.ctx.handle, p(self.matrix), self.nr, 1, self.subset[0],
-                                                         self.subset[1], p(self.w), p(self._u)))
+        self._eigh_reduced(self._u)
         self.ctx.check(self._L.sc_dev_rtb_expand_f64(self.ctx.handle, p(self._u), self.nvec, self.nr, p(self._P),
                                                      p(self._boa), p(self._offset), self.n_atoms, p(self.v)))
         return self.w, self.v
@@ -277,13 +251,7 @@ class RTB(_BatchSolver):
             shown = ", ".join(str(a) for a in self._isolated[:10]) + (", ..." if len(self._isolated) > 10 else "")
             raise ValueError(f"{len(self._isolated)} atom(s) without any contact ({shown}): the block network has more "
                              "than six trivial modes")
-        if subset_by_index is None:
-            self.subset, self.nvec, self._first_row = None, self.nr, 0
-        else:
-            lo, hi = (int(x) for x in subset_by_index)
-            if not 0 <= lo <= hi < self.nr:
-                raise ValueError(f"subset_by_index {tuple(subset_by_index)} outside 0..{self.nr - 1}")
-            self.subset, self.nvec, self._first_row = (lo, hi), hi - lo + 1, lo
+        self._index_subset(subset_by_index)
         self.assemble()
         self._refined = False   # (block modes again)
         return self.eigh()

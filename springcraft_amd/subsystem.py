@@ -10,7 +10,8 @@ and the environment follows a system displacement as ``x_e = -H_ee^-1 H_es x_s``
 :func:`subsystem_partition` validates the split on the host (NumPy only); :class:`Subsystem` assembles the three blocks on
 the device straight from the pair list (``csrc/subsystem.hip``: the (dim N, dim N) matrix is never formed), reduces them with
 the device Cholesky solver (``csrc/potrf.hip``), solves H_eff with the device eigensolver and hands the modes to the mode
-consumers it shares with the batch solvers.
+consumers it shares with the batch solvers.  :class:`SubsystemBatch` does that for many structures on a common core in one
+batched pass and holds the one implementation of every step; a :class:`Subsystem` is its one-member case.
 """
 
 import ctypes as C
@@ -18,7 +19,7 @@ import ctypes as C
 import numpy as np
 
 from . import _hip, atoms as _atoms
-from .batch import _BatchSolver, _UniformLayout
+from .batch import _BatchSolver, _ReducedSolver
 
 __all__ = ["Subsystem", "SubsystemBatch", "aligned_core", "subsystem_partition"]
 
@@ -83,235 +84,6 @@ def _partition(n, system, allow_empty_environment):
     return idx, env, group, position
 
 
-class Subsystem(_BatchSolver):
-    """
-    Normal modes of a subsystem inside its relaxing environment, on the device.
-
-    Parameters
-    ----------
-    atoms : AtomArray, shape=(n,) or ndarray, shape=(n,3), dtype=float
-    force_field : ForceField, natoms=n
-        Any force field, patched and tabulated ones included: the device scans the contacts, ``force_constant()`` gives the
-        constants of the ordered pairs on the host, as for :class:`RTB`.  Asymmetric constants raise ValueError.
-    system : ndarray, shape=(n,), dtype=bool or ndarray, shape=(n_s,), dtype=int
-        The system atoms (:func:`subsystem_partition`); every other atom is environment.
-    masses : bool or ndarray, shape=(n,), dtype=float, optional
-        As for :class:`ANM`.  Only the SYSTEM atoms' masses are used: H_eff becomes ``T_s H_eff T_s`` with
-        ``T_s = diag(1 / sqrt(m_s))``.  The environment is massless -- this is the adiabatic approximation of the method: the
-        environment has no inertia and sits in its energy minimum for every position of the system.
-    dim : int, optional
-        3: the ANM Hessian; 1: the GNM Kirchhoff matrix.
-    device : int, optional
-
-    ``effective_hessian()`` is the (m, m) CUDA tensor H_eff, m = dim n_s, equal to its transpose bit for bit; the sums run in
-    a fixed order, so two calls agree bit for bit.  ``solve(subset_by_index=None)`` enqueues assembly, reduction and eigensolve
-    on torch's current stream and leaves ``w`` (1, nvec) and ``v`` (1, nvec, m), rows = unit modes of the system atoms in the
-    order of ``system_index``, the dim (dim + 1) / 2 trivial modes first; ``eigen()`` returns them as host arrays.  Call
-    :meth:`finish` before trusting them on the host: it raises ``np.linalg.LinAlgError`` when H_ee was not positive definite
-    (an environment that can move freely), and the solver can be used again afterwards.
-
-    After a solve every mode consumer of the batch solvers works on the system atoms, with a leading batch axis of one and
-    ``n_atoms = n_s``: ``frequencies``, ``mean_square_fluctuation``, ``bfactor``, ``dcc``, ``prs``,
-    ``generalized_correlation``, ``anisotropic_fluctuation``, ``overlap``, ``collectivity``, ``distance_fluctuation``,
-    ``linear_response``, ``mode_displacement``, ``rmsip(other=...)``; those that need dim 3 refuse dim 1 as they always do.
-
-    ``environment_displacement(rows=None)`` is the motion of the environment that follows the solved modes (or the q given
-    rows), (nvec or q, dim n_e); ``full_modes()`` puts both together in the original atom order, (nvec, dim N).  These rows are
-    NOT normalised: the system part of a row is the unit mode (in mass-weighted coordinates with ``masses``), the
-    environment part is what follows it.  With H the full matrix, ``H x`` of such a row vanishes at the environment atoms and
-    equals ``w_k v_k`` at the system atoms.
-
-    ``system_index`` (n_s,), ``environment_index`` (n_e,), ``group`` and ``position`` (n,) are the host arrays of
-    :func:`subsystem_partition`.
-    """
-
-    def __init__(self, atoms, force_field, system, masses=None, dim=3, device=None):
-        from .forcefield import device_plan
-        from .interaction import _normalised_patch, _pair_list, _validated_coord
-        from .pair_operator import _checked_dim, _model_masses, check_symmetric, pair_row_start
-
-        dim = _checked_dim(dim)
-        coord = _validated_coord(_atoms.coord(atoms), force_field)
-        n = len(coord)
-        self.system_index, self.environment_index, self.group, self.position = subsystem_partition(n, system)
-        mass = _model_masses(atoms, masses, n)
-        self.masses = mass
-        self.coord = coord
-        self.n_total, self.n_atoms, self.n_env = n, len(self.system_index), len(self.environment_index)
-
-        import torch
-
-        self.torch = torch
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-        self._L = _hip.lib()
-        self._stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.ctx = _hip.Context(self.device.index, stream=self._stream)
-        self.batch, self.dim, self.m, self.m_env = 1, dim, dim * self.n_atoms, dim * self.n_env
-        self.window, self.max_modes, self.counts = None, None, None
-        self.subset, self.nvec = None, self.m
-        self._first_row, self._common_modes = 0, self.m
-        self._layout = _UniformLayout(1, self.n_atoms, dim)
-        self.matrix = self.w = self.v = None
-        self._hes = self._hee = self._info = None
-        self._reduced = False
-
-        ff_desc, patch, _ = device_plan(force_field)
-        keep = []
-        patch_desc = _normalised_patch(patch, n, keep)
-        pairs, sq_dist = _pair_list(self.ctx, coord, ff_desc, patch_desc, want_sq_dist=True)
-        gamma = np.ascontiguousarray(force_field.force_constant(pairs[:, 0], pairs[:, 1], sq_dist), dtype=np.float64)
-        if gamma.shape != (len(pairs),):
-            raise ValueError(f"force_constant() returned shape {gamma.shape} for {len(pairs)} pairs")
-        check_symmetric(pairs, gamma, n)
-        self.n_pairs = len(pairs)
-        contacts = np.bincount(pairs[:, 0], minlength=n)
-        self._isolated = self.environment_index[contacts[self.environment_index] == 0]
-        self._coupled = bool(np.any(self.group[pairs[:, 0]] != self.group[pairs[:, 1]]))
-
-        with torch.cuda.device(self.device):
-            dev = self.device
-            self._coord = torch.from_numpy(np.array(coord)).to(dev)   # (a copy: the caller's array may be read-only)
-            self._pairs = torch.from_numpy(pairs).to(dev)
-            self._gamma = torch.from_numpy(gamma).to(dev)
-            self._row_start = torch.from_numpy(pair_row_start(pairs, n)).to(dev)
-            self._group = torch.from_numpy(self.group).to(dev)
-            self._pos = torch.from_numpy(self.position).to(dev)
-            self.inv_sqrt_mass = (None if mass is None else
-                                  torch.from_numpy(1.0 / np.sqrt(mass[self.system_index])).to(dev)[None, :].contiguous())
-
-    def _need_vectors(self):
-        if self.v is None:
-            raise ValueError("the mode consumers need the modes: call solve() first")
-
-    def _check_network(self):
-        if len(self._isolated):
-            shown = ", ".join(str(a) for a in self._isolated[:10]) + (", ..." if len(self._isolated) > 10 else "")
-            raise ValueError(f"{len(self._isolated)} environment atom(s) without any contact ({shown}): H_ee is singular")
-        if not self._coupled:
-            raise ValueError("the system shares no spring with the environment: there is nothing to reduce, and the "
-                             "environment's own rigid-body motions make H_ee singular")
-
-    # ---- assembly, reduction, eigensolve ------------------------------------------------------------------------------------
-    def blocks(self):
-        """``(H_ss (m, m), H_es (m_env, m), H_ee (m_env, m_env))`` as new CUDA tensors, every entry written; only enqueues."""
-        out = self._empty((self.m, self.m)), self._empty((self.m_env, self.m)), self._empty((self.m_env, self.m_env))
-        self._blocks_into(*out)
-        return out
-
-    def _blocks_into(self, hss, hes, hee):
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
-        self.ctx.check(self._L.sc_dev_subsystem_blocks_f64(
-            self.ctx.handle, p(self._coord), self.n_total, self.dim, p(self._pairs), self.n_pairs, p(self._gamma),
-            p(self._row_start), p(self._group), p(self._pos), self.n_atoms, self.n_env, p(self.inv_sqrt_mass), p(hss), p(hes),
-            p(hee)))
-
-    def _reduce_into(self, hss):
-        """``hss`` <- H_eff; ``self._hee`` <- L, ``self._hes`` <- Y = L^-1 H_es, kept for the follow motion."""
-        self._check_network()
-        if self._hes is None:
-            self._hes, self._hee = self._empty((self.m_env, self.m)), self._empty((self.m_env, self.m_env))
-            self._info = self.torch.zeros((1,), dtype=self.torch.int64, device=self.device)
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        self._blocks_into(hss, self._hes, self._hee)
-        self.ctx.check(self._L.sc_dev_subsystem_reduce_f64(self.ctx.handle, p(hss), p(self._hes), p(self._hee), self.m,
-                                                           self.m_env, p(self._info)))
-        self._reduced = True
-        return hss
-
-    def effective_hessian(self):
-        """(m, m) CUDA tensor ``H_ss - H_se H_ee^-1 H_es`` (``T_s ... T_s`` with masses), every entry written; only enqueues."""
-        return self._reduce_into(self._empty((self.m, self.m)))
-
-    def _allocate(self, m, nvec, want_vectors=True):
-        if self.matrix is None:
-            self.matrix = self._empty((1, m, m))
-        if self.w is None or self.w.shape[1] != nvec:
-            self.w = self._empty((1, nvec))
-            self.v = self._empty((1, nvec, m))
-
-    def assemble(self):
-        """``self.matrix`` (1, m, m) <- H_eff."""
-        self._allocate(self.m, self.nvec)
-        self._reduce_into(self.matrix[0])
-        return self.matrix
-
-    def eigh(self):
-        """Eigendecomposes ``self.matrix`` (destroyed): (w (1, nvec), v (1, nvec, m))."""
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        if self.subset is None:
-            self.ctx.check(self._L.sc_dev_eigh_f64(self.ctx.handle, p(self.matrix), self.m, 1, p(self.w), p(self.v)))
-        else:
-            self.ctx.check(self._L.sc_dev_eigh_range_f64(self.ctx.handle, p(self.matrix), self.m, 1, self.subset[0],
-                                                         self.subset[1], p(self.w), p(self.v)))
-        return self.w, self.v
-
-    def solve(self, subset_by_index=None):
-        """
-        Assembly, reduction and eigensolve, all enqueued on the device: ``w`` (1, nvec), ``v`` (1, nvec, m).
-        ``subset_by_index=(lo, hi)``: only the modes lo..hi (inclusive, ascending) through the partial-spectrum solver; row r
-        is then mode ``lo + r``.
-
-        An environment atom without any contact, or a system that shares no spring with the environment, makes H_ee
-        singular: ValueError before anything is enqueued.  (A network of several connected parts is the caller's to avoid,
-        as for an :class:`ANM`; a factorisation that fails anyway raises LinAlgError in :meth:`finish`.)
-        """
-        self._check_network()
-        if subset_by_index is None:
-            self.subset, self.nvec, self._first_row = None, self.m, 0
-        else:
-            lo, hi = (int(x) for x in subset_by_index)
-            if not 0 <= lo <= hi < self.m:
-                raise ValueError(f"subset_by_index {tuple(subset_by_index)} outside 0..{self.m - 1}")
-            self.subset, self.nvec, self._first_row = (lo, hi), hi - lo + 1, lo
-        self.assemble()
-        return self.eigh()
-
-    def eigen(self, subset_by_index=None):
-        """
-        Eigenvalues (ascending, shape (nvec,)) and modes (rows, shape (nvec, m)) of H_eff as host arrays, like
-        ``ANM.eigen()``: the first dim (dim + 1) / 2 belong to rigid-body motions of the system with its environment.
-        """
-        self.solve(subset_by_index)
-        w, v = self.finish()
-        return w[0].cpu().numpy(), v[0].cpu().numpy()
-
-    # ---- the environment's motion --------------------------------------------------------------------------------------------
-    def environment_displacement(self, rows=None):
-        """
-        ``x_e = -H_ee^-1 H_es x_s`` for the solved modes (``rows=None``: (nvec, m_env)) or for the q rows of a contiguous
-        CUDA float64 tensor (q, m) of system displacements (in mass-weighted coordinates with ``masses``).  Only enqueues.
-        """
-        if not self._reduced:
-            raise ValueError("the follow motion needs the reduction: call solve() or effective_hessian() first")
-        if rows is None:
-            self._need_vectors()
-            rows = self.v[0]
-        else:
-            q = rows.shape[0] if getattr(rows, "ndim", 0) == 2 else -1
-            self._device_f64(rows, (q, self.m), "rows")
-            if q < 1:
-                raise ValueError(f"Expected rows of shape (q, {self.m}) with q >= 1, got {tuple(rows.shape)}")
-        q = rows.shape[0]
-        out = self._empty((q, self.m_env))
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        self.ctx.check(self._L.sc_dev_subsystem_follow_f64(self.ctx.handle, p(self._hee), p(self._hes), self.m, self.m_env,
-                                                           p(rows), q, p(out)))
-        return out
-
-    def full_modes(self):
-        """
-        (nvec, dim N) CUDA tensor: the solved modes at the system atoms and the follow motion at the environment atoms, in
-        the original atom order.  NOT normalised (see the class docstring).
-        """
-        self._need_vectors()
-        torch, d = self.torch, self.dim
-        xe = self.environment_displacement()
-        out = self._empty((self.nvec, self.n_total, d))
-        out[:, torch.from_numpy(self.system_index).to(self.device)] = self.v[0].view(self.nvec, self.n_atoms, d)
-        out[:, torch.from_numpy(self.environment_index).to(self.device)] = xe.view(self.nvec, self.n_env, d)
-        return out.view(self.nvec, d * self.n_total)
-
-
 def aligned_core(alignment):
     """
     The common core of aligned structures (NumPy only).
@@ -347,7 +119,7 @@ def aligned_core(alignment):
     return columns, [np.ascontiguousarray(row[columns]) for row in a]
 
 
-class SubsystemBatch(_BatchSolver):
+class SubsystemBatch(_ReducedSolver):
     """
     Ensemble NMA on a common core (Bio3D's ``nma.pdbs(rm.gaps=TRUE)``, ProDy's ``reduceModel`` over an ensemble): every
     member keeps ALL its atoms in its own network, each network is reduced to the aligned positions all members share by
@@ -361,8 +133,9 @@ class SubsystemBatch(_BatchSolver):
     structures : list of B ndarray, shape=(n_b, 3), or AtomArray
         Sizes may differ.
     force_fields : ForceField or list of B ForceField
-        One for all members (only if it is not bound to particular atoms) or one per member; any force field, as for
-        :class:`Subsystem`.  Asymmetric constants raise ValueError naming the member.
+        One for all members (only if it is not bound to particular atoms) or one per member; any force field, patched and
+        tabulated ones included: the device scans the contacts, ``force_constant()`` gives the constants of the ordered
+        pairs on the host, as for :class:`RTB`.  Asymmetric constants raise ValueError naming the member.
     systems : list of B ndarray, shape=(n_s,), dtype=int
         The core atoms of every member, all of one length; column c of every member is the same aligned position
         (:func:`aligned_core`).  A member may be exactly its core (``n_e = 0``).
@@ -390,9 +163,11 @@ class SubsystemBatch(_BatchSolver):
     members' results are valid, and the solver can be used again.
     """
 
+    _who = "member {}: "              # opens a message about member b (a Subsystem has one member and does not name it)
+    _allow_empty_environment = True   # a member may be exactly its core
+
     def __init__(self, structures, force_fields, systems, masses=None, dim=3, fit=True, env_order=None, device=None):
-        from .forcefield import device_plan
-        from .interaction import _normalised_patch, _pair_list, _validated_coord
+        from .interaction import _validated_coord
         from .pair_operator import _checked_dim, _model_masses, check_symmetric, pair_row_start
 
         dim = _checked_dim(dim)
@@ -413,9 +188,9 @@ class SubsystemBatch(_BatchSolver):
         for b in range(nb):
             try:
                 coords.append(_validated_coord(_atoms.coord(structures[b]), force_fields[b]))
-                parts.append(_partition(len(coords[b]), systems[b], True))
+                parts.append(_partition(len(coords[b]), systems[b], self._allow_empty_environment))
             except ValueError as e:
-                raise ValueError(f"member {b}: {e}") from None
+                raise ValueError(f"{self._who.format(b)}{e}") from None
         n_s = len(parts[0][0])
         for b in range(nb):
             if len(parts[b][0]) != n_s:
@@ -424,16 +199,19 @@ class SubsystemBatch(_BatchSolver):
         fit = bool(fit) and dim == 3
         if fit and n_s < 3:
             raise ValueError(f"fit=True needs at least 3 system atoms to superimpose, got {n_s}")
-        self.system_index = [p[0] for p in parts]
-        self.environment_index = [p[1] for p in parts]
-        self.n_env = [len(p[1]) for p in parts]
+        # per member, for every step below; the public attributes of the same names are these lists
+        self._parts = parts
+        self._system_index = [p[0] for p in parts]
+        self._environment_index = [p[1] for p in parts]
+        self._n_env = [len(p[1]) for p in parts]
+        self.system_index, self.environment_index, self.n_env = self._system_index, self._environment_index, self._n_env
         self.sizes = [len(c) for c in coords]
-        need = max(self.n_env)
+        need = max(self._n_env)
         if env_order is None:
             env_order = need
         env_order = int(env_order)
         if env_order < need:
-            member = int(np.argmax(self.n_env))
+            member = int(np.argmax(self._n_env))
             raise ValueError(f"env_order = {env_order} is below the {need} environment atoms of member {member}")
         if masses is None or masses is False:
             mass = [None] * nb
@@ -443,22 +221,11 @@ class SubsystemBatch(_BatchSolver):
             mass = [_model_masses(structures[b], masses[b], self.sizes[b]) for b in range(nb)]
         self.masses = mass
 
-        import torch
-
-        self.torch = torch
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-        self._L = _hip.lib()
-        self._stream = torch.cuda.current_stream(self.device).cuda_stream
-        self.ctx = _hip.Context(self.device.index, stream=self._stream)
-        self.batch, self.dim, self.n_atoms, self.env_order = nb, dim, n_s, env_order
-        self.m, self.m_env = dim * n_s, dim * env_order
-        self.window, self.max_modes, self.counts = None, None, None
-        self.subset, self.nvec = None, self.m
-        self._first_row, self._common_modes = 0, self.m
-        self._layout = _UniformLayout(nb, n_s, dim)
-        self.matrix = self.w = self.v = None
+        self._device_setup(device, nb, n_s, dim, dim * n_s)
+        self.env_order, self.m_env = env_order, dim * env_order
         self._hes = self._hee = self._info = None
         self._reduced = False
+        torch = self.torch
 
         self.transforms = self.fit_rmsd = None
         if fit:
@@ -467,23 +234,13 @@ class SubsystemBatch(_BatchSolver):
 
         # the networks: the device scans the contacts, the force fields give the constants on the host, member by member
         pairs_all, gamma_all, starts, self._isolated, self._uncoupled = [], [], [], {}, []
-        plans = {}
         for b, (coord, ff) in enumerate(zip(coords, force_fields)):
-            n = self.sizes[b]
-            if id(ff) not in plans:
-                ff_desc, patch, _ = device_plan(ff)
-                plans[id(ff)] = (ff_desc, patch)
-            ff_desc, patch = plans[id(ff)]
-            keep = []
-            patch_desc = _normalised_patch(patch, n, keep)
-            pairs, sq_dist = _pair_list(self.ctx, coord, ff_desc, patch_desc, want_sq_dist=True)
-            gamma = np.ascontiguousarray(ff.force_constant(pairs[:, 0], pairs[:, 1], sq_dist), dtype=np.float64)
-            if gamma.shape != (len(pairs),):
-                raise ValueError(f"member {b}: force_constant() returned shape {gamma.shape} for {len(pairs)} pairs")
+            n, who = self.sizes[b], self._who.format(b)
+            pairs, gamma = self._scan_network(coord, ff, who)
             try:
                 check_symmetric(pairs, gamma, n)
             except ValueError as e:
-                raise ValueError(f"member {b}: {e}") from None
+                raise ValueError(f"{who}{e}") from None
             group, env = parts[b][2], parts[b][1]
             contacts = np.bincount(pairs[:, 0], minlength=n)
             lonely = env[contacts[env] == 0]
@@ -499,14 +256,14 @@ class SubsystemBatch(_BatchSolver):
         pair0 = np.concatenate([[0], np.cumsum(self.n_pairs)]).astype(np.int64)
         self.offsets = atom0
         # (batch, 5) int64: atom offset, atom count, pair offset, pair count, n_e -- the library stages it at every call
-        self._members = np.ascontiguousarray(np.stack([atom0[:-1], self.sizes, pair0[:-1], self.n_pairs, self.n_env], axis=1),
+        self._members = np.ascontiguousarray(np.stack([atom0[:-1], self.sizes, pair0[:-1], self.n_pairs, self._n_env], axis=1),
                                              dtype=np.int64)
         ism = None
         if any(mb is not None for mb in mass):
             ism = np.ones((nb, n_s))
             for b, mb in enumerate(mass):
                 if mb is not None:
-                    ism[b] = 1.0 / np.sqrt(mb[self.system_index[b]])
+                    ism[b] = 1.0 / np.sqrt(mb[self._system_index[b]])
         with torch.cuda.device(self.device):
             dev = self.device
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
@@ -517,12 +274,12 @@ class SubsystemBatch(_BatchSolver):
             self._group = up(np.concatenate([p[2] for p in parts]))
             self._pos = up(np.concatenate([p[3] for p in parts]))
             self.inv_sqrt_mass = None if ism is None else up(ism)
-            self.core_coord = up(np.stack([c[s] for c, s in zip(coords, self.system_index)]))
+            self.core_coord = up(np.stack([c[s] for c, s in zip(coords, self._system_index)]))
 
     def _fit_members(self, coords):
         from .ensemble import Ensemble, superimpose
 
-        cores = np.stack([c[s] for c, s in zip(coords, self.system_index)])
+        cores = np.stack([c[s] for c, s in zip(coords, self._system_index)])
         ens = Ensemble(cores, device=self.device.index)
         ens.superpose()
         mean = ens.mean().cpu().numpy()
@@ -530,17 +287,14 @@ class SubsystemBatch(_BatchSolver):
         self.transforms, self.fit_rmsd = (rot, trans), rmsd
         return [np.ascontiguousarray(c @ rot[b].T + trans[b]) for b, c in enumerate(coords)]
 
-    def _need_vectors(self):
-        if self.v is None:
-            raise ValueError("the mode consumers need the modes: call solve() first")
-
     def _check_network(self):
         for b, lonely in self._isolated.items():
             shown = ", ".join(str(a) for a in lonely[:10]) + (", ..." if len(lonely) > 10 else "")
-            raise ValueError(f"member {b}: {len(lonely)} environment atom(s) without any contact ({shown}): H_ee is singular")
+            raise ValueError(f"{self._who.format(b)}{len(lonely)} environment atom(s) without any contact ({shown}): H_ee is "
+                             "singular")
         if self._uncoupled:
-            raise ValueError(f"member {self._uncoupled[0]}: the system shares no spring with the environment: there is nothing "
-                             "to reduce, and the environment's own rigid-body motions make H_ee singular")
+            raise ValueError(f"{self._who.format(self._uncoupled[0])}the system shares no spring with the environment: there "
+                             "is nothing to reduce, and the environment's own rigid-body motions make H_ee singular")
 
     def _check_member(self, member):
         b = int(member)
@@ -606,30 +360,22 @@ class SubsystemBatch(_BatchSolver):
 
     def eigh(self):
         """Eigendecomposes ``self.matrix`` (destroyed): (w (B, nvec), v (B, nvec, m))."""
-        p = lambda t: C.c_void_p(t.data_ptr())   # noqa: E731
-        if self.subset is None:
-            self.ctx.check(self._L.sc_dev_eigh_f64(self.ctx.handle, p(self.matrix), self.m, self.batch, p(self.w), p(self.v)))
-        else:
-            self.ctx.check(self._L.sc_dev_eigh_range_f64(self.ctx.handle, p(self.matrix), self.m, self.batch, self.subset[0],
-                                                         self.subset[1], p(self.w), p(self.v)))
+        self._eigh_reduced(self.v)
         return self.w, self.v
 
     def solve(self, subset_by_index=None):
         """
         Assembly, reduction and eigensolve of all members, enqueued on the device: ``w`` (B, nvec), ``v`` (B, nvec, m).
-        ``subset_by_index=(lo, hi)``: only the modes lo..hi of every member; row r is then mode ``lo + r``.
+        ``subset_by_index=(lo, hi)``: only the modes lo..hi (inclusive, ascending) of every member through the
+        partial-spectrum solver; row r is then mode ``lo + r``.
 
         ValueError naming the member before anything is enqueued: an environment atom without any contact, or a member with
-        an environment whose system shares no spring with it.
+        an environment whose system shares no spring with it; either makes H_ee singular.  (A network of several connected
+        parts is the caller's to avoid, as for an :class:`ANM`; a factorisation that fails anyway raises LinAlgError in
+        :meth:`finish`.)
         """
         self._check_network()
-        if subset_by_index is None:
-            self.subset, self.nvec, self._first_row = None, self.m, 0
-        else:
-            lo, hi = (int(x) for x in subset_by_index)
-            if not 0 <= lo <= hi < self.m:
-                raise ValueError(f"subset_by_index {tuple(subset_by_index)} outside 0..{self.m - 1}")
-            self.subset, self.nvec, self._first_row = (lo, hi), hi - lo + 1, lo
+        self._index_subset(subset_by_index)
         self.assemble()
         return self.eigh()
 
@@ -660,9 +406,12 @@ class SubsystemBatch(_BatchSolver):
     def environment_displacement(self, member, rows=None):
         """
         ``x_e = -H_ee^-1 H_es x_s`` of one member for its solved modes (``rows=None``: (nvec, dim * n_env[member])) or for
-        the q rows of a contiguous CUDA float64 tensor (q, m).  A member without environment gives an empty (q, 0) tensor.
+        the q rows of a contiguous CUDA float64 tensor (q, m) of system displacements (in mass-weighted coordinates with
+        ``masses``).  A member without environment gives an empty (q, 0) tensor.  Only enqueues.
         """
-        b = self._check_member(member)
+        return self._follow(self._check_member(member), rows)
+
+    def _follow(self, b, rows):
         if not self._reduced:
             raise ValueError("the follow motion needs the reduction: call solve() or effective_hessian() first")
         if rows is None:
@@ -674,7 +423,7 @@ class SubsystemBatch(_BatchSolver):
             if q < 1:
                 raise ValueError(f"Expected rows of shape (q, {self.m}) with q >= 1, got {tuple(rows.shape)}")
         q = rows.shape[0]
-        own = self.dim * self.n_env[b]
+        own = self.dim * self._n_env[b]
         if own == 0:
             return self._empty((q, 0))
         out = self._empty((q, self.m_env))
@@ -688,12 +437,105 @@ class SubsystemBatch(_BatchSolver):
         (nvec, dim * n_b) CUDA tensor of one member: its solved modes at the core atoms and the follow motion at its
         environment atoms, in the member's atom order.  NOT normalised (see :class:`Subsystem`).
         """
-        b = self._check_member(member)
+        return self._full_modes(self._check_member(member))
+
+    def _full_modes(self, b):
         self._need_vectors()
         torch, d, n = self.torch, self.dim, self.sizes[b]
-        xe = self.environment_displacement(b)
+        xe = self._follow(b, None)
         out = self._empty((self.nvec, n, d))
-        out[:, torch.from_numpy(self.system_index[b]).to(self.device)] = self.v[b].view(self.nvec, self.n_atoms, d)
-        if self.n_env[b]:
-            out[:, torch.from_numpy(self.environment_index[b]).to(self.device)] = xe.view(self.nvec, self.n_env[b], d)
+        out[:, torch.from_numpy(self._system_index[b]).to(self.device)] = self.v[b].view(self.nvec, self.n_atoms, d)
+        if self._n_env[b]:
+            out[:, torch.from_numpy(self._environment_index[b]).to(self.device)] = xe.view(self.nvec, self._n_env[b], d)
         return out.view(self.nvec, d * n)
+
+
+class Subsystem(SubsystemBatch):
+    """
+    Normal modes of a subsystem inside its relaxing environment, on the device: the one-member case of
+    :class:`SubsystemBatch`, without a fit and with a slot of exactly the environment's order, so every step is that class's.
+
+    Parameters
+    ----------
+    atoms : AtomArray, shape=(n,) or ndarray, shape=(n,3), dtype=float
+    force_field : ForceField, natoms=n
+        Any force field, patched and tabulated ones included: the device scans the contacts, ``force_constant()`` gives the
+        constants of the ordered pairs on the host, as for :class:`RTB`.  Asymmetric constants raise ValueError.
+    system : ndarray, shape=(n,), dtype=bool or ndarray, shape=(n_s,), dtype=int
+        The system atoms (:func:`subsystem_partition`); every other atom is environment.
+    masses : bool or ndarray, shape=(n,), dtype=float, optional
+        As for :class:`ANM`.  Only the SYSTEM atoms' masses are used: H_eff becomes ``T_s H_eff T_s`` with
+        ``T_s = diag(1 / sqrt(m_s))``.  The environment is massless -- this is the adiabatic approximation of the method: the
+        environment has no inertia and sits in its energy minimum for every position of the system.
+    dim : int, optional
+        3: the ANM Hessian; 1: the GNM Kirchhoff matrix.
+    device : int, optional
+
+    ``effective_hessian()`` is the (m, m) CUDA tensor H_eff, m = dim n_s, equal to its transpose bit for bit; the sums run in
+    a fixed order, so two calls agree bit for bit.  ``solve(subset_by_index=None)`` enqueues assembly, reduction and eigensolve
+    on torch's current stream and leaves ``w`` (1, nvec) and ``v`` (1, nvec, m), rows = unit modes of the system atoms in the
+    order of ``system_index``, the dim (dim + 1) / 2 trivial modes first; ``eigen()`` returns them as host arrays.  Call
+    :meth:`finish` before trusting them on the host: it raises ``np.linalg.LinAlgError`` when H_ee was not positive definite
+    (an environment that can move freely), and the solver can be used again afterwards.
+
+    After a solve every mode consumer of the batch solvers works on the system atoms, with a leading batch axis of one and
+    ``n_atoms = n_s``: ``frequencies``, ``mean_square_fluctuation``, ``bfactor``, ``dcc``, ``prs``,
+    ``generalized_correlation``, ``anisotropic_fluctuation``, ``overlap``, ``collectivity``, ``distance_fluctuation``,
+    ``linear_response``, ``mode_displacement``, ``rmsip(other=...)``; those that need dim 3 refuse dim 1 as they always do.
+
+    ``environment_displacement(rows=None)`` is the motion of the environment that follows the solved modes (or the q given
+    rows), (nvec or q, dim n_e); ``full_modes()`` puts both together in the original atom order, (nvec, dim N).  These rows are
+    NOT normalised: the system part of a row is the unit mode (in mass-weighted coordinates with ``masses``), the
+    environment part is what follows it.  With H the full matrix, ``H x`` of such a row vanishes at the environment atoms and
+    equals ``w_k v_k`` at the system atoms.
+
+    ``system_index`` (n_s,), ``environment_index`` (n_e,), ``group`` and ``position`` (n,) are the host arrays of
+    :func:`subsystem_partition`.
+    """
+
+    _who = ""
+    _allow_empty_environment = False   # then there is nothing to reduce: use ANM / GNM
+
+    def __init__(self, atoms, force_field, system, masses=None, dim=3, device=None):
+        if masses is not None and masses is not True and masses is not False:
+            masses = [masses]
+        super().__init__([atoms], [force_field], [system], masses=masses, dim=dim, fit=False, device=device)
+        # the public face: one structure's arrays and counts, not lists per member
+        self.system_index, self.environment_index, self.group, self.position = self._parts[0]
+        self.coord, self.masses = self.fitted_coord[0], self.masses[0]
+        self.n_total, self.n_env, self.n_pairs = self.sizes[0], self._n_env[0], self.n_pairs[0]
+
+    def blocks(self):
+        """``(H_ss (m, m), H_es (m_env, m), H_ee (m_env, m_env))`` as new CUDA tensors, every entry written; only enqueues."""
+        return tuple(t[0] for t in super().blocks())
+
+    def effective_hessian(self):
+        """(m, m) CUDA tensor ``H_ss - H_se H_ee^-1 H_es`` (``T_s ... T_s`` with masses), every entry written; only enqueues."""
+        return super().effective_hessian()[0]
+
+    def eigen(self, subset_by_index=None):
+        """
+        Eigenvalues (ascending, shape (nvec,)) and modes (rows, shape (nvec, m)) of H_eff as host arrays, like
+        ``ANM.eigen()``: the first dim (dim + 1) / 2 belong to rigid-body motions of the system with its environment.
+        """
+        w, v = super().eigen(subset_by_index)
+        return w[0], v[0]
+
+    #: waits for what was enqueued and raises the context's own ``np.linalg.LinAlgError`` when H_ee was not positive
+    #: definite (there is no other member to name); reported once
+    finish = _BatchSolver.finish
+
+    def environment_displacement(self, rows=None):
+        """
+        ``x_e = -H_ee^-1 H_es x_s`` for the solved modes (``rows=None``: (nvec, m_env)) or for the q rows of a contiguous
+        CUDA float64 tensor (q, m) of system displacements (in mass-weighted coordinates with ``masses``).  Only enqueues.
+        """
+        return self._follow(0, rows)
+
+    def full_modes(self):
+        """
+        (nvec, dim N) CUDA tensor: the solved modes at the system atoms and the follow motion at the environment atoms, in
+        the original atom order.  NOT normalised (see the class docstring).
+        """
+        return self._full_modes(0)
+

@@ -123,13 +123,18 @@ int main() {
         }
     }
   {
+    // one structure reduces on the batched layout with batch = 1
     Arena m;
-    reduce_layout(m, 387, 63, 128, desc);
+    batch_reduce_layout(m, 387, 63, 1, 128, desc);
+    // the bytes of the single solver's own layout for (me 387, ms 63, outer 128, 136-byte records) before it was merged
+    // into this one, computed once from that revision's potrf_policy.h on the host: the merged carve is the same takes
+    CHECK(m.bytes() == 693128);
     std::vector<char> block(m.bytes());
     Arena c(block.data(), block.size());
-    const ReduceBufs R = reduce_layout(c, 387, 63, 128, desc);
-    CHECK(!c.overrun() && R.potrf.dinv && R.trsm.tmp && R.desc && R.desc + desc <= block.data() + block.size());
-    CHECK(R.potrf.descs < (char*)R.trsm.dinv && R.trsm.descs < R.desc);
+    const BatchReduceBufs R = batch_reduce_layout(c, 387, 63, 1, 128, desc);
+    CHECK(!c.overrun() && c.bytes() == m.bytes());
+    CHECK(!c.overrun() && R.potrf.dinv && R.trsm.tmp && R.descs && R.descs + desc <= block.data() + block.size());
+    CHECK(R.potrf.descs < (char*)R.trsm.dinv && R.trsm.descs < R.descs);
     Arena fm;
     follow_layout(fm, 387, 5, desc);
     std::vector<char> fb(fm.bytes());

@@ -239,7 +239,52 @@ def test_model_methods_build_the_same_solver(sc):
     assert g.dim == 1 and g.m == len(system)
 
 
-# ---- 4. refusals and failures -------------------------------------------------------------------------------------------------
+# ---- 4. the single-structure C entries, which the Python solver no longer calls -------------------------------------------------
+@pytest.mark.parametrize("with_masses", [False, True])
+@pytest.mark.parametrize("dim", [3, 1])
+def test_single_entries_equal_the_solver_bit_for_bit(sc, torch, dim, with_masses):
+    """
+    sc_dev_subsystem_blocks_f64 / _reduce_f64 / _follow_f64 called directly on a solver's own device inputs: dim 3 on case 1
+    (H_ee of order 66) and dim 1 on the second dim-1 case (order 65), so the factorisation crosses a diagonal-block boundary.
+    """
+    import ctypes as C
+
+    from springcraft_amd import _hip
+
+    coord, system, ff = sm.case_inputs(1) if dim == 3 else sm.dim1_inputs(1)
+    masses = sm.masses_of(len(coord)) if with_masses else None
+    sub = sc.Subsystem(coord, sm.package_ff(sc, ff), system, masses=masses, dim=dim)
+    m, me = sub.m, sub.m_env
+    assert me > 64 and (sub.inv_sqrt_mass is not None) == with_masses
+    L, h = sub._L, sub.ctx.handle
+    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+    hss, hes, hee = sub._empty((m, m)), sub._empty((me, m)), sub._empty((me, me))
+    info = torch.ones(1, dtype=torch.int64, device="cuda")
+
+    def blocks(n_atoms=sub.n_total, n_s=sub.n_atoms, n_e=sub.n_env):
+        return L.sc_dev_subsystem_blocks_f64(h, p(sub._coord), n_atoms, dim, p(sub._pairs), sub.n_pairs, p(sub._gamma),
+                                             p(sub._row_start), p(sub._group), p(sub._pos), n_s, n_e, p(sub.inv_sqrt_mass),
+                                             p(hss), p(hes), p(hee))
+
+    assert blocks() == _hip.SC_OK
+    for got, ref in zip((hss, hes, hee), sub.blocks()):
+        assert np.array_equal(got.cpu().numpy(), ref.cpu().numpy())
+    assert torch.equal(hss, hss.t()) and torch.equal(hee, hee.t())
+    assert L.sc_dev_subsystem_reduce_f64(h, p(hss), p(hes), p(hee), m, me, p(info)) == _hip.SC_OK
+    assert np.array_equal(hss.cpu().numpy(), sub.effective_hessian().cpu().numpy())
+    assert torch.equal(hss, hss.t()) and int(info.cpu()[0]) == 0
+    rows = torch.from_numpy(np.random.RandomState(dim).randn(3, m)).cuda()
+    xe = sub._empty((3, me))
+    assert L.sc_dev_subsystem_follow_f64(h, p(hee), p(hes), m, me, p(rows), 3, p(xe)) == _hip.SC_OK
+    assert np.array_equal(xe.cpu().numpy(), sub.environment_displacement(rows).cpu().numpy())
+    # the single entries keep their own refusals: an empty environment, and groups that do not make up the atoms
+    bad = _hip.SC_ERR_INVALID_ARG
+    assert blocks(n_s=sub.n_total, n_e=0) == bad and blocks(n_s=sub.n_atoms - 1) == bad and blocks(n_atoms=sub.n_total + 1) == bad
+    assert L.sc_dev_subsystem_reduce_f64(h, p(hss), p(hes), p(hee), m, 0, p(info)) == bad
+    sub.finish()
+
+
+# ---- 5. refusals and failures -------------------------------------------------------------------------------------------------
 def test_refusals_before_any_launch(sc):
     coord, system, ff = sm.case_inputs(0)
     field = sm.package_ff(sc, ff)

@@ -77,7 +77,7 @@ def main():
     t_asm = timed(lambda: s._blocks_into(s.matrix, s._hes, s._hee))
     t_red = timed(lambda: s._reduce_into(s.matrix)) - t_asm
     phases = {}
-    for name in ("subsystem_batch_potrf", "subsystem_batch_trsm", "subsystem_batch_syrk"):
+    for name in ("subsystem_potrf", "subsystem_trsm", "subsystem_syrk"):
         ms = C.c_double(0.0)
         L.sc_last_eigh_phase_ms(s.ctx.handle, name.encode(), C.byref(ms))
         phases[name] = ms.value
@@ -90,8 +90,8 @@ def main():
     own = sum(flops(3.0 * e) for e in s.n_env)
     say(f"m = {s.m}, slot order m_env = {s.m_env} (members' own orders {3 * min(s.n_env)} .. {3 * max(s.n_env)}), "
         f"scratch {s.workspace_bytes() / 2 ** 20:.1f} MiB")
-    say(f"assembly {t_asm:9.2f}   reduction {t_red:9.2f} (potrf {phases['subsystem_batch_potrf']:8.2f}, substitution "
-        f"{phases['subsystem_batch_trsm']:8.2f}, product + mirror {phases['subsystem_batch_syrk']:8.2f}; "
+    say(f"assembly {t_asm:9.2f}   reduction {t_red:9.2f} (potrf {phases['subsystem_potrf']:8.2f}, substitution "
+        f"{phases['subsystem_trsm']:8.2f}, product + mirror {phases['subsystem_syrk']:8.2f}; "
         f"{padded / t_red / 1e9:5.2f} TFLOP/s on the padded flops)   eigensolve {t_all - t_asm - t_red:10.2f}   whole solve {t_all:10.2f}")
     say(f"flops of the reduction: padded {padded:.3e}, the members' own {own:.3e}: the pad costs {padded / own - 1:.1%}")
     say()

@@ -109,7 +109,7 @@ def main():
         sub = sc.Subsystem(coord, sc.InvariantForceField(13.0), system)
         sub.set_profiling(True)
         sub._allocate(sub.m, sub.m)
-        hss = sub.matrix[0]
+        hss = sub.matrix
         t_asm = timed(lambda: sub._blocks_into(hss, sub._hes, sub._hee) if sub._hes is not None else sub._reduce_into(hss))
         t_red = timed(lambda: sub._reduce_into(hss)) - t_asm
         phases = {}
