@@ -30,23 +30,17 @@
 #include <cmath>
 
 #include "eigh_internal.h"
+#include "pair_block_tile.h"   // (the listed rows and the grid of the pair consumers; the kernel is not on its MFMA core)
 
 namespace {
 
-constexpr int kTile = 64;            // atoms per side of a tile
-constexpr int kRows = 8;             // listed rows staged in LDS at a time (24 KiB)
-constexpr int kSide = 3 * kTile;     // doubles of one atom set of one row
-constexpr int64_t kMaxSlab = 32768;  // grid.y carries the structures of a slab
+constexpr int kTile = pair_tile::kTile;   // atoms per side of a tile
+constexpr int kRows = 8;                  // listed rows staged in LDS at a time (24 KiB)
+constexpr int kSide = 3 * kTile;          // doubles of one atom set of one row
+using pair_tile::kMaxSlab;
 
-struct DistFluctArgs {
-  const double* v;          // (batch, nvec, m)
-  const double* s;          // (batch, nsel) weights
-  const int* rows;          // null: listed row kk is row row0 + kk
+struct DistFluctArgs : pair_tile::ListedRows {
   const double* coord;      // (batch, N, 3); ragged: packed
-  const double* scale;      // null, or (batch, N); ragged: packed
-  const RaggedRec* rag;     // null: uniform batch
-  double* out;              // (batch, N, N); ragged: packed at sq_off
-  int row0, nsel, nvec, m, b0;
 };
 
 // the kRows x 2 values lane `tid` < kSide fetches of the group of listed rows from kk0 on: column tid of the a side and of
@@ -198,12 +192,8 @@ int batch_distfluct_device(sc_ctx* ctx, const double* d_w, const double* d_v, in
   SC_TRY(launch_mode_weights(ctx, d_w, nvec, batch, sel, nsel, d_counts, d_s, rv));
   DistFluctArgs A{};
   A.v = d_v; A.s = d_s; A.coord = d_coord; A.scale = d_atom_scale; A.out = d_out;
-  A.rows = sel.kind == SC_SEL_ROWS ? sel.d_rows : nullptr;
-  A.row0 = sel.kind == SC_SEL_FROM_ROW ? (int)sel.row0 : 0;
-  A.rag = rv ? rv->d_rec : nullptr;
-  A.nsel = (int)nsel; A.nvec = (int)nvec; A.m = (int)m;
-  const int64_t T = (N + kTile - 1) / kTile;
-  const unsigned tiles = (unsigned)(T * (T + 1) / 2);
+  pair_tile::fill_listed_rows(A, sel, nsel, nvec, m, rv);
+  const unsigned tiles = pair_tile::tri_tiles(N);
   for (int64_t b0 = 0; b0 < batch; b0 += kMaxSlab) {
     A.b0 = (int)b0;
     hipLaunchKernelGGL(k_dist_fluct, dim3(tiles, (unsigned)std::min(kMaxSlab, batch - b0)), dim3(256), 0, st, A);

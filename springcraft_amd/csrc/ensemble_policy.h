@@ -58,7 +58,8 @@ static inline MeanBufs mean_layout(Arena& a, int64_t n_frames, int64_t n_atoms) 
 
 // ---- pairwise RMSD matrix (rmsd_matrix.hip) ----------------------------------------------------------------------------------
 // A workgroup of the product kernel owns kRmsdTile x kRmsdTile frame pairs and stages kRmsdRows atoms at a time.  The
-// transposed copy Y (N_pad, 3, M_pad) is padded to both with exact zeros, so the product has no tail code.
+// transposed copy Y (N_pad, 3, M_pad) is padded to both with exact zeros, so the product has no tail code.  (The two are the
+// tile of pair_block_tile.h, which asserts so.)
 constexpr int kRmsdTile = 64;
 constexpr int kRmsdRows = 8;
 static inline int64_t rmsd_pad_frames(int64_t n_frames) { return (n_frames + kRmsdTile - 1) / kRmsdTile * kRmsdTile; }

@@ -170,4 +170,11 @@ static inline bool resident_shape(int n, int nb, int cus, int max_order, int wan
   return true;
 }
 
+// ---- the pair consumers' grids (dist_fluct.hip, pair_block_tile.h): workgroups of one structure of n atoms in tiles of
+// `tile`, one per unordered pair of tiles; tri_tile_decode (eigh_internal.h) is the way back
+static inline int64_t tri_tile_count(int64_t n, int tile) {
+  const int64_t t = (n + tile - 1) / tile;
+  return t * (t + 1) / 2;
+}
+
 }  // namespace sc_host

@@ -19,11 +19,10 @@
 // weights and partial sums.  (2) k_lmi_whiten, one lane per atom, writes the nine entries of W_a behind them (the permutation
 // moves the zeros of L_a^-1, so six numbers do not describe W_a).  A pivot that is not finite or is <= 2^-40 times the block's
 // own diagonal entry (a definition: fewer than three selected modes, an atom at rest in the selection) makes all nine NaN.
-// (3) k_mode_lmi has the data flow and the tile ownership of k_mode_prs (mode_prs.hip, which describes them): 64 x 64 atom
-// tiles with tile_a >= tile_c, 512 lanes, 8 listed rows staged per step, the weight folded into the a side, 2 x 9 f64
-// 16 x 16 x 4 MFMA accumulators per wavefront with the nine entries of one C_ac in one lane.  Selection happens at the
-// fetch, so 0 * NaN from a window's padding never reaches a result, and a NaN weight is staged as NaN on the a side of all
-// atoms of its structure alone.
+// (3) k_mode_lmi runs on the pair-block core of pair_block_tile.h, which describes the data flow, with the tile ownership
+// of k_mode_prs (mode_prs.hip): 64 x 64 atom tiles with tile_a >= tile_c, the weight folded into the a side, the nine
+// entries of one C_ac in one lane, no per-atom scale.  Selection happens at the fetch, so 0 * NaN from a window's padding
+// never reaches a result, and a NaN weight is staged as NaN on the a side of all atoms of its structure alone.
 // The tensors are summed in chunks of kLmiTensorChunk listed rows, a constant, where the tensor consumer itself cuts by the
 // number of listed rows: rows without weight behind a structure's own (a ragged slot's pad rows) then fill chunks of
 // exact zeros and move no boundary, and a member of a ragged batch has the bits of its uniform solve.
@@ -41,26 +40,17 @@
 #include <cmath>
 
 #include "eigh_internal.h"
+#include "pair_block_tile.h"
 
 namespace {
 
-typedef double d4 __attribute__((ext_vector_type(4)));
+using namespace pair_tile;
 
-constexpr int kTile = 64;                     // atoms per side of a tile: 4 blocks of 16
-constexpr int kRows = 8;                      // listed rows staged in LDS at a time: two MFMA steps of 4
-constexpr int kSide = 3 * kTile;              // doubles of one atom set of one row
-constexpr int kRowStride = 2 * kSide + 16;    // (mode_prs.hip: the rows of one operand load alternate between bank halves)
-constexpr int64_t kMaxSlab = 32768;           // grid.y carries the structures of a slab
 constexpr double kPivotFloor = 0x1p-40;       // a pivot <= this times its diagonal entry: the block cannot be whitened
 
-struct LmiArgs {
-  const double* v;          // (batch, nvec, m)
-  const double* s;          // (batch, nsel) weights
-  const int* rows;          // null: listed row kk is row row0 + kk
+struct LmiArgs : ListedRows {   // (scale: null)
   const double* wh;         // (batch, N, 9) whitening factors; ragged: packed at 9 atom_off
-  const RaggedRec* rag;     // null: uniform batch
-  double* out;              // (batch, N, N); ragged: packed at sq_off
-  int row0, nsel, nvec, m, b0, information;
+  int information;
 };
 
 __device__ __forceinline__ double pick3(int i, double x0, double x1, double x2) { return i == 0 ? x0 : (i == 1 ? x1 : x2); }
@@ -118,22 +108,6 @@ __global__ __launch_bounds__(256) void k_lmi_whiten(const double* __restrict__ t
   }
 }
 
-// (fetch_rows of mode_prs.hip) the kRows values a loader lane fetches of the group of listed rows from kk0 on: its column
-// `g` of every row that carries a weight; on the a side a NaN weight takes the place of the row, which is not read
-__device__ __forceinline__ void fetch_rows(const LmiArgs& A, const double* __restrict__ vb, const double* __restrict__ sb,
-                                           int kk0, int g, bool ok, bool a_side, double (&pre)[kRows]) {
-#pragma unroll
-  for (int r = 0; r < kRows; ++r) {
-    const int kk = kk0 + r;
-    const double sv = kk < A.nsel ? sb[kk] : 0.0;   // (uniform over the workgroup)
-    pre[r] = (sv != sv && a_side) ? sv : 0.0;
-    if (sv != 0.0 && sv == sv && ok) {
-      const int row = min(max(A.rows ? A.rows[kk] : A.row0 + kk, 0), A.nvec - 1);
-      pre[r] = vb[(size_t)row * A.m + g];
-    }
-  }
-}
-
 // the value of one pair from its covariance block c[d][e] and the two whitening factors, in one fixed operation order
 __device__ __forceinline__ double lmi_pair(const double (&c)[3][3], const double (&wa)[9], const double (&wc)[9],
                                            int information) {
@@ -160,8 +134,7 @@ __device__ __forceinline__ double lmi_pair(const double (&c)[3][3], const double
 
 // grid (tiles with tile_a >= tile_c, structures of the slab)
 __global__ __launch_bounds__(512) void k_mode_lmi(const LmiArgs A) {
-  __shared__ double lds[kRows * kRowStride];
-  const int tid = threadIdx.x;
+  __shared__ double lds[kLdsDoubles];
   int ta, tc;
   tri_tile_decode(blockIdx.x, ta, tc);
   const int b = A.b0 + blockIdx.y;
@@ -170,102 +143,37 @@ __global__ __launch_bounds__(512) void k_mode_lmi(const LmiArgs A) {
   if (a0 >= N) return;                          // (the whole workgroup: a ragged structure smaller than the grid)
   const size_t atom_off = A.rag ? (size_t)A.rag[b].atom_off : (size_t)b * N;
   double* ob = A.out + (A.rag ? (size_t)A.rag[b].sq_off : (size_t)b * N * N);
-  const double* vb = A.v + (size_t)b * A.nvec * A.m;
-  const double* sb = A.s + (size_t)b * A.nsel;
   const double* whb = A.wh + atom_off * 9;
 
-  // the loader lanes: lanes 0..191 take the a side, 192..383 the c side; column `col` of a side is component `comp` of its
-  // atom `atom`
-  const bool loader = tid < 2 * kSide, a_side = tid < kSide;
-  const int col = a_side ? tid : tid - kSide;
-  const int atom = col / 3, comp = col - 3 * atom;
-  const int s0 = a_side ? a0 : c0;
-  const bool ok = loader && s0 + atom < N;
-  const int g = 3 * s0 + col;
-  const int slot = (a_side ? 0 : kSide) + comp * kTile + atom;
-
-  // the MFMA lanes: wavefront w, lane (fr, fk) supplies atom 16 ab + fr of the a side and atom 16 (cb0 + j) + fr of the c
-  // side, both of row fk of a step
-  const int w = tid >> 6, fr = tid & 15, fk = (tid >> 4) & 3;
-  const int ab = w & 3, cb0 = 2 * (w >> 2);
-  const double* la = lds + fk * kRowStride + 16 * ab + fr;
-  const double* lc = lds + fk * kRowStride + kSide + 16 * cb0 + fr;
+  const Lanes L = lanes(lds, threadIdx.x);
   d4 acc[2][3][3];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-#pragma unroll
-      for (int e = 0; e < 3; ++e) acc[j][d][e] = d4{0.0, 0.0, 0.0, 0.0};
+  mode_blocks<false>(A, lds, L, b, N, atom_off, a0, c0, acc);
 
-  double pre[kRows];
-  fetch_rows(A, vb, sb, 0, g, ok, a_side, pre);
-  for (int kk0 = 0; kk0 < A.nsel; kk0 += kRows) {
-    __syncthreads();   // the previous group has been multiplied
-    if (loader) {
-#pragma unroll
-      for (int r = 0; r < kRows; ++r) {
-        const int kk = kk0 + r;
-        const double sv = (a_side && kk < A.nsel) ? sb[kk] : 1.0;   // (the weight is folded into the a side alone)
-        lds[r * kRowStride + slot] = pre[r] * sv;
-      }
-    }
-    __syncthreads();
-    if (kk0 + kRows < A.nsel) fetch_rows(A, vb, sb, kk0 + kRows, g, ok, a_side, pre);
-#pragma unroll
-    for (int k4 = 0; k4 < kRows / 4; ++k4) {
-      if (kk0 + 4 * k4 >= A.nsel) break;   // (uniform) a step of nothing but the tail
-      double af[3], bf[2][3];
-#pragma unroll
-      for (int d = 0; d < 3; ++d) af[d] = la[4 * k4 * kRowStride + d * kTile];
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int e = 0; e < 3; ++e) bf[j][e] = lc[4 * k4 * kRowStride + e * kTile + 16 * j];
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int d = 0; d < 3; ++d)
-#pragma unroll
-          for (int e = 0; e < 3; ++e)
-            acc[j][d][e] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[d], bf[j][e], acc[j][d][e], 0, 0, 0);
-    }
-  }
-
-  // the epilogue: the lane's pairs (a = a0 + 16 ab + 4 r + fk, c = c0 + 16 (cb0 + j) + fr).  An atom behind the structure's
-  // own takes the factors of its last atom and stores nothing
+  // the epilogue: the lane's pairs.  An atom behind the structure's own takes the factors of its last atom and stores nothing
   const bool diag = ta == tc;
   const double defined = A.information ? HUGE_VAL : 1.0;
+  double wc[9];
+  for_pairs(
+      L, acc,
+      [&](int cl) {
+        const double* p = whb + (size_t)min(c0 + cl, N - 1) * 9;
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int c = c0 + 16 * (cb0 + j) + fr;
-    double wc[9];
-    {
-      const double* p = whb + (size_t)min(c, N - 1) * 9;
+        for (int i = 0; i < 9; ++i) wc[i] = p[i];
+      },
+      [&](int al, int cl, const double (&cb)[3][3]) {
+        const int a = a0 + al, c = c0 + cl;
+        double wa[9];
+        const double* p = whb + (size_t)min(a, N - 1) * 9;
 #pragma unroll
-      for (int i = 0; i < 9; ++i) wc[i] = p[i];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int a = a0 + 16 * ab + 4 * r + fk;
-      double wa[9];
-      const double* p = whb + (size_t)min(a, N - 1) * 9;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) wa[i] = p[i];
-      double cb[3][3];
-#pragma unroll
-      for (int d = 0; d < 3; ++d)
-#pragma unroll
-        for (int e = 0; e < 3; ++e) cb[d][e] = acc[j][d][e][r];
-      double val = lmi_pair(cb, wa, wc, A.information);
-      if (a >= N || c >= N || (diag && a < c)) continue;
-      if (a == c) {
-        val = wa[0] != wa[0] ? wa[0] : defined;   // (k_lmi_whiten writes nine NaN or none)
-      }
-      ob[(size_t)a * N + c] = val;
-      if (a != c) ob[(size_t)c * N + a] = val;
-    }
-  }
+        for (int i = 0; i < 9; ++i) wa[i] = p[i];
+        double val = lmi_pair(cb, wa, wc, A.information);
+        if (a >= N || c >= N || (diag && a < c)) return;
+        if (a == c) {
+          val = wa[0] != wa[0] ? wa[0] : defined;   // (k_lmi_whiten writes nine NaN or none)
+        }
+        ob[(size_t)a * N + c] = val;
+        if (a != c) ob[(size_t)c * N + a] = val;
+      });
 }
 
 }  // namespace
@@ -288,7 +196,6 @@ int batch_lmi_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
   hipStream_t st = ctx->stream;
   const int64_t nsel = batch_modes_nsel(sel, nvec);
   const int64_t N = rv ? rv->max_atoms : m / 3;   // (bounds the grids)
-  const RaggedRec* rag = rv ? rv->d_rec : nullptr;
   // the whole workspace: batch_aniso_device's layout (weights, partial sums in chunks of kLmiTensorChunk rows) is its head
   const size_t total = batch_modes_workspace_bytes(m, nvec, batch, 3, nsel, 8, 0, rv);
   SC_TRY(sc_reserve_modes(ctx, total));
@@ -299,18 +206,14 @@ int batch_lmi_device(sc_ctx* ctx, const double* d_w, const double* d_v, int64_t 
   SC_TRY(batch_aniso_device(ctx, d_w, d_v, m, nvec, batch, sel, d_counts, 0, d_t, rv, kLmiTensorChunk));
   LmiArgs A{};
   A.v = d_v; A.s = d_s; A.wh = d_wh; A.out = d_out;
-  A.rows = sel.kind == SC_SEL_ROWS ? sel.d_rows : nullptr;
-  A.row0 = sel.kind == SC_SEL_FROM_ROW ? (int)sel.row0 : 0;
-  A.rag = rag;
-  A.nsel = (int)nsel; A.nvec = (int)nvec; A.m = (int)m;
+  fill_listed_rows(A, sel, nsel, nvec, m, rv);
   A.information = information ? 1 : 0;
-  const int64_t T = (N + kTile - 1) / kTile;
-  const unsigned tiles = (unsigned)(T * (T + 1) / 2);
+  const unsigned tiles = tri_tiles(N);
   const unsigned strips = (unsigned)((N + 255) / 256);
   for (int64_t b0 = 0; b0 < batch; b0 += kMaxSlab) {
     const unsigned nb = (unsigned)std::min(kMaxSlab, batch - b0);
     A.b0 = (int)b0;
-    hipLaunchKernelGGL(k_lmi_whiten, dim3(strips, nb), dim3(256), 0, st, d_t, d_wh, (int)N, rag, (int)b0);
+    hipLaunchKernelGGL(k_lmi_whiten, dim3(strips, nb), dim3(256), 0, st, d_t, d_wh, (int)N, A.rag, (int)b0);
     hipLaunchKernelGGL(k_mode_lmi, dim3(tiles, nb), dim3(512), 0, st, A);
   }
   SC_HIP(ctx, hipGetLastError());

@@ -15,7 +15,8 @@
 // as exactly 0.0 by the workgroups of the pad frames and by every frame's workgroup behind its last atom.  A non-finite
 // coordinate makes G_f NaN (0 * NaN of a zero-weight atom included).
 //
-// k_rmsd_product is mode_prs.hip with frames and atoms in swapped roles.  One workgroup of 512 lanes owns a 64 x 64 tile of
+// k_rmsd_product is the core of pair_block_tile.h with frames and atoms in swapped roles, in a copy of its own (on the
+// shared functions it took 1.3 % longer at 10^4 x 2000: profiles/pair_block_tile.txt).  One workgroup of 512 lanes owns a 64 x 64 tile of
 // frame pairs and walks the atoms in ascending order, kRows at a time: 2 x 192 lanes fetch the 64 consecutive doubles of
 // the three components of the tile's two frame sets of each atom while the previous group is multiplied, into LDS as
 // [atom][side][component][frame].  A 16 x 16 x 4 MFMA is "component d of 16 frames f times component e of 16 frames g,
@@ -50,6 +51,7 @@ constexpr int kSide = 3 * kTile;              // doubles of one frame set of one
 constexpr int kRowStride = 2 * kSide + 16;
 constexpr int kJacobiSweeps = 30;             // horn_rotation's
 static_assert(kTile == 64 && kRows % 4 == 0, "the lane mapping below is written for 64 x 64 tiles and MFMA steps of 4");
+// (pair_block_tile.h asserts that its tile is this one)
 
 __device__ __forceinline__ bool is_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
 

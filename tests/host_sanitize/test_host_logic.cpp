@@ -230,6 +230,10 @@ int main() {
       CHECK(rows <= (S.reg ? 12 : 8) && 256 * S.Q >= S.m && S.lds_bytes <= 160 * 1024);
     }
   }
+  // ---- the pair consumers' grid: one workgroup per unordered pair of tiles
+  CHECK(sc_host::tri_tile_count(1, 64) == 1 && sc_host::tri_tile_count(64, 64) == 1 && sc_host::tri_tile_count(65, 64) == 3);
+  CHECK(sc_host::tri_tile_count(128, 64) == 3 && sc_host::tri_tile_count(129, 64) == 6 && sc_host::tri_tile_count(2000, 64) == 528);
+  CHECK(sc_host::tri_tile_count(0, 64) == 0 && sc_host::tri_tile_count(0x7fffffffLL, 64) == 33554432LL * 33554433LL / 2);
   // ---- the two-stage policy (csrc/twostage_policy.h): the decisions its comments document as measured, on a device of
   // 256 CUs / 8 XCDs with the default environment (a default-constructed TwoStageEnv: the process environment is not read)
   {
