@@ -980,6 +980,49 @@ int sc_dev_vsa_batch_blocks_f64(sc_ctx* ctx, const int64_t* members, int64_t bat
 int sc_dev_vsa_batch_reduce_f64(sc_ctx* ctx, double* d_hss, double* d_hes, double* d_hee, int64_t ms, int64_t me,
                                 int64_t batch, int64_t* d_info);
 
+/* ---- correlation networks (csrc/corr_network.hip) ---------------------------------------------------------------------------
+ * No reference counterpart.  They replace Bio3D's cna on a dccm / lmi map and the all-pairs shortest paths and betweenness
+ * of a graph library run on host copies of the maps (Sethi et al. 2009, WISP): the weighted residue graph of a coupling map,
+ * the shortest path between every pair of nodes, and how many of those paths every node carries.
+ *
+ * `count` members in the packed pair layout of the batch consumers' dcc / prs / lmi results: member b is an (n_b, n_b)
+ * row-major block at element offset off_b of every pair buffer, and its nodes start at atom_off_b of every per-node buffer.
+ * d_rec (count, 3) int64 on the DEVICE holds (n_b, off_b, atom_off_b); n_max >= every n_b sizes the grids (a member with
+ * n_b > n_max is skipped).  The caller keeps the records consistent with its buffers.  d_flags (count) int32: non-zero
+ * marks a member without a defined result.  A member's bits depend on its own input alone: not on the batch, its place in
+ * it or its neighbours; a member of a ragged batch has the bits of a batch of its own.  Every entry only enqueues.
+ *
+ * sc_dev_net_weights_f64: d_w[a, c] = -log(min(|c_ac|, 1)) where |c_ac| >= min_correlation and, with d_coord (sum n, 3) not
+ * NULL, |x_a - x_c|^2 <= contact_cutoff_sq; +inf elsewhere; 0 on the diagonal.  d_flags is written: 1 for a member with a
+ * NaN in its map or coordinates, else 0.  One streaming pass.
+ *
+ * sc_dev_net_paths_f64: d_d (distances, float64) and d_s (next hops, int32) of the non-negative weights d_w, which may be
+ * asymmetric; +inf is "no edge", the diagonal is taken as 0.  Blocked Floyd-Warshall with 64 x 64 tiles, D[i, j] = min(D[i,
+ * j], D[i, k] + D[k, j]), updated on strict improvement only with k ascending and S[i, j] <- S[i, k]; S starts as j on a
+ * finite edge, i on the diagonal, else -1.  2 n^3 additions and comparisons per member, 3 launches per round of 64 pivots
+ * whatever the batch.  d_s[i, j] is the node after i on the stored path to j, -1 exactly where d_d is +inf.  A symmetric d_w
+ * gives d_d equal to its transpose bit for bit.  d_flags is read and written: a member flagged already, or with a NaN or
+ * negative weight, ends with every d_d NaN and every d_s -1; nothing else is touched.  d_d may be d_w.
+ *
+ * sc_dev_net_usage: d_usage (sum n) int64, for node v the number of ordered pairs (a, t) with a, t, v distinct and t reachable
+ * from a whose STORED path a -> d_s[a, t] -> ... -> t passes through v: one path per pair, so on ties not Brandes' fractional
+ * betweenness.  A walk that takes more than n_b hops or meets a next hop outside 0 .. n_b - 1 sets the member's flag; a
+ * flagged member's usage is -1.  The counters of one target are held in LDS: n_max <= 8192.  It occupies
+ * sc_dev_net_workspace bytes of context scratch: an int32 per packed pair (total_sq = sum n_b^2).  That entry answers -1
+ * for a total_sq below 1 or above 2^48.
+ *
+ * SC_ERR_INVALID_ARG before anything is launched: count outside 1 .. 65535, n_max outside 1 .. 262144 (usage: 8192),
+ * min_correlation outside [0, 1], coordinates with a squared cutoff that is not positive, a total_sq that the workspace entry
+ * refuses or above count n_max^2, a NULL required pointer. */
+int sc_dev_net_weights_f64(sc_ctx* ctx, const int64_t* d_rec, int64_t count, int64_t n_max, const double* d_corr,
+                           const double* d_coord, double contact_cutoff_sq, double min_correlation, double* d_w,
+                           int32_t* d_flags);
+int sc_dev_net_paths_f64(sc_ctx* ctx, const int64_t* d_rec, int64_t count, int64_t n_max, const double* d_w, double* d_d,
+                         int32_t* d_s, int32_t* d_flags);
+int64_t sc_dev_net_workspace(int64_t total_sq);
+int sc_dev_net_usage(sc_ctx* ctx, const int64_t* d_rec, int64_t count, int64_t n_max, int64_t total_sq, const int32_t* d_s,
+                     int64_t* d_usage, int32_t* d_flags);
+
 #ifdef __cplusplus
 }
 #endif

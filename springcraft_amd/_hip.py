@@ -65,6 +65,7 @@ EXPORTED_SYMBOLS = [
     "sc_dev_potrf_workspace", "sc_dev_potrf_f64", "sc_dev_potrs_f64",
     "sc_dev_subsystem_blocks_f64", "sc_dev_subsystem_reduce_f64", "sc_dev_subsystem_follow_f64",
     "sc_dev_vsa_batch_workspace", "sc_dev_vsa_batch_blocks_f64", "sc_dev_vsa_batch_reduce_f64",
+    "sc_dev_net_weights_f64", "sc_dev_net_paths_f64", "sc_dev_net_workspace", "sc_dev_net_usage",
 ]
 
 SC_SEL_FROM_ROW = 0
@@ -290,6 +291,10 @@ def lib():
         "sc_dev_vsa_batch_workspace": (i32, [i32, i64, i64, i64, P(C.c_size_t)]),
         "sc_dev_vsa_batch_blocks_f64": (i32, [vp, vp, i64, i32, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "sc_dev_vsa_batch_reduce_f64": (i32, [vp, vp, vp, vp, i64, i64, i64, vp]),
+        "sc_dev_net_weights_f64": (i32, [vp, vp, i64, i64, vp, vp, dbl, dbl, vp, vp]),
+        "sc_dev_net_paths_f64": (i32, [vp, vp, i64, i64, vp, vp, vp, vp]),
+        "sc_dev_net_workspace": (i64, [i64]),
+        "sc_dev_net_usage": (i32, [vp, vp, i64, i64, i64, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

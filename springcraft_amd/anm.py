@@ -132,6 +132,10 @@ class ANM(ElasticNetworkModel):
         """Generalized correlation (n, n) from the linear mutual information (:func:`nma.generalized_correlation`)."""
         return nma.generalized_correlation(self, mode_subset, information)
 
+    def correlation_network(self, kind="dcc", mode_subset=None, contact_cutoff=None, min_correlation=0.0):
+        """Shortest communication paths and path usage of the ``dcc`` / ``lmi`` map (:func:`nma.correlation_network`)."""
+        return nma.correlation_network(self, kind, mode_subset, contact_cutoff, min_correlation)
+
     def subsystem(self, system, device=None):
         """
         The modes of the ``system`` atoms inside their relaxing environment, a :class:`~springcraft_amd.Subsystem` built

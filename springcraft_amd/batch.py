@@ -706,6 +706,10 @@ class _BatchSolver:
         the selection is the window (see :meth:`mean_square_fluctuation`, also for trivial modes inside it); an empty
         window gives zeros, and NaN under ``norm=True`` as 0 / 0 does in NumPy.
         """
+        return self._layout.pairs_out(self._dcc_packed(mode_subset, norm, tem, tem_factors))
+
+    def _dcc_packed(self, mode_subset, norm, tem=None, tem_factors=K_B):
+        """:meth:`dcc`'s result as the one packed buffer the kernels fill."""
         sel, counts = self._selection(mode_subset, pinv_default=True)
         buf = self._empty(self._layout.pairs_shape())
         self._call("dcc", C.byref(sel), counts, int(bool(norm)), int(self.consumer_budget_bytes or 0),
@@ -713,7 +717,7 @@ class _BatchSolver:
         if tem is not None:
             buf *= tem
             buf *= tem_factors
-        return self._layout.pairs_out(buf)
+        return buf
 
     def prs(self, mode_subset=None, norm=True, atom_scale=None):
         """
@@ -782,14 +786,48 @@ class _BatchSolver:
         Ragged: [(n_i, n_i), ...], views into one buffer packed like :meth:`dcc`'s; a member's bits are those of its
         uniform solve, whatever the other members and the slot order.
         """
-        lay = self._layout
+        return self._layout.pairs_out(self._lmi_packed(mode_subset, information))
+
+    def _lmi_packed(self, mode_subset, information):
+        """:meth:`generalized_correlation`'s result as the one packed buffer the kernel fills."""
         if self.dim != 3:
             raise ValueError("generalized_correlation needs an ANM solver (dim=3): for a GNM it is abs(dcc(norm=True))")
         self._need_vectors()
         sel, counts = self._selection(mode_subset, pinv_default=True)
-        buf = self._empty(lay.pairs_shape())
+        buf = self._empty(self._layout.pairs_shape())
         self._call("lmi", C.byref(sel), counts, int(bool(information)), C.c_void_p(buf.data_ptr()))
-        return lay.pairs_out(buf)
+        return buf
+
+    def correlation_network(self, kind="dcc", mode_subset=None, coord=None, contact_cutoff=None, min_correlation=0.0):
+        """
+        The :class:`~springcraft_amd.network.CorrelationNetwork` of every structure's coupling map, computed where the map
+        is: ``kind="dcc"`` takes ``dcc(mode_subset, norm=True)``, ``kind="lmi"`` ``generalized_correlation(mode_subset)``
+        (ANM solvers only: ``dim != 3`` raises its ValueError).  No reference counterpart (Bio3D: ``cna`` on ``dccm`` /
+        ``lmi``; the shortest paths and betweenness of a graph library on host copies of the maps).  An edge a - c exists
+        where ``|c_ac| >= min_correlation`` and, with ``coord`` -- a CUDA float64 tensor shaped like the solver's coordinates
+        -- and ``contact_cutoff``, the two atoms are within the cutoff; its weight is ``-log(min(|c_ac|, 1))``.  The result
+        holds ``weights``, ``distances`` and ``next_hop`` as (batch, n_atoms, n_atoms) CUDA tensors, ragged: lists of (n_i,
+        n_i) views of packed buffers, and ``path`` / ``path_length`` / ``usage`` / ``betweenness`` / ``reachable``.  A failed
+        structure's map is NaN, so its member is flagged: NaN distances, next hops -1.  Only enqueues.
+
+        ValueError before anything is enqueued: ``min_correlation`` outside [0, 1], a cutoff that is not positive, a cutoff
+        without coordinates or the reverse, an unknown ``kind``.
+        """
+        from . import network as _net
+
+        mc, cut = _net.check_network_args(min_correlation, contact_cutoff, coord is not None)
+        if kind not in ("dcc", "lmi"):
+            raise ValueError(f"kind must be 'dcc' or 'lmi', got {kind!r}")
+        lay = self._layout
+        if coord is not None:
+            self._device_f64(coord, lay.atoms_shape((3,)), "coord")
+        with self.torch.cuda.device(self.device):
+            buf = self._dcc_packed(mode_subset, True) if kind == "dcc" else self._lmi_packed(mode_subset, False)
+            sizes = lay.sizes if lay.ragged else [lay.n_atoms] * lay.batch
+            form = _net._Form(_net.check_sizes(sizes), "ragged" if lay.ragged else "uniform", False)
+            xyz = None if coord is None else coord.view(-1, 3)
+            return _net.network_from_packed(self.torch, self.device, self.ctx, form, buf.view(-1), xyz, cut, mc,
+                                            keep=(self._rows_keep,))
 
     # ---- how the modes of member a compare with those of member b (csrc/mode_subspace.hip) ---------------------------------
     # No reference counterpart (Bio3D: rmsip / covsoverlap; ProDy: calcSubspaceOverlap / calcCovOverlap / calcOverlap of two

@@ -72,6 +72,10 @@ class GNM(ElasticNetworkModel):
         """Dynamic cross-correlation (n,n) (gnm.py:246-303)."""
         return nma.dcc(self, mode_subset, norm, tem, tem_factors)
 
+    def correlation_network(self, mode_subset=None, contact_cutoff=None, min_correlation=0.0):
+        """Shortest communication paths and path usage of the ``dcc`` map (:func:`nma.correlation_network`)."""
+        return nma.correlation_network(self, "dcc", mode_subset, contact_cutoff, min_correlation)
+
     def overlap(self, displacement, mode_subset=None):
         """Overlap of the selected modes with one or q displacements, (k,) / (q, k) (:func:`nma.overlap`)."""
         return nma.overlap(self, displacement, mode_subset)

@@ -605,6 +605,25 @@ def generalized_correlation(anm, mode_subset=None, information=False):
     return anm._modes_device().lmi(mode_subset, information)
 
 
+def correlation_network(enm, kind="dcc", mode_subset=None, contact_cutoff=None, min_correlation=0.0):
+    """
+    The :class:`~springcraft_amd.network.CorrelationNetwork` of one model's coupling map: ``kind="dcc"`` takes
+    ``dcc(enm, mode_subset, norm=True)``, ``kind="lmi"`` ``generalized_correlation(enm, mode_subset)`` (ANM only, its
+    ValueError otherwise), and :func:`springcraft_amd.network.correlation_network` turns the map into edge weights
+    ``-log|c_ac|``, the shortest path between every pair of atoms and the atoms' path usage on the device.  With
+    ``contact_cutoff`` only atoms of the model within that distance are joined.  No reference counterpart (Bio3D: ``cna``).
+    The network's arrays are NumPy arrays, like the map.
+    """
+    from . import network as _net
+
+    _net.check_network_args(min_correlation, contact_cutoff, contact_cutoff is not None)
+    if kind not in ("dcc", "lmi"):
+        raise ValueError(f"kind must be 'dcc' or 'lmi', got {kind!r}")
+    corr = dcc(enm, mode_subset, norm=True) if kind == "dcc" else generalized_correlation(enm, mode_subset)
+    coord = None if contact_cutoff is None else np.asarray(enm._coord, dtype=np.float64)
+    return _net.correlation_network(corr, coord, contact_cutoff, min_correlation)
+
+
 def _comparable(enm_a, enm_b):
     """Two models whose modes share their coordinates: the same class and atom count, else ValueError (host only)."""
     _model_kind(enm_a)
