@@ -1023,6 +1023,57 @@ int64_t sc_dev_net_workspace(int64_t total_sq);
 int sc_dev_net_usage(sc_ctx* ctx, const int64_t* d_rec, int64_t count, int64_t n_max, int64_t total_sq, const int32_t* d_s,
                      int64_t* d_usage, int32_t* d_flags);
 
+/* ---- clustering of a dissimilarity matrix ---------------------------------------------------------------------------------
+ * No reference counterpart.  The entries replace a host copy of an (n, n) matrix and gmx cluster -method gromos, Bio3D's
+ * hclust / cutree or a k-medoids package run on it.  d_dist (n, n) float64 row-major on the DEVICE: an ensemble's pairwise
+ * RMSD matrix, the distances of a correlation network, 1 - |dcc|; symmetry is expected and not verified.  Item i is
+ * invalid when d_dist[i, i] is NaN: label -1, it neither counts nor is counted and is never a centre or a medoid.  Ties go
+ * to the lowest index; two calls agree bit for bit.
+ *
+ * A run's state lives in d_ws, ws_bytes >= sc_cluster_workspace(n, k) bytes of device memory the caller owns and leaves
+ * alone between the calls of a run; k = 0 sizes neighbour-count clustering, k >= 1 k-medoids with k medoids.  That entry
+ * answers -1 for n outside 1 .. 262144 and k outside 0 .. min(n, 1024).  d_status, four int32 on the device, is the only
+ * thing a host has to read during a run: [0] neighbour-count: the items without a label yet; k-medoids: 1 while SWAP may
+ * still improve, 0 once it has converged; [1] the clusters made / the swaps accepted; [2] 1: a NaN between two valid items
+ * -- every label is -1, [1] and [3] stay 0 and nothing else is defined; [3] k-medoids: the medoids placed, min(k, valid
+ * items).  d_labels (n) int32.  Every entry only enqueues on the context's stream.
+ *
+ * sc_dev_cluster_gromos_init_f64 (Daura et al. 1999): reads d_dist once and never again; writes the workspace -- the bit
+ * matrix adj[i, j] = (d_dist[i, j] <= cutoff or i == j) over valid i, j, one bit per pair, the counts of every row -- d_labels
+ * (all -1) and d_status.  sc_dev_cluster_gromos_rounds: `rounds` rounds, each two launches: the alive item with the most
+ * alive neighbours, the lowest index among equals, becomes centre c of the next cluster; its alive neighbours get label c's
+ * number and leave; the counts of the rest are lowered.  d_reps / d_sizes (max_clusters) int32 receive the centre and the
+ * size of every cluster made.  A round with nothing alive, or after max_clusters clusters, does nothing, so any number of
+ * rounds may be enqueued.  Reads and writes the workspace, d_labels, d_status.
+ *
+ * sc_dev_cluster_kmedoids_init_f64 (PAM BUILD): k passes over d_dist.  The first medoid is the valid item with the smallest
+ * sum over its row, every further one the item with the largest gain sum_j max(dn[j] - d_dist[i, j], 0); dn / ds are an
+ * item's distances to its nearest and second-nearest medoid, read along the medoid's row, the lowest slot among equals.
+ * Writes d_labels (the nearest slot), d_reps / d_sizes (k) int32 (the medoids, -1 / 0 past the medoids placed), d_td[0] (the
+ * total deviation sum_j dn[j]), d_status.  sc_dev_cluster_kmedoids_swaps_f64: `iterations` SWAP iterations, each one pass
+ * over d_dist and four launches: for every candidate x and slot s the change of the total deviation when x replaces the
+ * medoid of s (the FastPAM1 evaluation, Schubert & Rousseeuw 2021); the smallest change, lowest x then lowest s among
+ * equals, is applied if it is below 0 and d_td[status[1]] receives the new total deviation (dropped at td_cap entries);
+ * else status[0] becomes 0 and every later iteration does nothing.  sc_cluster_form: the form that evaluation takes for
+ * (n, k): 0, a workgroup keeps its candidate's row in LDS; 1, it gathers from global memory; same bits.
+ * SPRINGCRAFT_CLUSTER_FORM = stream forces 1; = lds and = auto leave the size rule.  Read at every call.
+ *
+ * SC_ERR_INVALID_ARG before anything is launched: sizes sc_cluster_workspace refuses (k-medoids: k = 0 too), a workspace
+ * that is NULL or smaller than it asks for, a cutoff that is negative or not finite, rounds or max_clusters outside 1 .. n,
+ * iterations outside 1 .. 65536, td_cap below 1, a NULL required pointer. */
+int64_t sc_cluster_workspace(int64_t n, int64_t k);
+int sc_cluster_form(int64_t n, int64_t k);
+int sc_dev_cluster_gromos_init_f64(sc_ctx* ctx, const double* d_dist, int64_t n, double cutoff, void* d_ws, size_t ws_bytes,
+                                   int32_t* d_labels, int32_t* d_status);
+int sc_dev_cluster_gromos_rounds(sc_ctx* ctx, int64_t n, int64_t rounds, int64_t max_clusters, void* d_ws, size_t ws_bytes,
+                                 int32_t* d_labels, int32_t* d_reps, int32_t* d_sizes, int32_t* d_status);
+int sc_dev_cluster_kmedoids_init_f64(sc_ctx* ctx, const double* d_dist, int64_t n, int64_t k, void* d_ws, size_t ws_bytes,
+                                     int32_t* d_labels, int32_t* d_reps, int32_t* d_sizes, double* d_td, int64_t td_cap,
+                                     int32_t* d_status);
+int sc_dev_cluster_kmedoids_swaps_f64(sc_ctx* ctx, const double* d_dist, int64_t n, int64_t k, int64_t iterations, void* d_ws,
+                                      size_t ws_bytes, int32_t* d_labels, int32_t* d_reps, int32_t* d_sizes, double* d_td,
+                                      int64_t td_cap, int32_t* d_status);
+
 #ifdef __cplusplus
 }
 #endif

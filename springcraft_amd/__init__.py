@@ -13,7 +13,8 @@ from .atoms import AtomArray, read_pdb_ca  # noqa: F401
 from .forcefield import *  # noqa: F401,F403
 from .gnm import *  # noqa: F401,F403
 from .interaction import *  # noqa: F401,F403
-from . import ensemble, iterative, network, nma  # noqa: F401
+from . import cluster, ensemble, iterative, network, nma  # noqa: F401
+from .cluster import Clustering, cluster_gromos, cluster_kmedoids  # noqa: F401
 from .ensemble import Ensemble, EssentialDynamics, rmsd_matrix, superimpose  # noqa: F401
 from .network import CorrelationNetwork, correlation_network, shortest_paths  # noqa: F401
 from .iterative import filter_coefficients, spectral_bound  # noqa: F401

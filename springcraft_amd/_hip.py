@@ -66,6 +66,8 @@ EXPORTED_SYMBOLS = [
     "sc_dev_subsystem_blocks_f64", "sc_dev_subsystem_reduce_f64", "sc_dev_subsystem_follow_f64",
     "sc_dev_vsa_batch_workspace", "sc_dev_vsa_batch_blocks_f64", "sc_dev_vsa_batch_reduce_f64",
     "sc_dev_net_weights_f64", "sc_dev_net_paths_f64", "sc_dev_net_workspace", "sc_dev_net_usage",
+    "sc_cluster_workspace", "sc_cluster_form", "sc_dev_cluster_gromos_init_f64", "sc_dev_cluster_gromos_rounds",
+    "sc_dev_cluster_kmedoids_init_f64", "sc_dev_cluster_kmedoids_swaps_f64",
 ]
 
 SC_SEL_FROM_ROW = 0
@@ -295,6 +297,12 @@ def lib():
         "sc_dev_net_paths_f64": (i32, [vp, vp, i64, i64, vp, vp, vp, vp]),
         "sc_dev_net_workspace": (i64, [i64]),
         "sc_dev_net_usage": (i32, [vp, vp, i64, i64, i64, vp, vp, vp]),
+        "sc_cluster_workspace": (i64, [i64, i64]),
+        "sc_cluster_form": (i32, [i64, i64]),
+        "sc_dev_cluster_gromos_init_f64": (i32, [vp, vp, i64, dbl, vp, C.c_size_t, vp, vp]),
+        "sc_dev_cluster_gromos_rounds": (i32, [vp, i64, i64, i64, vp, C.c_size_t, vp, vp, vp, vp]),
+        "sc_dev_cluster_kmedoids_init_f64": (i32, [vp, vp, i64, i64, vp, C.c_size_t, vp, vp, vp, vp, i64, vp]),
+        "sc_dev_cluster_kmedoids_swaps_f64": (i32, [vp, vp, i64, i64, i64, vp, C.c_size_t, vp, vp, vp, vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

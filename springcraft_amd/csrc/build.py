@@ -33,6 +33,7 @@ PER_FILE = {
     "pair_operator.hip": ["-ffp-contract=off"],
     "pair_panel.hip": ["-ffp-contract=off"],   # (the same promise for a column of a panel)
     "pair_cg.hip": ["-ffp-contract=off"],   # (the panel step's walk and bits, and one rounding per written operation)
+    "cluster.hip": ["-ffp-contract=off"],   # (every sum of the k-medoids kernels is the additions written, in their fixed order)
     # k_bt2_apply's diamond loop is 80 fully unrolled steps per half-diamond (every register index must be a constant):
     # above LLVM's default budget for `#pragma unroll`, below which the accumulators would live in scratch memory
     "bt2.hip": ["-mllvm", "-pragma-unroll-threshold=1000000"],

@@ -392,6 +392,37 @@ class Ensemble:
         index = torch.arange(self.n_frames, device=self.device)
         return torch.where(total == total.min(), index, torch.full_like(index, self.n_frames)).min().clamp(max=self.n_frames - 1)
 
+    def cluster(self, method="gromos", cutoff=None, k=None, fit=True, squared=False, **options):
+        """
+        The frames put into clusters by their pairwise RMSD: a :class:`~springcraft_amd.cluster.Clustering` of CUDA
+        tensors from ``rmsd_matrix(fit=fit, squared=squared)``, which is handed to the kernels where it is, not copied.
+        ``method="gromos"`` with ``cutoff`` (in the matrix' units: squared with ``squared``) is
+        :func:`~springcraft_amd.cluster.cluster_gromos`, ``method="kmedoids"`` with ``k``
+        :func:`~springcraft_amd.cluster.cluster_kmedoids`; ``options`` go to them (``max_clusters``, ``max_iter``,
+        ``check_every``).  A frame with a non-finite coordinate gets label -1.  ``k=1, squared=True`` gives :meth:`medoid`.
+        ValueError before any device work for an unknown method, a method without its parameter or a parameter out of range.
+        """
+        from . import cluster as _cluster
+
+        if method == "gromos":
+            if k is not None:
+                raise ValueError("method 'gromos' takes a cutoff, not k")
+            _cluster.check_gromos_args(self.n_frames, cutoff, options.get("max_clusters"), options.get("check_every", 32))
+        elif method == "kmedoids":
+            if cutoff is not None:
+                raise ValueError("method 'kmedoids' takes k, not a cutoff")
+            _cluster.check_kmedoids_args(self.n_frames, k, options.get("max_iter", 100), options.get("check_every", 4))
+        else:
+            raise ValueError(f"method must be 'gromos' or 'kmedoids', got {method!r}")
+        unknown = set(options) - ({"max_clusters", "check_every"} if method == "gromos" else {"max_iter", "check_every"})
+        if unknown:
+            raise ValueError(f"method {method!r} does not take {sorted(unknown)}")
+        _cluster.workspace_bytes(self.n_frames, 0 if method == "gromos" else int(k))
+        dist = self.rmsd_matrix(fit=fit, squared=squared)
+        if method == "gromos":
+            return _cluster.cluster_gromos(dist, cutoff, **options)
+        return _cluster.cluster_kmedoids(dist, k, **options)
+
     def deviations(self):
         """(M, N, 3) CUDA tensor, every frame minus the mean frame: displacement vectors for ``overlap()``."""
         return (self.frames - self.mean()[None, :, :]).contiguous()
