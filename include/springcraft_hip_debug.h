@@ -92,10 +92,13 @@ int sc_dbg_gemm_stamps(unsigned long long* out4, int reset);
  * the last reset; returns the number of records written through *count.  tools/gemm_trace.py */
 int sc_dbg_gemm_trace(unsigned long long* out, int max_records, int* count, int reset);
 
-/* The reduction stage of a full-spectrum solve on host data, with its factors: `batch` matrices a (batch x n x n, NumPy
+/* The stages of a solve on host data (csrc/eigh_debug.hip), on the drivers' own plan and reduction step (csrc/eigh_plan.h).
+ *
+ * The reduction stage of a full-spectrum solve on host data, with its factors: `batch` matrices a (batch x n x n, NumPy
  * layout, lower triangle read) go through the scaling pass and the tridiagonalisation the product would choose for (ctx, n,
- * batch) -- the plan of sc_dev_eigh_f64, with sc_ctx_set_two_stage, sc_dbg_set_chase, sc_dbg_set_panel_coop[_fail] and
- * sc_dbg_set_resident honoured -- and the product's back-transformation is applied to Z = I.  No kernel of its own.
+ * batch) -- the plan of sc_dev_eigh_f64 (csrc/eigh_policy.h:two_stage_for), with sc_ctx_set_two_stage, sc_dbg_set_chase,
+ * sc_dbg_set_panel_coop[_fail] and sc_dbg_set_resident honoured -- and the product's back-transformation is applied to
+ * Z = I.  No kernel of its own.
  *   d_out, e_out   batch x n each: the tridiagonal T (e[n - 1] = 0)
  *   scale_out      null, or batch: the power of two s the matrix was multiplied by, so that  s A = Q T Q^T
  *   band_out       null, or batch x (128 x n), two-stage path only: the band B after stage 1, B(i, j) at [(i - j) + 128 j]

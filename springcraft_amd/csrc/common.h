@@ -130,6 +130,12 @@ struct sc_ctx {
   int chase_tickets[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // workgroups per XCD of the most recent chase launch (chase_ctl_xcds of them)
   int chase_wait[3] = {-1, -1, -1};                  // (matrix, sweep, task) of the wait that timed out last
   bool profiling = false;
+  // the most recent profiled eigensolve, ms (sc_last_eigh_timings): the three phases between the solve's four events, then
+  // SYMV / SYR2K sums (one-stage) or band reduction / bulge chasing (two-stage); kTimeBt2 names the path as well: the
+  // fused back-transformation of the stage-2 reflectors (two-stage with vectors), or one of the two markers
+  enum { kTimeTridiag = 0, kTimeEigen = 1, kTimeBacktransform = 2, kTimeStageA = 3, kTimeStageB = 4, kTimeBt2 = 5 };
+  static constexpr double kTimeOneStage = 0.0;            // kTimeBt2 of a one-stage solve
+  static constexpr double kTimeTwoStageValues = 1e-9;     // kTimeBt2 of a two-stage solve without vectors
   double last_timings[6] = {0, 0, 0, 0, 0, 0};
   // named kernel-group durations of the most recent profiled eigensolve (sc_last_eigh_phase_ms)
   std::vector<std::pair<std::string, double>> phases;

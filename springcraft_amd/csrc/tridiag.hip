@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "eigh_internal.h"
+#include "eigh_policy.h"
 #include "host_logic.h"
 
 namespace {
@@ -1178,17 +1179,15 @@ struct ResPlan {
   size_t lds;
 };
 bool resident_enabled(const sc_ctx* ctx) {
-  static const int env_mode = [] { const char* e = getenv("SPRINGCRAFT_RESIDENT"); return e ? atoi(e) : -1; }();
-  const int mode = (ctx && ctx->resident_mode >= 0) ? ctx->resident_mode : env_mode;
+  const int mode = (ctx && ctx->resident_mode >= 0) ? ctx->resident_mode : sc_host::eigh_env().resident;
   return mode != 0 && !(ctx && ctx->resident_ok == 0);
 }
 static bool resident_plan(sc_ctx* ctx, int n, int batch, int nb, ResPlan* out) {
-  static const int env_wgs = [] { const char* e = getenv("SPRINGCRAFT_RESIDENT_WGS"); return e ? atoi(e) : 0; }();
-  static const int env_max = [] { const char* e = getenv("SPRINGCRAFT_RESIDENT_MAX"); return e ? atoi(e) : 0; }();
   if (!resident_enabled(ctx) || batch != 1) return false;
+  const sc_host::EighEnv& E = sc_host::eigh_env();
   sc_host::ResidentShape S{};
-  const int want = ctx->resident_wgs > 0 ? ctx->resident_wgs : env_wgs;
-  if (!sc_host::resident_shape(n, nb, ctx->num_cus > 0 ? ctx->num_cus : 256, env_max, want, &S)) return false;
+  const int want = ctx->resident_wgs > 0 ? ctx->resident_wgs : E.resident_wgs;
+  if (!sc_host::resident_shape(n, nb, ctx->num_cus > 0 ? ctx->num_cus : 256, E.resident_max, want, &S)) return false;
   ResPlan R{};
   R.off = S.off; R.m = S.m; R.P = S.P; R.logP = S.logP; R.Q = S.Q; R.reg = S.reg; R.lds = S.lds_bytes;
   *out = R;
@@ -1211,8 +1210,7 @@ static int launch_resident_q(sc_ctx* ctx, const ResArgs& g, const ResPlan& R, in
 static std::mutex g_resident_mu;
 static int resident_chain(sc_ctx* ctx, hipStream_t st, bool before) {
   static std::map<int, hipEvent_t> last;
-  static const bool off = getenv("SPRINGCRAFT_RESIDENT_NO_CHAIN") != nullptr;   // (diagnostic: what the chain is for)
-  if (off) return SC_OK;
+  if (sc_host::eigh_env().resident_no_chain) return SC_OK;   // (diagnostic: what the chain is for)
   auto it = last.find(ctx->device);
   if (before) {
     if (it != last.end()) SC_HIP(ctx, hipStreamWaitEvent(st, it->second, 0));
@@ -1238,8 +1236,7 @@ static int launch_resident(sc_ctx* ctx, double* d_a, long long stride_a, int bat
   g.hook = ctx->resident_hook;
   // (the first poll a microsecond or so after the publication: polls that come back empty slow the stores they wait
   // for -- all workgroups read all records --; n = 1536: 14.3 ms without the pause, 11.7 with 24 x 64 cycles, 13.8 with 64)
-  static const int env_delay = [] { const char* e = getenv("SPRINGCRAFT_RESIDENT_DELAY"); return e ? atoi(e) : 24; }();
-  g.delay = env_delay;
+  g.delay = sc_host::eigh_env().resident_delay;
   g.status = ctx->d_status;
   for (int b = 0; b < batch; ++b)
     SC_HIP(ctx, hipMemsetAsync(d_ws + (size_t)b * L.slab + L.rctl, 0xFF, tri_resident_bytes(L.n), st));

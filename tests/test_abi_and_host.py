@@ -233,6 +233,60 @@ def test_host_logic_under_sanitizers(tmp_path):
     assert r.returncode == 0 and "host logic ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
 
 
+EIGH_ENV = ("SPRINGCRAFT_NB", "SPRINGCRAFT_TWO_STAGE", "SPRINGCRAFT_NO_AUX", "SPRINGCRAFT_AUX_SINGLE", "SPRINGCRAFT_RESIDENT",
+            "SPRINGCRAFT_RESIDENT_WGS", "SPRINGCRAFT_RESIDENT_MAX", "SPRINGCRAFT_RESIDENT_NO_CHAIN", "SPRINGCRAFT_RESIDENT_DELAY")
+
+
+def test_eigh_policy_under_sanitizers(tmp_path):
+    """
+    The eigensolver's top-level policy (csrc/eigh_policy.h: panel width, one-stage or two-stage, what forks onto the second
+    stream) compiled with g++ under ASan + UBSan and checked against literals (tests/host_sanitize/test_eigh_policy.cpp).
+    """
+    import os
+    import shutil
+    import subprocess
+
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = str(tmp_path / "test_eigh_policy")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-I", join(ROOT, "include"), "-I", join(ROOT, "springcraft_amd", "csrc"),
+           join(ROOT, "tests", "host_sanitize", "test_eigh_policy.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0 and ("asan" in r.stderr.lower() or "ubsan" in r.stderr.lower()) and "cannot find" in r.stderr:
+        pytest.skip("sanitizer runtimes not installed")
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = {k: v for k, v in os.environ.items() if k not in EIGH_ENV}
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0 and "eigh policy ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+
+
+# sc_eigh_workspace_bytes(n, batch, want_vectors = 0 / 1) of the revision before the drivers shared one plan (taken from that
+# revision's library on the host: the function needs neither a context nor a device), default environment
+EIGH_WORKSPACE_BYTES = {
+    (1, 1): (9472, 2914048),
+    (63, 1): (139264, 4261376),
+    (300, 1): (662528, 13465088),
+    (300, 4): (2646016, 53854720),
+    (520, 64): (1159998464, 2611284992),
+    (2000, 16): (1762477568, 3751801600),
+    (6000, 4): (3100750336, 6128908800),
+    (8000, 1): (1376765440, 2642096896),
+}
+
+
+def test_eigh_workspace_totals_unchanged():
+    """One plan for every kind of solve carves the full-spectrum workspace to the byte as the two plans before it did."""
+    import os
+
+    from springcraft_amd import _hip
+
+    L = _hip.lib()
+    for (n, batch), want in EIGH_WORKSPACE_BYTES.items():
+        got = (L.sc_eigh_workspace_bytes(n, batch, 0), L.sc_eigh_workspace_bytes(n, batch, 1))
+        assert got == want, (n, batch, got, want, "set in the environment:", [k for k in EIGH_ENV if k in os.environ])
+
+
 def test_hip_sources_compile_without_warnings(tmp_path):
     """
     Every HIP source compiles for gfx950 with -Wall and no warning (a missing return slipped through once in round 2 and

@@ -3,7 +3,7 @@ Full-spectrum solves above the divide & conquer's LDS limits (orders 7000 .. 990
 
 Below n = 7000 every merge of the D&C keeps its sorted copies (k_dc_setup, 22 B per element) and its poles
 (k_dc_secular, 16 B per pole) in LDS; from 7001 / 9801 on the top merge works from global scratch (stedc.hip,
-kLdsCapSetup / kLdsCapSecular), and one matrix goes two-stage from 7001 on (eigh.hip, two_stage_for) -- the path
+kLdsCapSetup / kLdsCapSecular), and one matrix goes two-stage from 7001 on (eigh_policy.h, two_stage_for) -- the path
 ``ANM(coord, ff).eigen()`` takes for a structure of more than 2333 residues.  The references are exact in closed form
 wherever possible: elastic networks on a cubic lattice (spacing 3.8 A, cutoff 4.5 A: only axis neighbours are in
 contact) have the spectra of sums of path graphs,
