@@ -890,6 +890,30 @@ int sc_dev_ensemble_pca_f64(sc_ctx* ctx, const double* d_frames, int64_t n_frame
 int64_t sc_rmsd_matrix_workspace(int64_t n_a, int64_t n_b, int64_t n_atoms);
 int sc_dev_rmsd_matrix_f64(sc_ctx* ctx, const double* d_a, int64_t n_a, const double* d_b, int64_t n_b, int64_t n_atoms,
                            const double* d_weights, int flags, double* d_out);
+/* The neighbour bits of the frames of one ensemble without the matrix: what neighbour-count clustering needs of the (n, n)
+ * RMSD matrix is `value <= cutoff`, 1 bit per ordered pair instead of 8 bytes, and the product kernel of the matrix writes
+ * those bits from its registers.  words = ceil(n / 64); flags as above; cutoff in the value's units (squared with bit 1).
+ * d_adj (n, words) uint64: bit g & 63 of word g >> 6 of row f is set when both frames are finite and the value the matrix
+ * entry would write for (f, g) is <= cutoff, or f = g: the same double, compared.  A non-finite frame's row and column are
+ * zero, the bits of the columns >= n of the last word are zero, d_adj equals its transpose bit for bit, and every word is
+ * written exactly once: no memset, no atomics, two calls agree bit for bit.  d_count (n) int32: the rows' popcounts, a
+ * frame's number of neighbours, itself included.  d_valid (words) uint64: the finite frames.
+ *
+ * sc_dev_frame_neighbours_init_f64 writes them into d_ws, a neighbour-count workspace of ws_bytes >=
+ * sc_cluster_workspace(n, 0) bytes, with the alive set, d_labels (n, all -1) and d_status (valid frames, 0, 0, 0): the state
+ * sc_dev_cluster_gromos_init_f64 leaves from the stored matrix, so sc_dev_cluster_gromos_rounds runs on it unchanged.
+ * status[2] stays 0: a NaN pair exists only where a frame is not finite.
+ *
+ * Both occupy sc_rmsd_matrix_workspace(n, 0, n_atoms) bytes of context scratch and only enqueue.  SC_ERR_INVALID_ARG
+ * before anything is launched: non-positive sizes, unknown flag bits, more frames than clustering takes (262144), sizes for
+ * which sc_rmsd_matrix_workspace answers -1, a cutoff that is negative or not finite, a NULL pointer, a workspace that is
+ * too small. */
+int sc_dev_frame_neighbours_f64(sc_ctx* ctx, const double* d_frames, int64_t n_frames, int64_t n_atoms,
+                                const double* d_weights, int flags, double cutoff, uint64_t* d_adj, int32_t* d_count,
+                                uint64_t* d_valid);
+int sc_dev_frame_neighbours_init_f64(sc_ctx* ctx, const double* d_frames, int64_t n_frames, int64_t n_atoms,
+                                     const double* d_weights, int flags, double cutoff, void* d_ws, size_t ws_bytes,
+                                     int32_t* d_labels, int32_t* d_status);
 
 /* ---- dense Cholesky solver on the device (csrc/potrf.hip) ----------------------------------------------------------------
  * No reference counterpart (LAPACK: dpotrf / dpotrs).  `batch` symmetric positive definite matrices of one order n, float64,

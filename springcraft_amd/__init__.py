@@ -14,8 +14,8 @@ from .forcefield import *  # noqa: F401,F403
 from .gnm import *  # noqa: F401,F403
 from .interaction import *  # noqa: F401,F403
 from . import cluster, ensemble, iterative, network, nma  # noqa: F401
-from .cluster import Clustering, cluster_gromos, cluster_kmedoids  # noqa: F401
-from .ensemble import Ensemble, EssentialDynamics, rmsd_matrix, superimpose  # noqa: F401
+from .cluster import Clustering, cluster_gromos, cluster_gromos_frames, cluster_kmedoids  # noqa: F401
+from .ensemble import Ensemble, EssentialDynamics, FrameNeighbours, rmsd_matrix, superimpose  # noqa: F401
 from .network import CorrelationNetwork, correlation_network, shortest_paths  # noqa: F401
 from .iterative import filter_coefficients, spectral_bound  # noqa: F401
 from .pair_operator import PairOperator  # noqa: F401

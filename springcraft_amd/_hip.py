@@ -62,6 +62,7 @@ EXPORTED_SYMBOLS = [
     "sc_dev_pairs_cg_workspace", "sc_dev_pairs_cg_init_f64", "sc_dev_pairs_cg_step_f64",
     "sc_superpose_form", "sc_dev_superpose_f64", "sc_dev_ensemble_mean_f64", "sc_dev_ensemble_pca_f64",
     "sc_rmsd_matrix_workspace", "sc_dev_rmsd_matrix_f64",
+    "sc_dev_frame_neighbours_f64", "sc_dev_frame_neighbours_init_f64",
     "sc_dev_potrf_workspace", "sc_dev_potrf_f64", "sc_dev_potrs_f64",
     "sc_dev_subsystem_blocks_f64", "sc_dev_subsystem_reduce_f64", "sc_dev_subsystem_follow_f64",
     "sc_dev_vsa_batch_workspace", "sc_dev_vsa_batch_blocks_f64", "sc_dev_vsa_batch_reduce_f64",
@@ -284,6 +285,8 @@ def lib():
         "sc_dev_ensemble_pca_f64": (i32, [vp, vp, i64, i64, vp, vp, i64, vp, vp, vp, vp]),
         "sc_rmsd_matrix_workspace": (i64, [i64, i64, i64]),
         "sc_dev_rmsd_matrix_f64": (i32, [vp, vp, i64, vp, i64, i64, vp, i32, vp]),
+        "sc_dev_frame_neighbours_f64": (i32, [vp, vp, i64, i64, vp, i32, dbl, vp, vp, vp]),
+        "sc_dev_frame_neighbours_init_f64": (i32, [vp, vp, i64, i64, vp, i32, dbl, vp, C.c_size_t, vp, vp]),
         "sc_dev_potrf_workspace": (i32, [i64, i64, P(C.c_size_t)]),
         "sc_dev_potrf_f64": (i32, [vp, vp, i64, i64, i64, i64, vp]),
         "sc_dev_potrs_f64": (i32, [vp, vp, i64, i64, i64, i64, vp, i64, i64, i64, i32]),

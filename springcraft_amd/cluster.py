@@ -17,7 +17,11 @@ counts nor is counted and is never a representative.  A NaN between two valid it
 there are no clusters.  An item is always its own neighbour.  Ties go to the lowest index, two calls agree bit for bit.
 Kernels enqueue; the host reads four int32 every ``check_every`` rounds and nothing else comes back.
 
-Not built: hierarchical linkage, silhouettes, batches of matrices, a matrix-free form that never stores ``dist``.
+:func:`cluster_gromos_frames` (and ``Ensemble.cluster(..., matrix_free=True)``) is the matrix-free form of the first: the
+RMSD product kernel writes ``rmsd <= cutoff`` as bits straight into the run's workspace (``csrc/rmsd_matrix.hip``) and the
+(M, M) float64 matrix is never stored, 64 times less memory; the rounds are the same.
+
+Not built: hierarchical linkage, silhouettes, batches of matrices, matrix-free k-medoids (PAM reads ``dist`` in every pass).
 """
 
 import ctypes as C
@@ -26,7 +30,7 @@ import numpy as np
 
 from . import _hip
 
-__all__ = ["Clustering", "cluster_gromos", "cluster_kmedoids", "MAX_ITEMS", "MAX_MEDOIDS"]
+__all__ = ["Clustering", "cluster_gromos", "cluster_gromos_frames", "cluster_kmedoids", "MAX_ITEMS", "MAX_MEDOIDS"]
 
 #: the limits of ``csrc/cluster_policy.h``: an item is an int32 and a row a workgroup; a row's per-slot sums are held in LDS
 MAX_ITEMS = 262144
@@ -216,6 +220,22 @@ def cluster_gromos(dist, cutoff, max_clusters=None, check_every=32, device=None)
     cut, max_clusters, check_every = check_gromos_args(n, cutoff, max_clusters, check_every)
     size = workspace_bytes(n, 0)
     torch, dev, ctx, mat = _open(dist, host, device)
+
+    def init(ws, labels, status):
+        ctx.check(_hip.lib().sc_dev_cluster_gromos_init_f64(ctx.handle, _p(mat), n, cut, _p(ws), size, _p(labels), _p(status)))
+
+    out = _gromos_run(torch, dev, ctx, host, n, size, max_clusters, check_every, init, keep=(mat,))
+    if host:
+        ctx.synchronize()
+    return out
+
+
+def _gromos_run(torch, dev, ctx, host, n, size, max_clusters, check_every, init, keep=()):
+    """
+    A neighbour-count run of ``n`` items whose workspace ``init(ws, labels, status)`` fills, from a stored matrix
+    (:func:`cluster_gromos`) or from the frames (:func:`cluster_gromos_frames`): the buffers, the rounds in chunks of
+    ``check_every`` with one status read each, or exactly ``max_clusters`` rounds and no read.  Arguments checked already.
+    """
     L = _hip.lib()
     cap = n if max_clusters is None else max_clusters
     with torch.cuda.device(dev):
@@ -224,8 +244,8 @@ def cluster_gromos(dist, cutoff, max_clusters=None, check_every=32, device=None)
         reps = torch.empty((cap,), dtype=torch.int32, device=dev)
         sizes = torch.empty((cap,), dtype=torch.int32, device=dev)
         status = torch.empty((4,), dtype=torch.int32, device=dev)
-        out = Clustering("gromos", torch, ctx, host, labels, reps, sizes, status, keep=(mat, ws))
-        ctx.check(L.sc_dev_cluster_gromos_init_f64(ctx.handle, _p(mat), n, cut, _p(ws), size, _p(labels), _p(status)))
+        out = Clustering("gromos", torch, ctx, host, labels, reps, sizes, status, keep=tuple(keep) + (ws,))
+        init(ws, labels, status)
 
         def rounds(count):
             ctx.check(L.sc_dev_cluster_gromos_rounds(ctx.handle, n, count, cap, _p(ws), size, _p(labels), _p(reps),
@@ -240,8 +260,57 @@ def cluster_gromos(dist, cutoff, max_clusters=None, check_every=32, device=None)
                 done += min(check_every, n - done)
                 if out._read_status()[0] == 0:
                     break
-    if host:
-        ctx.synchronize()
+    return out
+
+
+def check_frame_counts(n_frames, n_atoms):
+    """ValueError for more frames than clustering takes, or frames the RMSD product cannot index: host arithmetic only."""
+    workspace_bytes(n_frames, 0)
+    if int(_hip.lib().sc_rmsd_matrix_workspace(int(n_frames), 0, int(n_atoms))) < 0:
+        raise ValueError(f"{n_frames} frames of {n_atoms} atoms are beyond the kernels' index range")
+
+
+def gromos_from_frames(ens, cutoff, fit=True, squared=False, max_clusters=None, check_every=32, host=False):
+    """
+    Neighbour-count clustering of the frames of the :class:`~springcraft_amd.Ensemble` ``ens`` without the RMSD matrix:
+    the product kernel fills the run's workspace with the neighbour bits (``sc_dev_frame_neighbours_init_f64``), then the
+    rounds of :func:`cluster_gromos`.  A :class:`Clustering` of CUDA tensors (``host``: of NumPy arrays).
+    """
+    n = ens.n_frames
+    cut, max_clusters, check_every = check_gromos_args(n, cutoff, max_clusters, check_every)
+    check_frame_counts(n, ens.n_atoms)
+    size = workspace_bytes(n, 0)
+    flags = (1 if fit else 0) | (2 if squared else 0)
+
+    def init(ws, labels, status):
+        ens.ctx.check(_hip.lib().sc_dev_frame_neighbours_init_f64(ens.ctx.handle, _p(ens.frames), n, ens.n_atoms, _p(ens._w),
+                                                                  flags, cut, _p(ws), size, _p(labels), _p(status)))
+
+    return _gromos_run(ens.torch, ens.device, ens.ctx, host, n, size, max_clusters, check_every, init, keep=(ens.frames, ens._w))
+
+
+def cluster_gromos_frames(coords, cutoff, weights=None, fit=True, squared=False, max_clusters=None, check_every=32, device=None):
+    """
+    Neighbour-count clustering of the frames ``coords`` (M, N, 3) by their pairwise RMSD, matrix-free: host arrays in, a
+    :class:`Clustering` of NumPy arrays out, like ``rmsd_matrix(coords, ...)`` followed by :func:`cluster_gromos` on its
+    result, with the same labels, centres and sizes, but the (M, M) float64 matrix is never stored: the device holds
+    M^2 / 8 bytes of neighbour bits instead of 8 M^2, so ``MAX_ITEMS`` frames fit where 60 000 did.  ``weights``, ``fit``
+    and ``squared`` as in :meth:`Ensemble.rmsd_matrix <springcraft_amd.Ensemble.rmsd_matrix>`; ``cutoff`` in the value's
+    units.
+
+    ValueError before any device work: coordinates that are not (M, N, 3), a cutoff that is negative or not finite, weights
+    that are negative or not finite, ``max_clusters`` or ``check_every`` below 1, more than ``MAX_ITEMS`` frames.
+    """
+    from . import ensemble as _ensemble
+
+    a = _ensemble._host_frames(coords)
+    w = _ensemble._checked_weights(weights, a.shape[1])
+    check_gromos_args(a.shape[0], cutoff, max_clusters, check_every)
+    check_frame_counts(a.shape[0], a.shape[1])
+    ens = _ensemble.Ensemble(a, weights=w, device=device)
+    out = gromos_from_frames(ens, cutoff, fit=fit, squared=squared, max_clusters=max_clusters, check_every=check_every,
+                             host=True)
+    ens.ctx.synchronize()
     return out
 
 

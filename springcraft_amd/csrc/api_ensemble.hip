@@ -1,6 +1,10 @@
 // C ABI (include/springcraft_hip.h), device-pointer entries of the conformational ensembles: superposition and the mean frame
-// (superpose.hip), ensemble PCA (ensemble_pca.hip), the pairwise RMSD matrix (rmsd_matrix.hip).  Argument checks, the scratch carve, the launcher call.
+// (superpose.hip), ensemble PCA (ensemble_pca.hip), the pairwise RMSD matrix and the frames' neighbour bits
+// (rmsd_matrix.hip).  Argument checks, the scratch carve, the launcher call.
+#include <cmath>
+
 #include "api_internal.h"
+#include "cluster_policy.h"
 #include "ensemble_internal.h"
 
 namespace {
@@ -10,6 +14,23 @@ int ensemble_sizes_check(sc_ctx* ctx, const char* what, int64_t n_frames, int64_
     return sc_set_error(ctx, SC_ERR_INVALID_ARG, "%s: the numbers of frames and atoms must be positive", what);
   if (n_frames > 0x7fffffffLL || n_atoms > 0x7fffffffLL / 3)
     return sc_set_error(ctx, SC_ERR_INVALID_ARG, "%s: at most 2^31 - 1 frames and coordinates per frame", what);
+  return SC_OK;
+}
+
+// the checks the two neighbour-bit entries share: what the product kernel and the clustering kernels can index, the flags
+// of the RMSD matrix, a cutoff a comparison can be made with
+int frame_neighbours_check(sc_ctx* ctx, const char* what, int64_t n_frames, int64_t n_atoms, int flags, double cutoff) {
+  if (n_frames <= 0 || n_atoms <= 0)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "%s: the numbers of frames and atoms must be positive", what);
+  if (flags & ~3) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "%s: flags has bits 0 (fit) and 1 (squared) only", what);
+  if (sc_host::cluster_shape_error(n_frames, 0))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "%s: at most %lld frames, got %lld", what, (long long)sc_host::kClusterMaxN,
+                        (long long)n_frames);
+  if (sc_host::rmsd_shape_error(n_frames, 0, n_atoms))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "%s: %lld frames of %lld atoms are beyond the kernels' index range", what,
+                        (long long)n_frames, (long long)n_atoms);
+  if (!(cutoff >= 0.0) || std::isinf(cutoff))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "%s: the cutoff must be finite and not negative, got %g", what, cutoff);
   return SC_OK;
 }
 
@@ -91,6 +112,42 @@ int sc_dev_rmsd_matrix_f64(sc_ctx* ctx, const double* d_a, int64_t n_a, const do
   sc_host::RmsdBufs B{};
   SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) { B = sc_host::rmsd_layout(a, n_a, d_b ? n_b : 0, n_atoms); }));
   return launch_rmsd_matrix(ctx, B, d_a, n_a, d_b, n_b, n_atoms, d_weights, (flags & 1) != 0, (flags & 2) != 0, d_out);
+}
+
+int sc_dev_frame_neighbours_f64(sc_ctx* ctx, const double* d_frames, int64_t n_frames, int64_t n_atoms,
+                                const double* d_weights, int flags, double cutoff, uint64_t* d_adj, int32_t* d_count,
+                                uint64_t* d_valid) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  SC_TRY(frame_neighbours_check(ctx, "frame neighbours", n_frames, n_atoms, flags, cutoff));
+  if (!d_frames || !d_adj || !d_count || !d_valid)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "frame neighbours: the frames, the bits, the counts and the validity words are required");
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  sc_host::RmsdBufs B{};
+  SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) { B = sc_host::rmsd_layout(a, n_frames, 0, n_atoms); }));
+  return launch_frame_neighbours(ctx, B, d_frames, n_frames, n_atoms, d_weights, (flags & 1) != 0, (flags & 2) != 0, cutoff,
+                                 d_adj, d_count, d_valid, nullptr, nullptr, nullptr, nullptr);
+}
+
+int sc_dev_frame_neighbours_init_f64(sc_ctx* ctx, const double* d_frames, int64_t n_frames, int64_t n_atoms,
+                                     const double* d_weights, int flags, double cutoff, void* d_ws, size_t ws_bytes,
+                                     int32_t* d_labels, int32_t* d_status) {
+  if (!ctx) return SC_ERR_INVALID_ARG;
+  const char* what = "frame neighbours init";
+  SC_TRY(frame_neighbours_check(ctx, what, n_frames, n_atoms, flags, cutoff));
+  if (!d_ws) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "%s: the workspace is required", what);
+  if (ws_bytes < sc_host::cluster_workspace_bytes(n_frames, 0))
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "%s: the workspace holds %zu bytes, sc_cluster_workspace asks for %zu", what,
+                        ws_bytes, sc_host::cluster_workspace_bytes(n_frames, 0));
+  sc_host::Arena ws(d_ws, ws_bytes);
+  const sc_host::ClusterBufs K = sc_host::cluster_layout(ws, n_frames, 0);
+  if (ws.overrun()) return sc_set_error(ctx, SC_ERR_INVALID_ARG, "%s: the workspace layout overran its buffer", what);
+  if (!d_frames || !d_labels || !d_status)
+    return sc_set_error(ctx, SC_ERR_INVALID_ARG, "%s: the frames, the labels and the status are required", what);
+  SC_HIP(ctx, hipSetDevice(ctx->device));
+  sc_host::RmsdBufs B{};
+  SC_TRY(carve_scratch(ctx, [&](sc_host::Arena& a) { B = sc_host::rmsd_layout(a, n_frames, 0, n_atoms); }));
+  return launch_frame_neighbours(ctx, B, d_frames, n_frames, n_atoms, d_weights, (flags & 1) != 0, (flags & 2) != 0, cutoff,
+                                 K.adj, K.count, K.valid, K.alive, d_labels, K.ctl, d_status);
 }
 
 }  // extern "C"

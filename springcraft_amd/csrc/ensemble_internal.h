@@ -20,3 +20,14 @@ int launch_ensemble_pca(sc_ctx* ctx, const sc_host::PcaPlan& P, const sc_host::P
 // ctx->scratch.  Enqueue only.
 int launch_rmsd_matrix(sc_ctx* ctx, const sc_host::RmsdBufs& B, const double* d_a, int64_t n_a, const double* d_b,
                        int64_t n_b, int64_t n_atoms, const double* d_weights, bool fit, bool squared, double* d_out);
+
+// rmsd_matrix.hip: the neighbour bits of the n frames d_frames (n, N, 3) without the matrix.  d_adj (n, cluster_words(n)):
+// bit g of row f is set when the value launch_rmsd_matrix would write for (f, g) is <= cutoff or f = g, both frames finite;
+// d_count (n): the rows' popcounts; d_valid (words): the finite frames.  Optional (null: not written): d_alive (words) <-
+// d_valid, d_labels (n) <- -1, and together d_ctl (kClusterCtlInts) <- 0, d_status (kClusterStatusInts) <- (finite frames,
+// 0, 0, 0): with all of them a neighbour-count run's workspace as launch_cluster_gromos_init leaves it.  B: rmsd_layout of
+// (n, 0, N) carved from ctx->scratch.  Enqueue only.
+int launch_frame_neighbours(sc_ctx* ctx, const sc_host::RmsdBufs& B, const double* d_frames, int64_t n, int64_t n_atoms,
+                            const double* d_weights, bool fit, bool squared, double cutoff, uint64_t* d_adj,
+                            int32_t* d_count, uint64_t* d_valid, uint64_t* d_alive, int32_t* d_labels, int32_t* d_ctl,
+                            int32_t* d_status);

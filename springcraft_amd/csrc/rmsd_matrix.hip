@@ -33,10 +33,27 @@
 //
 // Per (pair, atom): 9 multiply-adds = 18 flops on the matrix pipe; a tile reads 2 x 192 doubles of an atom for its 4096
 // pairs, 0.75 bytes per (pair, atom) from memory and the same again into LDS.  Per pair: one Jacobi in one lane.
+//
+// Neighbour bits (launch_frame_neighbours).  The same kernel with a second epilogue, for a self-comparison: instead of the
+// value a pair's bit, value <= cutoff, goes into the (n, ceil(n / 64)) bit matrix adj that neighbour-count clustering runs
+// on (cluster.hip), and the (n, n) matrix is never stored: 1 bit per ordered pair instead of 64.  pair_value is the one
+// value function of both epilogues, so a bit is the comparison of exactly the double the matrix would hold.  A 64 x 64
+// tile is one 64-bit word of 64 rows, word tile_g of the rows f0 .. f0 + 63.  Per (j, r) a wavefront's __ballot is 4 rows
+// (fk) x 16 columns (fr): bits 16 fk .. 16 fk + 15 are the columns 16 (gb0 + j) .. + 15 of row 16 fb + 4 r + fk, and the
+// lane fr = 0 of every 16-lane group stores them as quarter gb0 + j of that row's word, one uint16_t of a 64-word tile in
+// the staging LDS; the wavefronts w and w ^ 4 supply the two halves of a word.  Then 64 lanes store the rows' words and,
+// off the diagonal, 64 more the transposed words (bit i' of column i from row i' of the tile): word tile_f of the rows g0
+// .. g0 + 63.  A diagonal tile computes f > g only and ORs the tile with its transpose and the diagonal before its one
+// store.  The semantics are k_cluster_pack's: a valid frame (G not NaN) is its own neighbour, an invalid frame's row and
+// column are zero, the bits of the columns >= n of the last word are zero.  Every word of adj is written exactly once, by
+// one workgroup: no memset, no atomics, adj equals its transpose bit for bit.  k_neighbour_finish, one wavefront per row:
+// the row's popcount, label -1, the validity words from G and the status of a clustering run.
 #include <cmath>
+#include <cstdint>
 
 #include "block_sum.h"
 #include "eigh_internal.h"
+#include "cluster_policy.h"
 #include "ensemble_internal.h"
 
 namespace {
@@ -158,7 +175,37 @@ __device__ __forceinline__ double horn_lambda(const double (&S)[9]) {
   return best;
 }
 
+// The value of one pair from its nine sums (slot r of the accumulators S), the two frames' G and W: NaN when a frame is not
+// finite, exactly 0 for a frame with itself (`same`), else max(0, (Gf + Gg) - 2 lambda) / W or its root.  Both epilogues of
+// k_rmsd_product call this and nothing else.
+__device__ __forceinline__ double pair_value(const d4 (&S)[3][3], int r, double Gf, double Gg, double W, bool same, int fit,
+                                             int squared) {
+  const bool bad = Gf != Gf || Gg != Gg;
+  double v;
+  if (bad) {
+    v = __builtin_nan("");
+  } else if (same) {
+    v = 0.0;
+  } else {
+    double lambda;
+    if (fit) {
+      double s[9];
+#pragma unroll
+      for (int d = 0; d < 3; ++d)
+#pragma unroll
+        for (int e = 0; e < 3; ++e) s[3 * d + e] = S[d][e][r];
+      lambda = horn_lambda(s);
+    } else {
+      lambda = (S[0][0][r] + S[1][1][r]) + S[2][2][r];
+    }
+    v = fmax(0.0, (Gf + Gg) - 2.0 * lambda) / W;
+    if (!squared) v = sqrt(v);
+  }
+  return v;
+}
+
 struct RmsdArgs {
+  static constexpr bool kBits = false;
   const double* ya;   // (N_pad, 3, m_pad_a): the f side
   const double* yb;   // (N_pad, 3, m_pad_b): the g side; a self-comparison: ya
   const double* ga;   // (m_pad_a)
@@ -170,9 +217,22 @@ struct RmsdArgs {
   int tiles_b;            // 0: self-comparison, the triangle of tiles; else tiles along g
   int fit, squared;
 };
+// the bit epilogue's: a self-comparison (tiles_b = 0, n_b = n_a, out unused)
+struct NeighbourArgs : RmsdArgs {
+  static constexpr bool kBits = true;
+  unsigned long long* adj;   // (n_a, words)
+  long long words;
+  double cutoff;
+};
 
-// grid (tiles)
-__global__ __launch_bounds__(512) void k_rmsd_product(const RmsdArgs A) {
+typedef unsigned long long u64;
+// the bit tile in the staging buffer: written as uint16_t quarters, read as words
+typedef uint16_t __attribute__((may_alias)) tile_u16;
+typedef u64 __attribute__((may_alias)) tile_u64;
+
+// grid (tiles).  Args: RmsdArgs, the (n_a, n_b) matrix; NeighbourArgs, the neighbour bits of a self-comparison.
+template <class Args>
+__global__ __launch_bounds__(512) void k_rmsd_product(const Args A) {
   __shared__ double lds[kRows * kRowStride];
   const int tid = threadIdx.x;
   const bool self = A.tiles_b == 0;
@@ -243,38 +303,107 @@ __global__ __launch_bounds__(512) void k_rmsd_product(const RmsdArgs A) {
 
   const bool diag = self && tf == tg;
   const double W = A.wsum[0];
+  if constexpr (!Args::kBits) {
 #pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int g = g0 + 16 * (gb0 + j) + fr;
-    const double Gg = g < A.n_b ? A.gb[g] : 0.0;
+    for (int j = 0; j < 2; ++j) {
+      const int g = g0 + 16 * (gb0 + j) + fr;
+      const double Gg = g < A.n_b ? A.gb[g] : 0.0;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int f = f0 + 16 * fb + 4 * r + fk;
-      if (f >= A.n_a || g >= A.n_b || (diag && f < g)) continue;
-      const double Gf = A.ga[f];
-      const bool bad = Gf != Gf || Gg != Gg;
-      double v;
-      if (bad) {
-        v = __builtin_nan("");
-      } else if (diag && f == g) {
-        v = 0.0;
-      } else {
-        double lambda;
-        if (A.fit) {
-          double S[9];
-#pragma unroll
-          for (int d = 0; d < 3; ++d)
-#pragma unroll
-            for (int e = 0; e < 3; ++e) S[3 * d + e] = acc[j][d][e][r];
-          lambda = horn_lambda(S);
-        } else {
-          lambda = (acc[j][0][0][r] + acc[j][1][1][r]) + acc[j][2][2][r];
-        }
-        v = fmax(0.0, (Gf + Gg) - 2.0 * lambda) / W;
-        if (!A.squared) v = sqrt(v);
+      for (int r = 0; r < 4; ++r) {
+        const int f = f0 + 16 * fb + 4 * r + fk;
+        if (f >= A.n_a || g >= A.n_b || (diag && f < g)) continue;
+        const double v = pair_value(acc[j], r, A.ga[f], Gg, W, diag && f == g, A.fit, A.squared);
+        A.out[(size_t)f * A.n_b + g] = v;
+        if (self && f != g) A.out[(size_t)g * A.n_b + f] = v;
       }
-      A.out[(size_t)f * A.n_b + g] = v;
-      if (self && f != g) A.out[(size_t)g * A.n_b + f] = v;
+    }
+  } else {
+    const int n = A.n_a;
+    __syncthreads();   // every wavefront has read the last staged group: the buffer is free
+    tile_u16* tile16 = reinterpret_cast<tile_u16*>(lds);
+    const tile_u64* tile = reinterpret_cast<const tile_u64*>(lds);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int g = g0 + 16 * (gb0 + j) + fr;
+      const double Gg = g < n ? A.gb[g] : 0.0;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 16 * fb + 4 * r + fk, f = f0 + row;
+        bool in = false;
+        // (a NaN value, an invalid frame's, is not <= cutoff; the diagonal is set below)
+        if (f < n && g < n && !(diag && f <= g)) in = pair_value(acc[j], r, A.ga[f], Gg, W, false, A.fit, A.squared) <= A.cutoff;
+        const u64 m = __ballot(in);
+        if (fr == 0) tile16[4 * row + gb0 + j] = (uint16_t)(m >> (16 * fk));
+      }
+    }
+    __syncthreads();
+    if (tid < 128) {
+      const int i = tid & 63;
+      const bool across = tid >= 64;   // the transposed words: off the diagonal only
+      if (!(across && diag)) {
+        u64 word = 0, column = 0;
+        if (!across) word = tile[i];
+        if (across || diag)
+          for (int k = 0; k < 64; ++k) column |= ((tile[k] >> i) & 1ull) << k;
+        const int row = (across ? g0 : f0) + i;
+        if (row < n) {
+          if (diag) {
+            const double G = A.ga[row];
+            word |= column | (G == G ? 1ull << i : 0ull);
+          } else if (across) {
+            word = column;
+          }
+          A.adj[(size_t)row * A.words + (across ? tf : tg)] = word;
+        }
+      }
+    }
+  }
+}
+
+// grid (ceil(n / 4)), 256 threads: one wavefront per row of adj.  count[i] <- the row's popcount; labels[i] <- -1; the
+// wavefront of row 64 w: word w of valid (and alive) <- the frames whose G is not NaN.  Workgroup 0 also: ctl <- 0, status
+// <- (valid frames, 0, 0, 0).  alive, labels, ctl and status may be null (status and ctl together).
+__global__ __launch_bounds__(256) void k_neighbour_finish(const u64* __restrict__ adj, const double* __restrict__ G, long long n,
+                                                          long long words, int* __restrict__ count, u64* __restrict__ valid,
+                                                          u64* __restrict__ alive, int* __restrict__ labels,
+                                                          int* __restrict__ ctl, int* __restrict__ status) {
+  __shared__ int red[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long i = (long long)blockIdx.x * 4 + wave;
+  if (i < n) {
+    int c = 0;
+    for (long long w = lane; w < words; w += 64) c += __popcll(adj[i * words + w]);
+    for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off);
+    if (lane == 0) {
+      count[i] = c;
+      if (labels) labels[i] = -1;
+    }
+    if ((i & 63) == 0) {
+      bool ok = false;
+      if (i + lane < n) {
+        const double g = G[i + lane];
+        ok = g == g;
+      }
+      const u64 m = __ballot(ok);
+      if (lane == 0) {
+        valid[i >> 6] = m;
+        if (alive) alive[i >> 6] = m;
+      }
+    }
+  }
+  if (blockIdx.x == 0 && status) {   // (the whole workgroup)
+    int ok = 0;
+    for (long long j = threadIdx.x; j < n; j += 256) {
+      const double g = G[j];
+      ok += g == g;
+    }
+    for (int off = 32; off >= 1; off >>= 1) ok += __shfl_xor(ok, off);
+    if (lane == 0) red[wave] = ok;
+    __syncthreads();
+    if (threadIdx.x < sc_host::kClusterCtlInts) ctl[threadIdx.x] = 0;
+    if (threadIdx.x == 0) {
+      status[0] = ((red[0] + red[1]) + red[2]) + red[3];
+      status[1] = status[2] = status[3] = 0;
     }
   }
 }
@@ -302,7 +431,33 @@ int launch_rmsd_matrix(sc_ctx* ctx, const sc_host::RmsdBufs& B, const double* d_
   A.tiles_b = d_b ? (int)(mb / kTile) : 0;
   A.fit = fit; A.squared = squared;
   const unsigned tiles = (unsigned)sc_host::rmsd_tiles(n_a, d_b ? n_b : 0);
-  hipLaunchKernelGGL(k_rmsd_product, dim3(tiles), dim3(512), 0, st, A);
+  hipLaunchKernelGGL(k_rmsd_product<RmsdArgs>, dim3(tiles), dim3(512), 0, st, A);
+  SC_HIP(ctx, hipGetLastError());
+  return SC_OK;
+}
+
+int launch_frame_neighbours(sc_ctx* ctx, const sc_host::RmsdBufs& B, const double* d_frames, int64_t n, int64_t n_atoms,
+                            const double* d_weights, bool fit, bool squared, double cutoff, uint64_t* d_adj,
+                            int32_t* d_count, uint64_t* d_valid, uint64_t* d_alive, int32_t* d_labels, int32_t* d_ctl,
+                            int32_t* d_status) {
+  hipStream_t st = ctx->stream;
+  const long long n_pad = sc_host::rmsd_pad_atoms(n_atoms), m_pad = sc_host::rmsd_pad_frames(n);
+  const long long words = sc_host::cluster_words(n);   // (= m_pad / kTile: a tile is a word)
+  hipLaunchKernelGGL(k_rmsd_prepare, dim3((unsigned)m_pad), dim3(256), 0, st, d_frames, (long long)n, (long long)n_atoms,
+                     n_pad, m_pad, d_weights, fit ? nullptr : d_frames, B.ya, B.ga, B.wsum);
+  NeighbourArgs A{};
+  A.ya = A.yb = B.ya; A.ga = A.gb = B.ga;
+  A.wsum = B.wsum; A.out = nullptr;
+  A.m_pad_a = A.m_pad_b = m_pad;
+  A.n_a = A.n_b = (int)n;
+  A.groups = (int)(n_pad / kRows);
+  A.tiles_b = 0;
+  A.fit = fit; A.squared = squared;
+  A.adj = (u64*)d_adj; A.words = words; A.cutoff = cutoff;
+  hipLaunchKernelGGL(k_rmsd_product<NeighbourArgs>, dim3((unsigned)sc_host::rmsd_tiles(n, 0)), dim3(512), 0, st, A);
+  hipLaunchKernelGGL(k_neighbour_finish, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const u64*)d_adj,
+                     (const double*)B.ga, (long long)n, words, d_count, (u64*)d_valid, (u64*)d_alive, d_labels, d_ctl,
+                     d_status);
   SC_HIP(ctx, hipGetLastError());
   return SC_OK;
 }

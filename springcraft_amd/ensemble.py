@@ -5,7 +5,8 @@ superimpose with biotite; Bio3D: ``fit.xyz`` / ``pca.xyz``, ProDy: ``superpose``
 
 :func:`superimpose` is the host convenience for one or a few conformers, e.g. before ``nma.overlap(enm, fitted - fixed)``.
 :class:`Ensemble` keeps the frames on the device, fits them on a frame or iteratively on their mean
-(``csrc/superpose.hip``), gives the least-squares RMSD of every pair of frames (``csrc/rmsd_matrix.hip``) and turns them into :class:`EssentialDynamics`, the quasi-harmonic modes of the ensemble
+(``csrc/superpose.hip``), gives the least-squares RMSD of every pair of frames, or which pairs lie within a cutoff as a bit
+matrix (``csrc/rmsd_matrix.hip``), and turns them into :class:`EssentialDynamics`, the quasi-harmonic modes of the ensemble
 (``csrc/ensemble_pca.hip``): a mode source like :class:`~springcraft_amd.RTB`, with every mode consumer of the batch
 solvers and the comparisons ``rmsip`` / ``covariance_overlap`` / ``mode_overlap_matrix`` against an elastic network's modes.
 """
@@ -17,7 +18,7 @@ import numpy as np
 from . import _hip, atoms as _atoms
 from .batch import _BatchSolver, _UniformLayout
 
-__all__ = ["Ensemble", "EssentialDynamics", "superimpose", "rmsd_matrix"]
+__all__ = ["Ensemble", "EssentialDynamics", "FrameNeighbours", "superimpose", "rmsd_matrix"]
 
 
 # ---- host-side argument checks (before any device call) -----------------------------------------------------------------
@@ -193,6 +194,25 @@ class EssentialDynamics(_BatchSolver):
         self.ctx.synchronize()
         rank_check(self.variances.cpu().numpy(), self.n_frames, self.n_atoms)
         return self.w, self.v
+
+
+class FrameNeighbours:
+    """
+    What :meth:`Ensemble.neighbours` returns, CUDA tensors: ``bits`` (M, ceil(M / 64)) int64, bit ``g & 63`` of word
+    ``g >> 6`` of row f set when frames f and g are neighbours (equal to its transpose; the bits of the columns >= M of the
+    last word are 0); ``counts`` (M,) int32, the rows' popcounts: a frame's number of neighbours, itself included, 0 for a
+    non-finite frame; ``valid`` (ceil(M / 64),) int64, the bit set of the finite frames.  ``n_frames`` and ``cutoff`` as given.
+    """
+
+    def __init__(self, torch, n_frames, cutoff, bits, counts, valid):
+        self.torch, self.n_frames, self.cutoff = torch, n_frames, cutoff
+        self.bits, self.counts, self.valid = bits, counts, valid
+
+    def dense(self):
+        """(M, M) bool CUDA tensor of the bits, for inspection: M^2 bytes.  Only enqueues."""
+        torch = self.torch
+        shifts = torch.arange(64, dtype=torch.int64, device=self.bits.device)
+        return ((self.bits[:, :, None] >> shifts) & 1).bool().reshape(self.n_frames, -1)[:, : self.n_frames]
 
 
 class Ensemble:
@@ -392,7 +412,32 @@ class Ensemble:
         index = torch.arange(self.n_frames, device=self.device)
         return torch.where(total == total.min(), index, torch.full_like(index, self.n_frames)).min().clamp(max=self.n_frames - 1)
 
-    def cluster(self, method="gromos", cutoff=None, k=None, fit=True, squared=False, **options):
+    def neighbours(self, cutoff, fit=True, squared=False):
+        """
+        :class:`FrameNeighbours`: which frames lie within ``cutoff`` of which, ``rmsd_matrix(fit=fit, squared=squared) <=
+        cutoff`` as an (M, ceil(M / 64)) bit matrix and its row counts, written by the product kernel of the matrix without
+        the matrix: M^2 / 8 bytes, not 8 M^2.  A bit is the comparison of exactly the value ``rmsd_matrix`` would hold.  A
+        frame is its own neighbour; a frame with a non-finite coordinate has no neighbours and is nobody's.  The counts are
+        a density per frame, the bits a contact graph of conformers, and what ``cluster(matrix_free=True)`` runs on.
+        ValueError for a cutoff that is negative or not finite and for more than ``cluster.MAX_ITEMS`` frames.  Only enqueues.
+        """
+        from . import cluster as _cluster
+
+        cut = _cluster.check_gromos_args(self.n_frames, cutoff, None, 1)[0]
+        _cluster.check_frame_counts(self.n_frames, self.n_atoms)
+        torch, n = self.torch, self.n_frames
+        words = (n + 63) // 64
+        p = self._p
+        with torch.cuda.device(self.device):
+            bits = torch.empty((n, words), dtype=torch.int64, device=self.device)
+            counts = torch.empty((n,), dtype=torch.int32, device=self.device)
+            valid = torch.empty((words,), dtype=torch.int64, device=self.device)
+            self.ctx.check(self._L.sc_dev_frame_neighbours_f64(
+                self.ctx.handle, p(self.frames), n, self.n_atoms, p(self._w), (1 if fit else 0) | (2 if squared else 0), cut,
+                p(bits), p(counts), p(valid)))
+        return FrameNeighbours(torch, n, cut, bits, counts, valid)
+
+    def cluster(self, method="gromos", cutoff=None, k=None, fit=True, squared=False, matrix_free=False, **options):
         """
         The frames put into clusters by their pairwise RMSD: a :class:`~springcraft_amd.cluster.Clustering` of CUDA
         tensors from ``rmsd_matrix(fit=fit, squared=squared)``, which is handed to the kernels where it is, not copied.
@@ -400,10 +445,15 @@ class Ensemble:
         :func:`~springcraft_amd.cluster.cluster_gromos`, ``method="kmedoids"`` with ``k``
         :func:`~springcraft_amd.cluster.cluster_kmedoids`; ``options`` go to them (``max_clusters``, ``max_iter``,
         ``check_every``).  A frame with a non-finite coordinate gets label -1.  ``k=1, squared=True`` gives :meth:`medoid`.
+        ``matrix_free=True`` (``"gromos"`` only: k-medoids reads the matrix in every pass) never stores the matrix: the
+        product kernel writes the neighbour bits of :meth:`neighbours` into the run's workspace and the same rounds follow,
+        with the same result in 1 / 64 of the memory.
         ValueError before any device work for an unknown method, a method without its parameter or a parameter out of range.
         """
         from . import cluster as _cluster
 
+        if matrix_free and method == "kmedoids":
+            raise ValueError("matrix_free is for method 'gromos': k-medoids reads the matrix in every pass")
         if method == "gromos":
             if k is not None:
                 raise ValueError("method 'gromos' takes a cutoff, not k")
@@ -418,6 +468,8 @@ class Ensemble:
         if unknown:
             raise ValueError(f"method {method!r} does not take {sorted(unknown)}")
         _cluster.workspace_bytes(self.n_frames, 0 if method == "gromos" else int(k))
+        if matrix_free:
+            return _cluster.gromos_from_frames(self, cutoff, fit=fit, squared=squared, **options)
         dist = self.rmsd_matrix(fit=fit, squared=squared)
         if method == "gromos":
             return _cluster.cluster_gromos(dist, cutoff, **options)
