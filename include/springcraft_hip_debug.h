@@ -120,7 +120,7 @@ int sc_dbg_reduce_host(sc_ctx* ctx, const double* a, int n, int batch, int which
  * z_out batch x n x n, row k of the NumPy array = the eigenvector of w[k].  The call synchronises; a QL failure is
  * SC_ERR_NOCONV.  tests/test_stage_ratios_gpu.py */
 int sc_dbg_stedc_host(sc_ctx* ctx, const double* d, const double* e, int n, int batch, double* w_out, double* z_out);
-/* Rows of the largest leaf the D&C solves by QL at order n (DcLayout::leaf_max of dc_slab_doubles). */
+/* Rows of the largest leaf the D&C solves by QL at order n (kLeafMax of stedc_plan.h, the same at every order). */
 int sc_dbg_stedc_leaf_max(int n);
 
 /* The partial-spectrum stage (csrc/stein.hip) on `batch` tridiagonal matrices from the host, through the product's host

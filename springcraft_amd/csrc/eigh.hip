@@ -53,7 +53,7 @@ SolvePlan make_solve_plan(const sc_ctx* ctx, int n, int batch, bool vectors, Sol
   if (vectors) {
     if (!kind.partial) {
       P.off_dc = take(dc_slab_doubles(n, &P.DL) * 8 * batch);
-      P.n_mid_desc = 2 * dc_max_nodes(n, P.DL.leaf_max) * batch;   // two half-GEMMs per merge
+      P.n_mid_desc = 2 * dc_max_nodes(n) * batch;   // two half-GEMMs per merge
     } else if (kind.m_stein > 0) {
       P.off_stein = take(stein_workspace_doubles(n, kind.m_stein) * 8 * batch);
     }

@@ -170,8 +170,4 @@ extern "C" int sc_dbg_partial_tridiag_host(sc_ctx* ctx, const double* d, const d
   return SC_OK;
 }
 
-extern "C" int sc_dbg_stedc_leaf_max(int n) {
-  DcLayout DL;
-  (void)dc_slab_doubles(n, &DL);
-  return DL.leaf_max;
-}
+extern "C" int sc_dbg_stedc_leaf_max(int) { return sc_host::kLeafMax; }

@@ -4,6 +4,7 @@
 
 #include "common.h"
 #include "gemm_f64.h"
+#include "stedc_plan.h"
 
 // Per-matrix workspace slab of the tridiagonalisation (offsets in doubles from the slab base).
 struct TriLayout {
@@ -43,14 +44,17 @@ int tridiag_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, int bat
 // be null: the environment's answer)
 bool resident_enabled(const sc_ctx* ctx);
 
-// ---- divide & conquer ------------------------------------------------------------------------------
-struct DcNode {
-  int lo, mid, hi;
-};
+// ---- divide & conquer (stedc.hip) --------------------------------------------------------------------
+// The plan (stedc_plan.h) owns every decision: the merge tree of an order (DcNode, built once per solve inside
+// stedc_batched), the launch shapes and LDS bytes of the kernels of a merge level, which ping-pong buffer a level reads
+// and writes, and the layout of what the D&C keeps in sc_ctx::dc_aux (the uploaded tree, the profiling word, the sorted
+// copies of merges too wide for LDS) -- stedc_batched reserves and fills that buffer itself.  The caller owns the rest
+// and sizes it from the two functions below: per matrix a slab of dc_slab_doubles(n) doubles laid out by DcLayout, two
+// (batch, n, n) work matrices beside the output, and 2 * dc_max_nodes(n) * batch merge records.
+using sc_host::DcNode;
 
 struct DcLayout {
   int n;
-  int leaf_max;      // leaves have at most this many rows
   long long slab;    // per-matrix stride (doubles) of the D&C slab
   long long dd, ee;  // scaled copies of d, e (n each)
   long long w0, w1;  // eigenvalue ping-pong (n each)
@@ -78,9 +82,9 @@ struct DcLayout {
 int stedc_batched(sc_ctx* ctx, int n, int batch, const double* d_tri_ws, const TriLayout& TL,
                   double* d_dc_ws, const DcLayout& DL, double* d_w, long long stride_w,
                   double* d_q_out, double* d_q_tmp, double* d_u, long long stride_q,
-                  GemmDesc* d_merge_descs /* 2 * dc_max_nodes * batch */);
+                  GemmDesc* d_merge_descs /* 2 * dc_max_nodes(n) * batch */);
 size_t dc_slab_doubles(int n, DcLayout* out);
-int dc_max_nodes(int n, int leaf_max);
+int dc_max_nodes(int n);   // leaves and merges of the tree of order n
 
 // Eigenvalues only: Sturm-sequence bisection (one thread per eigenvalue).
 int sturm_bisect_batched(sc_ctx* ctx, int n, int batch, const double* d_tri_ws, const TriLayout& TL,

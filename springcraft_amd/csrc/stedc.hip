@@ -230,24 +230,13 @@ __global__ __launch_bounds__(1024) void k_dc_setup(double* __restrict__ dc_all, 
   const int tid = threadIdx.x, nthr = blockDim.x;
   const double* wold = ws + w_old_off;
 
-  double* sd;
-  double* sz;
-  int* scol;
-  unsigned char* smix;   // 1: the column has been mixed across the two halves by a deflation rotation
-  unsigned char* sflag;  // 1: negligible z component (dlaed2 type-1 deflation)
-  if (use_lds) {
-    sd = lds;
-    sz = lds + N;
-    scol = reinterpret_cast<int*>(lds + 2 * N);
-    smix = reinterpret_cast<unsigned char*>(scol + N);
-  } else {
-    double* base = gscratch + (size_t)b * gscratch_stride + 3LL * lo;
-    sd = base;
-    sz = base + N;
-    scol = reinterpret_cast<int*>(base + 2 * N);
-    smix = reinterpret_cast<unsigned char*>(scol + N);
-  }
-  sflag = smix + N;
+  const sc_host::DcSetupCarve sorted =
+      sc_host::dc_setup_carve(use_lds ? lds : gscratch + (size_t)b * gscratch_stride + (long long)sc_host::kSetupScratchDoubles * lo, N);
+  double* sd = sorted.d;
+  double* sz = sorted.z;
+  int* scol = sorted.col;
+  unsigned char* smix = sorted.mixed;   // 1: the column has been mixed across the two halves by a deflation rotation
+  unsigned char* sflag = sorted.flag;   // 1: negligible z component (dlaed2 type-1 deflation)
 
   const double rho_raw = ws[DL.ee + mid - 1];
   const double sgn = rho_raw < 0.0 ? -1.0 : 1.0;
@@ -806,61 +795,6 @@ __global__ void k_dc_unscale(const double* __restrict__ dc_all, DcLayout DL, lon
   if (i < DL.n) w_out[(size_t)blockIdx.y * stride_w + i] = ws[w_off + i] * ws[DL.scale];
 }
 
-// host-side tree ------------------------------------------------------------------------------------------------------
-struct Tree {
-  std::vector<DcNode> leaves;
-  std::vector<std::vector<DcNode>> levels;  // levels[0] merges leaves, back() is the root
-};
-
-Tree build_tree(int n, int leaf_max) {
-  int depth = 0;
-  while (((n + (1 << depth) - 1) >> depth) > leaf_max) ++depth;
-  // segments after `depth` halvings
-  std::vector<std::vector<DcNode>> by_depth(depth + 1);
-  by_depth[0].push_back(DcNode{0, n / 2, n});
-  for (int dlev = 0; dlev < depth; ++dlev) {
-    for (const DcNode& nd : by_depth[dlev]) {
-      by_depth[dlev + 1].push_back(DcNode{nd.lo, nd.lo + (nd.mid - nd.lo) / 2, nd.mid});
-      by_depth[dlev + 1].push_back(DcNode{nd.mid, nd.mid + (nd.hi - nd.mid) / 2, nd.hi});
-    }
-  }
-  Tree t;
-  t.leaves = by_depth[depth];
-  for (int dlev = depth - 1; dlev >= 0; --dlev) t.levels.push_back(by_depth[dlev]);
-  return t;
-}
-
-constexpr int kLeafMax = 32;
-constexpr int kLdsCapSetup = 7000;    // 22 B per element
-constexpr int kLdsCapSecular = 9800;  // 16 B per pole
-
-}  // namespace
-
-int dc_max_nodes(int n, int leaf_max) {
-  Tree t = build_tree(n, leaf_max);
-  size_t total = t.leaves.size();
-  for (auto& l : t.levels) total += l.size();
-  return (int)total;
-}
-
-size_t dc_slab_doubles(int n, DcLayout* out) {
-  DcLayout L{};
-  L.n = n;
-  L.leaf_max = kLeafMax;
-  long long off = 0;
-  const long long nn = ((long long)n + 7) / 8 * 8;
-  auto take = [&](long long cnt) { long long o = off; off += (cnt + 7) / 8 * 8; return o; };
-  L.dd = take(nn); L.ee = take(nn); L.w0 = take(nn); L.w1 = take(nn); L.z = take(nn);
-  L.dl = take(nn); L.zz = take(nn); L.ddef = take(nn); L.lam = take(nn); L.tauv = take(nn);
-  L.zhat = take(nn); L.rot_c = take(nn); L.rot_s = take(nn); L.scale = take(8);
-  L.src = take(nn); L.org = take(nn); L.dest = take(nn); L.rot_a = take(nn); L.rot_b = take(nn);
-  L.ktop_src = take(nn); L.ktop_k = take(nn); L.kbot_src = take(nn); L.kbot_k = take(nn);
-  L.cnt = take(2LL * dc_max_nodes(n, kLeafMax) + 8);
-  L.slab = off;
-  if (out) *out = L;
-  return (size_t)off;
-}
-
 // 2 m n k summed over the merge records (profiling: the sizes are decided on the device by k_dc_setup)
 __global__ __launch_bounds__(1024) void k_dc_desc_flops(const GemmDesc* __restrict__ d, int count, double* __restrict__ out) {
   __shared__ double part[16];
@@ -877,135 +811,158 @@ __global__ __launch_bounds__(1024) void k_dc_desc_flops(const GemmDesc* __restri
   }
 }
 
-int stedc_batched(sc_ctx* ctx, int n, int batch, const double* d_tri_ws, const TriLayout& TL,
-                  double* d_dc_ws, const DcLayout& DL, double* d_w, long long stride_w, double* d_q_out,
-                  double* d_q_tmp, double* d_u, long long stride_q, GemmDesc* d_merge_descs) {
-  hipStream_t st = ctx->stream;
-  Tree tree = build_tree(n, kLeafMax);
-  const int nlev = (int)tree.levels.size();
+// ---- host side: what to launch is stedc_plan.h's, the launches are here ---------------------------------------------
+using sc_host::DcLaunch;
+using sc_host::DcTree;
 
-  // node tables -> device (leaves first, then levels)
-  std::vector<DcNode> flat(tree.leaves);
-  std::vector<size_t> lev_off(nlev);
+dim3 grid_of(const DcLaunch& s) { return dim3(s.gx, s.gy, s.gz); }
+
+// The buffers of a solve: the caller's and the two carved out of ctx->dc_aux
+struct DcBuffers {
+  double* dc_ws;          // (batch) D&C slabs, DcLayout
+  double *q_out, *q_tmp;  // eigenvector ping-pong (sc_host::dc_q_is_out)
+  double* u;              // the merges' U
+  long long stride_q;
+  const DcNode* nodes;    // the tree in upload order
+  double* sorted;         // k_dc_setup's global carve of oversize merges, or null
+  double* q(int nlev, int stage) const { return sc_host::dc_q_is_out(nlev, stage) ? q_out : q_tmp; }
+};
+long long w_off(const DcLayout& DL, int stage) { return sc_host::dc_w_slot(stage) == 0 ? DL.w0 : DL.w1; }
+
+// The static parts of the two half-GEMM records of every merge, level by level, per level matrix by matrix (the order
+// k_dc_setup indexes when it fills in the sizes n and k)
+std::vector<GemmDesc> merge_records(const DcTree& tree, const DcLayout& DL, int batch, const DcBuffers& B) {
+  const int n = DL.n, nlev = tree.levels();
+  std::vector<GemmDesc> recs;
+  recs.reserve((size_t)2 * batch * tree.merges_before(nlev));
   for (int l = 0; l < nlev; ++l) {
-    lev_off[l] = flat.size();
-    flat.insert(flat.end(), tree.levels[l].begin(), tree.levels[l].end());
-  }
-  const size_t n_internal = flat.size() - tree.leaves.size();
-  // node tables + fail flag + the sorted copies of oversize merges: one cached allocation of the context
-  const size_t node_bytes = align_up(flat.size() * sizeof(DcNode), 256);
-  const size_t big_bytes = n > kLdsCapSetup ? (size_t)batch * 3 * n * sizeof(double) : 0;
-  SC_TRY(sc_reserve_dc_aux(ctx, node_bytes + 256 + big_bytes));
-  DcNode* d_nodes = reinterpret_cast<DcNode*>(ctx->dc_aux);
-  // (a QL failure goes to the context's deferred status word, read at the next synchronising call)
-  int* d_fail = reinterpret_cast<int*>(ctx->d_status + 1);
-  double* d_big = big_bytes ? reinterpret_cast<double*>(reinterpret_cast<char*>(d_nodes) + node_bytes + 256) : nullptr;
-  SC_TRY(sc_stage_upload(ctx, d_nodes, flat.data(), flat.size() * sizeof(DcNode)));
-
-  // eigenvector ping-pong: level l writes X[l+1]; X[nlev] must be d_q_out
-  auto qbuf = [&](int stage) { return ((nlev - stage) % 2 == 0) ? d_q_out : d_q_tmp; };
-
-  // merge GEMM descriptors for all levels (static parts), sizes are filled in by k_dc_setup
-  std::vector<GemmDesc> h_descs;
-  std::vector<size_t> desc_off(nlev);
-  for (int l = 0; l < nlev; ++l) {
-    desc_off[l] = h_descs.size();
-    const auto& nodes = tree.levels[l];
-    const double* q_old = qbuf(l);
-    double* q_new = qbuf(l + 1);
+    const double* q_old = B.q(nlev, l);
+    double* q_new = B.q(nlev, l + 1);
     for (int b = 0; b < batch; ++b)
-      for (size_t g = 0; g < nodes.size(); ++g) {
-        const DcNode& nd = nodes[g];
-        auto ip = [&](long long off) { return reinterpret_cast<const int*>(d_dc_ws + (size_t)b * DL.slab + off) + nd.lo; };
+      for (int g = 0; g < tree.level_size(l); ++g) {
+        const DcNode& nd = tree.level(l)[g];
+        auto ip = [&](long long off) { return reinterpret_cast<const int*>(B.dc_ws + (size_t)b * DL.slab + off) + nd.lo; };
         for (int half = 0; half < 2; ++half) {
           const int r0 = half == 0 ? nd.lo : nd.mid;
           GemmDesc D{};
-          D.a = q_old + (size_t)b * stride_q + r0;
+          D.a = q_old + (size_t)b * B.stride_q + r0;
           D.sa_i = 1; D.sa_k = n;
           D.a_kidx = ip(half == 0 ? DL.ktop_src : DL.kbot_src);
-          D.b = d_u + (size_t)b * stride_q + (size_t)nd.lo * n + nd.lo;
+          D.b = B.u + (size_t)b * B.stride_q + (size_t)nd.lo * n + nd.lo;
           D.sb_k = 1; D.sb_j = n;
           D.b_kidx = ip(half == 0 ? DL.ktop_k : DL.kbot_k);
-          D.c = q_new + (size_t)b * stride_q + r0;
+          D.c = q_new + (size_t)b * B.stride_q + r0;
           D.ldc = n;
           D.c_jidx = ip(DL.dest);
           D.m = half == 0 ? nd.mid - nd.lo : nd.hi - nd.mid; D.n = 0; D.k = 0;
           D.alpha = 1.0; D.beta = 0.0;
-          h_descs.push_back(D);
+          recs.push_back(D);
         }
       }
   }
-  if (!h_descs.empty()) SC_TRY(sc_stage_upload(ctx, d_merge_descs, h_descs.data(), h_descs.size() * sizeof(GemmDesc)));
+  return recs;
+}
 
+// The eight kernels and the merge products of level l
+int merge_level(sc_ctx* ctx, const DcTree& tree, int l, int batch, const DcLayout& DL, const DcBuffers& B,
+                GemmDesc* d_level_recs, PhaseTimer& t_gemm) {
+  hipStream_t st = ctx->stream;
+  const int n = DL.n, nlev = tree.levels(), G = tree.level_size(l), maxN = tree.level_maxn[l];
+  const sc_host::DcLevelLaunch S = sc_host::dc_level_launch(maxN, G, batch);
+  const DcNode* dn = B.nodes + tree.level_off[l];
+  double* q_old = B.q(nlev, l);
+  double* q_new = B.q(nlev, l + 1);
+  double* ws = B.dc_ws;
+  hipLaunchKernelGGL(k_dc_zero_offdiag, grid_of(S.zero_offdiag), dim3(S.zero_offdiag.threads), 0, st, dn, q_old,
+                     B.stride_q, n);
+  hipLaunchKernelGGL(k_dc_setup, grid_of(S.setup), dim3(S.setup.threads), S.setup.lds, st, ws, DL, dn, G, q_old,
+                     B.stride_q, w_off(DL, l), d_level_recs, (int)S.setup.use_lds, B.sorted,
+                     (long long)sc_host::kSetupScratchDoubles * n);
+  hipLaunchKernelGGL(k_dc_rotate, grid_of(S.rotate), dim3(S.rotate.threads), 0, st, ws, DL, dn, q_old, B.stride_q);
+  hipLaunchKernelGGL(k_dc_secular, grid_of(S.secular), dim3(S.secular.threads), S.secular.lds, st, ws, DL, dn,
+                     (int)S.secular.use_lds);
+  hipLaunchKernelGGL(k_dc_zhat, grid_of(S.zhat), dim3(S.zhat.threads), 0, st, ws, DL, dn);
+  hipLaunchKernelGGL(k_dc_vectors, grid_of(S.vectors), dim3(S.vectors.threads), 0, st, ws, DL, dn, B.u, B.stride_q);
+  hipLaunchKernelGGL(k_dc_finalize, grid_of(S.finalize), dim3(S.finalize.threads), 0, st, ws, DL, dn, w_off(DL, l + 1));
+  hipLaunchKernelGGL(k_dc_copy_deflated, grid_of(S.copy_deflated), dim3(S.copy_deflated.threads), 0, st, ws, DL, dn,
+                     q_old, q_new, B.stride_q);
+  t_gemm.start();
+  SC_TRY(launch_gemm_f64(ctx, d_level_recs, {.count = 2 * G * batch, .max_m = (maxN + 1) / 2, .max_n = maxN, .layout = kGemmAmBk, .gather = true}));
+  t_gemm.stop();
+  return SC_OK;
+}
+
+// Profiled solves: the flops of the merge products under "dc_gemm_gflop" -- their K and N depend on the deflation and
+// only exist in the device-side records (one small launch, an 8-byte copy and a synchronisation)
+int record_merge_flops(sc_ctx* ctx, const GemmDesc* d_recs, int count, double* d_flops) {
+  hipStream_t st = ctx->stream;
+  hipLaunchKernelGGL(k_dc_desc_flops, dim3(1), dim3(1024), 0, st, d_recs, count, d_flops);
+  double h_flops = 0.0;
+  SC_HIP(ctx, hipMemcpyAsync(&h_flops, d_flops, sizeof(double), hipMemcpyDeviceToHost, st));
+  SC_HIP(ctx, hipStreamSynchronize(st));
+  for (auto& ph : ctx->phases)
+    if (ph.first == "dc_gemm_gflop") { ph.second = h_flops * 1e-9; return SC_OK; }
+  ctx->phases.emplace_back("dc_gemm_gflop", h_flops * 1e-9);
+  return SC_OK;
+}
+
+}  // namespace
+
+int dc_max_nodes(int n) { return sc_host::dc_node_count(n); }
+
+size_t dc_slab_doubles(int n, DcLayout* out) {
+  DcLayout L{};
+  L.n = n;
+  long long off = 0;
+  const long long nn = ((long long)n + 7) / 8 * 8;
+  auto take = [&](long long cnt) { long long o = off; off += (cnt + 7) / 8 * 8; return o; };
+  L.dd = take(nn); L.ee = take(nn); L.w0 = take(nn); L.w1 = take(nn); L.z = take(nn);
+  L.dl = take(nn); L.zz = take(nn); L.ddef = take(nn); L.lam = take(nn); L.tauv = take(nn);
+  L.zhat = take(nn); L.rot_c = take(nn); L.rot_s = take(nn); L.scale = take(8);
+  L.src = take(nn); L.org = take(nn); L.dest = take(nn); L.rot_a = take(nn); L.rot_b = take(nn);
+  L.ktop_src = take(nn); L.ktop_k = take(nn); L.kbot_src = take(nn); L.kbot_k = take(nn);
+  L.cnt = take(2LL * dc_max_nodes(n) + 8);
+  L.slab = off;
+  if (out) *out = L;
+  return (size_t)off;
+}
+
+int stedc_batched(sc_ctx* ctx, int n, int batch, const double* d_tri_ws, const TriLayout& TL,
+                  double* d_dc_ws, const DcLayout& DL, double* d_w, long long stride_w, double* d_q_out,
+                  double* d_q_tmp, double* d_u, long long stride_q, GemmDesc* d_merge_descs) {
+  hipStream_t st = ctx->stream;
+  const DcTree tree = sc_host::dc_tree(n);
+  const int nlev = tree.levels();
+
+  // the tree (and the sorted copies of oversize merges) in the context's auxiliary buffer
+  const sc_host::DcAux A = sc_host::dc_aux_carve(tree.count(), n, batch);
+  SC_TRY(sc_reserve_dc_aux(ctx, A.total));
+  char* aux = static_cast<char*>(ctx->dc_aux);
+  DcNode* d_nodes = reinterpret_cast<DcNode*>(aux + A.nodes);
+  SC_TRY(sc_stage_upload(ctx, d_nodes, tree.nodes.data(), tree.count() * sizeof(DcNode)));
+  const DcBuffers B{d_dc_ws, d_q_out, d_q_tmp, d_u, stride_q, d_nodes,
+                    A.oversize ? reinterpret_cast<double*>(aux + A.sorted) : nullptr};
+
+  const std::vector<GemmDesc> recs = merge_records(tree, DL, batch, B);
+  if (!recs.empty()) SC_TRY(sc_stage_upload(ctx, d_merge_descs, recs.data(), recs.size() * sizeof(GemmDesc)));
+
+  // (a QL failure goes to the context's deferred status word, read at the next synchronising call)
+  int* d_fail = reinterpret_cast<int*>(ctx->d_status + 1);
   hipLaunchKernelGGL(k_dc_prepare, dim3((unsigned)batch), dim3(1024), 0, st, d_tri_ws, TL, d_dc_ws, DL,
-                     d_nodes + tree.leaves.size(), (int)n_internal);
-  hipLaunchKernelGGL((k_dc_leaves<kLeafMax>), dim3((unsigned)tree.leaves.size(), (unsigned)batch), dim3(64),
-                     0, st, d_dc_ws, DL, d_nodes, qbuf(0), stride_q, d_fail);
+                     d_nodes + tree.n_leaves, tree.merges_before(nlev));
+  hipLaunchKernelGGL((k_dc_leaves<sc_host::kLeafMax>), dim3((unsigned)tree.n_leaves, (unsigned)batch), dim3(64), 0, st,
+                     d_dc_ws, DL, d_nodes, B.q(nlev, 0), stride_q, d_fail);
 
   PhaseTimer t_gemm(ctx, "dc_gemm", st);
-  for (int l = 0; l < nlev; ++l) {
-    const auto& nodes = tree.levels[l];
-    const int G = (int)nodes.size();
-    const DcNode* dn = d_nodes + lev_off[l];
-    int maxN = 0;
-    for (auto& nd : nodes) maxN = std::max(maxN, nd.hi - nd.lo);
-    double* q_old = qbuf(l);
-    double* q_new = qbuf(l + 1);
-    const long long w_old = (l % 2 == 0) ? DL.w0 : DL.w1;
-    const long long w_new = (l % 2 == 0) ? DL.w1 : DL.w0;
-    GemmDesc* descs = d_merge_descs + desc_off[l];
-
-    hipLaunchKernelGGL(k_dc_zero_offdiag,
-                       dim3((unsigned)std::min(1024, (maxN * maxN / 2 + 255) / 256 + 1), (unsigned)G,
-                            (unsigned)batch),
-                       dim3(256), 0, st, dn, q_old, stride_q, n);
-    {
-      const int use_lds = maxN <= kLdsCapSetup ? 1 : 0;
-      const size_t lds = use_lds ? (size_t)maxN * 22 + 32 : 0;
-      const int threads = maxN >= 1024 ? 1024 : (maxN >= 256 ? 256 : 64);
-      hipLaunchKernelGGL(k_dc_setup, dim3((unsigned)G, (unsigned)batch), dim3(threads), lds, st, d_dc_ws, DL,
-                         dn, G, q_old, stride_q, w_old, descs, use_lds, d_big, (long long)3 * n);
-    }
-    hipLaunchKernelGGL(k_dc_rotate, dim3((unsigned)((maxN + 255) / 256), (unsigned)G, (unsigned)batch),
-                       dim3(256), 0, st, d_dc_ws, DL, dn, q_old, stride_q);
-    {
-      const int use_lds = maxN <= kLdsCapSecular ? 1 : 0;
-      const int threads = maxN >= 2048 ? 1024 : 256;
-      const int waves = threads / 64;
-      const size_t lds = use_lds ? (size_t)maxN * 16 + 16 : 0;
-      hipLaunchKernelGGL(k_dc_secular, dim3((unsigned)((maxN + waves - 1) / waves), (unsigned)G, (unsigned)batch),
-                         dim3(threads), lds, st, d_dc_ws, DL, dn, use_lds);
-    }
-    hipLaunchKernelGGL(k_dc_zhat, dim3((unsigned)((maxN + 3) / 4), (unsigned)G, (unsigned)batch), dim3(256), 0,
-                       st, d_dc_ws, DL, dn);
-    hipLaunchKernelGGL(k_dc_vectors, dim3((unsigned)maxN, (unsigned)G, (unsigned)batch), dim3(256), 0, st,
-                       d_dc_ws, DL, dn, d_u, stride_q);
-    hipLaunchKernelGGL(k_dc_finalize, dim3((unsigned)((maxN + 255) / 256), (unsigned)G, (unsigned)batch),
-                       dim3(256), 0, st, d_dc_ws, DL, dn, w_new);
-    hipLaunchKernelGGL(k_dc_copy_deflated, dim3((unsigned)maxN, (unsigned)G, (unsigned)batch), dim3(256), 0, st,
-                       d_dc_ws, DL, dn, q_old, q_new, stride_q);
-    t_gemm.start();
-    SC_TRY(launch_gemm_f64(ctx, descs, {.count = 2 * G * batch, .max_m = (maxN + 1) / 2, .max_n = maxN, .layout = kGemmAmBk, .gather = true}));
-    t_gemm.stop();
-  }
-  const long long w_final = (nlev % 2 == 0) ? DL.w0 : DL.w1;
+  for (int l = 0; l < nlev; ++l)
+    SC_TRY(merge_level(ctx, tree, l, batch, DL, B, d_merge_descs + (size_t)2 * batch * tree.merges_before(l), t_gemm));
   hipLaunchKernelGGL(k_dc_unscale, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, st,
-                     d_dc_ws, DL, w_final, d_w, stride_w);
+                     d_dc_ws, DL, w_off(DL, nlev), d_w, stride_w);
   SC_HIP(ctx, hipGetLastError());
 
   t_gemm.finish();
-  if (ctx->profiling && !h_descs.empty()) {
-    // flops of the merge GEMMs: their K and N depend on the deflation and only exist in the device-side records
-    // (profiling runs only; one small launch and an 8-byte copy)
-    double* d_flops = reinterpret_cast<double*>(reinterpret_cast<char*>(d_nodes) + node_bytes);   // (the 256 spare bytes)
-    hipLaunchKernelGGL(k_dc_desc_flops, dim3(1), dim3(1024), 0, st, d_merge_descs, (int)h_descs.size(), d_flops);
-    double h_flops = 0.0;
-    SC_HIP(ctx, hipMemcpyAsync(&h_flops, d_flops, sizeof(double), hipMemcpyDeviceToHost, st));
-    SC_HIP(ctx, hipStreamSynchronize(st));
-    bool found = false;
-    for (auto& ph : ctx->phases)
-      if (ph.first == "dc_gemm_gflop") { ph.second = h_flops * 1e-9; found = true; }
-    if (!found) ctx->phases.emplace_back("dc_gemm_gflop", h_flops * 1e-9);
-  }
+  if (ctx->profiling && !recs.empty())
+    SC_TRY(record_merge_flops(ctx, d_merge_descs, (int)recs.size(), reinterpret_cast<double*>(aux + A.flops)));
   return SC_OK;
 }
+

@@ -261,6 +261,29 @@ def test_eigh_policy_under_sanitizers(tmp_path):
     assert r.returncode == 0 and "eigh policy ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
 
 
+def test_stedc_plan_under_sanitizers(tmp_path):
+    """
+    The plan of the tridiagonal divide & conquer (csrc/stedc_plan.h: the merge tree, the launch shapes and LDS bytes of a
+    level's kernels, buffer parity, the layout of the auxiliary buffer) compiled with g++ under ASan + UBSan and checked
+    against literals (tests/host_sanitize/test_stedc_plan.cpp).
+    """
+    import shutil
+    import subprocess
+
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = str(tmp_path / "test_stedc_plan")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-I", join(ROOT, "include"), "-I", join(ROOT, "springcraft_amd", "csrc"),
+           join(ROOT, "tests", "host_sanitize", "test_stedc_plan.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0 and ("asan" in r.stderr.lower() or "ubsan" in r.stderr.lower()) and "cannot find" in r.stderr:
+        pytest.skip("sanitizer runtimes not installed")
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "stedc plan ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+
+
 # sc_eigh_workspace_bytes(n, batch, want_vectors = 0 / 1) of the revision before the drivers shared one plan (taken from that
 # revision's library on the host: the function needs neither a context nor a device), default environment
 EIGH_WORKSPACE_BYTES = {
@@ -272,6 +295,9 @@ EIGH_WORKSPACE_BYTES = {
     (2000, 16): (1762477568, 3751801600),
     (6000, 4): (3100750336, 6128908800),
     (8000, 1): (1376765440, 2642096896),
+    # (above both LDS caps of the D&C; of the revision before its plan header)
+    (7001, 2): (2075222784, 4066082048),
+    (9801, 3): (5750026496, 11246490880),
 }
 
 

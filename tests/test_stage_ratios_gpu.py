@@ -14,7 +14,8 @@ The test_form_* cases at the end hold one kernel form each to the same gate, at 
 (csrc/twostage_policy.h) selects it, and prove by the context's form counters that it ran: the expected counts are the
 literals of tests/host_sanitize/test_host_logic.cpp, derived by hand from the rules.  Not covered there:
 k_bt2_apply<8> on the (chunk, matrix) grid (it needs n >= 4609 at batch 7, and there is no in-process override), the
-partial-spectrum Q2 (ncols < n: tests/test_partial_ratios_gpu.py), and stedc above n = 1000.
+partial-spectrum Q2 (ncols < n: tests/test_partial_ratios_gpu.py), and stedc above n = 2048 (n > 7000:
+tests/test_large_order_gpu.py).
 """
 import ctypes as C
 import os
@@ -259,6 +260,33 @@ def test_tridiagonal_solver_is_independent_of_the_batch_slot(lib_ctx):
                                                "orth(Z)": sr.orth(z[0])})])
     for b in range(1, 8):
         assert np.array_equal(w[b], w[0]) and np.array_equal(z[b], z[0]), b
+
+
+@pytest.mark.parametrize("n", [255, 256, 1023, 1024, 2047, 2048])
+def test_tridiagonal_solver_at_the_launch_thresholds(lib_ctx, n):
+    """
+    stedc_batched at the orders on both sides of every step of its thread and LDS table (csrc/stedc_plan.h:dc_level_launch:
+    the top merge has n rows; k_dc_setup 64 / 256 / 1024 threads from 256 and 1024 rows, k_dc_secular 256 / 1024 from 2048),
+    a batch of two different matrices: a random tridiagonal matrix and the glued Wilkinson blocks.  The ratios and the gate
+    of test_tridiagonal_solver, formed on the device (sr.recon_t / sr.orth_t: the same formulas).
+    """
+    import torch
+
+    L, ctx = lib_ctx
+    rs = np.random.RandomState(2000 + n)
+    glued = sr.tridiagonal_inputs(n)["glued1e-4"]
+    e_random = rs.randn(n)
+    e_random[n - 1] = 0.0
+    names = ["random", "glued1e-4"]
+    d = np.stack([rs.randn(n), glued[0]])
+    e = np.stack([e_random, glued[1]])
+    w, z = sr.stedc_host(L, ctx, d, e)
+    rows = []
+    for b, name in enumerate(names):
+        t, zb, wb = (torch.from_numpy(x).cuda() for x in (sr.tridiagonal(d[b], e[b]), z[b], w[b]))
+        assert np.all(np.diff(w[b]) >= 0.0), (name, "eigenvalues not ascending")
+        rows.append((name, {"recon(T,Z,w)": sr.recon_t(t, zb, torch.diag(wb)), "orth(Z)": sr.orth_t(zb)}))
+    report(f"stedc n={n} thresholds", rows)
 
 
 # ---- the staged entries against the product path ---------------------------------------------------------------------------
