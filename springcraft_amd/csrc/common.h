@@ -216,6 +216,48 @@ int sc_reserve_win(sc_ctx* ctx, size_t bytes);
 int sc_reserve_modes(sc_ctx* ctx, size_t bytes);
 int sc_aux_stream(sc_ctx* ctx);   // creates aux_stream / aux_fork / aux_join if needed
 int sc_side_streams(sc_ctx* ctx, int count);   // makes sure side_streams / side_joins hold `count` entries
+// The context on another stream for a scope: launch_gemm_f64 and whatever else takes no stream launches on ctx->stream.
+struct StreamScope {
+  sc_ctx* c;
+  hipStream_t old;
+  StreamScope(sc_ctx* c_, hipStream_t s) : c(c_), old(c_->stream) { c->stream = s; }
+  ~StreamScope() { c->stream = old; }
+  StreamScope(const StreamScope&) = delete;
+  StreamScope& operator=(const StreamScope&) = delete;
+};
+// Parts of a batch side by side on the main stream and parts - 1 side streams.  fork: the side streams wait for what the
+// main stream holds so far; stream(q): where part q goes (part 0: the main stream); join: the main stream waits for every
+// side stream -- by the destructor at the latest, so also on an error path: what the side streams still have queued is
+// ordered before whatever the caller enqueues next on the main stream.
+class SideFork {
+ public:
+  SideFork(sc_ctx* ctx, hipStream_t main) : ctx_(ctx), main_(main) {}
+  ~SideFork() { (void)join(); }
+  SideFork(const SideFork&) = delete;
+  SideFork& operator=(const SideFork&) = delete;
+  int fork(int parts) {
+    SC_TRY(sc_aux_stream(ctx_));   // (its fork event)
+    SC_TRY(sc_side_streams(ctx_, parts - 1));
+    SC_HIP(ctx_, hipEventRecord(ctx_->aux_fork, main_));
+    for (int q = 1; q < parts; ++q) SC_HIP(ctx_, hipStreamWaitEvent(ctx_->side_streams[q - 1], ctx_->aux_fork, 0));
+    parts_ = parts;
+    return SC_OK;
+  }
+  hipStream_t stream(int q) const { return q == 0 ? main_ : ctx_->side_streams[q - 1]; }
+  int join() {
+    const int parts = parts_;
+    parts_ = 1;
+    for (int q = 1; q < parts; ++q) {
+      SC_HIP(ctx_, hipEventRecord(ctx_->side_joins[q - 1], ctx_->side_streams[q - 1]));
+      SC_HIP(ctx_, hipStreamWaitEvent(main_, ctx_->side_joins[q - 1], 0));
+    }
+    return SC_OK;
+  }
+ private:
+  sc_ctx* ctx_;
+  hipStream_t main_;
+  int parts_ = 1;
+};
 // d_dst <- bytes at h_src, enqueued on ctx->stream; h_src may be released as soon as the call returns
 int sc_stage_upload(sc_ctx* ctx, void* d_dst, const void* h_src, size_t bytes);
 // end of a solve that used sc_stage_upload: the arena may be reused when everything enqueued so far has run

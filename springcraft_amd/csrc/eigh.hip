@@ -47,7 +47,7 @@ SolvePlan make_solve_plan(const sc_ctx* ctx, int n, int batch, bool vectors, Sol
   if (P.two) {
     P.off_sb = take(sb_slab_doubles(n, batch, &P.SL) * 8 * batch);
     P.off_dia = take(sizeof(int) * ((size_t)n / 64 + 8));
-    P.n_tri_desc = std::max(P.n_tri_desc, sb_desc_count(n, batch));
+    P.n_tri_desc = std::max(P.n_tri_desc, stage1_record_count(n, batch));
   }
   if (kind.partial) P.n_mid_desc = 2 * batch;
   if (vectors) {
@@ -283,13 +283,11 @@ int eigh_batched_async(sc_ctx* ctx, double* d_a, int64_t n64, int64_t batch64, d
         t_tf->stop();
       }
       {
-        ctx->stream = ctx->aux_stream;   // (launch_gemm_f64 launches on the context's stream)
-        const int rc_prep = backtransform_batched(ctx, d_a, stride_a, n, batch, tri_ws, P.TL, bt_ws, P.BL, d_v, stride_a,
-                                                  n, q_tmp, bt_descs, bt_off, /*phase=*/2);
-        ctx->stream = st;
-        if (rc_prep != SC_OK) return rc_prep;     // (joined by the guard)
-        SC_HIP(ctx, hipEventRecord(ctx->aux_join, ctx->aux_stream));
+        StreamScope on_aux(ctx, ctx->aux_stream);
+        SC_TRY(backtransform_batched(ctx, d_a, stride_a, n, batch, tri_ws, P.TL, bt_ws, P.BL, d_v, stride_a, n, q_tmp,
+                                     bt_descs, bt_off, /*phase=*/2));   // (an error: joined by the guard)
       }
+      SC_HIP(ctx, hipEventRecord(ctx->aux_join, ctx->aux_stream));
     }
     SC_TRY(stedc_batched(ctx, n, batch, tri_ws, P.TL, dc_ws, P.DL, d_w, n, d_v, q_tmp, u, stride_a, P.mid_descs(base)));
     SC_TRY(unscale_values_batched(ctx, d_w, n, n, batch, tri_ws, P.TL));

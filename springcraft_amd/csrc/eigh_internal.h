@@ -5,6 +5,7 @@
 #include "common.h"
 #include "gemm_f64.h"
 #include "stedc_plan.h"
+#include "sy2sb_plan.h"
 
 // Per-matrix workspace slab of the tridiagonalisation (offsets in doubles from the slab base).
 struct TriLayout {
@@ -114,35 +115,14 @@ int backtransform_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, i
                           GemmDesc* d_descs /* bt_desc_count(n, batch) records */, int off = 1, int phase = 0);
 
 // ---- two-stage tridiagonalisation (twostage.hip, sy2sb.hip, sb2st.hip, bt2.hip) -------------------------------
-struct SbLayout {
-  int n;
-  long long slab;
-  long long vw, wv;   // [V|W], [W|V] panels of TWO consecutive panels, n x 256 (the trailing update takes them together)
-  long long xv;       // [X1|X2|V], n x 192
-  long long qrpart, qrpiv;   // panel-QR partial Gram rows / pivot row (two copies each)
-  long long qrpart8;         // blocked panel QR: per-chunk partial products of an inner block, nchunk x 8 x 64
-  long long xsplit;   // K slices of X1 and X2 when the SYMM runs split-K: 2 x symm_split x (n x 64)
-  int symm_split;     // 1: no split
-  long long small;    // split-K slices of V^T [X1|X2|V]
-  long long cmat;     // [T; T; -S/2], 192 x 64
-  long long small2;   // split-K slices of [W1|V1]^T V2 (second panel of a pair), 128 x 64 each
-  long long p2;       // their sum
-  long long ab;       // band storage 128 x n
-  int ngroups;        // sweep groups (64 sweeps each)
-  long long ndia;     // diamonds
-  long long vd;       // diamonds: V row-major (128 rows x 64 sweeps)
-  long long frag;     // diamonds: MFMA fragments of V^T and -(V T), 160 x 64 doubles each (k_dia_tfactor2 -> k_bt2_apply)
-  long long tau2;     // ndia x 64
-};
-// batch: matrices of the solve (few matrices: the SYMM of the band reduction is cut into K slices, which need room)
-size_t sb_slab_doubles(int n, int batch, SbLayout* out);
-int sb_desc_count(int n, int batch);
+// The slab of a matrix (SbLayout, sb_slab_doubles) and the count of stage 1's GEMM records (stage1_record_count): sy2sb_plan.h
+using sc_host::sb_slab_doubles, sc_host::stage1_record_count;
 int sb_band_width();
 // d_a: column-major lower triangle valid.  On exit d, e (and the stage-1 tau) are in the tri slab, the stage-1
 // reflectors in A (unit entry of column c at row c + sb_band_width()), the stage-2 reflectors in the sb slab.
 int sytrd_2stage_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, int batch, double* d_tri_ws,
                          const TriLayout& TL, double* d_sb_ws, const SbLayout& SL, int* d_dia_off /* n/64 + 2 ints */,
-                         GemmDesc* d_descs /* sb_desc_count */, float* ms_stage1, float* ms_stage2,
+                         GemmDesc* d_descs /* stage1_record_count */, float* ms_stage1, float* ms_stage2,
                          double* d_band_copy = nullptr);
 // Z <- Q2 Z (stage-2 reflectors): bt2_prepare (T factors; independent of Z, may run on another stream), then bt2_batched
 int bt2_prepare(sc_ctx* ctx, int n, int batch, double* d_sb_ws, const SbLayout& SL, hipStream_t st);

@@ -18,24 +18,7 @@
 
 #include "common.h"
 #include "gemm_policy.h"
-
-struct GemmDesc {
-  const double* a;
-  const double* b;
-  double* c;
-  int m, n, k;
-  long long sa_i, sa_k;   // element strides of A(i,k)
-  long long sb_k, sb_j;   // element strides of B(k,j)
-  long long ldc;          // column stride of C (row stride is 1)
-  double alpha, beta;
-  const int* a_kidx;      // optional gather on A's k axis: A(i,k) = a[i*sa_i + a_kidx[k]*sa_k]
-  const int* b_kidx;      // optional gather on B's k axis: B(k,j) = b[b_kidx[k]*sb_k + j*sb_j]
-  const int* c_jidx;      // optional scatter on C's column axis: C(:, j) lives at column c_jidx[j]
-  int lower_only;         // 1: store only elements with (row + row_off) >= (col + col_off) (SYR2K); 2: ((row + row_off) | 1) >= ...
-  int row_off, col_off;
-  long long split_stride; // split-K launches: slice s writes alpha*partial to C + s*split_stride (beta ignored)
-  int a_tri;              // launches with tri = true: 1: A(i,k) counts only for i >= k; 2: only for k > i
-};
+// (GemmDesc, the record of one problem, lives in gemm_policy.h beside GemmLaunch: the plans that build records need it without HIP)
 
 // One launch of `count` problems (records d_desc[0..count)) on k_gemm2; max_m / max_n bound the grid.  The policy --
 // block tile, grid order, chunks of at most 65535 records x slices -- is gemm_policy.h's.

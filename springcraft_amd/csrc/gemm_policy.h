@@ -12,6 +12,26 @@
 // sb_k = 1), "NT" (sa_i = 1, sb_j = 1)
 constexpr int kGemmAmBk = 0, kGemmAkBk = 1, kGemmAmBn = 2;
 
+// One problem of a launch, in device memory (what the fields mean to the kernels: gemm_f64.h).  Here, without HIP, for the
+// plans that build records on the host (sy2sb_plan.h); global, as the kernels' signatures name it.
+struct GemmDesc {
+  const double* a;
+  const double* b;
+  double* c;
+  int m, n, k;
+  long long sa_i, sa_k;   // element strides of A(i,k)
+  long long sb_k, sb_j;   // element strides of B(k,j)
+  long long ldc;          // column stride of C (row stride is 1)
+  double alpha, beta;
+  const int* a_kidx;      // optional gather on A's k axis: A(i,k) = a[i*sa_i + a_kidx[k]*sa_k]
+  const int* b_kidx;      // optional gather on B's k axis: B(k,j) = b[b_kidx[k]*sb_k + j*sb_j]
+  const int* c_jidx;      // optional scatter on C's column axis: C(:, j) lives at column c_jidx[j]
+  int lower_only;         // 1: store only elements with (row + row_off) >= (col + col_off) (SYR2K); 2: ((row + row_off) | 1) >= ...
+  int row_off, col_off;
+  long long split_stride; // split-K launches: slice s writes alpha*partial to C + s*split_stride (beta ignored)
+  int a_tri;              // launches with tri = true: 1: A(i,k) counts only for i >= k; 2: only for k > i
+};
+
 namespace sc_host {
 // ---- every SPRINGCRAFT_* value the GEMM launchers read, read once per process.
 // (SPRINGCRAFT_SYMM3 is TwoStageEnv's: the band reduction plans with it, symm3_takes receives it)

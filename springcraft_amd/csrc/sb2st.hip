@@ -1431,22 +1431,17 @@ static int chase_stepwise(sc_ctx* ctx, int n, int batch, double* d_sb_ws, const 
   const int nparts = sc_host::bulge_stream_parts(E, batch);
   ctx->last_chase_stream_parts = nparts;
   if (nparts > 1) {
-    SC_TRY(sc_aux_stream(ctx));            // (its fork event)
-    SC_TRY(sc_side_streams(ctx, nparts - 1));
-    SC_HIP(ctx, hipEventRecord(ctx->aux_fork, st));
-    for (int p = 1; p < nparts; ++p) SC_HIP(ctx, hipStreamWaitEvent(ctx->side_streams[p - 1], ctx->aux_fork, 0));
+    SideFork parts(ctx, st);
+    SC_TRY(parts.fork(nparts));
     const int burst = sc_host::bulge_burst(E);
     for (int t0 = 0; t0 <= t_max; t0 += burst)
       for (int p = 0; p < nparts; ++p) {
-        const int lo = (int)((long long)batch * p / nparts), hi = (int)((long long)batch * (p + 1) / nparts);
+        const sc_host::PartBounds pb = sc_host::part_bounds(batch, nparts, p);
         for (int t = t0; t <= std::min(t_max, t0 + burst - 1); ++t)
-          hipLaunchKernelGGL(k_bulge_step, dim3((unsigned)gx, (unsigned)(hi - lo)), dim3(256), 0,
-                             p == 0 ? st : ctx->side_streams[p - 1], d_sb_ws + (size_t)lo * SL.slab, SL, t);
+          hipLaunchKernelGGL(k_bulge_step, dim3((unsigned)gx, (unsigned)(pb.hi - pb.lo)), dim3(256), 0, parts.stream(p),
+                             d_sb_ws + (size_t)pb.lo * SL.slab, SL, t);
       }
-    for (int p = 1; p < nparts; ++p) {
-      SC_HIP(ctx, hipEventRecord(ctx->side_joins[p - 1], ctx->side_streams[p - 1]));
-      SC_HIP(ctx, hipStreamWaitEvent(st, ctx->side_joins[p - 1], 0));
-    }
+    SC_TRY(parts.join());
   } else {
     for (int t = 0; t <= t_max; ++t)
       hipLaunchKernelGGL(k_bulge_step, dim3((unsigned)gx, (unsigned)batch), dim3(256), 0, st, d_sb_ws, SL, t);

@@ -70,7 +70,6 @@ inline DcTree dc_tree(int n) {
 // The rule: a level whose widest merge has maxN rows keeps the kernel's working set in dynamic LDS while maxN is at most
 // the kernel's cap, (bytes per element) * maxN + (fixed part) bytes of it; above the cap the launch asks for no dynamic
 // LDS and the kernel works on global memory (use_lds = 0).
-constexpr size_t kLdsPerWorkgroup = 160 * 1024;
 // k_dc_setup: the merged order of the two child spectra (dc_setup_carve)
 constexpr int kSetupLdsPerElem = 22;
 constexpr int kSetupLdsFixed = 32;

@@ -1,9 +1,10 @@
 // Stage 1 of the two-stage tridiagonalisation (sy2sb): dense -> band of half-width kB.  The six forms of the panel QR
 // (k_panel_qr with k_pqr_blk_a / _b, k_panel_wg, k_panel_coop with its take-over k_panel_serial), the small kernels
-// between the GEMMs of the two-sided update (k_sum_xslices, k_sum_p2, k_sb_small), the GEMM records of a solve and the
-// host side: run_panel (one panel of a part of the batch) and sb_stage1.
+// between the GEMMs of the two-sided update (k_sum_xslices, k_sum_p2, k_sb_small) and the host side: launch_panel_qr and
+// run_panel (one panel of a part of the batch) and sb_stage1.
 //
-// Overview of the algorithm: twostage.hip; which form a panel gets: twostage_policy.h.
+// Overview of the algorithm: twostage.hip; which form a panel gets: twostage_policy.h; the GEMM records of a solve, the LDS
+// layouts the kernels carve and the launches size, k_panel_coop's records: sy2sb_plan.h.
 #include <algorithm>
 #include <vector>
 
@@ -11,6 +12,7 @@
 
 namespace {
 
+using sc_host::lds_bytes;
 constexpr int kEarly = (kIb + 2) / 2;   // column loads per thread that cover a launch of an inner block (kIb + 1 columns)
 
 // ================================================================================================================
@@ -33,10 +35,11 @@ __global__ __launch_bounds__(256) void k_panel_qr(double* __restrict__ a_all, lo
   // blocked panels that is at most 9 columns = 9 KB instead of 66 KB, i.e. 8 workgroups per CU instead of 2
   const int c_lo = j > 0 ? j - 1 : 0;
   const int ncl = c_end - c_lo;
-  double* P = sm;                      // [ncl][LD]   column c at P[(c - c_lo) * LD + r]
-  double* wv = sm + ncl * LD;          // [kB]  w_c of the reflector being applied
-  double* vv = wv + kB;                // [kQrRows]  v_r
-  double* red = vv + kQrRows;          // [4][kB]
+  const sc_host::LdsPanelQr lds = sc_host::lds_panel_qr(ncl);
+  double* P = sm + lds.P;              // [ncl][LD]   column c at P[(c - c_lo) * LD + r]
+  double* wv = sm + lds.wv;            // [kB]  w_c of the reflector being applied
+  double* vv = sm + lds.vv;            // [kQrRows]  v_r
+  double* red = sm + lds.red;          // [4][kB]
   __shared__ double s_scale, s_beta, s_tau;
 
   const int n = TL.n;
@@ -216,9 +219,10 @@ __global__ __launch_bounds__(256) void k_pqr_blk_a(double* __restrict__ a_all, l
                                                    double* __restrict__ sb_all, SbLayout SL, int j0, int c0) {
   constexpr int LD = kQrRows + 1;
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  double* P = sm;                      // [kB - c0][LD]: columns c0 .. kB-1, indexed relative to c0
-  double* vv = sm + (kB - c0) * LD;    // [kQrRows]
-  double* red = vv + kQrRows;          // [4][2][kB]
+  const sc_host::LdsBlk lds = sc_host::lds_pqr_blk_a(c0);
+  double* P = sm + lds.P;              // [kB - c0][LD]: columns c0 .. kB-1, indexed relative to c0
+  // (lds.mid: kQrRows doubles nobody uses any more; kept, the launch's byte count and with it the occupancy stay)
+  double* red = sm + lds.red;          // [4][2][kB]
   __shared__ double s_scale, s_beta;
   const int n = TL.n;
   const int r0 = j0 + kB, m = n - r0;
@@ -312,9 +316,10 @@ __global__ __launch_bounds__(256) void k_pqr_blk_b(double* __restrict__ a_all, l
                                                    double* __restrict__ sb_all, SbLayout SL, int j0, int c0) {
   constexpr int LD = kQrRows + 1;
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  double* P = sm;                      // [kB - c0][LD]: columns c0 .. kB-1, indexed relative to c0
-  double* Ms = sm + (kB - c0) * LD;    // [kIb][kB]  M, later W
-  double* red = Ms + kIb * kB;         // [4][kB]
+  const sc_host::LdsBlk lds = sc_host::lds_pqr_blk_b(c0);
+  double* P = sm + lds.P;              // [kB - c0][LD]: columns c0 .. kB-1, indexed relative to c0
+  double* Ms = sm + lds.mid;           // [kIb][kB]  M, later W
+  double* red = sm + lds.red;          // [4][kB]
   __shared__ double T[kIb][kIb];
   const int n = TL.n;
   const int r0 = j0 + kB, m = n - r0;
@@ -440,8 +445,6 @@ __global__ __launch_bounds__(256) void k_pqr_blk_b(double* __restrict__ a_all, l
 // block's reflectors applied to the rest of the panel as one block update), other reduction trees.
 // One workgroup streams its panel at the rate of one CU: the path is for batches (the matrices run side by side) and
 // panels of at most 4096 rows; larger panels and single large matrices keep the chunked launches.
-constexpr int kWgThreads = 1024, kWgWaves = kWgThreads / 64;
-
 // Sums of eight values over the 64 lanes with 10 exchanges instead of 48: three halving steps (a lane keeps half of its
 // values and receives the partner's sums of those), then three plain steps.  The exchanges inside a row of 16 lanes (eight of the ten) are DPP
 // moves on the vector ALU; the two across rows go through the LDS crossbar, which all 16 waves of the workgroup share.  Lane l < 8 returns the total of v[wave_reduce8_index(l)].
@@ -480,13 +483,14 @@ template <int RU, int CU, int NT = 1024>
 __global__ __launch_bounds__(NT) void k_panel_wg(double* __restrict__ a_all, long long stride_a,
                                                    double* __restrict__ tri_all, TriLayout TL,
                                                    double* __restrict__ sb_all, SbLayout SL, int j0) {
-  constexpr int kWgThreads = NT, kWgWaves = NT / 64;   // (shadow the file-level constants: NT threads per panel)
+  constexpr int kWgThreads = NT, kWgWaves = NT / 64;   // NT threads per panel
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  double* red = sm;                               // [2][kWgWaves][8] wave partials of the per-column sums (by column parity)
-  double* piv = red + 2 * kWgWaves * 8;           // [2][8]          pivot row of the inner block
-  double* tauL = piv + 16;                        // [8]
-  double* Ms = tauL + 8;                          // [8][kB]         M = V^T P, then W = T^T M (column index = panel column)
-  double* part = Ms + 8 * kB;                         // [kWgWaves][kB][8] wave partials of M
+  constexpr sc_host::LdsPanelWg lds = sc_host::lds_panel_wg(NT);
+  double* red = sm + lds.red;                     // [2][kWgWaves][8] wave partials of the per-column sums (by column parity)
+  double* piv = sm + lds.piv;                     // [2][8]          pivot row of the inner block
+  double* tauL = sm + lds.tauL;                   // [8]
+  double* Ms = sm + lds.Ms;                       // [8][kB]         M = V^T P, then W = T^T M (column index = panel column)
+  double* part = sm + lds.part;                   // [kWgWaves][kB][8] wave partials of M
   const int n = TL.n;
   const int r0 = j0 + kB, m = n - r0;
   double* A = a_all + (size_t)blockIdx.x * stride_a;
@@ -696,10 +700,9 @@ __global__ __launch_bounds__(NT) void k_panel_wg(double* __restrict__ a_all, lon
 // again.  Sequence numbers are unique within a solve ((panel + 1) * 128 + step) and the records are zeroed per solve.
 constexpr int kCoopRows = sc_host::kCoopRows;
 constexpr int kCoopLd = kCoopRows + 1;
-constexpr int kCoopVals = 8 * kB;                 // values of one block exchange (M and the Gram matrix)
-constexpr size_t kCoopLdsBytes = sizeof(double) * ((size_t)kB * kCoopLd + kCoopRows * 8 + 8 * kB + 64 + 16 + kB + 128 + 2);
-// workspace of one matrix (16-byte records): column records [2][G][16] | block partials [G][512] | block totals [512]
-__host__ __device__ inline size_t coop_recs_per_matrix(int G) { return (size_t)2 * G * 16 + (size_t)G * kCoopVals + kCoopVals; }
+constexpr int kCoopVals = sc_host::kCoopVals;     // values of one block exchange (M and the Gram matrix)
+constexpr size_t kCoopLdsBytes = lds_bytes(sc_host::lds_panel_coop().total);
+using sc_host::coop_recs_per_matrix;              // 16-byte records of one matrix (their layout: sy2sb_plan.h)
 
 __device__ __forceinline__ void st16_agent(void* p, double v, int tag) {
   const unsigned long long b = (unsigned long long)__double_as_longlong(v);
@@ -778,14 +781,16 @@ __global__ __launch_bounds__(kCoopRows) void k_panel_coop(double* __restrict__ a
                                                           double* __restrict__ sb_all, SbLayout SL, int j0, int G,
                                                           v4i* __restrict__ recs_all, int* __restrict__ ctl, int seq_base) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  double* Pl = sm;                          // [kB][kCoopLd]  the workgroup's rows of the panel
-  double* Vl = Pl + kB * kCoopLd;           // [256][8]       the inner block's reflectors by row; then partial sums
-  double* Ms = Vl + kCoopRows * 8;          // [8][kB]        M, then W = T^T M
-  double* red = Ms + 8 * kB;                // [2][4][8]
-  double* piv = red + 64;                   // [2][8]
-  double* tauA = piv + 16;                  // [kB]           tau of every column (stored at the end)
-  double* tot4 = tauA + kB;                 // [2][4][16]
-  int* s_dead = reinterpret_cast<int*>(tot4 + 128);
+  constexpr sc_host::LdsPanelCoop lds = sc_host::lds_panel_coop();
+  static_assert(lds.Vl == kB * kCoopLd, "rows of the panel image");
+  double* Pl = sm + lds.Pl;                 // [kB][kCoopLd]  the workgroup's rows of the panel
+  double* Vl = sm + lds.Vl;                 // [256][8]       the inner block's reflectors by row; then partial sums
+  double* Ms = sm + lds.Ms;                 // [8][kB]        M, then W = T^T M
+  double* red = sm + lds.red;               // [2][4][8]
+  double* piv = sm + lds.piv;               // [2][8]
+  double* tauA = sm + lds.tauA;             // [kB]           tau of every column (stored at the end)
+  double* tot4 = sm + lds.tot4;             // [2][4][16]
+  int* s_dead = reinterpret_cast<int*>(sm + lds.dead);
   const int n = TL.n;
   const int r0 = j0 + kB, m = n - r0;
   const int g = blockIdx.x, mat = blockIdx.y;
@@ -1110,10 +1115,11 @@ __global__ __launch_bounds__(1024) void k_sb_small(const double* __restrict__ tr
   // instead of 256 threads and larft's 64 dependent columns: 150-240 us -> see DESIGN section 7.
   constexpr int LD = kB + 1;
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  double* G = sm;                 // [kB][LD]  G[i * LD + j]
-  double* M1 = G + kB * LD;
-  double* T = M1 + kB * LD;
-  double* U = T + kB * LD;
+  constexpr sc_host::LdsSbSmall lds = sc_host::lds_sb_small();
+  double* G = sm + lds.G;         // [kB][LD]  G[i * LD + j]
+  double* M1 = sm + lds.M1;
+  double* T = sm + lds.T;
+  double* U = sm + lds.U;
   const double* tri = tri_all + (size_t)blockIdx.x * TL.slab;
   double* sb = sb_all + (size_t)blockIdx.x * SL.slab;
   const int tid = threadIdx.x, nthr = blockDim.x;
@@ -1195,101 +1201,8 @@ __global__ __launch_bounds__(1024) void k_sb_small(const double* __restrict__ tr
 }  // namespace
 
 // ================================================================================================================
-// Host side of stage 1.  Which kernel form a panel gets: twostage_policy.h.
-
-// The GEMM records of stage 1: per panel kDescKinds kinds x batch (the panels' roles: sc_host::panel_roles), grouped
-// [panel][kind][batch] as the launches read them.
-std::vector<GemmDesc> sb_stage1_records(int n, int batch, const std::vector<int>& role, double* d_a, long long stride_a,
-                                        double* d_sb_ws, const SbLayout& SL) {
-  const sc_host::TwoStageEnv& E = sc_host::two_stage_env();
-  const int npanels = (int)role.size();
-  std::vector<GemmDesc> h((size_t)npanels * kDescKinds * batch);
-  for (int p = 0; p < npanels; ++p) {
-    const int j0 = p * kB, r0 = j0 + kB, m = n - r0;
-    const int rl = role[(size_t)p];
-    const long long vw_w = rl == 2 ? 3 * kB : kB, wv_w = rl == 2 ? 2 * kB : 0;   // columns W goes to
-    for (int b = 0; b < batch; ++b) {
-      double* A = d_a + (size_t)b * stride_a;
-      double* sb = d_sb_ws + (size_t)b * SL.slab;
-      double* a22 = A + (size_t)r0 * n + r0;
-      GemmDesc* g = &h[((size_t)p * batch + b) * kDescKinds];
-      // X1 = L V
-      GemmDesc X1{};
-      X1.a = a22; X1.sa_i = 1; X1.sa_k = n; X1.a_tri = 1;
-      X1.b = sb + SL.xv + (size_t)2 * kB * n + r0; X1.sb_k = 1; X1.sb_j = n;
-      X1.c = sb + SL.xv + r0; X1.ldc = n;
-      X1.m = m; X1.n = kB; X1.k = m; X1.alpha = 1.0; X1.beta = 0.0;
-      if (SL.symm_split > 1) {   // K slices into their own buffers, summed into X1 / X2 by k_sum_xslices
-        X1.c = sb + SL.xsplit + r0;
-        X1.split_stride = (long long)n * kB;
-      }
-      g[0] = X1;
-      // X2 = strict(L)^T V
-      GemmDesc X2 = X1;
-      X2.sa_i = n; X2.sa_k = 1; X2.a_tri = 2;
-      X2.c = sb + SL.xv + (size_t)kB * n + r0;
-      if (SL.symm_split > 1) X2.c = sb + SL.xsplit + (size_t)SL.symm_split * n * kB + r0;
-      g[1] = X2;
-      // V^T [X1 | X2 | V], split-K slices
-      GemmDesc P{};
-      P.a = sb + SL.xv + (size_t)2 * kB * n + r0; P.sa_i = n; P.sa_k = 1;
-      P.b = sb + SL.xv + r0; P.sb_k = 1; P.sb_j = n;
-      P.c = sb + SL.small; P.ldc = kB;
-      P.m = kB; P.n = 3 * kB; P.k = m; P.alpha = 1.0; P.beta = 0.0;
-      P.split_stride = (long long)kB * 3 * kB;
-      g[2] = P;
-      // W = [X1 | X2 | V] C  -> its column block of [V|W..] and of [W|V..]
-      GemmDesc W{};
-      W.a = sb + SL.xv + r0; W.sa_i = 1; W.sa_k = n;
-      W.b = sb + SL.cmat; W.sb_k = 1; W.sb_j = 3 * kB;
-      W.c = sb + SL.vw + (size_t)vw_w * n + r0; W.ldc = n;
-      W.m = m; W.n = kB; W.k = 3 * kB; W.alpha = 1.0; W.beta = 0.0;
-      g[3] = W;
-      // (the [W|V] panel holds -[W|V], so that every product that subtracts -- the trailing updates, the correction of X
-      // in a pair -- has alpha = 1: the role-split kernel k_gemm3 keeps C itself in its accumulators and folds no sign;
-      // negation is exact, the results are bit for bit those of alpha = -1 on [W|V])
-      W.c = sb + SL.wv + (size_t)wv_w * n + r0;
-      W.alpha = -1.0;
-      g[4] = W;
-      // trailing update, lower triangle: A22 -= [V|W] [W|V]^T (single panel) or the four-block form (second of a pair)
-      GemmDesc R{};
-      R.a = sb + SL.vw + r0; R.sa_i = 1; R.sa_k = n;
-      R.b = sb + SL.wv + r0; R.sb_k = n; R.sb_j = 1;
-      R.c = a22; R.ldc = n;
-      R.m = m; R.n = m; R.k = rl == 2 ? 4 * kB : 2 * kB; R.alpha = 1.0; R.beta = 1.0;   // b = -[W|V]
-      // (with k_symm3 in use the trailing updates also keep the first super-diagonal entry of every even row: symm3.hip)
-      R.lower_only = sc_host::symm3_for(E, n) ? 2 : 1;
-      g[5] = R;
-      // first of a pair: only the next panel's 64 columns (and the band block above them) get this panel's update now
-      GemmDesc D = R;
-      D.n = kB; D.k = 2 * kB;
-      g[6] = D;
-      // second of a pair (rows r0 .. of the first panel's blocks): P2 = [W1|V1]^T V2, X1 -= [V1|W1] P2
-      GemmDesc Q{};
-      Q.a = sb + SL.wv + r0; Q.sa_i = n; Q.sa_k = 1;
-      Q.b = sb + SL.xv + (size_t)2 * kB * n + r0; Q.sb_k = 1; Q.sb_j = n;
-      Q.c = sb + SL.small2; Q.ldc = 2 * kB;
-      Q.m = 2 * kB; Q.n = kB; Q.k = m; Q.alpha = 1.0; Q.beta = 0.0;
-      Q.split_stride = (long long)2 * kB * kB;
-      g[7] = Q;
-      GemmDesc Cr{};
-      Cr.a = sb + SL.vw + r0; Cr.sa_i = 1; Cr.sa_k = n;
-      Cr.b = sb + SL.p2; Cr.sb_k = 1; Cr.sb_j = 2 * kB;
-      Cr.c = sb + SL.xv + r0; Cr.ldc = n;
-      Cr.m = m; Cr.n = kB; Cr.k = 2 * kB; Cr.alpha = 1.0; Cr.beta = 1.0;   // P2 comes out negated (a = -[W1|V1])
-      g[8] = Cr;
-    }
-  }
-  // regroup so that each launch's records are contiguous: [panel][kind][batch]
-  std::vector<GemmDesc> hs(h.size());
-  for (int p = 0; p < npanels; ++p)
-    for (int b = 0; b < batch; ++b) {
-      const GemmDesc* g = &h[((size_t)p * batch + b) * kDescKinds];
-      GemmDesc* o = &hs[(size_t)p * kDescKinds * batch];
-      for (int kd = 0; kd < kDescKinds; ++kd) o[(size_t)kd * batch + b] = g[kd];
-    }
-  return hs;
-}
+// Host side of stage 1.  Which kernel form a panel gets: twostage_policy.h; the records, their places and every LDS size:
+// sy2sb_plan.h.
 
 // What a panel needs of its solve.
 struct PanelRun {
@@ -1308,34 +1221,27 @@ struct PanelRun {
   SbTimers& t;
 };
 
-// One panel of the matrices [lo, hi) on `ps`: QR of the panel, X = A22 V, the small products, W, the trailing update
-// its role asks for (single: SYR2K; first of a pair: the next panel's columns only; second: the joint update).
-static int run_panel(const PanelRun& R, int p, int lo, int hi, hipStream_t ps, bool timed) {
+// The QR of panel p of the matrices [lo, lo + nb) on `ps`, in the form the policy names.
+static int launch_panel_qr(const PanelRun& R, int p, int lo, int nb, hipStream_t ps) {
   using sc_host::PanelQr;
-  const sc_host::TwoStageEnv& E = sc_host::two_stage_env();
   sc_ctx* ctx = R.ctx;
   const TriLayout& TL = R.TL;
-  const SbLayout& SL = R.SL;
-  const int n = R.n, batch = R.batch;
   const long long stride_a = R.stride_a;
-  struct StreamScope {   // launch_gemm_f64 launches on the context's stream
-    sc_ctx* c; hipStream_t old;
-    StreamScope(sc_ctx* c_, hipStream_t s) : c(c_), old(c_->stream) { c->stream = s; }
-    ~StreamScope() { c->stream = old; }
-  } scope(ctx, ps);
-  const int nb = hi - lo;
-  const int rl = R.role[(size_t)p];
+  const sc_host::PanelGeom g = sc_host::panel_geom(R.n, p);
+  const int j0 = g.j0, nr = g.nr;
   double* a_h = R.d_a + (size_t)lo * stride_a;
   double* tri_h = R.d_tri_ws + (size_t)lo * TL.slab;
-  double* sb_h = R.d_sb_ws + (size_t)lo * SL.slab;
-  const int j0 = p * kB, r0 = j0 + kB, m = n - r0;
-  const int nr = std::min(kB, m - 1);
-  const int nchunks = (m + kQrRows - 1) / kQrRows;
-  const dim3 qgrid((unsigned)nchunks, (unsigned)nb);
-  SbLayout SQ = SL;     // where the panel QR leaves V: the second panel of a pair uses the second half of [V|W..], [W|V..]
-  if (rl == 2) { SQ.vw += (long long)2 * kB * n; SQ.wv += (long long)2 * kB * n; }
-  if (timed) R.t.qr.start();
-  const sc_host::PanelQrForm F = sc_host::panel_qr_form(E, R.coop, R.coop_recs != nullptr, m, nb, ps == R.st);
+  double* sb_h = R.d_sb_ws + (size_t)lo * R.SL.slab;
+  const dim3 qgrid((unsigned)g.nchunks, (unsigned)nb);
+  SbLayout SQ = R.SL;   // where the panel QR leaves V: the second panel of a pair uses the second half of [V|W..], [W|V..]
+  if (R.role[(size_t)p] == 2) { SQ.vw += (long long)2 * kB * R.n; SQ.wv += (long long)2 * kB * R.n; }
+  const sc_host::PanelQrForm F =
+      sc_host::panel_qr_form(sc_host::two_stage_env(), R.coop, R.coop_recs != nullptr, g.m, nb, ps == R.st);
+  // k_panel_wg<ru, cu, nt>: one workgroup per matrix
+  auto wg = [&](void (*kernel)(double*, long long, double*, TriLayout, double*, SbLayout, int), int nt) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)nb), dim3((unsigned)nt), lds_bytes(sc_host::lds_panel_wg(nt).total), ps, a_h,
+                       stride_a, tri_h, TL, sb_h, SQ, j0);
+  };
   switch (F.kind) {
     case PanelQr::Coop: {
       const int coop_g = F.coop_g;
@@ -1350,30 +1256,21 @@ static int run_panel(const PanelRun& R, int p, int lo, int hi, hipStream_t ps, b
       ++ctx->cnt_coop_launches;
       break;
     }
-    case PanelQr::Wg1024: {
-      const size_t lds_wg = sizeof(double) * (size_t)(2 * kWgWaves * 8 + 16 + 8 + 8 * kB + kWgWaves * kB * 8);
-      const dim3 g1((unsigned)nb), b1((unsigned)kWgThreads);
+    case PanelQr::Wg1024:
       ++ctx->cnt_panel_form[std::max(1, std::min(F.ru, 4)) - 1];
-      if (F.ru == 1) hipLaunchKernelGGL((k_panel_wg<1, 8>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
-      else if (F.ru == 2) hipLaunchKernelGGL((k_panel_wg<2, 8>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
-      else if (F.ru == 3) hipLaunchKernelGGL((k_panel_wg<3, 4>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
-      else hipLaunchKernelGGL((k_panel_wg<4, 2>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
+      if (F.ru == 1) wg(k_panel_wg<1, 8>, 1024);
+      else if (F.ru == 2) wg(k_panel_wg<2, 8>, 1024);
+      else if (F.ru == 3) wg(k_panel_wg<3, 4>, 1024);
+      else wg(k_panel_wg<4, 2>, 1024);
       break;
-    }
-    case PanelQr::Wg512: {
-      constexpr int kW = 512 / 64;
-      const size_t lds_wg = sizeof(double) * (size_t)(2 * kW * 8 + 16 + 8 + 8 * kB + kW * kB * 8);
-      const dim3 g1((unsigned)nb), b1(512u);
+    case PanelQr::Wg512:
       ++ctx->cnt_panel_form[F.ru == 10 ? 4 : 5];
-      if (F.ru == 10) hipLaunchKernelGGL((k_panel_wg<10, 1, 512>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
-      else hipLaunchKernelGGL((k_panel_wg<12, 1, 512>), g1, b1, lds_wg, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0);
+      if (F.ru == 10) wg(k_panel_wg<10, 1, 512>, 512);
+      else wg(k_panel_wg<12, 1, 512>, 512);
       break;
-    }
     case PanelQr::Blocked: {
       // blocked panel: inner blocks of 8 columns, their reflectors applied to the rest of the panel at once
-      const size_t lds_qr_blk = sizeof(double) * ((size_t)(kIb + 1) * (kQrRows + 1) + kB + kQrRows + 4 * kB);
-      const size_t lds_blk_a = sizeof(double) * ((size_t)kB * (kQrRows + 1) + kQrRows + 8 * kB);
-      const size_t lds_blk_b = sizeof(double) * ((size_t)kB * (kQrRows + 1) + kIb * kB + 4 * kB);
+      const size_t lds_qr_blk = lds_bytes(sc_host::lds_panel_qr(kIb + 1).total);
       ++ctx->cnt_panel_form[6];
       hipLaunchKernelGGL(k_panel_qr, qgrid, dim3(256), lds_qr_blk, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, 0, nr, kIb);
       for (int c0 = 0; c0 < kB; c0 += kIb) {
@@ -1381,64 +1278,84 @@ static int run_panel(const PanelRun& R, int p, int lo, int hi, hipStream_t ps, b
           hipLaunchKernelGGL(k_panel_qr, qgrid, dim3(256), lds_qr_blk, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, j, nr,
                              c0 + kIb);
         // (their LDS image holds columns c0 .. kB-1 only)
-        const size_t cut = sizeof(double) * (size_t)c0 * (kQrRows + 1);
-        hipLaunchKernelGGL(k_pqr_blk_a, qgrid, dim3(256), lds_blk_a - cut, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, c0);
+        hipLaunchKernelGGL(k_pqr_blk_a, qgrid, dim3(256), lds_bytes(sc_host::lds_pqr_blk_a(c0).total), ps, a_h, stride_a, tri_h,
+                           TL, sb_h, SQ, j0, c0);
         if (c0 + kIb < kB)
-          hipLaunchKernelGGL(k_pqr_blk_b, qgrid, dim3(256), lds_blk_b - cut, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, c0);
+          hipLaunchKernelGGL(k_pqr_blk_b, qgrid, dim3(256), lds_bytes(sc_host::lds_pqr_blk_b(c0).total), ps, a_h, stride_a,
+                             tri_h, TL, sb_h, SQ, j0, c0);
       }
       break;
     }
     case PanelQr::Unblocked: {
-      const size_t lds_qr = sizeof(double) * ((size_t)kB * (kQrRows + 1) + kB + kQrRows + 4 * kB);
+      const size_t lds_qr = lds_bytes(sc_host::lds_panel_qr(kB).total);
       ++ctx->cnt_panel_form[7];
       for (int j = 0; j <= nr; ++j)
         hipLaunchKernelGGL(k_panel_qr, qgrid, dim3(256), lds_qr, ps, a_h, stride_a, tri_h, TL, sb_h, SQ, j0, j, nr, kB);
       break;
     }
   }
+  return SC_OK;
+}
+
+// One panel of the matrices [lo, hi) on `ps`: QR of the panel, X = A22 V, the small products, W, the trailing update
+// its role asks for (single: SYR2K; first of a pair: the next panel's columns only; second: the joint update).
+static int run_panel(const PanelRun& R, int p, int lo, int hi, hipStream_t ps, bool timed) {
+  using sc_host::SbRec, sc_host::kRecX1, sc_host::kRecX2, sc_host::kRecGram, sc_host::kRecW, sc_host::kRecNegW, sc_host::kRecTrail,
+      sc_host::kRecFirst, sc_host::kRecP2, sc_host::kRecCorr;
+  sc_ctx* ctx = R.ctx;
+  const SbLayout& SL = R.SL;
+  const int n = R.n, batch = R.batch, nb = hi - lo;
+  const int rl = R.role[(size_t)p];
+  const sc_host::PanelGeom g = sc_host::panel_geom(n, p);
+  const int j0 = g.j0, r0 = g.r0, m = g.m;
+  double* tri_h = R.d_tri_ws + (size_t)lo * R.TL.slab;
+  double* sb_h = R.d_sb_ws + (size_t)lo * SL.slab;
+  StreamScope scope(ctx, ps);   // launch_gemm_f64 launches on the context's stream
+  if (timed) R.t.qr.start();
+  SC_TRY(launch_panel_qr(R, p, lo, nb, ps));
   if (timed) R.t.qr.stop();
   if (rl != 0) ++ctx->cnt_panel_role[rl - 1];
-  const GemmDesc* g = R.d_descs + (size_t)p * kDescKinds * batch;   // [kind][batch]
+  // the records of this launch: one kind of panel p, matrices lo .. hi - 1
+  auto rec = [&](SbRec kind) { return R.d_descs + sc_host::stage1_record_index(p, kind, batch, lo); };
   if (timed) R.t.symm.start();
   // X = A22 V: one launch of k_symm3 (X into X1; X2 was zeroed for the whole solve) while the panel has enough tiles
   // for it, else X1 = L V and X2 = strict(L)^T V by two triangular-operand launches of k_gemm2
   if (R.use_symm3 && symm3_would_take(ctx, R.symm3_nb_min, m, SL.symm_split, /*aligned16=*/true) &&
-      launch_symm3(ctx, g + lo, nb, m, SL.symm_split, /*aligned16=*/true, /*any_size=*/true) == SC_OK) {
+      launch_symm3(ctx, rec(kRecX1), nb, m, SL.symm_split, /*aligned16=*/true, /*any_size=*/true) == SC_OK) {
     if (SL.symm_split > 1)
       hipLaunchKernelGGL(k_sum_xslices, dim3((unsigned)((m + 255) / 256), kB, (unsigned)nb), dim3(256), 0, ps, sb_h, SL, r0);
   } else {
     ++ctx->cnt_symm_tri;
-    // X1 = L V, X2 = strict(L)^T V
-    SC_TRY(launch_gemm_f64(ctx, g + lo, {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBk, .split_k = SL.symm_split, .tri = true}));
-    SC_TRY(launch_gemm_f64(ctx, g + batch + lo, {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAkBk, .split_k = SL.symm_split, .tri = true}));
+    SC_TRY(launch_gemm_f64(ctx, rec(kRecX1), {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBk, .split_k = SL.symm_split, .tri = true}));
+    SC_TRY(launch_gemm_f64(ctx, rec(kRecX2), {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAkBk, .split_k = SL.symm_split, .tri = true}));
     if (SL.symm_split > 1)
       hipLaunchKernelGGL(k_sum_xslices, dim3((unsigned)((m + 255) / 256), 2 * kB, (unsigned)nb), dim3(256), 0, ps, sb_h, SL, r0);
   }
   if (rl == 2) {   // the trailing matrix has not seen the first panel's update yet: X1 -= [V1|W1] ([W1|V1]^T V2)
-    SC_TRY(launch_gemm_f64(ctx, g + 7 * batch + lo, {.count = nb, .max_m = 2 * kB, .max_n = kB, .layout = kGemmAkBk, .split_k = kSmallSplit}));
+    SC_TRY(launch_gemm_f64(ctx, rec(kRecP2), {.count = nb, .max_m = 2 * kB, .max_n = kB, .layout = kGemmAkBk, .split_k = kSmallSplit}));
     hipLaunchKernelGGL(k_sum_p2, dim3((unsigned)(2 * kB * kB / 256), (unsigned)nb), dim3(256), 0, ps, sb_h, SL);
-    SC_TRY(launch_gemm_f64(ctx, g + 8 * batch + lo, {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBk}));
+    SC_TRY(launch_gemm_f64(ctx, rec(kRecCorr), {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBk}));
   }
   if (timed) R.t.symm.stop();
-  SC_TRY(launch_gemm_f64(ctx, g + 2 * batch + lo, {.count = nb, .max_m = kB, .max_n = 3 * kB, .layout = kGemmAkBk, .split_k = kSmallSplit}));
-  const size_t lds_small = sizeof(double) * 4 * kB * (kB + 1);
-  hipLaunchKernelGGL(k_sb_small, dim3((unsigned)nb), dim3(1024), lds_small, ps, tri_h, TL, sb_h, SL, j0);
+  SC_TRY(launch_gemm_f64(ctx, rec(kRecGram), {.count = nb, .max_m = kB, .max_n = 3 * kB, .layout = kGemmAkBk, .split_k = kSmallSplit}));
+  hipLaunchKernelGGL(k_sb_small, dim3((unsigned)nb), dim3(1024), lds_bytes(sc_host::lds_sb_small().total), ps, tri_h, R.TL, sb_h, SL, j0);
+  static_assert(kRecNegW == kRecW + 1, "W and -W of a whole batch are one launch of 2 * batch records");
   if (nb == batch) {
-    SC_TRY(launch_gemm_f64(ctx, g + 3 * batch, {.count = 2 * batch, .max_m = m, .max_n = kB, .layout = kGemmAmBk}));
+    SC_TRY(launch_gemm_f64(ctx, rec(kRecW), {.count = 2 * batch, .max_m = m, .max_n = kB, .layout = kGemmAmBk}));
   } else {
-    SC_TRY(launch_gemm_f64(ctx, g + 3 * batch + lo, {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBk}));
-    SC_TRY(launch_gemm_f64(ctx, g + 4 * batch + lo, {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBk}));
+    SC_TRY(launch_gemm_f64(ctx, rec(kRecW), {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBk}));
+    SC_TRY(launch_gemm_f64(ctx, rec(kRecNegW), {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBk}));
   }
   if (timed) R.t.syr2k.start();
   if (rl == 1)
-    SC_TRY(launch_gemm_f64(ctx, g + 6 * batch + lo, {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBn}));
+    SC_TRY(launch_gemm_f64(ctx, rec(kRecFirst), {.count = nb, .max_m = m, .max_n = kB, .layout = kGemmAmBn}));
   else
     // (records of one launch share (m, m, K); operands start at even rows of buffers with even leading dimension n)
-    if (launch_gemm3_uniform(ctx, g + 5 * batch + lo,
+    if (launch_gemm3_uniform(ctx, rec(kRecTrail),
                              {.count = nb, .m = m, .n = m, .k = rl == 2 ? 4 * kB : 2 * kB, .layout = kGemmAmBn, .lower = R.use_symm3 ? 2 : 1,
                               .alpha = 1.0, .beta = 1.0, .aligned16 = (n & 1) == 0 && (r0 & 1) == 0}) != SC_OK) {
       ++ctx->cnt_gemm3_declined;
-      SC_TRY(launch_gemm_f64(ctx, g + 5 * batch + lo, {.count = nb, .max_m = m, .max_n = m, .layout = kGemmAmBn, .lower_grid = true}));
+      SC_TRY(launch_gemm_f64(ctx, rec(kRecTrail), {.count = nb, .max_m = m, .max_n = m, .layout = kGemmAmBn, .lower_grid = true}));
     }
   if (timed) R.t.syr2k.stop();
   return SC_OK;
@@ -1467,13 +1384,11 @@ int sb_stage1(sc_ctx* ctx, double* d_a, long long stride_a, int n, int batch, do
       ctx->coop_attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_panel_coop),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kCoopLdsBytes) == hipSuccess;
     if (ctx->coop_attr == 1 && coop.nb_max >= 1) {
-      const size_t rec_bytes = (size_t)batch * coop_recs_per_matrix(coop.gmax) * sizeof(v4i);
-      const size_t ctl_bytes = align_up((size_t)batch * 8 * sizeof(int), 256);   // one control record per matrix
-      SC_TRY(sc_reserve_dc_aux(ctx, ctl_bytes + rec_bytes));
-      coop_ctl = reinterpret_cast<int*>(ctx->dc_aux);
-      coop_recs = reinterpret_cast<v4i*>(reinterpret_cast<char*>(ctx->dc_aux) + ctl_bytes);
-      // (sequence numbers are unique within a solve only)
-      SC_HIP(ctx, hipMemsetAsync(ctx->dc_aux, 0, ctl_bytes + rec_bytes, st));
+      const sc_host::CoopAux aux = sc_host::coop_aux_carve(batch, coop.gmax);
+      SC_TRY(sc_reserve_dc_aux(ctx, aux.total));
+      coop_ctl = reinterpret_cast<int*>(reinterpret_cast<char*>(ctx->dc_aux) + aux.ctl);
+      coop_recs = reinterpret_cast<v4i*>(reinterpret_cast<char*>(ctx->dc_aux) + aux.recs);
+      SC_HIP(ctx, hipMemsetAsync(ctx->dc_aux, 0, aux.total, st));
     }
   }
   // k_symm3 writes X into the X1 block of [X1 | X2 | V]; the X2 block reads zero for the whole solve (the panels at the
@@ -1492,22 +1407,15 @@ int sb_stage1(sc_ctx* ctx, double* d_a, long long stride_a, int n, int batch, do
       explicit SideBySide(sc_ctx* c_) : c(c_) { c->gemm3_side_by_side = true; }
       ~SideBySide() { c->gemm3_side_by_side = false; }
     } side_by_side(ctx);
-    SC_TRY(sc_aux_stream(ctx));
-    SC_TRY(sc_side_streams(ctx, s1_parts - 1));
-    SC_HIP(ctx, hipEventRecord(ctx->aux_fork, st));
-    for (int q = 1; q < s1_parts; ++q) SC_HIP(ctx, hipStreamWaitEvent(ctx->side_streams[q - 1], ctx->aux_fork, 0));
+    SideFork parts(ctx, st);
+    SC_TRY(parts.fork(s1_parts));
     int rc_parts = SC_OK;
     for (int p = 0; p < npanels && rc_parts == SC_OK; ++p)
       for (int q = 0; q < s1_parts && rc_parts == SC_OK; ++q) {
-        const int lo = (int)((long long)batch * q / s1_parts), hi = (int)((long long)batch * (q + 1) / s1_parts);
-        rc_parts = run_panel(R, p, lo, hi, q == 0 ? st : ctx->side_streams[q - 1], q == 0);
+        const sc_host::PartBounds pb = sc_host::part_bounds(batch, s1_parts, q);
+        rc_parts = run_panel(R, p, pb.lo, pb.hi, parts.stream(q), q == 0);
       }
-    // (also after an error: the side streams are joined before anything returns, so that what they still have queued
-    // is ordered before whatever the caller enqueues next on the main stream)
-    for (int q = 1; q < s1_parts; ++q) {
-      SC_HIP(ctx, hipEventRecord(ctx->side_joins[q - 1], ctx->side_streams[q - 1]));
-      SC_HIP(ctx, hipStreamWaitEvent(st, ctx->side_joins[q - 1], 0));
-    }
+    SC_TRY(parts.join());   // (also after an error: before anything returns)
     SC_TRY(rc_parts);
   } else {
     for (int p = 0; p < npanels; ++p) SC_TRY(run_panel(R, p, 0, batch, st, true));

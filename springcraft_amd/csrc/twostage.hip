@@ -17,55 +17,13 @@
 //
 // Role in the reference: part of np.linalg.eigh (LAPACK dsyevd) at nma.py:61; LAPACK itself uses the one-stage dsytrd.
 //
-// Files: this one holds the slab layout and the driver of stages 1 and 2; sy2sb.hip stage 1, sb2st.hip stage 2, bt2.hip the
-// Q2 back-transformation (bt2); twostage_internal.h what they share; twostage_policy.h every choice between kernel forms.
+// Files: this one holds the driver of stages 1 and 2; sy2sb.hip stage 1, sb2st.hip stage 2, bt2.hip the Q2
+// back-transformation (bt2); twostage_internal.h what they share; twostage_policy.h every choice between kernel forms;
+// sy2sb_plan.h the slab layout and what stage 1 launches with (records, LDS, carves).
 #include <algorithm>
 #include <vector>
 
 #include "twostage_internal.h"
-
-// ================================================================================================================
-// Layout
-size_t sb_slab_doubles(int n, int batch, SbLayout* out) {
-  SbLayout L{};
-  L.n = n;
-  long long off = 0;
-  auto take = [&](long long cnt) { long long o = off; off += (cnt + 31) / 32 * 32; return o; };
-  const int nchunk = (n + kQrRows - 1) / kQrRows + 1;
-  L.vw = take((long long)n * 4 * kB);
-  L.wv = take((long long)n * 4 * kB);
-  L.xv = take((long long)n * 3 * kB);
-  L.symm_split = sc_host::symm_split_for(sc_host::two_stage_env(), n, batch);
-  L.xsplit = L.symm_split > 1 ? take((long long)2 * L.symm_split * n * kB) : 0;
-  L.qrpart = take((long long)2 * nchunk * kB);
-  L.qrpiv = take(2 * (kB + 8));
-  L.qrpart8 = take((long long)nchunk * kIb * kB);
-  L.small = take((long long)kSmallSplit * kB * 3 * kB);
-  L.cmat = take(3 * kB * kB);
-  L.small2 = take((long long)kSmallSplit * 2 * kB * kB);
-  L.p2 = take(2 * kB * kB);
-  L.ab = take((long long)kLdab * n);
-  // diamonds
-  const int nsweep = std::max(n - 2, 0);
-  L.ngroups = (nsweep + kG - 1) / kG;
-  long long ndia = 0;
-  for (int S = 0; S < L.ngroups; ++S) {
-    const int len = (n - 1 - S * kG + kB - 1) / kB;
-    ndia += len;
-  }
-  L.ndia = ndia;
-  L.vd = take(ndia * kDiaSize);
-  L.frag = take(ndia * kFragDoubles);
-  L.tau2 = take(ndia * kG);
-  L.slab = off;
-  if (out) *out = L;
-  return (size_t)off;
-}
-
-int sb_desc_count(int n, int batch) {
-  const int npanels = n / kB + 1;
-  return npanels * kDescKinds * batch;
-}
 
 // ================================================================================================================
 // Stage 1 + 2 driver.  d_a: lower triangle valid (after mirror_lower_batched).  On exit: tri slab holds d, e and the
@@ -81,9 +39,10 @@ int sytrd_2stage_batched(sc_ctx* ctx, double* d_a, long long stride_a, int n, in
     SC_HIP(ctx, hipEventRecord(ev[0], st));
   }
 
-  // ---- descriptors of stage 1 (sy2sb.hip); the panels' roles: 0 single, 1 first of a pair, 2 second of a pair
-  const std::vector<int> role = sc_host::panel_roles(sc_host::two_stage_env(), n);
-  const std::vector<GemmDesc> hs = sb_stage1_records(n, batch, role, d_a, stride_a, d_sb_ws, SL);
+  // ---- descriptors of stage 1 (sy2sb_plan.h); the panels' roles: 0 single, 1 first of a pair, 2 second of a pair
+  const sc_host::TwoStageEnv& E = sc_host::two_stage_env();
+  const std::vector<int> role = sc_host::panel_roles(E, n);
+  const std::vector<GemmDesc> hs = sc_host::stage1_records(n, batch, role, sc_host::symm3_for(E, n), d_a, stride_a, d_sb_ws, SL);
   if (!hs.empty()) SC_TRY(sc_stage_upload(ctx, d_descs, hs.data(), hs.size() * sizeof(GemmDesc)));
   const std::vector<int> doff = dia_offsets(n);
   SC_TRY(sc_stage_upload(ctx, d_dia_off, doff.data(), doff.size() * sizeof(int)));

@@ -12,7 +12,7 @@
 namespace {
 
 constexpr int kB = sc_host::kBand;  // band half-width = panel width = reflector length of stage 2
-constexpr int kG = 64;            // sweeps per diamond
+constexpr int kG = sc_host::kSweepGroup;   // sweeps per diamond
 constexpr int kDiaLd = 128;       // leading dimension of a diamond (kB + kG - 1 = 127 rows used)
 constexpr int kDiaSize = kDiaLd * kG;
 
@@ -20,15 +20,12 @@ constexpr int kDiaSize = kDiaLd * kG;
 constexpr int kMiniFrags = 40;                     // fragments per mini: 20 of V^T, 20 of -(V T)
 constexpr int kDiaFrags = 4 * kMiniFrags;          // 160 per diamond
 constexpr int kFragDoubles = kDiaFrags * 64;       // 10240 doubles = 80 KB
+static_assert(kDiaSize == sc_host::kDiaDoubles && kFragDoubles == sc_host::kDiaFragDoubles, "the slab is sized in sy2sb_plan.h");
 
-constexpr int kLdab = 2 * kB;     // rows of the band storage: AB(i, j) = ab[(i - j) + j * kLdab]
-constexpr int kQrRows = 128;      // rows of the panel one k_panel_qr workgroup owns
-constexpr int kSmallSplit = 8;    // split-K of the V^T [X1|X2|V] product
-constexpr int kDescKinds = 9;     // GEMM records per panel and matrix (stage 1)
-#ifndef SC_QR_IB
-#define SC_QR_IB 8
-#endif
-constexpr int kIb = SC_QR_IB;     // inner block of the blocked panel QR (columns whose reflectors are applied to the rest at once)
+constexpr int kLdab = sc_host::kBandRows;       // rows of the band storage: AB(i, j) = ab[(i - j) + j * kLdab]
+constexpr int kQrRows = sc_host::kQrRows;       // rows of the panel one k_panel_qr workgroup owns
+constexpr int kSmallSplit = sc_host::kSmallSplit;   // split-K of the V^T [X1|X2|V] product
+constexpr int kIb = sc_host::kQrIb;             // inner block of the blocked panel QR (columns whose reflectors are applied to the rest at once)
 
 typedef int v4i __attribute__((ext_vector_type(4)));   // a 16-byte record (early hand-off of the chase, the cooperative panel)
 
@@ -93,10 +90,7 @@ struct SbTimers {
   void finish() { qr.finish(); symm.finish(); syr2k.finish(); bulge.finish(); }
 };
 
-// The GEMM records of stage 1 in [panel][kind][batch] order (sy2sb.hip); the driver uploads them.
-std::vector<GemmDesc> sb_stage1_records(int n, int batch, const std::vector<int>& role, double* d_a, long long stride_a,
-                                        double* d_sb_ws, const SbLayout& SL);
-// Stage 1 on ctx->stream, the GEMM records of the solve uploaded: dense -> band (sy2sb.hip).
+// Stage 1 on ctx->stream, the GEMM records of the solve (sc_host::stage1_records) uploaded: dense -> band (sy2sb.hip).
 int sb_stage1(sc_ctx* ctx, double* d_a, long long stride_a, int n, int batch, double* d_tri_ws, const TriLayout& TL,
               double* d_sb_ws, const SbLayout& SL, const GemmDesc* d_descs, const std::vector<int>& role, bool prof,
               SbTimers& timers);

@@ -24,6 +24,7 @@ constexpr int kWgRows512 = 12 * 512;   // ... with 512 threads (12 rows per thre
 constexpr int kCoopRows = 256;         // rows of a panel per workgroup of k_panel_coop
 constexpr int kCoopMaxG = 128;         // most workgroups per matrix of k_panel_coop
 constexpr int kEarlyRing = 8;          // early hand-off records per sweep of k_bulge_chase (16 bytes each)
+constexpr size_t kLdsPerWorkgroup = 160 * 1024;   // LDS of a CU: the most one workgroup can be launched with
 
 static inline size_t policy_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
@@ -105,8 +106,9 @@ static inline int panel_count(int n) {
 }
 // Role of every panel: 0 single, 1 first of a pair, 2 second of a pair.
 // Panels are taken in PAIRS where the trailing matrix is large enough: the second panel of a pair is factored from
-// columns that received the first panel's update alone (record D), its X = A22 V2 is computed from the NOT yet updated
-// trailing matrix and corrected by - [V1|W1] ([W1|V1]^T V2) (records Q, Corr), and one trailing update
+// columns that received the first panel's update alone (record kRecFirst of sy2sb_plan.h), its X = A22 V2 is computed from
+// the NOT yet updated trailing matrix and corrected by - [V1|W1] ([W1|V1]^T V2) (records kRecP2, kRecCorr), and one
+// trailing update (kRecTrail)
 // A22 -= [V1|W1|V2|W2] [W1|V1|W2|V2]^T (K = 256) serves both panels: the lower triangle is read and written once per
 // 128 columns of band instead of once per 64 (at K = 128 the C traffic of a tile takes as long as its MFMAs).
 static inline std::vector<int> panel_roles(const TwoStageEnv& E, int n) {

@@ -284,6 +284,29 @@ def test_stedc_plan_under_sanitizers(tmp_path):
     assert r.returncode == 0 and "stedc plan ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
 
 
+def test_sy2sb_plan_under_sanitizers(tmp_path):
+    """
+    The plan of the band reduction (csrc/sy2sb_plan.h: panel geometry, the GEMM records of a solve and their places, the
+    LDS layouts of the stage-1 kernels, k_panel_coop's carve of the auxiliary buffer, the parts of a split batch) compiled
+    with g++ under ASan + UBSan and checked against literals (tests/host_sanitize/test_sy2sb_plan.cpp).
+    """
+    import shutil
+    import subprocess
+
+    if shutil.which("g++") is None:
+        pytest.skip("g++ not available")
+    exe = str(tmp_path / "test_sy2sb_plan")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-I", join(ROOT, "include"), "-I", join(ROOT, "springcraft_amd", "csrc"),
+           join(ROOT, "tests", "host_sanitize", "test_sy2sb_plan.cpp"), "-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    if r.returncode != 0 and ("asan" in r.stderr.lower() or "ubsan" in r.stderr.lower()) and "cannot find" in r.stderr:
+        pytest.skip("sanitizer runtimes not installed")
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "sy2sb plan ok" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+
+
 # sc_eigh_workspace_bytes(n, batch, want_vectors = 0 / 1) of the revision before the drivers shared one plan (taken from that
 # revision's library on the host: the function needs neither a context nor a device), default environment
 EIGH_WORKSPACE_BYTES = {

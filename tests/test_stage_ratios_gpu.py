@@ -564,3 +564,68 @@ def test_form_bt2_xcd_deal(lib_ctx, batch, nw):
     print(f"[{label}] {time.perf_counter() - t0:.2f} s")
     report(label, rows)
     assert not any(wrong.values()), (label, "call: counter: (got, expected)", wrong)
+
+
+# ---- the band reduction's plan (csrc/sy2sb_plan.h): panel shapes, pairs and parts at the smallest orders that have them -----
+# pairs of panels per matrix: panel_roles of tests/host_sanitize/test_sy2sb_plan.cpp (384: 1, 2, 0, 0, 0; 512 and 513: 1, 2, 1, 2,
+# 0, 0, 0).  Below n = 256 the two-stage path does not exist (eigh_policy.h: two_stage_for): the staged entry refuses the
+# order, and the panel shapes of 66, 128 and 129 -- two rows; 64 rows with 63 reflectors; 65 rows -- are the last panels of
+# 322 (test_form_two_stage1_parts and others), 384 and 513.
+PLAN_PAIRS = {66: None, 128: None, 129: None, 384: 1, 512: 2, 513: 2}
+
+
+@pytest.mark.parametrize("batch", [1, 3, 33])
+@pytest.mark.parametrize("n", sorted(PLAN_PAIRS))
+def test_stage1_plan_orders(lib_ctx, n, batch):
+    """
+    Stage 1 (which = Q_ONE) with the two-stage path forced, one / three / 33 matrices: the stage-1 gates on every member, as
+    many first and second panels of a pair as the roles say (per part), two parts of 16 and 17 matrices at batch 33 and
+    one otherwise; at batch 33 the copies of one matrix at positions 0, 16 (the first of the second part) and 32 have
+    bit-equal d, e, band and Q1 -- the rule at sc_host::stage1_parts.
+    """
+    skip_if_forms_overridden()
+    L, ctx = lib_ctx
+    copies = (0, 16, 32) if batch == 33 else (0,)
+    ctx.set_two_stage(True)
+    label = f"plan: stage 1 n={n} x {batch}"
+    if PLAN_PAIRS[n] is None:
+        rc, _ = sr.reduce_raw(L, ctx, np.stack([sr.random_sym(n)] * batch), sr.Q_ONE)
+        assert rc == 1, rc          # SC_ERR_INVALID_ARG: below the two-stage minimum
+        return
+    names, mats = cycled_batch(n, batch, copies)
+    t0 = time.perf_counter()
+    out = {sr.Q_ONE: sr.reduce_host(L, ctx, mats, sr.Q_ONE)}
+    d, e, s, band, q1, two = out[sr.Q_ONE]
+    assert two, "the two-stage path was forced"
+    rows = [(name, {"recon(A,Q1,B)": sr.recon(scaled(mats[b], s[b]), q1[b], sr.band_matrix(band[b])), "orth(Q1)": sr.orth(q1[b]),
+                    "beyond_band": sr.band_beyond(band[b])}) for b, name in enumerate(names)]
+    got = {k: ctx.counter(k) for k in PER_CALL + LAST + QUIET}
+    print(f"[{label}] {time.perf_counter() - t0:.2f} s  " + " ".join(f"{k}={v}" for k, v in got.items() if v))
+    report(label, rows)
+    parts = 2 if batch == 33 else 1
+    assert got["stage1_parts"] == parts, got
+    assert got["panel_pair_first"] == PLAN_PAIRS[n] * parts and got["panel_pair_second"] == PLAN_PAIRS[n] * parts, got
+    assert all(got[k] == 0 for k in QUIET), got
+    identical(out, sr.Q_ONE, copies, label)
+
+
+def test_stage1_plan_coop(lib_ctx):
+    """k_panel_coop through the plan's carve of the auxiliary buffer: n = 384, one matrix, panels of at least 200 rows (320 and
+    256: the two panels of the pair), two workgroups each."""
+    skip_if_forms_overridden()
+    if coop_overridden():
+        pytest.skip("the cooperative kernel's rule is overridden (tools/test_matrix.sh)")
+    L, ctx = lib_ctx
+    n = 384
+    mats = sr.random_sym(n)[None]
+    ctx.set_two_stage(True)
+    ctx.check(L.sc_dbg_set_panel_coop(ctx.handle, 200))
+    label = f"plan: k_panel_coop n={n} x 1"
+    d, e, s, band, q1, two = sr.reduce_host(L, ctx, mats, sr.Q_ONE)
+    assert two, "the two-stage path was forced"
+    got = {k: ctx.counter(k) for k in PER_CALL + LAST + QUIET}
+    print(f"[{label}] " + " ".join(f"{k}={v}" for k, v in got.items() if v))
+    report(label, [("random", {"recon(A,Q1,B)": sr.recon(scaled(mats[0], s[0]), q1[0], sr.band_matrix(band[0])),
+                               "orth(Q1)": sr.orth(q1[0]), "beyond_band": sr.band_beyond(band[0])})])
+    assert got["panel_coop_launches"] == 2 and got["panel_pair_first"] == 1 and got["panel_pair_second"] == 1, got
+    assert got["stage1_parts"] == 1 and all(got[k] == 0 for k in QUIET), got
